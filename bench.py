@@ -94,7 +94,15 @@ def parse(argv=None):
     ap.add_argument("--configs4-steps", type=int, default=4, help="secondary.cpra_multi: timed steps (after one warm-up step)")
     ap.add_argument("--preflight-bytes", type=int, default=256 << 20,
                     help="multi-GPU: bytes per peer of the link-bandwidth preflight before the timed region (0 = skip it)")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps: write what the timed join returned in its last step as DIR/<name>.npy "
+                         "(float64; see dump_outputs), so that two builds can be compared output for output")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1 (ms_per_step is the wall clock of the timed steps divided by their number)")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    return args
 
 
 def relaunch_under_torchrun(args):
@@ -169,6 +177,22 @@ def sum_over_ranks(dist, torch, values):
     t = torch.tensor([v - (1 << 64) if v >= (1 << 63) else v for v in values], dtype=torch.int64)
     dist.all_reduce(t)
     return [int(v) & MASK64 for v in t.tolist()]
+
+
+def dump_outputs(directory, result):
+    """--dump-outputs: what a caller of the timed entry point receives from its last step - the join's aggregates
+    (count, sum_keys, sum_outer_vals, sum_inner_vals), four uint64 - as .npy files in float64:
+      result.npy            the four values as float64 (sums above 2^53 rounded to the nearest double)
+      result_u32_words.npy  shape (4, 2): the high and the low 32-bit word of each value, exact in float64
+    The relations come from the library's seeded generator, so the same arguments give the same inputs in every run."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    vals = [int(v) & MASK64 for v in result]
+    arrays = {"result": np.array(vals, dtype=np.float64),
+              "result_u32_words": np.array([[v >> 32, v & 0xFFFFFFFF] for v in vals], dtype=np.float64)}
+    for name, arr in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), arr)
+    return sorted(arrays)
 
 
 def cpu_baseline(hj, args, algo, more=()):
@@ -599,6 +623,8 @@ def main():
     got = last["result"] if (multi or not args.enqueue_only) else [int(x) & MASK64 for x in d_result.tolist()]
     # the analytic aggregates assume unique build keys, i.e. at least as many probe as build tuples
     checksum_ok = (got == expect_global and results_ok) if outer_total >= inner_total else None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, got)
 
     ms_per_step = elapsed / args.steps * 1e3
     value = outer_total / (elapsed / args.steps) / 1e9

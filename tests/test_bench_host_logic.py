@@ -1,8 +1,12 @@
 """CPU tests of bench.py's host-side logic (no GPU): argument defaults of the contract, the CPU allowance
-the CPU baseline uses, and that a GPU-less run fails loudly instead of falling back to anything."""
+the CPU baseline uses, that a GPU-less run fails loudly instead of falling back to anything, and what --dump-outputs
+writes; one GPU test runs a small bench and checks its line and its dumped outputs."""
+import json
 import os
 import subprocess
 import sys
+
+import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -72,3 +76,47 @@ def test_library_hash_covers_every_source_of_the_library(tmp_path, monkeypatch):
     with open(root / "hash_join_codes_knl_amd" / "csrc" / "exchange_layout.hpp", "a") as f:
         f.write("\n")
     assert B.library_hash() != l1
+
+
+def test_bench_steps_must_be_a_positive_count():
+    """--steps is the number of timed steps and ms_per_step their wall clock divided by it: zero steps is refused"""
+    import bench
+    assert bench.parse(["--steps", "7", "--warmup", "0"]).steps == 7
+    for bad in (["--steps", "0"], ["--steps", "-2"], ["--warmup", "-1"]):
+        with pytest.raises(SystemExit):
+            bench.parse(bad)
+
+
+def test_bench_dump_outputs_holds_the_aggregates_exactly(tmp_path):
+    """--dump-outputs: the four uint64 aggregates as float64, and as 32-bit words that float64 holds exactly"""
+    import numpy as np
+    import bench
+    vals = [1_000_000_000, (1 << 64) - 1, (1 << 53) + 1, 0]
+    names = bench.dump_outputs(str(tmp_path / "out"), vals)
+    files = sorted(os.listdir(tmp_path / "out"))
+    assert files == [n + ".npy" for n in names] == ["result.npy", "result_u32_words.npy"]
+    assert sum(os.path.getsize(tmp_path / "out" / f) for f in files) < 64 << 20
+    res = np.load(tmp_path / "out" / "result.npy")
+    words = np.load(tmp_path / "out" / "result_u32_words.npy")
+    assert res.dtype == words.dtype == np.float64 and res.shape == (4,) and words.shape == (4, 2)
+    assert res.tolist() == [float(v) for v in vals]
+    assert [(int(hi) << 32) | int(lo) for hi, lo in words] == vals
+
+
+@pytest.mark.gpu
+def test_bench_dumps_what_its_last_timed_step_returned(tmp_path):
+    """A small bench run: the line reports the timed steps asked for, and the dumped arrays are its join result"""
+    import numpy as np
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--cpu-outer", "0",
+           "--no-secondary", "--inner", "1000000", "--outer", "8000000", "--dump-outputs", str(tmp_path / "out")]
+    p = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0, p.stderr[-2000:]
+    lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    line = json.loads(lines[0])
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["checksum_ok"] is True
+    r = line["result"]
+    want = [r["count"], r["sum_keys"], r["sum_outer_vals"], r["sum_inner_vals"]]
+    words = np.load(tmp_path / "out" / "result_u32_words.npy")
+    assert [(int(hi) << 32) | int(lo) for hi, lo in words] == want
+    assert np.load(tmp_path / "out" / "result.npy").tolist() == [float(v) for v in want]
