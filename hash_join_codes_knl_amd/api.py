@@ -21,7 +21,7 @@ FLAG_UNIQUE = 1
 
 EXPORTS = [
     "hjgpu_kernel_hash", "hjgpu_library_hash", "hjgpu_device_count", "hjgpu_create", "hjgpu_destroy", "hjgpu_last_error", "hjgpu_status_string",
-    "hjgpu_get_device_info", "hjgpu_set_option", "hjgpu_reserve", "hjgpu_get_stats",
+    "hjgpu_get_device_info", "hjgpu_set_option", "hjgpu_reserve", "hjgpu_get_stats", "hjgpu_get_counter",
     "hjgpu_get_async_status", "hjgpu_accumulate_async_status", "hjgpu_set_async_output", "hjgpu_output_capacity",
     "hjgpu_malloc", "hjgpu_malloc_placed", "hjgpu_free", "hjgpu_memcpy_h2d", "hjgpu_memcpy_d2h", "hjgpu_synchronize", "hjgpu_audit_read", "hjgpu_audit_recheck",
     "hjgpu_host_alloc", "hjgpu_host_free",
@@ -195,6 +195,7 @@ def load_library(build_if_missing=True):
     L.hjgpu_set_option.argtypes = [vp, C.c_char_p, C.c_char_p]
     L.hjgpu_reserve.argtypes = [vp, sz, sz]
     L.hjgpu_get_stats.argtypes = [vp, C.POINTER(Stats)]
+    L.hjgpu_get_counter.argtypes = [vp, C.c_char_p, C.POINTER(C.c_uint64)]
     L.hjgpu_get_async_status.argtypes = [vp, vp]
     L.hjgpu_accumulate_async_status.argtypes = [vp, vp, vp]
     L.hjgpu_set_async_output.argtypes = [vp, C.POINTER(Output)]
@@ -387,6 +388,12 @@ class HjGpu:
         s = Stats()
         self._check(self.lib.hjgpu_get_stats(self.handle, C.byref(s)))
         return s.as_dict()
+
+    def counter(self, name):
+        """hjgpu_get_counter: "probe_fallbacks" (claimed probe sides done again exactly), "probe_exact" (1: exact path from now on)."""
+        v = C.c_uint64()
+        self._check(self.lib.hjgpu_get_counter(self.handle, name.encode(), C.byref(v)))
+        return v.value
 
     def synchronize(self, stream=None):
         self._check(self.lib.hjgpu_synchronize(self.handle, stream))

@@ -65,6 +65,9 @@ struct HjTuning {
     int placement_ms = 500;         // "placement_ms": wall-clock budget of one placement search (0 = none): when it is spent the best block so far is
                                     // taken (round 4's driver run spent 3.07 s in a search that found no fast block among twelve)
     bool placement_log = false;     // "placement_log": the search prints every candidate's fill time and its choice to stderr (diagnostics)
+    bool exact_probe_counts = false;    // "exact_probe_counts": every join histograms its probe side (K4) - no claimed probe side (A/B, tests)
+    int probe_slack = 12;           // "probe_slack": per cent of slack (plus 8 sigma + 64 rows) in the claimed probe side's optimistic regions;
+                                    // 0 = none at all (tests: forces the exact fallback)
     bool solo = false;              // "solo": the caller promises that NOTHING else runs on the device beside this context's blocking joins (one
                                     // process, one stream - the reference's programs): their partial-line stores (K6) stay plain,
                                     // 0.34 ms per 64 M x 1 G step faster.  Default 0: every store that may sit dirty in an L2 is non-temporal (round 5:
@@ -172,6 +175,11 @@ struct ScatterArgs {
                                     // NTP instance of the kernel, see k6_store8)
     const u64 *dyn;                 // pass 1 of a device-planned group (else NULL): {first row, rows} of the input inside kin / vin, in device
                                     // memory - geom.n / geom.part are computed from it in the kernel (geom holds the CAPACITY's ranges and tile)
+    // claimed pass 1 (the probe side of a blocking join, no K4): partition p writes [p * claim_cap, (p + 1) * claim_cap) of kout, whole
+    // lines from the front and the workgroups' last tails from the back; claim_cursors[16 p] = lines | tail tuples << 32 (zeroed per join)
+    u64 *claim_cursors;
+    u64 claim_cap;
+    uint32_t *claim_overflow;       // device flag: an optimistic region (pass 1 claimed, or pass 2 into claimed final regions) was full
 };
 
 struct JoinArgs {
@@ -212,6 +220,8 @@ struct JoinArgs {
     const uint32_t *multi_fill;
     uint32_t resume;                     // 1 (device-planned groups): every wave goes on in the output block its slot of final_offsets names (HJ_NO_CURSOR:
                                          // none yet) - the groups' joins share one block counter, one set of open blocks and ONE close_gaps at the end
+    uint32_t s_pieces;                   // claimed probe side: 1 - the probe side has 1 + s_pieces pieces per partition in soff / send (front lines,
+                                         // back tails) while the build side has `chunks` = 1; else 0
 };
 
 struct PlanArgs {
@@ -256,6 +266,11 @@ struct PlanArgs {
     u64 *seg2[2] = {nullptr, nullptr};   // [F1 + 1] p_major: the pass-1 partitions' bounds
     // a device-planned group (else NULL): {first row, rows} of relation r in device memory; n[r] and chunk_part[r] are then computed from it
     const u64 *dyn[2] = {nullptr, nullptr};
+    // claimed probe side (else 0): S has no histogram; its final partition q is the optimistic region [q * s_cap2, (q + 1) * s_cap2)
+    // (hj_launch_claimed_desc plans pass 2 of S after pass 1), and the join's probe slices are planned for a FULL region: whatever pass 2
+    // leaves in it, no work item gets more than HJ_JOIN_SLICE (+ 1 per piece) probe rows - the bound the <UNIQUE, DEDUP> join's
+    // per-row `matched` bitmap is sized for
+    u64 s_cap2 = 0;
 };
 
 // A relation that arrives pass-1-partitioned in pieces (the multi-GPU CPRA's receiving side): piece c = rows
@@ -290,6 +305,14 @@ __host__ __device__ inline u64 hj_group_shift(u64 dense_start, uint32_t g)
     return ((dense_start + 31) & ~(u64)31) - dense_start + (u64)32 * g;
 }
 int hj_launch_plan(const PlanArgs &a, hipStream_t stream);
+// Pass 2 of a claimed probe side, planned from pass 1's cursors (claim_cursors[16 p] = lines | back tuples << 32, regions of cap1
+// tuples): two segments per pass-1 partition - its front lines and its back tails - cut into tiles of `tile2`; the descriptors go to
+// tdesc (at most tdesc_cap) and their number to *total.  A set *overflow (pass 1 found a region full) plans no tile at all.
+// The join's view of a claimed probe side after pass 2: partition q's region [off2[q], end2[q]) holds cur2[q] = lines | tails << 32 -
+// pieces_beg / pieces_end [2P] = its front lines (q) and its back tails (P + q), clamped to the region (JoinArgs::s_pieces = 1)
+int hj_launch_claimed_pieces(const u64 *off2, const u64 *end2, const u64 *cur2, uint32_t P, u64 *pieces_beg, u64 *pieces_end, hipStream_t stream);
+int hj_launch_claimed_desc(const u64 *claim_cursors, u64 cap1, uint32_t F1, uint32_t F2, uint32_t tile2, uint4 *tdesc, uint32_t tdesc_cap,
+                           u64 *total, uint32_t *overflow, hipStream_t stream);
 // Batched partitioning of ONE relation (single chunk): the relation's pass-1 ranges are cut into batches of
 // `ranges_per_batch`; pass 1 of a batch writes into a small REUSED buffer (dense layout starting at 0) and pass 2 of
 // the batch reads it right away, while it is still in the 256 MiB Infinity Cache - the intermediate copy of the

@@ -214,6 +214,7 @@ MetaLayout carve(void *base, uint32_t C, uint32_t F1, uint32_t P, size_t ranges,
     auto take = [&](size_t n) { u64 *r = p ? p + at : nullptr; at += (n + 1) & ~size_t(1); return r; };
     m.counts[0] = take((size_t)C * P);
     m.counts[1] = take((size_t)C * P);
+    m.claim1 = take((size_t)F1 * HJ_LINE_TUPLES);
     m.tickets = reinterpret_cast<uint32_t *>(take(HJ_TICKET_WORDS / 2));     // HJ_TICKET_K4 / _K6 / _MULTI_FILL (hj_internal.hpp)
     m.counts_bytes = at * sizeof(u64);
     for (int r = 0; r < 2; ++r) {
@@ -228,6 +229,8 @@ MetaLayout carve(void *base, uint32_t C, uint32_t F1, uint32_t P, size_t ranges,
         m.seg2[r] = take((size_t)F1 + 1);
         m.more[r] = C > 8 ? take(P) : nullptr;
     }
+    m.claim_total = take(1);
+    m.pieces = take((size_t)4 * P);
     m.slice_prefix = take((size_t)P + 1);
     m.slices = take(P);
     m.item_part = reinterpret_cast<uint32_t *>(take(((size_t)P + items_extra + 2) / 2 + 1));
@@ -434,8 +437,17 @@ Pass1Geom make_geom(const HjTuning &tune, const void *keys, size_t n, uint32_t C
 // PHJ / CPRA: fused histogram -> plan -> scatter x2 -> LDS join
 // ---------------------------------------------------------------------------
 
+// Optimistic region of a claimed probe side for `mean` rows: slack per cent of them plus 8 sigma + 64 rows (none at all with slack 0),
+// in whole 128-byte lines
+static u64 claimed_cap(u64 mean, int slack)
+{
+    u64 c = mean;
+    if (slack > 0) c += mean * (u64)slack / 100 + (u64)(8.0 * sqrt((double)mean)) + 64;
+    return (c + HJ_LINE_TUPLES - 1) & ~(u64)(HJ_LINE_TUPLES - 1);
+}
+
 int phj_prepare(hjgpu_ctx *ctx, size_t inner, size_t outer, const hjgpu_phj_params *prm,
-                uint32_t chunks, PhjPlan *pl, bool pre, int big_override, size_t plan_inner)
+                uint32_t chunks, PhjPlan *pl, bool pre, int big_override, size_t plan_inner, bool claim_s)
 {
     ctx->prepared = false;               // the workspace is about to be re-planned (hjgpu_phj_build sets it again)
     ReserveClock clock(ctx);
@@ -471,7 +483,23 @@ int phj_prepare(hjgpu_ctx *ctx, size_t inner, size_t outer, const hjgpu_phj_para
     // workspace: pass-1 twins always, pass-2 twins when there is a second pass
     // packed (payload << 32 | key) twins: tmp[0] / tmp[2] = pass-1 output of R / S,
     // tmp[4] / tmp[6] = pass-2 output
-    const size_t rb = (inner + 4) * sizeof(u64), sb = (outer + 4) * sizeof(u64);
+    const size_t rb = (inner + 4) * sizeof(u64);
+    size_t sb = (outer + 4) * sizeof(u64), sb2 = sb + (size_t)pl->C * pl->P * HJ_LINE_TUPLES * sizeof(u64);
+    // Claimed probe side: a blocking whole join of one chunk in two passes whose pass 1 has the whole-line carry in 1024-thread
+    // workgroups.  Pass 1 of S needs no histogram: it claims whole lines of per-partition regions of cap1 tuples; pass 2 writes final
+    // regions of cap2 tuples.  Both are optimistic: hashed keys spread evenly, and a region that is full flags the join, which the
+    // blocking call then does again on the exact path (phj_like).
+    pl->claim_s = 0; pl->cap1 = pl->cap2 = 0;
+    if (claim_s && !pre && pl->C == 1 && pl->F2 > 1 && !ctx->tune.dense2 && ctx->tune.batch_tuples <= 0 && outer) {
+        const ScatterConfig c1 = hj_scatter_config(ctx->tune, 1, pl->F1, true);
+        if (c1.carry && c1.block == 1024 && (c1.vpt == 4 || c1.vpt == 3)) {
+            pl->claim_s = 1;
+            pl->cap1 = claimed_cap((u64)outer / pl->F1, ctx->tune.probe_slack);
+            pl->cap2 = claimed_cap((u64)outer / pl->P, ctx->tune.probe_slack);
+            sb = std::max(sb, (size_t)(pl->cap1 * pl->F1 + 4) * sizeof(u64));
+            sb2 = std::max(sb2, (size_t)(pl->cap2 * pl->P + 4) * sizeof(u64));
+        }
+    }
     if (!pre) {                          // pre-partitioned relations are read where the caller has them: no pass-1 twins
         CHK(ensure(ctx, ctx->tmp[0], rb));
         CHK(ensure_placed(ctx, ctx->tmp[2], sb));
@@ -480,16 +508,19 @@ int phj_prepare(hjgpu_ctx *ctx, size_t inner, size_t outer, const hjgpu_phj_para
         // the final layout starts every partition on a 128-byte line: < 16 tuples of padding each
         const size_t pad = (size_t)pl->C * pl->P * HJ_LINE_TUPLES * sizeof(u64);
         CHK(ensure(ctx, ctx->tmp[4], rb + pad));
-        CHK(ensure(ctx, ctx->tmp[6], sb + pad));
+        CHK(ensure(ctx, ctx->tmp[6], sb2));
     }
     // ranges of the larger relation bound the per-range tables of both
     // (sized for every relation up to these sizes: a batch of a prepared build side may be smaller than max_outer)
     const Pass1Geom gr = make_geom(ctx->tune, nullptr, inner, pl->C, pl->F1, true, true), gs = make_geom(ctx->tune, nullptr, outer, pl->C, pl->F1, true, true);
     pl->ranges = (size_t)(gr.ranges_per_chunk > gs.ranges_per_chunk ? gr.ranges_per_chunk : gs.ranges_per_chunk) * pl->C;
-    pl->items_extra = hj_join_items_capacity(pl->P, outer) - pl->P;
+    // (a claimed probe side plans every partition's probe slices for its whole region: cap2 rows each, see plan_items_body)
+    pl->items_extra = hj_join_items_capacity(pl->P, std::max<size_t>(outer, pl->claim_s ? (size_t)(pl->cap2 * pl->P) : 0)) - pl->P;
     // pass-2 tiles: whole tiles of the relation plus up to two ragged tiles per segment
     const size_t larger = inner > outer ? inner : outer;
+    // (a claimed probe side: two segments per pass-1 partition, its front lines and its back tails, in regions of cap1 tuples)
     pl->tiles2 = pl->F2 > 1 ? larger / (size_t)hj_scatter_tile(ctx->tune, 2, pl->F2, true) + 2 * (size_t)pl->C * pl->F1 + 8 : 0;
+    if (pl->claim_s) pl->tiles2 = std::max(pl->tiles2, (size_t)(pl->cap1 * pl->F1) / (size_t)hj_scatter_tile(ctx->tune, 2, pl->F2, true) + 4 * (size_t)pl->F1 + 8);
     // Batched probe-side partitioning (option "batch_tuples" > 0; two-pass, single-chunk plans with line-aligned final
     // partitions): pass 1 of a batch writes into one of two small reused buffers and pass 2 reads it straight away, so
     // the intermediate copy of the probe side can stay in the 256 MiB Infinity Cache.  Plain copies gain from that
@@ -632,6 +663,10 @@ int phj_enqueue(hjgpu_ctx *ctx, const PhjPlan &pl,
                                             geom[r].ranges_per_chunk, pl.F1, stream));
         return HJGPU_OK;
     };
+    // claimed probe side (PhjPlan::claim_s): only in the merged form of a blocking whole join
+    const bool claim = pl.claim_s && mode == PHJ_WHOLE && !pre && !grp && !inner_ready && !audit && pl.C == 1 && pad2 &&
+                       !pl.batch_ranges && ctx->tune.merged_plan;
+    if (claim) pa.s_cap2 = pl.cap2;
     auto pass1 = [&](int r) -> int {       // K6 pass 1: caller's columns -> tmp[0..3]
         if (!nn[r]) return HJGPU_OK;
         ScatterArgs sa;
@@ -643,6 +678,10 @@ int phj_enqueue(hjgpu_ctx *ctx, const PhjPlan &pl,
         sa.in_packed = 0; sa.out_packed = 1;
         sa.nt_partial = ctx->rows_plain ? 0u : 1u;
         sa.dyn = dyn[r];
+        if (claim && r == 1) {
+            sa.range_base = nullptr;
+            sa.claim_cursors = m.claim1; sa.claim_cap = pl.cap1; sa.claim_overflow = &st->probe_overflow;
+        }
         return hj_launch_scatter(sa, ctx->tune, scatter_cus(ctx), stream);
     };
     auto pass2 = [&](int r) -> int {       // K6 pass 2: tmp[0..3] -> tmp[4..7], one segment per (chunk, pass-1 partition)
@@ -656,6 +695,11 @@ int phj_enqueue(hjgpu_ctx *ctx, const PhjPlan &pl,
         sa.part_start = m.off2[r]; sa.part_end = m.end2[r]; sa.aligned_claims = pad2 ? 1u : 0u;
         sa.in_packed = 1; sa.out_packed = 1;
         sa.nt_partial = ctx->rows_plain ? 0u : 1u;
+        if (claim && r == 1) {
+            // the tiles hj_launch_claimed_desc planned from pass 1's cursors; regions that fill up flag the join
+            sa.tile_prefix = m.claim_total; sa.nseg = 0; sa.seg_off = nullptr;
+            sa.claim_overflow = &st->probe_overflow;
+        }
         return hj_launch_scatter(sa, ctx->tune, scatter_cus(ctx), stream);
     };
     // K4 -> K5 -> K6 x2 for one relation; ev = {after hist, after plan, after pass 1, after pass 2}
@@ -761,13 +805,17 @@ int phj_enqueue(hjgpu_ctx *ctx, const PhjPlan &pl,
     // hjgpu_get_stats keeps its meaning (histogram / plan / pass 1 / pass 2 of R and S together).
     const bool merged = grp || (mode == PHJ_WHOLE && !inner_ready && !pre && !pl.batch_ranges && ctx->tune.merged_plan);   // (a group: always)
     if (merged) {
-        CHK(k4(0)); CHK(k4(1));
+        // (a claimed probe side has neither K4 nor range bases: pass 1 claims lines, and the plan of its pass 2 follows pass 1)
+        CHK(k4(0)); if (!claim) CHK(k4(1));
         record(ctx, EV_S_HIST, stream);
         pa.mask = 7u;
         CHK(hj_launch_plan(pa, stream));
-        CHK(k5b(0)); CHK(k5b(1));
+        CHK(k5b(0)); if (!claim) CHK(k5b(1));
         record(ctx, EV_S_PLAN, stream);
         CHK(pass1(0)); CHK(pass1(1));
+        if (claim && outer)
+            CHK(hj_launch_claimed_desc(m.claim1, pl.cap1, pl.F1, pl.F2, pa.tile2, m.tdesc[1], (uint32_t)m.tdesc_cap, m.claim_total,
+                                       &st->probe_overflow, stream));
         record(ctx, EV_S_SC1, stream);
         CHK(pass2(0)); CHK(pass2(1));
         record(ctx, EV_S_SC2, stream);
@@ -799,6 +847,11 @@ int phj_enqueue(hjgpu_ctx *ctx, const PhjPlan &pl,
         ja.rk = fin[0]; ja.rv = fin[1]; ja.sk = fin[2]; ja.sv = fin[3];
         ja.roff = m.off2[0]; ja.soff = m.off2[1];
         ja.rend = m.end2[0]; ja.send = m.end2[1];
+        if (claim) {
+            // two pieces per partition: pass 2's front lines and back tails (hj_launch_claimed_pieces)
+            CHK(hj_launch_claimed_pieces(m.off2[1], m.end2[1], m.cur2[1], pl.P, m.pieces, m.pieces + 2 * (size_t)pl.P, stream));
+            ja.soff = m.pieces; ja.send = m.pieces + 2 * (size_t)pl.P; ja.s_pieces = 1;
+        }
         ja.slice_prefix = m.slice_prefix; ja.slices = m.slices; ja.item_part = m.item_part;
         // line-aligned two-pass layout: the chunks' pass-2 tiles wrote every final partition as ONE region
         ja.P = pl.P; ja.chunks = pad2 ? 1u : pl.C;
@@ -839,17 +892,30 @@ int phj_enqueue(hjgpu_ctx *ctx, const PhjPlan &pl,
     return HJGPU_OK;
 }
 
-int finish_blocking(hjgpu_ctx *ctx, hjgpu_result *result, const hjgpu_output *out, hipStream_t stream)
+static int finish_from(hjgpu_ctx *ctx, const DevState &h, hjgpu_result *result, const hjgpu_output *out)
 {
-    DevState h;
-    HIPCHK(ctx, hipMemcpyAsync(&h, ctx->state.p, sizeof(DevState), hipMemcpyDeviceToHost, stream));
-    HIPCHK(ctx, hipStreamSynchronize(stream));
     if (result) *result = h.result;
     if (h.zero_key) return fail(ctx, HJGPU_EZEROKEY, "NPJ: a build key is 0, the empty-bucket sentinel");
     if (h.overflow) return fail(ctx, HJGPU_EOVERFLOW, "materialised output exceeded its capacity");
     if (out && out->d_keys && h.dense != h.result.count && (h.result.count != 0 || h.dense != 0))
         return fail(ctx, HJGPU_EHIP, "internal: dense length != match count after close_gaps");
     return HJGPU_OK;
+}
+
+int finish_blocking(hjgpu_ctx *ctx, hjgpu_result *result, const hjgpu_output *out, hipStream_t stream)
+{
+    DevState h;
+    HIPCHK(ctx, hipMemcpyAsync(&h, ctx->state.p, sizeof(DevState), hipMemcpyDeviceToHost, stream));
+    HIPCHK(ctx, hipStreamSynchronize(stream));
+    return finish_from(ctx, h, result, out);
+}
+
+// May a join partition its probe side without K4 (the claimed form, PhjPlan::claim_s)?  Only the blocking whole join of one chunk asks;
+// option "exact_probe_counts", the diagnostics options and a context whose claimed join once overflowed say no.
+static bool claimed_probe_allowed(const hjgpu_ctx *ctx)
+{
+    const HjTuning &t = ctx->tune;
+    return !t.exact_probe_counts && !ctx->probe_exact && !t.audit && !t.scatter_prof && !t.dense2 && t.merged_plan && t.batch_tuples <= 0;
 }
 
 // ---------------------------------------------------------------------------
@@ -1080,11 +1146,22 @@ int hjgpu_reserve(hjgpu_ctx *ctx, size_t inner, size_t outer)
         grouped_caps(ctx, groups, inner, outer, &cap_r, &cap_s, &plan_inner);
         CHK(grouped_twins(ctx, group_layout(groups), inner, outer));
         CHK(phj_prepare(ctx, cap_r, cap_s, &prm, 8, &pl, false, -1, plan_inner));
-    } else
+    } else {
         CHK(phj_prepare(ctx, inner, outer, &prm, 8, &pl));     // 8 chunks = largest meta
+        // the blocking join's claimed probe side: optimistic regions, a little larger than the relation
+        if (claimed_probe_allowed(ctx)) CHK(phj_prepare(ctx, inner, outer, &prm, 1, &pl, false, -1, 0, true));
+    }
     size_t buckets; uint32_t factor;
     CHK(npj_prepare(ctx, inner, nullptr, &buckets, &factor));
     return HJGPU_OK;
+}
+
+int hjgpu_get_counter(hjgpu_ctx *ctx, const char *name, uint64_t *value)
+{
+    if (!ctx || !name || !value) return HJGPU_EINVAL;
+    if (strcmp(name, "probe_fallbacks") == 0) { *value = ctx->probe_fallbacks; return HJGPU_OK; }
+    if (strcmp(name, "probe_exact") == 0) { *value = (ctx->tune.exact_probe_counts || ctx->probe_exact) ? 1u : 0u; return HJGPU_OK; }
+    return fail(ctx, HJGPU_EINVAL, "unknown counter (probe_fallbacks, probe_exact)");
 }
 
 // the workspace's side of hjgpu_stats: what the context has spent growing it, and its last placement search
@@ -1735,8 +1812,21 @@ static int phj_like(hjgpu_ctx *ctx, uint32_t chunks,
         CHK(broadcast_enqueue(ctx, rk, rv, inner, sk, sv, outer, prm, out, stream, (hipEvent_t)inner_ready));
     } else {
         PhjPlan pl;
-        CHK(phj_prepare(ctx, inner, outer, prm, chunks, &pl));
+        const bool claim = blocking && chunks == 1 && !inner_ready && !local_join && !d_result && claimed_probe_allowed(ctx);
+        CHK(phj_prepare(ctx, inner, outer, prm, chunks, &pl, false, -1, 0, claim));
         CHK(phj_enqueue(ctx, pl, rk, rv, inner, sk, sv, outer, out, stream, (hipEvent_t)inner_ready));
+        if (pl.claim_s) {
+            DevState h;
+            HIPCHK(ctx, hipMemcpyAsync(&h, ctx->state.p, sizeof(DevState), hipMemcpyDeviceToHost, stream));
+            HIPCHK(ctx, hipStreamSynchronize(stream));
+            if (!h.probe_overflow) return finish_from(ctx, h, result, out);
+            // an optimistic region of the probe side was full (skewed keys): the join again, exactly (K4 of S, range bases), and every
+            // later join of this context exactly at once; the caller's result and rows are those of this second join
+            ctx->probe_exact = true;
+            ++ctx->probe_fallbacks;
+            CHK(phj_prepare(ctx, inner, outer, prm, chunks, &pl));
+            CHK(phj_enqueue(ctx, pl, rk, rv, inner, sk, sv, outer, out, stream, (hipEvent_t)inner_ready));
+        }
     }
     if (d_result)
         HIPCHK(ctx, hj_copy_async(d_result, ctx->state.p, sizeof(hjgpu_result), stream));

@@ -33,7 +33,7 @@ struct DevState {
     uint32_t pad;
     u64 work_counter2;      // the multi-fill half of a _UNIQUE join (hj_launch_join)
     uint32_t group_skew;    // a device-planned grouped join skipped a group that was larger than its workspace (group_desc_kernel)
-    uint32_t pad2;
+    uint32_t probe_overflow;    // a claimed probe side did not fit its optimistic regions (K6 / claimed_desc_kernel): the blocking call joins again exactly
 };
 
 // probe side (S) is partitioned first, then the build side (R): a caller can overlap the
@@ -75,6 +75,10 @@ struct hjgpu_ctx {
     hjgpu_output pending_out;
     bool has_pending_out = false;
     bool last_had_output = false;   // hjgpu_get_async_status: the last enqueued join wrote result columns
+    // claimed probe side: joins whose optimistic regions overflowed and were done again on the exact path; after the first, every later
+    // blocking join of the context takes the exact path at once (hjgpu_get_counter "probe_fallbacks" / "probe_exact")
+    uint64_t probe_fallbacks = 0;
+    bool probe_exact = false;
     bool rows_plain = false;        // the join being enqueued is SOLO - a blocking call of a context with option "solo": plain partial-line stores
                                     // in K6 (k6_store8) and plain result rows (join_kernel<..., NTROWS = false>); every other launch writes them non-temporal
     // grouped plans: pass-0 twins of the four columns, the groups' offsets and (device-planned) descriptors, and the call's accumulated
@@ -190,6 +194,9 @@ inline uint32_t align_of(const void *p) { return (uint32_t)(((uintptr_t)p >> 2) 
 // Carves the meta buffer; must match between sizing and use.
 struct MetaLayout {
     u64 *counts[2], *off2[2], *end2[2], *cur2[2], *off1[2], *cur1[2], *tp1[2], *seg1[2], *tp2[2];
+    u64 *claim1;                 // [F1 * 16] claimed probe side: pass 1's cursors, one per 128-byte line (zeroed with the counts)
+    u64 *claim_total;            // [1] claimed probe side: pass-2 tiles planned by hj_launch_claimed_desc
+    u64 *pieces;                 // [4 P] claimed probe side: the join's two pieces per partition (begins [2 P], ends [2 P])
     u64 *seg2[2];                // [F1 + 1] partition-major pass-1 layout of a chunked relation: bounds of the pass-1 partitions
     u64 *more[2];                // [P] more than 8 chunks: the counters of chunks 8 ... C - 1 added up (PlanArgs::more), else NULL
     u64 *slice_prefix, *slices;
@@ -240,6 +247,10 @@ struct PhjPlan {
     // multi-GPU CPRA; F1 = this rank's share k of its fan-out pre_F1tot, partitions [pre_base, pre_base + k)
     uint32_t pre;            // 1: the relations arrive pass-1-partitioned
     uint32_t pre_f1, pre_F1tot, pre_base;
+    // claimed probe side (blocking whole joins, phj_prepare's claim_s): no K4 of S; pass 1 of S writes regions of cap1 tuples per pass-1
+    // partition, pass 2 final regions of cap2 tuples (both optimistic, line multiples)
+    uint32_t claim_s;
+    u64 cap1, cap2;
 };
 static_assert(sizeof(PhjPlan) <= sizeof(hjgpu_ctx::prepared_plan), "prepared_plan too small");
 // the pieces a pre-partitioned relation arrives in (one per source rank)
@@ -254,8 +265,10 @@ enum PhjMode { PHJ_WHOLE = 0, PHJ_BUILD_ONLY = 1, PHJ_PROBE_ONLY = 2 };
 
 // plan_inner > 0: the fan-out is planned for a build side of that many rows while the workspace holds `inner` (device-planned groups: the
 // mean group decides the partitions, the largest group the plan allows decides the buffers)
+// claim_s: the probe side may be partitioned without its histogram pass (a blocking whole join, see claimed_probe_allowed); the plan
+// says in PhjPlan::claim_s whether it is
 int phj_prepare(hjgpu_ctx *ctx, size_t inner, size_t outer, const hjgpu_phj_params *prm, uint32_t chunks, PhjPlan *pl, bool pre = false,
-                int big_override = -1, size_t plan_inner = 0);
+                int big_override = -1, size_t plan_inner = 0, bool claim_s = false);
 // One group of a device-planned grouped join: desc = {build first row, build rows, probe first row, probe rows} in device memory; the
 // columns handed to phj_enqueue are the pass-0 twins, `inner` / `outer` the CAPACITY the plan was prepared for.  The join's state
 // (aggregates, block counter, open output blocks) is the whole grouped join's: phj_enqueue neither clears it nor closes the gaps.

@@ -337,9 +337,14 @@ __global__ __launch_bounds__(BLOCK, hj_join_waves_per_simd(BLOCK, LOG2SLOTS)) vo
         return hits;
     };
 
-    auto probe_item = [&](u64 slice, u64 nslices, auto probe4) {
+    // nslices_word = probe slices | extra probe pieces << 24: a claimed probe side (JoinArgs::s_pieces) has two pieces of one region per
+    // partition in soff / send - pass 2's front lines and back tails - where the build side has one (the count travels with the item's
+    // descriptor: a kernel-argument load here costs the 1024-thread instances scratch)
+    auto probe_item = [&](u64 slice, u64 nslices_word, auto probe4) {
         u64 row0 = 0;
-        for (uint32_t c = 0; c < C; ++c) {
+        const u64 nslices = nslices_word & 0xFFFFFFu;
+        const uint32_t pieces = C + (uint32_t)(nslices_word >> 24);
+        for (uint32_t c = 0; c < pieces; ++c) {
             const u64 b = a.soff[(u64)c * P + q], e = a.send[(u64)c * P + q];
             const u64 len = e - b;
             if (len == 0) continue;
@@ -375,7 +380,7 @@ __global__ __launch_bounds__(BLOCK, hj_join_waves_per_simd(BLOCK, LOG2SLOTS)) vo
             const u64 rb = a.roff[nq], rn = a.rend[nq] - rb;
             d_rb[slot] = rb;
             d_rn[slot] = rn;
-            d_nslices[slot] = nslices;
+            d_nslices[slot] = nslices | (a.s_pieces << 24);
             u64 rows = rn;
             for (uint32_t c = 1; c < C; ++c) rows += a.rend[(u64)c * P + nq] - a.roff[(u64)c * P + nq];
             if (groups == 1) {
@@ -406,7 +411,7 @@ __global__ __launch_bounds__(BLOCK, hj_join_waves_per_simd(BLOCK, LOG2SLOTS)) vo
         if (w >= total_items) break;
         q = hj_uniform(d_q[par]);
         const u64 slice = hj_uniform(d_slice[par]);
-        const u64 nslices = hj_uniform(d_nslices[par]);
+        const u64 nslices = hj_uniform(d_nslices[par]);            // | extra probe pieces << 24 (probe_item)
         const u64 rows_beg = hj_uniform(d_rows_beg[par]), rows_end = hj_uniform(d_rows_end[par]);
         if (tid == 0) claim(par ^ 1);                     // published by the clear barrier below
         u64 have_rows = pre_rows;

@@ -515,6 +515,13 @@ __global__ __launch_bounds__(PLAN_BLOCK) void plan_offsets_kernel(PlanArgs a)
     if (blockIdx.y == 2) { if (c == 0) plan_items_body(a); return; }
     const int r = blockIdx.y;
     if (!((a.mask >> r) & 1u)) return;
+    if (r == 1 && a.s_cap2) {
+        // claimed probe side (one chunk): optimistic final regions of s_cap2 tuples, cursors zero (pass 2 fills front and back)
+        for (uint32_t q = threadIdx.x; q < P; q += PLAN_BLOCK) {
+            hj_store(&a.off2[1][q], (u64)q * a.s_cap2); hj_store(&a.end2[1][q], (u64)(q + 1) * a.s_cap2); hj_store(&a.cur2[1][q], (u64)0);
+        }
+        return;
+    }
     const u64 *__restrict__ cnt = a.counts[r] + (u64)c * P;
     u64 *off2 = a.off2[r] + (u64)c * P;
     u64 *end2 = a.end2[r] + (u64)c * P;
@@ -617,6 +624,7 @@ __global__ __launch_bounds__(PLAN_BLOCK) void plan_tiles_kernel(PlanArgs a)
     __shared__ u64 scratch[PLAN_BLOCK / 64 + 1];
     const uint32_t C = a.chunks;
     if (!((a.mask >> blockIdx.x) & 1u)) return;
+    if (blockIdx.x == 1 && a.s_cap2) return;            // claimed probe side: hj_launch_claimed_desc plans its pass 2
     {
         const int r = blockIdx.x;
         // pass-1 tiles: segments are the chunks of the caller's (possibly unaligned) input
@@ -644,7 +652,7 @@ constexpr int TDESC_BLOCKS = 32;
 __global__ __launch_bounds__(PLAN_BLOCK) void tile_desc_kernel(PlanArgs a)
 {
     const int r = blockIdx.y;
-    if (!((a.mask >> r) & 1u) || !a.tdesc[r]) return;
+    if (!((a.mask >> r) & 1u) || !a.tdesc[r] || (r == 1 && a.s_cap2)) return;
     const uint32_t nseg = a.p_major ? a.F1 : a.chunks * a.F1, tile2 = a.tile2;
     const u64 *__restrict__ off1 = a.p_major ? a.seg2[r] : a.off1[r];
     const u64 *__restrict__ tp2 = a.tp2[r];
@@ -699,8 +707,10 @@ __device__ __forceinline__ void plan_items_body(const PlanArgs &a)
     for (uint32_t tile = 0; tile < P; tile += 2 * PLAN_BLOCK, parity ^= 1) {
         const uint32_t q0 = tile + 2 * threadIdx.x, q1 = q0 + 1;
         const u64 r0 = q0 < P ? rows_of(cr, q0) : 0, r1 = q1 < P ? rows_of(cr, q1) : 0;
-        const u64 s0 = q0 < P ? shape_of(r0, rows_of(cs, q0)) : 0;
-        const u64 s1 = q1 < P ? shape_of(r1, rows_of(cs, q1)) : 0;
+        // (a claimed probe side has no histogram: every partition is planned for its full region of s_cap2 rows, so that no slice of
+        // what pass 2 wrote there exceeds HJ_JOIN_SLICE rows; the join cuts the rows that are there into that many slices)
+        const u64 s0 = q0 < P ? shape_of(r0, a.s_cap2 ? a.s_cap2 : rows_of(cs, q0)) : 0;
+        const u64 s1 = q1 < P ? shape_of(r1, a.s_cap2 ? a.s_cap2 : rows_of(cs, q1)) : 0;
         multi += ((s0 & 0xFFFFFFFFull) && r0 > cap) ? 1u : 0u;
         multi += ((s1 & 0xFFFFFFFFull) && r1 > cap) ? 1u : 0u;
         const u64 n0 = (s0 & 0xFFFFFFFFull) * (s0 >> 32), n1 = (s1 & 0xFFFFFFFFull) * (s1 >> 32);
@@ -802,6 +812,79 @@ int hj_launch_plan(const PlanArgs &a, hipStream_t stream)
     return hipGetLastError() == hipSuccess ? HJGPU_OK : HJGPU_EHIP;
 }
 
+// Pass 2 of a claimed probe side (hj_internal.hpp: hj_launch_claimed_desc).  Every workgroup scans the 2 * F1 segments' tile counts
+// (thread p: the front and back segment of pass-1 partition p), then its waves write the descriptors of every CLAIMED_DESC_BLOCKS-th
+// segment, one lane per tile, as tile_desc_kernel does.
+constexpr int CLAIMED_DESC_BLOCKS = 32;
+__global__ __launch_bounds__(PLAN_BLOCK) void claimed_desc_kernel(const u64 *__restrict__ cursors, u64 cap1, uint32_t F1, uint32_t F2, uint32_t tile2,
+                                                                  uint4 *__restrict__ td, uint32_t tdesc_cap, u64 *__restrict__ total,
+                                                                  uint32_t *overflow)
+{
+    __shared__ u64 scratch[PLAN_BLOCK / 64 + 1];
+    __shared__ u64 seg_b[2 * PLAN_BLOCK], seg_e[2 * PLAN_BLOCK], seg_t[2 * PLAN_BLOCK];     // (F1 <= PLAN_BLOCK: hj_launch_claimed_desc)
+    __shared__ u64 all_tiles;
+    const bool full = *overflow != 0;                   // pass 1 lost tuples: the join is done again exactly, nothing to plan
+    const uint32_t p = threadIdx.x;
+    u64 fb = 0, fe = 0, bb = 0, be = 0;
+    if (p < F1 && !full) {
+        const u64 c = cursors[(u64)p * HJ_LINE_TUPLES];
+        const u64 base = (u64)p * cap1;
+        const u64 front = min(cap1, (u64)HJ_LINE_TUPLES * (uint32_t)c);
+        const u64 back = min(cap1 - front, c >> 32);    // (clamped: never a row outside the region)
+        fb = base; fe = base + front; bb = base + cap1 - back; be = base + cap1;
+    }
+    const u64 tf = hj_tiles_of(fb, fe, 0, tile2), tb = hj_tiles_of(bb, be, 0, tile2);
+    const u64 first = block_exclusive_scan<PLAN_BLOCK, u64>(tf + tb, scratch);
+    if (p < F1) {
+        seg_b[2 * p] = fb; seg_e[2 * p] = fe; seg_t[2 * p] = first;
+        seg_b[2 * p + 1] = bb; seg_e[2 * p + 1] = be; seg_t[2 * p + 1] = first + tf;
+    }
+    if (p == PLAN_BLOCK - 1) all_tiles = first + tf + tb;
+    __syncthreads();
+    const u64 n_tiles = all_tiles;
+    const bool fits = n_tiles <= tdesc_cap;
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        hj_store(total, fits ? n_tiles : (u64)0);
+        if (!fits) atomicOr(overflow, 1u);
+    }
+    if (!fits) return;
+    for (uint32_t i = blockIdx.x * (PLAN_BLOCK / 64) + (threadIdx.x >> 6); i < 2 * F1; i += CLAIMED_DESC_BLOCKS * (PLAN_BLOCK / 64)) {
+        const u64 gb = seg_b[i], ge = seg_e[i], t0 = seg_t[i];
+        const u64 t1 = t0 + hj_tiles_of(gb, ge, 0, tile2);
+        for (u64 t = t0 + (threadIdx.x & 63); t < t1; t += 64) {
+            const u64 g0 = (gb & ~3ull) + (t - t0) * tile2;
+            hj_store(&td[2 * t], make_uint4((uint32_t)gb, (uint32_t)(gb >> 32), (uint32_t)ge, (uint32_t)(ge >> 32)));
+            hj_store(&td[2 * t + 1], make_uint4((uint32_t)g0, (uint32_t)(g0 >> 32), (i / 2) * F2, i / 2));
+        }
+    }
+}
+
+int hj_launch_claimed_desc(const u64 *claim_cursors, u64 cap1, uint32_t F1, uint32_t F2, uint32_t tile2, uint4 *tdesc, uint32_t tdesc_cap,
+                           u64 *total, uint32_t *overflow, hipStream_t stream)
+{
+    if (F1 == 0 || F1 > (uint32_t)PLAN_BLOCK || F1 > HJGPU_MAX_FANOUT || cap1 == 0 || (cap1 & 3) || tile2 == 0) return HJGPU_EINVAL;
+    hipLaunchKernelGGL(claimed_desc_kernel, dim3(CLAIMED_DESC_BLOCKS), dim3(PLAN_BLOCK), 0, stream, claim_cursors, cap1, F1, F2, tile2, tdesc,
+                       tdesc_cap, total, overflow);
+    return hipGetLastError() == hipSuccess ? HJGPU_OK : HJGPU_EHIP;
+}
+
+__global__ __launch_bounds__(256) void claimed_pieces_kernel(const u64 *__restrict__ off2, const u64 *__restrict__ end2, const u64 *__restrict__ cur2,
+                                                             uint32_t P, u64 *__restrict__ pb, u64 *__restrict__ pe)
+{
+    const uint32_t q = blockIdx.x * 256 + threadIdx.x;
+    if (q >= P) return;
+    const u64 b = off2[q], e = end2[q], c = cur2[q];
+    const u64 fe = min(e, b + (u64)HJ_LINE_TUPLES * (uint32_t)c);        // (a full region was flagged: never a row outside it)
+    hj_store(&pb[q], b); hj_store(&pe[q], fe);
+    hj_store(&pb[P + q], max(fe, e - min(e - b, c >> 32))); hj_store(&pe[P + q], e);
+}
+
+int hj_launch_claimed_pieces(const u64 *off2, const u64 *end2, const u64 *cur2, uint32_t P, u64 *pieces_beg, u64 *pieces_end, hipStream_t stream)
+{
+    hipLaunchKernelGGL(claimed_pieces_kernel, dim3((P + 255) / 256), dim3(256), 0, stream, off2, end2, cur2, P, pieces_beg, pieces_end);
+    return hipGetLastError() == hipSuccess ? HJGPU_OK : HJGPU_EHIP;
+}
+
 // Grouped plans on the device (hj_internal.hpp: hj_launch_group_desc): one thread per group.
 __global__ __launch_bounds__(256) void group_desc_kernel(const u64 *__restrict__ roff, const u64 *__restrict__ soff, uint32_t G, uint32_t bins,
                                                          u64 cap_r, u64 cap_s, u64 n_r, u64 n_s, u64 *__restrict__ desc, uint32_t *skew)
@@ -899,10 +982,18 @@ int hj_launch_offsets_to_counts(const u64 *off, u64 *counts, uint32_t P, hipStre
 // NTP: the 8-byte (partial-line) stores are non-temporal too - every launch that is not solo (k6_store8).  A template parameter:
 // as a run-time flag around each store the two branches were merged by the compiler into ONE plain store (the nt hint does not
 // survive the merge; found in the ISA after a run in which "non-temporal" partial stores cost nothing).
-template <int BLOCK, int VPT, bool RANGED, bool IN_PACKED, bool OUT_PACKED, bool CARRY, bool NTP = true>
+//
+// CLAIM (pass 1 of a blocking join's probe side without K4, ScatterArgs::claim_cursors): no range bases.  Partition p owns the
+// region [p * claim_cap, (p + 1) * claim_cap) of the output; its cursor (claim_cursors[16 p], alone on a 128-byte line) counts
+// whole lines claimed from the front | tail tuples claimed from the back << 32.  The carry lives as long as the workgroup: every
+// tile emits whole lines only (one returning atomic per (tile, partition), issued when the counts exist, consumed after the sort),
+// and the workgroup's last < 16 tuples of a partition go to the back of the region when it runs out of tiles.  A claim that
+// would make front and back cross sets *claim_overflow and writes nothing: every store stays inside its partition's region.
+template <int BLOCK, int VPT, bool RANGED, bool IN_PACKED, bool OUT_PACKED, bool CARRY, bool NTP = true, bool CLAIM = false>
 __global__ __launch_bounds__(BLOCK) void scatter_kernel(ScatterArgs a)
 {
     static_assert(!CARRY || (RANGED && OUT_PACKED), "carry needs private cursors and packed output");
+    static_assert(!CLAIM || CARRY, "claimed pass-1 lines need the whole-line carry");
     constexpr int TILE = BLOCK * VPT * 4;
     constexpr int NW = BLOCK / 64;
     constexpr int BPT = (1024 + BLOCK - 1) / BLOCK;                 // max bins per thread (F <= 1024)
@@ -1089,7 +1180,7 @@ __global__ __launch_bounds__(BLOCK) void scatter_kernel(ScatterArgs a)
         }
     };
     for (;;) {
-        if (RANGED && cur.new_range) {
+        if (RANGED && !CLAIM && cur.new_range) {
 #pragma unroll
             for (int i = 0; i < BPT; ++i) {
                 const uint32_t bin = tid * bpt + i;
@@ -1204,17 +1295,28 @@ __global__ __launch_bounds__(BLOCK) void scatter_kernel(ScatterArgs a)
                     // c tuples wait in the carry, cnt[i] are new: emit up to the last line boundary
                     // that [cur0, cur0 + c + cnt) reaches (everything on the range's last tile)
                     const uint32_t c = mycc[i], avail = c + cnt[i];
-                    const u64 cur0 = mycur[i];
                     uint32_t e = avail;
-                    if (!cur.last_in_range) {
-                        const u64 end = (cur0 + avail) & ~(u64)(LINE - 1);
-                        e = end > cur0 ? (uint32_t)(end - cur0) : 0u;
+                    if (CLAIM) {
+                        // whole lines only; the claim (lines | back tuples << 32 before mine) is consumed after the sort
+                        e = avail & ~(LINE - 1);
+                        if (e) {
+                            uint32_t at = bin * LINE;
+                            asm volatile("" : "+v"(at));                // an index the compiler cannot take apart (see opaque_zero_now)
+                            dst[i] = atomicAdd(&a.claim_cursors[at], (u64)(e / LINE));
+                        }
+                        mycc[i] = avail - e;                            // < LINE; what is left at the end goes to the back
+                    } else {
+                        const u64 cur0 = mycur[i];
+                        if (!cur.last_in_range) {
+                            const u64 end = (cur0 + avail) & ~(u64)(LINE - 1);
+                            e = end > cur0 ? (uint32_t)(end - cur0) : 0u;
+                        }
+                        dst[i] = cur0;
+                        mycur[i] = cur0 + e; mycc[i] = avail - e;       // < LINE, and 0 after the range's last tile
                     }
                     if (e) carried[i] = c;                              // e >= c: cur0 + c lies before the boundary
                     else coff[i] = c;                                   // nothing leaves: the new tuples join the carry
                     emitted[i] = e;
-                    dst[i] = cur0;
-                    mycur[i] = cur0 + e; mycc[i] = avail - e;           // < LINE, and 0 after the range's last tile
                 }
             } else if (cnt[i]) {
                 if (RANGED) { dst[i] = mycur[i]; mycur[i] = dst[i] + cnt[i]; }
@@ -1251,8 +1353,10 @@ __global__ __launch_bounds__(BLOCK) void scatter_kernel(ScatterArgs a)
                     const uint32_t fresh = emitted[i] - carried[i];     // new tuples that leave with this tile
                     meta[bin] = emitted[i] | (carried[i] << 16);
                     left[bin] = (run + fresh) | (coff[i] << 16) | ((cnt[i] - fresh) << 20);
-                    delta[bin] = dst[i];
-                    add_units(bin, emitted[i] + ((uint32_t)dst[i] & (LINE - 1)));
+                    if (!CLAIM) {
+                        delta[bin] = dst[i];
+                        add_units(bin, emitted[i] + ((uint32_t)dst[i] & (LINE - 1)));
+                    }
                 } else if (OUT_PACKED) meta[bin] = (!RANGED && a.aligned_claims) ? (cnt[i] & ~(LINE - 1)) : cnt[i];
             }
             run += cnt[i];
@@ -1297,16 +1401,37 @@ __global__ __launch_bounds__(BLOCK) void scatter_kernel(ScatterArgs a)
             }
         }
         // consume the claims (pass 2: the atomics have had the scan and the sort to return) ...
-        if (!CARRY) {
+        if (CLAIM) {
+#pragma unroll
+            for (int i = 0; i < BPT; ++i) {
+                const uint32_t bin = tid * bpt + i;
+                if ((uint32_t)i < bpt && bin < F && emitted[i]) {
+                    const u64 lines = (uint32_t)dst[i], back = dst[i] >> 32;
+                    if ((u64)LINE * lines + emitted[i] + back <= a.claim_cap) {
+                        delta[bin] = (u64)bin * a.claim_cap + (u64)LINE * lines;
+                        add_units(bin, emitted[i]);
+                    } else {
+                        meta[bin] = 0;                                  // the region is full: nothing of this run is written
+                        atomicOr(a.claim_overflow, 1u);
+                    }
+                }
+            }
+        } else if (!CARRY) {
 #pragma unroll
             for (int i = 0; i < BPT; ++i)
                 if (!RANGED && OUT_PACKED && a.aligned_claims) {
                     const uint32_t bin = tid * bpt + i;
                     if ((uint32_t)i < bpt && bin < F) {
                         const uint32_t front = cnt[i] & ~(LINE - 1), tail = cnt[i] & (LINE - 1);
-                        delta[bin] = pstart[i] + (u64)LINE * (uint32_t)dst[i];               // lines claimed before mine
-                        tinfo[bin] = ((pend[i] - (dst[i] >> 32) - tail) << 4) | tail;        // tails fill the back, downwards
-                        add_units(bin, front);
+                        if (a.claim_overflow && (u64)LINE * (uint32_t)dst[i] + front + (dst[i] >> 32) + tail > pend[i] - pstart[i]) {
+                            // an optimistic final region (claimed probe side) is full: front and back would cross - nothing is written
+                            meta[bin] = 0; tinfo[bin] = 0;
+                            atomicOr(a.claim_overflow, 1u);
+                        } else {
+                            delta[bin] = pstart[i] + (u64)LINE * (uint32_t)dst[i];           // lines claimed before mine
+                            tinfo[bin] = ((pend[i] - (dst[i] >> 32) - tail) << 4) | tail;    // tails fill the back, downwards
+                            add_units(bin, front);
+                        }
                     }
                 } else if (cnt[i]) {
                     if (OUT_PACKED) {
@@ -1403,6 +1528,35 @@ __global__ __launch_bounds__(BLOCK) void scatter_kernel(ScatterArgs a)
         have_left = true;
         have_left_or_prev = true;
     }
+    if constexpr (CLAIM) {
+        // the workgroup has no tiles left: the last tile's tails join the carry, and every partition's < 16 waiting tuples are
+        // claimed from the BACK of its region (one returning atomic each), so that the front stays whole lines
+        for (uint32_t idx = tid; idx < F * LINE; idx += BLOCK) {
+            const uint32_t p = idx / LINE, j = idx % LINE;
+            const uint32_t m = left[p];
+            if (j < (m >> 20)) carry[p * LINE + ((m >> 16) & 0xFu) + j] = stage[(m & 0xFFFFu) + j];
+        }
+#pragma unroll
+        for (int i = 0; i < BPT; ++i) {
+            const uint32_t bin = tid * bpt + i;
+            if ((uint32_t)i < bpt && bin < F) {
+                uint32_t n = mycc[i];
+                if (n) {
+                    const u64 c0 = atomicAdd(&a.claim_cursors[bin * LINE], (u64)n << 32);
+                    const u64 lines = (uint32_t)c0, back = c0 >> 32;
+                    if ((u64)LINE * lines + back + n <= a.claim_cap) delta[bin] = (u64)(bin + 1) * a.claim_cap - back - n;
+                    else { n = 0; atomicOr(a.claim_overflow, 1u); }
+                }
+                meta[bin] = n;
+            }
+        }
+        hj_barrier_lds();
+        u64 *__restrict__ out64 = reinterpret_cast<u64 *>(a.kout);
+        for (uint32_t idx = tid; idx < F * LINE; idx += BLOCK) {
+            const uint32_t p = idx / LINE, j = idx % LINE;
+            if (j < meta[p]) k6_store8<NTP>(out64 + delta[p] + j, carry[p * LINE + j]);
+        }
+    }
 }
 
 // ---- geometry of a pass: workgroup size, vectors per thread, whole-line mode -------
@@ -1441,13 +1595,13 @@ int hj_scatter_tile(const HjTuning &t, int pass, uint32_t F, bool out_packed)
     return c.block * c.vpt * 4;
 }
 
-template <int BLOCK, int VPT, bool RANGED, bool IN_PACKED, bool OUT_PACKED, bool CARRY, bool NTP = true>
+template <int BLOCK, int VPT, bool RANGED, bool IN_PACKED, bool OUT_PACKED, bool CARRY, bool NTP = true, bool CLAIM = false>
 static int launch_scatter_t(const ScatterArgs &a, bool want_prof, int cus, hipStream_t stream)
 {
     const size_t lds = scatter_lds(BLOCK, VPT, a.F, CARRY, !RANGED);
     if (lds > HJ_LDS_LIMIT) return HJGPU_EINVAL;
     static HjPerDeviceOnce once;
-    if (hj_allow_dynamic_lds(reinterpret_cast<const void *>(&scatter_kernel<BLOCK, VPT, RANGED, IN_PACKED, OUT_PACKED, CARRY, NTP>),
+    if (hj_allow_dynamic_lds(reinterpret_cast<const void *>(&scatter_kernel<BLOCK, VPT, RANGED, IN_PACKED, OUT_PACKED, CARRY, NTP, CLAIM>),
                              (int)HJ_LDS_LIMIT, &once) != HJGPU_OK)
         return HJGPU_EHIP;
     // persistent grid: as many workgroups per CU as LDS (160 KiB) and threads (2048) allow
@@ -1467,7 +1621,7 @@ static int launch_scatter_t(const ScatterArgs &a, bool want_prof, int cus, hipSt
         (void)hipMemsetAsync(prof, 0, 8 * sizeof(u64), stream);
         b.prof = prof;
     }
-    hipLaunchKernelGGL((scatter_kernel<BLOCK, VPT, RANGED, IN_PACKED, OUT_PACKED, CARRY, NTP>), dim3(grid), dim3(BLOCK), lds, stream, b);
+    hipLaunchKernelGGL((scatter_kernel<BLOCK, VPT, RANGED, IN_PACKED, OUT_PACKED, CARRY, NTP, CLAIM>), dim3(grid), dim3(BLOCK), lds, stream, b);
     if (b.prof) {
         u64 h[8];
         (void)hipMemcpyAsync(h, prof, sizeof(h), hipMemcpyDeviceToHost, stream);
@@ -1504,6 +1658,15 @@ int hj_launch_scatter(const ScatterArgs &a, const HjTuning &t, int cus, hipStrea
     if (a.F == 0 || a.F > HJGPU_MAX_FANOUT) return HJGPU_EINVAL;
     const ScatterConfig c = hj_scatter_config(t, a.ranged ? 1 : 2, a.F, a.out_packed != 0);
     if (a.ranged && a.geom.tile != (uint32_t)(c.block * c.vpt * 4)) return HJGPU_EINVAL;
+    if (a.claim_cursors) {
+        // claimed pass 1 (the probe side of a blocking join): 1024-thread workgroups with the whole-line carry only
+        if (!a.ranged || a.in_packed || !a.out_packed || !c.carry || c.block != 1024 || !a.claim_overflow || !a.claim_cap) return HJGPU_EINVAL;
+        if (c.vpt == 4) return a.nt_partial ? launch_scatter_t<1024, 4, true, false, true, true, true, true>(a, t.scatter_prof, cus, stream)
+                                            : launch_scatter_t<1024, 4, true, false, true, true, false, true>(a, t.scatter_prof, cus, stream);
+        if (c.vpt == 3) return a.nt_partial ? launch_scatter_t<1024, 3, true, false, true, true, true, true>(a, t.scatter_prof, cus, stream)
+                                            : launch_scatter_t<1024, 3, true, false, true, true, false, true>(a, t.scatter_prof, cus, stream);
+        return HJGPU_EINVAL;
+    }
     SCATTER_CASE(1024, 4)
     SCATTER_CASE(1024, 3)
     SCATTER_CASE(1024, 2)
@@ -1561,6 +1724,14 @@ bool hj_tuning_set(HjTuning *t, const char *name, const char *value)
     if (is("placement_log")) return parse_flag(value, &t->placement_log);
     if (is("audit")) return parse_flag(value, &t->audit);
     if (is("solo")) return parse_flag(value, &t->solo);
+    if (is("exact_probe_counts")) return parse_flag(value, &t->exact_probe_counts);
+    if (is("probe_slack")) {
+        char *end = nullptr;
+        const long x = strtol(value, &end, 10);
+        if (end == value || *end || x < 0 || x > 100) return false;
+        t->probe_slack = (int)x;
+        return true;
+    }
     if (is("hist_min_lds")) {
         char *end = nullptr;
         const long x = strtol(value, &end, 10);
@@ -1638,7 +1809,7 @@ bool hj_tuning_set(HjTuning *t, const char *name, const char *value)
 void hj_tuning_from_env(HjTuning *t)
 {
     static const char *const names[] = {"dense2", "npj_refhash", "no_broadcast", "force_chained", "scatter_prof",
-                                        "unique", "merged_plan", "piece_interleave", "range_tiles", "batch_tuples", "group_from", "group_inner", "group_always", "group_device", "group_slack", "host_batch", "placement", "placement_ms", "placement_log", "audit", "solo", "hist_min_lds", "reserve_cus", "join_cfg", "scatter_cfg", "scatter2_cfg"};
+                                        "unique", "merged_plan", "piece_interleave", "range_tiles", "batch_tuples", "group_from", "group_inner", "group_always", "group_device", "group_slack", "host_batch", "placement", "placement_ms", "placement_log", "audit", "solo", "exact_probe_counts", "probe_slack", "hist_min_lds", "reserve_cus", "join_cfg", "scatter_cfg", "scatter2_cfg"};
     for (const char *n : names) {
         char env[64] = "HJGPU_";
         size_t at = strlen(env);

@@ -167,7 +167,9 @@ int  hjgpu_get_device_info(hjgpu_ctx *ctx, hjgpu_device_info *info);
  * "scatter_prof", "merged_plan", "piece_interleave" (0 / 1); "range_tiles" (n); "join_cfg" ("block,log2slots,batch"); "scatter_cfg" /
  * "scatter2_cfg" ("block,vectors[,carry]"); "placement" (candidate allocations for the probe side's pass-1
  * twin, 1..16; "placement_ms": the search's wall-clock budget, default 500, 0 = none; "placement_log" 1: every candidate's fill time on stderr); "batch_tuples" (n, 0 = off); "group_from" / "group_inner" (tuples), "group_always" and "group_device" (0 / 1), "group_slack" (per cent): the
- * grouped plans of hjgpu_phj / hjgpu_cpra (below); "solo" (0 / 1, default 0: the caller promises that nothing else runs on the device beside this context's BLOCKING joins - one process,
+ * grouped plans of hjgpu_phj / hjgpu_cpra (below); "exact_probe_counts" (0 / 1, default 0: a blocking two-pass hjgpu_phj of one chunk
+ * partitions its probe side without the histogram pass, into optimistic regions, and joins again exactly when one is full -
+ * hjgpu_get_counter; 1: always the exact path) and "probe_slack" (per cent of slack in those regions, default 12, 0 = none); "solo" (0 / 1, default 0: the caller promises that nothing else runs on the device beside this context's BLOCKING joins - one process,
  * one stream, as the reference's programs: the joins' partial-line and row stores then stay plain, 4 % faster; without the
  * promise every store that could sit dirty in an L2 is non-temporal, because plain stores ARE lost beside other queues' kernel
  * boundaries: 1.5 in 10^4 steps of the multi-GPU pipeline, DESIGN section 3 "Round 5"); diagnostics: "audit" (0 / 1: every stage of a join leaves a checksum of its output,
@@ -196,6 +198,11 @@ int  hjgpu_audit_recheck(hjgpu_ctx *ctx, uint64_t *words, size_t capacity, size_
  * columns, NPJ table) so that no allocation happens inside a timed join. */
 int  hjgpu_reserve(hjgpu_ctx *ctx, size_t inner_tuples, size_t outer_tuples);
 int  hjgpu_get_stats(hjgpu_ctx *ctx, hjgpu_stats *stats);
+/* Counters of the context (HJGPU_EINVAL for an unknown name):
+ *   "probe_fallbacks"  blocking PHJ joins whose claimed probe side (partitioned without its histogram pass, into optimistic regions)
+ *                      overflowed and that were therefore done again on the exact path; their results are the exact path's
+ *   "probe_exact"      1 when the context's blocking joins take the exact path (option "exact_probe_counts", or after a fallback) */
+int  hjgpu_get_counter(hjgpu_ctx *ctx, const char *name, uint64_t *value);
 
 /* ---- device memory helpers for hosts that do not link HIP (mamalloc/free,
  * npj.cpp:118-126, and the fread targets npj.cpp:1013-1039) ------------------- */
