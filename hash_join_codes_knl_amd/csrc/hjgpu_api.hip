@@ -433,6 +433,72 @@ Pass1Geom make_geom(const HjTuning &tune, const void *keys, size_t n, uint32_t C
     return g;
 }
 
+// ---- launch arguments (hjgpu_ctx.hpp) --------------------------------------------------------------------------------
+// every K6 launch starts here: its partial-line stores are plain only in a solo join (PlainRows), non-temporal in every other
+static ScatterArgs scatter_args(const hjgpu_ctx *ctx)
+{
+    ScatterArgs sa{};
+    sa.nt_partial = ctx->rows_plain ? 0u : 1u;
+    return sa;
+}
+
+ScatterArgs scatter_pass1(const hjgpu_ctx *ctx, const MetaLayout &m, int r, const Pass1Geom &geom, uint32_t F, uint32_t factor,
+                          const uint32_t *kin, const uint32_t *vin, uint32_t *kout, uint32_t *vout)
+{
+    ScatterArgs sa = scatter_args(ctx);
+    sa.kin = kin; sa.vin = vin; sa.kout = kout; sa.vout = vout;
+    sa.in_packed = 0; sa.out_packed = vout ? 0u : 1u;
+    sa.seg_off = m.seg1[r]; sa.tile_prefix = m.tp1[r]; sa.cursors = m.cur1[r];
+    sa.nseg = geom.chunks; sa.F = F; sa.factor = factor; sa.in_align = align_of(kin);
+    sa.ranged = 1; sa.work_counter = m.tickets + HJ_TICKET_K6 + 2 * r; sa.geom = geom; sa.range_base = m.range_base[r];
+    return sa;
+}
+
+// K6 pass 2 of relation r: packed tuples `in` -> `out`, one segment per (chunk, pass-1 partition) of the layout, rows placed by the atomic
+// cursors cur2 (aligned: whole lines claimed, final partitions line-aligned)
+static ScatterArgs scatter_pass2(const hjgpu_ctx *ctx, const MetaLayout &m, int r, const Pass1Geom &geom, const PhjPlan &pl, bool aligned,
+                                 const uint32_t *in, uint32_t *out)
+{
+    ScatterArgs sa = scatter_args(ctx);
+    sa.kin = in; sa.kout = out;
+    sa.in_packed = 1; sa.out_packed = 1;
+    sa.seg_off = m.off1[r]; sa.tile_prefix = m.tp2[r]; sa.cursors = m.cur2[r]; sa.tile_desc = m.tdesc[r];
+    sa.nseg = pl.C * pl.F1; sa.F = pl.F2; sa.factor = pl.f2;
+    sa.work_counter = m.tickets + HJ_TICKET_K6 + 2 * r + 1; sa.geom = geom;
+    sa.part_start = m.off2[r]; sa.part_end = m.end2[r]; sa.aligned_claims = aligned ? 1u : 0u;
+    return sa;
+}
+
+PlanArgs plan_args(const hjgpu_ctx *ctx, const MetaLayout &m, uint32_t C, uint32_t F1, uint32_t F2, uint32_t tile1, uint32_t tile2, bool unique,
+                   uint32_t mask)
+{
+    PlanArgs pa{};
+    for (int r = 0; r < 2; ++r) {
+        pa.counts[r] = m.counts[r]; pa.off2[r] = m.off2[r]; pa.end2[r] = m.end2[r]; pa.cur2[r] = m.cur2[r];
+        pa.off1[r] = m.off1[r]; pa.cur1[r] = m.cur1[r]; pa.tp1[r] = m.tp1[r];
+        pa.seg1[r] = m.seg1[r]; pa.tp2[r] = m.tp2[r];
+    }
+    pa.slice_prefix = m.slice_prefix; pa.slices = m.slices; pa.item_part = m.item_part;
+    pa.chunks = C; pa.F1 = F1; pa.F2 = F2; pa.tile1 = tile1; pa.tile2 = tile2;
+    pa.slice = HJ_JOIN_SLICE; pa.cap = (uint32_t)ctx->tune.join.cap(); pa.unique = unique ? 1u : 0u; pa.mask = mask;
+    return pa;
+}
+
+void join_output(const hjgpu_ctx *ctx, JoinArgs &ja, const hjgpu_output *out, u64 bs, u64 bl, DevState *st)
+{
+    if (!bs) return;
+    ja.ok = out->d_keys; ja.oov = out->d_outer_vals; ja.oiv = out->d_inner_vals;
+    ja.block_size = bs; ja.block_limit = bl; ja.block_counter = &st->block_counter;
+    ja.final_offsets = (u64 *)ctx->final_offsets.p; ja.overflow = &st->overflow;
+    ja.nt_rows = ctx->rows_plain ? 0u : 1u;        // plain result rows only in a solo join (PlainRows)
+}
+
+int close_gaps(hjgpu_ctx *ctx, const hjgpu_output *out, uint32_t workers, u64 bs, DevState *st, hipStream_t stream)
+{
+    return hj_launch_close_gaps_ex(out->d_keys, out->d_outer_vals, out->d_inner_vals, (const u64 *)ctx->final_offsets.p, workers, bs,
+                                   &st->block_counter, &st->overflow, ctx->moves.p, &st->nmoves, &st->dense, ctx->cus, stream);
+}
+
 // ---------------------------------------------------------------------------
 // PHJ / CPRA: fused histogram -> plan -> scatter x2 -> LDS join
 // ---------------------------------------------------------------------------
@@ -561,8 +627,9 @@ int phj_enqueue(hjgpu_ctx *ctx, const PhjPlan &pl,
     if ((pre != nullptr) != (pl.pre != 0)) return fail(ctx, HJGPU_EINVAL, "internal: plan and relations disagree about pre-partitioning");
     MetaLayout m = carve(ctx->meta.p, pl.C, pl.F1, pl.P, pl.ranges, pl.items_extra, pl.tiles2, pl.batch_cap, pl.tdesc_b_cap);
     DevState *st = reinterpret_cast<DevState *>(ctx->state.p);
+    const uint32_t workers = (uint32_t)hj_join_workers(ctx->tune, ctx->cus, pl.big_tables, pl.unique);
     u64 bs = 0, bl = 0;
-    CHK(setup_output(ctx, out, (uint32_t)hj_join_workers(ctx->tune, ctx->cus, pl.big_tables, pl.unique), &bs, &bl));
+    CHK(setup_output(ctx, out, workers, &bs, &bl));
 
     record(ctx, EV_BEGIN, stream);
     u64 *audit = nullptr;                // option "audit": this call's record (else NULL: nothing below is enqueued)
@@ -596,18 +663,13 @@ int phj_enqueue(hjgpu_ctx *ctx, const PhjPlan &pl,
     const size_t nn[2] = {inner, outer};
     uint32_t *t1[4] = {(uint32_t *)ctx->tmp[0].p, nullptr, (uint32_t *)ctx->tmp[2].p, nullptr};
     uint32_t *t2[4] = {(uint32_t *)ctx->tmp[4].p, nullptr, (uint32_t *)ctx->tmp[6].p, nullptr};
-    PlanArgs pa;
-    for (int r = 0; r < 2; ++r) {
-        pa.counts[r] = m.counts[r]; pa.off2[r] = m.off2[r]; pa.end2[r] = m.end2[r]; pa.cur2[r] = m.cur2[r];
-        pa.off1[r] = m.off1[r]; pa.cur1[r] = m.cur1[r]; pa.tp1[r] = m.tp1[r];
-        pa.seg1[r] = m.seg1[r]; pa.tp2[r] = m.tp2[r]; pa.tdesc[r] = m.tdesc[r];
-        pa.seg2[r] = m.seg2[r];
-        pa.more[r] = m.more[r];
-    }
+    PlanArgs pa = plan_args(ctx, m, pl.C, pl.F1, pl.F2, (uint32_t)hj_scatter_tile(ctx->tune, 1, pl.F1, true),
+                            (uint32_t)hj_scatter_tile(ctx->tune, 2, pl.F2, true), pl.unique, 0u);
+    pa.cap = (uint32_t)hj_join_config_of(ctx->tune, pl.big_tables).cap();
+    for (int r = 0; r < 2; ++r) { pa.tdesc[r] = m.tdesc[r]; pa.seg2[r] = m.seg2[r]; pa.more[r] = m.more[r]; }
     pa.tdesc_cap = (uint32_t)m.tdesc_cap;
     const u64 *dyn[2] = {grp ? grp->desc : nullptr, grp ? grp->desc + 2 : nullptr};           // {first row, rows} of R / S in device memory
     pa.dyn[0] = dyn[0]; pa.dyn[1] = dyn[1];
-    pa.unique = pl.unique ? 1u : 0u;
     pa.multi_fill = m.tickets + HJ_TICKET_MULTI_FILL;          // zeroed with the tickets; counted by the work-item plan, read by the _UNIQUE join
     // two-pass plans: final partitions start on 128-byte lines (pass 2 claims whole lines); option "dense2": dense
     const bool pad2 = pl.F2 > 1 && !ctx->tune.dense2;
@@ -625,12 +687,7 @@ int phj_enqueue(hjgpu_ctx *ctx, const PhjPlan &pl,
         pa.regular[r] = pieces ? 0u : 1u; pa.chunk_part[r] = geom[r].part;
         for (uint32_t c = 0; c < 9; ++c) pa.chunk_beg[r][c] = pieces ? pre->ch[r].b[c <= pl.C ? c : pl.C] : geom[r].beg(c);
     }
-    pa.slice_prefix = m.slice_prefix; pa.slices = m.slices; pa.item_part = m.item_part;
-    pa.chunks = pl.C; pa.F1 = pl.F1; pa.F2 = pl.F2;
     pa.in_align[0] = pre ? 0u : align_of(rk); pa.in_align[1] = pre ? 0u : align_of(sk);
-    pa.tile1 = (uint32_t)hj_scatter_tile(ctx->tune, 1, pl.F1, true); pa.tile2 = (uint32_t)hj_scatter_tile(ctx->tune, 2, pl.F2, true);
-    pa.slice = HJ_JOIN_SLICE;
-    pa.cap = (uint32_t)hj_join_config_of(ctx->tune, pl.big_tables).cap();
 
     uint32_t batches_used = 0;
     // option "audit" (audit_kernels.hip): stage 0 / 3 the relation as it is read, 1 / 4 its pass-1 output, 2 / 5 its final partitions
@@ -669,14 +726,7 @@ int phj_enqueue(hjgpu_ctx *ctx, const PhjPlan &pl,
     if (claim) pa.s_cap2 = pl.cap2;
     auto pass1 = [&](int r) -> int {       // K6 pass 1: caller's columns -> tmp[0..3]
         if (!nn[r]) return HJGPU_OK;
-        ScatterArgs sa;
-        memset(&sa, 0, sizeof(sa));
-        sa.kin = in_k[r]; sa.vin = in_v[r]; sa.kout = t1[2 * r]; sa.vout = t1[2 * r + 1];
-        sa.seg_off = m.seg1[r]; sa.tile_prefix = m.tp1[r]; sa.cursors = m.cur1[r];
-        sa.nseg = pl.C; sa.F = pl.F1; sa.factor = pl.f1; sa.in_align = align_of(in_k[r]);
-        sa.ranged = 1; sa.work_counter = m.tickets + HJ_TICKET_K6 + 2 * r; sa.geom = geom[r]; sa.range_base = m.range_base[r];
-        sa.in_packed = 0; sa.out_packed = 1;
-        sa.nt_partial = ctx->rows_plain ? 0u : 1u;
+        ScatterArgs sa = scatter_pass1(ctx, m, r, geom[r], pl.F1, pl.f1, in_k[r], in_v[r], t1[2 * r], t1[2 * r + 1]);
         sa.dyn = dyn[r];
         if (claim && r == 1) {
             sa.range_base = nullptr;
@@ -684,17 +734,18 @@ int phj_enqueue(hjgpu_ctx *ctx, const PhjPlan &pl,
         }
         return hj_launch_scatter(sa, ctx->tune, scatter_cus(ctx), stream);
     };
-    auto pass2 = [&](int r) -> int {       // K6 pass 2: tmp[0..3] -> tmp[4..7], one segment per (chunk, pass-1 partition)
+    // K6 pass 2: packed tuples `in` -> tmp[4..7] - pass 1's output in tmp[0..3], the pieces of a pre-partitioned relation, or the buffer of
+    // one batch of the probe side (batch >= 0)
+    auto pass2 = [&](int r, const uint32_t *in, int batch) -> int {
         if (!nn[r] || pl.F2 <= 1) return HJGPU_OK;
-        ScatterArgs sa;
-        memset(&sa, 0, sizeof(sa));
-        sa.kin = t1[2 * r]; sa.vin = t1[2 * r + 1]; sa.kout = t2[2 * r]; sa.vout = t2[2 * r + 1];
-        sa.seg_off = p_major ? m.seg2[r] : m.off1[r]; sa.tile_prefix = m.tp2[r]; sa.cursors = m.cur2[r]; sa.tile_desc = m.tdesc[r];
-        sa.nseg = p_major ? pl.F1 : pl.C * pl.F1; sa.F = pl.F2; sa.factor = pl.f2; sa.in_align = 0;
-        sa.ranged = 0; sa.work_counter = m.tickets + HJ_TICKET_K6 + 2 * r + 1; sa.geom = geom[r]; sa.range_base = nullptr;
-        sa.part_start = m.off2[r]; sa.part_end = m.end2[r]; sa.aligned_claims = pad2 ? 1u : 0u;
-        sa.in_packed = 1; sa.out_packed = 1;
-        sa.nt_partial = ctx->rows_plain ? 0u : 1u;
+        ScatterArgs sa = scatter_pass2(ctx, m, r, geom[r], pl, pad2, in, t2[2 * r]);
+        if (p_major) { sa.seg_off = m.seg2[r]; sa.nseg = pl.F1; }     // one segment per pass-1 partition
+        if (batch >= 0) {
+            // the batch's own pass-1 layout, pass-2 tiles and ticket
+            const size_t b = (size_t)batch;
+            sa.seg_off = m.boff + b * (pl.F1 + 1); sa.tile_prefix = m.tp2b + b * (pl.F1 + 1);
+            sa.tile_desc = m.tdescb + b * pl.tdesc_b_cap * 2; sa.nseg = pl.F1; sa.work_counter = m.btickets + 2 * b + 1;
+        }
         if (claim && r == 1) {
             // the tiles hj_launch_claimed_desc planned from pass 1's cursors; regions that fill up flag the join
             sa.tile_prefix = m.claim_total; sa.nseg = 0; sa.seg_off = nullptr;
@@ -717,18 +768,7 @@ int phj_enqueue(hjgpu_ctx *ctx, const PhjPlan &pl,
             CHK(hj_launch_plan(pa, stream));
             record(ctx, ev[1], stream);
             record(ctx, ev[2], stream);
-            if (nn[r]) {
-                ScatterArgs sa;
-                memset(&sa, 0, sizeof(sa));
-                sa.kin = reinterpret_cast<const uint32_t *>(pre->tuples[r]); sa.vin = nullptr; sa.kout = t2[2 * r]; sa.vout = t2[2 * r + 1];
-                sa.seg_off = m.off1[r]; sa.tile_prefix = m.tp2[r]; sa.cursors = m.cur2[r]; sa.tile_desc = m.tdesc[r];
-                sa.nseg = pl.C * pl.F1; sa.F = pl.F2; sa.factor = pl.f2; sa.in_align = 0;
-                sa.ranged = 0; sa.work_counter = m.tickets + HJ_TICKET_K6 + 2 * r + 1; sa.geom = geom[r]; sa.range_base = nullptr;
-                sa.part_start = m.off2[r]; sa.part_end = m.end2[r]; sa.aligned_claims = pad2 ? 1u : 0u;
-                sa.in_packed = 1; sa.out_packed = 1;
-                sa.nt_partial = ctx->rows_plain ? 0u : 1u;
-                CHK(hj_launch_scatter(sa, ctx->tune, scatter_cus(ctx), stream));
-            }
+            CHK(pass2(r, reinterpret_cast<const uint32_t *>(pre->tuples[r]), -1));
             record(ctx, ev[3], stream);
             CHK(audit_input(r)); CHK(audit_final(r));
             return HJGPU_OK;
@@ -757,29 +797,14 @@ int phj_enqueue(hjgpu_ctx *ctx, const PhjPlan &pl,
             record(ctx, ev[1], stream);
             for (uint32_t b = 0; b < batches; ++b) {
                 uint32_t *tbuf = (uint32_t *)ctx->tmp[1 + 2 * (b & 1)].p;
-                ScatterArgs sa;
-                memset(&sa, 0, sizeof(sa));
                 // pass 1 of the batch: the caller's columns -> the batch buffer (dense, from offset 0)
-                sa.kin = in_k[r]; sa.vin = in_v[r]; sa.kout = tbuf; sa.vout = nullptr;
-                sa.seg_off = m.seg1[r]; sa.tile_prefix = m.tp1[r]; sa.cursors = m.cur1[r];
-                sa.nseg = 1; sa.F = pl.F1; sa.factor = pl.f1; sa.in_align = align_of(in_k[r]);
-                sa.ranged = 1; sa.work_counter = m.btickets + 2 * b; sa.geom = geom[r]; sa.range_base = m.range_base[r];
+                ScatterArgs sa = scatter_pass1(ctx, m, r, geom[r], pl.F1, pl.f1, in_k[r], in_v[r], tbuf, nullptr);
+                sa.work_counter = m.btickets + 2 * b;
                 sa.range_begin = b * pl.batch_ranges;
                 sa.range_count = std::min(pl.batch_ranges, geom[r].ranges_per_chunk - sa.range_begin);
-                sa.in_packed = 0; sa.out_packed = 1;
-                sa.nt_partial = ctx->rows_plain ? 0u : 1u;
                 CHK(hj_launch_scatter(sa, ctx->tune, scatter_cus(ctx), stream));
                 // pass 2 of the batch: the batch buffer -> the relation's final, line-aligned partitions
-                memset(&sa, 0, sizeof(sa));
-                sa.kin = tbuf; sa.vin = nullptr; sa.kout = t2[2 * r]; sa.vout = t2[2 * r + 1];
-                sa.seg_off = m.boff + (size_t)b * (pl.F1 + 1); sa.tile_prefix = m.tp2b + (size_t)b * (pl.F1 + 1);
-                sa.cursors = m.cur2[r]; sa.tile_desc = m.tdescb + (size_t)b * pl.tdesc_b_cap * 2;
-                sa.nseg = pl.F1; sa.F = pl.F2; sa.factor = pl.f2; sa.in_align = 0;
-                sa.ranged = 0; sa.work_counter = m.btickets + 2 * b + 1; sa.geom = geom[r]; sa.range_base = nullptr;
-                sa.part_start = m.off2[r]; sa.part_end = m.end2[r]; sa.aligned_claims = 1u;
-                sa.in_packed = 1; sa.out_packed = 1;
-                sa.nt_partial = ctx->rows_plain ? 0u : 1u;
-                CHK(hj_launch_scatter(sa, ctx->tune, scatter_cus(ctx), stream));
+                CHK(pass2(r, tbuf, (int)b));
             }
             record(ctx, ev[2], stream);         // both passes interleaved: reported as pass 1, pass 2 = 0
             record(ctx, ev[3], stream);
@@ -791,7 +816,7 @@ int phj_enqueue(hjgpu_ctx *ctx, const PhjPlan &pl,
         record(ctx, ev[1], stream);
         CHK(pass1(r));
         record(ctx, ev[2], stream);
-        CHK(pass2(r));
+        CHK(pass2(r, t1[2 * r], -1));
         record(ctx, ev[3], stream);
         CHK(audit_input(r)); CHK(audit_pass1(r)); CHK(audit_final(r));
         return HJGPU_OK;
@@ -817,7 +842,7 @@ int phj_enqueue(hjgpu_ctx *ctx, const PhjPlan &pl,
             CHK(hj_launch_claimed_desc(m.claim1, pl.cap1, pl.F1, pl.F2, pa.tile2, m.tdesc[1], (uint32_t)m.tdesc_cap, m.claim_total,
                                        &st->probe_overflow, stream));
         record(ctx, EV_S_SC1, stream);
-        CHK(pass2(0)); CHK(pass2(1));
+        CHK(pass2(0, t1[0], -1)); CHK(pass2(1, t1[2], -1));
         record(ctx, EV_S_SC2, stream);
         record(ctx, EV_WAITED, stream);
         for (int e : ev_r) record(ctx, e, stream);
@@ -842,8 +867,7 @@ int phj_enqueue(hjgpu_ctx *ctx, const PhjPlan &pl,
 
     // K7+K8
     if (inner && outer && mode != PHJ_BUILD_ONLY) {
-        JoinArgs ja;
-        memset(&ja, 0, sizeof(ja));
+        JoinArgs ja{};
         ja.rk = fin[0]; ja.rv = fin[1]; ja.sk = fin[2]; ja.sv = fin[3];
         ja.roff = m.off2[0]; ja.soff = m.off2[1];
         ja.rend = m.end2[0]; ja.send = m.end2[1];
@@ -868,24 +892,12 @@ int phj_enqueue(hjgpu_ctx *ctx, const PhjPlan &pl,
         ja.work_counter2 = reinterpret_cast<u64 *>(m.tickets + HJ_TICKET_JOIN2);
         ja.multi_fill = m.tickets + HJ_TICKET_MULTI_FILL;
         ja.resume = grp ? 1u : 0u;
-        if (bs) {
-            ja.ok = out->d_keys; ja.oov = out->d_outer_vals; ja.oiv = out->d_inner_vals;
-            ja.block_size = bs; ja.block_limit = bl;
-            ja.block_counter = &st->block_counter;
-            ja.final_offsets = (u64 *)ctx->final_offsets.p;
-            ja.overflow = &st->overflow;
-            ja.nt_rows = ctx->rows_plain ? 0u : 1u;
-        }
+        join_output(ctx, ja, out, bs, bl, st);
         CHK(hj_launch_join(ja, ctx->tune, ctx->cus, stream));
         if (audit) CHK(hj_audit_copy(reinterpret_cast<const u64 *>(&st->result), audit + 4 * 6, 4, stream));
     }
     record(ctx, EV_JOIN, stream);
-    if (bs && inner && outer && mode != PHJ_BUILD_ONLY && !grp) {
-        CHK(hj_launch_close_gaps_ex(out->d_keys, out->d_outer_vals, out->d_inner_vals,
-                                    (const u64 *)ctx->final_offsets.p,
-                                    (uint32_t)hj_join_workers(ctx->tune, ctx->cus, pl.big_tables, pl.unique), bs, &st->block_counter,
-                                    &st->overflow, ctx->moves.p, &st->nmoves, &st->dense, ctx->cus, stream));
-    }
+    if (bs && inner && outer && mode != PHJ_BUILD_ONLY && !grp) CHK(close_gaps(ctx, out, workers, bs, st, stream));
     record(ctx, EV_GAPS, stream);
     ctx->stats.fanout1 = pl.F1; ctx->stats.fanout2 = pl.F2; ctx->stats.buckets = 0; ctx->stats.batches = batches_used;
     ctx->last_algo = 1;
@@ -902,11 +914,18 @@ static int finish_from(hjgpu_ctx *ctx, const DevState &h, hjgpu_result *result, 
     return HJGPU_OK;
 }
 
+// the join's DevState on the host, once the stream has done everything enqueued before
+static int read_state(hjgpu_ctx *ctx, DevState &h, hipStream_t stream)
+{
+    HIPCHK(ctx, hipMemcpyAsync(&h, ctx->state.p, sizeof(DevState), hipMemcpyDeviceToHost, stream));
+    HIPCHK(ctx, hipStreamSynchronize(stream));
+    return HJGPU_OK;
+}
+
 int finish_blocking(hjgpu_ctx *ctx, hjgpu_result *result, const hjgpu_output *out, hipStream_t stream)
 {
     DevState h;
-    HIPCHK(ctx, hipMemcpyAsync(&h, ctx->state.p, sizeof(DevState), hipMemcpyDeviceToHost, stream));
-    HIPCHK(ctx, hipStreamSynchronize(stream));
+    CHK(read_state(ctx, h, stream));
     return finish_from(ctx, h, result, out);
 }
 
@@ -965,12 +984,7 @@ int npj_probe_enqueue(hjgpu_ctx *ctx, const uint32_t *sk, const uint32_t *sv, si
         CHK(hj_launch_npj_probe(pa, ctx->cus, stream, nullptr));
     }
     record(ctx, EV_JOIN, stream);
-    if (bs && outer) {
-        CHK(hj_launch_close_gaps_ex(out->d_keys, out->d_outer_vals, out->d_inner_vals,
-                                    (const u64 *)ctx->final_offsets.p, (uint32_t)grid * 4, bs,
-                                    &st->block_counter, &st->overflow, ctx->moves.p, &st->nmoves, &st->dense,
-                                    ctx->cus, stream));
-    }
+    if (bs && outer) CHK(close_gaps(ctx, out, (uint32_t)grid * 4, bs, st, stream));
     record(ctx, EV_GAPS, stream);
     return HJGPU_OK;
 }
@@ -1248,8 +1262,7 @@ int hjgpu_get_async_status(hjgpu_ctx *ctx, void *stream_)
     hipStream_t stream = (hipStream_t)stream_;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     DevState h;
-    HIPCHK(ctx, hipMemcpyAsync(&h, ctx->state.p, sizeof(DevState), hipMemcpyDeviceToHost, stream));
-    HIPCHK(ctx, hipStreamSynchronize(stream));
+    CHK(read_state(ctx, h, stream));
     if (ctx->grp_last.valid && h.group_skew) {
         // the device-planned grouped join skipped a group that was larger than its workspace (its d_result says so: all ones): the same
         // join again, host-planned - this thread waits for pass 0 and for every group - with the result where the caller expects it
@@ -1265,8 +1278,7 @@ int hjgpu_get_async_status(hjgpu_ctx *ctx, void *stream_)
             CHK(phj_enqueue(ctx, pl, c.rk, c.rv, c.inner, c.sk, c.sv, c.outer, out, stream));
         }
         if (c.d_result) HIPCHK(ctx, hj_copy_async(c.d_result, ctx->state.p, sizeof(hjgpu_result), stream));
-        HIPCHK(ctx, hipMemcpyAsync(&h, ctx->state.p, sizeof(DevState), hipMemcpyDeviceToHost, stream));
-        HIPCHK(ctx, hipStreamSynchronize(stream));
+        CHK(read_state(ctx, h, stream));
     }
     if (h.zero_key) return fail(ctx, HJGPU_EZEROKEY, "NPJ: a build key is 0, the empty-bucket sentinel");
     if (h.overflow) return fail(ctx, HJGPU_EOVERFLOW, "materialised output exceeded its capacity");
@@ -1533,8 +1545,9 @@ static int broadcast_enqueue(hjgpu_ctx *ctx, const uint32_t *rk, const uint32_t 
     bm.sentinel = reinterpret_cast<uint32_t *>(d + 8);
     uint32_t *item_part = reinterpret_cast<uint32_t *>(d + 16);
     DevState *st = reinterpret_cast<DevState *>(ctx->state.p);
+    const uint32_t workers = (uint32_t)hj_join_workers(ctx->tune, ctx->cus, big, unique);
     u64 bs = 0, bl = 0;
-    CHK(setup_output(ctx, out, (uint32_t)hj_join_workers(ctx->tune, ctx->cus, big, unique), &bs, &bl));
+    CHK(setup_output(ctx, out, workers, &bs, &bl));
 
     record(ctx, EV_BEGIN, stream);
     HIPCHK(ctx, hj_zero_async(st, sizeof(DevState), stream));
@@ -1545,8 +1558,7 @@ static int broadcast_enqueue(hjgpu_ctx *ctx, const uint32_t *rk, const uint32_t 
     record(ctx, EV_R_HIST, stream);
     CHK(hj_launch_broadcast_meta(rk, inner, outer, (uint32_t)nslices, (uint32_t)groups, bm, stream));
     for (int e : {EV_R_PLAN, EV_R_SC1, EV_R_SC2}) record(ctx, e, stream);
-    JoinArgs ja;
-    memset(&ja, 0, sizeof(ja));
+    JoinArgs ja{};
     ja.rk = rk; ja.rv = rv; ja.sk = sk; ja.sv = sv;
     ja.roff = bm.roff; ja.rend = bm.rend; ja.soff = bm.soff; ja.send = bm.send;
     ja.slice_prefix = bm.slice_prefix; ja.slices = bm.slices; ja.item_part = item_part;
@@ -1556,19 +1568,10 @@ static int broadcast_enqueue(hjgpu_ctx *ctx, const uint32_t *rk, const uint32_t 
     ja.broadcast = 1; ja.sentinel = bm.sentinel; ja.big_tables = big ? 1u : 0u; ja.unique = unique ? 1u : 0u;
     ja.result = &st->result; ja.work_counter = &st->work_counter; ja.work_counter2 = &st->work_counter2;
     ja.multi_fill = &st->pad;                           // always 0: a broadcast join's build side is one table fill by construction
-    if (bs) {
-        ja.ok = out->d_keys; ja.oov = out->d_outer_vals; ja.oiv = out->d_inner_vals;
-        ja.block_size = bs; ja.block_limit = bl; ja.block_counter = &st->block_counter;
-        ja.final_offsets = (u64 *)ctx->final_offsets.p; ja.overflow = &st->overflow;
-        ja.nt_rows = ctx->rows_plain ? 0u : 1u;
-    }
+    join_output(ctx, ja, out, bs, bl, st);
     CHK(hj_launch_join(ja, ctx->tune, ctx->cus, stream));
     record(ctx, EV_JOIN, stream);
-    if (bs)
-        CHK(hj_launch_close_gaps_ex(out->d_keys, out->d_outer_vals, out->d_inner_vals,
-                                    (const u64 *)ctx->final_offsets.p, (uint32_t)hj_join_workers(ctx->tune, ctx->cus, big, unique), bs,
-                                    &st->block_counter, &st->overflow, ctx->moves.p, &st->nmoves, &st->dense,
-                                    ctx->cus, stream));
+    if (bs) CHK(close_gaps(ctx, out, workers, bs, st, stream));
     record(ctx, EV_GAPS, stream);
     ctx->stats.fanout1 = 1; ctx->stats.fanout2 = 1; ctx->stats.buckets = 0; ctx->stats.batches = 0;
     ctx->last_algo = 1;
@@ -1584,6 +1587,15 @@ static int broadcast_enqueue(hjgpu_ctx *ctx, const uint32_t *rk, const uint32_t 
 // group on a 128-byte line so that its columns can be handed to the two-pass plan as they are), then the groups are joined
 // one after the other by the plain plan, and their aggregates (and rows) added up.  One more read + write of both
 // relations buys single-fill tables in every group.
+// Pass 0 must split by a hash that is independent of the groups' own two passes: with the same multiplier every key of a group would fall into
+// 1 / G of the pass-1 partitions (SURVEY appendix A "Factor independence")
+static uint32_t pass0_factor(const hjgpu_phj_params *prm)
+{
+    const uint32_t f1 = (prm && prm->factor1) ? prm->factor1 : DEFAULT_F1, f2 = (prm && prm->factor2) ? prm->factor2 : DEFAULT_F2;
+    for (uint32_t cand : {0x7FEB352Du, 0x846CA68Bu, 0xC6A4A793u}) if (cand != f1 && cand != f2) return cand;
+    return DEFAULT_F0;
+}
+
 static int phj_grouped(hjgpu_ctx *ctx, uint32_t G, uint32_t chunks,
                        const uint32_t *rk, const uint32_t *rv, size_t inner,
                        const uint32_t *sk, const uint32_t *sv, size_t outer,
@@ -1600,18 +1612,12 @@ static int phj_grouped(hjgpu_ctx *ctx, uint32_t G, uint32_t chunks,
     hjgpu_stats sum, one;
     memset(&sum, 0, sizeof(sum));
     // pass 0: the probe side first, like the join itself (a build side that is still arriving is not supported here)
-    // pass 0 must split by a hash that is independent of the groups' own two passes: with the same multiplier every key of a
-    // group would fall into 1 / G of the pass-1 partitions (SURVEY appendix A "Factor independence")
-    uint32_t f0 = DEFAULT_F0;
-    {
-        const uint32_t f1 = (prm && prm->factor1) ? prm->factor1 : DEFAULT_F1, f2 = (prm && prm->factor2) ? prm->factor2 : DEFAULT_F2;
-        const uint32_t other[3] = {0x7FEB352Du, 0x846CA68Bu, 0xC6A4A793u};
-        for (uint32_t cand : other) if (cand != f1 && cand != f2) { f0 = cand; break; }
-    }
-    CHK(partition_columns(ctx, sk, sv, outer, f0, l.F0, l.bins, g_sk, g_sv, reinterpret_cast<uint64_t *>(d_off + (l.F0 + 1)), stream));
+    const uint32_t f0 = pass0_factor(prm);
+    const PartitionForm pass0 = {.group_bins = l.bins};
+    CHK(partition_op(ctx, sk, sv, outer, f0, l.F0, g_sk, g_sv, reinterpret_cast<uint64_t *>(d_off + (l.F0 + 1)), pass0, stream));
     CHK(hjgpu_get_stats(ctx, &one));
     sum.ms_scatter0 += one.ms_total;
-    CHK(partition_columns(ctx, rk, rv, inner, f0, l.F0, l.bins, g_rk, g_rv, reinterpret_cast<uint64_t *>(d_off), stream));
+    CHK(partition_op(ctx, rk, rv, inner, f0, l.F0, g_rk, g_rv, reinterpret_cast<uint64_t *>(d_off), pass0, stream));
     std::vector<u64> off((size_t)2 * (l.F0 + 1));
     HIPCHK(ctx, hipMemcpyAsync(off.data(), d_off, off.size() * sizeof(u64), hipMemcpyDeviceToHost, stream));
     CHK(hjgpu_get_stats(ctx, &one));                        // waits for the operator's last event
@@ -1653,8 +1659,7 @@ static int phj_grouped(hjgpu_ctx *ctx, uint32_t G, uint32_t chunks,
         CHK(phj_enqueue(ctx, pl, g_rk + pc[g].r0, g_rv + pc[g].r0, pc[g].rn, g_sk + pc[g].s0, g_sv + pc[g].s0, pc[g].sn,
                         vout, stream));
         DevState h;
-        HIPCHK(ctx, hipMemcpyAsync(&h, ctx->state.p, sizeof(DevState), hipMemcpyDeviceToHost, stream));
-        HIPCHK(ctx, hipStreamSynchronize(stream));
+        CHK(read_state(ctx, h, stream));
         CHK(hjgpu_get_stats(ctx, &one));
         sum.ms_histogram += one.ms_histogram; sum.ms_plan += one.ms_plan; sum.ms_scatter1 += one.ms_scatter1;
         sum.ms_scatter2 += one.ms_scatter2; sum.ms_join += one.ms_join; sum.ms_close_gaps += one.ms_close_gaps;
@@ -1721,20 +1726,16 @@ static int phj_grouped_device(hjgpu_ctx *ctx, uint32_t G, uint32_t chunks,
     uint32_t *g_sk = (uint32_t *)ctx->grp[2].p, *g_sv = (uint32_t *)ctx->grp[3].p;
     u64 *d_off = (u64 *)ctx->grp_off.p, *d_desc = d_off + (size_t)2 * (l.F0 + 1);
     DevState *st = reinterpret_cast<DevState *>(ctx->state.p);
-    uint32_t f0 = DEFAULT_F0;           // pass 0 splits by a hash independent of the groups' own two passes (see phj_grouped)
-    {
-        const uint32_t f1 = (prm && prm->factor1) ? prm->factor1 : DEFAULT_F1, f2 = (prm && prm->factor2) ? prm->factor2 : DEFAULT_F2;
-        const uint32_t other[3] = {0x7FEB352Du, 0x846CA68Bu, 0xC6A4A793u};
-        for (uint32_t cand : other) if (cand != f1 && cand != f2) { f0 = cand; break; }
-    }
+    const uint32_t f0 = pass0_factor(prm);
+    const PartitionForm pass0 = {.group_bins = l.bins};
     const uint32_t workers = (uint32_t)hj_join_workers(ctx->tune, ctx->cus, pl.big_tables, pl.unique);
     u64 bs = 0, bl = 0;
     CHK(setup_output(ctx, out, workers, &bs, &bl));
     HIPCHK(ctx, hipEventRecord(ctx->grp_ev_pass0[0], stream));
     // pass 0: the probe side first; the build side may still be arriving (hjgpu_phj_overlapped_async)
-    CHK(partition_columns(ctx, sk, sv, outer, f0, l.F0, l.bins, g_sk, g_sv, reinterpret_cast<uint64_t *>(d_off + (l.F0 + 1)), stream));
+    CHK(partition_op(ctx, sk, sv, outer, f0, l.F0, g_sk, g_sv, reinterpret_cast<uint64_t *>(d_off + (l.F0 + 1)), pass0, stream));
     if (inner_ready) HIPCHK(ctx, hipStreamWaitEvent(stream, inner_ready, 0));
-    CHK(partition_columns(ctx, rk, rv, inner, f0, l.F0, l.bins, g_rk, g_rv, reinterpret_cast<uint64_t *>(d_off), stream));
+    CHK(partition_op(ctx, rk, rv, inner, f0, l.F0, g_rk, g_rv, reinterpret_cast<uint64_t *>(d_off), pass0, stream));
     // the grouped join's state: cleared ONCE; every wave's output cursor "no block yet"
     HIPCHK(ctx, hj_zero_async(st, sizeof(DevState), stream));
     if (bs) HIPCHK(ctx, hj_fill_async(ctx->final_offsets.p, 0xFFFFFFFFu, (size_t)workers * sizeof(u64), stream));
@@ -1747,9 +1748,7 @@ static int phj_grouped_device(hjgpu_ctx *ctx, uint32_t G, uint32_t chunks,
         ctx->ev_cur = nullptr;
         CHK(rc);
     }
-    if (bs)
-        CHK(hj_launch_close_gaps_ex(out->d_keys, out->d_outer_vals, out->d_inner_vals, (const u64 *)ctx->final_offsets.p, workers, bs,
-                                    &st->block_counter, &st->overflow, ctx->moves.p, &st->nmoves, &st->dense, ctx->cus, stream));
+    if (bs) CHK(close_gaps(ctx, out, workers, bs, st, stream));
     if (d_result) CHK(hj_launch_group_result(&st->result, &st->group_skew, d_result, stream));
     HIPCHK(ctx, hipEventRecord(ctx->grp_ev_pass0[2], stream));
     // the last event every waiter looks at (hjgpu_get_stats), recorded in the context's own set
@@ -1797,8 +1796,7 @@ static int phj_like(hjgpu_ctx *ctx, uint32_t chunks,
             return HJGPU_OK;
         }
         DevState h;
-        HIPCHK(ctx, hipMemcpyAsync(&h, ctx->state.p, sizeof(DevState), hipMemcpyDeviceToHost, stream));
-        HIPCHK(ctx, hipStreamSynchronize(stream));
+        CHK(read_state(ctx, h, stream));
         if (!h.group_skew) return finish_blocking(ctx, result, out, stream);
         // a group was larger than the plan's workspace (heavy duplicates): the host-planned form sizes every group's join from its rows
         CHK(phj_grouped(ctx, groups, chunks, rk, rv, inner, sk, sv, outer, prm, out, stream));
@@ -1817,8 +1815,7 @@ static int phj_like(hjgpu_ctx *ctx, uint32_t chunks,
         CHK(phj_enqueue(ctx, pl, rk, rv, inner, sk, sv, outer, out, stream, (hipEvent_t)inner_ready));
         if (pl.claim_s) {
             DevState h;
-            HIPCHK(ctx, hipMemcpyAsync(&h, ctx->state.p, sizeof(DevState), hipMemcpyDeviceToHost, stream));
-            HIPCHK(ctx, hipStreamSynchronize(stream));
+            CHK(read_state(ctx, h, stream));
             if (!h.probe_overflow) return finish_from(ctx, h, result, out);
             // an optimistic region of the probe side was full (skewed keys): the join again, exactly (K4 of S, range bases), and every
             // later join of this context exactly at once; the caller's result and rows are those of this second join

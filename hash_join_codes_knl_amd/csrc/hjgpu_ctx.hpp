@@ -217,6 +217,20 @@ struct MetaLayout {
 };
 MetaLayout carve(void *base, uint32_t C, uint32_t F1, uint32_t P, size_t ranges, size_t items_extra = 0,
                  size_t tiles2 = 0, size_t batches = 0, size_t tdesc_b_cap = 0);
+// Launch arguments that many sites share are built here.  The store policy (PlainRows) is applied by these builders and nowhere else outside
+// the kernels: ScatterArgs::nt_partial by the K6 builders, JoinArgs::nt_rows by join_output.
+// K6 pass 1 of relation r in ranges (every (range, partition) writes from the base K5b laid out): columns kin / vin -> kout / vout, packed
+// tuples when vout is NULL.  The caller adds what is its own: claims, a batch's ranges and ticket, a group's dyn.
+ScatterArgs scatter_pass1(const hjgpu_ctx *ctx, const MetaLayout &m, int r, const Pass1Geom &geom, uint32_t F, uint32_t factor,
+                          const uint32_t *kin, const uint32_t *vin, uint32_t *kout, uint32_t *vout);
+// The plan kernels' arguments over the layout m, for C chunks of F1 x F2 partitions.  Everything else is zero / NULL until the caller sets
+// it: relation sizes, chunk bounds, input alignment, the two-pass layout (pad2, p_major, seg2, more), multi_fill, dyn, and the pass-2 tile
+// descriptors (a non-null tdesc adds a tile_desc_kernel launch).
+PlanArgs plan_args(const hjgpu_ctx *ctx, const MetaLayout &m, uint32_t C, uint32_t F1, uint32_t F2, uint32_t tile1, uint32_t tile2, bool unique,
+                   uint32_t mask);
+// A join's result rows: the block protocol into ja when bs > 0 (setup_output's block size and limit), and close_gaps after the join
+void join_output(const hjgpu_ctx *ctx, JoinArgs &ja, const hjgpu_output *out, u64 bs, u64 bl, DevState *st);
+int close_gaps(hjgpu_ctx *ctx, const hjgpu_output *out, uint32_t workers, u64 bs, DevState *st, hipStream_t stream);
 void choose_fanout(const HjTuning &tune, size_t inner, const hjgpu_phj_params *prm, uint32_t *F1, uint32_t *F2, bool *big_tables);
 void record(hjgpu_ctx *ctx, int which, hipStream_t s);
 int audit_begin(hjgpu_ctx *ctx, int kind, size_t inner, size_t outer, hipStream_t stream, u64 **rec);
@@ -284,8 +298,17 @@ int npj_probe_enqueue(hjgpu_ctx *ctx, const uint32_t *sk, const uint32_t *sv, si
 int npj_enqueue(hjgpu_ctx *ctx, const uint32_t *rk, const uint32_t *rv, size_t inner, const uint32_t *sk, const uint32_t *sv, size_t outer,
                 size_t buckets, uint32_t factor, const hjgpu_output *out, hipStream_t stream, bool unique);
 const hjgpu_output *take_async_output(hjgpu_ctx *ctx, const hjgpu_output *given);
-// hjgpu_ops.hip: the partition operator on separate columns (hjgpu_partition_async; pass 0 of a grouped plan: group_bins > 0)
-int partition_columns(hjgpu_ctx *ctx, const uint32_t *d_keys, const uint32_t *d_vals, size_t n, uint32_t factor, uint32_t fanout,
-                      uint32_t group_bins, uint32_t *d_keys_out, uint32_t *d_vals_out, uint64_t *d_offsets, void *stream_);
+// hjgpu_ops.hip: the partition operator on one relation (hjgpu_partition*, hjgpu_partition_packed_*; pass 0 of a grouped plan) - what
+// differs between its forms
+struct PartitionForm {
+    bool packed = false;                    // packed tuples (payload << 32 | key) at keys_out, audited (option "audit"); else the columns keys_out / vals_out
+    uint32_t group_bins = 0;                // the partitions in groups of group_bins neighbours, every group on a 128-byte line (hj_group_shift; the
+                                            // columns then need room for n + 32 * (groups + 1) rows); the offsets stay the dense prefix of the counts
+    uint32_t own_first = 0, own_count = 0;  // partitions [own_first, own_first + own_count) laid out behind all others
+    uint32_t factor2 = 0, fanout2 = 0;      // counts2 != NULL: the receivers' second level counted by the same read (bin = p1 * fanout2 + p2)
+    uint64_t *counts2 = nullptr;
+};
+int partition_op(hjgpu_ctx *ctx, const uint32_t *d_keys, const uint32_t *d_vals, size_t n, uint32_t factor, uint32_t fanout,
+                 uint32_t *keys_out, uint32_t *vals_out, uint64_t *d_offsets, const PartitionForm &form, void *stream_);
 
 }  // namespace hjapi

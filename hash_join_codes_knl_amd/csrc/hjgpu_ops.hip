@@ -8,21 +8,25 @@ using namespace hjapi;
 namespace hjapi {
 
 
-// group_bins > 0: the partitions in groups of group_bins neighbours, every group on a 128-byte line (hj_group_shift; the
-// columns then need room for n + 32 * (groups + 1) rows); d_offsets stay the dense prefix of the counts
-int partition_columns(hjgpu_ctx *ctx, const uint32_t *d_keys, const uint32_t *d_vals, size_t n,
-                             uint32_t factor, uint32_t fanout, uint32_t group_bins, uint32_t *d_keys_out, uint32_t *d_vals_out,
-                             uint64_t *d_offsets, void *stream_)
+// The partition operator on one relation: K4 -> K5 -> K6 pass 1 of the columns into `fanout` partitions, d_offsets = where they begin
+int partition_op(hjgpu_ctx *ctx, const uint32_t *d_keys, const uint32_t *d_vals, size_t n, uint32_t factor, uint32_t fanout,
+                 uint32_t *keys_out, uint32_t *vals_out, uint64_t *d_offsets, const PartitionForm &form, void *stream_)
 {
+    if (form.counts2 && (form.fanout2 < 1 || !(form.factor2 & 1) || form.factor2 == factor || (u64)fanout * form.fanout2 > HJGPU_MAX_PARTS))
+        return fail(ctx, HJGPU_EINVAL, "fused counts: factor2 odd and different from factor, fanout * fanout2 <= 32768");
     if (!ctx || !d_offsets) return fail(ctx, HJGPU_EINVAL, "null pointer");
+    if ((u64)form.own_first + form.own_count > fanout) return fail(ctx, HJGPU_EINVAL, "own_first + own_count must not exceed fanout");
     if (fanout == 0 || fanout > HJGPU_MAX_FANOUT || !(factor & 1))
         return fail(ctx, HJGPU_EINVAL, "fanout must be in [1, 1024] and factor odd");
-    if (n && (!d_keys_out || !d_vals_out)) return fail(ctx, HJGPU_EINVAL, "null output column");
+    if (form.packed) {
+        if (n && !keys_out) return fail(ctx, HJGPU_EINVAL, "null output array");
+        if ((uintptr_t)keys_out & 127) return fail(ctx, HJGPU_EALIGN, "the packed output must be 128-byte aligned (whole-line writes)");
+    } else if (n && (!keys_out || !vals_out)) return fail(ctx, HJGPU_EINVAL, "null output column");
     CHK(check_columns(ctx, d_keys, d_vals, n));
     hipStream_t stream = (hipStream_t)stream_;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     CHK(refuse_capture(ctx, stream));
-    const Pass1Geom geom = make_geom(ctx->tune, d_keys, n, 1, fanout, false);
+    const Pass1Geom geom = make_geom(ctx->tune, d_keys, n, 1, fanout, form.packed);
     MetaLayout sz = carve(nullptr, 1, fanout, fanout, geom.ranges_per_chunk);
     ctx->prepared = false;                 // the workspace is re-planned below
     CHK(ensure(ctx, ctx->meta, sz.total_bytes));
@@ -31,37 +35,41 @@ int partition_columns(hjgpu_ctx *ctx, const uint32_t *d_keys, const uint32_t *d_
     for (int i = 0; i < EV_COUNT; ++i) ctx->ev_valid[i] = false;
     ctx->last_algo = 2;
     record(ctx, EV_BEGIN, stream);
+    u64 *audit = nullptr;                  // option "audit", packed form: stage 0 the columns as read, stage 1 the packed output where it lies
+    if (form.packed) CHK(audit_begin(ctx, 3, n, 0, stream, &audit));
     HIPCHK(ctx, hj_zero_async(m.counts[0], m.counts_bytes, stream));
-    if (n) CHK(hj_launch_hist2(d_keys, geom, factor, fanout, 1u, 1u, m.counts[0], m.range_counts[0], m.tickets,
-                               ctx->cus, stream));
-    PlanArgs pa;
-    for (int r = 0; r < 2; ++r) {
-        pa.counts[r] = m.counts[r]; pa.off2[r] = m.off2[r]; pa.end2[r] = m.end2[r]; pa.cur2[r] = m.cur2[r];
-        pa.off1[r] = m.off1[r]; pa.cur1[r] = m.cur1[r]; pa.tp1[r] = m.tp1[r];
-        pa.seg1[r] = m.seg1[r]; pa.tp2[r] = m.tp2[r];
-    }
-    pa.tdesc[0] = pa.tdesc[1] = nullptr; pa.tdesc_cap = 0; pa.pad2 = 0; pa.unique = 0;
-    pa.n[0] = n; pa.n[1] = 0; pa.slice_prefix = m.slice_prefix; pa.slices = m.slices; pa.item_part = m.item_part;
-    for (uint32_t c = 0; c < 9; ++c) { pa.chunk_beg[0][c] = c ? n : 0; pa.chunk_beg[1][c] = 0; }
-    pa.regular[0] = pa.regular[1] = 0; pa.chunk_part[0] = pa.chunk_part[1] = 0;
-    pa.chunks = 1; pa.F1 = fanout; pa.F2 = 1;
-    pa.in_align[0] = align_of(d_keys); pa.in_align[1] = 0;
-    pa.tile1 = pa.tile2 = geom.tile; pa.slice = HJ_JOIN_SLICE; pa.cap = (uint32_t)ctx->tune.join.cap(); pa.mask = 7u;
+    if (form.counts2) {
+        // the same read of the keys also counts the RECEIVERS' second level (bin = p1 * fanout2 + p2, the join's fused
+        // histogram): they then need no histogram pass of their own over what arrives (K4p).  The pass-1 counts of this
+        // call are the row sums.
+        HIPCHK(ctx, hj_zero_async(form.counts2, (size_t)fanout * form.fanout2 * sizeof(u64), stream));
+        if (n) {
+            u64 *fused = reinterpret_cast<u64 *>(form.counts2);
+            CHK(hj_launch_hist2(d_keys, geom, factor, fanout, form.factor2, form.fanout2, fused, m.range_counts[0], m.tickets, ctx->cus, stream,
+                                (size_t)ctx->tune.hist_min_lds));
+            CHK(hj_launch_row_sums(fused, fanout, form.fanout2, m.counts[0], stream));
+        }
+    } else if (n) CHK(hj_launch_hist2(d_keys, geom, factor, fanout, 1u, 1u, m.counts[0], m.range_counts[0], m.tickets, ctx->cus, stream));
+    // (the column form plans all three parts, mask 7, the packed form only its relation)
+    PlanArgs pa = plan_args(ctx, m, 1, fanout, 1, geom.tile, geom.tile, false, form.packed ? 1u : 7u);
+    pa.n[0] = n; pa.in_align[0] = align_of(d_keys);
+    for (uint32_t c = 1; c < 9; ++c) pa.chunk_beg[0][c] = n;
     CHK(hj_launch_plan(pa, stream));
     if (n) {
-        CHK(hj_launch_range_base(m.range_counts[0], m.off1[0], m.range_base[0], 1,
-                                 geom.ranges_per_chunk, fanout, stream, 0, 0, group_bins));
-        ScatterArgs sa;
-        memset(&sa, 0, sizeof(sa));
-        sa.kin = d_keys; sa.vin = d_vals; sa.kout = d_keys_out; sa.vout = d_vals_out;
-        sa.seg_off = m.seg1[0]; sa.tile_prefix = m.tp1[0]; sa.cursors = m.cur1[0];
-        sa.nseg = 1; sa.F = fanout; sa.factor = factor; sa.in_align = align_of(d_keys);
-        sa.ranged = 1; sa.work_counter = m.tickets + HJ_TICKET_K6; sa.geom = geom; sa.range_base = m.range_base[0];
-        sa.in_packed = 0; sa.out_packed = 0;
-        sa.nt_partial = ctx->rows_plain ? 0u : 1u;
-                CHK(hj_launch_scatter(sa, ctx->tune, scatter_cus(ctx), stream));
+        CHK(hj_launch_range_base(m.range_counts[0], m.off1[0], m.range_base[0], 1, geom.ranges_per_chunk, fanout, stream,
+                                 form.own_first, form.own_count, form.group_bins));
+        CHK(hj_launch_scatter(scatter_pass1(ctx, m, 0, geom, fanout, factor, d_keys, d_vals, keys_out, vals_out), ctx->tune, scatter_cus(ctx),
+                              stream));
     }
     HIPCHK(ctx, hj_copy_async(d_offsets, m.off2[0], ((size_t)fanout + 1) * sizeof(u64), stream));
+    if (audit && n) {
+        CHK(hj_audit_sums_columns(d_keys, d_vals, n, audit, ctx->cus, stream));
+        CHK(ensure(ctx, ctx->audit_lay, (size_t)2 * (HJGPU_MAX_FANOUT + 1) * sizeof(u64)));
+        u64 *beg = reinterpret_cast<u64 *>(ctx->audit_lay.p), *end = beg + HJGPU_MAX_FANOUT + 1;
+        CHK(hj_audit_own_last(m.off2[0], fanout, form.own_first, form.own_count, n, beg, end, stream));
+        const HjAuditHash h = {factor, fanout, 0u, 1u, 1u, fanout};
+        CHK(audit_partitions(ctx, 1, reinterpret_cast<const u64 *>(keys_out), beg, end, fanout, h, audit, stream));
+    }
     record(ctx, EV_GAPS, stream);
     return HJGPU_OK;
 }
@@ -97,7 +105,7 @@ int hjgpu_partition_async(hjgpu_ctx *ctx, const uint32_t *d_keys, const uint32_t
                           uint32_t factor, uint32_t fanout, uint32_t *d_keys_out, uint32_t *d_vals_out,
                           uint64_t *d_offsets, void *stream_)
 {
-    return partition_columns(ctx, d_keys, d_vals, n, factor, fanout, 0, d_keys_out, d_vals_out, d_offsets, stream_);
+    return partition_op(ctx, d_keys, d_vals, n, factor, fanout, d_keys_out, d_vals_out, d_offsets, PartitionForm{}, stream_);
 }
 
 int hjgpu_partition(hjgpu_ctx *ctx, const uint32_t *d_keys, const uint32_t *d_vals, size_t n,
@@ -146,30 +154,19 @@ int hjgpu_join_partitions(hjgpu_ctx *ctx,
     DevState *st = reinterpret_cast<DevState *>(ctx->state.p);
     u64 bs = 0, bl = 0;
     const bool unique = ctx->tune.unique || (passes->flags & HJGPU_FLAG_UNIQUE);
-    CHK(setup_output(ctx, out, (uint32_t)hj_join_workers(ctx->tune, ctx->cus, false, unique), &bs, &bl));
+    const uint32_t workers = (uint32_t)hj_join_workers(ctx->tune, ctx->cus, false, unique);
+    CHK(setup_output(ctx, out, workers, &bs, &bl));
     record(ctx, EV_BEGIN, stream);
     HIPCHK(ctx, hj_zero_async(st, sizeof(DevState), stream));
     // counts = adjacent differences of the caller's offsets, then the usual plan
     // (re-derives identical offsets and the work-item prefix)
     CHK(hj_launch_offsets_to_counts((const u64 *)roff, m.counts[0], pl.P, stream));
     CHK(hj_launch_offsets_to_counts((const u64 *)soff, m.counts[1], pl.P, stream));
-    PlanArgs pa;
-    for (int r = 0; r < 2; ++r) {
-        pa.counts[r] = m.counts[r]; pa.off2[r] = m.off2[r]; pa.end2[r] = m.end2[r]; pa.cur2[r] = m.cur2[r];
-        pa.off1[r] = m.off1[r]; pa.cur1[r] = m.cur1[r]; pa.tp1[r] = m.tp1[r];
-        pa.seg1[r] = m.seg1[r]; pa.tp2[r] = m.tp2[r];
-    }
-    pa.tdesc[0] = pa.tdesc[1] = nullptr; pa.tdesc_cap = 0; pa.pad2 = 0; pa.unique = unique ? 1u : 0u;
-    pa.n[0] = pa.n[1] = 0; pa.slice_prefix = m.slice_prefix; pa.slices = m.slices; pa.item_part = m.item_part;
-    for (int r = 0; r < 2; ++r) for (uint32_t c = 0; c < 9; ++c) pa.chunk_beg[r][c] = 0;
-    pa.regular[0] = pa.regular[1] = 0; pa.chunk_part[0] = pa.chunk_part[1] = 0;
-    pa.chunks = 1; pa.F1 = pl.F1; pa.F2 = pl.F2; pa.in_align[0] = pa.in_align[1] = 0;
-    pa.tile1 = pa.tile2 = (uint32_t)hj_scatter_tile(ctx->tune, 2, 1, true); pa.slice = HJ_JOIN_SLICE;
-    pa.cap = (uint32_t)ctx->tune.join.cap(); pa.mask = 7u;
+    const uint32_t tile = (uint32_t)hj_scatter_tile(ctx->tune, 2, 1, true);
+    PlanArgs pa = plan_args(ctx, m, 1, pl.F1, pl.F2, tile, tile, unique, 7u);
     CHK(hj_launch_plan(pa, stream));
     for (int e : {EV_S_HIST, EV_S_PLAN, EV_S_SC1, EV_S_SC2, EV_WAITED, EV_R_HIST, EV_R_PLAN, EV_R_SC1, EV_R_SC2}) record(ctx, e, stream);
-    JoinArgs ja;
-    memset(&ja, 0, sizeof(ja));
+    JoinArgs ja{};
     ja.rk = rk; ja.rv = rv; ja.sk = sk; ja.sv = sv;
     ja.roff = (const u64 *)roff; ja.soff = (const u64 *)soff;    // caller's offsets (may start at non-zero)
     ja.rend = ja.roff + 1; ja.send = ja.soff + 1;
@@ -179,19 +176,10 @@ int hjgpu_join_partitions(hjgpu_ctx *ctx,
     ja.s_align = 0; ja.result = &st->result; ja.work_counter = &st->work_counter;
     ja.work_counter2 = &st->work_counter2;       // (multi_fill stays NULL: the caller's partitions were not counted)
     ja.unique = unique ? 1u : 0u;
-    if (bs) {
-        ja.ok = out->d_keys; ja.oov = out->d_outer_vals; ja.oiv = out->d_inner_vals;
-        ja.block_size = bs; ja.block_limit = bl; ja.block_counter = &st->block_counter;
-        ja.final_offsets = (u64 *)ctx->final_offsets.p; ja.overflow = &st->overflow;
-        ja.nt_rows = ctx->rows_plain ? 0u : 1u;
-    }
+    join_output(ctx, ja, out, bs, bl, st);
     CHK(hj_launch_join(ja, ctx->tune, ctx->cus, stream));
     record(ctx, EV_JOIN, stream);
-    if (bs)
-        CHK(hj_launch_close_gaps_ex(out->d_keys, out->d_outer_vals, out->d_inner_vals,
-                                    (const u64 *)ctx->final_offsets.p,
-                                    (uint32_t)hj_join_workers(ctx->tune, ctx->cus, false, unique), bs, &st->block_counter,
-                                    &st->overflow, ctx->moves.p, &st->nmoves, &st->dense, ctx->cus, stream));
+    if (bs) CHK(close_gaps(ctx, out, workers, bs, st, stream));
     record(ctx, EV_GAPS, stream);
     ctx->last_algo = 1;
     return finish_blocking(ctx, result, out, stream);
@@ -230,96 +218,19 @@ int hjgpu_npj_probe(hjgpu_ctx *ctx, const uint32_t *d_keys, const uint32_t *d_va
 }
 
 // ---- relations that arrive pass-1-partitioned (the receiving side of the multi-GPU CPRA) --------------------
-static int partition_packed(hjgpu_ctx *ctx, const uint32_t *d_keys, const uint32_t *d_vals, size_t n,
-                            uint32_t factor, uint32_t fanout, uint32_t own_first, uint32_t own_count,
-                            uint64_t *d_tuples_out, uint64_t *d_offsets, void *stream_,
-                            uint32_t factor2 = 0, uint32_t fanout2 = 0, uint64_t *d_counts2 = nullptr)
-{
-    if (d_counts2 && (fanout2 < 1 || !(factor2 & 1) || factor2 == factor || (u64)fanout * fanout2 > HJGPU_MAX_PARTS))
-        return fail(ctx, HJGPU_EINVAL, "fused counts: factor2 odd and different from factor, fanout * fanout2 <= 32768");
-    if (!ctx || !d_offsets) return fail(ctx, HJGPU_EINVAL, "null pointer");
-    if ((u64)own_first + own_count > fanout) return fail(ctx, HJGPU_EINVAL, "own_first + own_count must not exceed fanout");
-    if (fanout == 0 || fanout > HJGPU_MAX_FANOUT || !(factor & 1))
-        return fail(ctx, HJGPU_EINVAL, "fanout must be in [1, 1024] and factor odd");
-    if (n && !d_tuples_out) return fail(ctx, HJGPU_EINVAL, "null output array");
-    if ((uintptr_t)d_tuples_out & 127) return fail(ctx, HJGPU_EALIGN, "the packed output must be 128-byte aligned (whole-line writes)");
-    CHK(check_columns(ctx, d_keys, d_vals, n));
-    hipStream_t stream = (hipStream_t)stream_;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    CHK(refuse_capture(ctx, stream));
-    const Pass1Geom geom = make_geom(ctx->tune, d_keys, n, 1, fanout, true);
-    MetaLayout sz = carve(nullptr, 1, fanout, fanout, geom.ranges_per_chunk);
-    ctx->prepared = false;                 // the workspace is re-planned below
-    CHK(ensure(ctx, ctx->meta, sz.total_bytes));
-    MetaLayout m = carve(ctx->meta.p, 1, fanout, fanout, geom.ranges_per_chunk);
-    for (int i = 0; i < EV_COUNT; ++i) ctx->ev_valid[i] = false;
-    ctx->last_algo = 2;                    // hjgpu_get_stats().ms_total = the whole operator
-    record(ctx, EV_BEGIN, stream);
-    u64 *audit = nullptr;                  // option "audit": stage 0 the columns as read, stage 1 the packed output where it lies
-    CHK(audit_begin(ctx, 3, n, 0, stream, &audit));
-    HIPCHK(ctx, hj_zero_async(m.counts[0], m.counts_bytes, stream));
-    if (d_counts2) {
-        // the same read of the keys also counts the RECEIVERS' second level (bin = p1 * fanout2 + p2, the join's fused
-        // histogram): they then need no histogram pass of their own over what arrives (K4p).  The pass-1 counts of this
-        // call are the row sums.
-        HIPCHK(ctx, hj_zero_async(d_counts2, (size_t)fanout * fanout2 * sizeof(u64), stream));
-        if (n) {
-            u64 *fused = reinterpret_cast<u64 *>(d_counts2);
-            CHK(hj_launch_hist2(d_keys, geom, factor, fanout, factor2, fanout2, fused, m.range_counts[0], m.tickets, ctx->cus, stream, (size_t)ctx->tune.hist_min_lds));
-            CHK(hj_launch_row_sums(fused, fanout, fanout2, m.counts[0], stream));
-        }
-    } else if (n) CHK(hj_launch_hist2(d_keys, geom, factor, fanout, 1u, 1u, m.counts[0], m.range_counts[0], m.tickets, ctx->cus, stream));
-    PlanArgs pa;
-    for (int r = 0; r < 2; ++r) {
-        pa.counts[r] = m.counts[r]; pa.off2[r] = m.off2[r]; pa.end2[r] = m.end2[r]; pa.cur2[r] = m.cur2[r];
-        pa.off1[r] = m.off1[r]; pa.cur1[r] = m.cur1[r]; pa.tp1[r] = m.tp1[r];
-        pa.seg1[r] = m.seg1[r]; pa.tp2[r] = m.tp2[r];
-    }
-    pa.tdesc[0] = pa.tdesc[1] = nullptr; pa.tdesc_cap = 0; pa.pad2 = 0; pa.unique = 0;
-    pa.n[0] = n; pa.n[1] = 0; pa.slice_prefix = m.slice_prefix; pa.slices = m.slices; pa.item_part = m.item_part;
-    for (uint32_t c = 0; c < 9; ++c) { pa.chunk_beg[0][c] = c ? n : 0; pa.chunk_beg[1][c] = 0; }
-    pa.regular[0] = pa.regular[1] = 0; pa.chunk_part[0] = pa.chunk_part[1] = 0;
-    pa.chunks = 1; pa.F1 = fanout; pa.F2 = 1;
-    pa.in_align[0] = align_of(d_keys); pa.in_align[1] = 0;
-    pa.tile1 = pa.tile2 = geom.tile; pa.slice = HJ_JOIN_SLICE; pa.cap = (uint32_t)ctx->tune.join.cap(); pa.mask = 1u;
-    CHK(hj_launch_plan(pa, stream));
-    if (n) {
-        CHK(hj_launch_range_base(m.range_counts[0], m.off1[0], m.range_base[0], 1, geom.ranges_per_chunk, fanout, stream,
-                                 own_first, own_count));
-        ScatterArgs sa;
-        memset(&sa, 0, sizeof(sa));
-        sa.kin = d_keys; sa.vin = d_vals; sa.kout = reinterpret_cast<uint32_t *>(d_tuples_out); sa.vout = nullptr;
-        sa.seg_off = m.seg1[0]; sa.tile_prefix = m.tp1[0]; sa.cursors = m.cur1[0];
-        sa.nseg = 1; sa.F = fanout; sa.factor = factor; sa.in_align = align_of(d_keys);
-        sa.ranged = 1; sa.work_counter = m.tickets + HJ_TICKET_K6; sa.geom = geom; sa.range_base = m.range_base[0];
-        sa.in_packed = 0; sa.out_packed = 1;
-        sa.nt_partial = ctx->rows_plain ? 0u : 1u;
-                CHK(hj_launch_scatter(sa, ctx->tune, scatter_cus(ctx), stream));
-    }
-    HIPCHK(ctx, hj_copy_async(d_offsets, m.off2[0], ((size_t)fanout + 1) * sizeof(u64), stream));
-    if (audit && n) {
-        CHK(hj_audit_sums_columns(d_keys, d_vals, n, audit, ctx->cus, stream));
-        CHK(ensure(ctx, ctx->audit_lay, (size_t)2 * (HJGPU_MAX_FANOUT + 1) * sizeof(u64)));
-        u64 *beg = reinterpret_cast<u64 *>(ctx->audit_lay.p), *end = beg + HJGPU_MAX_FANOUT + 1;
-        CHK(hj_audit_own_last(m.off2[0], fanout, own_first, own_count, n, beg, end, stream));
-        const HjAuditHash h = {factor, fanout, 0u, 1u, 1u, fanout};
-        CHK(audit_partitions(ctx, 1, reinterpret_cast<const u64 *>(d_tuples_out), beg, end, fanout, h, audit, stream));
-    }
-    record(ctx, EV_GAPS, stream);
-    return HJGPU_OK;
-}
-
 int hjgpu_partition_packed_async(hjgpu_ctx *ctx, const uint32_t *d_keys, const uint32_t *d_vals, size_t n,
                                  uint32_t factor, uint32_t fanout, uint64_t *d_tuples_out, uint64_t *d_offsets, void *stream)
 {
-    return partition_packed(ctx, d_keys, d_vals, n, factor, fanout, 0, 0, d_tuples_out, d_offsets, stream);
+    return partition_op(ctx, d_keys, d_vals, n, factor, fanout, reinterpret_cast<uint32_t *>(d_tuples_out), nullptr, d_offsets,
+                        PartitionForm{.packed = true}, stream);
 }
 
 int hjgpu_partition_packed_own_last_async(hjgpu_ctx *ctx, const uint32_t *d_keys, const uint32_t *d_vals, size_t n,
                                           uint32_t factor, uint32_t fanout, uint32_t own_first, uint32_t own_count,
                                           uint64_t *d_tuples_out, uint64_t *d_offsets, void *stream)
 {
-    return partition_packed(ctx, d_keys, d_vals, n, factor, fanout, own_first, own_count, d_tuples_out, d_offsets, stream);
+    return partition_op(ctx, d_keys, d_vals, n, factor, fanout, reinterpret_cast<uint32_t *>(d_tuples_out), nullptr, d_offsets,
+                        PartitionForm{.packed = true, .own_first = own_first, .own_count = own_count}, stream);
 }
 
 int hjgpu_partition_packed_counted_async(hjgpu_ctx *ctx, const uint32_t *d_keys, const uint32_t *d_vals, size_t n,
@@ -328,8 +239,9 @@ int hjgpu_partition_packed_counted_async(hjgpu_ctx *ctx, const uint32_t *d_keys,
                                          uint64_t *d_counts2, void *stream)
 {
     if (!d_counts2) return fail(ctx, HJGPU_EINVAL, "null counts array");
-    return partition_packed(ctx, d_keys, d_vals, n, factor, fanout, own_first, own_count, d_tuples_out, d_offsets, stream,
-                            factor2, fanout2, d_counts2);
+    return partition_op(ctx, d_keys, d_vals, n, factor, fanout, reinterpret_cast<uint32_t *>(d_tuples_out), nullptr, d_offsets,
+                        PartitionForm{.packed = true, .own_first = own_first, .own_count = own_count, .factor2 = factor2, .fanout2 = fanout2,
+                                      .counts2 = d_counts2}, stream);
 }
 
 // what hjgpu_phj_build_prepartitioned plans for a build side of `inner` rows in `fanout1` pass-1 partitions

@@ -129,3 +129,18 @@ def test_clears_and_copies_are_the_librarys_own_kernels():
             # the two fallbacks inside hj_zero_async / hj_copy_async (ranges that are not made of 4-byte words: no caller has one)
             # and the diagnostics-only phase profile of K6 (option scatter_prof, synchronises)
             assert ("& 3" in ctx and f == "gen_kernels.hip") or "prof" in ctx, "%s:%d uses the runtime's %s" % (f, line, m.group(0))
+
+
+@pytest.mark.parametrize("field", ["nt_partial", "nt_rows"])
+def test_host_sets_the_store_policy_in_one_place(field):
+    """outside the kernels, ScatterArgs::nt_partial / JoinArgs::nt_rows are set once, from ctx->rows_plain: a zeroed argument struct
+    selects the plain-store instance, so a launch site that set the field itself could forget it and lose stores"""
+    sites = []
+    for f in sorted(os.listdir(CSRC)):
+        if f in ("partition_kernels.hip", "join_kernels.hip"):
+            continue
+        text = re.sub(r"//[^\n]*", "", open(os.path.join(CSRC, f)).read())
+        for m in re.finditer(r"\b%s\s*=(?!=)([^;]*);" % field, text):
+            sites.append((f, text[:m.start()].count("\n") + 1, m.group(1).strip()))
+    assert len(sites) == 1, "%s is assigned at %r" % (field, [s[:2] for s in sites])
+    assert "ctx->rows_plain" in sites[0][2], sites
