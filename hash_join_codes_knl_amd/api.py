@@ -18,6 +18,8 @@ TRANSPORT_RCCL, TRANSPORT_LOOPBACK = 0, 1
 MAX_FANOUT = 1024
 MAX_PARTS = 32768
 FLAG_UNIQUE = 1
+FLAG_SEMI = 2       # HJGPU_FLAG_SEMI: one row (key, outer_val) per probe tuple with a match
+FLAG_ANTI = 4       # HJGPU_FLAG_ANTI: one row (key, outer_val) per probe tuple without one
 
 EXPORTS = [
     "hjgpu_kernel_hash", "hjgpu_library_hash", "hjgpu_device_count", "hjgpu_create", "hjgpu_destroy", "hjgpu_last_error", "hjgpu_status_string",

@@ -29,8 +29,11 @@ typedef __attribute__((address_space(3))) u64 hj_lds_u64;
 // NT: the rows leave through non-temporal stores (EmitterT<true>, every join that may run beside other work) or plain ones
 // (EmitterT<false>: solo joins, option "solo").  A template parameter: a run-time flag around the three stores was merged by the
 // compiler into ONE plain store per column (tests/test_store_policy_isa.py reads the machine code).
-template <bool NT>
+// COLS: 3 result columns (key, outer_val, inner_val), or 2 (key, outer_val: semi- and anti-joins, whose rows carry no build
+// payload) - then `oiv` is neither read nor written and may be NULL.
+template <bool NT, int COLS = 3>
 struct EmitterT {
+    static_assert(COLS == 2 || COLS == 3, "two or three result columns");
     uint32_t *ok, *oov, *oiv;
     u64 block_size, block_limit;
     u64 *block_counter;
@@ -82,11 +85,11 @@ struct EmitterT {
         if constexpr (NT && HJ_ROW_STORE) {
             __builtin_nontemporal_store(key, &ok[pos]);
             __builtin_nontemporal_store(outer_val, &oov[pos]);
-            __builtin_nontemporal_store(inner_val, &oiv[pos]);
+            if constexpr (COLS == 3) __builtin_nontemporal_store(inner_val, &oiv[pos]);
         } else {
             ok[pos] = key;
             oov[pos] = outer_val;
-            oiv[pos] = inner_val;
+            if constexpr (COLS == 3) oiv[pos] = inner_val;
         }
     }
 
@@ -129,11 +132,11 @@ struct EmitterT {
             if constexpr (NT && HJ_ROW_STORE) {
                 __builtin_nontemporal_store(k4, reinterpret_cast<v4u_t *>(&ok[pos0]));
                 __builtin_nontemporal_store(o4, reinterpret_cast<v4u_t *>(&oov[pos0]));
-                __builtin_nontemporal_store(i4, reinterpret_cast<v4u_t *>(&oiv[pos0]));
+                if constexpr (COLS == 3) __builtin_nontemporal_store(i4, reinterpret_cast<v4u_t *>(&oiv[pos0]));
             } else {
                 *reinterpret_cast<v4u_t *>(&ok[pos0]) = k4;
                 *reinterpret_cast<v4u_t *>(&oov[pos0]) = o4;
-                *reinterpret_cast<v4u_t *>(&oiv[pos0]) = i4;
+                if constexpr (COLS == 3) *reinterpret_cast<v4u_t *>(&oiv[pos0]) = i4;
             }
         } else {
             // the lane's four rows straddle the end of the block: row by row (rows [0, room - rank) in the old block)
@@ -141,8 +144,9 @@ struct EmitterT {
             for (int i = 0; i < 4; ++i) {
                 const u64 pos = (rank + i < room) ? (o + rank + i) : (base + (rank + i - room));
                 if constexpr (NT && HJ_ROW_STORE) {
-                    __builtin_nontemporal_store(key[i], &ok[pos]); __builtin_nontemporal_store(outer_val[i], &oov[pos]); __builtin_nontemporal_store(inner_val[i], &oiv[pos]);
-                } else { ok[pos] = key[i]; oov[pos] = outer_val[i]; oiv[pos] = inner_val[i]; }
+                    __builtin_nontemporal_store(key[i], &ok[pos]); __builtin_nontemporal_store(outer_val[i], &oov[pos]);
+                    if constexpr (COLS == 3) __builtin_nontemporal_store(inner_val[i], &oiv[pos]);
+                } else { ok[pos] = key[i]; oov[pos] = outer_val[i]; if constexpr (COLS == 3) oiv[pos] = inner_val[i]; }
             }
         }
     }

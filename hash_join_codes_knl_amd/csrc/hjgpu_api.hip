@@ -353,11 +353,12 @@ int check_columns(hjgpu_ctx *ctx, const uint32_t *k, const uint32_t *v, size_t n
 }
 
 int setup_output(hjgpu_ctx *ctx, const hjgpu_output *out, uint32_t workers, u64 *block_size,
-                 u64 *block_limit)
+                 u64 *block_limit, uint32_t mode)
 {
     *block_size = 0; *block_limit = 0;
     if (!out || !out->d_keys) return HJGPU_OK;
-    if (!out->d_outer_vals || !out->d_inner_vals) return fail(ctx, HJGPU_EINVAL, "output columns");
+    // (semi- and anti-join rows have no inner_val: d_inner_vals may be NULL, it is neither read nor written)
+    if (!out->d_outer_vals || (!out->d_inner_vals && mode == HJ_MODE_INNER)) return fail(ctx, HJGPU_EINVAL, "output columns");
     u64 bs = out->block_size ? out->block_size : 65536;
     if (bs < 256 || (bs & (bs - 1))) return fail(ctx, HJGPU_EINVAL, "block_size must be a power of two >= 256");
     u64 bl = out->capacity / bs;
@@ -493,9 +494,25 @@ void join_output(const hjgpu_ctx *ctx, JoinArgs &ja, const hjgpu_output *out, u6
     ja.nt_rows = ctx->rows_plain ? 0u : 1u;        // plain result rows only in a solo join (PlainRows)
 }
 
-int close_gaps(hjgpu_ctx *ctx, const hjgpu_output *out, uint32_t workers, u64 bs, DevState *st, hipStream_t stream)
+int check_join_mode(hjgpu_ctx *ctx, uint32_t flags)
 {
-    return hj_launch_close_gaps_ex(out->d_keys, out->d_outer_vals, out->d_inner_vals, (const u64 *)ctx->final_offsets.p, workers, bs,
+    if ((flags & HJGPU_FLAG_SEMI) && (flags & HJGPU_FLAG_ANTI))
+        return fail(ctx, HJGPU_EINVAL, "HJGPU_FLAG_SEMI | HJGPU_FLAG_ANTI: a join is a semi-join or an anti-join, not both");
+    return HJGPU_OK;
+}
+
+int refuse_join_mode(hjgpu_ctx *ctx, uint32_t flags, const char *entry)
+{
+    if (!(flags & (HJGPU_FLAG_SEMI | HJGPU_FLAG_ANTI))) return HJGPU_OK;
+    char what[256];
+    snprintf(what, sizeof(what), "%s: HJGPU_FLAG_%s is not supported here (semi- and anti-joins: hjgpu_phj, hjgpu_cpra, hjgpu_npj, "
+             "their _async forms and hjgpu_phj_overlapped_async)", entry, (flags & HJGPU_FLAG_SEMI) ? "SEMI" : "ANTI");
+    return fail(ctx, HJGPU_EINVAL, what);
+}
+
+int close_gaps(hjgpu_ctx *ctx, const hjgpu_output *out, uint32_t workers, u64 bs, DevState *st, hipStream_t stream, bool rows2)
+{
+    return hj_launch_close_gaps_ex(out->d_keys, out->d_outer_vals, rows2 ? nullptr : out->d_inner_vals, (const u64 *)ctx->final_offsets.p, workers, bs,
                                    &st->block_counter, &st->overflow, ctx->moves.p, &st->nmoves, &st->dense, ctx->cus, stream);
 }
 
@@ -519,7 +536,8 @@ int phj_prepare(hjgpu_ctx *ctx, size_t inner, size_t outer, const hjgpu_phj_para
     ReserveClock clock(ctx);
     pl->C = chunks;
     pl->pre = pre ? 1u : 0u; pl->pre_f1 = 1; pl->pre_F1tot = 1; pl->pre_base = 0;
-    pl->unique = ctx->tune.unique || (prm && (prm->flags & HJGPU_FLAG_UNIQUE));
+    pl->mode = (uint8_t)(prm ? hj_join_mode(prm->flags) : HJ_MODE_INNER);
+    pl->unique = ctx->tune.unique || (prm && (prm->flags & HJGPU_FLAG_UNIQUE)) || pl->mode != HJ_MODE_INNER;
     choose_fanout(ctx->tune, plan_inner ? plan_inner : inner, prm, &pl->F1, &pl->F2, &pl->big_tables);
     if (big_override >= 0) pl->big_tables = big_override != 0;
     if (chunks > 8 && !pre) {
@@ -534,7 +552,11 @@ int phj_prepare(hjgpu_ctx *ctx, size_t inner, size_t outer, const hjgpu_phj_para
         }
     }
     if (pl->unique && !hj_join_config_built(hj_join_config_of(ctx->tune, pl->big_tables), true))
-        return fail(ctx, HJGPU_EINVAL, "HJGPU_FLAG_UNIQUE: the join_cfg geometry of this context has no _UNIQUE instance "
+        return fail(ctx, HJGPU_EINVAL, pl->mode == HJ_MODE_SEMI ? "HJGPU_FLAG_SEMI: the join_cfg geometry of this context has no _UNIQUE instance "
+                                                                  "(geometries with one: 512,13,2 and 1024,14,2)"
+                                     : pl->mode == HJ_MODE_ANTI ? "HJGPU_FLAG_ANTI: the join_cfg geometry of this context has no _UNIQUE instance "
+                                                                  "(geometries with one: 512,13,2 and 1024,14,2)"
+                                     : "HJGPU_FLAG_UNIQUE: the join_cfg geometry of this context has no _UNIQUE instance "
                                        "(geometries with one: 512,13,2 and 1024,14,2)");
     pl->P = pl->F1 * pl->F2;
     if (pl->F1 < 1 || pl->F2 < 1 || pl->F1 > HJGPU_MAX_FANOUT || pl->F2 > HJGPU_MAX_FANOUT ||
@@ -629,7 +651,7 @@ int phj_enqueue(hjgpu_ctx *ctx, const PhjPlan &pl,
     DevState *st = reinterpret_cast<DevState *>(ctx->state.p);
     const uint32_t workers = (uint32_t)hj_join_workers(ctx->tune, ctx->cus, pl.big_tables, pl.unique);
     u64 bs = 0, bl = 0;
-    CHK(setup_output(ctx, out, workers, &bs, &bl));
+    CHK(setup_output(ctx, out, workers, &bs, &bl, pl.mode));
 
     record(ctx, EV_BEGIN, stream);
     u64 *audit = nullptr;                // option "audit": this call's record (else NULL: nothing below is enqueued)
@@ -671,6 +693,7 @@ int phj_enqueue(hjgpu_ctx *ctx, const PhjPlan &pl,
     const u64 *dyn[2] = {grp ? grp->desc : nullptr, grp ? grp->desc + 2 : nullptr};           // {first row, rows} of R / S in device memory
     pa.dyn[0] = dyn[0]; pa.dyn[1] = dyn[1];
     pa.multi_fill = m.tickets + HJ_TICKET_MULTI_FILL;          // zeroed with the tickets; counted by the work-item plan, read by the _UNIQUE join
+    pa.anti = pl.mode == HJ_MODE_ANTI ? 1u : 0u;
     // two-pass plans: final partitions start on 128-byte lines (pass 2 claims whole lines); option "dense2": dense
     const bool pad2 = pl.F2 > 1 && !ctx->tune.dense2;
     pa.pad2 = pad2 ? 1u : 0u;
@@ -886,6 +909,7 @@ int phj_enqueue(hjgpu_ctx *ctx, const PhjPlan &pl,
         ja.packed = 1;
         ja.big_tables = pl.big_tables ? 1u : 0u;
         ja.unique = pl.unique ? 1u : 0u;
+        ja.mode = pl.mode;
         ja.result = &st->result;
         // (the work counters live with the tickets: zeroed with them, per join - also for a group, whose DevState is the grouped join's)
         ja.work_counter = reinterpret_cast<u64 *>(m.tickets + HJ_TICKET_JOIN);
@@ -897,7 +921,7 @@ int phj_enqueue(hjgpu_ctx *ctx, const PhjPlan &pl,
         if (audit) CHK(hj_audit_copy(reinterpret_cast<const u64 *>(&st->result), audit + 4 * 6, 4, stream));
     }
     record(ctx, EV_JOIN, stream);
-    if (bs && inner && outer && mode != PHJ_BUILD_ONLY && !grp) CHK(close_gaps(ctx, out, workers, bs, st, stream));
+    if (bs && inner && outer && mode != PHJ_BUILD_ONLY && !grp) CHK(close_gaps(ctx, out, workers, bs, st, stream, pl.mode != HJ_MODE_INNER));
     record(ctx, EV_GAPS, stream);
     ctx->stats.fanout1 = pl.F1; ctx->stats.fanout2 = pl.F2; ctx->stats.buckets = 0; ctx->stats.batches = batches_used;
     ctx->last_algo = 1;
@@ -945,6 +969,8 @@ bool npj_unique(const hjgpu_ctx *ctx, const hjgpu_npj_params *prm)
     return ctx->tune.unique || (prm && (prm->flags & HJGPU_FLAG_UNIQUE));
 }
 
+uint32_t npj_mode(const hjgpu_npj_params *prm) { return prm ? hj_join_mode(prm->flags) : HJ_MODE_INNER; }
+
 int npj_prepare(hjgpu_ctx *ctx, size_t inner, const hjgpu_npj_params *prm, size_t *buckets,
                 uint32_t *factor)
 {
@@ -965,17 +991,17 @@ int npj_prepare(hjgpu_ctx *ctx, size_t inner, const hjgpu_npj_params *prm, size_
 
 int npj_probe_enqueue(hjgpu_ctx *ctx, const uint32_t *sk, const uint32_t *sv, size_t outer,
                       const u64 *table, size_t buckets, uint32_t factor, const hjgpu_output *out,
-                      hipStream_t stream, bool line_hash, bool unique)
+                      hipStream_t stream, bool line_hash, bool unique, uint32_t mode)
 {
     DevState *st = reinterpret_cast<DevState *>(ctx->state.p);
     u64 bs = 0, bl = 0;
     const int grid = hj_npj_probe_grid(ctx->cus, outer);
-    CHK(setup_output(ctx, out, (uint32_t)grid * 4, &bs, &bl));
+    CHK(setup_output(ctx, out, (uint32_t)grid * 4, &bs, &bl, mode));
     if (outer) {
         NpjProbeArgs pa;
         memset(&pa, 0, sizeof(pa));
         pa.keys = sk; pa.vals = sv; pa.n = outer; pa.table = table; pa.buckets = buckets;
-        pa.factor = factor; pa.line_hash = line_hash ? 1u : 0u; pa.unique = unique ? 1u : 0u; pa.result = &st->result;
+        pa.factor = factor; pa.line_hash = line_hash ? 1u : 0u; pa.unique = (unique || mode) ? 1u : 0u; pa.mode = mode; pa.result = &st->result;
         if (bs) {
             pa.ok = out->d_keys; pa.oov = out->d_outer_vals; pa.oiv = out->d_inner_vals;
             pa.block_size = bs; pa.block_limit = bl; pa.block_counter = &st->block_counter;
@@ -984,14 +1010,14 @@ int npj_probe_enqueue(hjgpu_ctx *ctx, const uint32_t *sk, const uint32_t *sv, si
         CHK(hj_launch_npj_probe(pa, ctx->cus, stream, nullptr));
     }
     record(ctx, EV_JOIN, stream);
-    if (bs && outer) CHK(close_gaps(ctx, out, (uint32_t)grid * 4, bs, st, stream));
+    if (bs && outer) CHK(close_gaps(ctx, out, (uint32_t)grid * 4, bs, st, stream, mode != HJ_MODE_INNER));
     record(ctx, EV_GAPS, stream);
     return HJGPU_OK;
 }
 
 int npj_enqueue(hjgpu_ctx *ctx, const uint32_t *rk, const uint32_t *rv, size_t inner,
                 const uint32_t *sk, const uint32_t *sv, size_t outer,
-                size_t buckets, uint32_t factor, const hjgpu_output *out, hipStream_t stream, bool unique)
+                size_t buckets, uint32_t factor, const hjgpu_output *out, hipStream_t stream, bool unique, uint32_t mode)
 {
     CHK(refuse_capture(ctx, stream));
     DevState *st = reinterpret_cast<DevState *>(ctx->state.p);
@@ -1005,7 +1031,7 @@ int npj_enqueue(hjgpu_ctx *ctx, const uint32_t *rk, const uint32_t *rv, size_t i
     const bool line = !ctx->tune.npj_refhash;
     if (inner) CHK(hj_launch_npj_build(rk, rv, inner, table, buckets, factor, &st->zero_key, ctx->cus, stream, line));
     record(ctx, EV_R_HIST, stream);     // reused as "end of build"
-    CHK(npj_probe_enqueue(ctx, sk, sv, outer, table, buckets, factor, out, stream, line, unique));
+    CHK(npj_probe_enqueue(ctx, sk, sv, outer, table, buckets, factor, out, stream, line, unique, mode));
     ctx->stats.fanout1 = ctx->stats.fanout2 = 0; ctx->stats.buckets = buckets; ctx->stats.batches = 0;
     ctx->last_algo = 0;
     return HJGPU_OK;
@@ -1465,6 +1491,7 @@ int hjgpu_npj_async(hjgpu_ctx *ctx, const uint32_t *rk, const uint32_t *rv, size
     // the one-shot output is consumed by THIS call whether it succeeds or not: taken before any early return, so that a
     // failed call never leaves it to an unrelated later join (whose caller may have freed the columns by then)
     const hjgpu_output *out = take_async_output(ctx, nullptr);
+    if (prm) CHK(check_join_mode(ctx, prm->flags));
     CHK(check_columns(ctx, rk, rv, inner));
     CHK(check_columns(ctx, sk, sv, outer));
     hipStream_t stream = (hipStream_t)stream_;
@@ -1473,7 +1500,7 @@ int hjgpu_npj_async(hjgpu_ctx *ctx, const uint32_t *rk, const uint32_t *rv, size
     CHK(refuse_capture(ctx, stream));                    // before anything is allocated or probed
     CHK(npj_prepare(ctx, inner, prm, &buckets, &factor));
     ctx->last_had_output = out && out->d_keys;
-    CHK(npj_enqueue(ctx, rk, rv, inner, sk, sv, outer, buckets, factor, out, stream, npj_unique(ctx, prm)));
+    CHK(npj_enqueue(ctx, rk, rv, inner, sk, sv, outer, buckets, factor, out, stream, npj_unique(ctx, prm), npj_mode(prm)));
     if (d_result)
         HIPCHK(ctx, hj_copy_async(d_result, ctx->state.p, sizeof(hjgpu_result), stream));
     return HJGPU_OK;
@@ -1484,6 +1511,7 @@ int hjgpu_npj(hjgpu_ctx *ctx, const uint32_t *rk, const uint32_t *rv, size_t inn
               const hjgpu_npj_params *prm, hjgpu_result *result, const hjgpu_output *out, void *stream_)
 {
     if (!ctx) return HJGPU_EINVAL;
+    if (prm) CHK(check_join_mode(ctx, prm->flags));
     CHK(check_columns(ctx, rk, rv, inner));
     CHK(check_columns(ctx, sk, sv, outer));
     hipStream_t stream = (hipStream_t)stream_;
@@ -1493,7 +1521,7 @@ int hjgpu_npj(hjgpu_ctx *ctx, const uint32_t *rk, const uint32_t *rv, size_t inn
     CHK(npj_prepare(ctx, inner, prm, &buckets, &factor));
     ctx->last_had_output = out && out->d_keys;
     PlainRows plain(ctx, true);
-    CHK(npj_enqueue(ctx, rk, rv, inner, sk, sv, outer, buckets, factor, out, stream, npj_unique(ctx, prm)));
+    CHK(npj_enqueue(ctx, rk, rv, inner, sk, sv, outer, buckets, factor, out, stream, npj_unique(ctx, prm), npj_mode(prm)));
     return finish_blocking(ctx, result, out, stream);
 }
 
@@ -1513,6 +1541,8 @@ static size_t broadcast_rows(const HjTuning &tune, bool big_tables)
 
 static bool broadcast_applies(const HjTuning &tune, size_t inner, size_t outer, uint32_t chunks, const hjgpu_phj_params *prm)
 {
+    // an anti-join with no build rows reports the whole probe side, whatever the plan: one broadcast item per slice with no fill
+    if (prm && hj_join_mode(prm->flags) == HJ_MODE_ANTI && inner == 0 && outer) return true;
     if (tune.no_broadcast) return false;
     if (chunks != 1 || (prm && (prm->fanout1 || prm->fanout2))) return false;    // an explicit plan is honoured
     return inner && outer && inner <= broadcast_rows(tune, true) && inner <= 16383;
@@ -1532,7 +1562,13 @@ static int broadcast_enqueue(hjgpu_ctx *ctx, const uint32_t *rk, const uint32_t 
     const size_t cap = (size_t)hj_join_config_of(ctx->tune, big).cap();
     const size_t nslices = (outer + HJ_JOIN_SLICE - 1) / HJ_JOIN_SLICE;
     const size_t fills = (inner + cap - 1) / cap;
-    const bool unique = ctx->tune.unique || (prm && (prm->flags & HJGPU_FLAG_UNIQUE));
+    const uint32_t jmode = prm ? hj_join_mode(prm->flags) : HJ_MODE_INNER;
+    const bool unique = ctx->tune.unique || (prm && (prm->flags & HJGPU_FLAG_UNIQUE)) || jmode != HJ_MODE_INNER;
+    if (jmode != HJ_MODE_INNER && !hj_join_config_built(hj_join_config_of(ctx->tune, big), true))
+        return fail(ctx, HJGPU_EINVAL, jmode == HJ_MODE_SEMI ? "HJGPU_FLAG_SEMI: the join_cfg geometry of this context has no _UNIQUE instance "
+                                                              "(geometries with one: 512,13,2 and 1024,14,2)"
+                                                            : "HJGPU_FLAG_ANTI: the join_cfg geometry of this context has no _UNIQUE instance "
+                                                              "(geometries with one: 512,13,2 and 1024,14,2)");
     const size_t groups = unique ? 1 : (fills < (size_t)HJ_JOIN_FILL_GROUPS ? fills : (size_t)HJ_JOIN_FILL_GROUPS);
     const size_t items = nslices * groups;
     if (nslices >= (1ull << 32)) return fail(ctx, HJGPU_EINVAL, "probe side too large for a broadcast join");
@@ -1547,7 +1583,7 @@ static int broadcast_enqueue(hjgpu_ctx *ctx, const uint32_t *rk, const uint32_t 
     DevState *st = reinterpret_cast<DevState *>(ctx->state.p);
     const uint32_t workers = (uint32_t)hj_join_workers(ctx->tune, ctx->cus, big, unique);
     u64 bs = 0, bl = 0;
-    CHK(setup_output(ctx, out, workers, &bs, &bl));
+    CHK(setup_output(ctx, out, workers, &bs, &bl, jmode));
 
     record(ctx, EV_BEGIN, stream);
     HIPCHK(ctx, hj_zero_async(st, sizeof(DevState), stream));
@@ -1565,13 +1601,13 @@ static int broadcast_enqueue(hjgpu_ctx *ctx, const uint32_t *rk, const uint32_t 
     ja.P = 1; ja.chunks = 1; ja.f1 = ja.f2 = 1; ja.F1 = ja.F2 = 1;
     ja.tf0 = tf0; ja.tf1 = tf1;
     ja.s_align = align_of(sk); ja.packed = 0;
-    ja.broadcast = 1; ja.sentinel = bm.sentinel; ja.big_tables = big ? 1u : 0u; ja.unique = unique ? 1u : 0u;
+    ja.broadcast = 1; ja.sentinel = bm.sentinel; ja.big_tables = big ? 1u : 0u; ja.unique = unique ? 1u : 0u; ja.mode = jmode;
     ja.result = &st->result; ja.work_counter = &st->work_counter; ja.work_counter2 = &st->work_counter2;
     ja.multi_fill = &st->pad;                           // always 0: a broadcast join's build side is one table fill by construction
     join_output(ctx, ja, out, bs, bl, st);
     CHK(hj_launch_join(ja, ctx->tune, ctx->cus, stream));
     record(ctx, EV_JOIN, stream);
-    if (bs) CHK(close_gaps(ctx, out, workers, bs, st, stream));
+    if (bs) CHK(close_gaps(ctx, out, workers, bs, st, stream, jmode != HJ_MODE_INNER));
     record(ctx, EV_GAPS, stream);
     ctx->stats.fanout1 = 1; ctx->stats.fanout2 = 1; ctx->stats.buckets = 0; ctx->stats.batches = 0;
     ctx->last_algo = 1;
@@ -1640,8 +1676,9 @@ static int phj_grouped(hjgpu_ctx *ctx, uint32_t G, uint32_t chunks,
     memset(&acc, 0, sizeof(acc));
     bool out_on = out && out->d_keys;
     const u64 bs = out_on ? (out->block_size ? out->block_size : 65536) : 0;
+    const uint32_t jmode = prm ? hj_join_mode(prm->flags) : HJ_MODE_INNER;
     for (uint32_t g = 0; g < G; ++g) {
-        if (pc[g].sn == 0 || pc[g].rn == 0) continue;       // nothing can match
+        if (pc[g].sn == 0 || (pc[g].rn == 0 && jmode != HJ_MODE_ANTI)) continue;       // nothing can match (an anti-join reports it all)
         hjgpu_output view;
         const hjgpu_output *vout = nullptr;
         if (out_on) {
@@ -1650,14 +1687,20 @@ static int phj_grouped(hjgpu_ctx *ctx, uint32_t G, uint32_t chunks,
             if (left / bs == 0) { acc.overflow = 1; out_on = false; }
             else {
                 view = *out;
-                view.d_keys += acc.dense; view.d_outer_vals += acc.dense; view.d_inner_vals += acc.dense;
+                view.d_keys += acc.dense; view.d_outer_vals += acc.dense;
+                if (view.d_inner_vals) view.d_inner_vals += acc.dense;
                 view.capacity = left / bs * bs; view.block_size = bs;
                 vout = &view;
             }
         }
-        CHK(phj_prepare(ctx, pc[g].rn, pc[g].sn, prm, chunks, &pl));
-        CHK(phj_enqueue(ctx, pl, g_rk + pc[g].r0, g_rv + pc[g].r0, pc[g].rn, g_sk + pc[g].s0, g_sv + pc[g].s0, pc[g].sn,
-                        vout, stream));
+        if (pc[g].rn == 0) {
+            // an anti-join's group without build rows: all of its probe rows (a broadcast join with no fill)
+            CHK(broadcast_enqueue(ctx, g_rk, g_rv, 0, g_sk + pc[g].s0, g_sv + pc[g].s0, pc[g].sn, prm, vout, stream, nullptr));
+        } else {
+            CHK(phj_prepare(ctx, pc[g].rn, pc[g].sn, prm, chunks, &pl));
+            CHK(phj_enqueue(ctx, pl, g_rk + pc[g].r0, g_rv + pc[g].r0, pc[g].rn, g_sk + pc[g].s0, g_sv + pc[g].s0, pc[g].sn,
+                            vout, stream));
+        }
         DevState h;
         CHK(read_state(ctx, h, stream));
         CHK(hjgpu_get_stats(ctx, &one));
@@ -1730,7 +1773,7 @@ static int phj_grouped_device(hjgpu_ctx *ctx, uint32_t G, uint32_t chunks,
     const PartitionForm pass0 = {.group_bins = l.bins};
     const uint32_t workers = (uint32_t)hj_join_workers(ctx->tune, ctx->cus, pl.big_tables, pl.unique);
     u64 bs = 0, bl = 0;
-    CHK(setup_output(ctx, out, workers, &bs, &bl));
+    CHK(setup_output(ctx, out, workers, &bs, &bl, pl.mode));
     HIPCHK(ctx, hipEventRecord(ctx->grp_ev_pass0[0], stream));
     // pass 0: the probe side first; the build side may still be arriving (hjgpu_phj_overlapped_async)
     CHK(partition_op(ctx, sk, sv, outer, f0, l.F0, g_sk, g_sv, reinterpret_cast<uint64_t *>(d_off + (l.F0 + 1)), pass0, stream));
@@ -1739,7 +1782,8 @@ static int phj_grouped_device(hjgpu_ctx *ctx, uint32_t G, uint32_t chunks,
     // the grouped join's state: cleared ONCE; every wave's output cursor "no block yet"
     HIPCHK(ctx, hj_zero_async(st, sizeof(DevState), stream));
     if (bs) HIPCHK(ctx, hj_fill_async(ctx->final_offsets.p, 0xFFFFFFFFu, (size_t)workers * sizeof(u64), stream));
-    CHK(hj_launch_group_desc(d_off, d_off + (l.F0 + 1), G, l.bins, (u64)cap_r, (u64)cap_s, (u64)inner, (u64)outer, d_desc, &st->group_skew, stream));
+    CHK(hj_launch_group_desc(d_off, d_off + (l.F0 + 1), G, l.bins, (u64)cap_r, (u64)cap_s, (u64)inner, (u64)outer, d_desc, &st->group_skew, stream,
+                             pl.mode == HJ_MODE_ANTI));
     HIPCHK(ctx, hipEventRecord(ctx->grp_ev_pass0[1], stream));
     for (uint32_t g = 0; g < G; ++g) {
         const GroupRun run = {d_desc + 4 * (size_t)g};
@@ -1748,7 +1792,7 @@ static int phj_grouped_device(hjgpu_ctx *ctx, uint32_t G, uint32_t chunks,
         ctx->ev_cur = nullptr;
         CHK(rc);
     }
-    if (bs) CHK(close_gaps(ctx, out, workers, bs, st, stream));
+    if (bs) CHK(close_gaps(ctx, out, workers, bs, st, stream, pl.mode != HJ_MODE_INNER));
     if (d_result) CHK(hj_launch_group_result(&st->result, &st->group_skew, d_result, stream));
     HIPCHK(ctx, hipEventRecord(ctx->grp_ev_pass0[2], stream));
     // the last event every waiter looks at (hjgpu_get_stats), recorded in the context's own set
@@ -1773,6 +1817,7 @@ static int phj_like(hjgpu_ctx *ctx, uint32_t chunks,
     if (!ctx) return HJGPU_EINVAL;
     if (!blocking) out = take_async_output(ctx, out);    // consumed by this call even if it fails below (see hjgpu_npj_async)
     PlainRows plain(ctx, blocking);
+    if (prm) CHK(check_join_mode(ctx, prm->flags));
     CHK(check_columns(ctx, rk, rv, inner));
     CHK(check_columns(ctx, sk, sv, outer));
     if (chunks < 1 || chunks > HJ_MAX_CHUNKS) return fail(ctx, HJGPU_EINVAL, "chunks must be in [1, 256]");
@@ -1784,7 +1829,8 @@ static int phj_like(hjgpu_ctx *ctx, uint32_t chunks,
     const uint32_t groups = grouped_groups(ctx, inner, outer, prm);
     // (the local join of a multi-GPU call - hjgpu_phj_overlapped_async - is always planned on the device: a rank's host thread waits with a
     // deadline or not at all)
-    if (groups > 1 && outer && (grouped_on_device(ctx) || local_join)) {
+    const bool anti_all = prm && hj_join_mode(prm->flags) == HJ_MODE_ANTI && inner == 0 && outer;     // broadcast_applies
+    if (groups > 1 && outer && !anti_all && (grouped_on_device(ctx) || local_join)) {
         CHK(phj_grouped_device(ctx, groups, chunks, rk, rv, inner, sk, sv, outer, prm, out, d_result, stream, (hipEvent_t)inner_ready));
         if (!blocking) {
             // what hjgpu_get_async_status needs to do the join again, host-planned, should a group have been larger than its workspace
@@ -1802,7 +1848,7 @@ static int phj_like(hjgpu_ctx *ctx, uint32_t chunks,
         CHK(phj_grouped(ctx, groups, chunks, rk, rv, inner, sk, sv, outer, prm, out, stream));
         return finish_blocking(ctx, result, out, stream);
     }
-    if (groups > 1 && outer) {
+    if (groups > 1 && outer && !anti_all) {
         // option "group_device" = 0 (or "audit"): this thread waits for pass 0 and for every group - never inside a multi-GPU call, whose
         // rank threads wait with a deadline (hjgpu_phj_overlapped_async is hjgpu_phj_multi's / hjgpu_cpra_multi's local join)
         CHK(phj_grouped(ctx, groups, chunks, rk, rv, inner, sk, sv, outer, prm, out, stream));
@@ -1859,6 +1905,7 @@ int hjgpu_phj_build(hjgpu_ctx *ctx, const uint32_t *rk, const uint32_t *rv, size
                     const hjgpu_phj_params *prm, void *stream_)
 {
     if (!ctx) return HJGPU_EINVAL;
+    if (prm) CHK(refuse_join_mode(ctx, prm->flags, "hjgpu_phj_build"));
     CHK(check_columns(ctx, rk, rv, inner));
     hipStream_t stream = (hipStream_t)stream_;
     HIPCHK(ctx, hipSetDevice(ctx->device));

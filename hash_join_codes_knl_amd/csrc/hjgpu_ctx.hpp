@@ -230,7 +230,12 @@ PlanArgs plan_args(const hjgpu_ctx *ctx, const MetaLayout &m, uint32_t C, uint32
                    uint32_t mask);
 // A join's result rows: the block protocol into ja when bs > 0 (setup_output's block size and limit), and close_gaps after the join
 void join_output(const hjgpu_ctx *ctx, JoinArgs &ja, const hjgpu_output *out, u64 bs, u64 bl, DevState *st);
-int close_gaps(hjgpu_ctx *ctx, const hjgpu_output *out, uint32_t workers, u64 bs, DevState *st, hipStream_t stream);
+// (rows2: the rows of a semi- / anti-join - key and outer_val only, the inner column is left alone)
+int close_gaps(hjgpu_ctx *ctx, const hjgpu_output *out, uint32_t workers, u64 bs, DevState *st, hipStream_t stream, bool rows2 = false);
+// HJGPU_FLAG_SEMI | HJGPU_FLAG_ANTI together: refused
+int check_join_mode(hjgpu_ctx *ctx, uint32_t flags);
+// an entry point without semi- and anti-joins refuses either flag (never an inner join in their place); the text names the flag
+int refuse_join_mode(hjgpu_ctx *ctx, uint32_t flags, const char *entry);
 void choose_fanout(const HjTuning &tune, size_t inner, const hjgpu_phj_params *prm, uint32_t *F1, uint32_t *F2, bool *big_tables);
 void record(hjgpu_ctx *ctx, int which, hipStream_t s);
 int audit_begin(hjgpu_ctx *ctx, int kind, size_t inner, size_t outer, hipStream_t stream, u64 **rec);
@@ -239,7 +244,7 @@ int audit_partitions(hjgpu_ctx *ctx, int stage, const u64 *tuples, const u64 *be
                      hipStream_t stream);
 int refuse_capture(hjgpu_ctx *ctx, hipStream_t stream);
 int check_columns(hjgpu_ctx *ctx, const uint32_t *k, const uint32_t *v, size_t n);
-int setup_output(hjgpu_ctx *ctx, const hjgpu_output *out, uint32_t workers, u64 *block_size, u64 *block_limit);
+int setup_output(hjgpu_ctx *ctx, const hjgpu_output *out, uint32_t workers, u64 *block_size, u64 *block_limit, uint32_t mode = HJ_MODE_INNER);
 uint32_t range_tiles_for(const HjTuning &tune, u64 max_tiles, uint32_t F1);
 uint32_t ranges_of(const HjTuning &tune, u64 max_tiles, uint32_t F1);
 uint32_t ranges_capacity(const HjTuning &tune, u64 max_tiles, uint32_t F1);
@@ -250,7 +255,8 @@ struct PhjPlan {
     uint32_t C, F1, F2, P;
     uint32_t f1, f2, tf0, tf1;
     bool big_tables;
-    bool unique;             // HJGPU_FLAG_UNIQUE / option "unique"
+    bool unique;             // HJGPU_FLAG_UNIQUE / option "unique"; also set for semi- and anti-joins (their first-match walk, one fill group)
+    uint8_t mode;            // HJ_MODE_*: HJGPU_FLAG_SEMI / HJGPU_FLAG_ANTI (a byte: beside the two flags, the plan keeps its size)
     // batched probe-side partitioning: 0 batches = off
     uint32_t batch_ranges;   // pass-1 ranges per batch
     uint32_t batch_cap;      // batches the tables hold
@@ -292,11 +298,12 @@ int phj_enqueue(hjgpu_ctx *ctx, const PhjPlan &pl, const uint32_t *rk, const uin
                 hipEvent_t inner_ready = nullptr, PhjMode mode = PHJ_WHOLE, const PrePieces *pre = nullptr, const GroupRun *grp = nullptr);
 int finish_blocking(hjgpu_ctx *ctx, hjgpu_result *result, const hjgpu_output *out, hipStream_t stream);
 bool npj_unique(const hjgpu_ctx *ctx, const hjgpu_npj_params *prm);
+uint32_t npj_mode(const hjgpu_npj_params *prm);
 int npj_prepare(hjgpu_ctx *ctx, size_t inner, const hjgpu_npj_params *prm, size_t *buckets, uint32_t *factor);
 int npj_probe_enqueue(hjgpu_ctx *ctx, const uint32_t *sk, const uint32_t *sv, size_t outer, const u64 *table, size_t buckets, uint32_t factor,
-                      const hjgpu_output *out, hipStream_t stream, bool line_hash = false, bool unique = false);
+                      const hjgpu_output *out, hipStream_t stream, bool line_hash = false, bool unique = false, uint32_t mode = HJ_MODE_INNER);
 int npj_enqueue(hjgpu_ctx *ctx, const uint32_t *rk, const uint32_t *rv, size_t inner, const uint32_t *sk, const uint32_t *sv, size_t outer,
-                size_t buckets, uint32_t factor, const hjgpu_output *out, hipStream_t stream, bool unique);
+                size_t buckets, uint32_t factor, const hjgpu_output *out, hipStream_t stream, bool unique, uint32_t mode = HJ_MODE_INNER);
 const hjgpu_output *take_async_output(hjgpu_ctx *ctx, const hjgpu_output *given);
 // hjgpu_ops.hip: the partition operator on one relation (hjgpu_partition*, hjgpu_partition_packed_*; pass 0 of a grouped plan) - what
 // differs between its forms

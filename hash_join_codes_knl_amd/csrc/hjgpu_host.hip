@@ -454,6 +454,8 @@ static int join_host_impl(hjgpu_ctx *ctx, int algorithm,
                           const hjgpu_host_rows *rows, hjgpu_result *result, hjgpu_stats *stats, uint64_t *cursor)
 {
     if (!ctx || algorithm < 0 || algorithm > 2) return HJGPU_EINVAL;
+    if (pp) CHK(refuse_join_mode(ctx, pp->flags, "hjgpu_join_host"));
+    if (np) CHK(refuse_join_mode(ctx, np->flags, "hjgpu_join_host"));
     if ((inner && (!ik || !iv)) || (outer && (!ok || !ov))) return fail(ctx, HJGPU_EINVAL, "null column");
     HIPCHK(ctx, hipSetDevice(ctx->device));
     {

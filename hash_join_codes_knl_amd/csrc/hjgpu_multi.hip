@@ -1961,27 +1961,39 @@ int hjgpu_comm_preflight(hjgpu_comm *c, size_t link_bytes, hjgpu_preflight *rep)
     return HJGPU_OK;
 }
 
+// HJGPU_FLAG_SEMI / _ANTI: no multi-GPU semi- or anti-join - refused, never an inner join in its place
+static int refuse_join_mode_multi(hjgpu_comm *c, uint32_t flags, const char *entry)
+{
+    if (!(flags & (HJGPU_FLAG_SEMI | HJGPU_FLAG_ANTI))) return HJGPU_OK;
+    return cfail(c, HJGPU_EINVAL, entry, (flags & HJGPU_FLAG_SEMI) ? "HJGPU_FLAG_SEMI is not supported by the multi-GPU joins"
+                                                                  : "HJGPU_FLAG_ANTI is not supported by the multi-GPU joins");
+}
+
 int hjgpu_phj_multi(hjgpu_comm *c, const hjgpu_shard *shards, int root, const hjgpu_phj_params *params,
                     hjgpu_result *result, hjgpu_multi_stats *stats)
 {
+    if (params) CHKM(refuse_join_mode_multi(c, params->flags, "hjgpu_phj_multi"));
     return replicated_join(c, 1, shards, nullptr, root, params, nullptr, result, stats);
 }
 
 int hjgpu_npj_multi(hjgpu_comm *c, const hjgpu_shard *shards, int root, const hjgpu_npj_params *params,
                     hjgpu_result *result, hjgpu_multi_stats *stats)
 {
+    if (params) CHKM(refuse_join_mode_multi(c, params->flags, "hjgpu_npj_multi"));
     return replicated_join(c, 0, shards, nullptr, root, nullptr, params, result, stats);
 }
 
 int hjgpu_cpra_multi(hjgpu_comm *c, const hjgpu_shard *shards, const hjgpu_phj_params *params, int slices,
                      hjgpu_result *result, hjgpu_multi_stats *stats)
 {
+    if (params) CHKM(refuse_join_mode_multi(c, params->flags, "hjgpu_cpra_multi"));
     return cpra_join(c, shards, nullptr, params, slices, result, stats);
 }
 
 int hjgpu_phj_multi_rows(hjgpu_comm *c, const hjgpu_shard *shards, hjgpu_shard_rows *rows, int root,
                          const hjgpu_phj_params *params, hjgpu_result *result, hjgpu_multi_stats *stats)
 {
+    if (params) CHKM(refuse_join_mode_multi(c, params->flags, "hjgpu_phj_multi_rows"));
     if (!rows) return cfail(c, HJGPU_EINVAL, "hjgpu_phj_multi_rows: rows is required");
     return replicated_join(c, 1, shards, rows, root, params, nullptr, result, stats);
 }
@@ -1989,6 +2001,7 @@ int hjgpu_phj_multi_rows(hjgpu_comm *c, const hjgpu_shard *shards, hjgpu_shard_r
 int hjgpu_npj_multi_rows(hjgpu_comm *c, const hjgpu_shard *shards, hjgpu_shard_rows *rows, int root,
                          const hjgpu_npj_params *params, hjgpu_result *result, hjgpu_multi_stats *stats)
 {
+    if (params) CHKM(refuse_join_mode_multi(c, params->flags, "hjgpu_npj_multi_rows"));
     if (!rows) return cfail(c, HJGPU_EINVAL, "hjgpu_npj_multi_rows: rows is required");
     return replicated_join(c, 0, shards, rows, root, nullptr, params, result, stats);
 }
@@ -1996,6 +2009,7 @@ int hjgpu_npj_multi_rows(hjgpu_comm *c, const hjgpu_shard *shards, hjgpu_shard_r
 int hjgpu_cpra_multi_rows(hjgpu_comm *c, const hjgpu_shard *shards, hjgpu_shard_rows *rows, const hjgpu_phj_params *params,
                           int slices, hjgpu_result *result, hjgpu_multi_stats *stats)
 {
+    if (params) CHKM(refuse_join_mode_multi(c, params->flags, "hjgpu_cpra_multi_rows"));
     if (!rows) return cfail(c, HJGPU_EINVAL, "hjgpu_cpra_multi_rows: rows is required");
     return cpra_join(c, shards, rows, params, slices, result, stats);
 }
@@ -2017,6 +2031,8 @@ static int join_host_multi_impl(hjgpu_comm *c, int algorithm,
     if (!c || algorithm < 0 || algorithm > 2) return HJGPU_EINVAL;
     CHKM(refuse_broken(c));
     if ((int)c->ranks.size() != c->nranks) return cfail(c, HJGPU_EINVAL, "hjgpu_join_host_multi needs a local communicator");
+    if (pp) CHKM(refuse_join_mode_multi(c, pp->flags, "hjgpu_join_host_multi"));
+    if (np) CHKM(refuse_join_mode_multi(c, np->flags, "hjgpu_join_host_multi"));
     if ((inner && (!ik || !iv)) || (outer && (!ok || !ov))) return cfail(c, HJGPU_EINVAL, "null column");
     if (host_rows && (!result || (host_rows->capacity && (!host_rows->keys || !host_rows->outer_vals || !host_rows->inner_vals))))
         return cfail(c, HJGPU_EINVAL, "hjgpu_join_host_rows_multi: result and the three result columns are required");

@@ -125,6 +125,7 @@ int hjgpu_join_partitions(hjgpu_ctx *ctx,
 {
     if (!ctx || !passes || !roff || !soff || !rk || !rv || !sk || !sv)
         return fail(ctx, HJGPU_EINVAL, "null pointer");
+    CHK(refuse_join_mode(ctx, passes->flags, "hjgpu_join_partitions"));
     if (((uintptr_t)sk & 15) || ((uintptr_t)sv & 15))
         return fail(ctx, HJGPU_EALIGN, "probe columns must be 16-byte aligned");
     hipStream_t stream = (hipStream_t)stream_;
@@ -261,6 +262,7 @@ int hjgpu_prepartitioned_plan(hjgpu_ctx *ctx, size_t inner, uint32_t fanout1, co
                               uint32_t *fanout2, uint32_t *factor2)
 {
     if (!ctx || !fanout1 || !fanout2 || !factor2) return HJGPU_EINVAL;
+    if (params) CHK(refuse_join_mode(ctx, params->flags, "hjgpu_prepartitioned_plan"));
     bool big = false;
     prepartitioned_plan(ctx, inner, fanout1, params, fanout2, &big);
     *factor2 = (params && params->factor2) ? params->factor2 : DEFAULT_F2;
@@ -289,6 +291,7 @@ int hjgpu_phj_build_prepartitioned(hjgpu_ctx *ctx, const uint64_t *d_tuples, con
                                    size_t max_outer, const hjgpu_phj_params *prm, void *stream_)
 {
     if (!ctx) return HJGPU_EINVAL;
+    if (prm) CHK(refuse_join_mode(ctx, prm->flags, "hjgpu_phj_build_prepartitioned"));
     PrePieces pre;
     size_t inner = 0;
     CHK(check_layout(ctx, d_tuples, lay, &pre.ch[0], &inner));

@@ -73,10 +73,19 @@ constexpr int hj_join_waves_per_simd(int block, int log2slots)
 #define HJ_EMIT4 1
 #endif
 // NTROWS: result rows through non-temporal stores (EmitterT<true>; JoinArgs::nt_rows) - false only for solo joins
-template <int BLOCK, int LOG2SLOTS, int BATCH, bool PACKED, bool UNIQUE, bool DEDUP = false, bool NTROWS = true>
-__global__ __launch_bounds__(BLOCK, hj_join_waves_per_simd(BLOCK, LOG2SLOTS)) void join_kernel(JoinArgs a)
+// MODE (HJ_MODE_*): what a probe tuple reports.  HJ_MODE_INNER: its matches (join_kernel).  HJ_MODE_SEMI / HJ_MODE_ANTI
+// (exists_probe_kernel, always with UNIQUE): ONE row (key, outer_val) when it has a match / when it has none, from its match state -
+// the first-match walk of _UNIQUE; rows of two columns (EmitterT<.., 2>), aggregates without sum_inner_vals.  Anti-join details:
+//   * the probe rows of an item with no build rows (a partition or group without build tuples, or a whole join with inner == 0) are
+//     all reported - the plan gives such partitions work items under ANTI (PlanArgs::anti);
+//   * a multi-fill item (DEDUP) only sets its rows' `matched` bits during the fills and reports the rows whose bit is clear in ONE
+//     more pass over its probe rows after the last fill;
+//   * a broadcast join's probe key equal to the sentinel matches nothing and is reported.
+template <int BLOCK, int LOG2SLOTS, int BATCH, bool PACKED, bool UNIQUE, bool DEDUP, bool NTROWS, int MODE>
+__device__ __forceinline__ void join_body(JoinArgs a)
 {
     static_assert(UNIQUE || !DEDUP, "DEDUP is the multi-fill half of a _UNIQUE join");
+    static_assert(MODE == HJ_MODE_INNER || (UNIQUE && NTROWS), "semi- and anti-joins walk to the first match, rows non-temporal");
     // the plan found no partition that takes several fills (the planned case): nothing for this launch to do
     if (DEDUP && a.multi_fill && *a.multi_fill == 0) return;
     constexpr uint32_t SLOTS = 1u << LOG2SLOTS;
@@ -105,7 +114,7 @@ __global__ __launch_bounds__(BLOCK, hj_join_waves_per_simd(BLOCK, LOG2SLOTS)) vo
     const u64 *__restrict__ r64 = reinterpret_cast<const u64 *>(a.rk);
     const uint32_t tf0 = a.tf0, tf1 = a.tf1;
 
-    EmitterT<NTROWS> em;
+    EmitterT<NTROWS, MODE == HJ_MODE_INNER ? 3 : 2> em;
     em.init(a.ok, a.oov, a.oiv, a.block_size, a.block_limit, a.block_counter, a.overflow,
             &wave_cursor[wave]);
     // (the multi-fill half of a _UNIQUE join runs behind the single-fill half on the same stream, with the same grid: wave w of
@@ -117,6 +126,7 @@ __global__ __launch_bounds__(BLOCK, hj_join_waves_per_simd(BLOCK, LOG2SLOTS)) vo
     u64 acc_n = 0, acc_k = 0, acc_o = 0, acc_i = 0;
     uint32_t empty = 0;
     uint32_t q = 0;
+    bool anti_tail = false;                          // HJ_MODE_ANTI: the pass that reports the item's rows without a match
 
     // ---- visit rows [fill_beg, fill_end) of the chunk-concatenated build partition q ----
     // rows below `from_row` were already inserted (from the prefetch registers)
@@ -181,6 +191,23 @@ __global__ __launch_bounds__(BLOCK, hj_join_waves_per_simd(BLOCK, LOG2SLOTS)) vo
         }
     };
 
+    // semi- / anti-join: the tuples j of a probe vector with bit j of `rep` leave as rows (key, outer_val)
+    auto report4 = [&](const uint32_t (&key)[4], const uint32_t (&val)[4], uint32_t rep) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const bool r = (rep >> j) & 1u;
+            acc_n += r ? 1u : 0u; acc_k += r ? key[j] : 0u; acc_o += r ? val[j] : 0u;
+        }
+        if (a.ok) {
+            const uint32_t none[4] = {0u, 0u, 0u, 0u};
+            if (rep == 15u && a.block_size >= 512) em.emit4(key, val, none);       // (emit4: blocks of 512 rows and more)
+            else if (rep) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) if ((rep >> j) & 1u) em.emit(key[j], val[j], 0u);
+            }
+        }
+    };
+
     // ---- stream the S rows [gb, ge): BATCH key + BATCH payload vectors in flight per lane ----
     // `row0`: index of row gb among the probe rows of this work item (UNIQUE's `matched` bits)
     auto for_each_probe_vector = [&](u64 gb, u64 ge, u64 row0, auto probe4) {
@@ -201,6 +228,32 @@ __global__ __launch_bounds__(BLOCK, hj_join_waves_per_simd(BLOCK, LOG2SLOTS)) vo
                 if (g >= ge) break;
                 const uint32_t key[4] = {kk[u].x, PACKED ? kk[u].z : kk[u].y, PACKED ? vv[u].x : kk[u].z, PACKED ? vv[u].z : kk[u].w};
                 const uint32_t val[4] = {PACKED ? kk[u].y : vv[u].x, PACKED ? kk[u].w : vv[u].y, PACKED ? vv[u].y : vv[u].z, vv[u].w};
+                if constexpr (MODE != HJ_MODE_INNER) {
+                    // inr: the rows of the slice that are still open (DEDUP: not reported by an earlier fill); valid: those that may match -
+                    // a probe key equal to the broadcast sentinel matches nothing (see below), and the anti-join reports it
+                    bool inr[4], valid[4];
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        const uint32_t row = (uint32_t)(row0 + (g + j - gb));
+                        inr[j] = (g + j >= gb) && (g + j < ge);
+                        if (dedup && inr[j]) inr[j] = !((matched[row >> 5] >> (row & 31)) & 1u);
+                        valid[j] = inr[j] && (PACKED || key[j] != empty);
+                    }
+                    const uint32_t hits = anti_tail ? 0u : probe4(key, val, valid);
+                    if (dedup) {
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) {
+                            const uint32_t row = (uint32_t)(row0 + (g + j - gb));
+                            if ((hits >> j) & 1u) atomicOr(&matched[row >> 5], 1u << (row & 31));
+                        }
+                    }
+                    uint32_t rep = 0;
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) rep |= (inr[j] && (((hits >> j) & 1u) != 0) == (MODE == HJ_MODE_SEMI)) ? 1u << j : 0u;
+                    if (MODE == HJ_MODE_ANTI && dedup && !anti_tail) rep = 0;       // the fills only mark; the tail pass reports
+                    report4(key, val, rep);
+                    continue;
+                }
                 bool valid[4];
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
@@ -248,6 +301,11 @@ __global__ __launch_bounds__(BLOCK, hj_join_waves_per_simd(BLOCK, LOG2SLOTS)) vo
             t1[j] = tab64[a1];
             t2[j] = tab64[a2];
 #endif
+        }
+        if constexpr (MODE != HJ_MODE_INNER) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) hits |= (valid[j] && ((uint32_t)t1[j] == key[j] || (uint32_t)t2[j] == key[j])) ? 1u << j : 0u;
+            return hits;
         }
         u64 sk_ = 0, so_ = 0, si_ = 0;
         uint32_t n = 0;
@@ -321,11 +379,13 @@ __global__ __launch_bounds__(BLOCK, hj_join_waves_per_simd(BLOCK, LOG2SLOTS)) vo
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const bool hit = live[j] && (t[j].x == key[j]);
-                acc_n += hit ? 1u : 0u;
-                acc_k += hit ? key[j] : 0u;
-                acc_o += hit ? val[j] : 0u;
-                acc_i += hit ? t[j].y : 0u;
-                if (a.ok) { if (hit) em.emit(key[j], val[j], t[j].y); }
+                if constexpr (MODE == HJ_MODE_INNER) {
+                    acc_n += hit ? 1u : 0u;
+                    acc_k += hit ? key[j] : 0u;
+                    acc_o += hit ? val[j] : 0u;
+                    acc_i += hit ? t[j].y : 0u;
+                    if (a.ok) { if (hit) em.emit(key[j], val[j], t[j].y); }
+                }
                 hits |= hit ? 1u << j : 0u;
                 live[j] = live[j] && (t[j].x != empty) && !(UNIQUE && hit);
                 slot[j] = (slot[j] + step[j]) & MASK;
@@ -469,7 +529,8 @@ __global__ __launch_bounds__(BLOCK, hj_join_waves_per_simd(BLOCK, LOG2SLOTS)) vo
             // build rows of the NEXT item: issue the loads now, they land during this probe
             // (not in the DEDUP instance: the 16 prefetch registers are what it would spill to scratch, and no shipped
             // kernel may use scratch - see the note at hj_launch_join)
-            if (!DEDUP && fill_beg == 0 && C == 1 && PACKED && d_item[par ^ 1] < total_items) {
+            // (nor in the semi- / anti-join instances: their report path leaves no room for them either, 3 VGPRs spilled)
+            if (MODE == HJ_MODE_INNER && !DEDUP && fill_beg == 0 && C == 1 && PACKED && d_item[par ^ 1] < total_items) {
                 const u64 nb = d_rb[par ^ 1];
                 pre_rows = min(min(d_rn[par ^ 1], (u64)BLOCK * RB), (u64)CAP);
 #pragma unroll
@@ -499,6 +560,16 @@ __global__ __launch_bounds__(BLOCK, hj_join_waves_per_simd(BLOCK, LOG2SLOTS)) vo
             }
             __syncthreads();   // table is reused by the next fill / work item
         }
+        if constexpr (MODE == HJ_MODE_ANTI) {
+            // an item without build rows reports all its probe rows; a multi-fill item the rows no fill has marked
+            if (DEDUP || rows_beg >= rows_end) {
+                auto probe4_none = [](const uint32_t (&)[4], const uint32_t (&)[4], const bool (&)[4]) -> uint32_t { return 0u; };
+                anti_tail = true;
+                probe_item(slice, nslices, probe4_none);
+                anti_tail = false;
+                if (DEDUP) __syncthreads();          // every lane has read `matched` before the next item clears it
+            }
+        }
         if (rows_beg >= rows_end) __syncthreads();   // no fill (a trailing fill group of an oversize partition): publish the next claim
         par ^= 1;
     }
@@ -518,6 +589,21 @@ __global__ __launch_bounds__(BLOCK, hj_join_waves_per_simd(BLOCK, LOG2SLOTS)) vo
         u64 *dst = reinterpret_cast<u64 *>(a.result) + tid;
         if (s) atomicAdd(dst, s);
     }
+}
+
+template <int BLOCK, int LOG2SLOTS, int BATCH, bool PACKED, bool UNIQUE, bool DEDUP = false, bool NTROWS = true>
+__global__ __launch_bounds__(BLOCK, hj_join_waves_per_simd(BLOCK, LOG2SLOTS)) void join_kernel(JoinArgs a)
+{
+    join_body<BLOCK, LOG2SLOTS, BATCH, PACKED, UNIQUE, DEDUP, NTROWS, HJ_MODE_INNER>(a);
+}
+
+// Semi- and anti-joins (HJGPU_FLAG_SEMI / _ANTI): the _UNIQUE join's two launches - single-fill items, then multi-fill ones (DEDUP) -
+// reporting each probe tuple's match state.  A kernel of its own name: every join_kernel instance is a three-column inner join
+// (tests/test_store_policy_isa.py reads them so).  Rows are always non-temporal (no solo instance).
+template <int BLOCK, int LOG2SLOTS, int BATCH, bool PACKED, int MODE, bool DEDUP>
+__global__ __launch_bounds__(BLOCK, hj_join_waves_per_simd(BLOCK, LOG2SLOTS)) void exists_probe_kernel(JoinArgs a)
+{
+    join_body<BLOCK, LOG2SLOTS, BATCH, PACKED, true, DEDUP, true, MODE>(a);
 }
 
 #include <stdlib.h>
@@ -554,7 +640,8 @@ __global__ __launch_bounds__(1024) void broadcast_meta_kernel(const uint32_t *__
 int hj_launch_broadcast_meta(const uint32_t *inner_keys, size_t inner, size_t outer, uint32_t nslices,
                              uint32_t groups, const BroadcastMeta &m, hipStream_t stream)
 {
-    if (inner == 0 || inner > 16383 || nslices == 0 || groups == 0) return HJGPU_EINVAL;
+    // (inner == 0: an anti-join with no build rows - every item reports its whole probe slice)
+    if (inner > 16383 || nslices == 0 || groups == 0) return HJGPU_EINVAL;
     hipLaunchKernelGGL(broadcast_meta_kernel, dim3(1), dim3(1024), 0, stream, inner_keys, (u64)inner, (u64)outer,
                        nslices, groups, m);
     return hipGetLastError() == hipSuccess ? HJGPU_OK : HJGPU_EHIP;
@@ -625,6 +712,18 @@ bool hj_join_config_built(const JoinConfig &c, bool unique)
         return hipGetLastError() == hipSuccess ? HJGPU_OK : HJGPU_EHIP;                           \
     }
 
+// a semi- or anti-join: the same two launches as a _UNIQUE join, exists_probe_kernel instead of join_kernel
+#define EXISTS_LAUNCH(B, L, U, P, M, DD, ARGS) \
+    hipLaunchKernelGGL((exists_probe_kernel<B, L, U, P, M, DD>), dim3(join_grid(cus, c)), dim3(B), 0, stream, ARGS)
+#define EXISTS_CASE(B, L, M)                                                                      \
+    if (c.block == B && c.log2slots == L && b.mode == M) {                                        \
+        JoinArgs d = b;                                                                           \
+        d.work_counter = b.work_counter2;                                                         \
+        if (b.packed) { EXISTS_LAUNCH(B, L, 2, true, M, false, b); EXISTS_LAUNCH(B, L, 1, true, M, true, d); }      \
+        else { EXISTS_LAUNCH(B, L, 2, false, M, false, b); EXISTS_LAUNCH(B, L, 1, false, M, true, d); }             \
+        return hipGetLastError() == hipSuccess ? HJGPU_OK : HJGPU_EHIP;                           \
+    }
+
 int hj_launch_join(const JoinArgs &a, const HjTuning &t, int cus, hipStream_t stream)
 {
     if ((a.P < 2 && !a.broadcast) || a.P < 1 || a.chunks == 0) return HJGPU_EINVAL;
@@ -632,7 +731,14 @@ int hj_launch_join(const JoinArgs &a, const HjTuning &t, int cus, hipStream_t st
     JoinArgs b = a;
     b.force_chained = t.force_chained ? 1u : 0u;       // tests: exercise the fallback table everywhere
     b.unique = (a.unique || t.unique) ? 1u : 0u;
-    if (b.unique && !b.work_counter2) return HJGPU_EINVAL;
+    if ((b.unique || b.mode) && !b.work_counter2) return HJGPU_EINVAL;
+    if (b.mode != HJ_MODE_INNER) {
+        EXISTS_CASE(512, 13, HJ_MODE_SEMI)
+        EXISTS_CASE(512, 13, HJ_MODE_ANTI)
+        EXISTS_CASE(1024, 14, HJ_MODE_SEMI)
+        EXISTS_CASE(1024, 14, HJ_MODE_ANTI)
+        return HJGPU_EINVAL;                           // a geometry without a _UNIQUE instance (hj_join_config_built)
+    }
     JOIN_CASE_UNIQUE(512, 13)
     JOIN_CASE_UNIQUE(1024, 14)
     JOIN_CASE(512, 13, 2, false)

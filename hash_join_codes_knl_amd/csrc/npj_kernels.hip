@@ -178,6 +178,136 @@ __global__ __launch_bounds__(NPJ_PROBE_BLOCK) void npj_probe_kernel(NpjProbeArgs
 }
 
 
+// Semi- / anti-join probes (HJGPU_FLAG_SEMI / _ANTI).  The inner-join kernels above stay as they are (their machine code is the library's
+// yardstick); this body is their walk with a compile-time MODE, instantiated for the two new modes only.
+// MODE (HJ_MODE_*, npj_exists_kernel): semi- / anti-join - with UNIQUE's walk, ONE row (key, outer_val) per probe tuple that found a
+// match / that reached an empty bucket without one.
+template <bool GROUPED, bool UNIQUE, int MODE>
+__device__ __forceinline__ void npj_exists_body(NpjProbeArgs a)
+{
+    static_assert(MODE != HJ_MODE_INNER && UNIQUE, "semi- and anti-joins walk to the first match");
+    constexpr int NW = NPJ_PROBE_BLOCK / 64;
+    __shared__ u64 red[4][NW];
+    __shared__ u64 wave_cursor[NW];
+    const int wave = threadIdx.x >> 6;
+    EmitterT<true, MODE == HJ_MODE_INNER ? 3 : 2> em;
+    em.init(a.ok, a.oov, a.oiv, a.block_size, a.block_limit, a.block_counter, a.overflow,
+            &wave_cursor[wave]);
+    if (hj_lane() == 0) wave_cursor[wave] = HJ_NO_CURSOR;
+
+    const uint32_t a0 = (uint32_t)(((uintptr_t)a.keys >> 2) & 3);
+    const uint4 *__restrict__ k4 = reinterpret_cast<const uint4 *>(a.keys - a0);
+    const uint4 *__restrict__ v4 = reinterpret_cast<const uint4 *>(a.vals - a0);
+    const u64 gb = a0, ge = a0 + a.n;
+    const u64 nvec = (ge + 3) >> 2;
+    const u64 stride = (u64)gridDim.x * NPJ_PROBE_BLOCK;
+    const u64 *__restrict__ table = a.table;
+    const u64 buckets = a.buckets;
+    const uint32_t factor = a.factor;
+
+    u64 acc_n = 0, acc_k = 0, acc_o = 0, acc_i = 0;
+    for (u64 v = (u64)blockIdx.x * NPJ_PROBE_BLOCK + threadIdx.x; v < nvec; v += stride) {
+        const uint4 kk = k4[v], vv = v4[v];
+        const u64 g = v << 2;
+        const uint32_t key[4] = {kk.x, kk.y, kk.z, kk.w};
+        const uint32_t val[4] = {vv.x, vv.y, vv.z, vv.w};
+        u64 h[4];
+        bool act[4], in[4], hit[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            act[j] = (g + j >= gb) && (g + j < ge);
+            in[j] = act[j]; hit[j] = false;
+            h[j] = npj_bucket(key[j], factor, buckets);
+        }
+        if (GROUPED) {
+            const uint4 *__restrict__ t4 = reinterpret_cast<const uint4 *>(table);
+            while (act[0] | act[1] | act[2] | act[3]) {
+                uint4 lo[4], hi[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {           // all group loads of the 4 chains in flight together
+                    lo[j] = make_uint4(0, 0, 0, 0); hi[j] = lo[j];
+                    if (act[j]) { const u64 grp = h[j] >> 2; lo[j] = t4[2 * grp]; hi[j] = t4[2 * grp + 1]; }
+                }
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    if (act[j]) {
+                        const uint32_t bk[4] = {lo[j].x, lo[j].z, hi[j].x, hi[j].z};   // keys of the group
+                        const uint32_t bv[4] = {lo[j].y, lo[j].w, hi[j].y, hi[j].w};   // payloads
+                        const uint32_t first = (uint32_t)h[j] & 3u;
+                        bool open = true;                                              // no empty bucket seen yet
+#pragma unroll
+                        for (int b = 0; b < 4; ++b) {
+                            const bool inb = open && ((uint32_t)b >= first);
+                            if (inb && bk[b] == 0u) open = false;
+                            else if (inb && bk[b] == key[j]) {
+                                if constexpr (MODE == HJ_MODE_INNER) {
+                                    acc_n += 1; acc_k += key[j]; acc_o += val[j]; acc_i += bv[b];
+                                    em.emit(key[j], val[j], bv[b]);
+                                } else hit[j] = true;
+                                if (UNIQUE) open = false;
+                            }
+                        }
+                        if (!open) act[j] = false;
+                        else { h[j] = (h[j] & ~3ull) + 4; if (h[j] >= buckets) h[j] = 0; }
+                    }
+                }
+            }
+        } else {
+            u64 t[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) t[j] = act[j] ? table[h[j]] : 0ull;
+            while (act[0] | act[1] | act[2] | act[3]) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    if (act[j]) {
+                        if ((uint32_t)t[j] == 0u) {
+                            act[j] = false;
+                        } else {
+                            if ((uint32_t)t[j] == key[j]) {
+                                const uint32_t iv = (uint32_t)(t[j] >> 32);
+                                if constexpr (MODE == HJ_MODE_INNER) {
+                                    acc_n += 1; acc_k += key[j]; acc_o += val[j]; acc_i += iv;
+                                    em.emit(key[j], val[j], iv);
+                                } else hit[j] = true;
+                                if (UNIQUE) { act[j] = false; continue; }
+                            }
+                            if (++h[j] == buckets) h[j] = 0;
+                            t[j] = table[h[j]];
+                        }
+                    }
+                }
+            }
+        }
+        if constexpr (MODE != HJ_MODE_INNER) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                if (in[j] && hit[j] == (MODE == HJ_MODE_SEMI)) {
+                    acc_n += 1; acc_k += key[j]; acc_o += val[j];
+                    em.emit(key[j], val[j], 0u);
+                }
+            }
+        }
+    }
+    if (a.ok && hj_lane() == 0)
+        hj_store(&a.final_offsets[(u64)blockIdx.x * NW + wave], wave_cursor[wave]);
+    acc_n = wave_reduce_sum(acc_n); acc_k = wave_reduce_sum(acc_k);
+    acc_o = wave_reduce_sum(acc_o); acc_i = wave_reduce_sum(acc_i);
+    if (hj_lane() == 0) { red[0][wave] = acc_n; red[1][wave] = acc_k; red[2][wave] = acc_o; red[3][wave] = acc_i; }
+    __syncthreads();
+    if (threadIdx.x < 4) {
+        u64 s = 0;
+        for (int i = 0; i < NW; ++i) s += red[threadIdx.x][i];
+        if (s) atomicAdd(reinterpret_cast<u64 *>(a.result) + threadIdx.x, s);
+    }
+}
+
+
+template <bool GROUPED, int MODE>
+__global__ __launch_bounds__(NPJ_PROBE_BLOCK) void npj_exists_kernel(NpjProbeArgs a)
+{
+    npj_exists_body<GROUPED, true, MODE>(a);
+}
+
 // LINE table (the library's own whole joins, hjgpu_npj*): the walk of a key starts on the
 // 64-byte line of 8 buckets it hashes to, h = 8 * H(key, f, buckets / 8), instead of on an
 // arbitrary bucket.  Same bucket format, same CAS build, same walk to the first empty bucket
@@ -306,6 +436,128 @@ __global__ __launch_bounds__(NPJ_PROBE_BLOCK) void npj_probe_line_kernel(NpjProb
     }
 }
 
+// Semi- / anti-join probes (HJGPU_FLAG_SEMI / _ANTI).  The inner-join kernels above stay as they are (their machine code is the library's
+// yardstick); this body is their walk with a compile-time MODE, instantiated for the two new modes only.
+// MODE (HJ_MODE_*, npj_exists_line_kernel): semi- / anti-join - lane 0 of the quad reports the tuple when its walk ends: on a match
+// (`found`, SEMI) or on an empty bucket without one (ANTI).
+template <bool MATERIALIZE, bool UNIQUE, int MODE>
+__device__ __forceinline__ void npj_exists_line_body(NpjProbeArgs a)
+{
+    static_assert(MODE != HJ_MODE_INNER && UNIQUE, "semi- and anti-joins walk to the first match");
+    constexpr int NW = NPJ_PROBE_BLOCK / 64;
+    constexpr int B = 4;                                   // lines in flight per quad
+    __shared__ u64 red[4][NW];
+    __shared__ u64 wave_cursor[NW];
+    const int wave = threadIdx.x >> 6;
+    EmitterT<true, MODE == HJ_MODE_INNER ? 3 : 2> em;
+    em.init(a.ok, a.oov, a.oiv, a.block_size, a.block_limit, a.block_counter, a.overflow,
+            &wave_cursor[wave]);
+    if (hj_lane() == 0) wave_cursor[wave] = HJ_NO_CURSOR;
+
+    const uint32_t a0 = (uint32_t)(((uintptr_t)a.keys >> 2) & 3);
+    const uint4 *__restrict__ k4 = reinterpret_cast<const uint4 *>(a.keys - a0);
+    const uint4 *__restrict__ v4 = reinterpret_cast<const uint4 *>(a.vals - a0);
+    const u64 gb = a0, ge = a0 + a.n;
+    const u64 nvec = (ge + 3) >> 2;
+    const u64 stride = (u64)gridDim.x * NPJ_PROBE_BLOCK;
+    const uint4 *__restrict__ t4 = reinterpret_cast<const uint4 *>(a.table);
+    const u64 lines = a.buckets >> 3;
+    const uint32_t factor = a.factor;
+    const uint32_t sub = threadIdx.x & 3;                  // my quarter of the line: buckets 2*sub, 2*sub + 1
+
+    u64 acc_n = 0, acc_k = 0, acc_o = 0, acc_i = 0;
+    // whole waves iterate together (the quad exchanges below need all four lanes)
+    for (u64 v0 = (u64)blockIdx.x * NPJ_PROBE_BLOCK + (threadIdx.x & ~63u); v0 < nvec; v0 += stride) {
+        const u64 v = v0 + hj_lane();
+        uint4 kk = make_uint4(0, 0, 0, 0), vv = kk;
+        if (v < nvec) { kk = k4[v]; vv = v4[v]; }
+        const u64 g = v << 2;
+        const uint32_t kc[4] = {kk.x, kk.y, kk.z, kk.w}, vc[4] = {vv.x, vv.y, vv.z, vv.w};
+        uint32_t okc[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) okc[j] = (v < nvec && g + j >= gb && g + j < ge) ? 1u : 0u;
+
+        // the quad's 16 tuples (4 lanes x 4 components), B at a time
+#pragma unroll
+        for (int r0 = 0; r0 < 16; r0 += B) {
+            uint32_t key[B], val[B];
+            bool act[B];
+            u64 ln[B];
+            uint4 q[B];
+#pragma unroll
+            for (int i = 0; i < B; ++i) {
+                const int r = r0 + i, comp = r & 3;                     // static after unrolling
+                // the tuple's owner is lane r / 4 of the quad: broadcast its key, payload and validity
+                if (r < 4) { key[i] = quad_perm<0x00>(kc[comp]); val[i] = quad_perm<0x00>(vc[comp]); act[i] = quad_perm<0x00>(okc[comp]) != 0; }
+                else if (r < 8) { key[i] = quad_perm<0x55>(kc[comp]); val[i] = quad_perm<0x55>(vc[comp]); act[i] = quad_perm<0x55>(okc[comp]) != 0; }
+                else if (r < 12) { key[i] = quad_perm<0xAA>(kc[comp]); val[i] = quad_perm<0xAA>(vc[comp]); act[i] = quad_perm<0xAA>(okc[comp]) != 0; }
+                else { key[i] = quad_perm<0xFF>(kc[comp]); val[i] = quad_perm<0xFF>(vc[comp]); act[i] = quad_perm<0xFF>(okc[comp]) != 0; }
+                ln[i] = npj_bucket(key[i], factor, lines);
+                q[i] = make_uint4(0, 0, 0, 0);
+                if (act[i]) {
+                    q[i] = t4[4 * ln[i] + sub];                         // 4 lanes x 16 bytes = the key's line
+                }
+            }
+#pragma unroll
+            for (int i = 0; i < B; ++i) {
+                while (act[i]) {                                        // uniform inside the quad
+                    // first empty bucket of the line, over the quad
+                    uint32_t fe = q[i].x == 0u ? 2 * sub : (q[i].z == 0u ? 2 * sub + 1 : 8u);
+                    fe = min(fe, quad_perm<0xB1>(fe));                  // lanes 0<->1, 2<->3
+                    fe = min(fe, quad_perm<0x4E>(fe));                  // lanes 0<->2, 1<->3
+                    bool m0 = q[i].x == key[i] && 2 * sub < fe;
+                    bool m1 = q[i].z == key[i] && 2 * sub + 1 < fe;
+                    bool found = false;                                 // UNIQUE: some lane of the quad holds a match
+                    if (UNIQUE) {
+                        // only the FIRST match of the walk counts: the lowest matching bucket of the line
+                        uint32_t fm = m0 ? 2 * sub : (m1 ? 2 * sub + 1 : 8u);
+                        const uint32_t mine = fm;
+                        fm = min(fm, quad_perm<0xB1>(fm));
+                        fm = min(fm, quad_perm<0x4E>(fm));
+                        found = fm < 8u;
+                        m0 = m0 && mine == fm && fm == 2 * sub;
+                        m1 = m1 && mine == fm && fm == 2 * sub + 1;
+                    }
+                    if constexpr (MODE == HJ_MODE_INNER) {
+                        const uint32_t m = (m0 ? 1u : 0u) + (m1 ? 1u : 0u);
+                        acc_n += m; acc_k += (u64)key[i] * m; acc_o += (u64)val[i] * m;
+                        acc_i += (m0 ? q[i].y : 0u); acc_i += (m1 ? q[i].w : 0u);
+                        if (MATERIALIZE) {
+                            if (m0) em.emit(key[i], val[i], q[i].y);
+                            if (m1) em.emit(key[i], val[i], q[i].w);
+                        }
+                    } else if (fe < 8u || found) {
+                        if (sub == 0 && found == (MODE == HJ_MODE_SEMI)) {
+                            acc_n += 1; acc_k += key[i]; acc_o += val[i];
+                            if (MATERIALIZE) em.emit(key[i], val[i], 0u);
+                        }
+                    }
+                    if (fe < 8u || (UNIQUE && found)) break;            // the walk ends at the first empty bucket (UNIQUE: first match)
+                    if (++ln[i] == lines) ln[i] = 0;                    // full line: the walk goes on in the next one
+                    q[i] = t4[4 * ln[i] + sub];
+                }
+            }
+        }
+    }
+    if (MATERIALIZE && hj_lane() == 0)
+        hj_store(&a.final_offsets[(u64)blockIdx.x * NW + wave], wave_cursor[wave]);
+    acc_n = wave_reduce_sum(acc_n); acc_k = wave_reduce_sum(acc_k);
+    acc_o = wave_reduce_sum(acc_o); acc_i = wave_reduce_sum(acc_i);
+    if (hj_lane() == 0) { red[0][wave] = acc_n; red[1][wave] = acc_k; red[2][wave] = acc_o; red[3][wave] = acc_i; }
+    __syncthreads();
+    if (threadIdx.x < 4) {
+        u64 s = 0;
+        for (int i = 0; i < NW; ++i) s += red[threadIdx.x][i];
+        if (s) atomicAdd(reinterpret_cast<u64 *>(a.result) + threadIdx.x, s);
+    }
+}
+
+template <bool MATERIALIZE, int MODE>
+__global__ __launch_bounds__(NPJ_PROBE_BLOCK) void npj_exists_line_kernel(NpjProbeArgs a)
+{
+    npj_exists_line_body<MATERIALIZE, true, MODE>(a);
+}
+
 int hj_npj_probe_grid(int cus, size_t n)
 {
     u64 blocks = ((n + 3) / 4 + NPJ_PROBE_BLOCK - 1) / NPJ_PROBE_BLOCK;
@@ -320,14 +572,22 @@ int hj_launch_npj_probe(const NpjProbeArgs &a, int cus, hipStream_t stream, int 
     if (grid_out) *grid_out = grid;
     if (a.line_hash) {
         if (a.buckets % 8 != 0 || ((uintptr_t)a.table & 63)) return HJGPU_EINVAL;
-        if (a.ok && a.unique) hipLaunchKernelGGL((npj_probe_line_kernel<true, true>), dim3(grid), dim3(NPJ_PROBE_BLOCK), 0, stream, a);
+        if (a.mode == HJ_MODE_SEMI && a.ok) hipLaunchKernelGGL((npj_exists_line_kernel<true, HJ_MODE_SEMI>), dim3(grid), dim3(NPJ_PROBE_BLOCK), 0, stream, a);
+        else if (a.mode == HJ_MODE_SEMI) hipLaunchKernelGGL((npj_exists_line_kernel<false, HJ_MODE_SEMI>), dim3(grid), dim3(NPJ_PROBE_BLOCK), 0, stream, a);
+        else if (a.mode == HJ_MODE_ANTI && a.ok) hipLaunchKernelGGL((npj_exists_line_kernel<true, HJ_MODE_ANTI>), dim3(grid), dim3(NPJ_PROBE_BLOCK), 0, stream, a);
+        else if (a.mode == HJ_MODE_ANTI) hipLaunchKernelGGL((npj_exists_line_kernel<false, HJ_MODE_ANTI>), dim3(grid), dim3(NPJ_PROBE_BLOCK), 0, stream, a);
+        else if (a.ok && a.unique) hipLaunchKernelGGL((npj_probe_line_kernel<true, true>), dim3(grid), dim3(NPJ_PROBE_BLOCK), 0, stream, a);
         else if (a.ok) hipLaunchKernelGGL((npj_probe_line_kernel<true, false>), dim3(grid), dim3(NPJ_PROBE_BLOCK), 0, stream, a);
         else if (a.unique) hipLaunchKernelGGL((npj_probe_line_kernel<false, true>), dim3(grid), dim3(NPJ_PROBE_BLOCK), 0, stream, a);
         else hipLaunchKernelGGL((npj_probe_line_kernel<false, false>), dim3(grid), dim3(NPJ_PROBE_BLOCK), 0, stream, a);
         return hipGetLastError() == hipSuccess ? HJGPU_OK : HJGPU_EHIP;
     }
     const bool grouped = (a.buckets % 4 == 0) && (((uintptr_t)a.table & 31) == 0);
-    if (grouped && a.unique) hipLaunchKernelGGL((npj_probe_kernel<true, true>), dim3(grid), dim3(NPJ_PROBE_BLOCK), 0, stream, a);
+    if (a.mode == HJ_MODE_SEMI && grouped) hipLaunchKernelGGL((npj_exists_kernel<true, HJ_MODE_SEMI>), dim3(grid), dim3(NPJ_PROBE_BLOCK), 0, stream, a);
+    else if (a.mode == HJ_MODE_SEMI) hipLaunchKernelGGL((npj_exists_kernel<false, HJ_MODE_SEMI>), dim3(grid), dim3(NPJ_PROBE_BLOCK), 0, stream, a);
+    else if (a.mode == HJ_MODE_ANTI && grouped) hipLaunchKernelGGL((npj_exists_kernel<true, HJ_MODE_ANTI>), dim3(grid), dim3(NPJ_PROBE_BLOCK), 0, stream, a);
+    else if (a.mode == HJ_MODE_ANTI) hipLaunchKernelGGL((npj_exists_kernel<false, HJ_MODE_ANTI>), dim3(grid), dim3(NPJ_PROBE_BLOCK), 0, stream, a);
+    else if (grouped && a.unique) hipLaunchKernelGGL((npj_probe_kernel<true, true>), dim3(grid), dim3(NPJ_PROBE_BLOCK), 0, stream, a);
     else if (grouped) hipLaunchKernelGGL((npj_probe_kernel<true, false>), dim3(grid), dim3(NPJ_PROBE_BLOCK), 0, stream, a);
     else if (a.unique) hipLaunchKernelGGL((npj_probe_kernel<false, true>), dim3(grid), dim3(NPJ_PROBE_BLOCK), 0, stream, a);
     else hipLaunchKernelGGL((npj_probe_kernel<false, false>), dim3(grid), dim3(NPJ_PROBE_BLOCK), 0, stream, a);
@@ -499,7 +759,7 @@ __global__ __launch_bounds__(256) void close_gaps_copy_kernel(
             // (non-temporal like the rows themselves: a move that is lost leaves a hole's stale row inside the dense result)
             hj_store(&k[dst + i], k[src + i]);
             hj_store(&ov[dst + i], ov[src + i]);
-            hj_store(&iv[dst + i], iv[src + i]);
+            if (iv) hj_store(&iv[dst + i], iv[src + i]);         // (semi- / anti-joins: no inner_val column)
         }
     }
 }

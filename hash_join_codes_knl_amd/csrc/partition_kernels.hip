@@ -686,7 +686,8 @@ __device__ __forceinline__ void plan_items_body(const PlanArgs &a)
     const uint32_t cap = a.cap ? a.cap : 1u, cap_shift = 31u - (uint32_t)__clz((int)cap);
     // (probe slices | fill groups << 32) of a partition with nr build and ns probe rows; 0 slices = no work
     auto shape_of = [&](u64 nr, u64 ns) -> u64 {
-        const u64 slices = (nr && ns) ? (ns + HJ_JOIN_SLICE - 1) >> SLICE_SHIFT : 0;
+        // (an anti-join reports the probe rows of a partition without build rows: such a partition has work items too)
+        const u64 slices = ((nr || a.anti) && ns) ? (ns + HJ_JOIN_SLICE - 1) >> SLICE_SHIFT : 0;
         const u64 groups = a.unique ? (u64)1 : min((u64)HJ_JOIN_FILL_GROUPS, max((u64)1, (nr + cap - 1) >> cap_shift));
         return slices | (groups << 32);
     };
@@ -887,7 +888,8 @@ int hj_launch_claimed_pieces(const u64 *off2, const u64 *end2, const u64 *cur2, 
 
 // Grouped plans on the device (hj_internal.hpp: hj_launch_group_desc): one thread per group.
 __global__ __launch_bounds__(256) void group_desc_kernel(const u64 *__restrict__ roff, const u64 *__restrict__ soff, uint32_t G, uint32_t bins,
-                                                         u64 cap_r, u64 cap_s, u64 n_r, u64 n_s, u64 *__restrict__ desc, uint32_t *skew)
+                                                         u64 cap_r, u64 cap_s, u64 n_r, u64 n_s, u64 *__restrict__ desc, uint32_t *skew,
+                                                         uint32_t anti)
 {
     const uint32_t g = blockIdx.x * 256 + threadIdx.x;
     if (g >= G) return;
@@ -897,16 +899,18 @@ __global__ __launch_bounds__(256) void group_desc_kernel(const u64 *__restrict__
     // beyond what the workspace was planned for - or offsets that are no prefix of the relations' rows (a caller who overlaps joins of ONE
     // context on several streams races on its workspace: never an address outside the columns): skipped, the join flagged
     if (rn > cap_r || sn > cap_s || re < rb || se < sb || re > n_r || se > n_s) { atomicOr(skew, 1u); rn = 0; sn = 0; }
-    if (rn == 0 || sn == 0) { rn = 0; sn = 0; }                                 // nothing can match
+    // nothing can match - but an anti-join reports every probe row of a group without build rows (PlanArgs::anti gives them work items)
+    if ((rn == 0 && !anti) || sn == 0) { rn = 0; sn = 0; }
     hj_store(&desc[4 * (u64)g + 0], rb + hj_group_shift(rb, g)); hj_store(&desc[4 * (u64)g + 1], rn);
     hj_store(&desc[4 * (u64)g + 2], sb + hj_group_shift(sb, g)); hj_store(&desc[4 * (u64)g + 3], sn);
 }
 
 int hj_launch_group_desc(const u64 *roff, const u64 *soff, uint32_t G, uint32_t bins, u64 cap_r, u64 cap_s, u64 n_r, u64 n_s, u64 *desc, uint32_t *skew,
-                         hipStream_t stream)
+                         hipStream_t stream, bool anti)
 {
     if (!G || !bins) return HJGPU_EINVAL;
-    hipLaunchKernelGGL(group_desc_kernel, dim3((G + 255) / 256), dim3(256), 0, stream, roff, soff, G, bins, cap_r, cap_s, n_r, n_s, desc, skew);
+    hipLaunchKernelGGL(group_desc_kernel, dim3((G + 255) / 256), dim3(256), 0, stream, roff, soff, G, bins, cap_r, cap_s, n_r, n_s, desc, skew,
+                       anti ? 1u : 0u);
     return hipGetLastError() == hipSuccess ? HJGPU_OK : HJGPU_EHIP;
 }
 

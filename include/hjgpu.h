@@ -55,6 +55,17 @@ extern "C" {
                                      sum_outer_vals count every probe tuple that has a match once, and
                                      sum_inner_vals adds the payload of ONE of its build tuples (which one
                                      depends on insertion order, in the reference as here).               */
+#define HJGPU_FLAG_SEMI   2u      /* semi-join (EXISTS / IN): ONE result row (key, outer_val) for every probe tuple whose key
+                                     equals at least one build key.  hjgpu_phj, hjgpu_cpra, hjgpu_npj, their _async forms and
+                                     hjgpu_phj_overlapped_async; every other join entry point refuses it (HJGPU_EINVAL).   */
+#define HJGPU_FLAG_ANTI   4u      /* anti-join (NOT EXISTS / NOT IN): ONE result row for every probe tuple whose key equals
+                                     no build key (all of them when inner == 0).  Same entry points as HJGPU_FLAG_SEMI.
+                                     For both: probe-side duplicates are reported one by one (bag semantics), build-side
+                                     duplicates never multiply a row; count / sum_keys / sum_outer_vals are taken over the
+                                     reported probe tuples, sum_inner_vals is 0; hjgpu_output::d_inner_vals is neither read
+                                     nor written and may be NULL.  SEMI | ANTI: HJGPU_EINVAL.  HJGPU_FLAG_UNIQUE (or option
+                                     "unique") beside either is ignored.  PHJ / CPRA: every key value is legal on both sides;
+                                     NPJ: a build key 0 is still HJGPU_EZEROKEY, a probe key 0 matches nothing.           */
 
 #define HJGPU_MAX_FANOUT  1024u   /* per partitioning pass                                   */
 #define HJGPU_MAX_PARTS   32768u  /* fanout1 * fanout2                                       */
