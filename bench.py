@@ -13,9 +13,12 @@ N > 1: one process per GPU (torchrun); the data path - exchange over RCCL, local
 library's C++ (hjgpu_phj_multi / hjgpu_cpra_multi, include/hjgpu.h); torch.distributed is the control plane only
 (gloo: the ncclUniqueId reaches the ranks, barriers around the timed region, max over ranks of the time).
 
-Prints ONE JSON line on rank 0 (see the driver contract in the task).  At N = 1 the line also carries, measured in
-the same process: NPJ (configs[1]) and one-GPU CPRA (`secondary`), the materialising PHJ (`materialized_default`, `materialized`), the
-CPU restatement of the same PHJ (`cpu_baseline`) and of configs[0] (`cpu_baseline_config0`).
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the
+line: nothing else.  With --full the line also carries what takes runs of its own, measured in the same process: the
+box's streaming-read ceiling (`empirical_stream_read_GBs`, `frac_of_stream_read`); at N = 1 NPJ
+(configs[1]) and one-GPU CPRA (`secondary`), the materialising PHJ (`materialized_default`, `materialized`), the CPU
+restatement of the same PHJ (`cpu_baseline`) and of configs[0] (`cpu_baseline_config0`); at N > 1 configs[4]
+(`secondary.cpra_multi`).
 """
 import argparse
 import json
@@ -53,18 +56,22 @@ def parse(argv=None):
                     help="Zipf exponent of the probe side's repeat picks (0 = uniform, the headline workload)")
     ap.add_argument("--fanout1", type=int, default=0)
     ap.add_argument("--fanout2", type=int, default=0)
+    ap.add_argument("--full", action="store_true",
+                    help="measure more than the headline: the streaming-read ceiling, the secondary legs, the materialising "
+                         "PHJ and the CPU baselines (N = 1), configs[4] (N > 1); a plain run times the headline only")
     ap.add_argument("--cpu-outer", type=int, default=1_000_000_000,
-                    help="probe tuples of the CPU-baseline sample (0 = skip every CPU leg); the default is the whole per-GPU "
-                         "workload: ~1 s (~18 CPU-seconds) on the 16 CPUs of a GPU box with the AVX-512 operators")
+                    help="--full: probe tuples of the CPU-baseline sample (0 = skip every CPU leg); the default is the whole "
+                         "per-GPU workload: ~1 s (~18 CPU-seconds) on 16 CPUs with the AVX-512 operators")
     ap.add_argument("--cpu-threads", type=int, default=0,
                     help="0 = the CPUs this process may use (affinity mask capped by the cgroup CPU quota)")
     ap.add_argument("--enqueue-only", action="store_true",
                     help="N = 1: time the enqueue-only entry points (hjgpu_*_async: all K6 stores non-temporal) instead of the blocking ones")
     ap.add_argument("--solo", action="store_true", help="N = 1: the headline with option solo (the caller's promise that nothing else runs on the device: K6's partial-line "
-                    "stores and the result rows plain); the default line measures the library's DEFAULT policy and reports the solo form in secondary.phj_solo")
+                    "stores and the result rows plain); the default line measures the library's DEFAULT policy, --full reports the solo form in secondary.phj_solo")
     ap.add_argument("--no-solo", action="store_true", help="kept for compatibility: the default since round 6")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the extra N = 1 measurements (NPJ, one-GPU CPRA, materialising PHJ, configs[0] on the CPU)")
+                    help="--full without the extra measurements (N = 1: NPJ, one-GPU CPRA, materialising PHJ, configs[0] on the "
+                         "CPU; N > 1: configs[4])")
     ap.add_argument("--materialize", action="store_true", help="kept for compatibility: the materialising PHJ is on by default")
     ap.add_argument("--force-dist", action="store_true",
                     help="at --gpus 1: go through the multi-GPU entry points with a one-rank RCCL communicator")
@@ -484,8 +491,8 @@ def main():
     else:
         hj = H.HjGpu(local_rank)
     # N = 1: the headline is the blocking join with the library's DEFAULT store policy (every store non-temporal: what any caller gets).
-    # --solo: option "solo" for the headline (plain partial-line stores; the line says so in config.solo_stores); the default line
-    # reports that form beside it (secondary.phj_solo).  The multi-GPU joins and every enqueue-only form never use it.
+    # --solo: option "solo" for the headline (plain partial-line stores; the line says so in config.solo_stores); a --full line
+    # without it reports that form beside it (secondary.phj_solo).  The multi-GPU joins and every enqueue-only form never use it.
     solo = not multi and not args.enqueue_only and args.solo and not args.no_solo
     if solo:
         hj.set_option("solo", "1")
@@ -590,13 +597,15 @@ def main():
         for _ in range(args.warmup):
             step()
     barrier()
-    # empirical streaming-read ceiling of this box: a plain 16-byte-load sweep of the
+    # --full: empirical streaming-read ceiling of this box: a plain 16-byte-load sweep of the
     # 4 GB probe-key column (nothing computed), outside the timed region
-    best = 1e9
-    for _ in range(4):
-        best = min(best, hj.stream_read_ms(sk.data_ptr(), 4 * outer // 65536 * 65536, stream))
-    stream_read_gbs = (4 * outer // 65536 * 65536) / (best * 1e-3) / 1e9 if outer >= 65536 else None
-    barrier()
+    stream_read_gbs = None
+    if args.full:
+        best = 1e9
+        for _ in range(4):
+            best = min(best, hj.stream_read_ms(sk.data_ptr(), 4 * outer // 65536 * 65536, stream))
+        stream_read_gbs = (4 * outer // 65536 * 65536) / (best * 1e-3) / 1e9 if outer >= 65536 else None
+        barrier()
     results_ok = True
     t0 = time.perf_counter()
     for _ in range(args.steps):
@@ -752,8 +761,8 @@ def main():
                                              "all_to_all_v": round(preflight["ms_all_to_all"], 3),
                                              "all_reduce": round(preflight["ms_all_reduce"], 3)}}
 
-    # ---- BASELINE configs[4] beside configs[3], N > 1 (one driver command measures both multi-GPU configurations) -----
-    if (multi and args.algo == "phj" and not args.no_secondary and args.zipf <= 0
+    # ---- --full: BASELINE configs[4] beside configs[3], N > 1 (one command measures both multi-GPU configurations) -----
+    if (args.full and multi and args.algo == "phj" and not args.no_secondary and args.zipf <= 0
             and (args.inner, args.outer) == (64_000_000, 1_000_000_000)):
         del shards
         rk = rv = sk = sv = None                       # the headline's columns make room (torch frees, the library keeps its workspaces)
@@ -761,8 +770,8 @@ def main():
         leg = cpra_multi_leg(args, H, torch, dist, comm, hj, dev, rank, n_gpus)
         out.setdefault("secondary", {})["cpra_multi"] = leg
 
-    # ---- the other BASELINE configurations, same process, N = 1 ---------------------------------------------------
-    extras = (not multi and rank == 0 and not args.no_secondary and args.algo == "phj" and args.zipf <= 0
+    # ---- --full: the other BASELINE configurations, same process, N = 1 --------------------------------------------
+    extras = (args.full and not multi and rank == 0 and not args.no_secondary and args.algo == "phj" and args.zipf <= 0
               and (args.inner, args.outer) == (64_000_000, 1_000_000_000))
     if extras:
         def time_steps(fn, warm=1, steps=5, ctx=None):
@@ -937,7 +946,7 @@ def main():
         del jk, jo, ji
         for c in jcols:
             c.free()
-    if rank == 0 and args.cpu_outer > 0:
+    if args.full and rank == 0 and args.cpu_outer > 0:
         try:
             out["cpu_baseline"] = cpu_baseline(hj, args, args.algo, ("npj", "cpra") if extras else ())
             for which, entry in out["cpu_baseline"].pop("others", {}).items():          # the NPJ and CPRA legs' own CPU baselines

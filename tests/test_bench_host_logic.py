@@ -1,6 +1,6 @@
 """CPU tests of bench.py's host-side logic (no GPU): argument defaults of the contract, the CPU allowance
 the CPU baseline uses, that a GPU-less run fails loudly instead of falling back to anything, and what --dump-outputs
-writes; one GPU test runs a small bench and checks its line and its dumped outputs."""
+writes; GPU tests run a small bench and check its line, its dumped outputs and what --full adds to a plain run."""
 import json
 import os
 import subprocess
@@ -87,6 +87,13 @@ def test_bench_steps_must_be_a_positive_count():
             bench.parse(bad)
 
 
+def test_bench_full_is_off_by_default():
+    """a plain run measures the headline only; --full adds the measurements that take runs of their own"""
+    import bench
+    assert bench.parse([]).full is False
+    assert bench.parse(["--full"]).full is True
+
+
 def test_bench_dump_outputs_holds_the_aggregates_exactly(tmp_path):
     """--dump-outputs: the four uint64 aggregates as float64, and as 32-bit words that float64 holds exactly"""
     import numpy as np
@@ -120,3 +127,24 @@ def test_bench_dumps_what_its_last_timed_step_returned(tmp_path):
     words = np.load(tmp_path / "out" / "result_u32_words.npy")
     assert [(int(hi) << 32) | int(lo) for hi, lo in words] == want
     assert np.load(tmp_path / "out" / "result.npy").tolist() == [float(v) for v in want]
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_leaves_the_extras_to_full():
+    """Without --full the line has no CPU baseline and no streaming-read ceiling; with it, both are measured and the
+    CPU restatement's checksum agrees.  The headline itself is checked in both runs."""
+    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+            "--inner", "1000000", "--outer", "8000000"]
+    lines = {}
+    for name, extra in (("plain", []), ("full", ["--full"])):
+        p = subprocess.run(base + extra, capture_output=True, text=True, timeout=300)
+        assert p.returncode == 0, p.stderr[-2000:]
+        got = [l for l in p.stdout.splitlines() if l.startswith("{")]
+        assert len(got) == 1
+        lines[name] = json.loads(got[0])
+        assert lines[name]["checksum_ok"] is True and lines[name]["steps"] == 2 and lines[name]["warmup"] == 1
+    plain, full = lines["plain"], lines["full"]
+    assert "cpu_baseline" not in plain and "secondary" not in plain
+    assert plain["empirical_stream_read_GBs"] is None and plain["roofline"]["frac_of_stream_read"] is None
+    assert full["empirical_stream_read_GBs"] > 0 and full["roofline"]["frac_of_stream_read"] > 0
+    assert full["cpu_baseline"]["value"] is not None and "checksum ok" in full["cpu_baseline"]["sample"]

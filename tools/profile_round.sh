@@ -30,5 +30,5 @@ round=${tag:0:3} &&
 cp gpurun_out/${tag}_traffic.json profiles/${round}_traffic.json &&
 cp gpurun_out/${tag}_npj_traffic.json profiles/${round}_npj_traffic.json &&
 cp gpurun_out/${tag}_cpra_traffic.json profiles/${round}_cpra_traffic.json &&
-python3 bench.py --steps 20 --warmup 5 > gpurun_out/${tag}_bench.json 2> gpurun_out/${tag}_bench.err
+python3 bench.py --full --steps 20 --warmup 5 > $out/${tag}_bench.json 2> $out/${tag}_bench.err
 echo "profile_round done rc=$?"

@@ -31,7 +31,7 @@ profiles)
   bash tools/profile_round.sh r06 > $out/r06_profile_round.log 2>&1; note "profile rc=$?"
   python3 tools/collect_traffic.py --materialized > $out/r06_materialized_traffic.log 2>&1 && cp $out/traffic.json $out/r06_materialized_traffic.json && cp $out/traffic.json profiles/r06_materialized_traffic.json
   python3 tools/collect_traffic.py --option unique=1 > $out/r06_unique_traffic.log 2>&1 && cp $out/traffic.json $out/r06_unique_traffic.json && cp $out/traffic.json profiles/r06_unique_traffic.json
-  python3 bench.py --steps 20 --warmup 5 > $out/r06_bench.json 2> $out/r06_bench.err; note "bench rc=$?"
+  python3 bench.py --full --steps 20 --warmup 5 > $out/r06_bench.json 2> $out/r06_bench.err; note "bench rc=$?"
   bash tools/pmc_sq.sh r06 > $out/r06_pmc_sq.log 2>&1; note "pmc rc=$?"
   ;;
 big)
@@ -42,7 +42,7 @@ big)
   ;;
 dist)
   # the multi-GPU entry points through RCCL at world 1 (bench.py --force-dist), all quoted workload shapes, and a rank's share beyond two passes' reach
-  timeout -k 10 400 python3 bench.py --force-dist --steps 8 --warmup 2 --cpu-outer 0 > $out/r06_bench_force_dist_configs4.json 2> $out/r06_fd_phj.err; note "fd phj+configs4 rc=$?"
+  timeout -k 10 400 python3 bench.py --force-dist --full --steps 8 --warmup 2 --cpu-outer 0 > $out/r06_bench_force_dist_configs4.json 2> $out/r06_fd_phj.err; note "fd phj+configs4 rc=$?"
   for algo in cpra npj; do
     timeout -k 10 300 python3 bench.py --force-dist --algo $algo --steps 8 --warmup 2 --cpu-outer 0 > $out/r06_bench_force_dist_$algo.json 2> $out/r06_fd_$algo.err; note "fd $algo rc=$?"
   done

@@ -10,7 +10,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ROWS = [
-    ("PHJ 64 M x 1 G (headline)", None),          # one run: also the materialised, CPRA and NPJ rows (bench.py's extras)
+    ("PHJ 64 M x 1 G (headline)", None),          # one run: also the materialised, CPRA and NPJ rows (bench.py --full)
     ("PHJ Zipf(1.0) probe side", ["--zipf", "1.0"]),
     ("PHJ Zipf(1.5) probe side", ["--zipf", "1.5"]),
     ("PHJ Zipf(2.0) probe side", ["--zipf", "2.0"]),
@@ -44,7 +44,7 @@ def main():
     print("|---|---|---|---|---|---|---|---|---|---|---|")
     for name, extra in ROWS:
         cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "10", "--warmup", "2", "--cpu-outer", "0"]
-        cmd += ["--no-secondary"] + extra if extra is not None else []
+        cmd += ["--no-secondary"] + extra if extra is not None else ["--full"]
         p = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
         lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
         if p.returncode != 0 or not lines:
