@@ -182,10 +182,19 @@ struct ScatterArgs {
     uint32_t *claim_overflow;       // device flag: an optimistic region (pass 1 claimed, or pass 2 into claimed final regions) was full
 };
 
-// What a join reports (HJGPU_FLAG_SEMI / HJGPU_FLAG_ANTI, derived once by hj_join_mode): every match of a probe tuple (inner join), or
-// ONE row (key, outer_val) per probe tuple that has a match (semi-join) / that has none (anti-join).
-enum : uint32_t { HJ_MODE_INNER = 0, HJ_MODE_SEMI = 1, HJ_MODE_ANTI = 2 };
-inline uint32_t hj_join_mode(uint32_t flags) { return (flags & HJGPU_FLAG_SEMI) ? HJ_MODE_SEMI : (flags & HJGPU_FLAG_ANTI) ? HJ_MODE_ANTI : HJ_MODE_INNER; }
+// What a join reports (HJGPU_FLAG_SEMI / _ANTI / _LEFT_OUTER, derived once by hj_join_mode): every match of a probe tuple (inner join),
+// ONE row (key, outer_val) per probe tuple that has a match (semi-join) / that has none (anti-join), or every match plus ONE row
+// (key, outer_val, HJGPU_NULL_VAL) per probe tuple that has none (left outer join).
+enum : uint32_t { HJ_MODE_INNER = 0, HJ_MODE_SEMI = 1, HJ_MODE_ANTI = 2, HJ_MODE_LEFT_OUTER = 3 };
+inline uint32_t hj_join_mode(uint32_t flags)
+{
+    return (flags & HJGPU_FLAG_SEMI) ? HJ_MODE_SEMI : (flags & HJGPU_FLAG_ANTI) ? HJ_MODE_ANTI
+         : (flags & HJGPU_FLAG_LEFT_OUTER) ? HJ_MODE_LEFT_OUTER : HJ_MODE_INNER;
+}
+// the modes that report probe rows without a match: a partition / group / join without build rows still has work
+inline bool hj_mode_keeps_unmatched(uint32_t mode) { return mode == HJ_MODE_ANTI || mode == HJ_MODE_LEFT_OUTER; }
+// the modes whose rows have two columns (key, outer_val): d_inner_vals is neither read nor written
+inline bool hj_mode_rows2(uint32_t mode) { return mode == HJ_MODE_SEMI || mode == HJ_MODE_ANTI; }
 
 struct JoinArgs {
     const uint32_t *rk, *rv, *sk, *sv;   // co-partitioned columns (packed: rk / sk = packed tuples)
@@ -215,8 +224,8 @@ struct JoinArgs {
     // broadcast join (tiny build side, nothing partitioned): P = 1, the relations are the caller's columns, the
     // empty sentinel is *sentinel (a value no build key equals, found by hj_launch_broadcast_meta)
     uint32_t broadcast;
-    uint32_t mode;                       // HJ_MODE_*: semi- / anti-joins take exists_probe_kernel (in the padding before `sentinel`: the
-                                         // other fields keep their offsets)
+    uint32_t mode;                       // HJ_MODE_*: semi- / anti-joins take exists_probe_kernel, left outer joins outer_probe_kernel (in
+                                         // the padding before `sentinel`: the other fields keep their offsets)
     const uint32_t *sentinel;
     uint32_t force_chained;              // tests: skip the cuckoo fast path (option "force_chained")
     uint32_t unique;                     // _UNIQUE (npj.cpp:288-290): a probe key reports its first match only
@@ -260,7 +269,8 @@ struct PlanArgs {
     uint32_t cap;             // build rows per LDS table fill of the join kernel that will run (JoinConfig::cap)
     uint32_t mask;            // bit 0: plan R, bit 1: plan S, bit 2: join work items
     uint32_t unique;          // _UNIQUE joins: all table fills of a probe slice stay with ONE work item (see join_kernel); also semi- / anti-joins
-    uint32_t anti = 0;        // anti-joins: a partition with probe rows and no build rows has work items too (its rows are all reported)
+    uint32_t anti = 0;        // anti- and left outer joins (hj_mode_keeps_unmatched): a partition with probe rows and no build rows has
+                              // work items too (its rows are all reported)
     uint32_t *multi_fill = nullptr;   // += partitions with work whose build rows take more than one table fill (zeroed per join)
     // Chunked relations (one-GPU CPRA), line-aligned final layout: the pass-1 output is laid out PARTITION-major - the
     // chunks' regions of a pass-1 partition lie side by side, off1[c * F1 + p] still says where chunk c writes partition
@@ -295,7 +305,7 @@ int hj_launch_hist2(const uint32_t *keys, const Pass1Geom &geom,
                     int cus, hipStream_t stream, size_t min_lds = 0, const u64 *dyn = nullptr /* device: {first row, rows}, see ScatterArgs::dyn */);
 // Grouped plans on the device: from pass 0's offsets (dense prefixes of the F0 = G * bins counters of both relations) to one descriptor per
 // group, desc[g] = {build first row, build rows, probe first row, probe rows} (first rows as pass 0 laid the groups out: hj_group_shift).
-// A group with an empty side gets no rows at all (nothing can match; anti: a group without build rows keeps its probe rows); one beyond
+// A group with an empty side gets no rows at all (nothing can match; anti / left outer: a group without build rows keeps its probe rows); one beyond
 // cap_r / cap_s rows gets none either and raises *skew.
 int hj_launch_group_desc(const u64 *roff, const u64 *soff, uint32_t G, uint32_t bins, u64 cap_r, u64 cap_s, u64 n_r, u64 n_s, u64 *desc, uint32_t *skew,
                          hipStream_t stream, bool anti = false);
@@ -355,7 +365,8 @@ struct NpjProbeArgs {
     uint32_t factor;
     uint32_t line_hash;                  // 1: walks start on 64-byte lines (the library's own tables)
     uint32_t unique;                     // _UNIQUE (npj.cpp:288-290): the walk ends at the key's first match
-    uint32_t mode;                       // HJ_MODE_*: semi- / anti-joins take npj_exists_*_kernel (rows without inner_val)
+    uint32_t mode;                       // HJ_MODE_*: semi- / anti-joins take npj_exists_*_kernel (rows without inner_val), left outer
+                                         // joins npj_outer_*_kernel
     hjgpu_result *result;
     uint32_t *ok, *oov, *oiv;
     u64 block_size, block_limit;

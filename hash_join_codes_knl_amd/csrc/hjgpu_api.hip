@@ -358,7 +358,7 @@ int setup_output(hjgpu_ctx *ctx, const hjgpu_output *out, uint32_t workers, u64 
     *block_size = 0; *block_limit = 0;
     if (!out || !out->d_keys) return HJGPU_OK;
     // (semi- and anti-join rows have no inner_val: d_inner_vals may be NULL, it is neither read nor written)
-    if (!out->d_outer_vals || (!out->d_inner_vals && mode == HJ_MODE_INNER)) return fail(ctx, HJGPU_EINVAL, "output columns");
+    if (!out->d_outer_vals || (!out->d_inner_vals && !hj_mode_rows2(mode))) return fail(ctx, HJGPU_EINVAL, "output columns");
     u64 bs = out->block_size ? out->block_size : 65536;
     if (bs < 256 || (bs & (bs - 1))) return fail(ctx, HJGPU_EINVAL, "block_size must be a power of two >= 256");
     u64 bl = out->capacity / bs;
@@ -498,15 +498,32 @@ int check_join_mode(hjgpu_ctx *ctx, uint32_t flags)
 {
     if ((flags & HJGPU_FLAG_SEMI) && (flags & HJGPU_FLAG_ANTI))
         return fail(ctx, HJGPU_EINVAL, "HJGPU_FLAG_SEMI | HJGPU_FLAG_ANTI: a join is a semi-join or an anti-join, not both");
+    if ((flags & HJGPU_FLAG_LEFT_OUTER) && (flags & (HJGPU_FLAG_SEMI | HJGPU_FLAG_ANTI)))
+        return fail(ctx, HJGPU_EINVAL, (flags & HJGPU_FLAG_SEMI) ? "HJGPU_FLAG_LEFT_OUTER | HJGPU_FLAG_SEMI: a join is a left outer join or a semi-join, not both"
+                                                                 : "HJGPU_FLAG_LEFT_OUTER | HJGPU_FLAG_ANTI: a join is a left outer join or an anti-join, not both");
     return HJGPU_OK;
+}
+
+static const char *join_mode_flag_name(uint32_t flags)
+{
+    return (flags & HJGPU_FLAG_SEMI) ? "HJGPU_FLAG_SEMI" : (flags & HJGPU_FLAG_ANTI) ? "HJGPU_FLAG_ANTI" : "HJGPU_FLAG_LEFT_OUTER";
 }
 
 int refuse_join_mode(hjgpu_ctx *ctx, uint32_t flags, const char *entry)
 {
-    if (!(flags & (HJGPU_FLAG_SEMI | HJGPU_FLAG_ANTI))) return HJGPU_OK;
+    if (!(flags & (HJGPU_FLAG_SEMI | HJGPU_FLAG_ANTI | HJGPU_FLAG_LEFT_OUTER))) return HJGPU_OK;
     char what[256];
-    snprintf(what, sizeof(what), "%s: HJGPU_FLAG_%s is not supported here (semi- and anti-joins: hjgpu_phj, hjgpu_cpra, hjgpu_npj, "
-             "their _async forms and hjgpu_phj_overlapped_async)", entry, (flags & HJGPU_FLAG_SEMI) ? "SEMI" : "ANTI");
+    snprintf(what, sizeof(what), "%s: %s is not supported here (semi-, anti- and left outer joins: hjgpu_phj, hjgpu_cpra, hjgpu_npj, "
+             "their _async forms and hjgpu_phj_overlapped_async)", entry, join_mode_flag_name(flags));
+    return fail(ctx, HJGPU_EINVAL, what);
+}
+
+// a join mode on a join_cfg geometry without a _UNIQUE instance (semi-, anti- and left outer joins take the _UNIQUE join's two launches)
+static int refuse_mode_geometry(hjgpu_ctx *ctx, uint32_t mode)
+{
+    char what[160];
+    snprintf(what, sizeof(what), "HJGPU_FLAG_%s: the join_cfg geometry of this context has no _UNIQUE instance (geometries with one: 512,13,2 and "
+             "1024,14,2)", mode == HJ_MODE_SEMI ? "SEMI" : mode == HJ_MODE_ANTI ? "ANTI" : mode == HJ_MODE_LEFT_OUTER ? "LEFT_OUTER" : "UNIQUE");
     return fail(ctx, HJGPU_EINVAL, what);
 }
 
@@ -537,7 +554,8 @@ int phj_prepare(hjgpu_ctx *ctx, size_t inner, size_t outer, const hjgpu_phj_para
     pl->C = chunks;
     pl->pre = pre ? 1u : 0u; pl->pre_f1 = 1; pl->pre_F1tot = 1; pl->pre_base = 0;
     pl->mode = (uint8_t)(prm ? hj_join_mode(prm->flags) : HJ_MODE_INNER);
-    pl->unique = ctx->tune.unique || (prm && (prm->flags & HJGPU_FLAG_UNIQUE)) || pl->mode != HJ_MODE_INNER;
+    pl->first_match = ctx->tune.unique || (prm && (prm->flags & HJGPU_FLAG_UNIQUE)) || hj_mode_rows2(pl->mode);
+    pl->unique = pl->first_match || pl->mode != HJ_MODE_INNER;
     choose_fanout(ctx->tune, plan_inner ? plan_inner : inner, prm, &pl->F1, &pl->F2, &pl->big_tables);
     if (big_override >= 0) pl->big_tables = big_override != 0;
     if (chunks > 8 && !pre) {
@@ -551,13 +569,7 @@ int phj_prepare(hjgpu_ctx *ctx, size_t inner, size_t outer, const hjgpu_phj_para
             pl->F2 = 2; pl->F1 = (parts + 1) / 2;
         }
     }
-    if (pl->unique && !hj_join_config_built(hj_join_config_of(ctx->tune, pl->big_tables), true))
-        return fail(ctx, HJGPU_EINVAL, pl->mode == HJ_MODE_SEMI ? "HJGPU_FLAG_SEMI: the join_cfg geometry of this context has no _UNIQUE instance "
-                                                                  "(geometries with one: 512,13,2 and 1024,14,2)"
-                                     : pl->mode == HJ_MODE_ANTI ? "HJGPU_FLAG_ANTI: the join_cfg geometry of this context has no _UNIQUE instance "
-                                                                  "(geometries with one: 512,13,2 and 1024,14,2)"
-                                     : "HJGPU_FLAG_UNIQUE: the join_cfg geometry of this context has no _UNIQUE instance "
-                                       "(geometries with one: 512,13,2 and 1024,14,2)");
+    if (pl->unique && !hj_join_config_built(hj_join_config_of(ctx->tune, pl->big_tables), true)) return refuse_mode_geometry(ctx, pl->mode);
     pl->P = pl->F1 * pl->F2;
     if (pl->F1 < 1 || pl->F2 < 1 || pl->F1 > HJGPU_MAX_FANOUT || pl->F2 > HJGPU_MAX_FANOUT ||
         pl->P < 2 || pl->P > HJGPU_MAX_PARTS)
@@ -693,7 +705,7 @@ int phj_enqueue(hjgpu_ctx *ctx, const PhjPlan &pl,
     const u64 *dyn[2] = {grp ? grp->desc : nullptr, grp ? grp->desc + 2 : nullptr};           // {first row, rows} of R / S in device memory
     pa.dyn[0] = dyn[0]; pa.dyn[1] = dyn[1];
     pa.multi_fill = m.tickets + HJ_TICKET_MULTI_FILL;          // zeroed with the tickets; counted by the work-item plan, read by the _UNIQUE join
-    pa.anti = pl.mode == HJ_MODE_ANTI ? 1u : 0u;
+    pa.anti = hj_mode_keeps_unmatched(pl.mode) ? 1u : 0u;
     // two-pass plans: final partitions start on 128-byte lines (pass 2 claims whole lines); option "dense2": dense
     const bool pad2 = pl.F2 > 1 && !ctx->tune.dense2;
     pa.pad2 = pad2 ? 1u : 0u;
@@ -908,7 +920,7 @@ int phj_enqueue(hjgpu_ctx *ctx, const PhjPlan &pl,
         ja.s_align = 0;
         ja.packed = 1;
         ja.big_tables = pl.big_tables ? 1u : 0u;
-        ja.unique = pl.unique ? 1u : 0u;
+        ja.unique = pl.first_match ? 1u : 0u;
         ja.mode = pl.mode;
         ja.result = &st->result;
         // (the work counters live with the tickets: zeroed with them, per join - also for a group, whose DevState is the grouped join's)
@@ -921,7 +933,7 @@ int phj_enqueue(hjgpu_ctx *ctx, const PhjPlan &pl,
         if (audit) CHK(hj_audit_copy(reinterpret_cast<const u64 *>(&st->result), audit + 4 * 6, 4, stream));
     }
     record(ctx, EV_JOIN, stream);
-    if (bs && inner && outer && mode != PHJ_BUILD_ONLY && !grp) CHK(close_gaps(ctx, out, workers, bs, st, stream, pl.mode != HJ_MODE_INNER));
+    if (bs && inner && outer && mode != PHJ_BUILD_ONLY && !grp) CHK(close_gaps(ctx, out, workers, bs, st, stream, hj_mode_rows2(pl.mode)));
     record(ctx, EV_GAPS, stream);
     ctx->stats.fanout1 = pl.F1; ctx->stats.fanout2 = pl.F2; ctx->stats.buckets = 0; ctx->stats.batches = batches_used;
     ctx->last_algo = 1;
@@ -1001,7 +1013,7 @@ int npj_probe_enqueue(hjgpu_ctx *ctx, const uint32_t *sk, const uint32_t *sv, si
         NpjProbeArgs pa;
         memset(&pa, 0, sizeof(pa));
         pa.keys = sk; pa.vals = sv; pa.n = outer; pa.table = table; pa.buckets = buckets;
-        pa.factor = factor; pa.line_hash = line_hash ? 1u : 0u; pa.unique = (unique || mode) ? 1u : 0u; pa.mode = mode; pa.result = &st->result;
+        pa.factor = factor; pa.line_hash = line_hash ? 1u : 0u; pa.unique = (unique || hj_mode_rows2(mode)) ? 1u : 0u; pa.mode = mode; pa.result = &st->result;
         if (bs) {
             pa.ok = out->d_keys; pa.oov = out->d_outer_vals; pa.oiv = out->d_inner_vals;
             pa.block_size = bs; pa.block_limit = bl; pa.block_counter = &st->block_counter;
@@ -1010,7 +1022,7 @@ int npj_probe_enqueue(hjgpu_ctx *ctx, const uint32_t *sk, const uint32_t *sv, si
         CHK(hj_launch_npj_probe(pa, ctx->cus, stream, nullptr));
     }
     record(ctx, EV_JOIN, stream);
-    if (bs && outer) CHK(close_gaps(ctx, out, (uint32_t)grid * 4, bs, st, stream, mode != HJ_MODE_INNER));
+    if (bs && outer) CHK(close_gaps(ctx, out, (uint32_t)grid * 4, bs, st, stream, hj_mode_rows2(mode)));
     record(ctx, EV_GAPS, stream);
     return HJGPU_OK;
 }
@@ -1541,8 +1553,8 @@ static size_t broadcast_rows(const HjTuning &tune, bool big_tables)
 
 static bool broadcast_applies(const HjTuning &tune, size_t inner, size_t outer, uint32_t chunks, const hjgpu_phj_params *prm)
 {
-    // an anti-join with no build rows reports the whole probe side, whatever the plan: one broadcast item per slice with no fill
-    if (prm && hj_join_mode(prm->flags) == HJ_MODE_ANTI && inner == 0 && outer) return true;
+    // an anti- or left outer join with no build rows reports the whole probe side, whatever the plan: one broadcast item per slice with no fill
+    if (prm && hj_mode_keeps_unmatched(hj_join_mode(prm->flags)) && inner == 0 && outer) return true;
     if (tune.no_broadcast) return false;
     if (chunks != 1 || (prm && (prm->fanout1 || prm->fanout2))) return false;    // an explicit plan is honoured
     return inner && outer && inner <= broadcast_rows(tune, true) && inner <= 16383;
@@ -1563,12 +1575,10 @@ static int broadcast_enqueue(hjgpu_ctx *ctx, const uint32_t *rk, const uint32_t 
     const size_t nslices = (outer + HJ_JOIN_SLICE - 1) / HJ_JOIN_SLICE;
     const size_t fills = (inner + cap - 1) / cap;
     const uint32_t jmode = prm ? hj_join_mode(prm->flags) : HJ_MODE_INNER;
-    const bool unique = ctx->tune.unique || (prm && (prm->flags & HJGPU_FLAG_UNIQUE)) || jmode != HJ_MODE_INNER;
-    if (jmode != HJ_MODE_INNER && !hj_join_config_built(hj_join_config_of(ctx->tune, big), true))
-        return fail(ctx, HJGPU_EINVAL, jmode == HJ_MODE_SEMI ? "HJGPU_FLAG_SEMI: the join_cfg geometry of this context has no _UNIQUE instance "
-                                                              "(geometries with one: 512,13,2 and 1024,14,2)"
-                                                            : "HJGPU_FLAG_ANTI: the join_cfg geometry of this context has no _UNIQUE instance "
-                                                              "(geometries with one: 512,13,2 and 1024,14,2)");
+    // first_match: the probe walk (JoinArgs::unique); unique: one fill group per probe slice (semi-, anti- and left outer joins too)
+    const bool first_match = ctx->tune.unique || (prm && (prm->flags & HJGPU_FLAG_UNIQUE)) || hj_mode_rows2(jmode);
+    const bool unique = first_match || jmode != HJ_MODE_INNER;
+    if (jmode != HJ_MODE_INNER && !hj_join_config_built(hj_join_config_of(ctx->tune, big), true)) return refuse_mode_geometry(ctx, jmode);
     const size_t groups = unique ? 1 : (fills < (size_t)HJ_JOIN_FILL_GROUPS ? fills : (size_t)HJ_JOIN_FILL_GROUPS);
     const size_t items = nslices * groups;
     if (nslices >= (1ull << 32)) return fail(ctx, HJGPU_EINVAL, "probe side too large for a broadcast join");
@@ -1601,13 +1611,13 @@ static int broadcast_enqueue(hjgpu_ctx *ctx, const uint32_t *rk, const uint32_t 
     ja.P = 1; ja.chunks = 1; ja.f1 = ja.f2 = 1; ja.F1 = ja.F2 = 1;
     ja.tf0 = tf0; ja.tf1 = tf1;
     ja.s_align = align_of(sk); ja.packed = 0;
-    ja.broadcast = 1; ja.sentinel = bm.sentinel; ja.big_tables = big ? 1u : 0u; ja.unique = unique ? 1u : 0u; ja.mode = jmode;
+    ja.broadcast = 1; ja.sentinel = bm.sentinel; ja.big_tables = big ? 1u : 0u; ja.unique = first_match ? 1u : 0u; ja.mode = jmode;
     ja.result = &st->result; ja.work_counter = &st->work_counter; ja.work_counter2 = &st->work_counter2;
     ja.multi_fill = &st->pad;                           // always 0: a broadcast join's build side is one table fill by construction
     join_output(ctx, ja, out, bs, bl, st);
     CHK(hj_launch_join(ja, ctx->tune, ctx->cus, stream));
     record(ctx, EV_JOIN, stream);
-    if (bs) CHK(close_gaps(ctx, out, workers, bs, st, stream, jmode != HJ_MODE_INNER));
+    if (bs) CHK(close_gaps(ctx, out, workers, bs, st, stream, hj_mode_rows2(jmode)));
     record(ctx, EV_GAPS, stream);
     ctx->stats.fanout1 = 1; ctx->stats.fanout2 = 1; ctx->stats.buckets = 0; ctx->stats.batches = 0;
     ctx->last_algo = 1;
@@ -1678,7 +1688,7 @@ static int phj_grouped(hjgpu_ctx *ctx, uint32_t G, uint32_t chunks,
     const u64 bs = out_on ? (out->block_size ? out->block_size : 65536) : 0;
     const uint32_t jmode = prm ? hj_join_mode(prm->flags) : HJ_MODE_INNER;
     for (uint32_t g = 0; g < G; ++g) {
-        if (pc[g].sn == 0 || (pc[g].rn == 0 && jmode != HJ_MODE_ANTI)) continue;       // nothing can match (an anti-join reports it all)
+        if (pc[g].sn == 0 || (pc[g].rn == 0 && !hj_mode_keeps_unmatched(jmode))) continue;   // nothing can match (anti / left outer: all reported)
         hjgpu_output view;
         const hjgpu_output *vout = nullptr;
         if (out_on) {
@@ -1694,7 +1704,7 @@ static int phj_grouped(hjgpu_ctx *ctx, uint32_t G, uint32_t chunks,
             }
         }
         if (pc[g].rn == 0) {
-            // an anti-join's group without build rows: all of its probe rows (a broadcast join with no fill)
+            // an anti- or left outer join's group without build rows: all of its probe rows (a broadcast join with no fill)
             CHK(broadcast_enqueue(ctx, g_rk, g_rv, 0, g_sk + pc[g].s0, g_sv + pc[g].s0, pc[g].sn, prm, vout, stream, nullptr));
         } else {
             CHK(phj_prepare(ctx, pc[g].rn, pc[g].sn, prm, chunks, &pl));
@@ -1783,7 +1793,7 @@ static int phj_grouped_device(hjgpu_ctx *ctx, uint32_t G, uint32_t chunks,
     HIPCHK(ctx, hj_zero_async(st, sizeof(DevState), stream));
     if (bs) HIPCHK(ctx, hj_fill_async(ctx->final_offsets.p, 0xFFFFFFFFu, (size_t)workers * sizeof(u64), stream));
     CHK(hj_launch_group_desc(d_off, d_off + (l.F0 + 1), G, l.bins, (u64)cap_r, (u64)cap_s, (u64)inner, (u64)outer, d_desc, &st->group_skew, stream,
-                             pl.mode == HJ_MODE_ANTI));
+                             hj_mode_keeps_unmatched(pl.mode)));
     HIPCHK(ctx, hipEventRecord(ctx->grp_ev_pass0[1], stream));
     for (uint32_t g = 0; g < G; ++g) {
         const GroupRun run = {d_desc + 4 * (size_t)g};
@@ -1792,7 +1802,7 @@ static int phj_grouped_device(hjgpu_ctx *ctx, uint32_t G, uint32_t chunks,
         ctx->ev_cur = nullptr;
         CHK(rc);
     }
-    if (bs) CHK(close_gaps(ctx, out, workers, bs, st, stream, pl.mode != HJ_MODE_INNER));
+    if (bs) CHK(close_gaps(ctx, out, workers, bs, st, stream, hj_mode_rows2(pl.mode)));
     if (d_result) CHK(hj_launch_group_result(&st->result, &st->group_skew, d_result, stream));
     HIPCHK(ctx, hipEventRecord(ctx->grp_ev_pass0[2], stream));
     // the last event every waiter looks at (hjgpu_get_stats), recorded in the context's own set
@@ -1829,7 +1839,7 @@ static int phj_like(hjgpu_ctx *ctx, uint32_t chunks,
     const uint32_t groups = grouped_groups(ctx, inner, outer, prm);
     // (the local join of a multi-GPU call - hjgpu_phj_overlapped_async - is always planned on the device: a rank's host thread waits with a
     // deadline or not at all)
-    const bool anti_all = prm && hj_join_mode(prm->flags) == HJ_MODE_ANTI && inner == 0 && outer;     // broadcast_applies
+    const bool anti_all = prm && hj_mode_keeps_unmatched(hj_join_mode(prm->flags)) && inner == 0 && outer;     // broadcast_applies
     if (groups > 1 && outer && !anti_all && (grouped_on_device(ctx) || local_join)) {
         CHK(phj_grouped_device(ctx, groups, chunks, rk, rv, inner, sk, sv, outer, prm, out, d_result, stream, (hipEvent_t)inner_ready));
         if (!blocking) {

@@ -230,11 +230,11 @@ PlanArgs plan_args(const hjgpu_ctx *ctx, const MetaLayout &m, uint32_t C, uint32
                    uint32_t mask);
 // A join's result rows: the block protocol into ja when bs > 0 (setup_output's block size and limit), and close_gaps after the join
 void join_output(const hjgpu_ctx *ctx, JoinArgs &ja, const hjgpu_output *out, u64 bs, u64 bl, DevState *st);
-// (rows2: the rows of a semi- / anti-join - key and outer_val only, the inner column is left alone)
+// (rows2: the rows of a semi- / anti-join - key and outer_val only, the inner column is left alone; hj_mode_rows2)
 int close_gaps(hjgpu_ctx *ctx, const hjgpu_output *out, uint32_t workers, u64 bs, DevState *st, hipStream_t stream, bool rows2 = false);
 // HJGPU_FLAG_SEMI | HJGPU_FLAG_ANTI together: refused
 int check_join_mode(hjgpu_ctx *ctx, uint32_t flags);
-// an entry point without semi- and anti-joins refuses either flag (never an inner join in their place); the text names the flag
+// an entry point without semi-, anti- and left outer joins refuses those flags (never an inner join in their place); the text names the flag
 int refuse_join_mode(hjgpu_ctx *ctx, uint32_t flags, const char *entry);
 void choose_fanout(const HjTuning &tune, size_t inner, const hjgpu_phj_params *prm, uint32_t *F1, uint32_t *F2, bool *big_tables);
 void record(hjgpu_ctx *ctx, int which, hipStream_t s);
@@ -255,8 +255,10 @@ struct PhjPlan {
     uint32_t C, F1, F2, P;
     uint32_t f1, f2, tf0, tf1;
     bool big_tables;
-    bool unique;             // HJGPU_FLAG_UNIQUE / option "unique"; also set for semi- and anti-joins (their first-match walk, one fill group)
-    uint8_t mode;            // HJ_MODE_*: HJGPU_FLAG_SEMI / HJGPU_FLAG_ANTI (a byte: beside the two flags, the plan keeps its size)
+    bool unique;             // HJGPU_FLAG_UNIQUE / option "unique"; also set for semi-, anti- and left outer joins (one fill group per slice)
+    uint8_t mode;            // HJ_MODE_*: HJGPU_FLAG_SEMI / _ANTI / _LEFT_OUTER (a byte: beside the flags, the plan keeps its size)
+    bool first_match;        // the probe walk ends at a key's first match (JoinArgs::unique): `unique`, except for a left outer join without
+                             // HJGPU_FLAG_UNIQUE
     // batched probe-side partitioning: 0 batches = off
     uint32_t batch_ranges;   // pass-1 ranges per batch
     uint32_t batch_cap;      // batches the tables hold

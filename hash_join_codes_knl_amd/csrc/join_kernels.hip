@@ -72,6 +72,11 @@ constexpr int hj_join_waves_per_simd(int block, int log2slots)
 #ifndef HJ_EMIT4
 #define HJ_EMIT4 1
 #endif
+// the probe of a left outer join's tail pass (join_body): no table, every open row is reported as a NULL row
+struct hj_tail_pass {
+    __device__ uint32_t operator()(const uint32_t (&)[4], const uint32_t (&)[4], const bool (&)[4]) const { return 0u; }
+};
+
 // NTROWS: result rows through non-temporal stores (EmitterT<true>; JoinArgs::nt_rows) - false only for solo joins
 // MODE (HJ_MODE_*): what a probe tuple reports.  HJ_MODE_INNER: its matches (join_kernel).  HJ_MODE_SEMI / HJ_MODE_ANTI
 // (exists_probe_kernel, always with UNIQUE): ONE row (key, outer_val) when it has a match / when it has none, from its match state -
@@ -81,11 +86,20 @@ constexpr int hj_join_waves_per_simd(int block, int log2slots)
 //   * a multi-fill item (DEDUP) only sets its rows' `matched` bits during the fills and reports the rows whose bit is clear in ONE
 //     more pass over its probe rows after the last fill;
 //   * a broadcast join's probe key equal to the sentinel matches nothing and is reported.
+// HJ_MODE_LEFT_OUTER (outer_probe_kernel): the inner join's rows plus ONE row (key, outer_val, HJGPU_NULL_VAL) per probe tuple without a
+// match.  Here UNIQUE is the first-match walk only (HJGPU_FLAG_UNIQUE); the two launches - single-fill items, then multi-fill ones
+// (DEDUP) - and one fill group per probe slice (PlanArgs::unique) hold either way.  A single-fill item emits a probe vector's matches and
+// NULL rows together (one emit4 when each of its tuples yields exactly one row: every full vector under UNIQUE); a multi-fill item emits
+// the matches of every fill and marks their rows (under UNIQUE the marks also skip the rows in later fills), then reports the unmarked
+// rows in the anti-join's tail pass; an item without build rows reports all its probe rows.
 template <int BLOCK, int LOG2SLOTS, int BATCH, bool PACKED, bool UNIQUE, bool DEDUP, bool NTROWS, int MODE>
 __device__ __forceinline__ void join_body(JoinArgs a)
 {
-    static_assert(UNIQUE || !DEDUP, "DEDUP is the multi-fill half of a _UNIQUE join");
-    static_assert(MODE == HJ_MODE_INNER || (UNIQUE && NTROWS), "semi- and anti-joins walk to the first match, rows non-temporal");
+    static_assert(UNIQUE || !DEDUP || MODE == HJ_MODE_LEFT_OUTER, "DEDUP is the multi-fill half of a _UNIQUE or left outer join");
+    static_assert(MODE == HJ_MODE_INNER || ((UNIQUE || MODE == HJ_MODE_LEFT_OUTER) && NTROWS),
+                  "semi- and anti-joins walk to the first match; rows non-temporal");
+    // the two launches of a _UNIQUE join: single-fill items, then multi-fill ones (DEDUP); left outer joins always
+    constexpr bool SPLIT = UNIQUE || MODE == HJ_MODE_LEFT_OUTER;
     // the plan found no partition that takes several fills (the planned case): nothing for this launch to do
     if (DEDUP && a.multi_fill && *a.multi_fill == 0) return;
     constexpr uint32_t SLOTS = 1u << LOG2SLOTS;
@@ -114,7 +128,7 @@ __device__ __forceinline__ void join_body(JoinArgs a)
     const u64 *__restrict__ r64 = reinterpret_cast<const u64 *>(a.rk);
     const uint32_t tf0 = a.tf0, tf1 = a.tf1;
 
-    EmitterT<NTROWS, MODE == HJ_MODE_INNER ? 3 : 2> em;
+    EmitterT<NTROWS, (MODE == HJ_MODE_SEMI || MODE == HJ_MODE_ANTI) ? 2 : 3> em;
     em.init(a.ok, a.oov, a.oiv, a.block_size, a.block_limit, a.block_counter, a.overflow,
             &wave_cursor[wave]);
     // (the multi-fill half of a _UNIQUE join runs behind the single-fill half on the same stream, with the same grid: wave w of
@@ -127,6 +141,7 @@ __device__ __forceinline__ void join_body(JoinArgs a)
     uint32_t empty = 0;
     uint32_t q = 0;
     bool anti_tail = false;                          // HJ_MODE_ANTI: the pass that reports the item's rows without a match
+    uint32_t lo_open = 0;                            // HJ_MODE_LEFT_OUTER, single-fill items: the current vector's tuples of the slice
 
     // ---- visit rows [fill_beg, fill_end) of the chunk-concatenated build partition q ----
     // rows below `from_row` were already inserted (from the prefetch registers)
@@ -191,19 +206,20 @@ __device__ __forceinline__ void join_body(JoinArgs a)
         }
     };
 
-    // semi- / anti-join: the tuples j of a probe vector with bit j of `rep` leave as rows (key, outer_val)
-    auto report4 = [&](const uint32_t (&key)[4], const uint32_t (&val)[4], uint32_t rep) {
+    // semi- / anti-join: the tuples j of a probe vector with bit j of `rep` leave as rows (key, outer_val); left outer join: as NULL rows
+    // (key, outer_val, `iv` = HJGPU_NULL_VAL), which add nothing to sum_inner_vals
+    auto report4 = [&](const uint32_t (&key)[4], const uint32_t (&val)[4], uint32_t rep, uint32_t iv) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const bool r = (rep >> j) & 1u;
             acc_n += r ? 1u : 0u; acc_k += r ? key[j] : 0u; acc_o += r ? val[j] : 0u;
         }
         if (a.ok) {
-            const uint32_t none[4] = {0u, 0u, 0u, 0u};
+            const uint32_t none[4] = {iv, iv, iv, iv};
             if (rep == 15u && a.block_size >= 512) em.emit4(key, val, none);       // (emit4: blocks of 512 rows and more)
             else if (rep) {
 #pragma unroll
-                for (int j = 0; j < 4; ++j) if ((rep >> j) & 1u) em.emit(key[j], val[j], 0u);
+                for (int j = 0; j < 4; ++j) if ((rep >> j) & 1u) em.emit(key[j], val[j], iv);
             }
         }
     };
@@ -211,6 +227,8 @@ __device__ __forceinline__ void join_body(JoinArgs a)
     // ---- stream the S rows [gb, ge): BATCH key + BATCH payload vectors in flight per lane ----
     // `row0`: index of row gb among the probe rows of this work item (UNIQUE's `matched` bits)
     auto for_each_probe_vector = [&](u64 gb, u64 ge, u64 row0, auto probe4) {
+        // left outer join: the tail pass (see below) is an instance of its own, the probes' instances carry no tail path
+        constexpr bool TAIL = __is_same(decltype(probe4), hj_tail_pass);
         for (u64 g0 = (gb & ~3ull) + (u64)tid * 4; g0 < ge; g0 += (u64)BLOCK * 4 * BATCH) {
             uint4 kk[BATCH], vv[BATCH];
 #pragma unroll
@@ -228,7 +246,7 @@ __device__ __forceinline__ void join_body(JoinArgs a)
                 if (g >= ge) break;
                 const uint32_t key[4] = {kk[u].x, PACKED ? kk[u].z : kk[u].y, PACKED ? vv[u].x : kk[u].z, PACKED ? vv[u].z : kk[u].w};
                 const uint32_t val[4] = {PACKED ? kk[u].y : vv[u].x, PACKED ? kk[u].w : vv[u].y, PACKED ? vv[u].y : vv[u].z, vv[u].w};
-                if constexpr (MODE != HJ_MODE_INNER) {
+                if constexpr (MODE == HJ_MODE_SEMI || MODE == HJ_MODE_ANTI) {
                     // inr: the rows of the slice that are still open (DEDUP: not reported by an earlier fill); valid: those that may match -
                     // a probe key equal to the broadcast sentinel matches nothing (see below), and the anti-join reports it
                     bool inr[4], valid[4];
@@ -251,8 +269,46 @@ __device__ __forceinline__ void join_body(JoinArgs a)
 #pragma unroll
                     for (int j = 0; j < 4; ++j) rep |= (inr[j] && (((hits >> j) & 1u) != 0) == (MODE == HJ_MODE_SEMI)) ? 1u << j : 0u;
                     if (MODE == HJ_MODE_ANTI && dedup && !anti_tail) rep = 0;       // the fills only mark; the tail pass reports
-                    report4(key, val, rep);
+                    report4(key, val, rep, 0u);
                     continue;
+                }
+                if constexpr (MODE == HJ_MODE_LEFT_OUTER) {
+                    // inr: the rows of the slice still open (DEDUP: under UNIQUE, and in the tail pass, not yet matched by a fill);
+                    // valid: those that may match (a probe key equal to the broadcast sentinel matches nothing: a NULL row)
+                    bool inr[4], valid[4];
+                    uint32_t open = 0;
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        const uint32_t row = (uint32_t)(row0 + (g + j - gb));
+                        inr[j] = (g + j >= gb) && (g + j < ge);
+                        if (dedup && (UNIQUE || TAIL) && inr[j]) inr[j] = !((matched[row >> 5] >> (row & 31)) & 1u);
+                        valid[j] = inr[j] && (PACKED || key[j] != empty);
+                        open |= inr[j] ? 1u << j : 0u;
+                    }
+                    if constexpr (TAIL) {
+                        if constexpr (DEDUP) {
+                            // row by row: report4's emit4 beside the fills' costs the 1024-thread DEDUP instance 3 spilled VGPRs
+#pragma unroll
+                            for (int j = 0; j < 4; ++j) {
+                                if ((open >> j) & 1u) {
+                                    acc_n += 1; acc_k += key[j]; acc_o += val[j];
+                                    if (a.ok) em.emit(key[j], val[j], HJGPU_NULL_VAL);
+                                }
+                            }
+                        } else report4(key, val, open, HJGPU_NULL_VAL);
+                        continue;
+                    } else {
+                        lo_open = open;               // the single-fill probes emit the NULL rows of `open` beside the matches
+                        const uint32_t hits = probe4(key, val, valid);
+                        if (dedup) {
+#pragma unroll
+                            for (int j = 0; j < 4; ++j) {
+                                const uint32_t row = (uint32_t)(row0 + (g + j - gb));
+                                if ((hits >> j) & 1u) atomicOr(&matched[row >> 5], 1u << (row & 31));
+                            }
+                        }
+                        continue;
+                    }
                 }
                 bool valid[4];
 #pragma unroll
@@ -302,9 +358,52 @@ __device__ __forceinline__ void join_body(JoinArgs a)
             t2[j] = tab64[a2];
 #endif
         }
-        if constexpr (MODE != HJ_MODE_INNER) {
+        if constexpr (MODE == HJ_MODE_SEMI || MODE == HJ_MODE_ANTI) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) hits |= (valid[j] && ((uint32_t)t1[j] == key[j] || (uint32_t)t2[j] == key[j])) ? 1u << j : 0u;
+            return hits;
+        }
+        if constexpr (MODE == HJ_MODE_LEFT_OUTER) {
+            // the inner join's matches; a single-fill item also the NULL row of every open tuple without one (a multi-fill item: the tail pass)
+            u64 sk_ = 0, so_ = 0, si_ = 0;
+            uint32_t n = 0;
+            bool one = true;                  // every tuple of the vector yields exactly one row: ONE emit4
+            uint32_t iv4[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const bool h1 = valid[j] && ((uint32_t)t1[j] == key[j]);
+                const bool h2 = valid[j] && ((uint32_t)t2[j] == key[j]) && !(UNIQUE && h1);
+                const bool z = !DEDUP && ((lo_open >> j) & 1u) && !h1 && !h2;
+                const uint32_t m = (h1 ? 1u : 0u) + (h2 ? 1u : 0u) + (z ? 1u : 0u);
+                hits |= (h1 || h2) ? 1u << j : 0u;
+                n += m;
+                sk_ += (u64)key[j] * m;
+                so_ += (u64)val[j] * m;
+                si_ += (h1 ? (uint32_t)(t1[j] >> 32) : 0u);
+                si_ += (h2 ? (uint32_t)(t2[j] >> 32) : 0u);
+                one = one && m == 1u;
+            }
+            if (a.ok) {
+                // (a wave's emit4 writes up to 256 rows and claims at most ONE new block: blocks of 512 rows and more)
+                if (one && a.block_size >= 512) {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j)
+                        iv4[j] = ((uint32_t)t1[j] == key[j] && valid[j]) ? (uint32_t)(t1[j] >> 32)
+                               : ((uint32_t)t2[j] == key[j] && valid[j]) ? (uint32_t)(t2[j] >> 32) : HJGPU_NULL_VAL;
+                    em.emit4(key, val, iv4);
+                }
+                else if (n) {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        const bool h1 = valid[j] && ((uint32_t)t1[j] == key[j]);
+                        const bool h2 = valid[j] && ((uint32_t)t2[j] == key[j]) && !(UNIQUE && h1);
+                        if (h1 | h2) em.emit(key[j], val[j], (uint32_t)((h1 ? t1[j] : t2[j]) >> 32));
+                        if (h1 & h2) em.emit(key[j], val[j], (uint32_t)(t2[j] >> 32));
+                        if (!DEDUP && ((lo_open >> j) & 1u) && !h1 && !h2) em.emit(key[j], val[j], HJGPU_NULL_VAL);
+                    }
+                }
+            }
+            acc_n += n; acc_k += sk_; acc_o += so_; acc_i += si_;
             return hits;
         }
         u64 sk_ = 0, so_ = 0, si_ = 0;
@@ -379,7 +478,7 @@ __device__ __forceinline__ void join_body(JoinArgs a)
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const bool hit = live[j] && (t[j].x == key[j]);
-                if constexpr (MODE == HJ_MODE_INNER) {
+                if constexpr (MODE == HJ_MODE_INNER || MODE == HJ_MODE_LEFT_OUTER) {
                     acc_n += hit ? 1u : 0u;
                     acc_k += hit ? key[j] : 0u;
                     acc_o += hit ? val[j] : 0u;
@@ -394,6 +493,8 @@ __device__ __forceinline__ void join_body(JoinArgs a)
 #pragma unroll
             for (int j = 0; j < 4; ++j) if (live[j]) t[j] = tab[slot[j]];
         }
+        // left outer join, single-fill item: the NULL rows of the open tuples without a match
+        if constexpr (MODE == HJ_MODE_LEFT_OUTER && !DEDUP) report4(key, val, lo_open & ~hits, HJGPU_NULL_VAL);
         return hits;
     };
 
@@ -487,7 +588,7 @@ __device__ __forceinline__ void join_body(JoinArgs a)
             while ((hj_hash(empty, a.f1, a.F1) - a.p1_base) * a.F2 + hj_hash(empty, a.f2, a.F2) == q) ++empty;
         }
         const u64 EMPTY64 = (u64)empty;
-        if (UNIQUE) {
+        if (SPLIT) {
             // single-fill items belong to the <UNIQUE, !DEDUP> launch, multi-fill items to <UNIQUE, DEDUP>
             const bool multi = rows_end - rows_beg > CAP;
             if (multi != DEDUP) {
@@ -570,6 +671,13 @@ __device__ __forceinline__ void join_body(JoinArgs a)
                 if (DEDUP) __syncthreads();          // every lane has read `matched` before the next item clears it
             }
         }
+        if constexpr (MODE == HJ_MODE_LEFT_OUTER) {
+            // the anti-join's tail pass: NULL rows for all probe rows of an item without build rows / the unmarked rows of a multi-fill item
+            if (DEDUP || rows_beg >= rows_end) {
+                probe_item(slice, nslices, hj_tail_pass{});
+                if (DEDUP) __syncthreads();          // every lane has read `matched` before the next item clears it
+            }
+        }
         if (rows_beg >= rows_end) __syncthreads();   // no fill (a trailing fill group of an oversize partition): publish the next claim
         par ^= 1;
     }
@@ -604,6 +712,14 @@ template <int BLOCK, int LOG2SLOTS, int BATCH, bool PACKED, int MODE, bool DEDUP
 __global__ __launch_bounds__(BLOCK, hj_join_waves_per_simd(BLOCK, LOG2SLOTS)) void exists_probe_kernel(JoinArgs a)
 {
     join_body<BLOCK, LOG2SLOTS, BATCH, PACKED, true, DEDUP, true, MODE>(a);
+}
+
+// Left outer joins (HJGPU_FLAG_LEFT_OUTER): the _UNIQUE join's two launches - single-fill items, then multi-fill ones (DEDUP) - with
+// UNIQUE the first-match walk of HJGPU_FLAG_UNIQUE only.  A kernel of its own name, like exists_probe_kernel; rows always non-temporal.
+template <int BLOCK, int LOG2SLOTS, int BATCH, bool PACKED, bool UNIQUE, bool DEDUP>
+__global__ __launch_bounds__(BLOCK, hj_join_waves_per_simd(BLOCK, LOG2SLOTS)) void outer_probe_kernel(JoinArgs a)
+{
+    join_body<BLOCK, LOG2SLOTS, BATCH, PACKED, UNIQUE, DEDUP, true, HJ_MODE_LEFT_OUTER>(a);
 }
 
 #include <stdlib.h>
@@ -724,6 +840,18 @@ bool hj_join_config_built(const JoinConfig &c, bool unique)
         return hipGetLastError() == hipSuccess ? HJGPU_OK : HJGPU_EHIP;                           \
     }
 
+// a left outer join: the same two launches, outer_probe_kernel with the first-match walk or without it
+#define OUTER_LAUNCH(B, L, U, P, UNQ, DD, ARGS) \
+    hipLaunchKernelGGL((outer_probe_kernel<B, L, U, P, UNQ, DD>), dim3(join_grid(cus, c)), dim3(B), 0, stream, ARGS)
+#define OUTER_CASE(B, L, UNQ)                                                                     \
+    if (c.block == B && c.log2slots == L && (b.unique != 0) == UNQ) {                             \
+        JoinArgs d = b;                                                                           \
+        d.work_counter = b.work_counter2;                                                         \
+        if (b.packed) { OUTER_LAUNCH(B, L, 2, true, UNQ, false, b); OUTER_LAUNCH(B, L, 1, true, UNQ, true, d); }    \
+        else { OUTER_LAUNCH(B, L, 2, false, UNQ, false, b); OUTER_LAUNCH(B, L, 1, false, UNQ, true, d); }           \
+        return hipGetLastError() == hipSuccess ? HJGPU_OK : HJGPU_EHIP;                           \
+    }
+
 int hj_launch_join(const JoinArgs &a, const HjTuning &t, int cus, hipStream_t stream)
 {
     if ((a.P < 2 && !a.broadcast) || a.P < 1 || a.chunks == 0) return HJGPU_EINVAL;
@@ -732,6 +860,13 @@ int hj_launch_join(const JoinArgs &a, const HjTuning &t, int cus, hipStream_t st
     b.force_chained = t.force_chained ? 1u : 0u;       // tests: exercise the fallback table everywhere
     b.unique = (a.unique || t.unique) ? 1u : 0u;
     if ((b.unique || b.mode) && !b.work_counter2) return HJGPU_EINVAL;
+    if (b.mode == HJ_MODE_LEFT_OUTER) {
+        OUTER_CASE(512, 13, false)
+        OUTER_CASE(512, 13, true)
+        OUTER_CASE(1024, 14, false)
+        OUTER_CASE(1024, 14, true)
+        return HJGPU_EINVAL;                           // a geometry without a _UNIQUE instance (hj_join_config_built)
+    }
     if (b.mode != HJ_MODE_INNER) {
         EXISTS_CASE(512, 13, HJ_MODE_SEMI)
         EXISTS_CASE(512, 13, HJ_MODE_ANTI)

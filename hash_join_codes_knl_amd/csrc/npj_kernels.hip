@@ -178,19 +178,20 @@ __global__ __launch_bounds__(NPJ_PROBE_BLOCK) void npj_probe_kernel(NpjProbeArgs
 }
 
 
-// Semi- / anti-join probes (HJGPU_FLAG_SEMI / _ANTI).  The inner-join kernels above stay as they are (their machine code is the library's
-// yardstick); this body is their walk with a compile-time MODE, instantiated for the two new modes only.
-// MODE (HJ_MODE_*, npj_exists_kernel): semi- / anti-join - with UNIQUE's walk, ONE row (key, outer_val) per probe tuple that found a
-// match / that reached an empty bucket without one.
+// Semi- / anti-join and left outer join probes (HJGPU_FLAG_SEMI / _ANTI / _LEFT_OUTER).  The inner-join kernels above stay as they are
+// (their machine code is the library's yardstick); this body is their walk with a compile-time MODE, instantiated for the new modes only.
+// MODE (HJ_MODE_*): semi- / anti-join (npj_exists_kernel) - with UNIQUE's walk, ONE row (key, outer_val) per probe tuple that found a
+// match / that reached an empty bucket without one; left outer join (npj_outer_kernel) - the inner join's rows (every match, or the
+// first under UNIQUE), then ONE row (key, outer_val, HJGPU_NULL_VAL) per probe tuple whose walk found none.
 template <bool GROUPED, bool UNIQUE, int MODE>
-__device__ __forceinline__ void npj_exists_body(NpjProbeArgs a)
+__device__ __forceinline__ void npj_mode_body(NpjProbeArgs a)
 {
-    static_assert(MODE != HJ_MODE_INNER && UNIQUE, "semi- and anti-joins walk to the first match");
+    static_assert(MODE != HJ_MODE_INNER && (UNIQUE || MODE == HJ_MODE_LEFT_OUTER), "semi- and anti-joins walk to the first match");
     constexpr int NW = NPJ_PROBE_BLOCK / 64;
     __shared__ u64 red[4][NW];
     __shared__ u64 wave_cursor[NW];
     const int wave = threadIdx.x >> 6;
-    EmitterT<true, MODE == HJ_MODE_INNER ? 3 : 2> em;
+    EmitterT<true, (MODE == HJ_MODE_SEMI || MODE == HJ_MODE_ANTI) ? 2 : 3> em;
     em.init(a.ok, a.oov, a.oiv, a.block_size, a.block_limit, a.block_counter, a.overflow,
             &wave_cursor[wave]);
     if (hj_lane() == 0) wave_cursor[wave] = HJ_NO_CURSOR;
@@ -240,10 +241,11 @@ __device__ __forceinline__ void npj_exists_body(NpjProbeArgs a)
                             const bool inb = open && ((uint32_t)b >= first);
                             if (inb && bk[b] == 0u) open = false;
                             else if (inb && bk[b] == key[j]) {
-                                if constexpr (MODE == HJ_MODE_INNER) {
+                                if constexpr (MODE == HJ_MODE_INNER || MODE == HJ_MODE_LEFT_OUTER) {
                                     acc_n += 1; acc_k += key[j]; acc_o += val[j]; acc_i += bv[b];
                                     em.emit(key[j], val[j], bv[b]);
-                                } else hit[j] = true;
+                                }
+                                if constexpr (MODE != HJ_MODE_INNER) hit[j] = true;
                                 if (UNIQUE) open = false;
                             }
                         }
@@ -265,10 +267,11 @@ __device__ __forceinline__ void npj_exists_body(NpjProbeArgs a)
                         } else {
                             if ((uint32_t)t[j] == key[j]) {
                                 const uint32_t iv = (uint32_t)(t[j] >> 32);
-                                if constexpr (MODE == HJ_MODE_INNER) {
+                                if constexpr (MODE == HJ_MODE_INNER || MODE == HJ_MODE_LEFT_OUTER) {
                                     acc_n += 1; acc_k += key[j]; acc_o += val[j]; acc_i += iv;
                                     em.emit(key[j], val[j], iv);
-                                } else hit[j] = true;
+                                }
+                                if constexpr (MODE != HJ_MODE_INNER) hit[j] = true;
                                 if (UNIQUE) { act[j] = false; continue; }
                             }
                             if (++h[j] == buckets) h[j] = 0;
@@ -278,7 +281,15 @@ __device__ __forceinline__ void npj_exists_body(NpjProbeArgs a)
                 }
             }
         }
-        if constexpr (MODE != HJ_MODE_INNER) {
+        if constexpr (MODE == HJ_MODE_LEFT_OUTER) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                if (in[j] && !hit[j]) {                 // (a probe key 0 stops at the first empty bucket: no match, a NULL row)
+                    acc_n += 1; acc_k += key[j]; acc_o += val[j];
+                    em.emit(key[j], val[j], HJGPU_NULL_VAL);
+                }
+            }
+        } else if constexpr (MODE != HJ_MODE_INNER) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 if (in[j] && hit[j] == (MODE == HJ_MODE_SEMI)) {
@@ -305,7 +316,13 @@ __device__ __forceinline__ void npj_exists_body(NpjProbeArgs a)
 template <bool GROUPED, int MODE>
 __global__ __launch_bounds__(NPJ_PROBE_BLOCK) void npj_exists_kernel(NpjProbeArgs a)
 {
-    npj_exists_body<GROUPED, true, MODE>(a);
+    npj_mode_body<GROUPED, true, MODE>(a);
+}
+
+template <bool GROUPED, bool UNIQUE>
+__global__ __launch_bounds__(NPJ_PROBE_BLOCK) void npj_outer_kernel(NpjProbeArgs a)
+{
+    npj_mode_body<GROUPED, UNIQUE, HJ_MODE_LEFT_OUTER>(a);
 }
 
 // LINE table (the library's own whole joins, hjgpu_npj*): the walk of a key starts on the
@@ -436,20 +453,21 @@ __global__ __launch_bounds__(NPJ_PROBE_BLOCK) void npj_probe_line_kernel(NpjProb
     }
 }
 
-// Semi- / anti-join probes (HJGPU_FLAG_SEMI / _ANTI).  The inner-join kernels above stay as they are (their machine code is the library's
-// yardstick); this body is their walk with a compile-time MODE, instantiated for the two new modes only.
-// MODE (HJ_MODE_*, npj_exists_line_kernel): semi- / anti-join - lane 0 of the quad reports the tuple when its walk ends: on a match
-// (`found`, SEMI) or on an empty bucket without one (ANTI).
+// Semi- / anti-join and left outer join probes (HJGPU_FLAG_SEMI / _ANTI / _LEFT_OUTER).  The inner-join kernels above stay as they are
+// (their machine code is the library's yardstick); this body is their walk with a compile-time MODE, instantiated for the new modes only.
+// MODE (HJ_MODE_*): semi- / anti-join (npj_exists_line_kernel) - lane 0 of the quad reports the tuple when its walk ends: on a match
+// (`found`, SEMI) or on an empty bucket without one (ANTI); left outer join (npj_outer_line_kernel) - the inner join's rows, and lane 0
+// of the quad reports a NULL row when the walk ends without any match of the quad in any of its lines.
 template <bool MATERIALIZE, bool UNIQUE, int MODE>
-__device__ __forceinline__ void npj_exists_line_body(NpjProbeArgs a)
+__device__ __forceinline__ void npj_mode_line_body(NpjProbeArgs a)
 {
-    static_assert(MODE != HJ_MODE_INNER && UNIQUE, "semi- and anti-joins walk to the first match");
+    static_assert(MODE != HJ_MODE_INNER && (UNIQUE || MODE == HJ_MODE_LEFT_OUTER), "semi- and anti-joins walk to the first match");
     constexpr int NW = NPJ_PROBE_BLOCK / 64;
     constexpr int B = 4;                                   // lines in flight per quad
     __shared__ u64 red[4][NW];
     __shared__ u64 wave_cursor[NW];
     const int wave = threadIdx.x >> 6;
-    EmitterT<true, MODE == HJ_MODE_INNER ? 3 : 2> em;
+    EmitterT<true, (MODE == HJ_MODE_SEMI || MODE == HJ_MODE_ANTI) ? 2 : 3> em;
     em.init(a.ok, a.oov, a.oiv, a.block_size, a.block_limit, a.block_counter, a.overflow,
             &wave_cursor[wave]);
     if (hj_lane() == 0) wave_cursor[wave] = HJ_NO_CURSOR;
@@ -466,6 +484,9 @@ __device__ __forceinline__ void npj_exists_line_body(NpjProbeArgs a)
     const uint32_t sub = threadIdx.x & 3;                  // my quarter of the line: buckets 2*sub, 2*sub + 1
 
     u64 acc_n = 0, acc_k = 0, acc_o = 0, acc_i = 0;
+    // left outer join: the current walk has found a match (quad-uniform).  Declared here, set only by the left outer instances: an
+    // initialised local beside the walk reorders two register moves of the semi- / anti-join instances
+    bool got;
     // whole waves iterate together (the quad exchanges below need all four lanes)
     for (u64 v0 = (u64)blockIdx.x * NPJ_PROBE_BLOCK + (threadIdx.x & ~63u); v0 < nvec; v0 += stride) {
         const u64 v = v0 + hj_lane();
@@ -500,6 +521,7 @@ __device__ __forceinline__ void npj_exists_line_body(NpjProbeArgs a)
             }
 #pragma unroll
             for (int i = 0; i < B; ++i) {
+                if constexpr (MODE == HJ_MODE_LEFT_OUTER) got = false;
                 while (act[i]) {                                        // uniform inside the quad
                     // first empty bucket of the line, over the quad
                     uint32_t fe = q[i].x == 0u ? 2 * sub : (q[i].z == 0u ? 2 * sub + 1 : 8u);
@@ -518,7 +540,7 @@ __device__ __forceinline__ void npj_exists_line_body(NpjProbeArgs a)
                         m0 = m0 && mine == fm && fm == 2 * sub;
                         m1 = m1 && mine == fm && fm == 2 * sub + 1;
                     }
-                    if constexpr (MODE == HJ_MODE_INNER) {
+                    if constexpr (MODE == HJ_MODE_INNER || MODE == HJ_MODE_LEFT_OUTER) {
                         const uint32_t m = (m0 ? 1u : 0u) + (m1 ? 1u : 0u);
                         acc_n += m; acc_k += (u64)key[i] * m; acc_o += (u64)val[i] * m;
                         acc_i += (m0 ? q[i].y : 0u); acc_i += (m1 ? q[i].w : 0u);
@@ -530,6 +552,19 @@ __device__ __forceinline__ void npj_exists_line_body(NpjProbeArgs a)
                         if (sub == 0 && found == (MODE == HJ_MODE_SEMI)) {
                             acc_n += 1; acc_k += key[i]; acc_o += val[i];
                             if (MATERIALIZE) em.emit(key[i], val[i], 0u);
+                        }
+                    }
+                    if constexpr (MODE == HJ_MODE_LEFT_OUTER) {
+                        if (UNIQUE) got = got || found;
+                        else {
+                            uint32_t any = (m0 || m1) ? 1u : 0u;                // a match anywhere in the quad's line
+                            any |= quad_perm<0xB1>(any);
+                            any |= quad_perm<0x4E>(any);
+                            got = got || any != 0u;
+                        }
+                        if ((fe < 8u || (UNIQUE && found)) && !got && sub == 0) {
+                            acc_n += 1; acc_k += key[i]; acc_o += val[i];
+                            if (MATERIALIZE) em.emit(key[i], val[i], HJGPU_NULL_VAL);
                         }
                     }
                     if (fe < 8u || (UNIQUE && found)) break;            // the walk ends at the first empty bucket (UNIQUE: first match)
@@ -555,7 +590,13 @@ __device__ __forceinline__ void npj_exists_line_body(NpjProbeArgs a)
 template <bool MATERIALIZE, int MODE>
 __global__ __launch_bounds__(NPJ_PROBE_BLOCK) void npj_exists_line_kernel(NpjProbeArgs a)
 {
-    npj_exists_line_body<MATERIALIZE, true, MODE>(a);
+    npj_mode_line_body<MATERIALIZE, true, MODE>(a);
+}
+
+template <bool MATERIALIZE, bool UNIQUE>
+__global__ __launch_bounds__(NPJ_PROBE_BLOCK) void npj_outer_line_kernel(NpjProbeArgs a)
+{
+    npj_mode_line_body<MATERIALIZE, UNIQUE, HJ_MODE_LEFT_OUTER>(a);
 }
 
 int hj_npj_probe_grid(int cus, size_t n)
@@ -572,7 +613,11 @@ int hj_launch_npj_probe(const NpjProbeArgs &a, int cus, hipStream_t stream, int 
     if (grid_out) *grid_out = grid;
     if (a.line_hash) {
         if (a.buckets % 8 != 0 || ((uintptr_t)a.table & 63)) return HJGPU_EINVAL;
-        if (a.mode == HJ_MODE_SEMI && a.ok) hipLaunchKernelGGL((npj_exists_line_kernel<true, HJ_MODE_SEMI>), dim3(grid), dim3(NPJ_PROBE_BLOCK), 0, stream, a);
+        if (a.mode == HJ_MODE_LEFT_OUTER && a.ok && a.unique) hipLaunchKernelGGL((npj_outer_line_kernel<true, true>), dim3(grid), dim3(NPJ_PROBE_BLOCK), 0, stream, a);
+        else if (a.mode == HJ_MODE_LEFT_OUTER && a.ok) hipLaunchKernelGGL((npj_outer_line_kernel<true, false>), dim3(grid), dim3(NPJ_PROBE_BLOCK), 0, stream, a);
+        else if (a.mode == HJ_MODE_LEFT_OUTER && a.unique) hipLaunchKernelGGL((npj_outer_line_kernel<false, true>), dim3(grid), dim3(NPJ_PROBE_BLOCK), 0, stream, a);
+        else if (a.mode == HJ_MODE_LEFT_OUTER) hipLaunchKernelGGL((npj_outer_line_kernel<false, false>), dim3(grid), dim3(NPJ_PROBE_BLOCK), 0, stream, a);
+        else if (a.mode == HJ_MODE_SEMI && a.ok) hipLaunchKernelGGL((npj_exists_line_kernel<true, HJ_MODE_SEMI>), dim3(grid), dim3(NPJ_PROBE_BLOCK), 0, stream, a);
         else if (a.mode == HJ_MODE_SEMI) hipLaunchKernelGGL((npj_exists_line_kernel<false, HJ_MODE_SEMI>), dim3(grid), dim3(NPJ_PROBE_BLOCK), 0, stream, a);
         else if (a.mode == HJ_MODE_ANTI && a.ok) hipLaunchKernelGGL((npj_exists_line_kernel<true, HJ_MODE_ANTI>), dim3(grid), dim3(NPJ_PROBE_BLOCK), 0, stream, a);
         else if (a.mode == HJ_MODE_ANTI) hipLaunchKernelGGL((npj_exists_line_kernel<false, HJ_MODE_ANTI>), dim3(grid), dim3(NPJ_PROBE_BLOCK), 0, stream, a);
@@ -583,7 +628,11 @@ int hj_launch_npj_probe(const NpjProbeArgs &a, int cus, hipStream_t stream, int 
         return hipGetLastError() == hipSuccess ? HJGPU_OK : HJGPU_EHIP;
     }
     const bool grouped = (a.buckets % 4 == 0) && (((uintptr_t)a.table & 31) == 0);
-    if (a.mode == HJ_MODE_SEMI && grouped) hipLaunchKernelGGL((npj_exists_kernel<true, HJ_MODE_SEMI>), dim3(grid), dim3(NPJ_PROBE_BLOCK), 0, stream, a);
+    if (a.mode == HJ_MODE_LEFT_OUTER && grouped && a.unique) hipLaunchKernelGGL((npj_outer_kernel<true, true>), dim3(grid), dim3(NPJ_PROBE_BLOCK), 0, stream, a);
+    else if (a.mode == HJ_MODE_LEFT_OUTER && grouped) hipLaunchKernelGGL((npj_outer_kernel<true, false>), dim3(grid), dim3(NPJ_PROBE_BLOCK), 0, stream, a);
+    else if (a.mode == HJ_MODE_LEFT_OUTER && a.unique) hipLaunchKernelGGL((npj_outer_kernel<false, true>), dim3(grid), dim3(NPJ_PROBE_BLOCK), 0, stream, a);
+    else if (a.mode == HJ_MODE_LEFT_OUTER) hipLaunchKernelGGL((npj_outer_kernel<false, false>), dim3(grid), dim3(NPJ_PROBE_BLOCK), 0, stream, a);
+    else if (a.mode == HJ_MODE_SEMI && grouped) hipLaunchKernelGGL((npj_exists_kernel<true, HJ_MODE_SEMI>), dim3(grid), dim3(NPJ_PROBE_BLOCK), 0, stream, a);
     else if (a.mode == HJ_MODE_SEMI) hipLaunchKernelGGL((npj_exists_kernel<false, HJ_MODE_SEMI>), dim3(grid), dim3(NPJ_PROBE_BLOCK), 0, stream, a);
     else if (a.mode == HJ_MODE_ANTI && grouped) hipLaunchKernelGGL((npj_exists_kernel<true, HJ_MODE_ANTI>), dim3(grid), dim3(NPJ_PROBE_BLOCK), 0, stream, a);
     else if (a.mode == HJ_MODE_ANTI) hipLaunchKernelGGL((npj_exists_kernel<false, HJ_MODE_ANTI>), dim3(grid), dim3(NPJ_PROBE_BLOCK), 0, stream, a);

@@ -686,7 +686,7 @@ __device__ __forceinline__ void plan_items_body(const PlanArgs &a)
     const uint32_t cap = a.cap ? a.cap : 1u, cap_shift = 31u - (uint32_t)__clz((int)cap);
     // (probe slices | fill groups << 32) of a partition with nr build and ns probe rows; 0 slices = no work
     auto shape_of = [&](u64 nr, u64 ns) -> u64 {
-        // (an anti-join reports the probe rows of a partition without build rows: such a partition has work items too)
+        // (anti- and left outer joins report the probe rows of a partition without build rows: such a partition has work items too)
         const u64 slices = ((nr || a.anti) && ns) ? (ns + HJ_JOIN_SLICE - 1) >> SLICE_SHIFT : 0;
         const u64 groups = a.unique ? (u64)1 : min((u64)HJ_JOIN_FILL_GROUPS, max((u64)1, (nr + cap - 1) >> cap_shift));
         return slices | (groups << 32);
@@ -899,7 +899,8 @@ __global__ __launch_bounds__(256) void group_desc_kernel(const u64 *__restrict__
     // beyond what the workspace was planned for - or offsets that are no prefix of the relations' rows (a caller who overlaps joins of ONE
     // context on several streams races on its workspace: never an address outside the columns): skipped, the join flagged
     if (rn > cap_r || sn > cap_s || re < rb || se < sb || re > n_r || se > n_s) { atomicOr(skew, 1u); rn = 0; sn = 0; }
-    // nothing can match - but an anti-join reports every probe row of a group without build rows (PlanArgs::anti gives them work items)
+    // nothing can match - but anti- and left outer joins report every probe row of a group without build rows (PlanArgs::anti gives
+    // them work items)
     if ((rn == 0 && !anti) || sn == 0) { rn = 0; sn = 0; }
     hj_store(&desc[4 * (u64)g + 0], rb + hj_group_shift(rb, g)); hj_store(&desc[4 * (u64)g + 1], rn);
     hj_store(&desc[4 * (u64)g + 2], sb + hj_group_shift(sb, g)); hj_store(&desc[4 * (u64)g + 3], sn);

@@ -66,6 +66,22 @@ extern "C" {
                                      nor written and may be NULL.  SEMI | ANTI: HJGPU_EINVAL.  HJGPU_FLAG_UNIQUE (or option
                                      "unique") beside either is ignored.  PHJ / CPRA: every key value is legal on both sides;
                                      NPJ: a build key 0 is still HJGPU_EZEROKEY, a probe key 0 matches nothing.           */
+#define HJGPU_FLAG_LEFT_OUTER 8u  /* left outer join that keeps the probe side (S LEFT JOIN R ON S.key = R.key, S the outer
+                                     relation): every inner-join row, exactly as without the flag (build-side duplicates
+                                     multiply the rows, probe-side duplicates are reported one by one), plus ONE row
+                                     (key, outer_val, HJGPU_NULL_VAL) for every probe tuple whose key equals no build key (every
+                                     probe tuple when inner == 0).  count, sum_keys and sum_outer_vals are taken over all rows,
+                                     NULL rows included; sum_inner_vals adds the matched rows' payloads only (a NULL adds 0, as
+                                     SQL's SUM ignores NULL) - the one case where sum_inner_vals is NOT the sum of the
+                                     d_inner_vals column.  Rows have three columns: hjgpu_output::d_inner_vals is required.  A
+                                     row cannot tell a NULL from a genuine build payload 0xFFFFFFFF; the aggregates are exact
+                                     either way.  With HJGPU_FLAG_UNIQUE (or option "unique"): exactly one row per probe tuple,
+                                     its first match or its NULL row (count == outer; which build payload a key with duplicate
+                                     build keys gets is unspecified) - the dimension-lookup join.  Same entry points as
+                                     HJGPU_FLAG_SEMI; every other join entry point refuses it (HJGPU_EINVAL), as do
+                                     LEFT_OUTER | SEMI and LEFT_OUTER | ANTI.  PHJ / CPRA: every key value is legal on both sides;
+                                     NPJ: a build key 0 is still HJGPU_EZEROKEY, a probe key 0 matches nothing (a NULL row).   */
+#define HJGPU_NULL_VAL    0xFFFFFFFFu  /* the inner_val of a left outer join's row without a match                        */
 
 #define HJGPU_MAX_FANOUT  1024u   /* per partitioning pass                                   */
 #define HJGPU_MAX_PARTS   32768u  /* fanout1 * fanout2                                       */
@@ -76,7 +92,9 @@ typedef struct {
     uint64_t count;            /* J                                                          */
     uint64_t sum_keys;         /* sum join_keys[j]        mod 2^64                           */
     uint64_t sum_outer_vals;   /* sum join_outer_vals[j]  (probe-side payload)               */
-    uint64_t sum_inner_vals;   /* sum join_inner_vals[j]  (build-side payload)               */
+    uint64_t sum_inner_vals;   /* sum join_inner_vals[j]  (build-side payload); left outer
+                                  joins (HJGPU_FLAG_LEFT_OUTER): over the matched rows only,
+                                  a NULL row's HJGPU_NULL_VAL adds 0                          */
 } hjgpu_result;
 
 /* Optional materialised output: three device columns of `capacity` uint32.
