@@ -21,7 +21,9 @@ FLAG_UNIQUE = 1
 FLAG_SEMI = 2       # HJGPU_FLAG_SEMI: one row (key, outer_val) per probe tuple with a match
 FLAG_ANTI = 4       # HJGPU_FLAG_ANTI: one row (key, outer_val) per probe tuple without one
 FLAG_LEFT_OUTER = 8     # HJGPU_FLAG_LEFT_OUTER: every match, plus one row (key, outer_val, NULL_VAL) per probe tuple without one
-NULL_VAL = 0xFFFFFFFF   # HJGPU_NULL_VAL: the inner_val of a left outer join's row without a match
+FLAG_RIGHT_OUTER = 16   # HJGPU_FLAG_RIGHT_OUTER: every match, plus one row (key, NULL_VAL, inner_val) per build tuple without one
+FLAG_FULL_OUTER = FLAG_LEFT_OUTER | FLAG_RIGHT_OUTER     # HJGPU_FLAG_FULL_OUTER: both kinds of NULL rows
+NULL_VAL = 0xFFFFFFFF   # HJGPU_NULL_VAL: the value on the side without a match in an outer join's NULL row
 
 EXPORTS = [
     "hjgpu_kernel_hash", "hjgpu_library_hash", "hjgpu_device_count", "hjgpu_create", "hjgpu_destroy", "hjgpu_last_error", "hjgpu_status_string",

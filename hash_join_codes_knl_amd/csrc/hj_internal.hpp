@@ -127,6 +127,7 @@ constexpr uint32_t HJ_TICKET_K6 = 2 * HJ_MAX_CHUNKS;          // K6: [2 * r + pa
 constexpr uint32_t HJ_TICKET_MULTI_FILL = 2 * HJ_MAX_CHUNKS + 8;
 constexpr uint32_t HJ_TICKET_JOIN = 2 * HJ_MAX_CHUNKS + 10;          // K7+K8: two uint64 work counters (8-byte aligned: the block starts on one), the
 constexpr uint32_t HJ_TICKET_JOIN2 = 2 * HJ_MAX_CHUNKS + 12;         // second for the multi-fill half of a _UNIQUE join - zeroed with the tickets, per join
+constexpr uint32_t HJ_TICKET_JOIN3 = 2 * HJ_MAX_CHUNKS + 14;         // third: the marking launch of a full outer join's multi-fill items
 constexpr uint32_t HJ_TICKET_WORDS = 2 * HJ_MAX_CHUNKS + 16;
 struct Pass1Geom {
     u64 n, part;                    // chunk c = rows [part * c, c + 1 == chunks ? n : part * (c + 1)): thread_beg / thread_end with
@@ -182,17 +183,31 @@ struct ScatterArgs {
     uint32_t *claim_overflow;       // device flag: an optimistic region (pass 1 claimed, or pass 2 into claimed final regions) was full
 };
 
-// What a join reports (HJGPU_FLAG_SEMI / _ANTI / _LEFT_OUTER, derived once by hj_join_mode): every match of a probe tuple (inner join),
+// What a join reports (HJGPU_FLAG_SEMI / _ANTI / _LEFT_OUTER / _RIGHT_OUTER, derived once by hj_join_mode): every match of a probe tuple (inner join),
 // ONE row (key, outer_val) per probe tuple that has a match (semi-join) / that has none (anti-join), or every match plus ONE row
 // (key, outer_val, HJGPU_NULL_VAL) per probe tuple that has none (left outer join).
-enum : uint32_t { HJ_MODE_INNER = 0, HJ_MODE_SEMI = 1, HJ_MODE_ANTI = 2, HJ_MODE_LEFT_OUTER = 3 };
+enum : uint32_t { HJ_MODE_INNER = 0, HJ_MODE_SEMI = 1, HJ_MODE_ANTI = 2, HJ_MODE_LEFT_OUTER = 3, HJ_MODE_RIGHT_OUTER = 4, HJ_MODE_FULL_OUTER = 5,
+                  HJ_MODE_MARK = 6 /* kernels only: the marking launch of a full outer join's multi-fill items, never a join's mode */ };
 inline uint32_t hj_join_mode(uint32_t flags)
 {
     return (flags & HJGPU_FLAG_SEMI) ? HJ_MODE_SEMI : (flags & HJGPU_FLAG_ANTI) ? HJ_MODE_ANTI
+         : (flags & HJGPU_FLAG_FULL_OUTER) == HJGPU_FLAG_FULL_OUTER ? HJ_MODE_FULL_OUTER
+         : (flags & HJGPU_FLAG_RIGHT_OUTER) ? HJ_MODE_RIGHT_OUTER
          : (flags & HJGPU_FLAG_LEFT_OUTER) ? HJ_MODE_LEFT_OUTER : HJ_MODE_INNER;
 }
 // the modes that report probe rows without a match: a partition / group / join without build rows still has work
-inline bool hj_mode_keeps_unmatched(uint32_t mode) { return mode == HJ_MODE_ANTI || mode == HJ_MODE_LEFT_OUTER; }
+inline bool hj_mode_keeps_unmatched(uint32_t mode) { return mode == HJ_MODE_ANTI || mode == HJ_MODE_LEFT_OUTER || mode == HJ_MODE_FULL_OUTER; }
+// the modes that report BUILD rows without a match (right and full outer joins): the probes mark what they hit - one bit per build row
+// (PHJ / CPRA: JoinArgs::build_bits) or bucket (NPJ: NpjProbeArgs::bucket_bits) - and a tail kernel behind them reports the rest, so a
+// partition / group / join without probe rows still has build rows to report
+inline bool hj_mode_keeps_build(uint32_t mode) { return mode == HJ_MODE_RIGHT_OUTER || mode == HJ_MODE_FULL_OUTER; }
+// what such a join is when one side is empty: without build rows a full outer join is the left outer join (a right outer join the inner
+// join: no rows), without probe rows both are the right outer join (the tail alone)
+inline uint32_t hj_mode_for_sides(uint32_t mode, bool inner_rows)
+{
+    if (inner_rows) return mode;
+    return mode == HJ_MODE_FULL_OUTER ? (uint32_t)HJ_MODE_LEFT_OUTER : mode == HJ_MODE_RIGHT_OUTER ? (uint32_t)HJ_MODE_INNER : mode;
+}
 // the modes whose rows have two columns (key, outer_val): d_inner_vals is neither read nor written
 inline bool hj_mode_rows2(uint32_t mode) { return mode == HJ_MODE_SEMI || mode == HJ_MODE_ANTI; }
 
@@ -224,7 +239,7 @@ struct JoinArgs {
     // broadcast join (tiny build side, nothing partitioned): P = 1, the relations are the caller's columns, the
     // empty sentinel is *sentinel (a value no build key equals, found by hj_launch_broadcast_meta)
     uint32_t broadcast;
-    uint32_t mode;                       // HJ_MODE_*: semi- / anti-joins take exists_probe_kernel, left outer joins outer_probe_kernel (in
+    uint32_t mode;                       // HJ_MODE_*: semi- / anti-joins take exists_probe_kernel, left / right / full outer joins outer_ / right_ / full_probe_kernel (in
                                          // the padding before `sentinel`: the other fields keep their offsets)
     const uint32_t *sentinel;
     uint32_t force_chained;              // tests: skip the cuckoo fast path (option "force_chained")
@@ -238,7 +253,15 @@ struct JoinArgs {
                                          // none yet) - the groups' joins share one block counter, one set of open blocks and ONE close_gaps at the end
     uint32_t s_pieces;                   // claimed probe side: 1 - the probe side has 1 + s_pieces pieces per partition in soff / send (front lines,
                                          // back tails) while the build side has `chunks` = 1; else 0
+    // right / full outer joins (hj_mode_keeps_build): one bit per row of the partitioned build array `rk` (bit i = tuple i of the array),
+    // zeroed per join; the probes OR in the rows whose key a probe tuple carried, hj_launch_build_unmatched reports the others
+    uint32_t *build_bits;
+    u64 *work_counter3;                  // full outer joins: the work counter of the launch that marks for the multi-fill items (mark_probe_kernel)
 };
+// The tail of a right / full outer join (build_unmatched_kernel), behind the join's launches on the same stream and with the join's grid:
+// every row of the partitioned build array (pieces roff / rend of `a`) whose bit in a.build_bits is clear leaves as (key, HJGPU_NULL_VAL,
+// inner_val) and is added to count / sum_keys / sum_inner_vals.  Wave w of workgroup b goes on in the output block that wave left open.
+int hj_launch_build_unmatched(const JoinArgs &a, const HjTuning &t, int cus, hipStream_t stream);
 
 struct PlanArgs {
     const u64 *counts[2];     // [chunks*P] fused two-level histograms of R (0) and S (1)
@@ -308,7 +331,7 @@ int hj_launch_hist2(const uint32_t *keys, const Pass1Geom &geom,
 // A group with an empty side gets no rows at all (nothing can match; anti / left outer: a group without build rows keeps its probe rows); one beyond
 // cap_r / cap_s rows gets none either and raises *skew.
 int hj_launch_group_desc(const u64 *roff, const u64 *soff, uint32_t G, uint32_t bins, u64 cap_r, u64 cap_s, u64 n_r, u64 n_s, u64 *desc, uint32_t *skew,
-                         hipStream_t stream, bool anti = false);
+                         hipStream_t stream, bool anti = false, bool keep_build = false /* right / full outer: a group without probe rows keeps its build rows */);
 // d_result of a device-planned grouped join: the aggregates, or all ones when a group was skipped (*skew != 0): never a plausible partial count
 int hj_launch_group_result(const hjgpu_result *state, const uint32_t *skew, hjgpu_result *d_result, hipStream_t stream);
 // own_count > 0 (chunks == 1): partitions [own_first, own_first + own_count) are laid out behind all others
@@ -373,7 +396,11 @@ struct NpjProbeArgs {
     u64 *block_counter;
     u64 *final_offsets;
     uint32_t *overflow;
+    uint32_t *bucket_bits;               // right / full outer joins: one bit per bucket, zeroed per join; the probes OR in every bucket they match
 };
+// The tail of a right / full outer NPJ join (npj_unmatched_kernel), with the probe's grid (`grid`; its waves go on in the probe's open
+// output blocks when `resume`): every tuple of the table whose bucket's bit is clear leaves as (key, HJGPU_NULL_VAL, inner_val)
+int hj_launch_npj_unmatched(const NpjProbeArgs &a, int grid, bool resume, hipStream_t stream);
 int hj_launch_npj_probe(const NpjProbeArgs &a, int cus, hipStream_t stream, int *grid_out);
 
 // K9: compact the per-wave partially filled tail blocks (npj.cpp:475-514).

@@ -358,6 +358,9 @@ int setup_output(hjgpu_ctx *ctx, const hjgpu_output *out, uint32_t workers, u64 
     *block_size = 0; *block_limit = 0;
     if (!out || !out->d_keys) return HJGPU_OK;
     // (semi- and anti-join rows have no inner_val: d_inner_vals may be NULL, it is neither read nor written)
+    if (hj_mode_keeps_build(mode) && (!out->d_outer_vals || !out->d_inner_vals))
+        return fail(ctx, HJGPU_EINVAL, mode == HJ_MODE_FULL_OUTER ? "HJGPU_FLAG_FULL_OUTER: rows have three columns, d_outer_vals and d_inner_vals are both required"
+                                                                  : "HJGPU_FLAG_RIGHT_OUTER: rows have three columns, d_outer_vals and d_inner_vals are both required");
     if (!out->d_outer_vals || (!out->d_inner_vals && !hj_mode_rows2(mode))) return fail(ctx, HJGPU_EINVAL, "output columns");
     u64 bs = out->block_size ? out->block_size : 65536;
     if (bs < 256 || (bs & (bs - 1))) return fail(ctx, HJGPU_EINVAL, "block_size must be a power of two >= 256");
@@ -498,6 +501,19 @@ int check_join_mode(hjgpu_ctx *ctx, uint32_t flags)
 {
     if ((flags & HJGPU_FLAG_SEMI) && (flags & HJGPU_FLAG_ANTI))
         return fail(ctx, HJGPU_EINVAL, "HJGPU_FLAG_SEMI | HJGPU_FLAG_ANTI: a join is a semi-join or an anti-join, not both");
+    if (flags & HJGPU_FLAG_RIGHT_OUTER) {
+        // (a first-match walk leaves the other copies of a duplicated build key unvisited: neither in a row nor NULL)
+        const bool full = (flags & HJGPU_FLAG_FULL_OUTER) == HJGPU_FLAG_FULL_OUTER;
+        const char *other = (flags & HJGPU_FLAG_SEMI) ? "HJGPU_FLAG_SEMI" : (flags & HJGPU_FLAG_ANTI) ? "HJGPU_FLAG_ANTI"
+                          : (flags & HJGPU_FLAG_UNIQUE) ? "HJGPU_FLAG_UNIQUE" : ctx->tune.unique ? "option unique" : nullptr;
+        if (other) {
+            char what[200];
+            snprintf(what, sizeof(what), "%s with %s: a join that keeps the build side reports every copy of a build key; it is no semi-, anti- or "
+                     "first-match join", full ? "HJGPU_FLAG_FULL_OUTER" : "HJGPU_FLAG_RIGHT_OUTER", other);
+            return fail(ctx, HJGPU_EINVAL, what);
+        }
+        return HJGPU_OK;
+    }
     if ((flags & HJGPU_FLAG_LEFT_OUTER) && (flags & (HJGPU_FLAG_SEMI | HJGPU_FLAG_ANTI)))
         return fail(ctx, HJGPU_EINVAL, (flags & HJGPU_FLAG_SEMI) ? "HJGPU_FLAG_LEFT_OUTER | HJGPU_FLAG_SEMI: a join is a left outer join or a semi-join, not both"
                                                                  : "HJGPU_FLAG_LEFT_OUTER | HJGPU_FLAG_ANTI: a join is a left outer join or an anti-join, not both");
@@ -506,14 +522,16 @@ int check_join_mode(hjgpu_ctx *ctx, uint32_t flags)
 
 static const char *join_mode_flag_name(uint32_t flags)
 {
-    return (flags & HJGPU_FLAG_SEMI) ? "HJGPU_FLAG_SEMI" : (flags & HJGPU_FLAG_ANTI) ? "HJGPU_FLAG_ANTI" : "HJGPU_FLAG_LEFT_OUTER";
+    return (flags & HJGPU_FLAG_SEMI) ? "HJGPU_FLAG_SEMI" : (flags & HJGPU_FLAG_ANTI) ? "HJGPU_FLAG_ANTI"
+         : (flags & HJGPU_FLAG_FULL_OUTER) == HJGPU_FLAG_FULL_OUTER ? "HJGPU_FLAG_FULL_OUTER"
+         : (flags & HJGPU_FLAG_RIGHT_OUTER) ? "HJGPU_FLAG_RIGHT_OUTER" : "HJGPU_FLAG_LEFT_OUTER";
 }
 
 int refuse_join_mode(hjgpu_ctx *ctx, uint32_t flags, const char *entry)
 {
-    if (!(flags & (HJGPU_FLAG_SEMI | HJGPU_FLAG_ANTI | HJGPU_FLAG_LEFT_OUTER))) return HJGPU_OK;
+    if (!(flags & (HJGPU_FLAG_SEMI | HJGPU_FLAG_ANTI | HJGPU_FLAG_LEFT_OUTER | HJGPU_FLAG_RIGHT_OUTER))) return HJGPU_OK;
     char what[256];
-    snprintf(what, sizeof(what), "%s: %s is not supported here (semi-, anti- and left outer joins: hjgpu_phj, hjgpu_cpra, hjgpu_npj, "
+    snprintf(what, sizeof(what), "%s: %s is not supported here (semi-, anti- and outer joins: hjgpu_phj, hjgpu_cpra, hjgpu_npj, "
              "their _async forms and hjgpu_phj_overlapped_async)", entry, join_mode_flag_name(flags));
     return fail(ctx, HJGPU_EINVAL, what);
 }
@@ -523,7 +541,8 @@ static int refuse_mode_geometry(hjgpu_ctx *ctx, uint32_t mode)
 {
     char what[160];
     snprintf(what, sizeof(what), "HJGPU_FLAG_%s: the join_cfg geometry of this context has no _UNIQUE instance (geometries with one: 512,13,2 and "
-             "1024,14,2)", mode == HJ_MODE_SEMI ? "SEMI" : mode == HJ_MODE_ANTI ? "ANTI" : mode == HJ_MODE_LEFT_OUTER ? "LEFT_OUTER" : "UNIQUE");
+             "1024,14,2)", mode == HJ_MODE_SEMI ? "SEMI" : mode == HJ_MODE_ANTI ? "ANTI" : mode == HJ_MODE_LEFT_OUTER ? "LEFT_OUTER"
+             : mode == HJ_MODE_RIGHT_OUTER ? "RIGHT_OUTER" : mode == HJ_MODE_FULL_OUTER ? "FULL_OUTER" : "UNIQUE");
     return fail(ctx, HJGPU_EINVAL, what);
 }
 
@@ -546,6 +565,14 @@ static u64 claimed_cap(u64 mean, int slack)
     return (c + HJ_LINE_TUPLES - 1) & ~(u64)(HJ_LINE_TUPLES - 1);
 }
 
+// right / full outer joins: bytes of the bitmap with one bit per row of the partitioned build array (pass 1's twin, or pass 2's with its
+// line padding; + the 4 spare tuples, whole words, one word of slack)
+static size_t build_bits_bytes(const PhjPlan &pl, size_t inner)
+{
+    const size_t rows = inner + 4 + (pl.F2 > 1 ? (size_t)pl.C * pl.P * HJ_LINE_TUPLES : 0);
+    return ((rows + 31) / 32 + 2) * sizeof(uint32_t);
+}
+
 int phj_prepare(hjgpu_ctx *ctx, size_t inner, size_t outer, const hjgpu_phj_params *prm,
                 uint32_t chunks, PhjPlan *pl, bool pre, int big_override, size_t plan_inner, bool claim_s)
 {
@@ -553,9 +580,10 @@ int phj_prepare(hjgpu_ctx *ctx, size_t inner, size_t outer, const hjgpu_phj_para
     ReserveClock clock(ctx);
     pl->C = chunks;
     pl->pre = pre ? 1u : 0u; pl->pre_f1 = 1; pl->pre_F1tot = 1; pl->pre_base = 0;
-    pl->mode = (uint8_t)(prm ? hj_join_mode(prm->flags) : HJ_MODE_INNER);
+    pl->mode = (uint8_t)hj_mode_for_sides(prm ? hj_join_mode(prm->flags) : HJ_MODE_INNER, inner != 0);
     pl->first_match = ctx->tune.unique || (prm && (prm->flags & HJGPU_FLAG_UNIQUE)) || hj_mode_rows2(pl->mode);
-    pl->unique = pl->first_match || pl->mode != HJ_MODE_INNER;
+    // (a right outer join is planned like the inner join: fill groups, one launch)
+    pl->unique = pl->first_match || (pl->mode != HJ_MODE_INNER && pl->mode != HJ_MODE_RIGHT_OUTER);
     choose_fanout(ctx->tune, plan_inner ? plan_inner : inner, prm, &pl->F1, &pl->F2, &pl->big_tables);
     if (big_override >= 0) pl->big_tables = big_override != 0;
     if (chunks > 8 && !pre) {
@@ -569,7 +597,8 @@ int phj_prepare(hjgpu_ctx *ctx, size_t inner, size_t outer, const hjgpu_phj_para
             pl->F2 = 2; pl->F1 = (parts + 1) / 2;
         }
     }
-    if (pl->unique && !hj_join_config_built(hj_join_config_of(ctx->tune, pl->big_tables), true)) return refuse_mode_geometry(ctx, pl->mode);
+    if ((pl->unique || hj_mode_keeps_build(pl->mode)) && !hj_join_config_built(hj_join_config_of(ctx->tune, pl->big_tables), true))
+        return refuse_mode_geometry(ctx, pl->mode);
     pl->P = pl->F1 * pl->F2;
     if (pl->F1 < 1 || pl->F2 < 1 || pl->F1 > HJGPU_MAX_FANOUT || pl->F2 > HJGPU_MAX_FANOUT ||
         pl->P < 2 || pl->P > HJGPU_MAX_PARTS)
@@ -645,6 +674,7 @@ int phj_prepare(hjgpu_ctx *ctx, size_t inner, size_t outer, const hjgpu_phj_para
             CHK(ensure(ctx, ctx->tmp[3], pl->batch_bytes));
         }
     }
+    if (hj_mode_keeps_build(pl->mode)) CHK(ensure(ctx, ctx->build_bits, build_bits_bytes(*pl, inner)));
     MetaLayout sz = carve(nullptr, pl->C, pl->F1, pl->P, pl->ranges, pl->items_extra, pl->tiles2, pl->batch_cap, pl->tdesc_b_cap);
     CHK(ensure(ctx, ctx->meta, sz.total_bytes));
     CHK(ensure(ctx, ctx->state, sizeof(DevState)));
@@ -900,8 +930,10 @@ int phj_enqueue(hjgpu_ctx *ctx, const PhjPlan &pl,
     const uint32_t *fin[4] = {t1[0], t1[1], t1[2], t1[3]};
     if (pl.F2 > 1) for (int i = 0; i < 4; ++i) fin[i] = t2[i];
 
-    // K7+K8
-    if (inner && outer && mode != PHJ_BUILD_ONLY) {
+    // K7+K8 (right / full outer joins: + the bitmap's clear in front and the tail kernel behind; without probe rows the tail alone)
+    const bool keepb = hj_mode_keeps_build(pl.mode);
+    if (keepb && (pre || mode != PHJ_WHOLE)) return fail(ctx, HJGPU_EINVAL, "internal: a right / full outer join is a whole join");
+    if (inner && (outer || keepb) && mode != PHJ_BUILD_ONLY) {
         JoinArgs ja{};
         ja.rk = fin[0]; ja.rv = fin[1]; ja.sk = fin[2]; ja.sv = fin[3];
         ja.roff = m.off2[0]; ja.soff = m.off2[1];
@@ -926,14 +958,22 @@ int phj_enqueue(hjgpu_ctx *ctx, const PhjPlan &pl,
         // (the work counters live with the tickets: zeroed with them, per join - also for a group, whose DevState is the grouped join's)
         ja.work_counter = reinterpret_cast<u64 *>(m.tickets + HJ_TICKET_JOIN);
         ja.work_counter2 = reinterpret_cast<u64 *>(m.tickets + HJ_TICKET_JOIN2);
+        ja.work_counter3 = reinterpret_cast<u64 *>(m.tickets + HJ_TICKET_JOIN3);
         ja.multi_fill = m.tickets + HJ_TICKET_MULTI_FILL;
         ja.resume = grp ? 1u : 0u;
         join_output(ctx, ja, out, bs, bl, st);
-        CHK(hj_launch_join(ja, ctx->tune, ctx->cus, stream));
+        if (keepb) {
+            ja.build_bits = reinterpret_cast<uint32_t *>(ctx->build_bits.p);
+            HIPCHK(ctx, hj_zero_async(ja.build_bits, build_bits_bytes(pl, inner), stream));
+            // no join launch below: every wave of the tail starts without an open block (a group goes on in the grouped join's)
+            if (!outer && bs && !grp) HIPCHK(ctx, hj_fill_async(ctx->final_offsets.p, 0xFFFFFFFFu, (size_t)workers * sizeof(u64), stream));
+        }
+        if (outer) CHK(hj_launch_join(ja, ctx->tune, ctx->cus, stream));
+        if (keepb) CHK(hj_launch_build_unmatched(ja, ctx->tune, ctx->cus, stream));
         if (audit) CHK(hj_audit_copy(reinterpret_cast<const u64 *>(&st->result), audit + 4 * 6, 4, stream));
     }
     record(ctx, EV_JOIN, stream);
-    if (bs && inner && outer && mode != PHJ_BUILD_ONLY && !grp) CHK(close_gaps(ctx, out, workers, bs, st, stream, hj_mode_rows2(pl.mode)));
+    if (bs && inner && (outer || keepb) && mode != PHJ_BUILD_ONLY && !grp) CHK(close_gaps(ctx, out, workers, bs, st, stream, hj_mode_rows2(pl.mode)));
     record(ctx, EV_GAPS, stream);
     ctx->stats.fanout1 = pl.F1; ctx->stats.fanout2 = pl.F2; ctx->stats.buckets = 0; ctx->stats.batches = batches_used;
     ctx->last_algo = 1;
@@ -983,6 +1023,8 @@ bool npj_unique(const hjgpu_ctx *ctx, const hjgpu_npj_params *prm)
 
 uint32_t npj_mode(const hjgpu_npj_params *prm) { return prm ? hj_join_mode(prm->flags) : HJ_MODE_INNER; }
 
+static size_t npj_bucket_bits_bytes(size_t buckets) { return ((buckets + 31) / 32 + 1) * sizeof(uint32_t); }
+
 int npj_prepare(hjgpu_ctx *ctx, size_t inner, const hjgpu_npj_params *prm, size_t *buckets,
                 uint32_t *factor)
 {
@@ -997,32 +1039,38 @@ int npj_prepare(hjgpu_ctx *ctx, size_t inner, const hjgpu_npj_params *prm, size_
     *factor = (prm && prm->factor) ? prm->factor : DEFAULT_NPJ_FACTOR;
     if (!(*factor & 1)) return fail(ctx, HJGPU_EINVAL, "hash factor must be odd");
     CHK(ensure_placed(ctx, ctx->table, b * sizeof(u64)));     // >= 1 GB tables: the build (memset + CAS) is 8 % faster in a well-placed block
+    if (hj_mode_keeps_build(npj_mode(prm))) CHK(ensure(ctx, ctx->build_bits, npj_bucket_bits_bytes(b)));   // right / full outer: one bit per bucket
     CHK(ensure(ctx, ctx->state, sizeof(DevState)));
     return HJGPU_OK;
 }
 
 int npj_probe_enqueue(hjgpu_ctx *ctx, const uint32_t *sk, const uint32_t *sv, size_t outer,
                       const u64 *table, size_t buckets, uint32_t factor, const hjgpu_output *out,
-                      hipStream_t stream, bool line_hash, bool unique, uint32_t mode)
+                      hipStream_t stream, bool line_hash, bool unique, uint32_t mode, uint32_t *bucket_bits)
 {
     DevState *st = reinterpret_cast<DevState *>(ctx->state.p);
     u64 bs = 0, bl = 0;
     const int grid = hj_npj_probe_grid(ctx->cus, outer);
+    const bool keepb = hj_mode_keeps_build(mode);
+    if (keepb && (!bucket_bits || unique)) return fail(ctx, HJGPU_EINVAL, "internal: a right / full outer NPJ join needs its bucket bitmap and the full walk");
     CHK(setup_output(ctx, out, (uint32_t)grid * 4, &bs, &bl, mode));
-    if (outer) {
+    if (outer || keepb) {
         NpjProbeArgs pa;
         memset(&pa, 0, sizeof(pa));
         pa.keys = sk; pa.vals = sv; pa.n = outer; pa.table = table; pa.buckets = buckets;
         pa.factor = factor; pa.line_hash = line_hash ? 1u : 0u; pa.unique = (unique || hj_mode_rows2(mode)) ? 1u : 0u; pa.mode = mode; pa.result = &st->result;
+        pa.bucket_bits = bucket_bits;
         if (bs) {
             pa.ok = out->d_keys; pa.oov = out->d_outer_vals; pa.oiv = out->d_inner_vals;
             pa.block_size = bs; pa.block_limit = bl; pa.block_counter = &st->block_counter;
             pa.final_offsets = (u64 *)ctx->final_offsets.p; pa.overflow = &st->overflow;
         }
-        CHK(hj_launch_npj_probe(pa, ctx->cus, stream, nullptr));
+        if (outer) CHK(hj_launch_npj_probe(pa, ctx->cus, stream, nullptr));
+        // the tail: the table's tuples whose bucket no probe marked, in the probe's open output blocks (no probe rows: none open)
+        if (keepb) CHK(hj_launch_npj_unmatched(pa, grid, outer != 0, stream));
     }
     record(ctx, EV_JOIN, stream);
-    if (bs && outer) CHK(close_gaps(ctx, out, (uint32_t)grid * 4, bs, st, stream, hj_mode_rows2(mode)));
+    if (bs && (outer || keepb)) CHK(close_gaps(ctx, out, (uint32_t)grid * 4, bs, st, stream, hj_mode_rows2(mode)));
     record(ctx, EV_GAPS, stream);
     return HJGPU_OK;
 }
@@ -1043,7 +1091,14 @@ int npj_enqueue(hjgpu_ctx *ctx, const uint32_t *rk, const uint32_t *rv, size_t i
     const bool line = !ctx->tune.npj_refhash;
     if (inner) CHK(hj_launch_npj_build(rk, rv, inner, table, buckets, factor, &st->zero_key, ctx->cus, stream, line));
     record(ctx, EV_R_HIST, stream);     // reused as "end of build"
-    CHK(npj_probe_enqueue(ctx, sk, sv, outer, table, buckets, factor, out, stream, line, unique, mode));
+    // (no build rows: a full outer join is the left outer join, a right outer join has no rows - hj_mode_for_sides)
+    mode = hj_mode_for_sides(mode, inner != 0);
+    uint32_t *bits = nullptr;
+    if (hj_mode_keeps_build(mode)) {
+        bits = reinterpret_cast<uint32_t *>(ctx->build_bits.p);
+        HIPCHK(ctx, hj_zero_async(bits, npj_bucket_bits_bytes(buckets), stream));
+    }
+    CHK(npj_probe_enqueue(ctx, sk, sv, outer, table, buckets, factor, out, stream, line, unique, mode, bits));
     ctx->stats.fanout1 = ctx->stats.fanout2 = 0; ctx->stats.buckets = buckets; ctx->stats.batches = 0;
     ctx->last_algo = 0;
     return HJGPU_OK;
@@ -1139,7 +1194,7 @@ int hjgpu_destroy(hjgpu_ctx *ctx)
     (void)hipDeviceSynchronize();
     DevBuf *all[] = {&ctx->tmp[0], &ctx->tmp[1], &ctx->tmp[2], &ctx->tmp[3], &ctx->tmp[4], &ctx->tmp[5],
                      &ctx->tmp[6], &ctx->tmp[7], &ctx->meta, &ctx->table, &ctx->state, &ctx->moves,
-                     &ctx->final_offsets, &ctx->grp[0], &ctx->grp[1], &ctx->grp[2], &ctx->grp[3], &ctx->grp_off, &ctx->audit, &ctx->audit_lay};
+                     &ctx->final_offsets, &ctx->build_bits, &ctx->grp[0], &ctx->grp[1], &ctx->grp[2], &ctx->grp[3], &ctx->grp_off, &ctx->audit, &ctx->audit_lay};
     for (DevBuf *b : all) if (b->p) (void)hipFree(b->p);
     for (int i = 0; i < EV_COUNT; ++i) (void)hipEventDestroy(ctx->ev[i]);
     if (ctx->aux) (void)hipStreamDestroy(ctx->aux);
@@ -1555,6 +1610,9 @@ static bool broadcast_applies(const HjTuning &tune, size_t inner, size_t outer, 
 {
     // an anti- or left outer join with no build rows reports the whole probe side, whatever the plan: one broadcast item per slice with no fill
     if (prm && hj_mode_keeps_unmatched(hj_join_mode(prm->flags)) && inner == 0 && outer) return true;
+    // right / full outer joins take the partitioned plan: the bitmap lives over the partitioned build array, and a tiny build side is no
+    // reason for a second marking scheme over the caller's columns
+    if (prm && hj_mode_keeps_build(hj_join_mode(prm->flags))) return false;
     if (tune.no_broadcast) return false;
     if (chunks != 1 || (prm && (prm->fanout1 || prm->fanout2))) return false;    // an explicit plan is honoured
     return inner && outer && inner <= broadcast_rows(tune, true) && inner <= 16383;
@@ -1574,7 +1632,8 @@ static int broadcast_enqueue(hjgpu_ctx *ctx, const uint32_t *rk, const uint32_t 
     const size_t cap = (size_t)hj_join_config_of(ctx->tune, big).cap();
     const size_t nslices = (outer + HJ_JOIN_SLICE - 1) / HJ_JOIN_SLICE;
     const size_t fills = (inner + cap - 1) / cap;
-    const uint32_t jmode = prm ? hj_join_mode(prm->flags) : HJ_MODE_INNER;
+    const uint32_t jmode = hj_mode_for_sides(prm ? hj_join_mode(prm->flags) : HJ_MODE_INNER, inner != 0);
+    if (hj_mode_keeps_build(jmode)) return fail(ctx, HJGPU_EINVAL, "internal: right / full outer joins are not broadcast");
     // first_match: the probe walk (JoinArgs::unique); unique: one fill group per probe slice (semi-, anti- and left outer joins too)
     const bool first_match = ctx->tune.unique || (prm && (prm->flags & HJGPU_FLAG_UNIQUE)) || hj_mode_rows2(jmode);
     const bool unique = first_match || jmode != HJ_MODE_INNER;
@@ -1688,7 +1747,9 @@ static int phj_grouped(hjgpu_ctx *ctx, uint32_t G, uint32_t chunks,
     const u64 bs = out_on ? (out->block_size ? out->block_size : 65536) : 0;
     const uint32_t jmode = prm ? hj_join_mode(prm->flags) : HJ_MODE_INNER;
     for (uint32_t g = 0; g < G; ++g) {
-        if (pc[g].sn == 0 || (pc[g].rn == 0 && !hj_mode_keeps_unmatched(jmode))) continue;   // nothing can match (anti / left outer: all reported)
+        // nothing can match (anti / left / full outer: the probe rows of a group without build rows are all reported; right / full outer:
+        // the build rows of a group without probe rows - its build side is partitioned and the tail runs alone)
+        if ((pc[g].sn == 0 && !(hj_mode_keeps_build(jmode) && pc[g].rn)) || (pc[g].rn == 0 && !hj_mode_keeps_unmatched(jmode))) continue;
         hjgpu_output view;
         const hjgpu_output *vout = nullptr;
         if (out_on) {
@@ -1793,7 +1854,7 @@ static int phj_grouped_device(hjgpu_ctx *ctx, uint32_t G, uint32_t chunks,
     HIPCHK(ctx, hj_zero_async(st, sizeof(DevState), stream));
     if (bs) HIPCHK(ctx, hj_fill_async(ctx->final_offsets.p, 0xFFFFFFFFu, (size_t)workers * sizeof(u64), stream));
     CHK(hj_launch_group_desc(d_off, d_off + (l.F0 + 1), G, l.bins, (u64)cap_r, (u64)cap_s, (u64)inner, (u64)outer, d_desc, &st->group_skew, stream,
-                             hj_mode_keeps_unmatched(pl.mode)));
+                             hj_mode_keeps_unmatched(pl.mode), hj_mode_keeps_build(pl.mode)));
     HIPCHK(ctx, hipEventRecord(ctx->grp_ev_pass0[1], stream));
     for (uint32_t g = 0; g < G; ++g) {
         const GroupRun run = {d_desc + 4 * (size_t)g};

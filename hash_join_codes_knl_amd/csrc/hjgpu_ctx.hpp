@@ -53,6 +53,7 @@ struct hjgpu_ctx {
     DevBuf state;           // DevState
     DevBuf moves;           // close_gaps move list
     DevBuf final_offsets;   // per-wave end cursors
+    DevBuf build_bits;      // right / full outer joins: one bit per row of the partitioned build array (PHJ / CPRA) or per bucket (NPJ)
     hipEvent_t ev[EV_COUNT];
     bool ev_valid[EV_COUNT];
     hjgpu_stats stats;
@@ -303,7 +304,8 @@ bool npj_unique(const hjgpu_ctx *ctx, const hjgpu_npj_params *prm);
 uint32_t npj_mode(const hjgpu_npj_params *prm);
 int npj_prepare(hjgpu_ctx *ctx, size_t inner, const hjgpu_npj_params *prm, size_t *buckets, uint32_t *factor);
 int npj_probe_enqueue(hjgpu_ctx *ctx, const uint32_t *sk, const uint32_t *sv, size_t outer, const u64 *table, size_t buckets, uint32_t factor,
-                      const hjgpu_output *out, hipStream_t stream, bool line_hash = false, bool unique = false, uint32_t mode = HJ_MODE_INNER);
+                      const hjgpu_output *out, hipStream_t stream, bool line_hash = false, bool unique = false, uint32_t mode = HJ_MODE_INNER,
+                      uint32_t *bucket_bits = nullptr /* right / full outer joins of hjgpu_npj*: the zeroed bucket bitmap; the tail follows the probe */);
 int npj_enqueue(hjgpu_ctx *ctx, const uint32_t *rk, const uint32_t *rv, size_t inner, const uint32_t *sk, const uint32_t *sv, size_t outer,
                 size_t buckets, uint32_t factor, const hjgpu_output *out, hipStream_t stream, bool unique, uint32_t mode = HJ_MODE_INNER);
 const hjgpu_output *take_async_output(hjgpu_ctx *ctx, const hjgpu_output *given);

@@ -76,6 +76,10 @@ constexpr int hj_join_waves_per_simd(int block, int log2slots)
 struct hj_tail_pass {
     __device__ uint32_t operator()(const uint32_t (&)[4], const uint32_t (&)[4], const bool (&)[4]) const { return 0u; }
 };
+// the probe of HJ_MODE_MARK (join_body): nothing is reported, the table slots the item's probe rows hit are marked
+struct hj_mark_pass {
+    __device__ uint32_t operator()(const uint32_t (&)[4], const uint32_t (&)[4], const bool (&)[4]) const { return 0u; }
+};
 
 // NTROWS: result rows through non-temporal stores (EmitterT<true>; JoinArgs::nt_rows) - false only for solo joins
 // MODE (HJ_MODE_*): what a probe tuple reports.  HJ_MODE_INNER: its matches (join_kernel).  HJ_MODE_SEMI / HJ_MODE_ANTI
@@ -92,14 +96,41 @@ struct hj_tail_pass {
 // NULL rows together (one emit4 when each of its tuples yields exactly one row: every full vector under UNIQUE); a multi-fill item emits
 // the matches of every fill and marks their rows (under UNIQUE the marks also skip the rows in later fills), then reports the unmarked
 // rows in the anti-join's tail pass; an item without build rows reports all its probe rows.
+// HJ_MODE_RIGHT_OUTER (right_probe_kernel) reports what the inner join reports, HJ_MODE_FULL_OUTER (full_probe_kernel) what the left outer
+// join reports; both also find out which BUILD rows matched.  "Matched" is a property of a build key - if any probe tuple carries it,
+// every build row with it is matched - so the table needs no row ids: a probe sets one bit per table SLOT it hits in LDS (`slot_bits`),
+// and after the probe loop of each table fill the workgroup walks the fill's build rows once more (L2-hot), looks every key up and ORs
+// "a slot holding this key is marked" into JoinArgs::build_bits, one bit per row of the partitioned build array.  The OR is atomic, on
+// whole 32-bit words from a ballot (a wave's rows are consecutive): the slices of one partition are work items of their own, in any
+// workgroups and any order, and each sees only its own probe rows.  The rows whose bit stays clear - also those of partitions without a
+// single work item - are reported by build_unmatched_kernel behind the join.  Never with UNIQUE: a first-match walk would leave the other
+// copies of a duplicated build key unvisited.
+// The multi-fill items of a full outer join: the left outer join's multi-fill instance is at its 128 VGPRs - anything added to it, even the
+// clear of `slot_bits`, spills - so it reports them as it is (outer_probe_kernel<.., DEDUP>), and a third launch, HJ_MODE_MARK
+// (mark_probe_kernel), fills the tables of those items once more and only marks (hj_mark_pass): no rows, no aggregates.
+template <bool ON, uint32_t WORDS>
+struct SlotBits {
+    static __device__ __forceinline__ uint32_t *get() { __shared__ uint32_t bits[WORDS]; return bits; }
+};
+template <uint32_t WORDS>
+struct SlotBits<false, WORDS> {
+    static __device__ __forceinline__ uint32_t *get() { return nullptr; }
+};
+
 template <int BLOCK, int LOG2SLOTS, int BATCH, bool PACKED, bool UNIQUE, bool DEDUP, bool NTROWS, int MODE>
 __device__ __forceinline__ void join_body(JoinArgs a)
 {
-    static_assert(UNIQUE || !DEDUP || MODE == HJ_MODE_LEFT_OUTER, "DEDUP is the multi-fill half of a _UNIQUE or left outer join");
-    static_assert(MODE == HJ_MODE_INNER || ((UNIQUE || MODE == HJ_MODE_LEFT_OUTER) && NTROWS),
+    // LEFTISH: the modes that report like the left outer join; KEEPB: the modes that mark the build rows their probes hit
+    constexpr bool LEFTISH = MODE == HJ_MODE_LEFT_OUTER || MODE == HJ_MODE_FULL_OUTER;
+    constexpr bool MARKING = MODE == HJ_MODE_MARK;
+    constexpr bool KEEPB = MODE == HJ_MODE_RIGHT_OUTER || MODE == HJ_MODE_FULL_OUTER || MARKING;
+    static_assert(UNIQUE || !DEDUP || MODE == HJ_MODE_LEFT_OUTER || MARKING, "DEDUP is the multi-fill half of a _UNIQUE or left / full outer join");
+    static_assert(MODE == HJ_MODE_INNER || ((UNIQUE || LEFTISH || KEEPB) && NTROWS),
                   "semi- and anti-joins walk to the first match; rows non-temporal");
-    // the two launches of a _UNIQUE join: single-fill items, then multi-fill ones (DEDUP); left outer joins always
-    constexpr bool SPLIT = UNIQUE || MODE == HJ_MODE_LEFT_OUTER;
+    static_assert(!(KEEPB && UNIQUE), "right and full outer joins walk to every copy of a build key");
+    static_assert(MARKING == (KEEPB && DEDUP), "the multi-fill items of a full outer join are marked by a launch of its own");
+    // the two launches of a _UNIQUE join: single-fill items, then multi-fill ones (DEDUP); left and full outer joins always
+    constexpr bool SPLIT = UNIQUE || LEFTISH || MARKING;
     // the plan found no partition that takes several fills (the planned case): nothing for this launch to do
     if (DEDUP && a.multi_fill && *a.multi_fill == 0) return;
     constexpr uint32_t SLOTS = 1u << LOG2SLOTS;
@@ -114,10 +145,11 @@ __device__ __forceinline__ void join_body(JoinArgs a)
     __shared__ u64 wave_cursor[NW];
     __shared__ uint32_t cuckoo_failed;
     // UNIQUE: one bit per probe row of the current work item (<= HJ_JOIN_SLICE + 1 rows per chunk piece)
-    constexpr uint32_t MATCHED_WORDS = DEDUP ? (HJ_JOIN_SLICE + 64) / 32 + 2 : 1;
+    constexpr uint32_t MATCHED_WORDS = (DEDUP && !MARKING) ? (HJ_JOIN_SLICE + 64) / 32 + 2 : 1;
     __shared__ uint32_t matched[MATCHED_WORDS];
     constexpr bool dedup = DEDUP;                // every item of the DEDUP launch takes more than one fill, none of the other's
     uint2 *tab = reinterpret_cast<uint2 *>(tab64);   // chained view: .x = key, .y = payload
+    uint32_t *const slot_bits = SlotBits<KEEPB, SLOTS / 32>::get();   // KEEPB: one bit per table slot a probe of this fill has hit
 
     const int tid = threadIdx.x;
     const int wave = tid >> 6;
@@ -229,6 +261,7 @@ __device__ __forceinline__ void join_body(JoinArgs a)
     auto for_each_probe_vector = [&](u64 gb, u64 ge, u64 row0, auto probe4) {
         // left outer join: the tail pass (see below) is an instance of its own, the probes' instances carry no tail path
         constexpr bool TAIL = __is_same(decltype(probe4), hj_tail_pass);
+        constexpr bool MARK = __is_same(decltype(probe4), hj_mark_pass);
         for (u64 g0 = (gb & ~3ull) + (u64)tid * 4; g0 < ge; g0 += (u64)BLOCK * 4 * BATCH) {
             uint4 kk[BATCH], vv[BATCH];
 #pragma unroll
@@ -272,7 +305,31 @@ __device__ __forceinline__ void join_body(JoinArgs a)
                     report4(key, val, rep, 0u);
                     continue;
                 }
-                if constexpr (MODE == HJ_MODE_LEFT_OUTER) {
+                if constexpr (MARK) {
+                    // the first slot of the key's walk that holds it: what mark_build_rows looks at (both slots of a cuckoo table)
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        if (g + j < gb || g + j >= ge) continue;
+                        if (!cuckoo_failed) {
+                            const uint32_t a1 = (key[j] * tf0) >> SHIFT;
+                            const uint32_t a2 = (a1 + (((key[j] * tf1) >> SHIFT) | 1u)) & MASK;
+                            const uint32_t k1 = (uint32_t)tab64[a1], k2 = (uint32_t)tab64[a2];
+                            const uint32_t at = k1 == key[j] ? a1 : a2;
+                            if (k1 == key[j] || k2 == key[j]) atomicOr(&slot_bits[at >> 5], 1u << (at & 31));
+                        } else {
+                            uint32_t slot = (key[j] * tf0) >> SHIFT;
+                            const uint32_t step = ((key[j] * tf1) >> SHIFT) | 1u;
+                            for (uint32_t n = 0; n < SLOTS; ++n) {
+                                const uint32_t tk = tab[slot].x;
+                                if (tk == key[j]) { atomicOr(&slot_bits[slot >> 5], 1u << (slot & 31)); break; }
+                                if (tk == empty) break;
+                                slot = (slot + step) & MASK;
+                            }
+                        }
+                    }
+                    continue;
+                }
+                if constexpr (LEFTISH) {
                     // inr: the rows of the slice still open (DEDUP: under UNIQUE, and in the tail pass, not yet matched by a fill);
                     // valid: those that may match (a probe key equal to the broadcast sentinel matches nothing: a NULL row)
                     bool inr[4], valid[4];
@@ -363,7 +420,18 @@ __device__ __forceinline__ void join_body(JoinArgs a)
             for (int j = 0; j < 4; ++j) hits |= (valid[j] && ((uint32_t)t1[j] == key[j] || (uint32_t)t2[j] == key[j])) ? 1u << j : 0u;
             return hits;
         }
-        if constexpr (MODE == HJ_MODE_LEFT_OUTER) {
+        if constexpr (KEEPB) {
+            // one marked slot per matched key is enough: the walk over the build rows below looks at both slots of a key
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const uint32_t a1 = (key[j] * tf0) >> SHIFT;
+                const uint32_t a2 = (a1 + (((key[j] * tf1) >> SHIFT) | 1u)) & MASK;
+                const bool h1 = valid[j] && ((uint32_t)t1[j] == key[j]), h2 = valid[j] && ((uint32_t)t2[j] == key[j]);
+                const uint32_t at = h1 ? a1 : a2;
+                if (h1 || h2) atomicOr(&slot_bits[at >> 5], 1u << (at & 31));             // ds_or_b32
+            }
+        }
+        if constexpr (LEFTISH) {
             // the inner join's matches; a single-fill item also the NULL row of every open tuple without one (a multi-fill item: the tail pass)
             u64 sk_ = 0, so_ = 0, si_ = 0;
             uint32_t n = 0;
@@ -478,7 +546,7 @@ __device__ __forceinline__ void join_body(JoinArgs a)
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const bool hit = live[j] && (t[j].x == key[j]);
-                if constexpr (MODE == HJ_MODE_INNER || MODE == HJ_MODE_LEFT_OUTER) {
+                if constexpr (MODE == HJ_MODE_INNER || LEFTISH || KEEPB) {
                     acc_n += hit ? 1u : 0u;
                     acc_k += hit ? key[j] : 0u;
                     acc_o += hit ? val[j] : 0u;
@@ -486,6 +554,7 @@ __device__ __forceinline__ void join_body(JoinArgs a)
                     if (a.ok) { if (hit) em.emit(key[j], val[j], t[j].y); }
                 }
                 hits |= hit ? 1u << j : 0u;
+                if constexpr (KEEPB) { if (hit) atomicOr(&slot_bits[slot[j] >> 5], 1u << (slot[j] & 31)); }   // every copy: the full walk
                 live[j] = live[j] && (t[j].x != empty) && !(UNIQUE && hit);
                 slot[j] = (slot[j] + step[j]) & MASK;
             }
@@ -494,7 +563,7 @@ __device__ __forceinline__ void join_body(JoinArgs a)
             for (int j = 0; j < 4; ++j) if (live[j]) t[j] = tab[slot[j]];
         }
         // left outer join, single-fill item: the NULL rows of the open tuples without a match
-        if constexpr (MODE == HJ_MODE_LEFT_OUTER && !DEDUP) report4(key, val, lo_open & ~hits, HJGPU_NULL_VAL);
+        if constexpr (LEFTISH && !DEDUP) report4(key, val, lo_open & ~hits, HJGPU_NULL_VAL);
         return hits;
     };
 
@@ -515,6 +584,50 @@ __device__ __forceinline__ void join_body(JoinArgs a)
             if (se <= sb) continue;
             for_each_probe_vector(a.s_align + sb, a.s_align + se, row0, probe4);
             row0 += se - sb;
+        }
+    };
+
+    // KEEPB, after the probes of a table fill: rows [fill_beg, fill_end) of partition q once more - a row whose key sits in a marked slot
+    // gets its bit in a.build_bits.  The lanes of a wave hold consecutive rows of one piece, so a ballot gives whole words: the lane on a
+    // word boundary (and lane 0) ORs the word in, non-zero words only.
+    auto mark_build_rows = [&](u64 fill_beg, u64 fill_end, bool chained) {
+        u64 seen = 0;
+        for (uint32_t c = 0; c < C; ++c) {
+            const u64 b = a.roff[(u64)c * P + q], e = a.rend[(u64)c * P + q];
+            const u64 len = e - b;
+            const u64 lo = max(seen, fill_beg), hi = min(seen + len, fill_end);
+            for (u64 base = lo; base < hi; base += BLOCK) {
+                const u64 i = base + tid;
+                const u64 at = b + (i - seen);                // row of the partitioned build array
+                bool hit = false;
+                if (i < hi) {
+                    const uint32_t k = PACKED ? (uint32_t)r64[at] : a.rk[at];
+                    if (!chained) {
+                        const uint32_t a1 = (k * tf0) >> SHIFT;
+                        const uint32_t a2 = (a1 + (((k * tf1) >> SHIFT) | 1u)) & MASK;
+                        const u64 t1 = tab64[a1], t2 = tab64[a2];
+                        hit = ((uint32_t)t1 == k && ((slot_bits[a1 >> 5] >> (a1 & 31)) & 1u)) ||
+                              ((uint32_t)t2 == k && ((slot_bits[a2 >> 5] >> (a2 & 31)) & 1u));
+                    } else {
+                        // the key is in the table (this fill inserted it); a probe that carried it marked every copy
+                        uint32_t slot = (k * tf0) >> SHIFT;
+                        const uint32_t step = ((k * tf1) >> SHIFT) | 1u;
+                        for (uint32_t n = 0; n < SLOTS; ++n) {
+                            const uint32_t tk = tab[slot].x;
+                            if (tk == k) { hit = (slot_bits[slot >> 5] >> (slot & 31)) & 1u; break; }
+                            if (tk == empty) break;
+                            slot = (slot + step) & MASK;
+                        }
+                    }
+                }
+                const u64 m = __ballot(hit);
+                const uint32_t lane = hj_lane(), sh = (uint32_t)at & 31u;
+                if (m && (sh == 0 || lane == 0)) {
+                    const uint32_t w = (uint32_t)((m >> lane) << sh);      // rows at ... at + 31 - sh = lanes lane ... lane + 31 - sh
+                    if (w) atomicOr(&a.build_bits[at >> 5], w);            // global_atomic_or, no return
+                }
+            }
+            seen += len;
         }
     };
 
@@ -596,13 +709,14 @@ __device__ __forceinline__ void join_body(JoinArgs a)
                 par ^= 1;
                 continue;
             }
-            if (DEDUP) for (uint32_t i = tid; i < MATCHED_WORDS; i += BLOCK) matched[i] = 0;    // published by the clear barrier
+            if (DEDUP && !MARKING) for (uint32_t i = tid; i < MATCHED_WORDS; i += BLOCK) matched[i] = 0;    // published by the clear barrier
         }
 
         for (u64 fill_beg = rows_beg; fill_beg < rows_end; fill_beg += CAP) {
             const u64 fill_end = min(rows_end, fill_beg + CAP);
             // ---- clear + cuckoo build --------------------------------------------
             for (uint32_t i = tid; i < SLOTS; i += BLOCK) tab64[i] = EMPTY64;
+            if constexpr (KEEPB) for (uint32_t i = tid; i < SLOTS / 32; i += BLOCK) slot_bits[i] = 0;
             if (tid == 0) cuckoo_failed = a.force_chained;
             __syncthreads();
             auto cuckoo_insert = [&](uint32_t k, uint32_t v) {
@@ -641,7 +755,8 @@ __device__ __forceinline__ void join_body(JoinArgs a)
                 }
             }
             if (!cuckoo_failed) {
-                probe_item(slice, nslices, probe4_cuckoo);
+                if constexpr (MARKING) probe_item(slice, nslices, hj_mark_pass{});
+                else probe_item(slice, nslices, probe4_cuckoo);
             } else {
                 // ---- fallback: rebuild as double-hashing chains, multi-match probe -----
                 __syncthreads();
@@ -657,7 +772,12 @@ __device__ __forceinline__ void join_body(JoinArgs a)
                     }
                 });
                 __syncthreads();
-                probe_item(slice, nslices, probe4_chained);
+                if constexpr (MARKING) probe_item(slice, nslices, hj_mark_pass{});
+                else probe_item(slice, nslices, probe4_chained);
+            }
+            if constexpr (KEEPB) {
+                __syncthreads();   // every probe of this fill has left its marks
+                mark_build_rows(fill_beg, fill_end, cuckoo_failed != 0);
             }
             __syncthreads();   // table is reused by the next fill / work item
         }
@@ -671,7 +791,7 @@ __device__ __forceinline__ void join_body(JoinArgs a)
                 if (DEDUP) __syncthreads();          // every lane has read `matched` before the next item clears it
             }
         }
-        if constexpr (MODE == HJ_MODE_LEFT_OUTER) {
+        if constexpr (LEFTISH) {
             // the anti-join's tail pass: NULL rows for all probe rows of an item without build rows / the unmarked rows of a multi-fill item
             if (DEDUP || rows_beg >= rows_end) {
                 probe_item(slice, nslices, hj_tail_pass{});
@@ -720,6 +840,84 @@ template <int BLOCK, int LOG2SLOTS, int BATCH, bool PACKED, bool UNIQUE, bool DE
 __global__ __launch_bounds__(BLOCK, hj_join_waves_per_simd(BLOCK, LOG2SLOTS)) void outer_probe_kernel(JoinArgs a)
 {
     join_body<BLOCK, LOG2SLOTS, BATCH, PACKED, UNIQUE, DEDUP, true, HJ_MODE_LEFT_OUTER>(a);
+}
+
+// Right outer joins (HJGPU_FLAG_RIGHT_OUTER): the inner join's single launch (fill groups as planned for it), marking the build rows it hits;
+// full outer joins (HJGPU_FLAG_FULL_OUTER): the left outer join's two launches - the first marking likewise - and mark_probe_kernel.  Kernels of their own names; packed
+// inputs only (the broadcast join, the one user of column inputs, is bypassed in these modes); rows always non-temporal; no build-row prefetch.
+template <int BLOCK, int LOG2SLOTS, int BATCH, bool PACKED>
+__global__ __launch_bounds__(BLOCK, hj_join_waves_per_simd(BLOCK, LOG2SLOTS)) void right_probe_kernel(JoinArgs a)
+{
+    join_body<BLOCK, LOG2SLOTS, BATCH, PACKED, false, false, true, HJ_MODE_RIGHT_OUTER>(a);
+}
+
+template <int BLOCK, int LOG2SLOTS, int BATCH, bool PACKED>
+__global__ __launch_bounds__(BLOCK, hj_join_waves_per_simd(BLOCK, LOG2SLOTS)) void full_probe_kernel(JoinArgs a)
+{
+    join_body<BLOCK, LOG2SLOTS, BATCH, PACKED, false, false, true, HJ_MODE_FULL_OUTER>(a);
+}
+
+// the marks of a full outer join's multi-fill items (their rows: outer_probe_kernel<.., DEDUP>); aggregate-only by construction
+template <int BLOCK, int LOG2SLOTS, int BATCH, bool PACKED>
+__global__ __launch_bounds__(BLOCK, hj_join_waves_per_simd(BLOCK, LOG2SLOTS)) void mark_probe_kernel(JoinArgs a)
+{
+    join_body<BLOCK, LOG2SLOTS, BATCH, PACKED, false, true, true, HJ_MODE_MARK>(a);
+}
+
+// The tail of a right / full outer join: the rows of the partitioned (packed) build array whose bit in a.build_bits is clear leave as
+// (key, HJGPU_NULL_VAL, inner_val).  It runs behind the join's launches with the join's grid and block: wave w of workgroup b resumes the
+// output block that wave left open (final_offsets), so close_gaps sees one launch's worth of worker slots.  The array is walked piece by
+// piece (roff / rend of every partition and chunk: line-aligned partitions have gaps), a piece cut into `split` equal parts so that few
+// large pieces still occupy the grid; four tuples (2 x 16 bytes) and their four bits per lane and step.
+template <int BLOCK>
+__global__ __launch_bounds__(BLOCK) void build_unmatched_kernel(JoinArgs a, uint32_t split)
+{
+    constexpr int NW = BLOCK / 64;
+    __shared__ u64 red[3][NW];
+    __shared__ u64 wave_cursor[NW];
+    const int tid = threadIdx.x, wave = tid >> 6;
+    EmitterT<true, 3> em;
+    em.init(a.ok, a.oov, a.oiv, a.block_size, a.block_limit, a.block_counter, a.overflow, &wave_cursor[wave]);
+    if (hj_lane() == 0) wave_cursor[wave] = a.ok ? a.final_offsets[(u64)blockIdx.x * NW + wave] : HJ_NO_CURSOR;
+    const uint4 *__restrict__ r4 = reinterpret_cast<const uint4 *>(a.rk);
+    const uint32_t *__restrict__ bits = a.build_bits;
+    const u64 units = (u64)a.P * a.chunks * split;
+    u64 acc_n = 0, acc_k = 0, acc_i = 0;
+    for (u64 u = blockIdx.x; u < units; u += gridDim.x) {
+        const u64 piece = u / split, part = u - piece * split;
+        const u64 b = a.roff[piece], len = a.rend[piece] - b;
+        const u64 sb = b + len * part / split, se = b + len * (part + 1) / split;
+        for (u64 g = (sb & ~3ull) + (u64)tid * 4; g < se; g += (u64)BLOCK * 4) {
+            const uint4 x = r4[g >> 1], y = r4[(g >> 1) + 1];                 // tuples g ... g + 3 (the array ends in 4 spare tuples)
+            const uint32_t seen = bits[g >> 5] >> ((uint32_t)g & 31u);          // g is a multiple of 4: the four bits lie in one word
+            const uint32_t key[4] = {x.x, x.z, y.x, y.z}, val[4] = {x.y, x.w, y.y, y.w};
+            uint32_t rep = 0;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const bool r = g + j >= sb && g + j < se && !((seen >> j) & 1u);
+                rep |= r ? 1u << j : 0u;
+                acc_n += r ? 1u : 0u; acc_k += r ? key[j] : 0u; acc_i += r ? val[j] : 0u;
+            }
+            if (a.ok) {
+                const uint32_t none[4] = {HJGPU_NULL_VAL, HJGPU_NULL_VAL, HJGPU_NULL_VAL, HJGPU_NULL_VAL};
+                if (rep == 15u && a.block_size >= 512) em.emit4(key, none, val);       // (emit4: blocks of 512 rows and more)
+                else if (rep) {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) if ((rep >> j) & 1u) em.emit(key[j], HJGPU_NULL_VAL, val[j]);
+                }
+            }
+        }
+    }
+    if (a.ok && hj_lane() == 0) hj_store(&a.final_offsets[(u64)blockIdx.x * NW + wave], wave_cursor[wave]);
+    acc_n = wave_reduce_sum(acc_n); acc_k = wave_reduce_sum(acc_k); acc_i = wave_reduce_sum(acc_i);
+    if (hj_lane() == 0) { red[0][wave] = acc_n; red[1][wave] = acc_k; red[2][wave] = acc_i; }
+    __syncthreads();
+    if (tid < 3) {
+        u64 s = 0;
+        for (int i = 0; i < NW; ++i) s += red[tid][i];
+        u64 *dst = reinterpret_cast<u64 *>(a.result) + (tid == 2 ? 3 : tid);       // count, sum_keys, sum_inner_vals
+        if (s) atomicAdd(dst, s);
+    }
 }
 
 #include <stdlib.h>
@@ -852,6 +1050,41 @@ bool hj_join_config_built(const JoinConfig &c, bool unique)
         return hipGetLastError() == hipSuccess ? HJGPU_OK : HJGPU_EHIP;                           \
     }
 
+// a right outer join: one launch, as the inner join (packed inputs only); a full outer join: the left outer join's two launches - the
+// multi-fill one as it is - and the marks of the multi-fill items
+#define RIGHT_CASE(B, L)                                                                          \
+    if (c.block == B && c.log2slots == L) {                                                       \
+        if (!b.packed) return HJGPU_EINVAL;                                                       \
+        hipLaunchKernelGGL((right_probe_kernel<B, L, 2, true>), dim3(join_grid(cus, c)), dim3(B), 0, stream, b);    \
+        return hipGetLastError() == hipSuccess ? HJGPU_OK : HJGPU_EHIP;                           \
+    }
+#define FULL_CASE(B, L)                                                                           \
+    if (c.block == B && c.log2slots == L) {                                                       \
+        if (!b.packed) return HJGPU_EINVAL;                                                       \
+        if (!b.work_counter3) return HJGPU_EINVAL;                                                \
+        JoinArgs d = b, e = b;                                                                    \
+        d.work_counter = b.work_counter2;                                                         \
+        e.work_counter = b.work_counter3; e.ok = nullptr;                                         \
+        hipLaunchKernelGGL((full_probe_kernel<B, L, 2, true>), dim3(join_grid(cus, c)), dim3(B), 0, stream, b);                \
+        hipLaunchKernelGGL((outer_probe_kernel<B, L, 1, true, false, true>), dim3(join_grid(cus, c)), dim3(B), 0, stream, d);  \
+        hipLaunchKernelGGL((mark_probe_kernel<B, L, 1, true>), dim3(join_grid(cus, c)), dim3(B), 0, stream, e);                \
+        return hipGetLastError() == hipSuccess ? HJGPU_OK : HJGPU_EHIP;                           \
+    }
+
+int hj_launch_build_unmatched(const JoinArgs &a, const HjTuning &t, int cus, hipStream_t stream)
+{
+    if (!a.packed || !a.build_bits || a.P < 1 || a.chunks == 0 || (a.ok && !a.final_offsets)) return HJGPU_EINVAL;
+    const JoinConfig &c = hj_join_config_of(t, a.big_tables != 0);
+    const int grid = join_grid(cus, c);
+    const u64 pieces = (u64)a.P * a.chunks;
+    u64 split = (u64)grid * 4 / pieces;
+    split = split < 1 ? 1 : split > 4096 ? 4096 : split;
+    if (c.block == 512) hipLaunchKernelGGL((build_unmatched_kernel<512>), dim3(grid), dim3(512), 0, stream, a, (uint32_t)split);
+    else if (c.block == 1024) hipLaunchKernelGGL((build_unmatched_kernel<1024>), dim3(grid), dim3(1024), 0, stream, a, (uint32_t)split);
+    else return HJGPU_EINVAL;
+    return hipGetLastError() == hipSuccess ? HJGPU_OK : HJGPU_EHIP;
+}
+
 int hj_launch_join(const JoinArgs &a, const HjTuning &t, int cus, hipStream_t stream)
 {
     if ((a.P < 2 && !a.broadcast) || a.P < 1 || a.chunks == 0) return HJGPU_EINVAL;
@@ -860,6 +1093,12 @@ int hj_launch_join(const JoinArgs &a, const HjTuning &t, int cus, hipStream_t st
     b.force_chained = t.force_chained ? 1u : 0u;       // tests: exercise the fallback table everywhere
     b.unique = (a.unique || t.unique) ? 1u : 0u;
     if ((b.unique || b.mode) && !b.work_counter2) return HJGPU_EINVAL;
+    if (hj_mode_keeps_build(b.mode)) {
+        if (b.unique || !b.build_bits) return HJGPU_EINVAL;
+        if (b.mode == HJ_MODE_RIGHT_OUTER) { RIGHT_CASE(512, 13) RIGHT_CASE(1024, 14) }
+        else { FULL_CASE(512, 13) FULL_CASE(1024, 14) }
+        return HJGPU_EINVAL;                           // a geometry without these instances (hj_join_config_built)
+    }
     if (b.mode == HJ_MODE_LEFT_OUTER) {
         OUTER_CASE(512, 13, false)
         OUTER_CASE(512, 13, true)

@@ -186,7 +186,11 @@ __global__ __launch_bounds__(NPJ_PROBE_BLOCK) void npj_probe_kernel(NpjProbeArgs
 template <bool GROUPED, bool UNIQUE, int MODE>
 __device__ __forceinline__ void npj_mode_body(NpjProbeArgs a)
 {
-    static_assert(MODE != HJ_MODE_INNER && (UNIQUE || MODE == HJ_MODE_LEFT_OUTER), "semi- and anti-joins walk to the first match");
+    // LEFTISH: the modes that report like the left outer join; KEEPB (right / full outer joins, never UNIQUE: the walk visits every copy of
+    // a key): every bucket a probe matches gets its bit in a.bucket_bits - one bucket per build tuple, so bucket-level marks are exact
+    constexpr bool LEFTISH = MODE == HJ_MODE_LEFT_OUTER || MODE == HJ_MODE_FULL_OUTER;
+    constexpr bool KEEPB = MODE == HJ_MODE_RIGHT_OUTER || MODE == HJ_MODE_FULL_OUTER;
+    static_assert(MODE != HJ_MODE_INNER && (UNIQUE || LEFTISH || KEEPB) && !(UNIQUE && KEEPB), "semi- and anti-joins walk to the first match");
     constexpr int NW = NPJ_PROBE_BLOCK / 64;
     __shared__ u64 red[4][NW];
     __shared__ u64 wave_cursor[NW];
@@ -241,10 +245,11 @@ __device__ __forceinline__ void npj_mode_body(NpjProbeArgs a)
                             const bool inb = open && ((uint32_t)b >= first);
                             if (inb && bk[b] == 0u) open = false;
                             else if (inb && bk[b] == key[j]) {
-                                if constexpr (MODE == HJ_MODE_INNER || MODE == HJ_MODE_LEFT_OUTER) {
+                                if constexpr (MODE == HJ_MODE_INNER || LEFTISH || KEEPB) {
                                     acc_n += 1; acc_k += key[j]; acc_o += val[j]; acc_i += bv[b];
                                     em.emit(key[j], val[j], bv[b]);
                                 }
+                                if constexpr (KEEPB) { const u64 at = (h[j] & ~3ull) + b; atomicOr(&a.bucket_bits[at >> 5], 1u << ((uint32_t)at & 31u)); }
                                 if constexpr (MODE != HJ_MODE_INNER) hit[j] = true;
                                 if (UNIQUE) open = false;
                             }
@@ -267,10 +272,11 @@ __device__ __forceinline__ void npj_mode_body(NpjProbeArgs a)
                         } else {
                             if ((uint32_t)t[j] == key[j]) {
                                 const uint32_t iv = (uint32_t)(t[j] >> 32);
-                                if constexpr (MODE == HJ_MODE_INNER || MODE == HJ_MODE_LEFT_OUTER) {
+                                if constexpr (MODE == HJ_MODE_INNER || LEFTISH || KEEPB) {
                                     acc_n += 1; acc_k += key[j]; acc_o += val[j]; acc_i += iv;
                                     em.emit(key[j], val[j], iv);
                                 }
+                                if constexpr (KEEPB) atomicOr(&a.bucket_bits[h[j] >> 5], 1u << ((uint32_t)h[j] & 31u));
                                 if constexpr (MODE != HJ_MODE_INNER) hit[j] = true;
                                 if (UNIQUE) { act[j] = false; continue; }
                             }
@@ -281,7 +287,7 @@ __device__ __forceinline__ void npj_mode_body(NpjProbeArgs a)
                 }
             }
         }
-        if constexpr (MODE == HJ_MODE_LEFT_OUTER) {
+        if constexpr (LEFTISH) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 if (in[j] && !hit[j]) {                 // (a probe key 0 stops at the first empty bucket: no match, a NULL row)
@@ -289,7 +295,7 @@ __device__ __forceinline__ void npj_mode_body(NpjProbeArgs a)
                     em.emit(key[j], val[j], HJGPU_NULL_VAL);
                 }
             }
-        } else if constexpr (MODE != HJ_MODE_INNER) {
+        } else if constexpr (MODE == HJ_MODE_SEMI || MODE == HJ_MODE_ANTI) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 if (in[j] && hit[j] == (MODE == HJ_MODE_SEMI)) {
@@ -461,7 +467,9 @@ __global__ __launch_bounds__(NPJ_PROBE_BLOCK) void npj_probe_line_kernel(NpjProb
 template <bool MATERIALIZE, bool UNIQUE, int MODE>
 __device__ __forceinline__ void npj_mode_line_body(NpjProbeArgs a)
 {
-    static_assert(MODE != HJ_MODE_INNER && (UNIQUE || MODE == HJ_MODE_LEFT_OUTER), "semi- and anti-joins walk to the first match");
+    constexpr bool LEFTISH = MODE == HJ_MODE_LEFT_OUTER || MODE == HJ_MODE_FULL_OUTER;     // as in npj_mode_body
+    constexpr bool KEEPB = MODE == HJ_MODE_RIGHT_OUTER || MODE == HJ_MODE_FULL_OUTER;
+    static_assert(MODE != HJ_MODE_INNER && (UNIQUE || LEFTISH || KEEPB) && !(UNIQUE && KEEPB), "semi- and anti-joins walk to the first match");
     constexpr int NW = NPJ_PROBE_BLOCK / 64;
     constexpr int B = 4;                                   // lines in flight per quad
     __shared__ u64 red[4][NW];
@@ -521,7 +529,7 @@ __device__ __forceinline__ void npj_mode_line_body(NpjProbeArgs a)
             }
 #pragma unroll
             for (int i = 0; i < B; ++i) {
-                if constexpr (MODE == HJ_MODE_LEFT_OUTER) got = false;
+                if constexpr (LEFTISH) got = false;
                 while (act[i]) {                                        // uniform inside the quad
                     // first empty bucket of the line, over the quad
                     uint32_t fe = q[i].x == 0u ? 2 * sub : (q[i].z == 0u ? 2 * sub + 1 : 8u);
@@ -540,7 +548,7 @@ __device__ __forceinline__ void npj_mode_line_body(NpjProbeArgs a)
                         m0 = m0 && mine == fm && fm == 2 * sub;
                         m1 = m1 && mine == fm && fm == 2 * sub + 1;
                     }
-                    if constexpr (MODE == HJ_MODE_INNER || MODE == HJ_MODE_LEFT_OUTER) {
+                    if constexpr (MODE == HJ_MODE_INNER || LEFTISH || KEEPB) {
                         const uint32_t m = (m0 ? 1u : 0u) + (m1 ? 1u : 0u);
                         acc_n += m; acc_k += (u64)key[i] * m; acc_o += (u64)val[i] * m;
                         acc_i += (m0 ? q[i].y : 0u); acc_i += (m1 ? q[i].w : 0u);
@@ -548,13 +556,18 @@ __device__ __forceinline__ void npj_mode_line_body(NpjProbeArgs a)
                             if (m0) em.emit(key[i], val[i], q[i].y);
                             if (m1) em.emit(key[i], val[i], q[i].w);
                         }
+                        if constexpr (KEEPB) {
+                            // my two buckets of the line: 8 * line + 2 * sub and the next one - an even index, both bits in one word
+                            const u64 at = 8 * ln[i] + 2 * sub;
+                            if (m0 || m1) atomicOr(&a.bucket_bits[at >> 5], ((m0 ? 1u : 0u) | (m1 ? 2u : 0u)) << ((uint32_t)at & 31u));
+                        }
                     } else if (fe < 8u || found) {
                         if (sub == 0 && found == (MODE == HJ_MODE_SEMI)) {
                             acc_n += 1; acc_k += key[i]; acc_o += val[i];
                             if (MATERIALIZE) em.emit(key[i], val[i], 0u);
                         }
                     }
-                    if constexpr (MODE == HJ_MODE_LEFT_OUTER) {
+                    if constexpr (LEFTISH) {
                         if (UNIQUE) got = got || found;
                         else {
                             uint32_t any = (m0 || m1) ? 1u : 0u;                // a match anywhere in the quad's line
@@ -599,6 +612,86 @@ __global__ __launch_bounds__(NPJ_PROBE_BLOCK) void npj_outer_line_kernel(NpjProb
     npj_mode_line_body<MATERIALIZE, UNIQUE, HJ_MODE_LEFT_OUTER>(a);
 }
 
+// Right and full outer joins (HJGPU_FLAG_RIGHT_OUTER / _FULL_OUTER): the inner / left outer probes, marking every bucket they match
+// (NpjProbeArgs::bucket_bits).  Kernels of their own names; never UNIQUE.
+template <bool GROUPED>
+__global__ __launch_bounds__(NPJ_PROBE_BLOCK) void npj_right_kernel(NpjProbeArgs a)
+{
+    npj_mode_body<GROUPED, false, HJ_MODE_RIGHT_OUTER>(a);
+}
+
+template <bool GROUPED>
+__global__ __launch_bounds__(NPJ_PROBE_BLOCK) void npj_full_kernel(NpjProbeArgs a)
+{
+    npj_mode_body<GROUPED, false, HJ_MODE_FULL_OUTER>(a);
+}
+
+template <bool MATERIALIZE>
+__global__ __launch_bounds__(NPJ_PROBE_BLOCK) void npj_right_line_kernel(NpjProbeArgs a)
+{
+    npj_mode_line_body<MATERIALIZE, false, HJ_MODE_RIGHT_OUTER>(a);
+}
+
+template <bool MATERIALIZE>
+__global__ __launch_bounds__(NPJ_PROBE_BLOCK) void npj_full_line_kernel(NpjProbeArgs a)
+{
+    npj_mode_line_body<MATERIALIZE, false, HJ_MODE_FULL_OUTER>(a);
+}
+
+// The tail of a right / full outer NPJ join, behind the probe with the probe's grid: scans the table (four buckets = 2 x 16 bytes and
+// their four bits per lane and step; buckets is a multiple of 8) and reports every tuple (key != 0) whose bucket's bit is clear as
+// (key, HJGPU_NULL_VAL, inner_val).  `resume`: the waves go on in the output blocks the probe's waves left open.
+__global__ __launch_bounds__(NPJ_PROBE_BLOCK) void npj_unmatched_kernel(NpjProbeArgs a, uint32_t resume)
+{
+    constexpr int NW = NPJ_PROBE_BLOCK / 64;
+    __shared__ u64 red[3][NW];
+    __shared__ u64 wave_cursor[NW];
+    const int wave = threadIdx.x >> 6;
+    Emitter em;
+    em.init(a.ok, a.oov, a.oiv, a.block_size, a.block_limit, a.block_counter, a.overflow, &wave_cursor[wave]);
+    if (hj_lane() == 0) wave_cursor[wave] = (a.ok && resume) ? a.final_offsets[(u64)blockIdx.x * NW + wave] : HJ_NO_CURSOR;
+    const uint4 *__restrict__ t4 = reinterpret_cast<const uint4 *>(a.table);
+    const uint32_t *__restrict__ bits = a.bucket_bits;
+    const u64 nvec = a.buckets >> 2, stride = (u64)gridDim.x * NPJ_PROBE_BLOCK;
+    u64 acc_n = 0, acc_k = 0, acc_i = 0;
+    for (u64 v = (u64)blockIdx.x * NPJ_PROBE_BLOCK + threadIdx.x; v < nvec; v += stride) {
+        const uint4 x = t4[2 * v], y = t4[2 * v + 1];
+        const uint32_t seen = bits[v >> 3] >> (((uint32_t)v & 7u) * 4);      // buckets 4v ... 4v + 3
+        const uint32_t key[4] = {x.x, x.z, y.x, y.z}, val[4] = {x.y, x.w, y.y, y.w};
+        uint32_t rep = 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const bool r = key[j] != 0u && !((seen >> j) & 1u);
+            rep |= r ? 1u << j : 0u;
+            acc_n += r ? 1u : 0u; acc_k += r ? key[j] : 0u; acc_i += r ? val[j] : 0u;
+        }
+        if (a.ok) {
+            const uint32_t none[4] = {HJGPU_NULL_VAL, HJGPU_NULL_VAL, HJGPU_NULL_VAL, HJGPU_NULL_VAL};
+            if (rep == 15u && a.block_size >= 512) em.emit4(key, none, val);       // (emit4: blocks of 512 rows and more)
+            else if (rep) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) if ((rep >> j) & 1u) em.emit(key[j], HJGPU_NULL_VAL, val[j]);
+            }
+        }
+    }
+    if (a.ok && hj_lane() == 0) hj_store(&a.final_offsets[(u64)blockIdx.x * NW + wave], wave_cursor[wave]);
+    acc_n = wave_reduce_sum(acc_n); acc_k = wave_reduce_sum(acc_k); acc_i = wave_reduce_sum(acc_i);
+    if (hj_lane() == 0) { red[0][wave] = acc_n; red[1][wave] = acc_k; red[2][wave] = acc_i; }
+    __syncthreads();
+    if (threadIdx.x < 3) {
+        u64 s = 0;
+        for (int i = 0; i < NW; ++i) s += red[threadIdx.x][i];
+        if (s) atomicAdd(reinterpret_cast<u64 *>(a.result) + (threadIdx.x == 2 ? 3 : threadIdx.x), s);     // count, sum_keys, sum_inner_vals
+    }
+}
+
+int hj_launch_npj_unmatched(const NpjProbeArgs &a, int grid, bool resume, hipStream_t stream)
+{
+    if (!a.bucket_bits || a.buckets % 8 != 0 || ((uintptr_t)a.table & 15) || grid < 1 || (a.ok && !a.final_offsets)) return HJGPU_EINVAL;
+    hipLaunchKernelGGL(npj_unmatched_kernel, dim3(grid), dim3(NPJ_PROBE_BLOCK), 0, stream, a, resume ? 1u : 0u);
+    return hipGetLastError() == hipSuccess ? HJGPU_OK : HJGPU_EHIP;
+}
+
 int hj_npj_probe_grid(int cus, size_t n)
 {
     u64 blocks = ((n + 3) / 4 + NPJ_PROBE_BLOCK - 1) / NPJ_PROBE_BLOCK;
@@ -611,8 +704,14 @@ int hj_launch_npj_probe(const NpjProbeArgs &a, int cus, hipStream_t stream, int 
 {
     const int grid = hj_npj_probe_grid(cus, a.n);
     if (grid_out) *grid_out = grid;
+    if (hj_mode_keeps_build(a.mode) && (a.unique || !a.bucket_bits)) return HJGPU_EINVAL;
     if (a.line_hash) {
         if (a.buckets % 8 != 0 || ((uintptr_t)a.table & 63)) return HJGPU_EINVAL;
+        if (a.mode == HJ_MODE_RIGHT_OUTER && a.ok) hipLaunchKernelGGL((npj_right_line_kernel<true>), dim3(grid), dim3(NPJ_PROBE_BLOCK), 0, stream, a);
+        else if (a.mode == HJ_MODE_RIGHT_OUTER) hipLaunchKernelGGL((npj_right_line_kernel<false>), dim3(grid), dim3(NPJ_PROBE_BLOCK), 0, stream, a);
+        else if (a.mode == HJ_MODE_FULL_OUTER && a.ok) hipLaunchKernelGGL((npj_full_line_kernel<true>), dim3(grid), dim3(NPJ_PROBE_BLOCK), 0, stream, a);
+        else if (a.mode == HJ_MODE_FULL_OUTER) hipLaunchKernelGGL((npj_full_line_kernel<false>), dim3(grid), dim3(NPJ_PROBE_BLOCK), 0, stream, a);
+        else
         if (a.mode == HJ_MODE_LEFT_OUTER && a.ok && a.unique) hipLaunchKernelGGL((npj_outer_line_kernel<true, true>), dim3(grid), dim3(NPJ_PROBE_BLOCK), 0, stream, a);
         else if (a.mode == HJ_MODE_LEFT_OUTER && a.ok) hipLaunchKernelGGL((npj_outer_line_kernel<true, false>), dim3(grid), dim3(NPJ_PROBE_BLOCK), 0, stream, a);
         else if (a.mode == HJ_MODE_LEFT_OUTER && a.unique) hipLaunchKernelGGL((npj_outer_line_kernel<false, true>), dim3(grid), dim3(NPJ_PROBE_BLOCK), 0, stream, a);
@@ -628,6 +727,11 @@ int hj_launch_npj_probe(const NpjProbeArgs &a, int cus, hipStream_t stream, int 
         return hipGetLastError() == hipSuccess ? HJGPU_OK : HJGPU_EHIP;
     }
     const bool grouped = (a.buckets % 4 == 0) && (((uintptr_t)a.table & 31) == 0);
+    if (a.mode == HJ_MODE_RIGHT_OUTER && grouped) hipLaunchKernelGGL((npj_right_kernel<true>), dim3(grid), dim3(NPJ_PROBE_BLOCK), 0, stream, a);
+    else if (a.mode == HJ_MODE_RIGHT_OUTER) hipLaunchKernelGGL((npj_right_kernel<false>), dim3(grid), dim3(NPJ_PROBE_BLOCK), 0, stream, a);
+    else if (a.mode == HJ_MODE_FULL_OUTER && grouped) hipLaunchKernelGGL((npj_full_kernel<true>), dim3(grid), dim3(NPJ_PROBE_BLOCK), 0, stream, a);
+    else if (a.mode == HJ_MODE_FULL_OUTER) hipLaunchKernelGGL((npj_full_kernel<false>), dim3(grid), dim3(NPJ_PROBE_BLOCK), 0, stream, a);
+    else
     if (a.mode == HJ_MODE_LEFT_OUTER && grouped && a.unique) hipLaunchKernelGGL((npj_outer_kernel<true, true>), dim3(grid), dim3(NPJ_PROBE_BLOCK), 0, stream, a);
     else if (a.mode == HJ_MODE_LEFT_OUTER && grouped) hipLaunchKernelGGL((npj_outer_kernel<true, false>), dim3(grid), dim3(NPJ_PROBE_BLOCK), 0, stream, a);
     else if (a.mode == HJ_MODE_LEFT_OUTER && a.unique) hipLaunchKernelGGL((npj_outer_kernel<false, true>), dim3(grid), dim3(NPJ_PROBE_BLOCK), 0, stream, a);

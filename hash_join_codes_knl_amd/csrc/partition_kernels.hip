@@ -899,19 +899,20 @@ __global__ __launch_bounds__(256) void group_desc_kernel(const u64 *__restrict__
     // beyond what the workspace was planned for - or offsets that are no prefix of the relations' rows (a caller who overlaps joins of ONE
     // context on several streams races on its workspace: never an address outside the columns): skipped, the join flagged
     if (rn > cap_r || sn > cap_s || re < rb || se < sb || re > n_r || se > n_s) { atomicOr(skew, 1u); rn = 0; sn = 0; }
-    // nothing can match - but anti- and left outer joins report every probe row of a group without build rows (PlanArgs::anti gives
-    // them work items)
-    if ((rn == 0 && !anti) || sn == 0) { rn = 0; sn = 0; }
+    // nothing can match - but anti-, left and full outer joins (bit 0 of `anti`) report every probe row of a group without build rows
+    // (PlanArgs::anti gives them work items), and right and full outer joins (bit 1) every build row of a group without probe rows (the
+    // group's build side is partitioned for the tail kernel, its join has no work items)
+    if ((rn == 0 && !(anti & 1u)) || (sn == 0 && !((anti & 2u) && rn))) { rn = 0; sn = 0; }
     hj_store(&desc[4 * (u64)g + 0], rb + hj_group_shift(rb, g)); hj_store(&desc[4 * (u64)g + 1], rn);
     hj_store(&desc[4 * (u64)g + 2], sb + hj_group_shift(sb, g)); hj_store(&desc[4 * (u64)g + 3], sn);
 }
 
 int hj_launch_group_desc(const u64 *roff, const u64 *soff, uint32_t G, uint32_t bins, u64 cap_r, u64 cap_s, u64 n_r, u64 n_s, u64 *desc, uint32_t *skew,
-                         hipStream_t stream, bool anti)
+                         hipStream_t stream, bool anti, bool keep_build)
 {
     if (!G || !bins) return HJGPU_EINVAL;
     hipLaunchKernelGGL(group_desc_kernel, dim3((G + 255) / 256), dim3(256), 0, stream, roff, soff, G, bins, cap_r, cap_s, n_r, n_s, desc, skew,
-                       anti ? 1u : 0u);
+                       (anti ? 1u : 0u) | (keep_build ? 2u : 0u));
     return hipGetLastError() == hipSuccess ? HJGPU_OK : HJGPU_EHIP;
 }
 

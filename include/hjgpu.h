@@ -81,7 +81,24 @@ extern "C" {
                                      HJGPU_FLAG_SEMI; every other join entry point refuses it (HJGPU_EINVAL), as do
                                      LEFT_OUTER | SEMI and LEFT_OUTER | ANTI.  PHJ / CPRA: every key value is legal on both sides;
                                      NPJ: a build key 0 is still HJGPU_EZEROKEY, a probe key 0 matches nothing (a NULL row).   */
-#define HJGPU_NULL_VAL    0xFFFFFFFFu  /* the inner_val of a left outer join's row without a match                        */
+#define HJGPU_FLAG_RIGHT_OUTER 16u /* right outer join that keeps the BUILD side (S RIGHT JOIN R ON S.key = R.key, R the inner
+                                     relation): every inner-join row, exactly as without the flag, plus ONE row
+                                     (key, HJGPU_NULL_VAL, inner_val) for every build tuple whose key equals no probe key
+                                     (build-side duplicates one by one; every build tuple when outer == 0; nothing extra when
+                                     inner == 0).  count, sum_keys and sum_inner_vals are taken over all rows; sum_outer_vals
+                                     adds the matched rows' payloads only.  Rows have three columns: d_outer_vals and
+                                     d_inner_vals are both required; hjgpu_output_capacity(rows) holds for the true row count
+                                     (at most the inner join's rows + inner).  Same entry points as HJGPU_FLAG_SEMI; every
+                                     other join entry point refuses it (HJGPU_EINVAL).  Refused beside HJGPU_FLAG_SEMI, _ANTI and
+                                     HJGPU_FLAG_UNIQUE / option "unique" (a first-match walk would leave the other copies of a
+                                     duplicated build key neither in a row nor NULL).  Keys as for HJGPU_FLAG_LEFT_OUTER.      */
+#define HJGPU_FLAG_FULL_OUTER (HJGPU_FLAG_LEFT_OUTER | HJGPU_FLAG_RIGHT_OUTER)
+                                  /* full outer join: the inner join's rows, the left outer join's NULL rows
+                                     (key, outer_val, HJGPU_NULL_VAL) and the right outer join's (key, HJGPU_NULL_VAL, inner_val).
+                                     sum_outer_vals and sum_inner_vals each skip the rows whose value on that side is the NULL.
+                                     inner == 0: identical to LEFT_OUTER; outer == 0: identical to RIGHT_OUTER.  At most the
+                                     inner join's rows + inner + outer rows.  Refusals as for HJGPU_FLAG_RIGHT_OUTER.          */
+#define HJGPU_NULL_VAL    0xFFFFFFFFu  /* the value on the side without a match in an outer join's NULL row              */
 
 #define HJGPU_MAX_FANOUT  1024u   /* per partitioning pass                                   */
 #define HJGPU_MAX_PARTS   32768u  /* fanout1 * fanout2                                       */
