@@ -152,3 +152,28 @@ struct EmitterT {
     }
 };
 typedef EmitterT<true> Emitter;     // NPJ: always non-temporal rows
+
+// The end of every kernel that reports rows and aggregates, in two steps.  hj_leave_cursor, by the kernels that have materialised: the
+// wave's cursor goes to its worker slot of final_offsets (close_gaps' input, or where the next launch of the same grid resumes).
+template <int NW>
+__device__ __forceinline__ void hj_leave_cursor(u64 *final_offsets, const u64 (&wave_cursor)[NW])
+{
+    const int wave = threadIdx.x >> 6;
+    if (hj_lane() == 0) hj_store(&final_offsets[(u64)blockIdx.x * NW + wave], wave_cursor[wave]);
+}
+// hj_add_to_result: the lanes' sums - count, sum_keys, sum_outer_vals, sum_inner_vals - are reduced per wave, per workgroup through
+// `red`, and leave as one atomic per non-zero sum into the four words of hjgpu_result.
+template <int NW>
+__device__ __forceinline__ void hj_add_to_result(u64 (&red)[4][NW], void *result, u64 acc_n, u64 acc_k, u64 acc_o, u64 acc_i)
+{
+    const int wave = threadIdx.x >> 6;
+    acc_n = wave_reduce_sum(acc_n); acc_k = wave_reduce_sum(acc_k);
+    acc_o = wave_reduce_sum(acc_o); acc_i = wave_reduce_sum(acc_i);
+    if (hj_lane() == 0) { red[0][wave] = acc_n; red[1][wave] = acc_k; red[2][wave] = acc_o; red[3][wave] = acc_i; }
+    __syncthreads();
+    if (threadIdx.x < 4) {
+        u64 s = 0;
+        for (int i = 0; i < NW; ++i) s += red[threadIdx.x][i];
+        if (s) atomicAdd(reinterpret_cast<u64 *>(result) + threadIdx.x, s);
+    }
+}

@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 #include "../../include/hjgpu.h"
 
 typedef unsigned long long u64;
@@ -376,6 +377,14 @@ int hj_launch_join(const JoinArgs &a, const HjTuning &t, int cus, hipStream_t st
 int hj_launch_exscan(const u64 *in, u64 *out, uint32_t n, hipStream_t stream);
 int hj_launch_offsets_to_counts(const u64 *off, u64 *counts, uint32_t P, hipStream_t stream);
 
+// a run-time flag as a compile-time one: f(std::true_type) or f(std::false_type) - how the launchers pick a kernel instance
+template <class F>
+inline void hj_with_bool(bool b, F &&f)
+{
+    if (b) f(std::true_type{});
+    else f(std::false_type{});
+}
+
 // NPJ
 int hj_launch_npj_build(const uint32_t *keys, const uint32_t *vals, size_t n, u64 *table,
                         size_t buckets, uint32_t factor, uint32_t *zero_key_flag,
@@ -410,7 +419,7 @@ int hj_launch_close_gaps_ex(uint32_t *k, uint32_t *ov, uint32_t *iv, const u64 *
                             uint32_t nworkers, u64 block_size, const u64 *block_counter,
                             const uint32_t *overflow, void *moves, uint32_t *nmoves,
                             u64 *dense_count, int cus, hipStream_t stream);
-int hj_join_workers(const HjTuning &t, int cus, bool big_tables = false, bool unique = false);
+int hj_join_workers(const HjTuning &t, int cus, bool big_tables = false);
 // Metadata of a broadcast join, written on the device: one partition holding all of R ([0, inner)) and all of S
 // ([0, outer)), `nslices` probe slices x `groups` fill groups (item_part must be zeroed by the caller), and a
 // sentinel: a value whose low 14 bits no build key shares (inner <= 16383).

@@ -691,7 +691,7 @@ int phj_enqueue(hjgpu_ctx *ctx, const PhjPlan &pl,
     if ((pre != nullptr) != (pl.pre != 0)) return fail(ctx, HJGPU_EINVAL, "internal: plan and relations disagree about pre-partitioning");
     MetaLayout m = carve(ctx->meta.p, pl.C, pl.F1, pl.P, pl.ranges, pl.items_extra, pl.tiles2, pl.batch_cap, pl.tdesc_b_cap);
     DevState *st = reinterpret_cast<DevState *>(ctx->state.p);
-    const uint32_t workers = (uint32_t)hj_join_workers(ctx->tune, ctx->cus, pl.big_tables, pl.unique);
+    const uint32_t workers = (uint32_t)hj_join_workers(ctx->tune, ctx->cus, pl.big_tables);
     u64 bs = 0, bl = 0;
     CHK(setup_output(ctx, out, workers, &bs, &bl, pl.mode));
 
@@ -1409,7 +1409,7 @@ int hjgpu_output_capacity(hjgpu_ctx *ctx, int algorithm, size_t outer_tuples, si
     const size_t bs = block_size ? block_size : 65536;
     if (bs < 256 || (bs & (bs - 1))) return fail(ctx, HJGPU_EINVAL, "block_size must be a power of two >= 256");
     const size_t workers = algorithm == 0 ? (size_t)hj_npj_probe_grid(ctx->cus, outer_tuples) * 4
-                                          : (size_t)std::max(hj_join_workers(ctx->tune, ctx->cus, false, true), hj_join_workers(ctx->tune, ctx->cus, true, true));
+                                          : (size_t)std::max(hj_join_workers(ctx->tune, ctx->cus, false), hj_join_workers(ctx->tune, ctx->cus, true));
     *capacity = (rows / bs + 1 + workers) * bs;
     return HJGPU_OK;
 }
@@ -1650,7 +1650,7 @@ static int broadcast_enqueue(hjgpu_ctx *ctx, const uint32_t *rk, const uint32_t 
     bm.sentinel = reinterpret_cast<uint32_t *>(d + 8);
     uint32_t *item_part = reinterpret_cast<uint32_t *>(d + 16);
     DevState *st = reinterpret_cast<DevState *>(ctx->state.p);
-    const uint32_t workers = (uint32_t)hj_join_workers(ctx->tune, ctx->cus, big, unique);
+    const uint32_t workers = (uint32_t)hj_join_workers(ctx->tune, ctx->cus, big);
     u64 bs = 0, bl = 0;
     CHK(setup_output(ctx, out, workers, &bs, &bl, jmode));
 
@@ -1842,7 +1842,7 @@ static int phj_grouped_device(hjgpu_ctx *ctx, uint32_t G, uint32_t chunks,
     DevState *st = reinterpret_cast<DevState *>(ctx->state.p);
     const uint32_t f0 = pass0_factor(prm);
     const PartitionForm pass0 = {.group_bins = l.bins};
-    const uint32_t workers = (uint32_t)hj_join_workers(ctx->tune, ctx->cus, pl.big_tables, pl.unique);
+    const uint32_t workers = (uint32_t)hj_join_workers(ctx->tune, ctx->cus, pl.big_tables);
     u64 bs = 0, bl = 0;
     CHK(setup_output(ctx, out, workers, &bs, &bl, pl.mode));
     HIPCHK(ctx, hipEventRecord(ctx->grp_ev_pass0[0], stream));

@@ -155,7 +155,7 @@ int hjgpu_join_partitions(hjgpu_ctx *ctx,
     DevState *st = reinterpret_cast<DevState *>(ctx->state.p);
     u64 bs = 0, bl = 0;
     const bool unique = ctx->tune.unique || (passes->flags & HJGPU_FLAG_UNIQUE);
-    const uint32_t workers = (uint32_t)hj_join_workers(ctx->tune, ctx->cus, false, unique);
+    const uint32_t workers = (uint32_t)hj_join_workers(ctx->tune, ctx->cus, false);
     CHK(setup_output(ctx, out, workers, &bs, &bl));
     record(ctx, EV_BEGIN, stream);
     HIPCHK(ctx, hj_zero_async(st, sizeof(DevState), stream));

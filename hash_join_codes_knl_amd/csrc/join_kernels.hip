@@ -65,6 +65,14 @@ constexpr int hj_join_waves_per_simd(int block, int log2slots)
     return w < 1 ? 1 : w;
 }
 
+// The two slots of a key in the cuckoo table of 2^LOG2SLOTS slots: the top bits of key * tf0, and an odd distance from key * tf1 further
+template <int LOG2SLOTS>
+__device__ __forceinline__ uint2 hj_cuckoo_slots(uint32_t key, uint32_t tf0, uint32_t tf1)
+{
+    const uint32_t a1 = (key * tf0) >> (32 - LOG2SLOTS);
+    return make_uint2(a1, (a1 + (((key * tf1) >> (32 - LOG2SLOTS)) | 1u)) & ((1u << LOG2SLOTS) - 1));
+}
+
 // HJ_EMIT4 (build-time, default 1; 0 for A/B): a probe vector whose four tuples matched exactly once each leaves the lane as ONE 16-byte
 // store per result column (EmitterT::emit4) instead of four 4-byte ones.  Round 6, 64 M x 1 G with 10^9 rows, default policy
 // (non-temporal rows), one process, same allocations: join 4.48 -> 3.83 ms (profiles/r06_ab_emit4.txt) - the 4-byte non-temporal
@@ -311,8 +319,8 @@ __device__ __forceinline__ void join_body(JoinArgs a)
                     for (int j = 0; j < 4; ++j) {
                         if (g + j < gb || g + j >= ge) continue;
                         if (!cuckoo_failed) {
-                            const uint32_t a1 = (key[j] * tf0) >> SHIFT;
-                            const uint32_t a2 = (a1 + (((key[j] * tf1) >> SHIFT) | 1u)) & MASK;
+                            const uint2 at2 = hj_cuckoo_slots<LOG2SLOTS>(key[j], tf0, tf1);
+                            const uint32_t a1 = at2.x, a2 = at2.y;
                             const uint32_t k1 = (uint32_t)tab64[a1], k2 = (uint32_t)tab64[a2];
                             const uint32_t at = k1 == key[j] ? a1 : a2;
                             if (k1 == key[j] || k2 == key[j]) atomicOr(&slot_bits[at >> 5], 1u << (at & 31));
@@ -401,7 +409,8 @@ __device__ __forceinline__ void join_body(JoinArgs a)
         uint32_t hits = 0;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            const uint32_t a1 = (key[j] * tf0) >> SHIFT;
+            const uint2 at = hj_cuckoo_slots<LOG2SLOTS>(key[j], tf0, tf1);
+            const uint32_t a1 = at.x;
 #if defined(HJ_JOIN_LIMIT_STUDY) && HJ_JOIN_LIMIT_STUDY == 1
             // LIMIT STUDY, never the product (tools/build_variant.py join_one_slot -DHJ_JOIN_LIMIT_STUDY=1; results are WRONG): the second
             // slot's multiply, address and LDS read do not exist - an upper bound on what ANY scheme that fetches a key's two slots with one
@@ -410,9 +419,8 @@ __device__ __forceinline__ void join_body(JoinArgs a)
             t1[j] = tab64[a1];
             t2[j] = t1[j] ^ ((u64)1 << 63);
 #else
-            const uint32_t a2 = (a1 + (((key[j] * tf1) >> SHIFT) | 1u)) & MASK;
             t1[j] = tab64[a1];
-            t2[j] = tab64[a2];
+            t2[j] = tab64[at.y];
 #endif
         }
         if constexpr (MODE == HJ_MODE_SEMI || MODE == HJ_MODE_ANTI) {
@@ -424,10 +432,9 @@ __device__ __forceinline__ void join_body(JoinArgs a)
             // one marked slot per matched key is enough: the walk over the build rows below looks at both slots of a key
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                const uint32_t a1 = (key[j] * tf0) >> SHIFT;
-                const uint32_t a2 = (a1 + (((key[j] * tf1) >> SHIFT) | 1u)) & MASK;
+                const uint2 a12 = hj_cuckoo_slots<LOG2SLOTS>(key[j], tf0, tf1);
                 const bool h1 = valid[j] && ((uint32_t)t1[j] == key[j]), h2 = valid[j] && ((uint32_t)t2[j] == key[j]);
-                const uint32_t at = h1 ? a1 : a2;
+                const uint32_t at = h1 ? a12.x : a12.y;
                 if (h1 || h2) atomicOr(&slot_bits[at >> 5], 1u << (at & 31));             // ds_or_b32
             }
         }
@@ -603,8 +610,8 @@ __device__ __forceinline__ void join_body(JoinArgs a)
                 if (i < hi) {
                     const uint32_t k = PACKED ? (uint32_t)r64[at] : a.rk[at];
                     if (!chained) {
-                        const uint32_t a1 = (k * tf0) >> SHIFT;
-                        const uint32_t a2 = (a1 + (((k * tf1) >> SHIFT) | 1u)) & MASK;
+                        const uint2 a12 = hj_cuckoo_slots<LOG2SLOTS>(k, tf0, tf1);
+                        const uint32_t a1 = a12.x, a2 = a12.y;
                         const u64 t1 = tab64[a1], t2 = tab64[a2];
                         hit = ((uint32_t)t1 == k && ((slot_bits[a1 >> 5] >> (a1 & 31)) & 1u)) ||
                               ((uint32_t)t2 == k && ((slot_bits[a2 >> 5] >> (a2 & 31)) & 1u));
@@ -727,10 +734,8 @@ __device__ __forceinline__ void join_body(JoinArgs a)
                     const u64 old = atomicExch(&tab64[loc], cur);            // ds_wrxchg_rtn_b64
                     if ((uint32_t)old == empty) break;                       // slot was free
                     // `old` was evicted: it moves to the other one of its two slots
-                    const uint32_t ok_ = (uint32_t)old;
-                    const uint32_t a1 = (ok_ * tf0) >> SHIFT;
-                    const uint32_t a2 = (a1 + (((ok_ * tf1) >> SHIFT) | 1u)) & MASK;
-                    loc = (loc == a1) ? a2 : a1;
+                    const uint2 a12 = hj_cuckoo_slots<LOG2SLOTS>((uint32_t)old, tf0, tf1);
+                    loc = (loc == a12.x) ? a12.y : a12.x;
                     cur = old;
                 }
                 if (it == CUCKOO_MAX_EVICTIONS) cuckoo_failed = 1;           // a tuple is left in hand
@@ -784,9 +789,8 @@ __device__ __forceinline__ void join_body(JoinArgs a)
         if constexpr (MODE == HJ_MODE_ANTI) {
             // an item without build rows reports all its probe rows; a multi-fill item the rows no fill has marked
             if (DEDUP || rows_beg >= rows_end) {
-                auto probe4_none = [](const uint32_t (&)[4], const uint32_t (&)[4], const bool (&)[4]) -> uint32_t { return 0u; };
                 anti_tail = true;
-                probe_item(slice, nslices, probe4_none);
+                probe_item(slice, nslices, hj_tail_pass{});
                 anti_tail = false;
                 if (DEDUP) __syncthreads();          // every lane has read `matched` before the next item clears it
             }
@@ -803,20 +807,10 @@ __device__ __forceinline__ void join_body(JoinArgs a)
     }
 
     // ---- per-wave cursors -> final offsets (close_gaps input) ---------------------
-    if (a.ok && hj_lane() == 0)
-        hj_store(&a.final_offsets[(u64)blockIdx.x * NW + wave], wave_cursor[wave]);
+    if (a.ok) hj_leave_cursor(a.final_offsets, wave_cursor);
 
     // ---- workgroup reduction of the aggregates, 4 atomics per workgroup ---------
-    acc_n = wave_reduce_sum(acc_n); acc_k = wave_reduce_sum(acc_k);
-    acc_o = wave_reduce_sum(acc_o); acc_i = wave_reduce_sum(acc_i);
-    if (hj_lane() == 0) { red[0][wave] = acc_n; red[1][wave] = acc_k; red[2][wave] = acc_o; red[3][wave] = acc_i; }
-    __syncthreads();
-    if (tid < 4) {
-        u64 s = 0;
-        for (int i = 0; i < NW; ++i) s += red[tid][i];
-        u64 *dst = reinterpret_cast<u64 *>(a.result) + tid;
-        if (s) atomicAdd(dst, s);
-    }
+    hj_add_to_result(red, a.result, acc_n, acc_k, acc_o, acc_i);
 }
 
 template <int BLOCK, int LOG2SLOTS, int BATCH, bool PACKED, bool UNIQUE, bool DEDUP = false, bool NTROWS = true>
@@ -908,7 +902,8 @@ __global__ __launch_bounds__(BLOCK) void build_unmatched_kernel(JoinArgs a, uint
             }
         }
     }
-    if (a.ok && hj_lane() == 0) hj_store(&a.final_offsets[(u64)blockIdx.x * NW + wave], wave_cursor[wave]);
+    if (a.ok) hj_leave_cursor(a.final_offsets, wave_cursor);
+    // (three sums, written out: the reduction as a call changes the schedule of this kernel, see hj_add_to_result)
     acc_n = wave_reduce_sum(acc_n); acc_k = wave_reduce_sum(acc_k); acc_i = wave_reduce_sum(acc_i);
     if (hj_lane() == 0) { red[0][wave] = acc_n; red[1][wave] = acc_k; red[2][wave] = acc_i; }
     __syncthreads();
@@ -967,35 +962,16 @@ const JoinConfig &hj_join_config_big()
     return cfg;
 }
 
-// workgroups per CU the LDS table allows (160 KiB per CU), capped by 2048 threads per CU
-static int join_wgs_per_cu(const JoinConfig &c)
-{
-    // + 9 KiB: the UNIQUE instances' `matched` bits; the same grid for both keeps hj_join_workers one number
-    return hj_join_wgs_per_cu(c.block, c.log2slots);
-}
-
-static int join_grid(int cus, const JoinConfig &c) { return cus * join_wgs_per_cu(c); }
+// workgroups per CU the LDS table allows (160 KiB per CU, + 9 KiB: the UNIQUE instances' `matched` bits; the same grid for both keeps
+// hj_join_workers one number), capped by 2048 threads per CU
+static int join_grid(int cus, const JoinConfig &c) { return cus * hj_join_wgs_per_cu(c.block, c.log2slots); }
 // Worker slots (final_offsets entries, one open output block each) of a join: one per wave of ONE launch.  A _UNIQUE join is
 // two launches (see join_kernel) of the same grid; the second half's waves continue in the first half's open blocks.
-int hj_join_workers(const HjTuning &t, int cus, bool big_tables, bool unique)
+int hj_join_workers(const HjTuning &t, int cus, bool big_tables)
 {
-    (void)unique;
     const JoinConfig &c = hj_join_config_of(t, big_tables);
     return join_grid(cus, c) * (c.block / 64);
 }
-
-// (the plain-row instances serve solo materialising joins only; aggregate-only joins never emit: the NTROWS = true instance)
-#define JOIN_LAUNCH(B, L, U, P, UNQ, DD, ARGS)                                                                          \
-    do {                                                                                                                \
-        if ((ARGS).ok && !(ARGS).nt_rows) hipLaunchKernelGGL((join_kernel<B, L, U, P, UNQ, DD, false>), dim3(join_grid(cus, c)), dim3(B), 0, stream, ARGS); \
-        else hipLaunchKernelGGL((join_kernel<B, L, U, P, UNQ, DD, true>), dim3(join_grid(cus, c)), dim3(B), 0, stream, ARGS);                              \
-    } while (0)
-#define JOIN_CASE(B, L, U, UNQ)                                                                   \
-    if (c.block == B && c.log2slots == L && c.batch == U && (b.unique != 0) == UNQ) {             \
-        if (b.packed) JOIN_LAUNCH(B, L, U, true, UNQ, false, b);                                  \
-        else JOIN_LAUNCH(B, L, U, false, UNQ, false, b);                                          \
-        return hipGetLastError() == hipSuccess ? HJGPU_OK : HJGPU_EHIP;                           \
-    }
 
 // The geometries that are built (option "join_cfg"): {block, log2slots, batch, a UNIQUE instance exists}.
 // NO SHIPPED INSTANCE MAY USE SCRATCH (tests/test_kernel_resources.py reads the compiler's remarks): a K6 instance with a
@@ -1015,61 +991,88 @@ bool hj_join_config_built(const JoinConfig &c, bool unique)
     return false;
 }
 
-// the two launches of a _UNIQUE join (see join_kernel): single-fill items at the default geometry, then the multi-fill
-// items (their own work counter and worker slots) at one vector per lane
-#define JOIN_CASE_UNIQUE(B, L)                                                                    \
-    if (c.block == B && c.log2slots == L && b.unique) {                                           \
-        JoinArgs d = b;                                                                           \
-        d.work_counter = b.work_counter2;                                                         \
-        if (b.packed) { JOIN_LAUNCH(B, L, 2, true, true, false, b); JOIN_LAUNCH(B, L, 1, true, true, true, d); }      \
-        else { JOIN_LAUNCH(B, L, 2, false, true, false, b); JOIN_LAUNCH(B, L, 1, false, true, true, d); }             \
-        return hipGetLastError() == hipSuccess ? HJGPU_OK : HJGPU_EHIP;                           \
-    }
+// The launches of one join at geometry (B, L), all with the same grid on the same stream.  `first`: the join's arguments as they are.
+// `multi`: the multi-fill items of a join of two launches (see join_kernel) - a _UNIQUE join (join_kernel), a semi- or anti-join
+// (exists_probe_kernel), a left outer join (outer_probe_kernel, with the first-match walk or without it) - at one vector per lane, with
+// their own work counter.  `mark`: a full outer join's third launch, the marks of its multi-fill items (their rows: the left outer
+// join's multi-fill instance as it is), with the third work counter and no rows.  A right outer join is one launch, as the inner join;
+// right and full outer joins take packed inputs only.  SPLIT: the geometry has the instances of the joins of several launches.
+// (the plain-row instances serve solo materialising joins only; aggregate-only joins never emit: the NTROWS = true instance)
+typedef void (*JoinKernel)(JoinArgs);
+struct JoinLaunches { JoinKernel first, multi, mark; };
 
-// a semi- or anti-join: the same two launches as a _UNIQUE join, exists_probe_kernel instead of join_kernel
-#define EXISTS_LAUNCH(B, L, U, P, M, DD, ARGS) \
-    hipLaunchKernelGGL((exists_probe_kernel<B, L, U, P, M, DD>), dim3(join_grid(cus, c)), dim3(B), 0, stream, ARGS)
-#define EXISTS_CASE(B, L, M)                                                                      \
-    if (c.block == B && c.log2slots == L && b.mode == M) {                                        \
-        JoinArgs d = b;                                                                           \
-        d.work_counter = b.work_counter2;                                                         \
-        if (b.packed) { EXISTS_LAUNCH(B, L, 2, true, M, false, b); EXISTS_LAUNCH(B, L, 1, true, M, true, d); }      \
-        else { EXISTS_LAUNCH(B, L, 2, false, M, false, b); EXISTS_LAUNCH(B, L, 1, false, M, true, d); }             \
-        return hipGetLastError() == hipSuccess ? HJGPU_OK : HJGPU_EHIP;                           \
-    }
+// the inner join: join_kernel, the geometry's one batch (2) or, under _UNIQUE, its two launches; `nt`: the NTROWS instances
+template <int B, int L, bool SPLIT>
+static JoinLaunches inner_join_kernels(bool packed, bool unique, bool nt, int batch)
+{
+    JoinLaunches k = {nullptr, nullptr, nullptr};
+    hj_with_bool(packed, [&](auto p) {
+        hj_with_bool(nt, [&](auto r) {
+            constexpr bool P = decltype(p)::value, NT = decltype(r)::value;
+            if (!unique) {
+                if (batch == 2) k.first = join_kernel<B, L, 2, P, false, false, NT>;
+            } else if constexpr (SPLIT) {
+                k.first = join_kernel<B, L, 2, P, true, false, NT>;
+                k.multi = join_kernel<B, L, 1, P, true, true, NT>;
+            }
+        });
+    });
+    return k;
+}
 
-// a left outer join: the same two launches, outer_probe_kernel with the first-match walk or without it
-#define OUTER_LAUNCH(B, L, U, P, UNQ, DD, ARGS) \
-    hipLaunchKernelGGL((outer_probe_kernel<B, L, U, P, UNQ, DD>), dim3(join_grid(cus, c)), dim3(B), 0, stream, ARGS)
-#define OUTER_CASE(B, L, UNQ)                                                                     \
-    if (c.block == B && c.log2slots == L && (b.unique != 0) == UNQ) {                             \
-        JoinArgs d = b;                                                                           \
-        d.work_counter = b.work_counter2;                                                         \
-        if (b.packed) { OUTER_LAUNCH(B, L, 2, true, UNQ, false, b); OUTER_LAUNCH(B, L, 1, true, UNQ, true, d); }    \
-        else { OUTER_LAUNCH(B, L, 2, false, UNQ, false, b); OUTER_LAUNCH(B, L, 1, false, UNQ, true, d); }           \
-        return hipGetLastError() == hipSuccess ? HJGPU_OK : HJGPU_EHIP;                           \
+// every other mode (SPLIT geometries only); rows always non-temporal
+template <int B, int L>
+static JoinLaunches mode_join_kernels(uint32_t mode, bool packed, bool unique)
+{
+    JoinLaunches k = {nullptr, nullptr, nullptr};
+    if (hj_mode_keeps_build(mode)) {
+        if (!packed) return k;
+        if (mode == HJ_MODE_RIGHT_OUTER) k.first = right_probe_kernel<B, L, 2, true>;
+        else {
+            k.first = full_probe_kernel<B, L, 2, true>;
+            k.multi = outer_probe_kernel<B, L, 1, true, false, true>;
+            k.mark = mark_probe_kernel<B, L, 1, true>;
+        }
+        return k;
     }
+    hj_with_bool(packed, [&](auto p) {
+        constexpr bool P = decltype(p)::value;
+        if (mode == HJ_MODE_SEMI) {
+            k.first = exists_probe_kernel<B, L, 2, P, HJ_MODE_SEMI, false>;
+            k.multi = exists_probe_kernel<B, L, 1, P, HJ_MODE_SEMI, true>;
+        } else if (mode == HJ_MODE_ANTI) {
+            k.first = exists_probe_kernel<B, L, 2, P, HJ_MODE_ANTI, false>;
+            k.multi = exists_probe_kernel<B, L, 1, P, HJ_MODE_ANTI, true>;
+        } else if (mode == HJ_MODE_LEFT_OUTER) {
+            hj_with_bool(unique, [&](auto u) {
+                constexpr bool U = decltype(u)::value;
+                k.first = outer_probe_kernel<B, L, 2, P, U, false>;
+                k.multi = outer_probe_kernel<B, L, 1, P, U, true>;
+            });
+        }
+    });
+    return k;
+}
 
-// a right outer join: one launch, as the inner join (packed inputs only); a full outer join: the left outer join's two launches - the
-// multi-fill one as it is - and the marks of the multi-fill items
-#define RIGHT_CASE(B, L)                                                                          \
-    if (c.block == B && c.log2slots == L) {                                                       \
-        if (!b.packed) return HJGPU_EINVAL;                                                       \
-        hipLaunchKernelGGL((right_probe_kernel<B, L, 2, true>), dim3(join_grid(cus, c)), dim3(B), 0, stream, b);    \
-        return hipGetLastError() == hipSuccess ? HJGPU_OK : HJGPU_EHIP;                           \
+template <int B, int L, bool SPLIT>
+static int launch_join_at(const JoinArgs &b, int batch, int grid, hipStream_t stream)
+{
+    JoinLaunches k = {nullptr, nullptr, nullptr};
+    if (b.mode == HJ_MODE_INNER) k = inner_join_kernels<B, L, SPLIT>(b.packed != 0, b.unique != 0, !(b.ok && !b.nt_rows), batch);
+    else if constexpr (SPLIT) k = mode_join_kernels<B, L>(b.mode, b.packed != 0, b.unique != 0);
+    // a geometry without this join's instances (hj_join_config_built), column inputs to a right / full outer join, no third counter
+    if (!k.first || (k.mark && !b.work_counter3)) return HJGPU_EINVAL;
+    const JoinKernel kernels[3] = {k.first, k.multi, k.mark};
+    u64 *const counters[3] = {b.work_counter, b.work_counter2, b.work_counter3};
+    for (int i = 0; i < 3; ++i) {
+        if (!kernels[i]) continue;
+        JoinArgs d = b;
+        d.work_counter = counters[i];
+        if (i == 2) d.ok = nullptr;
+        hipLaunchKernelGGL(kernels[i], dim3(grid), dim3(B), 0, stream, d);
     }
-#define FULL_CASE(B, L)                                                                           \
-    if (c.block == B && c.log2slots == L) {                                                       \
-        if (!b.packed) return HJGPU_EINVAL;                                                       \
-        if (!b.work_counter3) return HJGPU_EINVAL;                                                \
-        JoinArgs d = b, e = b;                                                                    \
-        d.work_counter = b.work_counter2;                                                         \
-        e.work_counter = b.work_counter3; e.ok = nullptr;                                         \
-        hipLaunchKernelGGL((full_probe_kernel<B, L, 2, true>), dim3(join_grid(cus, c)), dim3(B), 0, stream, b);                \
-        hipLaunchKernelGGL((outer_probe_kernel<B, L, 1, true, false, true>), dim3(join_grid(cus, c)), dim3(B), 0, stream, d);  \
-        hipLaunchKernelGGL((mark_probe_kernel<B, L, 1, true>), dim3(join_grid(cus, c)), dim3(B), 0, stream, e);                \
-        return hipGetLastError() == hipSuccess ? HJGPU_OK : HJGPU_EHIP;                           \
-    }
+    return hipGetLastError() == hipSuccess ? HJGPU_OK : HJGPU_EHIP;
+}
 
 int hj_launch_build_unmatched(const JoinArgs &a, const HjTuning &t, int cus, hipStream_t stream)
 {
@@ -1093,30 +1096,10 @@ int hj_launch_join(const JoinArgs &a, const HjTuning &t, int cus, hipStream_t st
     b.force_chained = t.force_chained ? 1u : 0u;       // tests: exercise the fallback table everywhere
     b.unique = (a.unique || t.unique) ? 1u : 0u;
     if ((b.unique || b.mode) && !b.work_counter2) return HJGPU_EINVAL;
-    if (hj_mode_keeps_build(b.mode)) {
-        if (b.unique || !b.build_bits) return HJGPU_EINVAL;
-        if (b.mode == HJ_MODE_RIGHT_OUTER) { RIGHT_CASE(512, 13) RIGHT_CASE(1024, 14) }
-        else { FULL_CASE(512, 13) FULL_CASE(1024, 14) }
-        return HJGPU_EINVAL;                           // a geometry without these instances (hj_join_config_built)
-    }
-    if (b.mode == HJ_MODE_LEFT_OUTER) {
-        OUTER_CASE(512, 13, false)
-        OUTER_CASE(512, 13, true)
-        OUTER_CASE(1024, 14, false)
-        OUTER_CASE(1024, 14, true)
-        return HJGPU_EINVAL;                           // a geometry without a _UNIQUE instance (hj_join_config_built)
-    }
-    if (b.mode != HJ_MODE_INNER) {
-        EXISTS_CASE(512, 13, HJ_MODE_SEMI)
-        EXISTS_CASE(512, 13, HJ_MODE_ANTI)
-        EXISTS_CASE(1024, 14, HJ_MODE_SEMI)
-        EXISTS_CASE(1024, 14, HJ_MODE_ANTI)
-        return HJGPU_EINVAL;                           // a geometry without a _UNIQUE instance (hj_join_config_built)
-    }
-    JOIN_CASE_UNIQUE(512, 13)
-    JOIN_CASE_UNIQUE(1024, 14)
-    JOIN_CASE(512, 13, 2, false)
-    JOIN_CASE(1024, 14, 2, false)
-    JOIN_CASE(256, 12, 2, false)
+    if (hj_mode_keeps_build(b.mode) && (b.unique || !b.build_bits)) return HJGPU_EINVAL;
+    const int grid = join_grid(cus, c);
+    if (c.block == 512 && c.log2slots == 13) return launch_join_at<512, 13, true>(b, c.batch, grid, stream);
+    if (c.block == 1024 && c.log2slots == 14) return launch_join_at<1024, 14, true>(b, c.batch, grid, stream);
+    if (c.block == 256 && c.log2slots == 12) return launch_join_at<256, 12, false>(b, c.batch, grid, stream);
     return HJGPU_EINVAL;
 }

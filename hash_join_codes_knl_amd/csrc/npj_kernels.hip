@@ -65,7 +65,34 @@ int hj_launch_npj_build(const uint32_t *keys, const uint32_t *vals, size_t n, u6
 }
 
 constexpr int NPJ_PROBE_BLOCK = 256;
+constexpr int NPJ_PROBE_WAVES = NPJ_PROBE_BLOCK / 64;
 
+// What every probe body starts with: the emitter and this wave's cursor, and the probe columns as 16-byte vectors - the columns are
+// aligned down to 16 bytes, tuple i of the relation is component gb + i, the vectors [0, nvec) cover [gb, ge).
+struct NpjProbeColumns {
+    const uint4 *k4, *v4;
+    u64 gb, ge, nvec, stride;
+};
+template <class Em>
+__device__ __forceinline__ NpjProbeColumns npj_probe_begin(const NpjProbeArgs &a, Em &em, u64 (&wave_cursor)[NPJ_PROBE_WAVES])
+{
+    const int wave = threadIdx.x >> 6;
+    em.init(a.ok, a.oov, a.oiv, a.block_size, a.block_limit, a.block_counter, a.overflow,
+            &wave_cursor[wave]);
+    if (hj_lane() == 0) wave_cursor[wave] = HJ_NO_CURSOR;
+    const uint32_t a0 = (uint32_t)(((uintptr_t)a.keys >> 2) & 3);
+    NpjProbeColumns c;
+    c.k4 = reinterpret_cast<const uint4 *>(a.keys - a0);
+    c.v4 = reinterpret_cast<const uint4 *>(a.vals - a0);
+    c.gb = a0; c.ge = a0 + a.n;
+    c.nvec = (c.ge + 3) >> 2;
+    c.stride = (u64)gridDim.x * NPJ_PROBE_BLOCK;
+    return c;
+}
+
+// The bucket / group walk of every join mode but the inner join (npj_probe_kernel below: the same walk as the kernel's own body, whose
+// machine code changes when it is an inlined function; folding it in here waits for a measurement against it) on a table with the
+// reference's hash (the line walk further below: the library's own tables).
 // GROUPED: the walk fetches aligned groups of 4 buckets (32 bytes, two 16-byte loads
 // issued together) instead of one bucket per dependent load.  The walk has to reach
 // the first EMPTY bucket (every match counts, npj.cpp:426-442), i.e. 2.5 buckets on
@@ -73,24 +100,140 @@ constexpr int NPJ_PROBE_BLOCK = 256;
 // trips per probe; a group resolves most walks in one.  Needs buckets % 4 == 0
 // (the library's own tables; any other table takes the bucket-at-a-time path).
 // UNIQUE: the reference's _UNIQUE build (npj.cpp:288-290, 436-438): the walk of a probe key ends at its first match.
+// MODE (HJ_MODE_*): semi- / anti-join (HJGPU_FLAG_SEMI / _ANTI, npj_exists_kernel) -
+// with UNIQUE's walk, ONE row (key, outer_val) per probe tuple that found a match / that reached an empty bucket without one; left outer
+// join (HJGPU_FLAG_LEFT_OUTER, npj_outer_kernel) - the inner join's rows (every match, or the first under UNIQUE), then ONE row
+// (key, outer_val, HJGPU_NULL_VAL) per probe tuple whose walk found none.
+template <bool GROUPED, bool UNIQUE, int MODE>
+__device__ __forceinline__ void npj_probe_body(NpjProbeArgs a)
+{
+    // LEFTISH: the modes that report like the left outer join; KEEPB (right / full outer joins, never UNIQUE: the walk visits every copy of
+    // a key): every bucket a probe matches gets its bit in a.bucket_bits - one bucket per build tuple, so bucket-level marks are exact
+    constexpr bool LEFTISH = MODE == HJ_MODE_LEFT_OUTER || MODE == HJ_MODE_FULL_OUTER;
+    constexpr bool KEEPB = MODE == HJ_MODE_RIGHT_OUTER || MODE == HJ_MODE_FULL_OUTER;
+    constexpr bool MATCHES = LEFTISH || KEEPB;     // the modes that report a row per match
+    static_assert(MODE != HJ_MODE_INNER && (UNIQUE || LEFTISH || KEEPB) && !(UNIQUE && KEEPB), "semi- and anti-joins walk to the first match");
+    constexpr int NW = NPJ_PROBE_WAVES;
+    __shared__ u64 red[4][NW];
+    __shared__ u64 wave_cursor[NW];
+    EmitterT<true, MATCHES ? 3 : 2> em;
+    const NpjProbeColumns c = npj_probe_begin(a, em, wave_cursor);
+    const uint4 *__restrict__ k4 = c.k4, *__restrict__ v4 = c.v4;
+    const u64 gb = c.gb, ge = c.ge, nvec = c.nvec, stride = c.stride;
+    const u64 *__restrict__ table = a.table;
+    const u64 buckets = a.buckets;
+    const uint32_t factor = a.factor;
+
+    u64 acc_n = 0, acc_k = 0, acc_o = 0, acc_i = 0;
+    for (u64 v = (u64)blockIdx.x * NPJ_PROBE_BLOCK + threadIdx.x; v < nvec; v += stride) {
+        const uint4 kk = k4[v], vv = v4[v];
+        const u64 g = v << 2;
+        const uint32_t key[4] = {kk.x, kk.y, kk.z, kk.w};
+        const uint32_t val[4] = {vv.x, vv.y, vv.z, vv.w};
+        u64 h[4];
+        bool act[4], in[4], hit[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            act[j] = (g + j >= gb) && (g + j < ge);
+            in[j] = act[j]; hit[j] = false;
+            h[j] = npj_bucket(key[j], factor, buckets);
+        }
+        if (GROUPED) {
+            const uint4 *__restrict__ t4 = reinterpret_cast<const uint4 *>(table);
+            while (act[0] | act[1] | act[2] | act[3]) {
+                uint4 lo[4], hi[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {           // all group loads of the 4 chains in flight together
+                    lo[j] = make_uint4(0, 0, 0, 0); hi[j] = lo[j];
+                    if (act[j]) { const u64 grp = h[j] >> 2; lo[j] = t4[2 * grp]; hi[j] = t4[2 * grp + 1]; }
+                }
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    if (act[j]) {
+                        const uint32_t bk[4] = {lo[j].x, lo[j].z, hi[j].x, hi[j].z};   // keys of the group
+                        const uint32_t bv[4] = {lo[j].y, lo[j].w, hi[j].y, hi[j].w};   // payloads
+                        const uint32_t first = (uint32_t)h[j] & 3u;
+                        bool open = true;                                              // no empty bucket seen yet
+#pragma unroll
+                        for (int b = 0; b < 4; ++b) {
+                            const bool inb = open && ((uint32_t)b >= first);
+                            if (inb && bk[b] == 0u) open = false;
+                            else if (inb && bk[b] == key[j]) {
+                                if constexpr (MATCHES) {
+                                    acc_n += 1; acc_k += key[j]; acc_o += val[j]; acc_i += bv[b];
+                                    em.emit(key[j], val[j], bv[b]);
+                                }
+                                if constexpr (KEEPB) { const u64 at = (h[j] & ~3ull) + b; atomicOr(&a.bucket_bits[at >> 5], 1u << ((uint32_t)at & 31u)); }
+                                hit[j] = true;
+                                if (UNIQUE) open = false;
+                            }
+                        }
+                        if (!open) act[j] = false;
+                        else { h[j] = (h[j] & ~3ull) + 4; if (h[j] >= buckets) h[j] = 0; }
+                    }
+                }
+            }
+        } else {
+            u64 t[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) t[j] = act[j] ? table[h[j]] : 0ull;
+            while (act[0] | act[1] | act[2] | act[3]) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    if (act[j]) {
+                        if ((uint32_t)t[j] == 0u) {
+                            act[j] = false;
+                        } else {
+                            if ((uint32_t)t[j] == key[j]) {
+                                const uint32_t iv = (uint32_t)(t[j] >> 32);
+                                if constexpr (MATCHES) {
+                                    acc_n += 1; acc_k += key[j]; acc_o += val[j]; acc_i += iv;
+                                    em.emit(key[j], val[j], iv);
+                                }
+                                if constexpr (KEEPB) atomicOr(&a.bucket_bits[h[j] >> 5], 1u << ((uint32_t)h[j] & 31u));
+                                hit[j] = true;
+                                if (UNIQUE) { act[j] = false; continue; }
+                            }
+                            if (++h[j] == buckets) h[j] = 0;
+                            t[j] = table[h[j]];
+                        }
+                    }
+                }
+            }
+        }
+        if constexpr (LEFTISH) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                if (in[j] && !hit[j]) {                 // (a probe key 0 stops at the first empty bucket: no match, a NULL row)
+                    acc_n += 1; acc_k += key[j]; acc_o += val[j];
+                    em.emit(key[j], val[j], HJGPU_NULL_VAL);
+                }
+            }
+        } else if constexpr (MODE == HJ_MODE_SEMI || MODE == HJ_MODE_ANTI) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                if (in[j] && hit[j] == (MODE == HJ_MODE_SEMI)) {
+                    acc_n += 1; acc_k += key[j]; acc_o += val[j];
+                    em.emit(key[j], val[j], 0u);
+                }
+            }
+        }
+    }
+    if (a.ok) hj_leave_cursor(a.final_offsets, wave_cursor);
+    hj_add_to_result(red, a.result, acc_n, acc_k, acc_o, acc_i);
+}
+
+// The inner join's walk, a body of its own ("One body per probe walk"): npj_probe_body without the modes.
 template <bool GROUPED, bool UNIQUE>
 __global__ __launch_bounds__(NPJ_PROBE_BLOCK) void npj_probe_kernel(NpjProbeArgs a)
 {
     constexpr int NW = NPJ_PROBE_BLOCK / 64;
     __shared__ u64 red[4][NW];
     __shared__ u64 wave_cursor[NW];
-    const int wave = threadIdx.x >> 6;
     Emitter em;
-    em.init(a.ok, a.oov, a.oiv, a.block_size, a.block_limit, a.block_counter, a.overflow,
-            &wave_cursor[wave]);
-    if (hj_lane() == 0) wave_cursor[wave] = HJ_NO_CURSOR;
-
-    const uint32_t a0 = (uint32_t)(((uintptr_t)a.keys >> 2) & 3);
-    const uint4 *__restrict__ k4 = reinterpret_cast<const uint4 *>(a.keys - a0);
-    const uint4 *__restrict__ v4 = reinterpret_cast<const uint4 *>(a.vals - a0);
-    const u64 gb = a0, ge = a0 + a.n;
-    const u64 nvec = (ge + 3) >> 2;
-    const u64 stride = (u64)gridDim.x * NPJ_PROBE_BLOCK;
+    const NpjProbeColumns c = npj_probe_begin(a, em, wave_cursor);
+    const uint4 *__restrict__ k4 = c.k4, *__restrict__ v4 = c.v4;
+    const u64 gb = c.gb, ge = c.ge, nvec = c.nvec, stride = c.stride;
     const u64 *__restrict__ table = a.table;
     const u64 buckets = a.buckets;
     const uint32_t factor = a.factor;
@@ -164,8 +307,8 @@ __global__ __launch_bounds__(NPJ_PROBE_BLOCK) void npj_probe_kernel(NpjProbeArgs
             }
         }
     }
-    if (a.ok && hj_lane() == 0)
-        hj_store(&a.final_offsets[(u64)blockIdx.x * NW + wave], wave_cursor[wave]);
+    if (a.ok) hj_leave_cursor(a.final_offsets, wave_cursor);
+    const int wave = threadIdx.x >> 6;          // (hj_add_to_result, written out: as a call it changes this kernel's machine code)
     acc_n = wave_reduce_sum(acc_n); acc_k = wave_reduce_sum(acc_k);
     acc_o = wave_reduce_sum(acc_o); acc_i = wave_reduce_sum(acc_i);
     if (hj_lane() == 0) { red[0][wave] = acc_n; red[1][wave] = acc_k; red[2][wave] = acc_o; red[3][wave] = acc_i; }
@@ -176,159 +319,17 @@ __global__ __launch_bounds__(NPJ_PROBE_BLOCK) void npj_probe_kernel(NpjProbeArgs
         if (s) atomicAdd(reinterpret_cast<u64 *>(a.result) + threadIdx.x, s);
     }
 }
-
-
-// Semi- / anti-join and left outer join probes (HJGPU_FLAG_SEMI / _ANTI / _LEFT_OUTER).  The inner-join kernels above stay as they are
-// (their machine code is the library's yardstick); this body is their walk with a compile-time MODE, instantiated for the new modes only.
-// MODE (HJ_MODE_*): semi- / anti-join (npj_exists_kernel) - with UNIQUE's walk, ONE row (key, outer_val) per probe tuple that found a
-// match / that reached an empty bucket without one; left outer join (npj_outer_kernel) - the inner join's rows (every match, or the
-// first under UNIQUE), then ONE row (key, outer_val, HJGPU_NULL_VAL) per probe tuple whose walk found none.
-template <bool GROUPED, bool UNIQUE, int MODE>
-__device__ __forceinline__ void npj_mode_body(NpjProbeArgs a)
-{
-    // LEFTISH: the modes that report like the left outer join; KEEPB (right / full outer joins, never UNIQUE: the walk visits every copy of
-    // a key): every bucket a probe matches gets its bit in a.bucket_bits - one bucket per build tuple, so bucket-level marks are exact
-    constexpr bool LEFTISH = MODE == HJ_MODE_LEFT_OUTER || MODE == HJ_MODE_FULL_OUTER;
-    constexpr bool KEEPB = MODE == HJ_MODE_RIGHT_OUTER || MODE == HJ_MODE_FULL_OUTER;
-    static_assert(MODE != HJ_MODE_INNER && (UNIQUE || LEFTISH || KEEPB) && !(UNIQUE && KEEPB), "semi- and anti-joins walk to the first match");
-    constexpr int NW = NPJ_PROBE_BLOCK / 64;
-    __shared__ u64 red[4][NW];
-    __shared__ u64 wave_cursor[NW];
-    const int wave = threadIdx.x >> 6;
-    EmitterT<true, (MODE == HJ_MODE_SEMI || MODE == HJ_MODE_ANTI) ? 2 : 3> em;
-    em.init(a.ok, a.oov, a.oiv, a.block_size, a.block_limit, a.block_counter, a.overflow,
-            &wave_cursor[wave]);
-    if (hj_lane() == 0) wave_cursor[wave] = HJ_NO_CURSOR;
-
-    const uint32_t a0 = (uint32_t)(((uintptr_t)a.keys >> 2) & 3);
-    const uint4 *__restrict__ k4 = reinterpret_cast<const uint4 *>(a.keys - a0);
-    const uint4 *__restrict__ v4 = reinterpret_cast<const uint4 *>(a.vals - a0);
-    const u64 gb = a0, ge = a0 + a.n;
-    const u64 nvec = (ge + 3) >> 2;
-    const u64 stride = (u64)gridDim.x * NPJ_PROBE_BLOCK;
-    const u64 *__restrict__ table = a.table;
-    const u64 buckets = a.buckets;
-    const uint32_t factor = a.factor;
-
-    u64 acc_n = 0, acc_k = 0, acc_o = 0, acc_i = 0;
-    for (u64 v = (u64)blockIdx.x * NPJ_PROBE_BLOCK + threadIdx.x; v < nvec; v += stride) {
-        const uint4 kk = k4[v], vv = v4[v];
-        const u64 g = v << 2;
-        const uint32_t key[4] = {kk.x, kk.y, kk.z, kk.w};
-        const uint32_t val[4] = {vv.x, vv.y, vv.z, vv.w};
-        u64 h[4];
-        bool act[4], in[4], hit[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            act[j] = (g + j >= gb) && (g + j < ge);
-            in[j] = act[j]; hit[j] = false;
-            h[j] = npj_bucket(key[j], factor, buckets);
-        }
-        if (GROUPED) {
-            const uint4 *__restrict__ t4 = reinterpret_cast<const uint4 *>(table);
-            while (act[0] | act[1] | act[2] | act[3]) {
-                uint4 lo[4], hi[4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {           // all group loads of the 4 chains in flight together
-                    lo[j] = make_uint4(0, 0, 0, 0); hi[j] = lo[j];
-                    if (act[j]) { const u64 grp = h[j] >> 2; lo[j] = t4[2 * grp]; hi[j] = t4[2 * grp + 1]; }
-                }
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    if (act[j]) {
-                        const uint32_t bk[4] = {lo[j].x, lo[j].z, hi[j].x, hi[j].z};   // keys of the group
-                        const uint32_t bv[4] = {lo[j].y, lo[j].w, hi[j].y, hi[j].w};   // payloads
-                        const uint32_t first = (uint32_t)h[j] & 3u;
-                        bool open = true;                                              // no empty bucket seen yet
-#pragma unroll
-                        for (int b = 0; b < 4; ++b) {
-                            const bool inb = open && ((uint32_t)b >= first);
-                            if (inb && bk[b] == 0u) open = false;
-                            else if (inb && bk[b] == key[j]) {
-                                if constexpr (MODE == HJ_MODE_INNER || LEFTISH || KEEPB) {
-                                    acc_n += 1; acc_k += key[j]; acc_o += val[j]; acc_i += bv[b];
-                                    em.emit(key[j], val[j], bv[b]);
-                                }
-                                if constexpr (KEEPB) { const u64 at = (h[j] & ~3ull) + b; atomicOr(&a.bucket_bits[at >> 5], 1u << ((uint32_t)at & 31u)); }
-                                if constexpr (MODE != HJ_MODE_INNER) hit[j] = true;
-                                if (UNIQUE) open = false;
-                            }
-                        }
-                        if (!open) act[j] = false;
-                        else { h[j] = (h[j] & ~3ull) + 4; if (h[j] >= buckets) h[j] = 0; }
-                    }
-                }
-            }
-        } else {
-            u64 t[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) t[j] = act[j] ? table[h[j]] : 0ull;
-            while (act[0] | act[1] | act[2] | act[3]) {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    if (act[j]) {
-                        if ((uint32_t)t[j] == 0u) {
-                            act[j] = false;
-                        } else {
-                            if ((uint32_t)t[j] == key[j]) {
-                                const uint32_t iv = (uint32_t)(t[j] >> 32);
-                                if constexpr (MODE == HJ_MODE_INNER || LEFTISH || KEEPB) {
-                                    acc_n += 1; acc_k += key[j]; acc_o += val[j]; acc_i += iv;
-                                    em.emit(key[j], val[j], iv);
-                                }
-                                if constexpr (KEEPB) atomicOr(&a.bucket_bits[h[j] >> 5], 1u << ((uint32_t)h[j] & 31u));
-                                if constexpr (MODE != HJ_MODE_INNER) hit[j] = true;
-                                if (UNIQUE) { act[j] = false; continue; }
-                            }
-                            if (++h[j] == buckets) h[j] = 0;
-                            t[j] = table[h[j]];
-                        }
-                    }
-                }
-            }
-        }
-        if constexpr (LEFTISH) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                if (in[j] && !hit[j]) {                 // (a probe key 0 stops at the first empty bucket: no match, a NULL row)
-                    acc_n += 1; acc_k += key[j]; acc_o += val[j];
-                    em.emit(key[j], val[j], HJGPU_NULL_VAL);
-                }
-            }
-        } else if constexpr (MODE == HJ_MODE_SEMI || MODE == HJ_MODE_ANTI) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                if (in[j] && hit[j] == (MODE == HJ_MODE_SEMI)) {
-                    acc_n += 1; acc_k += key[j]; acc_o += val[j];
-                    em.emit(key[j], val[j], 0u);
-                }
-            }
-        }
-    }
-    if (a.ok && hj_lane() == 0)
-        hj_store(&a.final_offsets[(u64)blockIdx.x * NW + wave], wave_cursor[wave]);
-    acc_n = wave_reduce_sum(acc_n); acc_k = wave_reduce_sum(acc_k);
-    acc_o = wave_reduce_sum(acc_o); acc_i = wave_reduce_sum(acc_i);
-    if (hj_lane() == 0) { red[0][wave] = acc_n; red[1][wave] = acc_k; red[2][wave] = acc_o; red[3][wave] = acc_i; }
-    __syncthreads();
-    if (threadIdx.x < 4) {
-        u64 s = 0;
-        for (int i = 0; i < NW; ++i) s += red[threadIdx.x][i];
-        if (s) atomicAdd(reinterpret_cast<u64 *>(a.result) + threadIdx.x, s);
-    }
-}
-
 
 template <bool GROUPED, int MODE>
 __global__ __launch_bounds__(NPJ_PROBE_BLOCK) void npj_exists_kernel(NpjProbeArgs a)
 {
-    npj_mode_body<GROUPED, true, MODE>(a);
+    npj_probe_body<GROUPED, true, MODE>(a);
 }
 
 template <bool GROUPED, bool UNIQUE>
 __global__ __launch_bounds__(NPJ_PROBE_BLOCK) void npj_outer_kernel(NpjProbeArgs a)
 {
-    npj_mode_body<GROUPED, UNIQUE, HJ_MODE_LEFT_OUTER>(a);
+    npj_probe_body<GROUPED, UNIQUE, HJ_MODE_LEFT_OUTER>(a);
 }
 
 // LINE table (the library's own whole joins, hjgpu_npj*): the walk of a key starts on the
@@ -351,10 +352,146 @@ __device__ __forceinline__ uint32_t quad_perm(uint32_t x)
     return (uint32_t)__builtin_amdgcn_mov_dpp((int)x, CTRL, 0xF, 0xF, true);
 }
 
+// The quad's line walk of every join mode but the inner join (npj_probe_line_kernel below, for the same reason as npj_probe_kernel).
 // MATERIALIZE is a template parameter on purpose: with a run-time `if (a.ok)` inside the walk loop
 // the -O3 build evaluated that (uniform) test per lane at a loop header that the continuation
 // re-enters with only the walking lanes enabled, and later rounds of other lanes then took the
 // emit path with a.ok == NULL (memory access fault; -O1 was fine).
+// MODE (HJ_MODE_*): semi- / anti-join
+// (npj_exists_line_kernel) - lane 0 of the quad reports the tuple when its walk ends: on a match (`found`, SEMI) or on an empty bucket
+// without one (ANTI); left outer join (npj_outer_line_kernel) - the inner join's rows, and lane 0 of the quad reports a NULL row when the
+// walk ends without any match of the quad in any of its lines.
+template <bool MATERIALIZE, bool UNIQUE, int MODE>
+__device__ __forceinline__ void npj_probe_line_body(NpjProbeArgs a)
+{
+    constexpr bool LEFTISH = MODE == HJ_MODE_LEFT_OUTER || MODE == HJ_MODE_FULL_OUTER;     // as in npj_probe_body
+    constexpr bool KEEPB = MODE == HJ_MODE_RIGHT_OUTER || MODE == HJ_MODE_FULL_OUTER;
+    constexpr bool MATCHES = LEFTISH || KEEPB;
+    static_assert(MODE != HJ_MODE_INNER && (UNIQUE || LEFTISH || KEEPB) && !(UNIQUE && KEEPB), "semi- and anti-joins walk to the first match");
+    constexpr int NW = NPJ_PROBE_WAVES;
+    constexpr int B = 4;                                   // lines in flight per quad
+    __shared__ u64 red[4][NW];
+    __shared__ u64 wave_cursor[NW];
+    const int wave = threadIdx.x >> 6;
+    EmitterT<true, MATCHES ? 3 : 2> em;
+    const NpjProbeColumns c = npj_probe_begin(a, em, wave_cursor);
+    const uint4 *__restrict__ k4 = c.k4, *__restrict__ v4 = c.v4;
+    const u64 gb = c.gb, ge = c.ge, nvec = c.nvec, stride = c.stride;
+    const uint4 *__restrict__ t4 = reinterpret_cast<const uint4 *>(a.table);
+    const u64 lines = a.buckets >> 3;
+    const uint32_t factor = a.factor;
+    const uint32_t sub = threadIdx.x & 3;                  // my quarter of the line: buckets 2*sub, 2*sub + 1
+
+    u64 acc_n = 0, acc_k = 0, acc_o = 0, acc_i = 0;
+    // left outer join: the current walk has found a match (quad-uniform).  Declared here, set only by the left outer instances: an
+    // initialised local beside the walk reorders two register moves of the semi- / anti-join instances
+    bool got;
+    // whole waves iterate together (the quad exchanges below need all four lanes)
+    for (u64 v0 = (u64)blockIdx.x * NPJ_PROBE_BLOCK + (threadIdx.x & ~63u); v0 < nvec; v0 += stride) {
+        const u64 v = v0 + hj_lane();
+        uint4 kk = make_uint4(0, 0, 0, 0), vv = kk;
+        if (v < nvec) { kk = k4[v]; vv = v4[v]; }
+        const u64 g = v << 2;
+        const uint32_t kc[4] = {kk.x, kk.y, kk.z, kk.w}, vc[4] = {vv.x, vv.y, vv.z, vv.w};
+        uint32_t okc[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) okc[j] = (v < nvec && g + j >= gb && g + j < ge) ? 1u : 0u;
+
+        // the quad's 16 tuples (4 lanes x 4 components), B at a time
+#pragma unroll
+        for (int r0 = 0; r0 < 16; r0 += B) {
+            uint32_t key[B], val[B];
+            bool act[B];
+            u64 ln[B];
+            uint4 q[B];
+#pragma unroll
+            for (int i = 0; i < B; ++i) {
+                const int r = r0 + i, comp = r & 3;                     // static after unrolling
+                // the tuple's owner is lane r / 4 of the quad: broadcast its key, payload and validity
+                if (r < 4) { key[i] = quad_perm<0x00>(kc[comp]); val[i] = quad_perm<0x00>(vc[comp]); act[i] = quad_perm<0x00>(okc[comp]) != 0; }
+                else if (r < 8) { key[i] = quad_perm<0x55>(kc[comp]); val[i] = quad_perm<0x55>(vc[comp]); act[i] = quad_perm<0x55>(okc[comp]) != 0; }
+                else if (r < 12) { key[i] = quad_perm<0xAA>(kc[comp]); val[i] = quad_perm<0xAA>(vc[comp]); act[i] = quad_perm<0xAA>(okc[comp]) != 0; }
+                else { key[i] = quad_perm<0xFF>(kc[comp]); val[i] = quad_perm<0xFF>(vc[comp]); act[i] = quad_perm<0xFF>(okc[comp]) != 0; }
+                ln[i] = npj_bucket(key[i], factor, lines);
+                q[i] = make_uint4(0, 0, 0, 0);
+                if (act[i]) {
+                    q[i] = t4[4 * ln[i] + sub];                         // 4 lanes x 16 bytes = the key's line
+                }
+            }
+#pragma unroll
+            for (int i = 0; i < B; ++i) {
+                if constexpr (LEFTISH) got = false;
+                while (act[i]) {                                        // uniform inside the quad
+                    // first empty bucket of the line, over the quad
+                    uint32_t fe = q[i].x == 0u ? 2 * sub : (q[i].z == 0u ? 2 * sub + 1 : 8u);
+                    fe = min(fe, quad_perm<0xB1>(fe));                  // lanes 0<->1, 2<->3
+                    fe = min(fe, quad_perm<0x4E>(fe));                  // lanes 0<->2, 1<->3
+                    bool m0 = q[i].x == key[i] && 2 * sub < fe;
+                    bool m1 = q[i].z == key[i] && 2 * sub + 1 < fe;
+                    bool found = false;                                 // UNIQUE: some lane of the quad holds a match
+                    if (UNIQUE) {
+                        // only the FIRST match of the walk counts: the lowest matching bucket of the line
+                        uint32_t fm = m0 ? 2 * sub : (m1 ? 2 * sub + 1 : 8u);
+                        const uint32_t mine = fm;
+                        fm = min(fm, quad_perm<0xB1>(fm));
+                        fm = min(fm, quad_perm<0x4E>(fm));
+                        found = fm < 8u;
+                        m0 = m0 && mine == fm && fm == 2 * sub;
+                        m1 = m1 && mine == fm && fm == 2 * sub + 1;
+                    }
+                    if constexpr (MATCHES) {
+                        const uint32_t m = (m0 ? 1u : 0u) + (m1 ? 1u : 0u);
+                        acc_n += m; acc_k += (u64)key[i] * m; acc_o += (u64)val[i] * m;
+                        acc_i += (m0 ? q[i].y : 0u); acc_i += (m1 ? q[i].w : 0u);
+                        if (MATERIALIZE) {
+                            if (m0) em.emit(key[i], val[i], q[i].y);
+                            if (m1) em.emit(key[i], val[i], q[i].w);
+                        }
+                        if constexpr (KEEPB) {
+                            // my two buckets of the line: 8 * line + 2 * sub and the next one - an even index, both bits in one word
+                            const u64 at = 8 * ln[i] + 2 * sub;
+                            if (m0 || m1) atomicOr(&a.bucket_bits[at >> 5], ((m0 ? 1u : 0u) | (m1 ? 2u : 0u)) << ((uint32_t)at & 31u));
+                        }
+                    } else if (fe < 8u || found) {
+                        if (sub == 0 && found == (MODE == HJ_MODE_SEMI)) {
+                            acc_n += 1; acc_k += key[i]; acc_o += val[i];
+                            if (MATERIALIZE) em.emit(key[i], val[i], 0u);
+                        }
+                    }
+                    if constexpr (LEFTISH) {
+                        if (UNIQUE) got = got || found;
+                        else {
+                            uint32_t any = (m0 || m1) ? 1u : 0u;                // a match anywhere in the quad's line
+                            any |= quad_perm<0xB1>(any);
+                            any |= quad_perm<0x4E>(any);
+                            got = got || any != 0u;
+                        }
+                        if ((fe < 8u || (UNIQUE && found)) && !got && sub == 0) {
+                            acc_n += 1; acc_k += key[i]; acc_o += val[i];
+                            if (MATERIALIZE) em.emit(key[i], val[i], HJGPU_NULL_VAL);
+                        }
+                    }
+                    if (fe < 8u || (UNIQUE && found)) break;            // the walk ends at the first empty bucket (UNIQUE: first match)
+                    if (++ln[i] == lines) ln[i] = 0;                    // full line: the walk goes on in the next one
+                    q[i] = t4[4 * ln[i] + sub];
+                }
+            }
+        }
+    }
+    if (MATERIALIZE) hj_leave_cursor(a.final_offsets, wave_cursor);
+    // (hj_add_to_result, written out: as a call it reorders two register moves at the head of the semi- / anti-join instances' loop)
+    acc_n = wave_reduce_sum(acc_n); acc_k = wave_reduce_sum(acc_k);
+    acc_o = wave_reduce_sum(acc_o); acc_i = wave_reduce_sum(acc_i);
+    if (hj_lane() == 0) { red[0][wave] = acc_n; red[1][wave] = acc_k; red[2][wave] = acc_o; red[3][wave] = acc_i; }
+    __syncthreads();
+    if (threadIdx.x < 4) {
+        u64 s = 0;
+        for (int i = 0; i < NW; ++i) s += red[threadIdx.x][i];
+        if (s) atomicAdd(reinterpret_cast<u64 *>(a.result) + threadIdx.x, s);
+    }
+}
+
+// The inner join's line walk, a body of its own ("One body per probe walk"): npj_probe_line_body without the modes.
 template <bool MATERIALIZE, bool UNIQUE>
 __global__ __launch_bounds__(NPJ_PROBE_BLOCK) void npj_probe_line_kernel(NpjProbeArgs a)
 {
@@ -364,16 +501,9 @@ __global__ __launch_bounds__(NPJ_PROBE_BLOCK) void npj_probe_line_kernel(NpjProb
     __shared__ u64 wave_cursor[NW];
     const int wave = threadIdx.x >> 6;
     Emitter em;
-    em.init(a.ok, a.oov, a.oiv, a.block_size, a.block_limit, a.block_counter, a.overflow,
-            &wave_cursor[wave]);
-    if (hj_lane() == 0) wave_cursor[wave] = HJ_NO_CURSOR;
-
-    const uint32_t a0 = (uint32_t)(((uintptr_t)a.keys >> 2) & 3);
-    const uint4 *__restrict__ k4 = reinterpret_cast<const uint4 *>(a.keys - a0);
-    const uint4 *__restrict__ v4 = reinterpret_cast<const uint4 *>(a.vals - a0);
-    const u64 gb = a0, ge = a0 + a.n;
-    const u64 nvec = (ge + 3) >> 2;
-    const u64 stride = (u64)gridDim.x * NPJ_PROBE_BLOCK;
+    const NpjProbeColumns c = npj_probe_begin(a, em, wave_cursor);
+    const uint4 *__restrict__ k4 = c.k4, *__restrict__ v4 = c.v4;
+    const u64 gb = c.gb, ge = c.ge, nvec = c.nvec, stride = c.stride;
     const uint4 *__restrict__ t4 = reinterpret_cast<const uint4 *>(a.table);
     const u64 lines = a.buckets >> 3;
     const uint32_t factor = a.factor;
@@ -446,149 +576,7 @@ __global__ __launch_bounds__(NPJ_PROBE_BLOCK) void npj_probe_line_kernel(NpjProb
             }
         }
     }
-    if (MATERIALIZE && hj_lane() == 0)
-        hj_store(&a.final_offsets[(u64)blockIdx.x * NW + wave], wave_cursor[wave]);
-    acc_n = wave_reduce_sum(acc_n); acc_k = wave_reduce_sum(acc_k);
-    acc_o = wave_reduce_sum(acc_o); acc_i = wave_reduce_sum(acc_i);
-    if (hj_lane() == 0) { red[0][wave] = acc_n; red[1][wave] = acc_k; red[2][wave] = acc_o; red[3][wave] = acc_i; }
-    __syncthreads();
-    if (threadIdx.x < 4) {
-        u64 s = 0;
-        for (int i = 0; i < NW; ++i) s += red[threadIdx.x][i];
-        if (s) atomicAdd(reinterpret_cast<u64 *>(a.result) + threadIdx.x, s);
-    }
-}
-
-// Semi- / anti-join and left outer join probes (HJGPU_FLAG_SEMI / _ANTI / _LEFT_OUTER).  The inner-join kernels above stay as they are
-// (their machine code is the library's yardstick); this body is their walk with a compile-time MODE, instantiated for the new modes only.
-// MODE (HJ_MODE_*): semi- / anti-join (npj_exists_line_kernel) - lane 0 of the quad reports the tuple when its walk ends: on a match
-// (`found`, SEMI) or on an empty bucket without one (ANTI); left outer join (npj_outer_line_kernel) - the inner join's rows, and lane 0
-// of the quad reports a NULL row when the walk ends without any match of the quad in any of its lines.
-template <bool MATERIALIZE, bool UNIQUE, int MODE>
-__device__ __forceinline__ void npj_mode_line_body(NpjProbeArgs a)
-{
-    constexpr bool LEFTISH = MODE == HJ_MODE_LEFT_OUTER || MODE == HJ_MODE_FULL_OUTER;     // as in npj_mode_body
-    constexpr bool KEEPB = MODE == HJ_MODE_RIGHT_OUTER || MODE == HJ_MODE_FULL_OUTER;
-    static_assert(MODE != HJ_MODE_INNER && (UNIQUE || LEFTISH || KEEPB) && !(UNIQUE && KEEPB), "semi- and anti-joins walk to the first match");
-    constexpr int NW = NPJ_PROBE_BLOCK / 64;
-    constexpr int B = 4;                                   // lines in flight per quad
-    __shared__ u64 red[4][NW];
-    __shared__ u64 wave_cursor[NW];
-    const int wave = threadIdx.x >> 6;
-    EmitterT<true, (MODE == HJ_MODE_SEMI || MODE == HJ_MODE_ANTI) ? 2 : 3> em;
-    em.init(a.ok, a.oov, a.oiv, a.block_size, a.block_limit, a.block_counter, a.overflow,
-            &wave_cursor[wave]);
-    if (hj_lane() == 0) wave_cursor[wave] = HJ_NO_CURSOR;
-
-    const uint32_t a0 = (uint32_t)(((uintptr_t)a.keys >> 2) & 3);
-    const uint4 *__restrict__ k4 = reinterpret_cast<const uint4 *>(a.keys - a0);
-    const uint4 *__restrict__ v4 = reinterpret_cast<const uint4 *>(a.vals - a0);
-    const u64 gb = a0, ge = a0 + a.n;
-    const u64 nvec = (ge + 3) >> 2;
-    const u64 stride = (u64)gridDim.x * NPJ_PROBE_BLOCK;
-    const uint4 *__restrict__ t4 = reinterpret_cast<const uint4 *>(a.table);
-    const u64 lines = a.buckets >> 3;
-    const uint32_t factor = a.factor;
-    const uint32_t sub = threadIdx.x & 3;                  // my quarter of the line: buckets 2*sub, 2*sub + 1
-
-    u64 acc_n = 0, acc_k = 0, acc_o = 0, acc_i = 0;
-    // left outer join: the current walk has found a match (quad-uniform).  Declared here, set only by the left outer instances: an
-    // initialised local beside the walk reorders two register moves of the semi- / anti-join instances
-    bool got;
-    // whole waves iterate together (the quad exchanges below need all four lanes)
-    for (u64 v0 = (u64)blockIdx.x * NPJ_PROBE_BLOCK + (threadIdx.x & ~63u); v0 < nvec; v0 += stride) {
-        const u64 v = v0 + hj_lane();
-        uint4 kk = make_uint4(0, 0, 0, 0), vv = kk;
-        if (v < nvec) { kk = k4[v]; vv = v4[v]; }
-        const u64 g = v << 2;
-        const uint32_t kc[4] = {kk.x, kk.y, kk.z, kk.w}, vc[4] = {vv.x, vv.y, vv.z, vv.w};
-        uint32_t okc[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) okc[j] = (v < nvec && g + j >= gb && g + j < ge) ? 1u : 0u;
-
-        // the quad's 16 tuples (4 lanes x 4 components), B at a time
-#pragma unroll
-        for (int r0 = 0; r0 < 16; r0 += B) {
-            uint32_t key[B], val[B];
-            bool act[B];
-            u64 ln[B];
-            uint4 q[B];
-#pragma unroll
-            for (int i = 0; i < B; ++i) {
-                const int r = r0 + i, comp = r & 3;                     // static after unrolling
-                // the tuple's owner is lane r / 4 of the quad: broadcast its key, payload and validity
-                if (r < 4) { key[i] = quad_perm<0x00>(kc[comp]); val[i] = quad_perm<0x00>(vc[comp]); act[i] = quad_perm<0x00>(okc[comp]) != 0; }
-                else if (r < 8) { key[i] = quad_perm<0x55>(kc[comp]); val[i] = quad_perm<0x55>(vc[comp]); act[i] = quad_perm<0x55>(okc[comp]) != 0; }
-                else if (r < 12) { key[i] = quad_perm<0xAA>(kc[comp]); val[i] = quad_perm<0xAA>(vc[comp]); act[i] = quad_perm<0xAA>(okc[comp]) != 0; }
-                else { key[i] = quad_perm<0xFF>(kc[comp]); val[i] = quad_perm<0xFF>(vc[comp]); act[i] = quad_perm<0xFF>(okc[comp]) != 0; }
-                ln[i] = npj_bucket(key[i], factor, lines);
-                q[i] = make_uint4(0, 0, 0, 0);
-                if (act[i]) {
-                    q[i] = t4[4 * ln[i] + sub];                         // 4 lanes x 16 bytes = the key's line
-                }
-            }
-#pragma unroll
-            for (int i = 0; i < B; ++i) {
-                if constexpr (LEFTISH) got = false;
-                while (act[i]) {                                        // uniform inside the quad
-                    // first empty bucket of the line, over the quad
-                    uint32_t fe = q[i].x == 0u ? 2 * sub : (q[i].z == 0u ? 2 * sub + 1 : 8u);
-                    fe = min(fe, quad_perm<0xB1>(fe));                  // lanes 0<->1, 2<->3
-                    fe = min(fe, quad_perm<0x4E>(fe));                  // lanes 0<->2, 1<->3
-                    bool m0 = q[i].x == key[i] && 2 * sub < fe;
-                    bool m1 = q[i].z == key[i] && 2 * sub + 1 < fe;
-                    bool found = false;                                 // UNIQUE: some lane of the quad holds a match
-                    if (UNIQUE) {
-                        // only the FIRST match of the walk counts: the lowest matching bucket of the line
-                        uint32_t fm = m0 ? 2 * sub : (m1 ? 2 * sub + 1 : 8u);
-                        const uint32_t mine = fm;
-                        fm = min(fm, quad_perm<0xB1>(fm));
-                        fm = min(fm, quad_perm<0x4E>(fm));
-                        found = fm < 8u;
-                        m0 = m0 && mine == fm && fm == 2 * sub;
-                        m1 = m1 && mine == fm && fm == 2 * sub + 1;
-                    }
-                    if constexpr (MODE == HJ_MODE_INNER || LEFTISH || KEEPB) {
-                        const uint32_t m = (m0 ? 1u : 0u) + (m1 ? 1u : 0u);
-                        acc_n += m; acc_k += (u64)key[i] * m; acc_o += (u64)val[i] * m;
-                        acc_i += (m0 ? q[i].y : 0u); acc_i += (m1 ? q[i].w : 0u);
-                        if (MATERIALIZE) {
-                            if (m0) em.emit(key[i], val[i], q[i].y);
-                            if (m1) em.emit(key[i], val[i], q[i].w);
-                        }
-                        if constexpr (KEEPB) {
-                            // my two buckets of the line: 8 * line + 2 * sub and the next one - an even index, both bits in one word
-                            const u64 at = 8 * ln[i] + 2 * sub;
-                            if (m0 || m1) atomicOr(&a.bucket_bits[at >> 5], ((m0 ? 1u : 0u) | (m1 ? 2u : 0u)) << ((uint32_t)at & 31u));
-                        }
-                    } else if (fe < 8u || found) {
-                        if (sub == 0 && found == (MODE == HJ_MODE_SEMI)) {
-                            acc_n += 1; acc_k += key[i]; acc_o += val[i];
-                            if (MATERIALIZE) em.emit(key[i], val[i], 0u);
-                        }
-                    }
-                    if constexpr (LEFTISH) {
-                        if (UNIQUE) got = got || found;
-                        else {
-                            uint32_t any = (m0 || m1) ? 1u : 0u;                // a match anywhere in the quad's line
-                            any |= quad_perm<0xB1>(any);
-                            any |= quad_perm<0x4E>(any);
-                            got = got || any != 0u;
-                        }
-                        if ((fe < 8u || (UNIQUE && found)) && !got && sub == 0) {
-                            acc_n += 1; acc_k += key[i]; acc_o += val[i];
-                            if (MATERIALIZE) em.emit(key[i], val[i], HJGPU_NULL_VAL);
-                        }
-                    }
-                    if (fe < 8u || (UNIQUE && found)) break;            // the walk ends at the first empty bucket (UNIQUE: first match)
-                    if (++ln[i] == lines) ln[i] = 0;                    // full line: the walk goes on in the next one
-                    q[i] = t4[4 * ln[i] + sub];
-                }
-            }
-        }
-    }
-    if (MATERIALIZE && hj_lane() == 0)
-        hj_store(&a.final_offsets[(u64)blockIdx.x * NW + wave], wave_cursor[wave]);
+    if (MATERIALIZE) hj_leave_cursor(a.final_offsets, wave_cursor);
     acc_n = wave_reduce_sum(acc_n); acc_k = wave_reduce_sum(acc_k);
     acc_o = wave_reduce_sum(acc_o); acc_i = wave_reduce_sum(acc_i);
     if (hj_lane() == 0) { red[0][wave] = acc_n; red[1][wave] = acc_k; red[2][wave] = acc_o; red[3][wave] = acc_i; }
@@ -603,13 +591,13 @@ __device__ __forceinline__ void npj_mode_line_body(NpjProbeArgs a)
 template <bool MATERIALIZE, int MODE>
 __global__ __launch_bounds__(NPJ_PROBE_BLOCK) void npj_exists_line_kernel(NpjProbeArgs a)
 {
-    npj_mode_line_body<MATERIALIZE, true, MODE>(a);
+    npj_probe_line_body<MATERIALIZE, true, MODE>(a);
 }
 
 template <bool MATERIALIZE, bool UNIQUE>
 __global__ __launch_bounds__(NPJ_PROBE_BLOCK) void npj_outer_line_kernel(NpjProbeArgs a)
 {
-    npj_mode_line_body<MATERIALIZE, UNIQUE, HJ_MODE_LEFT_OUTER>(a);
+    npj_probe_line_body<MATERIALIZE, UNIQUE, HJ_MODE_LEFT_OUTER>(a);
 }
 
 // Right and full outer joins (HJGPU_FLAG_RIGHT_OUTER / _FULL_OUTER): the inner / left outer probes, marking every bucket they match
@@ -617,25 +605,25 @@ __global__ __launch_bounds__(NPJ_PROBE_BLOCK) void npj_outer_line_kernel(NpjProb
 template <bool GROUPED>
 __global__ __launch_bounds__(NPJ_PROBE_BLOCK) void npj_right_kernel(NpjProbeArgs a)
 {
-    npj_mode_body<GROUPED, false, HJ_MODE_RIGHT_OUTER>(a);
+    npj_probe_body<GROUPED, false, HJ_MODE_RIGHT_OUTER>(a);
 }
 
 template <bool GROUPED>
 __global__ __launch_bounds__(NPJ_PROBE_BLOCK) void npj_full_kernel(NpjProbeArgs a)
 {
-    npj_mode_body<GROUPED, false, HJ_MODE_FULL_OUTER>(a);
+    npj_probe_body<GROUPED, false, HJ_MODE_FULL_OUTER>(a);
 }
 
 template <bool MATERIALIZE>
 __global__ __launch_bounds__(NPJ_PROBE_BLOCK) void npj_right_line_kernel(NpjProbeArgs a)
 {
-    npj_mode_line_body<MATERIALIZE, false, HJ_MODE_RIGHT_OUTER>(a);
+    npj_probe_line_body<MATERIALIZE, false, HJ_MODE_RIGHT_OUTER>(a);
 }
 
 template <bool MATERIALIZE>
 __global__ __launch_bounds__(NPJ_PROBE_BLOCK) void npj_full_line_kernel(NpjProbeArgs a)
 {
-    npj_mode_line_body<MATERIALIZE, false, HJ_MODE_FULL_OUTER>(a);
+    npj_probe_line_body<MATERIALIZE, false, HJ_MODE_FULL_OUTER>(a);
 }
 
 // The tail of a right / full outer NPJ join, behind the probe with the probe's grid: scans the table (four buckets = 2 x 16 bytes and
@@ -643,7 +631,7 @@ __global__ __launch_bounds__(NPJ_PROBE_BLOCK) void npj_full_line_kernel(NpjProbe
 // (key, HJGPU_NULL_VAL, inner_val).  `resume`: the waves go on in the output blocks the probe's waves left open.
 __global__ __launch_bounds__(NPJ_PROBE_BLOCK) void npj_unmatched_kernel(NpjProbeArgs a, uint32_t resume)
 {
-    constexpr int NW = NPJ_PROBE_BLOCK / 64;
+    constexpr int NW = NPJ_PROBE_WAVES;
     __shared__ u64 red[3][NW];
     __shared__ u64 wave_cursor[NW];
     const int wave = threadIdx.x >> 6;
@@ -674,7 +662,8 @@ __global__ __launch_bounds__(NPJ_PROBE_BLOCK) void npj_unmatched_kernel(NpjProbe
             }
         }
     }
-    if (a.ok && hj_lane() == 0) hj_store(&a.final_offsets[(u64)blockIdx.x * NW + wave], wave_cursor[wave]);
+    if (a.ok) hj_leave_cursor(a.final_offsets, wave_cursor);
+    // (three sums, written out: the reduction as a call changes the schedule of this kernel, see hj_add_to_result)
     acc_n = wave_reduce_sum(acc_n); acc_k = wave_reduce_sum(acc_k); acc_i = wave_reduce_sum(acc_i);
     if (hj_lane() == 0) { red[0][wave] = acc_n; red[1][wave] = acc_k; red[2][wave] = acc_i; }
     __syncthreads();
@@ -700,50 +689,36 @@ int hj_npj_probe_grid(int cus, size_t n)
     return (int)blocks;
 }
 
+// The probe kernel of a join mode.  LINE: the line walk, else the bucket / group walk; X: the walk's first template argument
+// (MATERIALIZE / GROUPED); U: the first-match walk (semi- and anti-joins always, right and full outer joins never).
+typedef void (*NpjProbeKernel)(NpjProbeArgs);
+template <bool LINE, bool X, bool U>
+static NpjProbeKernel npj_probe_kernel_of(uint32_t mode)
+{
+    switch (mode) {
+    case HJ_MODE_SEMI: return LINE ? npj_exists_line_kernel<X, HJ_MODE_SEMI> : npj_exists_kernel<X, HJ_MODE_SEMI>;
+    case HJ_MODE_ANTI: return LINE ? npj_exists_line_kernel<X, HJ_MODE_ANTI> : npj_exists_kernel<X, HJ_MODE_ANTI>;
+    case HJ_MODE_LEFT_OUTER: return LINE ? npj_outer_line_kernel<X, U> : npj_outer_kernel<X, U>;
+    case HJ_MODE_RIGHT_OUTER: return LINE ? npj_right_line_kernel<X> : npj_right_kernel<X>;
+    case HJ_MODE_FULL_OUTER: return LINE ? npj_full_line_kernel<X> : npj_full_kernel<X>;
+    default: return LINE ? npj_probe_line_kernel<X, U> : npj_probe_kernel<X, U>;
+    }
+}
+
 int hj_launch_npj_probe(const NpjProbeArgs &a, int cus, hipStream_t stream, int *grid_out)
 {
     const int grid = hj_npj_probe_grid(cus, a.n);
     if (grid_out) *grid_out = grid;
     if (hj_mode_keeps_build(a.mode) && (a.unique || !a.bucket_bits)) return HJGPU_EINVAL;
-    if (a.line_hash) {
-        if (a.buckets % 8 != 0 || ((uintptr_t)a.table & 63)) return HJGPU_EINVAL;
-        if (a.mode == HJ_MODE_RIGHT_OUTER && a.ok) hipLaunchKernelGGL((npj_right_line_kernel<true>), dim3(grid), dim3(NPJ_PROBE_BLOCK), 0, stream, a);
-        else if (a.mode == HJ_MODE_RIGHT_OUTER) hipLaunchKernelGGL((npj_right_line_kernel<false>), dim3(grid), dim3(NPJ_PROBE_BLOCK), 0, stream, a);
-        else if (a.mode == HJ_MODE_FULL_OUTER && a.ok) hipLaunchKernelGGL((npj_full_line_kernel<true>), dim3(grid), dim3(NPJ_PROBE_BLOCK), 0, stream, a);
-        else if (a.mode == HJ_MODE_FULL_OUTER) hipLaunchKernelGGL((npj_full_line_kernel<false>), dim3(grid), dim3(NPJ_PROBE_BLOCK), 0, stream, a);
-        else
-        if (a.mode == HJ_MODE_LEFT_OUTER && a.ok && a.unique) hipLaunchKernelGGL((npj_outer_line_kernel<true, true>), dim3(grid), dim3(NPJ_PROBE_BLOCK), 0, stream, a);
-        else if (a.mode == HJ_MODE_LEFT_OUTER && a.ok) hipLaunchKernelGGL((npj_outer_line_kernel<true, false>), dim3(grid), dim3(NPJ_PROBE_BLOCK), 0, stream, a);
-        else if (a.mode == HJ_MODE_LEFT_OUTER && a.unique) hipLaunchKernelGGL((npj_outer_line_kernel<false, true>), dim3(grid), dim3(NPJ_PROBE_BLOCK), 0, stream, a);
-        else if (a.mode == HJ_MODE_LEFT_OUTER) hipLaunchKernelGGL((npj_outer_line_kernel<false, false>), dim3(grid), dim3(NPJ_PROBE_BLOCK), 0, stream, a);
-        else if (a.mode == HJ_MODE_SEMI && a.ok) hipLaunchKernelGGL((npj_exists_line_kernel<true, HJ_MODE_SEMI>), dim3(grid), dim3(NPJ_PROBE_BLOCK), 0, stream, a);
-        else if (a.mode == HJ_MODE_SEMI) hipLaunchKernelGGL((npj_exists_line_kernel<false, HJ_MODE_SEMI>), dim3(grid), dim3(NPJ_PROBE_BLOCK), 0, stream, a);
-        else if (a.mode == HJ_MODE_ANTI && a.ok) hipLaunchKernelGGL((npj_exists_line_kernel<true, HJ_MODE_ANTI>), dim3(grid), dim3(NPJ_PROBE_BLOCK), 0, stream, a);
-        else if (a.mode == HJ_MODE_ANTI) hipLaunchKernelGGL((npj_exists_line_kernel<false, HJ_MODE_ANTI>), dim3(grid), dim3(NPJ_PROBE_BLOCK), 0, stream, a);
-        else if (a.ok && a.unique) hipLaunchKernelGGL((npj_probe_line_kernel<true, true>), dim3(grid), dim3(NPJ_PROBE_BLOCK), 0, stream, a);
-        else if (a.ok) hipLaunchKernelGGL((npj_probe_line_kernel<true, false>), dim3(grid), dim3(NPJ_PROBE_BLOCK), 0, stream, a);
-        else if (a.unique) hipLaunchKernelGGL((npj_probe_line_kernel<false, true>), dim3(grid), dim3(NPJ_PROBE_BLOCK), 0, stream, a);
-        else hipLaunchKernelGGL((npj_probe_line_kernel<false, false>), dim3(grid), dim3(NPJ_PROBE_BLOCK), 0, stream, a);
-        return hipGetLastError() == hipSuccess ? HJGPU_OK : HJGPU_EHIP;
-    }
+    if (a.line_hash && (a.buckets % 8 != 0 || ((uintptr_t)a.table & 63))) return HJGPU_EINVAL;
     const bool grouped = (a.buckets % 4 == 0) && (((uintptr_t)a.table & 31) == 0);
-    if (a.mode == HJ_MODE_RIGHT_OUTER && grouped) hipLaunchKernelGGL((npj_right_kernel<true>), dim3(grid), dim3(NPJ_PROBE_BLOCK), 0, stream, a);
-    else if (a.mode == HJ_MODE_RIGHT_OUTER) hipLaunchKernelGGL((npj_right_kernel<false>), dim3(grid), dim3(NPJ_PROBE_BLOCK), 0, stream, a);
-    else if (a.mode == HJ_MODE_FULL_OUTER && grouped) hipLaunchKernelGGL((npj_full_kernel<true>), dim3(grid), dim3(NPJ_PROBE_BLOCK), 0, stream, a);
-    else if (a.mode == HJ_MODE_FULL_OUTER) hipLaunchKernelGGL((npj_full_kernel<false>), dim3(grid), dim3(NPJ_PROBE_BLOCK), 0, stream, a);
-    else
-    if (a.mode == HJ_MODE_LEFT_OUTER && grouped && a.unique) hipLaunchKernelGGL((npj_outer_kernel<true, true>), dim3(grid), dim3(NPJ_PROBE_BLOCK), 0, stream, a);
-    else if (a.mode == HJ_MODE_LEFT_OUTER && grouped) hipLaunchKernelGGL((npj_outer_kernel<true, false>), dim3(grid), dim3(NPJ_PROBE_BLOCK), 0, stream, a);
-    else if (a.mode == HJ_MODE_LEFT_OUTER && a.unique) hipLaunchKernelGGL((npj_outer_kernel<false, true>), dim3(grid), dim3(NPJ_PROBE_BLOCK), 0, stream, a);
-    else if (a.mode == HJ_MODE_LEFT_OUTER) hipLaunchKernelGGL((npj_outer_kernel<false, false>), dim3(grid), dim3(NPJ_PROBE_BLOCK), 0, stream, a);
-    else if (a.mode == HJ_MODE_SEMI && grouped) hipLaunchKernelGGL((npj_exists_kernel<true, HJ_MODE_SEMI>), dim3(grid), dim3(NPJ_PROBE_BLOCK), 0, stream, a);
-    else if (a.mode == HJ_MODE_SEMI) hipLaunchKernelGGL((npj_exists_kernel<false, HJ_MODE_SEMI>), dim3(grid), dim3(NPJ_PROBE_BLOCK), 0, stream, a);
-    else if (a.mode == HJ_MODE_ANTI && grouped) hipLaunchKernelGGL((npj_exists_kernel<true, HJ_MODE_ANTI>), dim3(grid), dim3(NPJ_PROBE_BLOCK), 0, stream, a);
-    else if (a.mode == HJ_MODE_ANTI) hipLaunchKernelGGL((npj_exists_kernel<false, HJ_MODE_ANTI>), dim3(grid), dim3(NPJ_PROBE_BLOCK), 0, stream, a);
-    else if (grouped && a.unique) hipLaunchKernelGGL((npj_probe_kernel<true, true>), dim3(grid), dim3(NPJ_PROBE_BLOCK), 0, stream, a);
-    else if (grouped) hipLaunchKernelGGL((npj_probe_kernel<true, false>), dim3(grid), dim3(NPJ_PROBE_BLOCK), 0, stream, a);
-    else if (a.unique) hipLaunchKernelGGL((npj_probe_kernel<false, true>), dim3(grid), dim3(NPJ_PROBE_BLOCK), 0, stream, a);
-    else hipLaunchKernelGGL((npj_probe_kernel<false, false>), dim3(grid), dim3(NPJ_PROBE_BLOCK), 0, stream, a);
+    NpjProbeKernel kernel = nullptr;
+    hj_with_bool(a.line_hash != 0, [&](auto line) {
+        hj_with_bool(line ? a.ok != nullptr : grouped, [&](auto x) {
+            hj_with_bool(a.unique != 0, [&](auto u) { kernel = npj_probe_kernel_of<decltype(line)::value, decltype(x)::value, decltype(u)::value>(a.mode); });
+        });
+    });
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(NPJ_PROBE_BLOCK), 0, stream, a);
     return hipGetLastError() == hipSuccess ? HJGPU_OK : HJGPU_EHIP;
 }
 

@@ -7,8 +7,7 @@ import re
 
 import pytest
 
-from device_compile import compile_device
-from test_semi_anti_isa import instances, kernarg_bytes, _stores
+from device_compile import compile_device, instances, kernarg_bytes, _stores
 
 KERNELS = {"join_kernels.hip": ["outer_probe_kernel"], "npj_kernels.hip": ["npj_outer_kernel", "npj_outer_line_kernel"]}
 OIV = {"join_kernels.hip": 168, "npj_kernels.hip": 80}       # offsetof(JoinArgs, oiv), offsetof(NpjProbeArgs, oiv)

@@ -7,8 +7,7 @@ import re
 
 import pytest
 
-from device_compile import compile_device
-from test_semi_anti_isa import instances, kernarg_bytes, _stores
+from device_compile import compile_device, instances, kernarg_bytes, _stores
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # the probes that mark (PHJ / CPRA: table slots in LDS, then build rows in memory; NPJ: buckets in memory), and the tails that report

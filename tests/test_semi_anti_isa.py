@@ -5,20 +5,10 @@ import re
 
 import pytest
 
-from device_compile import compile_device
+from device_compile import compile_device, instances, kernarg_bytes, _stores
 
 MODES = {"1": "semi", "2": "anti"}
 KERNELS = {"join_kernels.hip": ["exists_probe_kernel"], "npj_kernels.hip": ["npj_exists_kernel", "npj_exists_line_kernel"]}
-STORE = re.compile(r"^(global|flat|buffer)_store_(\w+)")
-
-
-def instances(source, name):
-    text, res = compile_device(source)
-    out = {}
-    for m in re.finditer(r"^(_Z\d+%s\w+):\s*; @" % name, text, re.M):
-        body = text[m.end():text.find("s_endpgm", m.end())]
-        out[m.group(1)] = body
-    return out, res
 
 
 @pytest.mark.parametrize("source,name", [(s, n) for s, ns in KERNELS.items() for n in ns])
@@ -40,16 +30,6 @@ def test_no_scratch_no_spills(source, name):
     assert not bad, bad
 
 
-def _stores(body):
-    stores = collections.Counter()
-    for line in body.splitlines():
-        line = line.split(";")[0].strip()
-        hit = STORE.match(line)
-        if hit:
-            stores[(hit.group(2), " nt" in line)] += 1
-    return stores
-
-
 @pytest.mark.parametrize("source,name", [(s, n) for s, ns in KERNELS.items() for n in ns])
 def test_every_store_non_temporal(source, name):
     found, _ = instances(source, name)
@@ -57,18 +37,6 @@ def test_every_store_non_temporal(source, name):
     for k, body in found.items():
         plain = {s: n for s, n in _stores(body).items() if not s[1]}
         assert not plain, (k, plain)
-
-
-SLOAD = re.compile(r"s_load_dword(?:x(\d+))?\s+s\[?[\d:]+\]?,\s*s\[\d+:\d+\],\s*0x([0-9a-f]+)")
-
-
-def kernarg_bytes(body):
-    """the kernel-argument bytes the instance's scalar loads read (offsets are bytes into the argument struct)"""
-    covered = set()
-    for m in SLOAD.finditer(body):
-        off, n = int(m.group(2), 16), int(m.group(1) or 1)
-        covered.update(range(off, off + 4 * n))
-    return covered
 
 
 @pytest.mark.parametrize("source,inner_name,names,oiv", [

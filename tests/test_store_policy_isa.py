@@ -26,19 +26,18 @@ STORE = re.compile(r"^(global|flat|buffer)_store_\w+")
 
 
 def isa(source):
-    """{mangled kernel name: Counter{(store instruction, non-temporal?): n}} of csrc/<source>"""
-    from device_compile import compile_device
-    text = compile_device(source)[0]
+    """{mangled kernel name: Counter{(store instruction, non-temporal?): n}} of csrc/<source>
+    (keyed by the whole instruction name, global_store_dword ...; device_compile._stores keys by the width alone)"""
+    from device_compile import instances
     kernels = {}
-    for m in re.finditer(r"^(_Z\w+):\s*; @", text, re.M):
-        body = text[m.end():text.find("s_endpgm", m.end())]
+    for name, body in instances(source)[0].items():
         stores = collections.Counter()
         for line in body.splitlines():
             line = line.split(";")[0].strip()
             hit = STORE.match(line)
             if hit:
                 stores[(hit.group(0), " nt" in line)] += 1
-        kernels[m.group(1)] = stores
+        kernels[name] = stores
     return kernels
 
 

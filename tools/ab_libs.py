@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """A/B timing of two (or more) builds of libhjgpu.so INSIDE ONE PROCESS, interleaved, same relations:
-usage: python tools/ab_libs.py <a.so> <b.so> ... [--rounds R --reps K --inner N --outer N --algo phj]
-(variants: tools/build_variant.py).  Every join is checked against the analytic aggregates.
+usage: python tools/ab_libs.py <a.so> <b.so> ... [--rounds R --reps K --inner N --outer N --algo phj --option name=value]
+(variants: tools/build_variant.py).  Every join is checked against the analytic aggregates.  Per phase: median / lowest / highest ms.
 --sequential: K6's time depends on WHICH allocation holds its output (placement), so contexts that live
 side by side compare their workspaces' luck as much as their kernels.  In this mode only one measured context
 exists at a time: it is created (placement=1: the first allocation), timed and destroyed, round after round - the
@@ -26,13 +26,17 @@ def main():
     ap.add_argument("--no-check", action="store_true", help="timing experiments with deliberately wrong variants")
     ap.add_argument("--sequential", action="store_true", help="one measured context at a time, same allocations for all")
     ap.add_argument("--rows", action="store_true", help="materialise the result (three columns shared by all builds)")
+    ap.add_argument("--option", action="append", default=[], metavar="NAME=VALUE", help="a context option set on every build's context")
     a = ap.parse_args()
     import hash_join_codes_knl_amd as H
     from hash_join_codes_knl_amd import api
     def make(path):
         os.environ["HJGPU_LIBRARY"] = os.path.abspath(path)
         api._lib = None                      # the next context binds (and keeps) this build
-        return H.HjGpu(0)
+        c = H.HjGpu(0)
+        for opt in a.option:
+            c.set_option(*opt.split("=", 1))
+        return c
     ctxs = [make(a.libs[0])] if a.sequential else [make(path) for path in a.libs]
     hj = ctxs[0]                             # owns the relations
     ik, iv, ok, ov = hj.column(a.inner), hj.column(a.inner), hj.column(a.outer), hj.column(a.outer)
@@ -68,7 +72,7 @@ def main():
                     for ph in phases:
                         data[path][ph].append(st[ph])
     for path in a.libs:
-        print("%-28s" % os.path.basename(path), " ".join("%s %.3f/%.3f |" % (ph[3:], statistics.median(x), min(x))
+        print("%-28s" % os.path.basename(path), " ".join("%s %.3f/%.3f/%.3f |" % (ph[3:], statistics.median(x), min(x), max(x))
                                                           for ph, x in data[path].items() if max(x) > 0), flush=True)
 
 
