@@ -23,6 +23,8 @@ FLAG_ANTI = 4       # HJGPU_FLAG_ANTI: one row (key, outer_val) per probe tuple 
 FLAG_LEFT_OUTER = 8     # HJGPU_FLAG_LEFT_OUTER: every match, plus one row (key, outer_val, NULL_VAL) per probe tuple without one
 FLAG_RIGHT_OUTER = 16   # HJGPU_FLAG_RIGHT_OUTER: every match, plus one row (key, NULL_VAL, inner_val) per build tuple without one
 FLAG_FULL_OUTER = FLAG_LEFT_OUTER | FLAG_RIGHT_OUTER     # HJGPU_FLAG_FULL_OUTER: both kinds of NULL rows
+FLAG_RIGHT_SEMI = 32    # HJGPU_FLAG_RIGHT_SEMI: one row (key, inner_val) per build tuple whose key a probe tuple carries
+FLAG_RIGHT_ANTI = 64    # HJGPU_FLAG_RIGHT_ANTI: one row (key, inner_val) per build tuple whose key no probe tuple carries
 NULL_VAL = 0xFFFFFFFF   # HJGPU_NULL_VAL: the value on the side without a match in an outer join's NULL row
 
 EXPORTS = [

@@ -184,14 +184,18 @@ struct ScatterArgs {
     uint32_t *claim_overflow;       // device flag: an optimistic region (pass 1 claimed, or pass 2 into claimed final regions) was full
 };
 
-// What a join reports (HJGPU_FLAG_SEMI / _ANTI / _LEFT_OUTER / _RIGHT_OUTER, derived once by hj_join_mode): every match of a probe tuple (inner join),
-// ONE row (key, outer_val) per probe tuple that has a match (semi-join) / that has none (anti-join), or every match plus ONE row
-// (key, outer_val, HJGPU_NULL_VAL) per probe tuple that has none (left outer join).
+// What a join reports (HJGPU_FLAG_SEMI / _ANTI / _LEFT_OUTER / _RIGHT_OUTER / _RIGHT_SEMI / _RIGHT_ANTI, derived once by hj_join_mode): every match of a
+// probe tuple (inner join), ONE row (key, outer_val) per probe tuple that has a match (semi-join) / that has none (anti-join), every match plus ONE row
+// (key, outer_val, HJGPU_NULL_VAL) per probe tuple that has none (left outer join), or ONE row (key, inner_val) per BUILD tuple whose key
+// a probe tuple carries (right semi-join) / no probe tuple carries (right anti-join).
 enum : uint32_t { HJ_MODE_INNER = 0, HJ_MODE_SEMI = 1, HJ_MODE_ANTI = 2, HJ_MODE_LEFT_OUTER = 3, HJ_MODE_RIGHT_OUTER = 4, HJ_MODE_FULL_OUTER = 5,
-                  HJ_MODE_MARK = 6 /* kernels only: the marking launch of a full outer join's multi-fill items, never a join's mode */ };
+                  HJ_MODE_MARK = 6 /* kernels only: a launch that marks and reports nothing - the multi-fill items of a full outer join, every
+                                      probe of a right semi- / anti-join -, never a join's mode */,
+                  HJ_MODE_RIGHT_SEMI = 7, HJ_MODE_RIGHT_ANTI = 8 };
 inline uint32_t hj_join_mode(uint32_t flags)
 {
-    return (flags & HJGPU_FLAG_SEMI) ? HJ_MODE_SEMI : (flags & HJGPU_FLAG_ANTI) ? HJ_MODE_ANTI
+    return (flags & HJGPU_FLAG_RIGHT_SEMI) ? HJ_MODE_RIGHT_SEMI : (flags & HJGPU_FLAG_RIGHT_ANTI) ? HJ_MODE_RIGHT_ANTI
+         : (flags & HJGPU_FLAG_SEMI) ? HJ_MODE_SEMI : (flags & HJGPU_FLAG_ANTI) ? HJ_MODE_ANTI
          : (flags & HJGPU_FLAG_FULL_OUTER) == HJGPU_FLAG_FULL_OUTER ? HJ_MODE_FULL_OUTER
          : (flags & HJGPU_FLAG_RIGHT_OUTER) ? HJ_MODE_RIGHT_OUTER
          : (flags & HJGPU_FLAG_LEFT_OUTER) ? HJ_MODE_LEFT_OUTER : HJ_MODE_INNER;
@@ -202,7 +206,15 @@ inline bool hj_mode_keeps_unmatched(uint32_t mode) { return mode == HJ_MODE_ANTI
 // (PHJ / CPRA: JoinArgs::build_bits) or bucket (NPJ: NpjProbeArgs::bucket_bits) - and a tail kernel behind them reports the rest, so a
 // partition / group / join without probe rows still has build rows to report
 inline bool hj_mode_keeps_build(uint32_t mode) { return mode == HJ_MODE_RIGHT_OUTER || mode == HJ_MODE_FULL_OUTER; }
-// what such a join is when one side is empty: without build rows a full outer join is the left outer join (a right outer join the inner
+// the modes whose rows are build tuples, (key, inner_val), and nothing else (right semi- and anti-joins): every probe only marks (HJ_MODE_MARK),
+// the tail kernel reports the marked rows / buckets (right semi-join) or the clear ones (right anti-join).  d_outer_vals is neither read
+// nor written
+inline bool hj_mode_reports_build(uint32_t mode) { return mode == HJ_MODE_RIGHT_SEMI || mode == HJ_MODE_RIGHT_ANTI; }
+// the modes with marks and a tail kernel: the bitmap is allocated, zeroed per join (and per group), and the tail runs behind the probes
+inline bool hj_mode_marks_build(uint32_t mode) { return hj_mode_keeps_build(mode) || hj_mode_reports_build(mode); }
+// the modes with rows to report where there are build rows and no probe rows (a join, a group): the tail alone.  Not the right semi-join
+inline bool hj_mode_build_alone(uint32_t mode) { return hj_mode_keeps_build(mode) || mode == HJ_MODE_RIGHT_ANTI; }
+// what such a join is when one side is empty (right semi- and anti-joins stay what they are: no build rows, no rows): without build rows a full outer join is the left outer join (a right outer join the inner
 // join: no rows), without probe rows both are the right outer join (the tail alone)
 inline uint32_t hj_mode_for_sides(uint32_t mode, bool inner_rows)
 {
@@ -259,6 +271,10 @@ struct JoinArgs {
     uint32_t *build_bits;
     u64 *work_counter3;                  // full outer joins: the work counter of the launch that marks for the multi-fill items (mark_probe_kernel)
 };
+// The tail of a right semi- / anti-join (build_rows_kernel), launched like hj_launch_build_unmatched: every row of the partitioned build array
+// whose bit in a.build_bits is set (a.mode == HJ_MODE_RIGHT_SEMI) / clear (HJ_MODE_RIGHT_ANTI) leaves as (key, inner_val) - a.oiv is the
+// second column, a.oov is not touched - and is added to count / sum_keys / sum_inner_vals.
+int hj_launch_build_rows(const JoinArgs &a, const HjTuning &t, int cus, hipStream_t stream);
 // The tail of a right / full outer join (build_unmatched_kernel), behind the join's launches on the same stream and with the join's grid:
 // every row of the partitioned build array (pieces roff / rend of `a`) whose bit in a.build_bits is clear leaves as (key, HJGPU_NULL_VAL,
 // inner_val) and is added to count / sum_keys / sum_inner_vals.  Wave w of workgroup b goes on in the output block that wave left open.
@@ -405,11 +421,14 @@ struct NpjProbeArgs {
     u64 *block_counter;
     u64 *final_offsets;
     uint32_t *overflow;
-    uint32_t *bucket_bits;               // right / full outer joins: one bit per bucket, zeroed per join; the probes OR in every bucket they match
+    uint32_t *bucket_bits;               // the modes that mark (hj_mode_marks_build): one bit per bucket, zeroed per join; the probes OR in every bucket they match
 };
 // The tail of a right / full outer NPJ join (npj_unmatched_kernel), with the probe's grid (`grid`; its waves go on in the probe's open
 // output blocks when `resume`): every tuple of the table whose bucket's bit is clear leaves as (key, HJGPU_NULL_VAL, inner_val)
 int hj_launch_npj_unmatched(const NpjProbeArgs &a, int grid, bool resume, hipStream_t stream);
+// The tail of a right semi- / anti-join (npj_rows_kernel): every tuple of the table whose bucket's bit is set (a.mode == HJ_MODE_RIGHT_SEMI) /
+// clear (HJ_MODE_RIGHT_ANTI) leaves as (key, inner_val), a.oiv the second column.  No probe has reported anything: no open blocks to resume
+int hj_launch_npj_rows(const NpjProbeArgs &a, int grid, hipStream_t stream);
 int hj_launch_npj_probe(const NpjProbeArgs &a, int cus, hipStream_t stream, int *grid_out);
 
 // K9: compact the per-wave partially filled tail blocks (npj.cpp:475-514).

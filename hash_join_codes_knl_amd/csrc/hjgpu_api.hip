@@ -361,6 +361,12 @@ int setup_output(hjgpu_ctx *ctx, const hjgpu_output *out, uint32_t workers, u64 
     if (hj_mode_keeps_build(mode) && (!out->d_outer_vals || !out->d_inner_vals))
         return fail(ctx, HJGPU_EINVAL, mode == HJ_MODE_FULL_OUTER ? "HJGPU_FLAG_FULL_OUTER: rows have three columns, d_outer_vals and d_inner_vals are both required"
                                                                   : "HJGPU_FLAG_RIGHT_OUTER: rows have three columns, d_outer_vals and d_inner_vals are both required");
+    // (right semi- and anti-join rows are build tuples, (key, inner_val): d_outer_vals may be NULL, it is neither read nor written)
+    if (hj_mode_reports_build(mode)) {
+        if (!out->d_inner_vals)
+            return fail(ctx, HJGPU_EINVAL, mode == HJ_MODE_RIGHT_SEMI ? "HJGPU_FLAG_RIGHT_SEMI: rows are (key, inner_val), d_inner_vals is required"
+                                                                      : "HJGPU_FLAG_RIGHT_ANTI: rows are (key, inner_val), d_inner_vals is required");
+    } else
     if (!out->d_outer_vals || (!out->d_inner_vals && !hj_mode_rows2(mode))) return fail(ctx, HJGPU_EINVAL, "output columns");
     u64 bs = out->block_size ? out->block_size : 65536;
     if (bs < 256 || (bs & (bs - 1))) return fail(ctx, HJGPU_EINVAL, "block_size must be a power of two >= 256");
@@ -499,6 +505,20 @@ void join_output(const hjgpu_ctx *ctx, JoinArgs &ja, const hjgpu_output *out, u6
 
 int check_join_mode(hjgpu_ctx *ctx, uint32_t flags)
 {
+    if (flags & (HJGPU_FLAG_RIGHT_SEMI | HJGPU_FLAG_RIGHT_ANTI)) {
+        // (HJGPU_FLAG_UNIQUE / option "unique" beside them is ignored: no row depends on which copy of a build key a walk finds)
+        const char *mine = (flags & HJGPU_FLAG_RIGHT_SEMI) ? "HJGPU_FLAG_RIGHT_SEMI" : "HJGPU_FLAG_RIGHT_ANTI";
+        const char *other = (flags & HJGPU_FLAG_SEMI) ? "HJGPU_FLAG_SEMI" : (flags & HJGPU_FLAG_ANTI) ? "HJGPU_FLAG_ANTI"
+                          : (flags & HJGPU_FLAG_FULL_OUTER) == HJGPU_FLAG_FULL_OUTER ? "HJGPU_FLAG_FULL_OUTER"
+                          : (flags & HJGPU_FLAG_LEFT_OUTER) ? "HJGPU_FLAG_LEFT_OUTER" : (flags & HJGPU_FLAG_RIGHT_OUTER) ? "HJGPU_FLAG_RIGHT_OUTER"
+                          : ((flags & HJGPU_FLAG_RIGHT_SEMI) && (flags & HJGPU_FLAG_RIGHT_ANTI)) ? "HJGPU_FLAG_RIGHT_ANTI" : nullptr;
+        if (other) {
+            char what[200];
+            snprintf(what, sizeof(what), "%s | %s: a right semi- or anti-join reports build tuples only; it is no other kind of join beside that", mine, other);
+            return fail(ctx, HJGPU_EINVAL, what);
+        }
+        return HJGPU_OK;
+    }
     if ((flags & HJGPU_FLAG_SEMI) && (flags & HJGPU_FLAG_ANTI))
         return fail(ctx, HJGPU_EINVAL, "HJGPU_FLAG_SEMI | HJGPU_FLAG_ANTI: a join is a semi-join or an anti-join, not both");
     if (flags & HJGPU_FLAG_RIGHT_OUTER) {
@@ -522,14 +542,16 @@ int check_join_mode(hjgpu_ctx *ctx, uint32_t flags)
 
 static const char *join_mode_flag_name(uint32_t flags)
 {
-    return (flags & HJGPU_FLAG_SEMI) ? "HJGPU_FLAG_SEMI" : (flags & HJGPU_FLAG_ANTI) ? "HJGPU_FLAG_ANTI"
+    return (flags & HJGPU_FLAG_RIGHT_SEMI) ? "HJGPU_FLAG_RIGHT_SEMI" : (flags & HJGPU_FLAG_RIGHT_ANTI) ? "HJGPU_FLAG_RIGHT_ANTI"
+         : (flags & HJGPU_FLAG_SEMI) ? "HJGPU_FLAG_SEMI" : (flags & HJGPU_FLAG_ANTI) ? "HJGPU_FLAG_ANTI"
          : (flags & HJGPU_FLAG_FULL_OUTER) == HJGPU_FLAG_FULL_OUTER ? "HJGPU_FLAG_FULL_OUTER"
          : (flags & HJGPU_FLAG_RIGHT_OUTER) ? "HJGPU_FLAG_RIGHT_OUTER" : "HJGPU_FLAG_LEFT_OUTER";
 }
 
 int refuse_join_mode(hjgpu_ctx *ctx, uint32_t flags, const char *entry)
 {
-    if (!(flags & (HJGPU_FLAG_SEMI | HJGPU_FLAG_ANTI | HJGPU_FLAG_LEFT_OUTER | HJGPU_FLAG_RIGHT_OUTER))) return HJGPU_OK;
+    if (!(flags & (HJGPU_FLAG_SEMI | HJGPU_FLAG_ANTI | HJGPU_FLAG_LEFT_OUTER | HJGPU_FLAG_RIGHT_OUTER | HJGPU_FLAG_RIGHT_SEMI | HJGPU_FLAG_RIGHT_ANTI)))
+        return HJGPU_OK;
     char what[256];
     snprintf(what, sizeof(what), "%s: %s is not supported here (semi-, anti- and outer joins: hjgpu_phj, hjgpu_cpra, hjgpu_npj, "
              "their _async forms and hjgpu_phj_overlapped_async)", entry, join_mode_flag_name(flags));
@@ -542,13 +564,17 @@ static int refuse_mode_geometry(hjgpu_ctx *ctx, uint32_t mode)
     char what[160];
     snprintf(what, sizeof(what), "HJGPU_FLAG_%s: the join_cfg geometry of this context has no _UNIQUE instance (geometries with one: 512,13,2 and "
              "1024,14,2)", mode == HJ_MODE_SEMI ? "SEMI" : mode == HJ_MODE_ANTI ? "ANTI" : mode == HJ_MODE_LEFT_OUTER ? "LEFT_OUTER"
-             : mode == HJ_MODE_RIGHT_OUTER ? "RIGHT_OUTER" : mode == HJ_MODE_FULL_OUTER ? "FULL_OUTER" : "UNIQUE");
+             : mode == HJ_MODE_RIGHT_OUTER ? "RIGHT_OUTER" : mode == HJ_MODE_FULL_OUTER ? "FULL_OUTER"
+             : mode == HJ_MODE_RIGHT_SEMI ? "RIGHT_SEMI" : mode == HJ_MODE_RIGHT_ANTI ? "RIGHT_ANTI" : "UNIQUE");
     return fail(ctx, HJGPU_EINVAL, what);
 }
 
-int close_gaps(hjgpu_ctx *ctx, const hjgpu_output *out, uint32_t workers, u64 bs, DevState *st, hipStream_t stream, bool rows2)
+int close_gaps(hjgpu_ctx *ctx, const hjgpu_output *out, uint32_t workers, u64 bs, DevState *st, hipStream_t stream, uint32_t mode)
 {
-    return hj_launch_close_gaps_ex(out->d_keys, out->d_outer_vals, rows2 ? nullptr : out->d_inner_vals, (const u64 *)ctx->final_offsets.p, workers, bs,
+    // two-column rows: (key, outer_val) of a semi- / anti-join, or (key, inner_val) of a right semi- / anti-join - d_inner_vals in the outer column's place
+    const bool rows2 = hj_mode_rows2(mode), build2 = hj_mode_reports_build(mode);
+    return hj_launch_close_gaps_ex(out->d_keys, build2 ? out->d_inner_vals : out->d_outer_vals, (rows2 || build2) ? nullptr : out->d_inner_vals,
+                                   (const u64 *)ctx->final_offsets.p, workers, bs,
                                    &st->block_counter, &st->overflow, ctx->moves.p, &st->nmoves, &st->dense, ctx->cus, stream);
 }
 
@@ -582,7 +608,8 @@ int phj_prepare(hjgpu_ctx *ctx, size_t inner, size_t outer, const hjgpu_phj_para
     pl->pre = pre ? 1u : 0u; pl->pre_f1 = 1; pl->pre_F1tot = 1; pl->pre_base = 0;
     pl->mode = (uint8_t)hj_mode_for_sides(prm ? hj_join_mode(prm->flags) : HJ_MODE_INNER, inner != 0);
     pl->first_match = ctx->tune.unique || (prm && (prm->flags & HJGPU_FLAG_UNIQUE)) || hj_mode_rows2(pl->mode);
-    // (a right outer join is planned like the inner join: fill groups, one launch)
+    // (a right outer join is planned like the inner join: fill groups, one launch; right semi- and anti-joins like the _UNIQUE join: one
+    // fill group per probe slice, single-fill and multi-fill items in launches of their own)
     pl->unique = pl->first_match || (pl->mode != HJ_MODE_INNER && pl->mode != HJ_MODE_RIGHT_OUTER);
     choose_fanout(ctx->tune, plan_inner ? plan_inner : inner, prm, &pl->F1, &pl->F2, &pl->big_tables);
     if (big_override >= 0) pl->big_tables = big_override != 0;
@@ -597,7 +624,7 @@ int phj_prepare(hjgpu_ctx *ctx, size_t inner, size_t outer, const hjgpu_phj_para
             pl->F2 = 2; pl->F1 = (parts + 1) / 2;
         }
     }
-    if ((pl->unique || hj_mode_keeps_build(pl->mode)) && !hj_join_config_built(hj_join_config_of(ctx->tune, pl->big_tables), true))
+    if ((pl->unique || hj_mode_marks_build(pl->mode)) && !hj_join_config_built(hj_join_config_of(ctx->tune, pl->big_tables), true))
         return refuse_mode_geometry(ctx, pl->mode);
     pl->P = pl->F1 * pl->F2;
     if (pl->F1 < 1 || pl->F2 < 1 || pl->F1 > HJGPU_MAX_FANOUT || pl->F2 > HJGPU_MAX_FANOUT ||
@@ -674,7 +701,7 @@ int phj_prepare(hjgpu_ctx *ctx, size_t inner, size_t outer, const hjgpu_phj_para
             CHK(ensure(ctx, ctx->tmp[3], pl->batch_bytes));
         }
     }
-    if (hj_mode_keeps_build(pl->mode)) CHK(ensure(ctx, ctx->build_bits, build_bits_bytes(*pl, inner)));
+    if (hj_mode_marks_build(pl->mode)) CHK(ensure(ctx, ctx->build_bits, build_bits_bytes(*pl, inner)));
     MetaLayout sz = carve(nullptr, pl->C, pl->F1, pl->P, pl->ranges, pl->items_extra, pl->tiles2, pl->batch_cap, pl->tdesc_b_cap);
     CHK(ensure(ctx, ctx->meta, sz.total_bytes));
     CHK(ensure(ctx, ctx->state, sizeof(DevState)));
@@ -931,8 +958,10 @@ int phj_enqueue(hjgpu_ctx *ctx, const PhjPlan &pl,
     if (pl.F2 > 1) for (int i = 0; i < 4; ++i) fin[i] = t2[i];
 
     // K7+K8 (right / full outer joins: + the bitmap's clear in front and the tail kernel behind; without probe rows the tail alone)
-    const bool keepb = hj_mode_keeps_build(pl.mode);
-    if (keepb && (pre || mode != PHJ_WHOLE)) return fail(ctx, HJGPU_EINVAL, "internal: a right / full outer join is a whole join");
+    // (right semi- / anti-joins: the same clear and a tail of their own, hj_launch_build_rows, behind launches that only mark; a right
+    // semi-join without probe rows has nothing to report)
+    const bool marks = hj_mode_marks_build(pl.mode), keepb = hj_mode_build_alone(pl.mode), build_rows = hj_mode_reports_build(pl.mode);
+    if (marks && (pre || mode != PHJ_WHOLE)) return fail(ctx, HJGPU_EINVAL, "internal: a join that marks its build rows is a whole join");
     if (inner && (outer || keepb) && mode != PHJ_BUILD_ONLY) {
         JoinArgs ja{};
         ja.rk = fin[0]; ja.rv = fin[1]; ja.sk = fin[2]; ja.sv = fin[3];
@@ -962,18 +991,19 @@ int phj_enqueue(hjgpu_ctx *ctx, const PhjPlan &pl,
         ja.multi_fill = m.tickets + HJ_TICKET_MULTI_FILL;
         ja.resume = grp ? 1u : 0u;
         join_output(ctx, ja, out, bs, bl, st);
-        if (keepb) {
+        if (marks) {
             ja.build_bits = reinterpret_cast<uint32_t *>(ctx->build_bits.p);
             HIPCHK(ctx, hj_zero_async(ja.build_bits, build_bits_bytes(pl, inner), stream));
-            // no join launch below: every wave of the tail starts without an open block (a group goes on in the grouped join's)
-            if (!outer && bs && !grp) HIPCHK(ctx, hj_fill_async(ctx->final_offsets.p, 0xFFFFFFFFu, (size_t)workers * sizeof(u64), stream));
+            // no join launch below, or none that emits: every wave of the tail starts without an open block (a group goes on in the grouped join's)
+            if ((!outer || build_rows) && bs && !grp) HIPCHK(ctx, hj_fill_async(ctx->final_offsets.p, 0xFFFFFFFFu, (size_t)workers * sizeof(u64), stream));
         }
         if (outer) CHK(hj_launch_join(ja, ctx->tune, ctx->cus, stream));
-        if (keepb) CHK(hj_launch_build_unmatched(ja, ctx->tune, ctx->cus, stream));
+        if (build_rows) CHK(hj_launch_build_rows(ja, ctx->tune, ctx->cus, stream));
+        else if (marks) CHK(hj_launch_build_unmatched(ja, ctx->tune, ctx->cus, stream));
         if (audit) CHK(hj_audit_copy(reinterpret_cast<const u64 *>(&st->result), audit + 4 * 6, 4, stream));
     }
     record(ctx, EV_JOIN, stream);
-    if (bs && inner && (outer || keepb) && mode != PHJ_BUILD_ONLY && !grp) CHK(close_gaps(ctx, out, workers, bs, st, stream, hj_mode_rows2(pl.mode)));
+    if (bs && inner && (outer || keepb) && mode != PHJ_BUILD_ONLY && !grp) CHK(close_gaps(ctx, out, workers, bs, st, stream, pl.mode));
     record(ctx, EV_GAPS, stream);
     ctx->stats.fanout1 = pl.F1; ctx->stats.fanout2 = pl.F2; ctx->stats.buckets = 0; ctx->stats.batches = batches_used;
     ctx->last_algo = 1;
@@ -1039,7 +1069,7 @@ int npj_prepare(hjgpu_ctx *ctx, size_t inner, const hjgpu_npj_params *prm, size_
     *factor = (prm && prm->factor) ? prm->factor : DEFAULT_NPJ_FACTOR;
     if (!(*factor & 1)) return fail(ctx, HJGPU_EINVAL, "hash factor must be odd");
     CHK(ensure_placed(ctx, ctx->table, b * sizeof(u64)));     // >= 1 GB tables: the build (memset + CAS) is 8 % faster in a well-placed block
-    if (hj_mode_keeps_build(npj_mode(prm))) CHK(ensure(ctx, ctx->build_bits, npj_bucket_bits_bytes(b)));   // right / full outer: one bit per bucket
+    if (hj_mode_marks_build(npj_mode(prm))) CHK(ensure(ctx, ctx->build_bits, npj_bucket_bits_bytes(b)));   // the modes that mark: one bit per bucket
     CHK(ensure(ctx, ctx->state, sizeof(DevState)));
     return HJGPU_OK;
 }
@@ -1051,8 +1081,11 @@ int npj_probe_enqueue(hjgpu_ctx *ctx, const uint32_t *sk, const uint32_t *sv, si
     DevState *st = reinterpret_cast<DevState *>(ctx->state.p);
     u64 bs = 0, bl = 0;
     const int grid = hj_npj_probe_grid(ctx->cus, outer);
-    const bool keepb = hj_mode_keeps_build(mode);
-    if (keepb && (!bucket_bits || unique)) return fail(ctx, HJGPU_EINVAL, "internal: a right / full outer NPJ join needs its bucket bitmap and the full walk");
+    // (right semi- / anti-joins: the probe only marks, a tail of their own reports - hj_launch_npj_rows; the first-match walk is never theirs,
+    // whatever `unique` says; a right semi-join without probe rows has nothing to report)
+    const bool build_rows = hj_mode_reports_build(mode), keepb = hj_mode_build_alone(mode);
+    if (hj_mode_keeps_build(mode) && (!bucket_bits || unique)) return fail(ctx, HJGPU_EINVAL, "internal: a right / full outer NPJ join needs its bucket bitmap and the full walk");
+    if (build_rows && !bucket_bits) return fail(ctx, HJGPU_EINVAL, "internal: a right semi- / anti-join needs its bucket bitmap");
     CHK(setup_output(ctx, out, (uint32_t)grid * 4, &bs, &bl, mode));
     if (outer || keepb) {
         NpjProbeArgs pa;
@@ -1067,10 +1100,11 @@ int npj_probe_enqueue(hjgpu_ctx *ctx, const uint32_t *sk, const uint32_t *sv, si
         }
         if (outer) CHK(hj_launch_npj_probe(pa, ctx->cus, stream, nullptr));
         // the tail: the table's tuples whose bucket no probe marked, in the probe's open output blocks (no probe rows: none open)
-        if (keepb) CHK(hj_launch_npj_unmatched(pa, grid, outer != 0, stream));
+        if (build_rows) CHK(hj_launch_npj_rows(pa, grid, stream));
+        else if (keepb) CHK(hj_launch_npj_unmatched(pa, grid, outer != 0, stream));
     }
     record(ctx, EV_JOIN, stream);
-    if (bs && (outer || keepb)) CHK(close_gaps(ctx, out, (uint32_t)grid * 4, bs, st, stream, hj_mode_rows2(mode)));
+    if (bs && (outer || keepb)) CHK(close_gaps(ctx, out, (uint32_t)grid * 4, bs, st, stream, mode));
     record(ctx, EV_GAPS, stream);
     return HJGPU_OK;
 }
@@ -1094,7 +1128,7 @@ int npj_enqueue(hjgpu_ctx *ctx, const uint32_t *rk, const uint32_t *rv, size_t i
     // (no build rows: a full outer join is the left outer join, a right outer join has no rows - hj_mode_for_sides)
     mode = hj_mode_for_sides(mode, inner != 0);
     uint32_t *bits = nullptr;
-    if (hj_mode_keeps_build(mode)) {
+    if (hj_mode_marks_build(mode)) {
         bits = reinterpret_cast<uint32_t *>(ctx->build_bits.p);
         HIPCHK(ctx, hj_zero_async(bits, npj_bucket_bits_bytes(buckets), stream));
     }
@@ -1612,7 +1646,7 @@ static bool broadcast_applies(const HjTuning &tune, size_t inner, size_t outer, 
     if (prm && hj_mode_keeps_unmatched(hj_join_mode(prm->flags)) && inner == 0 && outer) return true;
     // right / full outer joins take the partitioned plan: the bitmap lives over the partitioned build array, and a tiny build side is no
     // reason for a second marking scheme over the caller's columns
-    if (prm && hj_mode_keeps_build(hj_join_mode(prm->flags))) return false;
+    if (prm && hj_mode_marks_build(hj_join_mode(prm->flags))) return false;
     if (tune.no_broadcast) return false;
     if (chunks != 1 || (prm && (prm->fanout1 || prm->fanout2))) return false;    // an explicit plan is honoured
     return inner && outer && inner <= broadcast_rows(tune, true) && inner <= 16383;
@@ -1633,7 +1667,7 @@ static int broadcast_enqueue(hjgpu_ctx *ctx, const uint32_t *rk, const uint32_t 
     const size_t nslices = (outer + HJ_JOIN_SLICE - 1) / HJ_JOIN_SLICE;
     const size_t fills = (inner + cap - 1) / cap;
     const uint32_t jmode = hj_mode_for_sides(prm ? hj_join_mode(prm->flags) : HJ_MODE_INNER, inner != 0);
-    if (hj_mode_keeps_build(jmode)) return fail(ctx, HJGPU_EINVAL, "internal: right / full outer joins are not broadcast");
+    if (hj_mode_marks_build(jmode)) return fail(ctx, HJGPU_EINVAL, "internal: joins that mark their build rows are not broadcast");
     // first_match: the probe walk (JoinArgs::unique); unique: one fill group per probe slice (semi-, anti- and left outer joins too)
     const bool first_match = ctx->tune.unique || (prm && (prm->flags & HJGPU_FLAG_UNIQUE)) || hj_mode_rows2(jmode);
     const bool unique = first_match || jmode != HJ_MODE_INNER;
@@ -1676,7 +1710,7 @@ static int broadcast_enqueue(hjgpu_ctx *ctx, const uint32_t *rk, const uint32_t 
     join_output(ctx, ja, out, bs, bl, st);
     CHK(hj_launch_join(ja, ctx->tune, ctx->cus, stream));
     record(ctx, EV_JOIN, stream);
-    if (bs) CHK(close_gaps(ctx, out, workers, bs, st, stream, hj_mode_rows2(jmode)));
+    if (bs) CHK(close_gaps(ctx, out, workers, bs, st, stream, jmode));
     record(ctx, EV_GAPS, stream);
     ctx->stats.fanout1 = 1; ctx->stats.fanout2 = 1; ctx->stats.buckets = 0; ctx->stats.batches = 0;
     ctx->last_algo = 1;
@@ -1749,7 +1783,8 @@ static int phj_grouped(hjgpu_ctx *ctx, uint32_t G, uint32_t chunks,
     for (uint32_t g = 0; g < G; ++g) {
         // nothing can match (anti / left / full outer: the probe rows of a group without build rows are all reported; right / full outer:
         // the build rows of a group without probe rows - its build side is partitioned and the tail runs alone)
-        if ((pc[g].sn == 0 && !(hj_mode_keeps_build(jmode) && pc[g].rn)) || (pc[g].rn == 0 && !hj_mode_keeps_unmatched(jmode))) continue;
+        // (right anti-join: as right outer; a right semi-join's group without probe rows has nothing to report)
+        if ((pc[g].sn == 0 && !(hj_mode_build_alone(jmode) && pc[g].rn)) || (pc[g].rn == 0 && !hj_mode_keeps_unmatched(jmode))) continue;
         hjgpu_output view;
         const hjgpu_output *vout = nullptr;
         if (out_on) {
@@ -1758,7 +1793,8 @@ static int phj_grouped(hjgpu_ctx *ctx, uint32_t G, uint32_t chunks,
             if (left / bs == 0) { acc.overflow = 1; out_on = false; }
             else {
                 view = *out;
-                view.d_keys += acc.dense; view.d_outer_vals += acc.dense;
+                view.d_keys += acc.dense;
+                if (view.d_outer_vals) view.d_outer_vals += acc.dense;      // (NULL: a right semi- / anti-join's rows have no outer_val)
                 if (view.d_inner_vals) view.d_inner_vals += acc.dense;
                 view.capacity = left / bs * bs; view.block_size = bs;
                 vout = &view;
@@ -1854,7 +1890,7 @@ static int phj_grouped_device(hjgpu_ctx *ctx, uint32_t G, uint32_t chunks,
     HIPCHK(ctx, hj_zero_async(st, sizeof(DevState), stream));
     if (bs) HIPCHK(ctx, hj_fill_async(ctx->final_offsets.p, 0xFFFFFFFFu, (size_t)workers * sizeof(u64), stream));
     CHK(hj_launch_group_desc(d_off, d_off + (l.F0 + 1), G, l.bins, (u64)cap_r, (u64)cap_s, (u64)inner, (u64)outer, d_desc, &st->group_skew, stream,
-                             hj_mode_keeps_unmatched(pl.mode), hj_mode_keeps_build(pl.mode)));
+                             hj_mode_keeps_unmatched(pl.mode), hj_mode_build_alone(pl.mode)));
     HIPCHK(ctx, hipEventRecord(ctx->grp_ev_pass0[1], stream));
     for (uint32_t g = 0; g < G; ++g) {
         const GroupRun run = {d_desc + 4 * (size_t)g};
@@ -1863,7 +1899,7 @@ static int phj_grouped_device(hjgpu_ctx *ctx, uint32_t G, uint32_t chunks,
         ctx->ev_cur = nullptr;
         CHK(rc);
     }
-    if (bs) CHK(close_gaps(ctx, out, workers, bs, st, stream, hj_mode_rows2(pl.mode)));
+    if (bs) CHK(close_gaps(ctx, out, workers, bs, st, stream, pl.mode));
     if (d_result) CHK(hj_launch_group_result(&st->result, &st->group_skew, d_result, stream));
     HIPCHK(ctx, hipEventRecord(ctx->grp_ev_pass0[2], stream));
     // the last event every waiter looks at (hjgpu_get_stats), recorded in the context's own set

@@ -231,9 +231,10 @@ PlanArgs plan_args(const hjgpu_ctx *ctx, const MetaLayout &m, uint32_t C, uint32
                    uint32_t mask);
 // A join's result rows: the block protocol into ja when bs > 0 (setup_output's block size and limit), and close_gaps after the join
 void join_output(const hjgpu_ctx *ctx, JoinArgs &ja, const hjgpu_output *out, u64 bs, u64 bl, DevState *st);
-// (rows2: the rows of a semi- / anti-join - key and outer_val only, the inner column is left alone; hj_mode_rows2)
-int close_gaps(hjgpu_ctx *ctx, const hjgpu_output *out, uint32_t workers, u64 bs, DevState *st, hipStream_t stream, bool rows2 = false);
-// HJGPU_FLAG_SEMI | HJGPU_FLAG_ANTI together: refused
+// (mode: a semi- / anti-join's rows are key and outer_val only, the inner column is left alone - hj_mode_rows2; a right semi- / anti-join's key
+// and inner_val only, the outer column is left alone - hj_mode_reports_build)
+int close_gaps(hjgpu_ctx *ctx, const hjgpu_output *out, uint32_t workers, u64 bs, DevState *st, hipStream_t stream, uint32_t mode = HJ_MODE_INNER);
+// HJGPU_FLAG_SEMI | HJGPU_FLAG_ANTI together, and the other combinations that name two kinds of join: refused
 int check_join_mode(hjgpu_ctx *ctx, uint32_t flags);
 // an entry point without semi-, anti- and left outer joins refuses those flags (never an inner join in their place); the text names the flag
 int refuse_join_mode(hjgpu_ctx *ctx, uint32_t flags, const char *entry);
@@ -256,7 +257,7 @@ struct PhjPlan {
     uint32_t C, F1, F2, P;
     uint32_t f1, f2, tf0, tf1;
     bool big_tables;
-    bool unique;             // HJGPU_FLAG_UNIQUE / option "unique"; also set for semi-, anti- and left outer joins (one fill group per slice)
+    bool unique;             // HJGPU_FLAG_UNIQUE / option "unique"; also set for semi-, anti-, left outer, right semi- and right anti-joins (one fill group per slice)
     uint8_t mode;            // HJ_MODE_*: HJGPU_FLAG_SEMI / _ANTI / _LEFT_OUTER (a byte: beside the flags, the plan keeps its size)
     bool first_match;        // the probe walk ends at a key's first match (JoinArgs::unique): `unique`, except for a left outer join without
                              // HJGPU_FLAG_UNIQUE

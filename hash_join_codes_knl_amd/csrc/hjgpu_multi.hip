@@ -1961,11 +1961,14 @@ int hjgpu_comm_preflight(hjgpu_comm *c, size_t link_bytes, hjgpu_preflight *rep)
     return HJGPU_OK;
 }
 
-// HJGPU_FLAG_SEMI / _ANTI / _LEFT_OUTER / _RIGHT_OUTER / _FULL_OUTER: no multi-GPU semi-, anti- or outer join - refused, never an inner join in its place
+// HJGPU_FLAG_SEMI / _ANTI / _LEFT_OUTER / _RIGHT_OUTER / _FULL_OUTER / _RIGHT_SEMI / _RIGHT_ANTI: no multi-GPU semi-, anti- or outer join - refused, never an inner join in its place
 static int refuse_join_mode_multi(hjgpu_comm *c, uint32_t flags, const char *entry)
 {
-    if (!(flags & (HJGPU_FLAG_SEMI | HJGPU_FLAG_ANTI | HJGPU_FLAG_LEFT_OUTER | HJGPU_FLAG_RIGHT_OUTER))) return HJGPU_OK;
-    return cfail(c, HJGPU_EINVAL, entry, (flags & HJGPU_FLAG_SEMI) ? "HJGPU_FLAG_SEMI is not supported by the multi-GPU joins"
+    if (!(flags & (HJGPU_FLAG_SEMI | HJGPU_FLAG_ANTI | HJGPU_FLAG_LEFT_OUTER | HJGPU_FLAG_RIGHT_OUTER | HJGPU_FLAG_RIGHT_SEMI | HJGPU_FLAG_RIGHT_ANTI)))
+        return HJGPU_OK;
+    return cfail(c, HJGPU_EINVAL, entry, (flags & HJGPU_FLAG_RIGHT_SEMI) ? "HJGPU_FLAG_RIGHT_SEMI is not supported by the multi-GPU joins"
+                                       : (flags & HJGPU_FLAG_RIGHT_ANTI) ? "HJGPU_FLAG_RIGHT_ANTI is not supported by the multi-GPU joins"
+                                       : (flags & HJGPU_FLAG_SEMI) ? "HJGPU_FLAG_SEMI is not supported by the multi-GPU joins"
                                        : (flags & HJGPU_FLAG_ANTI) ? "HJGPU_FLAG_ANTI is not supported by the multi-GPU joins"
                                        : (flags & HJGPU_FLAG_FULL_OUTER) == HJGPU_FLAG_FULL_OUTER ? "HJGPU_FLAG_FULL_OUTER is not supported by the multi-GPU joins"
                                        : (flags & HJGPU_FLAG_RIGHT_OUTER) ? "HJGPU_FLAG_RIGHT_OUTER is not supported by the multi-GPU joins"

@@ -116,6 +116,10 @@ struct hj_mark_pass {
 // The multi-fill items of a full outer join: the left outer join's multi-fill instance is at its 128 VGPRs - anything added to it, even the
 // clear of `slot_bits`, spills - so it reports them as it is (outer_probe_kernel<.., DEDUP>), and a third launch, HJ_MODE_MARK
 // (mark_probe_kernel), fills the tables of those items once more and only marks (hj_mark_pass): no rows, no aggregates.
+// Right semi- and anti-joins (HJ_MODE_RIGHT_SEMI / _ANTI) report build rows only, so ALL their probes are HJ_MODE_MARK: the single-fill
+// items by mark_single_probe_kernel (DEDUP = false), the multi-fill items by mark_probe_kernel as it is; build_rows_kernel behind them
+// reports the marked / the clear rows.  hj_mark_pass stops at a key's first hit: the slot it marks is the slot mark_build_rows finds - a
+// cuckoo table's row pass looks at both slots of a key, a chained table's walks from the same first slot to the same first copy.
 template <bool ON, uint32_t WORDS>
 struct SlotBits {
     static __device__ __forceinline__ uint32_t *get() { __shared__ uint32_t bits[WORDS]; return bits; }
@@ -136,7 +140,7 @@ __device__ __forceinline__ void join_body(JoinArgs a)
     static_assert(MODE == HJ_MODE_INNER || ((UNIQUE || LEFTISH || KEEPB) && NTROWS),
                   "semi- and anti-joins walk to the first match; rows non-temporal");
     static_assert(!(KEEPB && UNIQUE), "right and full outer joins walk to every copy of a build key");
-    static_assert(MARKING == (KEEPB && DEDUP), "the multi-fill items of a full outer join are marked by a launch of its own");
+    static_assert(!(KEEPB && DEDUP) || MARKING, "the multi-fill items of a full outer join are marked by a launch of its own");
     // the two launches of a _UNIQUE join: single-fill items, then multi-fill ones (DEDUP); left and full outer joins always
     constexpr bool SPLIT = UNIQUE || LEFTISH || MARKING;
     // the plan found no partition that takes several fills (the planned case): nothing for this launch to do
@@ -858,6 +862,14 @@ __global__ __launch_bounds__(BLOCK, hj_join_waves_per_simd(BLOCK, LOG2SLOTS)) vo
     join_body<BLOCK, LOG2SLOTS, BATCH, PACKED, false, true, true, HJ_MODE_MARK>(a);
 }
 
+// Right semi- and anti-joins (HJGPU_FLAG_RIGHT_SEMI / _RIGHT_ANTI): the marks of the single-fill items - the multi-fill items take
+// mark_probe_kernel.  Launched without output columns (JoinArgs::ok == NULL): no rows, no aggregates, the waves' cursors stay as they are.
+template <int BLOCK, int LOG2SLOTS, int BATCH, bool PACKED>
+__global__ __launch_bounds__(BLOCK, hj_join_waves_per_simd(BLOCK, LOG2SLOTS)) void mark_single_probe_kernel(JoinArgs a)
+{
+    join_body<BLOCK, LOG2SLOTS, BATCH, PACKED, false, false, true, HJ_MODE_MARK>(a);
+}
+
 // The tail of a right / full outer join: the rows of the partitioned (packed) build array whose bit in a.build_bits is clear leave as
 // (key, HJGPU_NULL_VAL, inner_val).  It runs behind the join's launches with the join's grid and block: wave w of workgroup b resumes the
 // output block that wave left open (final_offsets), so close_gaps sees one launch's worth of worker slots.  The array is walked piece by
@@ -904,6 +916,60 @@ __global__ __launch_bounds__(BLOCK) void build_unmatched_kernel(JoinArgs a, uint
     }
     if (a.ok) hj_leave_cursor(a.final_offsets, wave_cursor);
     // (three sums, written out: the reduction as a call changes the schedule of this kernel, see hj_add_to_result)
+    acc_n = wave_reduce_sum(acc_n); acc_k = wave_reduce_sum(acc_k); acc_i = wave_reduce_sum(acc_i);
+    if (hj_lane() == 0) { red[0][wave] = acc_n; red[1][wave] = acc_k; red[2][wave] = acc_i; }
+    __syncthreads();
+    if (tid < 3) {
+        u64 s = 0;
+        for (int i = 0; i < NW; ++i) s += red[tid][i];
+        u64 *dst = reinterpret_cast<u64 *>(a.result) + (tid == 2 ? 3 : tid);       // count, sum_keys, sum_inner_vals
+        if (s) atomicAdd(dst, s);
+    }
+}
+
+// The tail of a right semi- / anti-join, build_unmatched_kernel's sibling: the same walk over the partitioned build array, the same grid
+// and worker slots.  `flip` = 0: the rows whose bit is clear (right anti-join); ~0: the rows whose bit is set (right semi-join).  Rows
+// of two columns, (key, inner_val): a.oiv is the emitter's second column, a.oov is not touched.  No join launch has emitted anything, so
+// the cursors it resumes are "no block yet" (a device-planned group: what the groups before it left).
+template <int BLOCK>
+__global__ __launch_bounds__(BLOCK) void build_rows_kernel(JoinArgs a, uint32_t split, uint32_t flip)
+{
+    constexpr int NW = BLOCK / 64;
+    __shared__ u64 red[3][NW];
+    __shared__ u64 wave_cursor[NW];
+    const int tid = threadIdx.x, wave = tid >> 6;
+    EmitterT<true, 2> em;
+    em.init(a.ok, a.oiv, nullptr, a.block_size, a.block_limit, a.block_counter, a.overflow, &wave_cursor[wave]);
+    if (hj_lane() == 0) wave_cursor[wave] = a.ok ? a.final_offsets[(u64)blockIdx.x * NW + wave] : HJ_NO_CURSOR;
+    const uint4 *__restrict__ r4 = reinterpret_cast<const uint4 *>(a.rk);
+    const uint32_t *__restrict__ bits = a.build_bits;
+    const u64 units = (u64)a.P * a.chunks * split;
+    u64 acc_n = 0, acc_k = 0, acc_i = 0;
+    for (u64 u = blockIdx.x; u < units; u += gridDim.x) {
+        const u64 piece = u / split, part = u - piece * split;
+        const u64 b = a.roff[piece], len = a.rend[piece] - b;
+        const u64 sb = b + len * part / split, se = b + len * (part + 1) / split;
+        for (u64 g = (sb & ~3ull) + (u64)tid * 4; g < se; g += (u64)BLOCK * 4) {
+            const uint4 x = r4[g >> 1], y = r4[(g >> 1) + 1];                 // tuples g ... g + 3 (the array ends in 4 spare tuples)
+            const uint32_t skip = (bits[g >> 5] ^ flip) >> ((uint32_t)g & 31u);   // g is a multiple of 4: the four bits lie in one word
+            const uint32_t key[4] = {x.x, x.z, y.x, y.z}, val[4] = {x.y, x.w, y.y, y.w};
+            uint32_t rep = 0;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const bool r = g + j >= sb && g + j < se && !((skip >> j) & 1u);
+                rep |= r ? 1u << j : 0u;
+                acc_n += r ? 1u : 0u; acc_k += r ? key[j] : 0u; acc_i += r ? val[j] : 0u;
+            }
+            if (a.ok) {
+                if (rep == 15u && a.block_size >= 512) em.emit4(key, val, val);        // (emit4: blocks of 512 rows and more)
+                else if (rep) {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) if ((rep >> j) & 1u) em.emit(key[j], val[j], 0u);
+                }
+            }
+        }
+    }
+    if (a.ok) hj_leave_cursor(a.final_offsets, wave_cursor);
     acc_n = wave_reduce_sum(acc_n); acc_k = wave_reduce_sum(acc_k); acc_i = wave_reduce_sum(acc_i);
     if (hj_lane() == 0) { red[0][wave] = acc_n; red[1][wave] = acc_k; red[2][wave] = acc_i; }
     __syncthreads();
@@ -996,7 +1062,8 @@ bool hj_join_config_built(const JoinConfig &c, bool unique)
 // (exists_probe_kernel), a left outer join (outer_probe_kernel, with the first-match walk or without it) - at one vector per lane, with
 // their own work counter.  `mark`: a full outer join's third launch, the marks of its multi-fill items (their rows: the left outer
 // join's multi-fill instance as it is), with the third work counter and no rows.  A right outer join is one launch, as the inner join;
-// right and full outer joins take packed inputs only.  SPLIT: the geometry has the instances of the joins of several launches.
+// a right semi- or anti-join is `first` = mark_single_probe_kernel and `mark`, both without rows (no `multi`: nothing is reported here).
+// Right and full outer, right semi- and anti-joins take packed inputs only.  SPLIT: the geometry has the instances of the joins of several launches.
 // (the plain-row instances serve solo materialising joins only; aggregate-only joins never emit: the NTROWS = true instance)
 typedef void (*JoinKernel)(JoinArgs);
 struct JoinLaunches { JoinKernel first, multi, mark; };
@@ -1025,10 +1092,13 @@ template <int B, int L>
 static JoinLaunches mode_join_kernels(uint32_t mode, bool packed, bool unique)
 {
     JoinLaunches k = {nullptr, nullptr, nullptr};
-    if (hj_mode_keeps_build(mode)) {
+    if (hj_mode_marks_build(mode)) {
         if (!packed) return k;
         if (mode == HJ_MODE_RIGHT_OUTER) k.first = right_probe_kernel<B, L, 2, true>;
-        else {
+        else if (hj_mode_reports_build(mode)) {
+            k.first = mark_single_probe_kernel<B, L, 2, true>;
+            k.mark = mark_probe_kernel<B, L, 1, true>;
+        } else {
             k.first = full_probe_kernel<B, L, 2, true>;
             k.multi = outer_probe_kernel<B, L, 1, true, false, true>;
             k.mark = mark_probe_kernel<B, L, 1, true>;
@@ -1068,7 +1138,7 @@ static int launch_join_at(const JoinArgs &b, int batch, int grid, hipStream_t st
         if (!kernels[i]) continue;
         JoinArgs d = b;
         d.work_counter = counters[i];
-        if (i == 2) d.ok = nullptr;
+        if (i == 2 || hj_mode_reports_build(b.mode)) d.ok = nullptr;     // the marking launches report nothing
         hipLaunchKernelGGL(kernels[i], dim3(grid), dim3(B), 0, stream, d);
     }
     return hipGetLastError() == hipSuccess ? HJGPU_OK : HJGPU_EHIP;
@@ -1088,6 +1158,21 @@ int hj_launch_build_unmatched(const JoinArgs &a, const HjTuning &t, int cus, hip
     return hipGetLastError() == hipSuccess ? HJGPU_OK : HJGPU_EHIP;
 }
 
+int hj_launch_build_rows(const JoinArgs &a, const HjTuning &t, int cus, hipStream_t stream)
+{
+    if (!hj_mode_reports_build(a.mode) || !a.packed || !a.build_bits || a.P < 1 || a.chunks == 0 || (a.ok && (!a.final_offsets || !a.oiv))) return HJGPU_EINVAL;
+    const JoinConfig &c = hj_join_config_of(t, a.big_tables != 0);
+    const int grid = join_grid(cus, c);
+    const u64 pieces = (u64)a.P * a.chunks;
+    u64 split = (u64)grid * 4 / pieces;
+    split = split < 1 ? 1 : split > 4096 ? 4096 : split;
+    const uint32_t flip = a.mode == HJ_MODE_RIGHT_SEMI ? ~0u : 0u;
+    if (c.block == 512) hipLaunchKernelGGL((build_rows_kernel<512>), dim3(grid), dim3(512), 0, stream, a, (uint32_t)split, flip);
+    else if (c.block == 1024) hipLaunchKernelGGL((build_rows_kernel<1024>), dim3(grid), dim3(1024), 0, stream, a, (uint32_t)split, flip);
+    else return HJGPU_EINVAL;
+    return hipGetLastError() == hipSuccess ? HJGPU_OK : HJGPU_EHIP;
+}
+
 int hj_launch_join(const JoinArgs &a, const HjTuning &t, int cus, hipStream_t stream)
 {
     if ((a.P < 2 && !a.broadcast) || a.P < 1 || a.chunks == 0) return HJGPU_EINVAL;
@@ -1097,6 +1182,7 @@ int hj_launch_join(const JoinArgs &a, const HjTuning &t, int cus, hipStream_t st
     b.unique = (a.unique || t.unique) ? 1u : 0u;
     if ((b.unique || b.mode) && !b.work_counter2) return HJGPU_EINVAL;
     if (hj_mode_keeps_build(b.mode) && (b.unique || !b.build_bits)) return HJGPU_EINVAL;
+    if (hj_mode_reports_build(b.mode) && !b.build_bits) return HJGPU_EINVAL;      // (unique: ignored, the marking walk stops at the first hit anyway)
     const int grid = join_grid(cus, c);
     if (c.block == 512 && c.log2slots == 13) return launch_join_at<512, 13, true>(b, c.batch, grid, stream);
     if (c.block == 1024 && c.log2slots == 14) return launch_join_at<1024, 14, true>(b, c.batch, grid, stream);

@@ -109,9 +109,11 @@ __device__ __forceinline__ void npj_probe_body(NpjProbeArgs a)
 {
     // LEFTISH: the modes that report like the left outer join; KEEPB (right / full outer joins, never UNIQUE: the walk visits every copy of
     // a key): every bucket a probe matches gets its bit in a.bucket_bits - one bucket per build tuple, so bucket-level marks are exact
+    // MARKING (HJ_MODE_MARK, the probe of a right semi- / anti-join): the same marks and nothing else - no row, no aggregate
     constexpr bool LEFTISH = MODE == HJ_MODE_LEFT_OUTER || MODE == HJ_MODE_FULL_OUTER;
-    constexpr bool KEEPB = MODE == HJ_MODE_RIGHT_OUTER || MODE == HJ_MODE_FULL_OUTER;
-    constexpr bool MATCHES = LEFTISH || KEEPB;     // the modes that report a row per match
+    constexpr bool MARKING = MODE == HJ_MODE_MARK;
+    constexpr bool MATCHES = LEFTISH || MODE == HJ_MODE_RIGHT_OUTER || MODE == HJ_MODE_FULL_OUTER;     // the modes that report a row per match
+    constexpr bool KEEPB = MODE == HJ_MODE_RIGHT_OUTER || MODE == HJ_MODE_FULL_OUTER || MARKING;
     static_assert(MODE != HJ_MODE_INNER && (UNIQUE || LEFTISH || KEEPB) && !(UNIQUE && KEEPB), "semi- and anti-joins walk to the first match");
     constexpr int NW = NPJ_PROBE_WAVES;
     __shared__ u64 red[4][NW];
@@ -365,8 +367,10 @@ template <bool MATERIALIZE, bool UNIQUE, int MODE>
 __device__ __forceinline__ void npj_probe_line_body(NpjProbeArgs a)
 {
     constexpr bool LEFTISH = MODE == HJ_MODE_LEFT_OUTER || MODE == HJ_MODE_FULL_OUTER;     // as in npj_probe_body
-    constexpr bool KEEPB = MODE == HJ_MODE_RIGHT_OUTER || MODE == HJ_MODE_FULL_OUTER;
-    constexpr bool MATCHES = LEFTISH || KEEPB;
+    constexpr bool MARKING = MODE == HJ_MODE_MARK;
+    constexpr bool MATCHES = LEFTISH || MODE == HJ_MODE_RIGHT_OUTER || MODE == HJ_MODE_FULL_OUTER;
+    constexpr bool KEEPB = MODE == HJ_MODE_RIGHT_OUTER || MODE == HJ_MODE_FULL_OUTER || MARKING;
+    static_assert(!(MARKING && MATERIALIZE), "the marking probe reports nothing");
     static_assert(MODE != HJ_MODE_INNER && (UNIQUE || LEFTISH || KEEPB) && !(UNIQUE && KEEPB), "semi- and anti-joins walk to the first match");
     constexpr int NW = NPJ_PROBE_WAVES;
     constexpr int B = 4;                                   // lines in flight per quad
@@ -452,6 +456,9 @@ __device__ __forceinline__ void npj_probe_line_body(NpjProbeArgs a)
                             const u64 at = 8 * ln[i] + 2 * sub;
                             if (m0 || m1) atomicOr(&a.bucket_bits[at >> 5], ((m0 ? 1u : 0u) | (m1 ? 2u : 0u)) << ((uint32_t)at & 31u));
                         }
+                    } else if constexpr (MARKING) {
+                        const u64 at = 8 * ln[i] + 2 * sub;                     // as above
+                        if (m0 || m1) atomicOr(&a.bucket_bits[at >> 5], ((m0 ? 1u : 0u) | (m1 ? 2u : 0u)) << ((uint32_t)at & 31u));
                     } else if (fe < 8u || found) {
                         if (sub == 0 && found == (MODE == HJ_MODE_SEMI)) {
                             acc_n += 1; acc_k += key[i]; acc_o += val[i];
@@ -626,6 +633,19 @@ __global__ __launch_bounds__(NPJ_PROBE_BLOCK) void npj_full_line_kernel(NpjProbe
     npj_probe_line_body<MATERIALIZE, false, HJ_MODE_FULL_OUTER>(a);
 }
 
+// The probes of right semi- and anti-joins (HJGPU_FLAG_RIGHT_SEMI / _RIGHT_ANTI): the full walk - one bucket per build tuple, every copy
+// of a key is visited -, marking every bucket it matches and reporting nothing (HJ_MODE_MARK).  Launched without output columns.
+template <bool GROUPED>
+__global__ __launch_bounds__(NPJ_PROBE_BLOCK) void npj_mark_kernel(NpjProbeArgs a)
+{
+    npj_probe_body<GROUPED, false, HJ_MODE_MARK>(a);
+}
+
+__global__ __launch_bounds__(NPJ_PROBE_BLOCK) void npj_mark_line_kernel(NpjProbeArgs a)
+{
+    npj_probe_line_body<false, false, HJ_MODE_MARK>(a);
+}
+
 // The tail of a right / full outer NPJ join, behind the probe with the probe's grid: scans the table (four buckets = 2 x 16 bytes and
 // their four bits per lane and step; buckets is a multiple of 8) and reports every tuple (key != 0) whose bucket's bit is clear as
 // (key, HJGPU_NULL_VAL, inner_val).  `resume`: the waves go on in the output blocks the probe's waves left open.
@@ -681,6 +701,60 @@ int hj_launch_npj_unmatched(const NpjProbeArgs &a, int grid, bool resume, hipStr
     return hipGetLastError() == hipSuccess ? HJGPU_OK : HJGPU_EHIP;
 }
 
+// The tail of a right semi- / anti-join, npj_unmatched_kernel's sibling: the same scan of the table.  `flip` = 0: the tuples whose bucket's
+// bit is clear (right anti-join); ~0: those whose bit is set (right semi-join).  Rows of two columns, (key, inner_val): a.oiv is the
+// emitter's second column, a.oov is not touched.  The probe has reported nothing: every wave starts without an open block.
+__global__ __launch_bounds__(NPJ_PROBE_BLOCK) void npj_rows_kernel(NpjProbeArgs a, uint32_t flip)
+{
+    constexpr int NW = NPJ_PROBE_WAVES;
+    __shared__ u64 red[3][NW];
+    __shared__ u64 wave_cursor[NW];
+    const int wave = threadIdx.x >> 6;
+    EmitterT<true, 2> em;
+    em.init(a.ok, a.oiv, nullptr, a.block_size, a.block_limit, a.block_counter, a.overflow, &wave_cursor[wave]);
+    if (hj_lane() == 0) wave_cursor[wave] = HJ_NO_CURSOR;
+    const uint4 *__restrict__ t4 = reinterpret_cast<const uint4 *>(a.table);
+    const uint32_t *__restrict__ bits = a.bucket_bits;
+    const u64 nvec = a.buckets >> 2, stride = (u64)gridDim.x * NPJ_PROBE_BLOCK;
+    u64 acc_n = 0, acc_k = 0, acc_i = 0;
+    for (u64 v = (u64)blockIdx.x * NPJ_PROBE_BLOCK + threadIdx.x; v < nvec; v += stride) {
+        const uint4 x = t4[2 * v], y = t4[2 * v + 1];
+        const uint32_t skip = (bits[v >> 3] ^ flip) >> (((uint32_t)v & 7u) * 4);      // buckets 4v ... 4v + 3
+        const uint32_t key[4] = {x.x, x.z, y.x, y.z}, val[4] = {x.y, x.w, y.y, y.w};
+        uint32_t rep = 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const bool r = key[j] != 0u && !((skip >> j) & 1u);
+            rep |= r ? 1u << j : 0u;
+            acc_n += r ? 1u : 0u; acc_k += r ? key[j] : 0u; acc_i += r ? val[j] : 0u;
+        }
+        if (a.ok) {
+            if (rep == 15u && a.block_size >= 512) em.emit4(key, val, val);        // (emit4: blocks of 512 rows and more)
+            else if (rep) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) if ((rep >> j) & 1u) em.emit(key[j], val[j], 0u);
+            }
+        }
+    }
+    if (a.ok) hj_leave_cursor(a.final_offsets, wave_cursor);
+    acc_n = wave_reduce_sum(acc_n); acc_k = wave_reduce_sum(acc_k); acc_i = wave_reduce_sum(acc_i);
+    if (hj_lane() == 0) { red[0][wave] = acc_n; red[1][wave] = acc_k; red[2][wave] = acc_i; }
+    __syncthreads();
+    if (threadIdx.x < 3) {
+        u64 s = 0;
+        for (int i = 0; i < NW; ++i) s += red[threadIdx.x][i];
+        if (s) atomicAdd(reinterpret_cast<u64 *>(a.result) + (threadIdx.x == 2 ? 3 : threadIdx.x), s);     // count, sum_keys, sum_inner_vals
+    }
+}
+
+int hj_launch_npj_rows(const NpjProbeArgs &a, int grid, hipStream_t stream)
+{
+    if (!hj_mode_reports_build(a.mode) || !a.bucket_bits || a.buckets % 8 != 0 || ((uintptr_t)a.table & 15) || grid < 1 ||
+        (a.ok && (!a.final_offsets || !a.oiv))) return HJGPU_EINVAL;
+    hipLaunchKernelGGL(npj_rows_kernel, dim3(grid), dim3(NPJ_PROBE_BLOCK), 0, stream, a, a.mode == HJ_MODE_RIGHT_SEMI ? ~0u : 0u);
+    return hipGetLastError() == hipSuccess ? HJGPU_OK : HJGPU_EHIP;
+}
+
 int hj_npj_probe_grid(int cus, size_t n)
 {
     u64 blocks = ((n + 3) / 4 + NPJ_PROBE_BLOCK - 1) / NPJ_PROBE_BLOCK;
@@ -701,6 +775,8 @@ static NpjProbeKernel npj_probe_kernel_of(uint32_t mode)
     case HJ_MODE_LEFT_OUTER: return LINE ? npj_outer_line_kernel<X, U> : npj_outer_kernel<X, U>;
     case HJ_MODE_RIGHT_OUTER: return LINE ? npj_right_line_kernel<X> : npj_right_kernel<X>;
     case HJ_MODE_FULL_OUTER: return LINE ? npj_full_line_kernel<X> : npj_full_kernel<X>;
+    case HJ_MODE_RIGHT_SEMI:
+    case HJ_MODE_RIGHT_ANTI: return LINE ? npj_mark_line_kernel : npj_mark_kernel<X>;      // (launched without output columns)
     default: return LINE ? npj_probe_line_kernel<X, U> : npj_probe_kernel<X, U>;
     }
 }
@@ -710,15 +786,21 @@ int hj_launch_npj_probe(const NpjProbeArgs &a, int cus, hipStream_t stream, int 
     const int grid = hj_npj_probe_grid(cus, a.n);
     if (grid_out) *grid_out = grid;
     if (hj_mode_keeps_build(a.mode) && (a.unique || !a.bucket_bits)) return HJGPU_EINVAL;
-    if (a.line_hash && (a.buckets % 8 != 0 || ((uintptr_t)a.table & 63))) return HJGPU_EINVAL;
-    const bool grouped = (a.buckets % 4 == 0) && (((uintptr_t)a.table & 31) == 0);
+    // right semi- / anti-joins: the marking probe - launched without output columns (the tail has the rows), never the first-match walk
+    NpjProbeArgs b = a;
+    if (hj_mode_reports_build(a.mode)) {
+        if (!a.bucket_bits) return HJGPU_EINVAL;
+        b.ok = nullptr; b.unique = 0;
+    }
+    if (b.line_hash && (b.buckets % 8 != 0 || ((uintptr_t)b.table & 63))) return HJGPU_EINVAL;
+    const bool grouped = (b.buckets % 4 == 0) && (((uintptr_t)b.table & 31) == 0);
     NpjProbeKernel kernel = nullptr;
-    hj_with_bool(a.line_hash != 0, [&](auto line) {
-        hj_with_bool(line ? a.ok != nullptr : grouped, [&](auto x) {
-            hj_with_bool(a.unique != 0, [&](auto u) { kernel = npj_probe_kernel_of<decltype(line)::value, decltype(x)::value, decltype(u)::value>(a.mode); });
+    hj_with_bool(b.line_hash != 0, [&](auto line) {
+        hj_with_bool(line ? b.ok != nullptr : grouped, [&](auto x) {
+            hj_with_bool(b.unique != 0, [&](auto u) { kernel = npj_probe_kernel_of<decltype(line)::value, decltype(x)::value, decltype(u)::value>(b.mode); });
         });
     });
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(NPJ_PROBE_BLOCK), 0, stream, a);
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(NPJ_PROBE_BLOCK), 0, stream, b);
     return hipGetLastError() == hipSuccess ? HJGPU_OK : HJGPU_EHIP;
 }
 

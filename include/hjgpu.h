@@ -98,6 +98,22 @@ extern "C" {
                                      sum_outer_vals and sum_inner_vals each skip the rows whose value on that side is the NULL.
                                      inner == 0: identical to LEFT_OUTER; outer == 0: identical to RIGHT_OUTER.  At most the
                                      inner join's rows + inner + outer rows.  Refusals as for HJGPU_FLAG_RIGHT_OUTER.          */
+#define HJGPU_FLAG_RIGHT_SEMI 32u  /* right semi-join (the build tuples WITH a partner: "the dimension rows with at least one fact"):
+                                     ONE row (key, inner_val) for every build tuple whose key equals at least one probe key.
+                                     Build-side duplicates are reported one by one, probe-side duplicates never multiply a row;
+                                     empty when inner == 0 or outer == 0.  count, sum_keys and sum_inner_vals are taken over the
+                                     reported build tuples, sum_outer_vals is 0.  Rows have two columns, d_keys and d_inner_vals
+                                     (required: HJGPU_EINVAL without it); d_outer_vals is neither read nor written and may be
+                                     NULL (the _async forms' hjgpu_set_async_output still wants all three).
+                                     hjgpu_output_capacity(rows) holds for the true row count (at most inner).  Same entry
+                                     points as HJGPU_FLAG_SEMI; every other join entry point refuses it (HJGPU_EINVAL).  Refused
+                                     beside HJGPU_FLAG_SEMI, _ANTI, _LEFT_OUTER, _RIGHT_OUTER and _RIGHT_ANTI; HJGPU_FLAG_UNIQUE
+                                     (or option "unique") beside it is ignored - no row depends on which copy a walk finds.
+                                     Keys as for HJGPU_FLAG_LEFT_OUTER; a payload 0xFFFFFFFF is an ordinary payload here.       */
+#define HJGPU_FLAG_RIGHT_ANTI 64u  /* right anti-join (the build tuples WITHOUT a partner: "the dimension rows no fact refers
+                                     to"): ONE row (key, inner_val) for every build tuple whose key equals no probe key - every
+                                     build tuple when outer == 0, none when inner == 0.  Everything else as for
+                                     HJGPU_FLAG_RIGHT_SEMI.                                                                      */
 #define HJGPU_NULL_VAL    0xFFFFFFFFu  /* the value on the side without a match in an outer join's NULL row              */
 
 #define HJGPU_MAX_FANOUT  1024u   /* per partitioning pass                                   */
