@@ -35,6 +35,7 @@ EXPORTS = [
     "hjgpu_host_alloc", "hjgpu_host_free",
     "hjgpu_histogram", "hjgpu_partition", "hjgpu_partition_async", "hjgpu_join_partitions",
     "hjgpu_npj_build", "hjgpu_npj_probe",
+    "hjgpu_npj_lookup", "hjgpu_npj_lookup_async", "hjgpu_npj_lookup_table",
     "hjgpu_npj", "hjgpu_phj", "hjgpu_cpra",
     "hjgpu_npj_async", "hjgpu_phj_async", "hjgpu_cpra_async", "hjgpu_phj_overlapped_async",
     "hjgpu_phj_build", "hjgpu_phj_probe", "hjgpu_phj_probe_async",
@@ -255,6 +256,9 @@ def load_library(build_if_missing=True):
     L.hjgpu_npj_build.argtypes = [vp, vp, vp, sz, vp, sz, u32, vp]
     L.hjgpu_npj_probe.argtypes = [vp, vp, vp, sz, vp, sz, u32, C.POINTER(Result),
                                   C.POINTER(Output), vp]
+    L.hjgpu_npj_lookup.argtypes = [vp, vp, vp, sz, vp, sz, C.POINTER(NpjParams), vp, vp, C.POINTER(Result), vp]
+    L.hjgpu_npj_lookup_async.argtypes = [vp, vp, vp, sz, vp, sz, C.POINTER(NpjParams), vp, vp, vp, vp]
+    L.hjgpu_npj_lookup_table.argtypes = [vp, vp, sz, vp, sz, u32, vp, vp, C.POINTER(Result), vp]
     join = [vp, vp, vp, sz, vp, vp, sz]
     L.hjgpu_npj.argtypes = join + [C.POINTER(NpjParams), C.POINTER(Result), C.POINTER(Output), vp]
     L.hjgpu_phj.argtypes = join + [C.POINTER(PhjParams), C.POINTER(Result), C.POINTER(Output), vp]
@@ -467,6 +471,27 @@ class HjGpu:
         self._check(self.lib.hjgpu_npj_probe(self.handle, self._ptr(d_keys), self._ptr(d_vals), n,
                                              self._ptr(d_table), buckets, factor, C.byref(r),
                                              self._out(out), stream))
+        return r.as_tuple()
+
+    # ---- positional look-up: vals_out[i] / bit i of match_bits answer probe key i, in the probe column's order ----------
+    def npj_lookup(self, rk, rv, inner, sk, outer, params=None, vals_out=None, match_bits=None, stream=None):
+        """hjgpu_npj_lookup: vals_out (outer uint32) and match_bits ((outer + 31) // 32 uint32) are device columns or None"""
+        r = Result()
+        self._check(self.lib.hjgpu_npj_lookup(self.handle, self._ptr(rk), self._ptr(rv), inner, self._ptr(sk), outer,
+                                              C.byref(params) if params is not None else None,
+                                              self._ptr(vals_out), self._ptr(match_bits), C.byref(r), stream))
+        return r.as_tuple()
+
+    def npj_lookup_async(self, rk, rv, inner, sk, outer, params, vals_out, match_bits, d_result, stream=None):
+        self._check(self.lib.hjgpu_npj_lookup_async(self.handle, self._ptr(rk), self._ptr(rv), inner, self._ptr(sk), outer,
+                                                    C.byref(params) if params is not None else None,
+                                                    self._ptr(vals_out), self._ptr(match_bits), self._ptr(d_result), stream))
+
+    def npj_lookup_table(self, sk, n, d_table, buckets, factor, vals_out=None, match_bits=None, stream=None):
+        """hjgpu_npj_lookup_table: the look-up in a table that npj_build made"""
+        r = Result()
+        self._check(self.lib.hjgpu_npj_lookup_table(self.handle, self._ptr(sk), n, self._ptr(d_table), buckets, factor,
+                                                    self._ptr(vals_out), self._ptr(match_bits), C.byref(r), stream))
         return r.as_tuple()
 
     # ---- whole joins ------------------------------------------------------------------

@@ -430,6 +430,22 @@ int hj_launch_npj_unmatched(const NpjProbeArgs &a, int grid, bool resume, hipStr
 // clear (HJ_MODE_RIGHT_ANTI) leaves as (key, inner_val), a.oiv the second column.  No probe has reported anything: no open blocks to resume
 int hj_launch_npj_rows(const NpjProbeArgs &a, int grid, hipStream_t stream);
 int hj_launch_npj_probe(const NpjProbeArgs &a, int cus, hipStream_t stream, int *grid_out);
+// Positional look-up (hjgpu_npj_lookup*): vals_out[i] = the payload of the first build tuple the walk of keys[i] meets (HJGPU_NULL_VAL: none),
+// bit i of match_bits = it met one; either may be NULL.  keys, vals_out and match_bits are 16-byte aligned.  count / sum_keys / sum_inner_vals
+// of the matched rows are added to *result.  line_hash: the library's own tables (npj_lookup_line_kernel), else the reference's hash
+// (npj_lookup_kernel).  The grid is hj_npj_probe_grid's; n == 0 launches nothing.
+struct NpjLookupArgs {
+    const uint32_t *keys;
+    size_t n;
+    const u64 *table;
+    size_t buckets;
+    uint32_t factor;
+    uint32_t line_hash;
+    hjgpu_result *result;
+    uint32_t *vals_out;
+    uint32_t *match_bits;
+};
+int hj_launch_npj_lookup(const NpjLookupArgs &a, int cus, hipStream_t stream);
 
 // K9: compact the per-wave partially filled tail blocks (npj.cpp:475-514).
 // moves: scratch of 2*HJ_MAX_WORKERS entries of 24 bytes + HJ_MAX_WORKERS entries of 8 bytes.

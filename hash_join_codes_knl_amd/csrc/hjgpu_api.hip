@@ -303,7 +303,7 @@ void record(hjgpu_ctx *ctx, int which, hipStream_t s)
             (void)hipEventRecord(ctx->ev_cur[which], s);
         return;
     }
-    if (which == EV_BEGIN) { ctx->stats_override = false; ctx->grp_ev_groups = 0; }
+    if (which == EV_BEGIN) { ctx->stats_override = false; ctx->grp_ev_groups = 0; ctx->last_lookup = false; }
     ctx->ev_valid[which] = (hipEventRecord(ctx->ev[which], s) == hipSuccess);
 }
 
@@ -1109,22 +1109,30 @@ int npj_probe_enqueue(hjgpu_ctx *ctx, const uint32_t *sk, const uint32_t *sv, si
     return HJGPU_OK;
 }
 
-int npj_enqueue(hjgpu_ctx *ctx, const uint32_t *rk, const uint32_t *rv, size_t inner,
-                const uint32_t *sk, const uint32_t *sv, size_t outer,
-                size_t buckets, uint32_t factor, const hjgpu_output *out, hipStream_t stream, bool unique, uint32_t mode)
+// the head of a whole NPJ call (join or look-up): the state and the table cleared, the table built - up to the "end of build" event
+static int npj_build_enqueue(hjgpu_ctx *ctx, const uint32_t *rk, const uint32_t *rv, size_t inner, size_t buckets, uint32_t factor, hipStream_t stream, bool line)
 {
-    CHK(refuse_capture(ctx, stream));
     DevState *st = reinterpret_cast<DevState *>(ctx->state.p);
     u64 *table = reinterpret_cast<u64 *>(ctx->table.p);
     record(ctx, EV_BEGIN, stream);
     HIPCHK(ctx, hj_zero_async(st, sizeof(DevState), stream));
     // K1 set() npj.cpp:865-868 ; K2 build() 871-877
     HIPCHK(ctx, hj_zero_async(table, buckets * sizeof(u64), stream));
+    if (inner) CHK(hj_launch_npj_build(rk, rv, inner, table, buckets, factor, &st->zero_key, ctx->cus, stream, line));
+    record(ctx, EV_R_HIST, stream);     // reused as "end of build"
+    return HJGPU_OK;
+}
+
+int npj_enqueue(hjgpu_ctx *ctx, const uint32_t *rk, const uint32_t *rv, size_t inner,
+                const uint32_t *sk, const uint32_t *sv, size_t outer,
+                size_t buckets, uint32_t factor, const hjgpu_output *out, hipStream_t stream, bool unique, uint32_t mode)
+{
+    CHK(refuse_capture(ctx, stream));
+    u64 *table = reinterpret_cast<u64 *>(ctx->table.p);
     // whole joins own their table: line-hashed layout (operator-level hjgpu_npj_build / _probe keep
     // the reference's hash so that their tables stay interchangeable with the reference's)
     const bool line = !ctx->tune.npj_refhash;
-    if (inner) CHK(hj_launch_npj_build(rk, rv, inner, table, buckets, factor, &st->zero_key, ctx->cus, stream, line));
-    record(ctx, EV_R_HIST, stream);     // reused as "end of build"
+    CHK(npj_build_enqueue(ctx, rk, rv, inner, buckets, factor, stream, line));
     // (no build rows: a full outer join is the left outer join, a right outer join has no rows - hj_mode_for_sides)
     mode = hj_mode_for_sides(mode, inner != 0);
     uint32_t *bits = nullptr;
@@ -1136,6 +1144,52 @@ int npj_enqueue(hjgpu_ctx *ctx, const uint32_t *rk, const uint32_t *rv, size_t i
     ctx->stats.fanout1 = ctx->stats.fanout2 = 0; ctx->stats.buckets = buckets; ctx->stats.batches = 0;
     ctx->last_algo = 0;
     return HJGPU_OK;
+}
+
+// The positional look-up behind a built table (hjgpu_npj_lookup*): one kernel.  No setup_output, no final_offsets, no close_gaps - the
+// two events that bracket close_gaps elsewhere are recorded back to back (ms_close_gaps 0).  ctx->state is zeroed by the caller.
+int npj_lookup_enqueue(hjgpu_ctx *ctx, const uint32_t *sk, size_t outer, const u64 *table, size_t buckets, uint32_t factor,
+                       uint32_t *vals_out, uint32_t *match_bits, hipStream_t stream, bool line_hash)
+{
+    DevState *st = reinterpret_cast<DevState *>(ctx->state.p);
+    NpjLookupArgs la;
+    memset(&la, 0, sizeof(la));
+    la.keys = sk; la.n = outer; la.table = table; la.buckets = buckets; la.factor = factor; la.line_hash = line_hash ? 1u : 0u;
+    la.result = &st->result; la.vals_out = vals_out; la.match_bits = match_bits;
+    if (outer) CHK(hj_launch_npj_lookup(la, ctx->cus, stream));
+    record(ctx, EV_JOIN, stream);
+    record(ctx, EV_GAPS, stream);
+    ctx->stats.fanout1 = ctx->stats.fanout2 = 0; ctx->stats.buckets = buckets; ctx->stats.batches = 0;
+    ctx->last_algo = 0;
+    ctx->last_had_output = false;
+    ctx->last_lookup = true;
+    return HJGPU_OK;
+}
+
+// what every look-up entry point checks of its probe column and outputs
+int check_lookup_columns(hjgpu_ctx *ctx, const uint32_t *sk, size_t outer, const uint32_t *vals_out, const uint32_t *match_bits)
+{
+    if (outer && !sk) return fail(ctx, HJGPU_EINVAL, "null column pointer");
+    if (outer && ((uintptr_t)sk & 15)) return fail(ctx, HJGPU_EALIGN, "the probe key column must be 16-byte aligned");
+    if ((uintptr_t)vals_out & 15) return fail(ctx, HJGPU_EALIGN, "d_vals_out must be 16-byte aligned");
+    if ((uintptr_t)match_bits & 15) return fail(ctx, HJGPU_EALIGN, "d_match_bits must be 16-byte aligned");
+    return HJGPU_OK;
+}
+
+static int npj_lookup_whole(hjgpu_ctx *ctx, const uint32_t *rk, const uint32_t *rv, size_t inner, const uint32_t *sk, size_t outer,
+                            const hjgpu_npj_params *prm, uint32_t *vals_out, uint32_t *match_bits, hipStream_t stream, const char *entry)
+{
+    // (HJGPU_FLAG_UNIQUE is what the look-up is by definition: ignored)
+    if (prm) CHK(refuse_join_mode(ctx, prm->flags, entry));
+    CHK(check_columns(ctx, rk, rv, inner));
+    CHK(check_lookup_columns(ctx, sk, outer, vals_out, match_bits));
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    size_t buckets; uint32_t factor;
+    CHK(refuse_capture(ctx, stream));                    // before anything is allocated or probed
+    CHK(npj_prepare(ctx, inner, prm, &buckets, &factor));     // (no mode flag is left in prm: no bucket bitmap)
+    const bool line = !ctx->tune.npj_refhash;
+    CHK(npj_build_enqueue(ctx, rk, rv, inner, buckets, factor, stream, line));
+    return npj_lookup_enqueue(ctx, sk, outer, reinterpret_cast<const u64 *>(ctx->table.p), buckets, factor, vals_out, match_bits, stream, line);
 }
 
 // hjgpu_accumulate_async_status: the two flags of the last join -> two running uint64 counters
@@ -1376,7 +1430,7 @@ int hjgpu_get_stats(hjgpu_ctx *ctx, hjgpu_stats *s)
         r.ms_join = span(EV_R_SC2, EV_JOIN);
         r.ms_build = 0;
     }
-    r.ms_close_gaps = span(EV_JOIN, EV_GAPS);
+    r.ms_close_gaps = ctx->last_lookup ? 0.f : span(EV_JOIN, EV_GAPS);     // (a look-up records the two events back to back)
     r.ms_scatter0 = 0; r.groups = 0;
     *s = r;
     return HJGPU_OK;
@@ -1624,6 +1678,26 @@ int hjgpu_npj(hjgpu_ctx *ctx, const uint32_t *rk, const uint32_t *rv, size_t inn
     PlainRows plain(ctx, true);
     CHK(npj_enqueue(ctx, rk, rv, inner, sk, sv, outer, buckets, factor, out, stream, npj_unique(ctx, prm), npj_mode(prm)));
     return finish_blocking(ctx, result, out, stream);
+}
+
+int hjgpu_npj_lookup_async(hjgpu_ctx *ctx, const uint32_t *rk, const uint32_t *rv, size_t inner, const uint32_t *sk, size_t outer,
+                           const hjgpu_npj_params *prm, uint32_t *vals_out, uint32_t *match_bits, hjgpu_result *d_result, void *stream_)
+{
+    if (!ctx) return HJGPU_EINVAL;
+    hipStream_t stream = (hipStream_t)stream_;
+    CHK(npj_lookup_whole(ctx, rk, rv, inner, sk, outer, prm, vals_out, match_bits, stream, "hjgpu_npj_lookup_async"));
+    if (d_result)
+        HIPCHK(ctx, hj_copy_async(d_result, ctx->state.p, sizeof(hjgpu_result), stream));
+    return HJGPU_OK;
+}
+
+int hjgpu_npj_lookup(hjgpu_ctx *ctx, const uint32_t *rk, const uint32_t *rv, size_t inner, const uint32_t *sk, size_t outer,
+                     const hjgpu_npj_params *prm, uint32_t *vals_out, uint32_t *match_bits, hjgpu_result *result, void *stream_)
+{
+    if (!ctx) return HJGPU_EINVAL;
+    hipStream_t stream = (hipStream_t)stream_;
+    CHK(npj_lookup_whole(ctx, rk, rv, inner, sk, outer, prm, vals_out, match_bits, stream, "hjgpu_npj_lookup"));
+    return finish_blocking(ctx, result, nullptr, stream);
 }
 
 // Broadcast join: a build side that fits ONE LDS table is not worth partitioning anything.  Every work item (a

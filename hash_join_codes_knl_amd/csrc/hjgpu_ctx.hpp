@@ -58,6 +58,7 @@ struct hjgpu_ctx {
     bool ev_valid[EV_COUNT];
     hjgpu_stats stats;
     int last_algo = -1;     // 0 npj, 1 phj/cpra
+    bool last_lookup = false;   // the last operation was a positional look-up (hjgpu_npj_lookup*): no close_gaps, ms_close_gaps is 0
     // hjgpu_phj_build: the partitioned build side (tmp[0] / tmp[4]) and its plan (meta) stay valid until
     // another entry point uses the workspace
     bool prepared = false;
@@ -310,6 +311,10 @@ int npj_probe_enqueue(hjgpu_ctx *ctx, const uint32_t *sk, const uint32_t *sv, si
 int npj_enqueue(hjgpu_ctx *ctx, const uint32_t *rk, const uint32_t *rv, size_t inner, const uint32_t *sk, const uint32_t *sv, size_t outer,
                 size_t buckets, uint32_t factor, const hjgpu_output *out, hipStream_t stream, bool unique, uint32_t mode = HJ_MODE_INNER);
 const hjgpu_output *take_async_output(hjgpu_ctx *ctx, const hjgpu_output *given);
+// the positional look-up in a built table (hjgpu_npj_lookup*: npj_kernels.hip); ctx->state zeroed by the caller, EV_BEGIN / EV_R_HIST recorded
+int npj_lookup_enqueue(hjgpu_ctx *ctx, const uint32_t *sk, size_t outer, const u64 *table, size_t buckets, uint32_t factor,
+                       uint32_t *vals_out, uint32_t *match_bits, hipStream_t stream, bool line_hash);
+int check_lookup_columns(hjgpu_ctx *ctx, const uint32_t *sk, size_t outer, const uint32_t *vals_out, const uint32_t *match_bits);
 // hjgpu_ops.hip: the partition operator on one relation (hjgpu_partition*, hjgpu_partition_packed_*; pass 0 of a grouped plan) - what
 // differs between its forms
 struct PartitionForm {

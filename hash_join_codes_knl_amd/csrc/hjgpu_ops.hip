@@ -218,6 +218,22 @@ int hjgpu_npj_probe(hjgpu_ctx *ctx, const uint32_t *d_keys, const uint32_t *d_va
     return finish_blocking(ctx, result, out, stream);
 }
 
+int hjgpu_npj_lookup_table(hjgpu_ctx *ctx, const uint32_t *d_keys, size_t n, const uint64_t *d_table, size_t buckets, uint32_t factor,
+                           uint32_t *d_vals_out, uint32_t *d_match_bits, hjgpu_result *result, void *stream_)
+{
+    if (!ctx || !d_table || buckets == 0) return fail(ctx, HJGPU_EINVAL, "null pointer");
+    if ((uintptr_t)d_table & 7) return fail(ctx, HJGPU_EALIGN, "the table must be 8-byte aligned");
+    CHK(check_lookup_columns(ctx, d_keys, n, d_vals_out, d_match_bits));
+    hipStream_t stream = (hipStream_t)stream_;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    CHK(refuse_capture(ctx, stream));
+    CHK(ensure(ctx, ctx->state, sizeof(DevState)));
+    HIPCHK(ctx, hj_zero_async(ctx->state.p, sizeof(DevState), stream));
+    record(ctx, EV_BEGIN, stream); record(ctx, EV_R_HIST, stream);
+    CHK(npj_lookup_enqueue(ctx, d_keys, n, (const u64 *)d_table, buckets, factor, d_vals_out, d_match_bits, stream, false));
+    return finish_blocking(ctx, result, nullptr, stream);
+}
+
 // ---- relations that arrive pass-1-partitioned (the receiving side of the multi-GPU CPRA) --------------------
 int hjgpu_partition_packed_async(hjgpu_ctx *ctx, const uint32_t *d_keys, const uint32_t *d_vals, size_t n,
                                  uint32_t factor, uint32_t fanout, uint64_t *d_tuples_out, uint64_t *d_offsets, void *stream)

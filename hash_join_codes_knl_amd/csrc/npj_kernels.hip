@@ -805,6 +805,239 @@ int hj_launch_npj_probe(const NpjProbeArgs &a, int cus, hipStream_t stream, int 
 }
 
 // --------------------------------------------------------------------------
+// Positional look-up (hjgpu_npj_lookup*, DESIGN.md section 5 "Positional look-up"): out[i] = the payload of the first build tuple the walk
+// of probe key i meets (HJGPU_NULL_VAL: none), bit i of the bitmap = it met one - both IN THE PROBE COLUMN'S ORDER.  No probe payloads,
+// no emitter, no block claims: lane L of a wave trip owns rows 4 L ... 4 L + 3 of the trip's 256 consecutive rows, ends the trip with
+// their four answers and a nibble of match bits, and writes one 16-byte vector; the nibbles of 8 lanes make one word of the bitmap.
+// Bodies of their own beside the join walks (which stay as they are, instruction for instruction); the epilogue is the shared
+// hj_add_to_result.  The key column is 16-byte aligned (the entry points refuse anything else): vector v holds rows 4 v ... 4 v + 3.
+// VALS / BITS are template parameters for npj_probe_line_body's reason for MATERIALIZE, and so that no store sits behind a run-time flag
+// (tests/test_store_policy_isa.py); <false, false> is the aggregate-only instance.
+// --------------------------------------------------------------------------
+__device__ __forceinline__ uint32_t half_row_mirror(uint32_t x)
+{
+    return (uint32_t)__builtin_amdgcn_mov_dpp((int)x, 0x141, 0xF, 0xF, true);          // row_half_mirror: inside every 8 lanes
+}
+
+// The end of a wave trip, all 64 lanes (the bitmap's words are combined across lanes): v = this lane's vector, res / nib = the answers and
+// match bits of its four rows (nib is 0 for every row at n and beyond, so the last word's high bits leave as 0).
+template <bool VALS, bool BITS>
+__device__ __forceinline__ void npj_lookup_leave(const NpjLookupArgs &a, u64 v, const uint32_t (&kc)[4], const uint32_t (&res)[4], uint32_t nib,
+                                                 u64 &acc_n, u64 &acc_k, u64 &acc_i)
+{
+    const u64 n = a.n, g = v << 2;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const bool hit = (nib >> j) & 1u;
+        acc_n += hit ? 1u : 0u; acc_k += hit ? kc[j] : 0u; acc_i += hit ? res[j] : 0u;
+    }
+    if constexpr (VALS) {
+        if (g + 4 <= n) hj_store(reinterpret_cast<uint4 *>(a.vals_out) + v, make_uint4(res[0], res[1], res[2], res[3]));
+        else {                                                  // the last, partial vector: nothing at n and beyond is written
+#pragma unroll
+            for (int j = 0; j < 3; ++j) if (g + j < n) hj_store(a.vals_out + g + j, res[j]);
+        }
+    }
+    if constexpr (BITS) {
+        // 8 lanes x 4 rows = one word: OR over each group of 8 lanes, its first lane stores
+        uint32_t w = nib << ((threadIdx.x & 7u) * 4);
+        w |= quad_perm<0xB1>(w);                                // lanes 0<->1, 2<->3
+        w |= quad_perm<0x4E>(w);                                // lanes 0<->2, 1<->3
+        w |= half_row_mirror(w);                                // lane i <-> 7 - i of the group: the other quad
+        // (v is a multiple of 8 in the storing lane: word v / 8 starts at row 4 v; a word whose first row is at n or beyond is not stored)
+        if ((threadIdx.x & 7u) == 0 && g < n) hj_store(a.match_bits + (v >> 3), w);
+    }
+}
+
+// The library's own line-hashed tables: the quad walk of npj_probe_line_body with the first-match rule, without the payload column.  After
+// its walk tuple r of the quad's 16 has its answer in ONE lane - the one whose bucket is the first match - and the answer belongs to lane
+// r / 4 of the quad, component r & 3: a quad OR of (mine ? payload : 0) takes it there (`found` is quad-uniform already: it comes out
+// of the quad's min-reduction of the first matching bucket).
+template <bool VALS, bool BITS>
+__global__ __launch_bounds__(NPJ_PROBE_BLOCK) void npj_lookup_line_kernel(NpjLookupArgs a)
+{
+    constexpr int NW = NPJ_PROBE_WAVES;
+    constexpr int B = 4;                                   // lines in flight per quad
+    __shared__ u64 red[4][NW];
+    const uint4 *__restrict__ k4 = reinterpret_cast<const uint4 *>(a.keys);
+    const u64 n = a.n, nvec = (n + 3) >> 2, stride = (u64)gridDim.x * NPJ_PROBE_BLOCK;
+    const uint4 *__restrict__ t4 = reinterpret_cast<const uint4 *>(a.table);
+    const u64 lines = a.buckets >> 3;
+    const uint32_t factor = a.factor;
+    const uint32_t sub = threadIdx.x & 3;                  // my quarter of the line: buckets 2*sub, 2*sub + 1
+
+    u64 acc_n = 0, acc_k = 0, acc_i = 0;
+    // whole waves iterate together (the quad exchanges and the bitmap's words need all lanes)
+    for (u64 v0 = (u64)blockIdx.x * NPJ_PROBE_BLOCK + (threadIdx.x & ~63u); v0 < nvec; v0 += stride) {
+        const u64 v = v0 + hj_lane();
+        uint4 kk = make_uint4(0, 0, 0, 0);
+        if (v < nvec) kk = k4[v];
+        const u64 g = v << 2;
+        const uint32_t kc[4] = {kk.x, kk.y, kk.z, kk.w};
+        uint32_t okc[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) okc[j] = (g + j < n) ? 1u : 0u;
+        uint32_t res[4] = {HJGPU_NULL_VAL, HJGPU_NULL_VAL, HJGPU_NULL_VAL, HJGPU_NULL_VAL};
+        uint32_t nib = 0;
+
+        // the quad's 16 tuples (4 lanes x 4 components), B at a time
+#pragma unroll
+        for (int r0 = 0; r0 < 16; r0 += B) {
+            uint32_t key[B];
+            bool act[B];
+            u64 ln[B];
+            uint4 q[B];
+#pragma unroll
+            for (int i = 0; i < B; ++i) {
+                const int r = r0 + i, comp = r & 3;                     // static after unrolling
+                // the tuple's owner is lane r / 4 of the quad: broadcast its key and validity
+                if (r < 4) { key[i] = quad_perm<0x00>(kc[comp]); act[i] = quad_perm<0x00>(okc[comp]) != 0; }
+                else if (r < 8) { key[i] = quad_perm<0x55>(kc[comp]); act[i] = quad_perm<0x55>(okc[comp]) != 0; }
+                else if (r < 12) { key[i] = quad_perm<0xAA>(kc[comp]); act[i] = quad_perm<0xAA>(okc[comp]) != 0; }
+                else { key[i] = quad_perm<0xFF>(kc[comp]); act[i] = quad_perm<0xFF>(okc[comp]) != 0; }
+                ln[i] = npj_bucket(key[i], factor, lines);
+                q[i] = make_uint4(0, 0, 0, 0);
+                if (act[i]) {
+                    q[i] = t4[4 * ln[i] + sub];                         // 4 lanes x 16 bytes = the key's line
+                }
+            }
+#pragma unroll
+            for (int i = 0; i < B; ++i) {
+                uint32_t pay = 0;                                       // the first match's payload, in the lane that holds its bucket
+                bool got = false;                                       // the walk found a match (quad-uniform)
+                while (act[i]) {                                        // uniform inside the quad
+                    // first empty bucket of the line, over the quad
+                    uint32_t fe = q[i].x == 0u ? 2 * sub : (q[i].z == 0u ? 2 * sub + 1 : 8u);
+                    fe = min(fe, quad_perm<0xB1>(fe));                  // lanes 0<->1, 2<->3
+                    fe = min(fe, quad_perm<0x4E>(fe));                  // lanes 0<->2, 1<->3
+                    const bool m0 = q[i].x == key[i] && 2 * sub < fe;
+                    const bool m1 = q[i].z == key[i] && 2 * sub + 1 < fe;
+                    // only the FIRST match of the walk counts: the lowest matching bucket of the line
+                    uint32_t fm = m0 ? 2 * sub : (m1 ? 2 * sub + 1 : 8u);
+                    const uint32_t mine = fm;
+                    fm = min(fm, quad_perm<0xB1>(fm));
+                    fm = min(fm, quad_perm<0x4E>(fm));
+                    got = fm < 8u;
+                    if (got && mine == fm) pay = m0 ? q[i].y : q[i].w;
+                    if (fe < 8u || got) break;                          // the walk ends at the first match or the first empty bucket
+                    if (++ln[i] == lines) ln[i] = 0;                    // full line: the walk goes on in the next one
+                    q[i] = t4[4 * ln[i] + sub];
+                }
+                // to the owner (a probe key 0 and a row at n or beyond: no match, pay 0)
+                pay |= quad_perm<0xB1>(pay);
+                pay |= quad_perm<0x4E>(pay);
+                const int r = r0 + i, comp = r & 3;
+                if (got && sub == (uint32_t)(r >> 2)) { res[comp] = pay; nib |= 1u << comp; }
+            }
+        }
+        npj_lookup_leave<VALS, BITS>(a, v, kc, res, nib, acc_n, acc_k, acc_i);
+    }
+    hj_add_to_result(red, a.result, acc_n, acc_k, 0ull, acc_i);
+}
+
+// Tables with the reference's hash (hjgpu_npj_lookup_table; whole look-ups under option "npj_refhash"): the bucket / group walk of
+// npj_probe_body with the first-match rule.  Every lane walks its own four rows: nothing to route.  GROUPED as there.
+template <bool GROUPED, bool VALS, bool BITS>
+__global__ __launch_bounds__(NPJ_PROBE_BLOCK) void npj_lookup_kernel(NpjLookupArgs a)
+{
+    constexpr int NW = NPJ_PROBE_WAVES;
+    __shared__ u64 red[4][NW];
+    const uint4 *__restrict__ k4 = reinterpret_cast<const uint4 *>(a.keys);
+    const u64 n = a.n, nvec = (n + 3) >> 2, stride = (u64)gridDim.x * NPJ_PROBE_BLOCK;
+    const u64 *__restrict__ table = a.table;
+    const u64 buckets = a.buckets;
+    const uint32_t factor = a.factor;
+
+    u64 acc_n = 0, acc_k = 0, acc_i = 0;
+    // whole waves iterate together (the bitmap's words need all lanes)
+    for (u64 v0 = (u64)blockIdx.x * NPJ_PROBE_BLOCK + (threadIdx.x & ~63u); v0 < nvec; v0 += stride) {
+        const u64 v = v0 + hj_lane();
+        uint4 kk = make_uint4(0, 0, 0, 0);
+        if (v < nvec) kk = k4[v];
+        const u64 g = v << 2;
+        const uint32_t key[4] = {kk.x, kk.y, kk.z, kk.w};
+        uint32_t res[4] = {HJGPU_NULL_VAL, HJGPU_NULL_VAL, HJGPU_NULL_VAL, HJGPU_NULL_VAL};
+        uint32_t nib = 0;
+        u64 h[4];
+        bool act[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            act[j] = g + j < n;
+            h[j] = npj_bucket(key[j], factor, buckets);
+        }
+        if (GROUPED) {
+            const uint4 *__restrict__ t4 = reinterpret_cast<const uint4 *>(table);
+            while (act[0] | act[1] | act[2] | act[3]) {
+                uint4 lo[4], hi[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {           // all group loads of the 4 chains in flight together
+                    lo[j] = make_uint4(0, 0, 0, 0); hi[j] = lo[j];
+                    if (act[j]) { const u64 grp = h[j] >> 2; lo[j] = t4[2 * grp]; hi[j] = t4[2 * grp + 1]; }
+                }
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    if (act[j]) {
+                        const uint32_t bk[4] = {lo[j].x, lo[j].z, hi[j].x, hi[j].z};   // keys of the group
+                        const uint32_t bv[4] = {lo[j].y, lo[j].w, hi[j].y, hi[j].w};   // payloads
+                        const uint32_t first = (uint32_t)h[j] & 3u;
+                        bool open = true;                                              // neither an empty bucket nor a match seen yet
+#pragma unroll
+                        for (int b = 0; b < 4; ++b) {
+                            const bool inb = open && ((uint32_t)b >= first);
+                            if (inb && bk[b] == 0u) open = false;
+                            else if (inb && bk[b] == key[j]) { res[j] = bv[b]; nib |= 1u << j; open = false; }
+                        }
+                        if (!open) act[j] = false;
+                        else { h[j] = (h[j] & ~3ull) + 4; if (h[j] >= buckets) h[j] = 0; }
+                    }
+                }
+            }
+        } else {
+            u64 t[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) t[j] = act[j] ? table[h[j]] : 0ull;
+            while (act[0] | act[1] | act[2] | act[3]) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    if (act[j]) {
+                        if ((uint32_t)t[j] == 0u) {
+                            act[j] = false;
+                        } else if ((uint32_t)t[j] == key[j]) {
+                            res[j] = (uint32_t)(t[j] >> 32); nib |= 1u << j;
+                            act[j] = false;
+                        } else {
+                            if (++h[j] == buckets) h[j] = 0;
+                            t[j] = table[h[j]];
+                        }
+                    }
+                }
+            }
+        }
+        npj_lookup_leave<VALS, BITS>(a, v, key, res, nib, acc_n, acc_k, acc_i);
+    }
+    hj_add_to_result(red, a.result, acc_n, acc_k, 0ull, acc_i);
+}
+
+int hj_launch_npj_lookup(const NpjLookupArgs &a, int cus, hipStream_t stream)
+{
+    if (a.n == 0) return HJGPU_OK;
+    if (!a.keys || !a.table || !a.result || a.buckets == 0) return HJGPU_EINVAL;
+    if ((((uintptr_t)a.keys | (uintptr_t)a.vals_out | (uintptr_t)a.match_bits) & 15) || ((uintptr_t)a.table & 7)) return HJGPU_EINVAL;
+    if (a.line_hash && (a.buckets % 8 != 0 || ((uintptr_t)a.table & 63))) return HJGPU_EINVAL;
+    const int grid = hj_npj_probe_grid(cus, a.n);
+    const bool grouped = (a.buckets % 4 == 0) && (((uintptr_t)a.table & 31) == 0);
+    void (*kernel)(NpjLookupArgs) = nullptr;
+    hj_with_bool(a.vals_out != nullptr, [&](auto vals) {
+        hj_with_bool(a.match_bits != nullptr, [&](auto bits) {
+            constexpr bool V = decltype(vals)::value, M = decltype(bits)::value;
+            kernel = a.line_hash ? npj_lookup_line_kernel<V, M> : grouped ? npj_lookup_kernel<true, V, M> : npj_lookup_kernel<false, V, M>;
+        });
+    });
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(NPJ_PROBE_BLOCK), 0, stream, a);
+    return hipGetLastError() == hipSuccess ? HJGPU_OK : HJGPU_EHIP;
+}
+
+// --------------------------------------------------------------------------
 // K9 close_gaps (npj.cpp:475-514).  Input: one end cursor per worker (wave);
 // [cursor, end of its block) is a hole.  The filled region is made the dense
 // prefix [0, J): tuples are taken from the highest filled positions and moved

@@ -325,6 +325,49 @@ int  hjgpu_npj_probe(hjgpu_ctx *ctx, const uint32_t *d_keys, const uint32_t *d_v
                      const uint64_t *d_table, size_t buckets, uint32_t factor,
                      hjgpu_result *result, const hjgpu_output *out, void *stream);
 
+/* ---- NPJ positional look-up (dimension look-up, S.key.map(R)) -------------------------
+ * For every probe key d_outer_keys[i], i in [0, outer), IN THE PROBE COLUMN'S ORDER - NPJ never reorders the probe side; no
+ * probe payload column is read, nothing goes through the block protocol or close_gaps:
+ *   d_vals_out[i]    the payload of a build tuple whose key equals d_outer_keys[i]: the FIRST one the walk meets (with duplicated
+ *                    build keys which copy that is depends on insertion order and is unspecified, as under HJGPU_FLAG_UNIQUE);
+ *                    HJGPU_NULL_VAL when no build key equals it.  No element at index >= outer is written.
+ *   d_match_bits     bit i & 31 (counted from the least significant) of word i >> 5 is 1 exactly when probe key i has a match -
+ *                    what tells a NULL from a genuine build payload 0xFFFFFFFF.  (outer + 31) / 32 words: the bits of the last
+ *                    word at positions >= outer are written 0, no word at index >= (outer + 31) / 32 is written.
+ * Either output may be NULL: the bits alone are the semi-join mask in probe order, the values alone the plain map, and with both
+ * NULL the call returns the aggregates only.
+ *   result           count = the probe tuples with a match, sum_keys = the sum of their keys, sum_outer_vals = 0 (there is no probe
+ *                    payload), sum_inner_vals = the sum of the looked-up payloads (a NULL adds 0).
+ * Keys, as for NPJ everywhere: a build key 0 is HJGPU_EZEROKEY (the blocking form returns it; after the _async form
+ * hjgpu_get_async_status / hjgpu_accumulate_async_status report it), a probe key 0 matches nothing (NULL, bit 0).  inner == 0: every
+ * value NULL, every bit 0, count 0.  outer == 0: nothing is written.
+ * Refusals: d_outer_keys, d_vals_out and d_match_bits must be 16-byte aligned (HJGPU_EALIGN), as the build columns; a capturing
+ * stream is HJGPU_EINVAL as everywhere.  params->flags: HJGPU_FLAG_UNIQUE is ignored (the look-up is first-match by definition), any
+ * join-mode flag (HJGPU_FLAG_SEMI ... HJGPU_FLAG_RIGHT_ANTI) is HJGPU_EINVAL naming the flag.  load and factor mean what they mean
+ * for hjgpu_npj; option "npj_refhash" selects the reference-hash table and its walk, as for whole joins.
+ * hjgpu_get_stats afterwards: ms_build, ms_join, ms_total and buckets as after hjgpu_npj, ms_close_gaps 0.  The _async form is
+ * enqueue-only under hjgpu_npj_async's rules (d_result in device memory, workspace reserved with hjgpu_reserve). */
+int  hjgpu_npj_lookup(hjgpu_ctx *ctx,
+                      const uint32_t *d_inner_keys, const uint32_t *d_inner_vals, size_t inner,
+                      const uint32_t *d_outer_keys, size_t outer,
+                      const hjgpu_npj_params *params,
+                      uint32_t *d_vals_out,      /* outer uint32, or NULL */
+                      uint32_t *d_match_bits,    /* (outer + 31) / 32 uint32, or NULL */
+                      hjgpu_result *result, void *stream);
+int  hjgpu_npj_lookup_async(hjgpu_ctx *ctx,
+                            const uint32_t *d_inner_keys, const uint32_t *d_inner_vals, size_t inner,
+                            const uint32_t *d_outer_keys, size_t outer,
+                            const hjgpu_npj_params *params,
+                            uint32_t *d_vals_out, uint32_t *d_match_bits,
+                            hjgpu_result *d_result, void *stream);
+/* The same look-up in a table that hjgpu_npj_build made (the reference's table format and hash): build once, look up any number
+ * of batches.  buckets and factor as given to hjgpu_npj_build (which reports a build key 0 itself); blocking.  The table must hold
+ * an empty bucket (hjgpu_npj_build: buckets > n), or the walk of an absent key never ends. */
+int  hjgpu_npj_lookup_table(hjgpu_ctx *ctx, const uint32_t *d_keys, size_t n,
+                            const uint64_t *d_table, size_t buckets, uint32_t factor,
+                            uint32_t *d_vals_out, uint32_t *d_match_bits,
+                            hjgpu_result *result, void *stream);
+
 /* ---- whole joins on HBM-resident columns (replace run()/run_hj()) ---------------- */
 /* run(), npj.cpp:769-927 */
 int  hjgpu_npj(hjgpu_ctx *ctx,
