@@ -599,9 +599,9 @@ static size_t build_bits_bytes(const PhjPlan &pl, size_t inner)
     return ((rows + 31) / 32 + 2) * sizeof(uint32_t);
 }
 
-int phj_prepare(hjgpu_ctx *ctx, size_t inner, size_t outer, const hjgpu_phj_params *prm,
-                uint32_t chunks, PhjPlan *pl, bool pre, int big_override, size_t plan_inner, bool claim_s)
+int phj_prepare(hjgpu_ctx *ctx, size_t inner, size_t outer, const hjgpu_phj_params *prm, uint32_t chunks, PhjPlan *pl, const PrepareOpts &o)
 {
+    const bool pre = o.pre;
     ctx->prepared = false;               // the workspace is about to be re-planned (hjgpu_phj_build sets it again)
     ReserveClock clock(ctx);
     pl->C = chunks;
@@ -611,8 +611,8 @@ int phj_prepare(hjgpu_ctx *ctx, size_t inner, size_t outer, const hjgpu_phj_para
     // (a right outer join is planned like the inner join: fill groups, one launch; right semi- and anti-joins like the _UNIQUE join: one
     // fill group per probe slice, single-fill and multi-fill items in launches of their own)
     pl->unique = pl->first_match || (pl->mode != HJ_MODE_INNER && pl->mode != HJ_MODE_RIGHT_OUTER);
-    choose_fanout(ctx->tune, plan_inner ? plan_inner : inner, prm, &pl->F1, &pl->F2, &pl->big_tables);
-    if (big_override >= 0) pl->big_tables = big_override != 0;
+    choose_fanout(ctx->tune, o.plan_inner ? o.plan_inner : inner, prm, &pl->F1, &pl->F2, &pl->big_tables);
+    if (o.big_tables >= 0) pl->big_tables = o.big_tables != 0;
     if (chunks > 8 && !pre) {
         // More than 8 chunks (the reference takes any #threads, cpra2.cpp:2023): always two passes with line-aligned final
         // partitions - every chunk's pass-2 tiles then write ONE shared region per final partition and the join sees a single
@@ -646,7 +646,7 @@ int phj_prepare(hjgpu_ctx *ctx, size_t inner, size_t outer, const hjgpu_phj_para
     // regions of cap2 tuples.  Both are optimistic: hashed keys spread evenly, and a region that is full flags the join, which the
     // blocking call then does again on the exact path (phj_like).
     pl->claim_s = 0; pl->cap1 = pl->cap2 = 0;
-    if (claim_s && !pre && pl->C == 1 && pl->F2 > 1 && !ctx->tune.dense2 && ctx->tune.batch_tuples <= 0 && outer) {
+    if (o.claim_s && !pre && pl->C == 1 && pl->F2 > 1 && !ctx->tune.dense2 && ctx->tune.batch_tuples <= 0 && outer) {
         const ScatterConfig c1 = hj_scatter_config(ctx->tune, 1, pl->F1, true);
         if (c1.carry && c1.block == 1024 && (c1.vpt == 4 || c1.vpt == 3)) {
             pl->claim_s = 1;
@@ -708,129 +708,174 @@ int phj_prepare(hjgpu_ctx *ctx, size_t inner, size_t outer, const hjgpu_phj_para
     return HJGPU_OK;
 }
 
-int phj_enqueue(hjgpu_ctx *ctx, const PhjPlan &pl,
-                const uint32_t *rk, const uint32_t *rv, size_t inner,
-                const uint32_t *sk, const uint32_t *sv, size_t outer,
-                const hjgpu_output *out, hipStream_t stream, hipEvent_t inner_ready, PhjMode mode, const PrePieces *pre, const GroupRun *grp)
-{
-    CHK(refuse_capture(ctx, stream));
-    if (grp && (pre || mode != PHJ_WHOLE || inner_ready)) return fail(ctx, HJGPU_EINVAL, "internal: a device-planned group is a whole join on resident columns");
-    if ((pre != nullptr) != (pl.pre != 0)) return fail(ctx, HJGPU_EINVAL, "internal: plan and relations disagree about pre-partitioning");
-    MetaLayout m = carve(ctx->meta.p, pl.C, pl.F1, pl.P, pl.ranges, pl.items_extra, pl.tiles2, pl.batch_cap, pl.tdesc_b_cap);
-    DevState *st = reinterpret_cast<DevState *>(ctx->state.p);
-    const uint32_t workers = (uint32_t)hj_join_workers(ctx->tune, ctx->cus, pl.big_tables);
-    u64 bs = 0, bl = 0;
-    CHK(setup_output(ctx, out, workers, &bs, &bl, pl.mode));
+// ---- phj_enqueue: the roads of one call and their stages ("Roads of the PHJ enqueue path") ----
+namespace {
 
-    record(ctx, EV_BEGIN, stream);
-    u64 *audit = nullptr;                // option "audit": this call's record (else NULL: nothing below is enqueued)
-    if (!grp) CHK(audit_begin(ctx, (int)mode, inner, outer, stream, &audit));   // (device-planned groups are not audited: option "audit" selects the host-planned form)
-    // counts[0] | counts[1] | tickets are contiguous: a whole join zeroes all, a prepared build its own
-    // histogram and the tickets, a probe of a prepared build the probe side's histogram and the tickets
+const int EV_OF_S[4] = {EV_S_HIST, EV_S_PLAN, EV_S_SC1, EV_S_SC2};     // after hist, after plan, after pass 1, after pass 2
+const int EV_OF_R[4] = {EV_R_HIST, EV_R_PLAN, EV_R_SC1, EV_R_SC2};
+
+// Which way a call goes, decided once from the plan and the call
+struct PhjRoad {
+    bool pad2;      // two-pass plans: final partitions start on 128-byte lines (pass 2 claims whole lines); option "dense2": dense
+    bool merged;    // both relations are there from the start: their stages run side by side, ONE set of plan launches (a group: always)
+    bool claim;     // merged, and the probe side is partitioned without its histogram (PhjPlan::claim_s)
+    bool joins;     // the call runs a join: there are build rows, and probe rows or a mode that reports build rows alone
+};
+
+PhjRoad phj_road(const hjgpu_ctx *ctx, const PhjPlan &pl, const Rel &R, const Rel &S, const EnqueueOpts &o)
+{
+    PhjRoad w;
+    const bool audited = ctx->tune.audit && !o.grp;      // (device-planned groups are not audited: the option selects the host-planned form)
+    w.pad2 = pl.F2 > 1 && !ctx->tune.dense2;
+    const bool resident = o.stages == PHJ_WHOLE && !o.inner_ready && !o.pre;      // nothing to wait for, nothing prepared
+    w.merged = o.grp || (resident && !pl.batch_ranges && ctx->tune.merged_plan);
+    w.claim = w.merged && !o.grp && pl.claim_s && !audited && pl.C == 1 && w.pad2;
+    w.joins = R.rows && (S.rows || hj_mode_build_alone(pl.mode)) && o.stages != PHJ_BUILD_ONLY;
+    return w;
+}
+
+// What one phj_enqueue call sets up once, and the stages it strings together.  Relation 0 is the build side R, 1 the probe side S.
+struct PhjRun {
+    hjgpu_ctx *ctx;
+    const PhjPlan &pl;
+    const EnqueueOpts &o;
+    const PhjRoad road;
+    hipStream_t stream;
+    MetaLayout m;
+    DevState *st;
+    Pass1Geom geom[2];
+    const uint32_t *in_k[2], *in_v[2];   // the caller's columns
+    size_t nn[2];                        // and their rows
+    uint32_t *t1[4], *t2[4];             // pass-1 / pass-2 twins: packed tuples in [0] (R) and [2] (S)
+    PlanArgs pa;
+    const u64 *dyn[2];                   // a device-planned group: {first row, rows} of R / S in device memory
+    u64 *audit = nullptr;                // option "audit": this call's record (else NULL: no audit stage is enqueued)
+    bool p_major = false;
+    uint32_t batches_used = 0;
+
+    PhjRun(hjgpu_ctx *c, const PhjPlan &p, const Rel &R, const Rel &S, const EnqueueOpts &opts, hipStream_t s)
+        : ctx(c), pl(p), o(opts), road(phj_road(c, p, R, S, opts)), stream(s),
+          m(carve(c->meta.p, p.C, p.F1, p.P, p.ranges, p.items_extra, p.tiles2, p.batch_cap, p.tdesc_b_cap)),
+          st(reinterpret_cast<DevState *>(c->state.p)),
+          geom{make_geom(c->tune, R.keys, R.rows, p.C, p.F1, true), make_geom(c->tune, S.keys, S.rows, p.C, p.F1, true)},
+          in_k{R.keys, S.keys}, in_v{R.vals, S.vals}, nn{R.rows, S.rows},
+          t1{(uint32_t *)c->tmp[0].p, nullptr, (uint32_t *)c->tmp[2].p, nullptr},
+          t2{(uint32_t *)c->tmp[4].p, nullptr, (uint32_t *)c->tmp[6].p, nullptr},
+          dyn{opts.grp ? opts.grp->desc : nullptr, opts.grp ? opts.grp->desc + 2 : nullptr} {}
+
+    bool pieces(int r) const { return o.pre && o.pre->tuples[r]; }
+
+    // geometry and plan arguments (host only: nothing is enqueued)
+    int setup()
     {
+        for (int r = 0; r < 2; ++r) {
+            if (pieces(r)) geom[r].align = 0;       // (the pieces' bounds go to the plan kernels as they are: pa.chunk_beg below)
+            if (!o.pre && (size_t)geom[r].ranges_per_chunk * pl.C > pl.ranges)
+                return fail(ctx, HJGPU_EINVAL, "internal: the relation needs more pass-1 ranges than the plan's tables hold");
+        }
+        pa = plan_args(ctx, m, pl.C, pl.F1, pl.F2, (uint32_t)hj_scatter_tile(ctx->tune, 1, pl.F1, true),
+                       (uint32_t)hj_scatter_tile(ctx->tune, 2, pl.F2, true), pl.unique, 0u);
+        pa.cap = (uint32_t)hj_join_config_of(ctx->tune, pl.big_tables).cap();
+        pa.tdesc_cap = (uint32_t)m.tdesc_cap;
+        pa.multi_fill = m.tickets + HJ_TICKET_MULTI_FILL;          // zeroed with the tickets; counted by the work-item plan, read by the _UNIQUE join
+        pa.anti = hj_mode_keeps_unmatched(pl.mode) ? 1u : 0u;
+        pa.pad2 = road.pad2 ? 1u : 0u;
+        // chunked relations (one-GPU CPRA): the chunks' regions of a pass-1 partition side by side, so that pass 2 and the join
+        // see what they see after an unchunked pass 1 (the pieces of a pre-partitioned relation lie where they arrived)
+        p_major = pl.C > 1 && road.pad2 && !o.pre;
+        pa.p_major = p_major ? 1u : 0u;
+        pa.seg_interleave = (o.pre && pl.C > 1 && road.pad2 && ctx->tune.piece_interleave) ? 1u : 0u;
+        if (road.claim) pa.s_cap2 = pl.cap2;
+        for (int r = 0; r < 2; ++r) {
+            pa.tdesc[r] = m.tdesc[r]; pa.seg2[r] = m.seg2[r]; pa.more[r] = m.more[r]; pa.dyn[r] = dyn[r];
+            // pre-partitioned pieces sit at absolute rows [b[0], b[C]) of the caller's array
+            pa.n[r] = pieces(r) ? o.pre->ch[r].b[pl.C] : nn[r];
+            pa.regular[r] = pieces(r) ? 0u : 1u; pa.chunk_part[r] = geom[r].part;
+            for (uint32_t c = 0; c < 9; ++c) pa.chunk_beg[r][c] = pieces(r) ? o.pre->ch[r].b[c <= pl.C ? c : pl.C] : geom[r].beg(c);
+            pa.in_align[r] = o.pre ? 0u : align_of(in_k[r]);
+        }
+        return HJGPU_OK;
+    }
+
+    // the audit record, and the per-join zeroes.  counts[0] | counts[1] | tickets are contiguous: a whole join zeroes all, a prepared
+    // build its own histogram and the tickets, a probe of a prepared build the probe side's histogram and the tickets
+    int begin()
+    {
+        if (!o.grp) CHK(audit_begin(ctx, (int)o.stages, nn[0], nn[1], stream, &audit));
         unsigned char *z0 = reinterpret_cast<unsigned char *>(m.counts[0]);
         unsigned char *z1 = reinterpret_cast<unsigned char *>(m.counts[1]);
         unsigned char *zt = reinterpret_cast<unsigned char *>(m.tickets);
         unsigned char *ze = z0 + m.counts_bytes;
-        if (mode == PHJ_WHOLE) HIPCHK(ctx, hj_zero_async(z0, m.counts_bytes, stream));
-        if (mode == PHJ_BUILD_ONLY) {
+        if (o.stages == PHJ_WHOLE) HIPCHK(ctx, hj_zero_async(z0, m.counts_bytes, stream));
+        if (o.stages == PHJ_BUILD_ONLY) {
             HIPCHK(ctx, hj_zero_async(z0, (size_t)(z1 - z0), stream));
             HIPCHK(ctx, hj_zero_async(zt, (size_t)(ze - zt), stream));
         }
-        if (mode == PHJ_PROBE_ONLY) HIPCHK(ctx, hj_zero_async(z1, (size_t)(ze - z1), stream));
+        if (o.stages == PHJ_PROBE_ONLY) HIPCHK(ctx, hj_zero_async(z1, (size_t)(ze - z1), stream));
+        if (o.stages != PHJ_BUILD_ONLY && !o.grp) HIPCHK(ctx, hj_zero_async(st, sizeof(DevState), stream));      // (a group: the grouped join's state goes on)
+        return HJGPU_OK;
     }
-    if (mode != PHJ_BUILD_ONLY && !grp) HIPCHK(ctx, hj_zero_async(st, sizeof(DevState), stream));      // (a group: the grouped join's state goes on)
 
-    Pass1Geom geom[2] = {make_geom(ctx->tune, rk, inner, pl.C, pl.F1, true), make_geom(ctx->tune, sk, outer, pl.C, pl.F1, true)};
-    if (pre)
-        for (int r = 0; r < 2; ++r) {
-            if (!pre->tuples[r]) continue;
-            geom[r].align = 0;                  // (the pieces' bounds go to the plan kernels as they are: pa.chunk_beg below)
-        }
-    for (int r = 0; r < 2; ++r)
-        if (!pre && (size_t)geom[r].ranges_per_chunk * pl.C > pl.ranges)
-            return fail(ctx, HJGPU_EINVAL, "internal: the relation needs more pass-1 ranges than the plan's tables hold");
-    const uint32_t *in_k[2] = {rk, sk}, *in_v[2] = {rv, sv};
-    const size_t nn[2] = {inner, outer};
-    uint32_t *t1[4] = {(uint32_t *)ctx->tmp[0].p, nullptr, (uint32_t *)ctx->tmp[2].p, nullptr};
-    uint32_t *t2[4] = {(uint32_t *)ctx->tmp[4].p, nullptr, (uint32_t *)ctx->tmp[6].p, nullptr};
-    PlanArgs pa = plan_args(ctx, m, pl.C, pl.F1, pl.F2, (uint32_t)hj_scatter_tile(ctx->tune, 1, pl.F1, true),
-                            (uint32_t)hj_scatter_tile(ctx->tune, 2, pl.F2, true), pl.unique, 0u);
-    pa.cap = (uint32_t)hj_join_config_of(ctx->tune, pl.big_tables).cap();
-    for (int r = 0; r < 2; ++r) { pa.tdesc[r] = m.tdesc[r]; pa.seg2[r] = m.seg2[r]; pa.more[r] = m.more[r]; }
-    pa.tdesc_cap = (uint32_t)m.tdesc_cap;
-    const u64 *dyn[2] = {grp ? grp->desc : nullptr, grp ? grp->desc + 2 : nullptr};           // {first row, rows} of R / S in device memory
-    pa.dyn[0] = dyn[0]; pa.dyn[1] = dyn[1];
-    pa.multi_fill = m.tickets + HJ_TICKET_MULTI_FILL;          // zeroed with the tickets; counted by the work-item plan, read by the _UNIQUE join
-    pa.anti = hj_mode_keeps_unmatched(pl.mode) ? 1u : 0u;
-    // two-pass plans: final partitions start on 128-byte lines (pass 2 claims whole lines); option "dense2": dense
-    const bool pad2 = pl.F2 > 1 && !ctx->tune.dense2;
-    pa.pad2 = pad2 ? 1u : 0u;
-    pa.n[0] = inner; pa.n[1] = outer;
-    // chunked relations (one-GPU CPRA): the chunks' regions of a pass-1 partition side by side, so that pass 2 and the join
-    // see what they see after an unchunked pass 1 (the pieces of a pre-partitioned relation lie where they arrived)
-    const bool p_major = pl.C > 1 && pad2 && !pre;
-    pa.p_major = p_major ? 1u : 0u;
-    pa.seg_interleave = (pre && pl.C > 1 && pad2 && ctx->tune.piece_interleave) ? 1u : 0u;
-    // pre-partitioned pieces sit at absolute rows [b[0], b[C]) of the caller's array
-    if (pre) for (int r = 0; r < 2; ++r) if (pre->tuples[r]) pa.n[r] = pre->ch[r].b[pl.C];
-    for (int r = 0; r < 2; ++r) {
-        const bool pieces = pre && pre->tuples[r];
-        pa.regular[r] = pieces ? 0u : 1u; pa.chunk_part[r] = geom[r].part;
-        for (uint32_t c = 0; c < 9; ++c) pa.chunk_beg[r][c] = pieces ? pre->ch[r].b[c <= pl.C ? c : pl.C] : geom[r].beg(c);
-    }
-    pa.in_align[0] = pre ? 0u : align_of(rk); pa.in_align[1] = pre ? 0u : align_of(sk);
-
-    uint32_t batches_used = 0;
     // option "audit" (audit_kernels.hip): stage 0 / 3 the relation as it is read, 1 / 4 its pass-1 output, 2 / 5 its final partitions
-    auto audit_input = [&](int r) -> int {
+    int audit_input(int r)
+    {
         if (!audit || !nn[r]) return HJGPU_OK;
         u64 *rec = audit + 4 * (r ? 0 : 3);
-        if (pre) return pre->tuples[r] ? hj_audit_sums_packed(pre->tuples[r], pre->ch[r].b[0], pre->ch[r].b[pl.C], rec, ctx->cus, stream) : HJGPU_OK;
+        if (o.pre) return o.pre->tuples[r] ? hj_audit_sums_packed(o.pre->tuples[r], o.pre->ch[r].b[0], o.pre->ch[r].b[pl.C], rec, ctx->cus, stream) : HJGPU_OK;
         return in_k[r] ? hj_audit_sums_columns(in_k[r], in_v[r], nn[r], rec, ctx->cus, stream) : HJGPU_OK;
-    };
-    auto audit_pass1 = [&](int r) -> int {
-        if (!audit || !nn[r] || pre || pl.C != 1 || pl.F2 <= 1) return HJGPU_OK;
+    }
+    int audit_pass1(int r)
+    {
+        if (!audit || !nn[r] || o.pre || pl.C != 1 || pl.F2 <= 1) return HJGPU_OK;
         const HjAuditHash h = {pl.f1, pl.F1, 0u, 1u, 1u, pl.F1};
         return audit_partitions(ctx, r ? 1 : 4, reinterpret_cast<const u64 *>(ctx->tmp[2 * r].p), m.off1[r], nullptr, pl.F1, h, audit, stream);
-    };
-    auto audit_final = [&](int r) -> int {
+    }
+    int audit_final(int r)
+    {
         if (!audit || !nn[r]) return HJGPU_OK;
         const bool two = pl.F2 > 1;
         const u64 *fin_r = reinterpret_cast<const u64 *>(two ? ctx->tmp[4 + 2 * r].p : ctx->tmp[2 * r].p);
-        const HjAuditHash h = {pre ? pl.pre_f1 : pl.f1, pre ? pl.pre_F1tot : pl.F1, pre ? pl.pre_base : 0u, pl.f2, pl.F2, pl.P};
-        return audit_partitions(ctx, r ? 2 : 5, fin_r, m.off2[r], m.end2[r], (pad2 ? 1u : pl.C) * pl.P, h, audit, stream);
-    };
-    // the stages of one relation's partitioning
-    auto k4 = [&](int r) -> int {          // one read of the key column gives the histograms of both passes
-        if (nn[r]) CHK(hj_launch_hist2(in_k[r], geom[r], pl.f1, pl.F1, pl.f2, pl.F2, m.counts[r],
-                                       m.range_counts[r], m.tickets + HJ_TICKET_K4 + HJ_MAX_CHUNKS * r, ctx->cus, stream, 0, dyn[r]));
-        return HJGPU_OK;
-    };
-    auto k5b = [&](int r) -> int {
-        if (nn[r]) CHK(hj_launch_range_base(m.range_counts[r], m.off1[r], m.range_base[r], pl.C,
-                                            geom[r].ranges_per_chunk, pl.F1, stream));
-        return HJGPU_OK;
-    };
-    // claimed probe side (PhjPlan::claim_s): only in the merged form of a blocking whole join
-    const bool claim = pl.claim_s && mode == PHJ_WHOLE && !pre && !grp && !inner_ready && !audit && pl.C == 1 && pad2 &&
-                       !pl.batch_ranges && ctx->tune.merged_plan;
-    if (claim) pa.s_cap2 = pl.cap2;
-    auto pass1 = [&](int r) -> int {       // K6 pass 1: caller's columns -> tmp[0..3]
+        const HjAuditHash h = {o.pre ? pl.pre_f1 : pl.f1, o.pre ? pl.pre_F1tot : pl.F1, o.pre ? pl.pre_base : 0u, pl.f2, pl.F2, pl.P};
+        return audit_partitions(ctx, r ? 2 : 5, fin_r, m.off2[r], m.end2[r], (road.pad2 ? 1u : pl.C) * pl.P, h, audit, stream);
+    }
+
+    // K4: one read of the key column gives the histograms of both passes
+    int histogram(int r)
+    {
+        if (!nn[r]) return HJGPU_OK;
+        return hj_launch_hist2(in_k[r], geom[r], pl.f1, pl.F1, pl.f2, pl.F2, m.counts[r],
+                               m.range_counts[r], m.tickets + HJ_TICKET_K4 + HJ_MAX_CHUNKS * r, ctx->cus, stream, 0, dyn[r]);
+    }
+    // K5 (+ the join's work items where the mask says so)
+    int plan(uint32_t mask)
+    {
+        pa.mask = mask;
+        return hj_launch_plan(pa, stream);
+    }
+    // K5b
+    int range_bases(int r)
+    {
+        if (!nn[r]) return HJGPU_OK;
+        return hj_launch_range_base(m.range_counts[r], m.off1[r], m.range_base[r], pl.C, geom[r].ranges_per_chunk, pl.F1, stream);
+    }
+    // K6 pass 1: caller's columns -> tmp[0..3]
+    int pass1(int r)
+    {
         if (!nn[r]) return HJGPU_OK;
         ScatterArgs sa = scatter_pass1(ctx, m, r, geom[r], pl.F1, pl.f1, in_k[r], in_v[r], t1[2 * r], t1[2 * r + 1]);
         sa.dyn = dyn[r];
-        if (claim && r == 1) {
+        if (road.claim && r == 1) {
             sa.range_base = nullptr;
             sa.claim_cursors = m.claim1; sa.claim_cap = pl.cap1; sa.claim_overflow = &st->probe_overflow;
         }
         return hj_launch_scatter(sa, ctx->tune, scatter_cus(ctx), stream);
-    };
+    }
     // K6 pass 2: packed tuples `in` -> tmp[4..7] - pass 1's output in tmp[0..3], the pieces of a pre-partitioned relation, or the buffer of
     // one batch of the probe side (batch >= 0)
-    auto pass2 = [&](int r, const uint32_t *in, int batch) -> int {
+    int pass2(int r, const uint32_t *in, int batch)
+    {
         if (!nn[r] || pl.F2 <= 1) return HJGPU_OK;
-        ScatterArgs sa = scatter_pass2(ctx, m, r, geom[r], pl, pad2, in, t2[2 * r]);
+        ScatterArgs sa = scatter_pass2(ctx, m, r, geom[r], pl, road.pad2, in, t2[2 * r]);
         if (p_major) { sa.seg_off = m.seg2[r]; sa.nseg = pl.F1; }     // one segment per pass-1 partition
         if (batch >= 0) {
             // the batch's own pass-1 layout, pass-2 tiles and ticket
@@ -838,73 +883,81 @@ int phj_enqueue(hjgpu_ctx *ctx, const PhjPlan &pl,
             sa.seg_off = m.boff + b * (pl.F1 + 1); sa.tile_prefix = m.tp2b + b * (pl.F1 + 1);
             sa.tile_desc = m.tdescb + b * pl.tdesc_b_cap * 2; sa.nseg = pl.F1; sa.work_counter = m.btickets + 2 * b + 1;
         }
-        if (claim && r == 1) {
+        if (road.claim && r == 1) {
             // the tiles hj_launch_claimed_desc planned from pass 1's cursors; regions that fill up flag the join
             sa.tile_prefix = m.claim_total; sa.nseg = 0; sa.seg_off = nullptr;
             sa.claim_overflow = &st->probe_overflow;
         }
         return hj_launch_scatter(sa, ctx->tune, scatter_cus(ctx), stream);
-    };
-    // K4 -> K5 -> K6 x2 for one relation; ev = {after hist, after plan, after pass 1, after pass 2}
-    auto partition_relation = [&](int r, uint32_t plan_mask, const int ev[4]) -> int {
-        if (pre) {
-            // The relation arrives pass-1-partitioned (multi-GPU CPRA: the exchange-level partitioning of the senders'
-            // chunks was pass 1, cpra2.cpp:1757-1827): K4p counts per (piece, final partition), K5 lays pass 2 out,
-            // K6 pass 2 reads the pieces where they are.  16 + 8 bytes per tuple less than partitioning from scratch.
-            if (nn[r] && pre->counts[r])
-                HIPCHK(ctx, hj_copy_async(m.counts[r], pre->counts[r], (size_t)pl.C * pl.P * sizeof(u64), stream));
-            else if (nn[r]) CHK(hj_launch_hist_packed(pre->tuples[r], pre->ch[r], pl.pre_f1, pl.pre_F1tot, pl.pre_base, pl.F1,
-                                                      pl.f2, pl.F2, m.counts[r], ctx->cus, stream));
-            record(ctx, ev[0], stream);
-            pa.mask = plan_mask;
-            CHK(hj_launch_plan(pa, stream));
-            record(ctx, ev[1], stream);
-            record(ctx, ev[2], stream);
-            CHK(pass2(r, reinterpret_cast<const uint32_t *>(pre->tuples[r]), -1));
-            record(ctx, ev[3], stream);
-            CHK(audit_input(r)); CHK(audit_final(r));
-            return HJGPU_OK;
-        }
-        CHK(k4(r));
+    }
+
+    // The relation arrives pass-1-partitioned (the exchange-level partitioning of the multi-GPU CPRA was pass 1, cpra2.cpp:1757-1827): pass 2
+    // reads the pieces where they are, 16 + 8 bytes per tuple less than partitioning from scratch.
+    int partition_pieces(int r, uint32_t plan_mask, const int ev[4])
+    {
+        if (nn[r] && o.pre->counts[r])
+            HIPCHK(ctx, hj_copy_async(m.counts[r], o.pre->counts[r], (size_t)pl.C * pl.P * sizeof(u64), stream));
+        else if (nn[r]) CHK(hj_launch_hist_packed(o.pre->tuples[r], o.pre->ch[r], pl.pre_f1, pl.pre_F1tot, pl.pre_base, pl.F1,
+                                                  pl.f2, pl.F2, m.counts[r], ctx->cus, stream));
         record(ctx, ev[0], stream);
-        // K5 (+ the join's work items once both histograms exist), K5b
-        pa.mask = plan_mask;
-        CHK(hj_launch_plan(pa, stream));
-        // batched probe side: the tables must hold this relation's batches and tiles per range
-        uint32_t batches = 0;
-        if (r == 1 && pl.batch_ranges && nn[r]) {
-            const u64 tiles = hj_tiles_of(0, nn[r], geom[r].align, geom[r].tile);
-            const u64 k = (tiles + geom[r].ranges_per_chunk - 1) / geom[r].ranges_per_chunk;
-            const u64 nb = (geom[r].ranges_per_chunk + pl.batch_ranges - 1) / pl.batch_ranges;
-            if (k + 1 <= pl.batch_tile_cap && nb <= pl.batch_cap && nb >= 2) batches = (uint32_t)nb;
+        CHK(plan(plan_mask));
+        record(ctx, ev[1], stream);
+        record(ctx, ev[2], stream);
+        CHK(pass2(r, reinterpret_cast<const uint32_t *>(o.pre->tuples[r]), -1));
+        record(ctx, ev[3], stream);
+        CHK(audit_input(r)); CHK(audit_final(r));
+        return HJGPU_OK;
+    }
+
+    // batches of a batched probe side (0: not batched): the tables must hold this relation's batches and tiles per range
+    uint32_t probe_batches() const
+    {
+        const int r = 1;
+        if (!pl.batch_ranges || !nn[r]) return 0;
+        const u64 tiles = hj_tiles_of(0, nn[r], geom[r].align, geom[r].tile);
+        const u64 k = (tiles + geom[r].ranges_per_chunk - 1) / geom[r].ranges_per_chunk;
+        const u64 nb = (geom[r].ranges_per_chunk + pl.batch_ranges - 1) / pl.batch_ranges;
+        return (k + 1 <= pl.batch_tile_cap && nb <= pl.batch_cap && nb >= 2) ? (uint32_t)nb : 0;
+    }
+    // The probe side in batches: pass 1 of a batch into one of two small buffers and pass 2 straight from it
+    int partition_batched(uint32_t plan_mask, const int ev[4], uint32_t batches)
+    {
+        const int r = 1;
+        CHK(histogram(r));
+        record(ctx, ev[0], stream);
+        CHK(plan(plan_mask));
+        BatchPlanArgs ba;
+        ba.range_counts = m.range_counts[r]; ba.range_base = m.range_base[r]; ba.boff = m.boff; ba.tp2b = m.tp2b;
+        ba.tdesc = m.tdescb; ba.tdesc_cap = (uint32_t)pl.tdesc_b_cap; ba.ranges = geom[r].ranges_per_chunk;
+        ba.ranges_per_batch = pl.batch_ranges; ba.F1 = pl.F1; ba.F2 = pl.F2;
+        ba.tile2 = (uint32_t)hj_scatter_tile(ctx->tune, 2, pl.F2, true);
+        CHK(hj_launch_batch_plan(ba, batches, stream));
+        HIPCHK(ctx, hj_zero_async(m.btickets, m.btickets_bytes, stream));
+        record(ctx, ev[1], stream);
+        for (uint32_t b = 0; b < batches; ++b) {
+            uint32_t *tbuf = (uint32_t *)ctx->tmp[1 + 2 * (b & 1)].p;
+            // pass 1 of the batch: the caller's columns -> the batch buffer (dense, from offset 0)
+            ScatterArgs sa = scatter_pass1(ctx, m, r, geom[r], pl.F1, pl.f1, in_k[r], in_v[r], tbuf, nullptr);
+            sa.work_counter = m.btickets + 2 * b;
+            sa.range_begin = b * pl.batch_ranges;
+            sa.range_count = std::min(pl.batch_ranges, geom[r].ranges_per_chunk - sa.range_begin);
+            CHK(hj_launch_scatter(sa, ctx->tune, scatter_cus(ctx), stream));
+            // pass 2 of the batch: the batch buffer -> the relation's final, line-aligned partitions
+            CHK(pass2(r, tbuf, (int)b));
         }
-        if (batches) {
-            BatchPlanArgs ba;
-            ba.range_counts = m.range_counts[r]; ba.range_base = m.range_base[r]; ba.boff = m.boff; ba.tp2b = m.tp2b;
-            ba.tdesc = m.tdescb; ba.tdesc_cap = (uint32_t)pl.tdesc_b_cap; ba.ranges = geom[r].ranges_per_chunk;
-            ba.ranges_per_batch = pl.batch_ranges; ba.F1 = pl.F1; ba.F2 = pl.F2;
-            ba.tile2 = (uint32_t)hj_scatter_tile(ctx->tune, 2, pl.F2, true);
-            CHK(hj_launch_batch_plan(ba, batches, stream));
-            HIPCHK(ctx, hj_zero_async(m.btickets, m.btickets_bytes, stream));
-            record(ctx, ev[1], stream);
-            for (uint32_t b = 0; b < batches; ++b) {
-                uint32_t *tbuf = (uint32_t *)ctx->tmp[1 + 2 * (b & 1)].p;
-                // pass 1 of the batch: the caller's columns -> the batch buffer (dense, from offset 0)
-                ScatterArgs sa = scatter_pass1(ctx, m, r, geom[r], pl.F1, pl.f1, in_k[r], in_v[r], tbuf, nullptr);
-                sa.work_counter = m.btickets + 2 * b;
-                sa.range_begin = b * pl.batch_ranges;
-                sa.range_count = std::min(pl.batch_ranges, geom[r].ranges_per_chunk - sa.range_begin);
-                CHK(hj_launch_scatter(sa, ctx->tune, scatter_cus(ctx), stream));
-                // pass 2 of the batch: the batch buffer -> the relation's final, line-aligned partitions
-                CHK(pass2(r, tbuf, (int)b));
-            }
-            record(ctx, ev[2], stream);         // both passes interleaved: reported as pass 1, pass 2 = 0
-            record(ctx, ev[3], stream);
-            batches_used = batches;
-            CHK(audit_input(r)); CHK(audit_final(r));
-            return HJGPU_OK;
-        }
-        CHK(k5b(r));
+        record(ctx, ev[2], stream);         // both passes interleaved: reported as pass 1, pass 2 = 0
+        record(ctx, ev[3], stream);
+        batches_used = batches;
+        CHK(audit_input(r)); CHK(audit_final(r));
+        return HJGPU_OK;
+    }
+    // K4 -> K5 -> K5b -> K6 x2
+    int partition_plain(int r, uint32_t plan_mask, const int ev[4])
+    {
+        CHK(histogram(r));
+        record(ctx, ev[0], stream);
+        CHK(plan(plan_mask));
+        CHK(range_bases(r));
         record(ctx, ev[1], stream);
         CHK(pass1(r));
         record(ctx, ev[2], stream);
@@ -912,71 +965,75 @@ int phj_enqueue(hjgpu_ctx *ctx, const PhjPlan &pl,
         record(ctx, ev[3], stream);
         CHK(audit_input(r)); CHK(audit_pass1(r)); CHK(audit_final(r));
         return HJGPU_OK;
-    };
-    const int ev_s[4] = {EV_S_HIST, EV_S_PLAN, EV_S_SC1, EV_S_SC2};
-    const int ev_r[4] = {EV_R_HIST, EV_R_PLAN, EV_R_SC1, EV_R_SC2};
-    // Both relations are there from the start (hjgpu_phj / hjgpu_cpra on resident columns: nothing to wait for): their
-    // stages run side by side - K4 of R and S, then ONE set of K5 launches that plans both relations and the join's work
-    // items (the plan kernels are single-workgroup, latency-bound: two sets cost twice the latency, 0.15 ms per step),
-    // then pass 1 of both, then pass 2 of both.  The phase events are recorded at the stage boundaries, so
-    // hjgpu_get_stats keeps its meaning (histogram / plan / pass 1 / pass 2 of R and S together).
-    const bool merged = grp || (mode == PHJ_WHOLE && !inner_ready && !pre && !pl.batch_ranges && ctx->tune.merged_plan);   // (a group: always)
-    if (merged) {
-        // (a claimed probe side has neither K4 nor range bases: pass 1 claims lines, and the plan of its pass 2 follows pass 1)
-        CHK(k4(0)); if (!claim) CHK(k4(1));
+    }
+    int partition_relation(int r, uint32_t plan_mask, const int ev[4])
+    {
+        if (o.pre) return partition_pieces(r, plan_mask, ev);
+        const uint32_t batches = r == 1 ? probe_batches() : 0;
+        return batches ? partition_batched(plan_mask, ev, batches) : partition_plain(r, plan_mask, ev);
+    }
+
+    // One relation after the other, the probe side first: the build side may still be arriving (inner_ready)
+    int partition_in_turn()
+    {
+        if (o.stages != PHJ_BUILD_ONLY) CHK(partition_relation(1, 2u, EV_OF_S));
+        else for (int e : EV_OF_S) record(ctx, e, stream);
+        if (o.inner_ready) HIPCHK(ctx, hipStreamWaitEvent(stream, o.inner_ready, 0));
+        record(ctx, EV_WAITED, stream);
+        if (o.stages == PHJ_WHOLE) CHK(partition_relation(0, 1u | 4u, EV_OF_R));       // build side + join work items
+        if (o.stages == PHJ_BUILD_ONLY) CHK(partition_relation(0, 1u, EV_OF_R));       // build side; work items come with a probe
+        if (o.stages == PHJ_PROBE_ONLY) {
+            record(ctx, EV_OF_R[0], stream);
+            CHK(plan(4u));
+            for (int i = 1; i < 4; ++i) record(ctx, EV_OF_R[i], stream);
+            CHK(audit_final(0));               // the prepared build side, as this probe finds it
+        }
+        return HJGPU_OK;
+    }
+
+    // Both relations side by side, with ONE set of K5 launches (single-workgroup, latency-bound: two sets cost 0.15 ms per step more).  The
+    // phase events are recorded at the stage boundaries: hjgpu_get_stats reports the stages of R and S together.
+    // (a claimed probe side has neither K4 nor range bases: pass 1 claims lines, and the plan of its pass 2 follows pass 1)
+    int partition_merged()
+    {
+        CHK(histogram(0)); if (!road.claim) CHK(histogram(1));
         record(ctx, EV_S_HIST, stream);
-        pa.mask = 7u;
-        CHK(hj_launch_plan(pa, stream));
-        CHK(k5b(0)); if (!claim) CHK(k5b(1));
+        CHK(plan(7u));
+        CHK(range_bases(0)); if (!road.claim) CHK(range_bases(1));
         record(ctx, EV_S_PLAN, stream);
         CHK(pass1(0)); CHK(pass1(1));
-        if (claim && outer)
+        if (road.claim && nn[1])
             CHK(hj_launch_claimed_desc(m.claim1, pl.cap1, pl.F1, pl.F2, pa.tile2, m.tdesc[1], (uint32_t)m.tdesc_cap, m.claim_total,
                                        &st->probe_overflow, stream));
         record(ctx, EV_S_SC1, stream);
         CHK(pass2(0, t1[0], -1)); CHK(pass2(1, t1[2], -1));
         record(ctx, EV_S_SC2, stream);
         record(ctx, EV_WAITED, stream);
-        for (int e : ev_r) record(ctx, e, stream);
+        for (int e : EV_OF_R) record(ctx, e, stream);
         for (int r = 0; r < 2; ++r) { CHK(audit_input(r)); CHK(audit_pass1(r)); CHK(audit_final(r)); }
+        return HJGPU_OK;
     }
-    if (!merged && mode != PHJ_BUILD_ONLY) CHK(partition_relation(1, 2u, ev_s));       // probe side first
-    else if (!merged) for (int e : ev_s) record(ctx, e, stream);
-    if (inner_ready) HIPCHK(ctx, hipStreamWaitEvent(stream, inner_ready, 0));
-    if (!merged) record(ctx, EV_WAITED, stream);
-    if (!merged && mode == PHJ_WHOLE) CHK(partition_relation(0, 1u | 4u, ev_r));       // build side + join work items
-    if (mode == PHJ_BUILD_ONLY) CHK(partition_relation(0, 1u, ev_r));       // build side; work items come with a probe
-    if (mode == PHJ_PROBE_ONLY) {
-        // the build side was partitioned by hjgpu_phj_build: only the work items are missing
-        record(ctx, ev_r[0], stream);
-        pa.mask = 4u;
-        CHK(hj_launch_plan(pa, stream));
-        for (int i = 1; i < 4; ++i) record(ctx, ev_r[i], stream);
-        CHK(audit_final(0));               // the prepared build side, as this probe finds it
-    }
-    const uint32_t *fin[4] = {t1[0], t1[1], t1[2], t1[3]};
-    if (pl.F2 > 1) for (int i = 0; i < 4; ++i) fin[i] = t2[i];
 
-    // K7+K8 (right / full outer joins: + the bitmap's clear in front and the tail kernel behind; without probe rows the tail alone)
-    // (right semi- / anti-joins: the same clear and a tail of their own, hj_launch_build_rows, behind launches that only mark; a right
-    // semi-join without probe rows has nothing to report)
-    const bool marks = hj_mode_marks_build(pl.mode), keepb = hj_mode_build_alone(pl.mode), build_rows = hj_mode_reports_build(pl.mode);
-    if (marks && (pre || mode != PHJ_WHOLE)) return fail(ctx, HJGPU_EINVAL, "internal: a join that marks its build rows is a whole join");
-    if (inner && (outer || keepb) && mode != PHJ_BUILD_ONLY) {
+    // K7+K8 over the final partitions.  Modes that mark build rows: the bitmap's clear in front and a tail kernel behind (without probe
+    // rows the tail alone; right semi- / anti-joins: launches that only mark, then hj_launch_build_rows)
+    int join(u64 bs, u64 bl, uint32_t workers)
+    {
+        const bool marks = hj_mode_marks_build(pl.mode), build_rows = hj_mode_reports_build(pl.mode);
+        uint32_t *const *fin = pl.F2 > 1 ? t2 : t1;
         JoinArgs ja{};
         ja.rk = fin[0]; ja.rv = fin[1]; ja.sk = fin[2]; ja.sv = fin[3];
         ja.roff = m.off2[0]; ja.soff = m.off2[1];
         ja.rend = m.end2[0]; ja.send = m.end2[1];
-        if (claim) {
+        if (road.claim) {
             // two pieces per partition: pass 2's front lines and back tails (hj_launch_claimed_pieces)
             CHK(hj_launch_claimed_pieces(m.off2[1], m.end2[1], m.cur2[1], pl.P, m.pieces, m.pieces + 2 * (size_t)pl.P, stream));
             ja.soff = m.pieces; ja.send = m.pieces + 2 * (size_t)pl.P; ja.s_pieces = 1;
         }
         ja.slice_prefix = m.slice_prefix; ja.slices = m.slices; ja.item_part = m.item_part;
         // line-aligned two-pass layout: the chunks' pass-2 tiles wrote every final partition as ONE region
-        ja.P = pl.P; ja.chunks = pad2 ? 1u : pl.C;
+        ja.P = pl.P; ja.chunks = road.pad2 ? 1u : pl.C;
         ja.f1 = pl.f1; ja.F1 = pl.F1; ja.f2 = pl.f2; ja.F2 = pl.F2;
-        if (pre) { ja.f1 = pl.pre_f1; ja.F1 = pl.pre_F1tot; ja.p1_base = pl.pre_base; }   // the empty sentinel of a partition
+        if (o.pre) { ja.f1 = pl.pre_f1; ja.F1 = pl.pre_F1tot; ja.p1_base = pl.pre_base; }   // the empty sentinel of a partition
         ja.tf0 = pl.tf0; ja.tf1 = pl.tf1;
         ja.s_align = 0;
         ja.packed = 1;
@@ -989,23 +1046,44 @@ int phj_enqueue(hjgpu_ctx *ctx, const PhjPlan &pl,
         ja.work_counter2 = reinterpret_cast<u64 *>(m.tickets + HJ_TICKET_JOIN2);
         ja.work_counter3 = reinterpret_cast<u64 *>(m.tickets + HJ_TICKET_JOIN3);
         ja.multi_fill = m.tickets + HJ_TICKET_MULTI_FILL;
-        ja.resume = grp ? 1u : 0u;
-        join_output(ctx, ja, out, bs, bl, st);
+        ja.resume = o.grp ? 1u : 0u;
+        join_output(ctx, ja, o.out, bs, bl, st);
         if (marks) {
             ja.build_bits = reinterpret_cast<uint32_t *>(ctx->build_bits.p);
-            HIPCHK(ctx, hj_zero_async(ja.build_bits, build_bits_bytes(pl, inner), stream));
+            HIPCHK(ctx, hj_zero_async(ja.build_bits, build_bits_bytes(pl, nn[0]), stream));
             // no join launch below, or none that emits: every wave of the tail starts without an open block (a group goes on in the grouped join's)
-            if ((!outer || build_rows) && bs && !grp) HIPCHK(ctx, hj_fill_async(ctx->final_offsets.p, 0xFFFFFFFFu, (size_t)workers * sizeof(u64), stream));
+            if ((!nn[1] || build_rows) && bs && !o.grp) HIPCHK(ctx, hj_fill_async(ctx->final_offsets.p, 0xFFFFFFFFu, (size_t)workers * sizeof(u64), stream));
         }
-        if (outer) CHK(hj_launch_join(ja, ctx->tune, ctx->cus, stream));
+        if (nn[1]) CHK(hj_launch_join(ja, ctx->tune, ctx->cus, stream));
         if (build_rows) CHK(hj_launch_build_rows(ja, ctx->tune, ctx->cus, stream));
         else if (marks) CHK(hj_launch_build_unmatched(ja, ctx->tune, ctx->cus, stream));
         if (audit) CHK(hj_audit_copy(reinterpret_cast<const u64 *>(&st->result), audit + 4 * 6, 4, stream));
+        return HJGPU_OK;
     }
+};
+
+}  // namespace
+
+int phj_enqueue(hjgpu_ctx *ctx, const PhjPlan &pl, const Rel &R, const Rel &S, hipStream_t stream, const EnqueueOpts &o)
+{
+    CHK(refuse_capture(ctx, stream));
+    if (o.grp && (o.pre || o.stages != PHJ_WHOLE || o.inner_ready)) return fail(ctx, HJGPU_EINVAL, "internal: a device-planned group is a whole join on resident columns");
+    if ((o.pre != nullptr) != (pl.pre != 0)) return fail(ctx, HJGPU_EINVAL, "internal: plan and relations disagree about pre-partitioning");
+    PhjRun run(ctx, pl, R, S, o, stream);
+    const uint32_t workers = (uint32_t)hj_join_workers(ctx->tune, ctx->cus, pl.big_tables);
+    u64 bs = 0, bl = 0;
+    CHK(setup_output(ctx, o.out, workers, &bs, &bl, pl.mode));
+
+    CHK(run.setup());
+    record(ctx, EV_BEGIN, stream);
+    CHK(run.begin());
+    CHK(run.road.merged ? run.partition_merged() : run.partition_in_turn());
+    if (hj_mode_marks_build(pl.mode) && (o.pre || o.stages != PHJ_WHOLE)) return fail(ctx, HJGPU_EINVAL, "internal: a join that marks its build rows is a whole join");
+    if (run.road.joins) CHK(run.join(bs, bl, workers));
     record(ctx, EV_JOIN, stream);
-    if (bs && inner && (outer || keepb) && mode != PHJ_BUILD_ONLY && !grp) CHK(close_gaps(ctx, out, workers, bs, st, stream, pl.mode));
+    if (bs && run.road.joins && !o.grp) CHK(close_gaps(ctx, o.out, workers, bs, run.st, stream, pl.mode));
     record(ctx, EV_GAPS, stream);
-    ctx->stats.fanout1 = pl.F1; ctx->stats.fanout2 = pl.F2; ctx->stats.buckets = 0; ctx->stats.batches = batches_used;
+    ctx->stats.fanout1 = pl.F1; ctx->stats.fanout2 = pl.F2; ctx->stats.buckets = 0; ctx->stats.batches = run.batches_used;
     ctx->last_algo = 1;
     return HJGPU_OK;
 }
@@ -1074,25 +1152,25 @@ int npj_prepare(hjgpu_ctx *ctx, size_t inner, const hjgpu_npj_params *prm, size_
     return HJGPU_OK;
 }
 
-int npj_probe_enqueue(hjgpu_ctx *ctx, const uint32_t *sk, const uint32_t *sv, size_t outer,
-                      const u64 *table, size_t buckets, uint32_t factor, const hjgpu_output *out,
-                      hipStream_t stream, bool line_hash, bool unique, uint32_t mode, uint32_t *bucket_bits)
+int npj_probe_enqueue(hjgpu_ctx *ctx, const Rel &S, const NpjTable &t, const hjgpu_output *out, hipStream_t stream, const NpjProbeOpts &o)
 {
+    const size_t outer = S.rows;
+    const uint32_t mode = o.mode;
     DevState *st = reinterpret_cast<DevState *>(ctx->state.p);
     u64 bs = 0, bl = 0;
     const int grid = hj_npj_probe_grid(ctx->cus, outer);
     // (right semi- / anti-joins: the probe only marks, a tail of their own reports - hj_launch_npj_rows; the first-match walk is never theirs,
     // whatever `unique` says; a right semi-join without probe rows has nothing to report)
     const bool build_rows = hj_mode_reports_build(mode), keepb = hj_mode_build_alone(mode);
-    if (hj_mode_keeps_build(mode) && (!bucket_bits || unique)) return fail(ctx, HJGPU_EINVAL, "internal: a right / full outer NPJ join needs its bucket bitmap and the full walk");
-    if (build_rows && !bucket_bits) return fail(ctx, HJGPU_EINVAL, "internal: a right semi- / anti-join needs its bucket bitmap");
+    if (hj_mode_keeps_build(mode) && (!o.bucket_bits || o.unique)) return fail(ctx, HJGPU_EINVAL, "internal: a right / full outer NPJ join needs its bucket bitmap and the full walk");
+    if (build_rows && !o.bucket_bits) return fail(ctx, HJGPU_EINVAL, "internal: a right semi- / anti-join needs its bucket bitmap");
     CHK(setup_output(ctx, out, (uint32_t)grid * 4, &bs, &bl, mode));
     if (outer || keepb) {
         NpjProbeArgs pa;
         memset(&pa, 0, sizeof(pa));
-        pa.keys = sk; pa.vals = sv; pa.n = outer; pa.table = table; pa.buckets = buckets;
-        pa.factor = factor; pa.line_hash = line_hash ? 1u : 0u; pa.unique = (unique || hj_mode_rows2(mode)) ? 1u : 0u; pa.mode = mode; pa.result = &st->result;
-        pa.bucket_bits = bucket_bits;
+        pa.keys = S.keys; pa.vals = S.vals; pa.n = outer; pa.table = t.slots; pa.buckets = t.buckets;
+        pa.factor = t.factor; pa.line_hash = t.line_hash ? 1u : 0u; pa.unique = (o.unique || hj_mode_rows2(mode)) ? 1u : 0u; pa.mode = mode; pa.result = &st->result;
+        pa.bucket_bits = o.bucket_bits;
         if (bs) {
             pa.ok = out->d_keys; pa.oov = out->d_outer_vals; pa.oiv = out->d_inner_vals;
             pa.block_size = bs; pa.block_limit = bl; pa.block_counter = &st->block_counter;
@@ -1128,7 +1206,6 @@ int npj_enqueue(hjgpu_ctx *ctx, const uint32_t *rk, const uint32_t *rv, size_t i
                 size_t buckets, uint32_t factor, const hjgpu_output *out, hipStream_t stream, bool unique, uint32_t mode)
 {
     CHK(refuse_capture(ctx, stream));
-    u64 *table = reinterpret_cast<u64 *>(ctx->table.p);
     // whole joins own their table: line-hashed layout (operator-level hjgpu_npj_build / _probe keep
     // the reference's hash so that their tables stay interchangeable with the reference's)
     const bool line = !ctx->tune.npj_refhash;
@@ -1140,7 +1217,8 @@ int npj_enqueue(hjgpu_ctx *ctx, const uint32_t *rk, const uint32_t *rv, size_t i
         bits = reinterpret_cast<uint32_t *>(ctx->build_bits.p);
         HIPCHK(ctx, hj_zero_async(bits, npj_bucket_bits_bytes(buckets), stream));
     }
-    CHK(npj_probe_enqueue(ctx, sk, sv, outer, table, buckets, factor, out, stream, line, unique, mode, bits));
+    const NpjTable table = {reinterpret_cast<const u64 *>(ctx->table.p), buckets, factor, line};
+    CHK(npj_probe_enqueue(ctx, {sk, sv, outer}, table, out, stream, {.unique = unique, .mode = mode, .bucket_bits = bits}));
     ctx->stats.fanout1 = ctx->stats.fanout2 = 0; ctx->stats.buckets = buckets; ctx->stats.batches = 0;
     ctx->last_algo = 0;
     return HJGPU_OK;
@@ -1148,18 +1226,18 @@ int npj_enqueue(hjgpu_ctx *ctx, const uint32_t *rk, const uint32_t *rv, size_t i
 
 // The positional look-up behind a built table (hjgpu_npj_lookup*): one kernel.  No setup_output, no final_offsets, no close_gaps - the
 // two events that bracket close_gaps elsewhere are recorded back to back (ms_close_gaps 0).  ctx->state is zeroed by the caller.
-int npj_lookup_enqueue(hjgpu_ctx *ctx, const uint32_t *sk, size_t outer, const u64 *table, size_t buckets, uint32_t factor,
-                       uint32_t *vals_out, uint32_t *match_bits, hipStream_t stream, bool line_hash)
+int npj_lookup_enqueue(hjgpu_ctx *ctx, const uint32_t *sk, size_t outer, const NpjTable &t, uint32_t *vals_out, uint32_t *match_bits,
+                       hipStream_t stream)
 {
     DevState *st = reinterpret_cast<DevState *>(ctx->state.p);
     NpjLookupArgs la;
     memset(&la, 0, sizeof(la));
-    la.keys = sk; la.n = outer; la.table = table; la.buckets = buckets; la.factor = factor; la.line_hash = line_hash ? 1u : 0u;
+    la.keys = sk; la.n = outer; la.table = t.slots; la.buckets = t.buckets; la.factor = t.factor; la.line_hash = t.line_hash ? 1u : 0u;
     la.result = &st->result; la.vals_out = vals_out; la.match_bits = match_bits;
     if (outer) CHK(hj_launch_npj_lookup(la, ctx->cus, stream));
     record(ctx, EV_JOIN, stream);
     record(ctx, EV_GAPS, stream);
-    ctx->stats.fanout1 = ctx->stats.fanout2 = 0; ctx->stats.buckets = buckets; ctx->stats.batches = 0;
+    ctx->stats.fanout1 = ctx->stats.fanout2 = 0; ctx->stats.buckets = t.buckets; ctx->stats.batches = 0;
     ctx->last_algo = 0;
     ctx->last_had_output = false;
     ctx->last_lookup = true;
@@ -1189,7 +1267,7 @@ static int npj_lookup_whole(hjgpu_ctx *ctx, const uint32_t *rk, const uint32_t *
     CHK(npj_prepare(ctx, inner, prm, &buckets, &factor));     // (no mode flag is left in prm: no bucket bitmap)
     const bool line = !ctx->tune.npj_refhash;
     CHK(npj_build_enqueue(ctx, rk, rv, inner, buckets, factor, stream, line));
-    return npj_lookup_enqueue(ctx, sk, outer, reinterpret_cast<const u64 *>(ctx->table.p), buckets, factor, vals_out, match_bits, stream, line);
+    return npj_lookup_enqueue(ctx, sk, outer, {reinterpret_cast<const u64 *>(ctx->table.p), buckets, factor, line}, vals_out, match_bits, stream);
 }
 
 // hjgpu_accumulate_async_status: the two flags of the last join -> two running uint64 counters
@@ -1212,8 +1290,8 @@ const hjgpu_output *take_async_output(hjgpu_ctx *ctx, const hjgpu_output *given)
 // ===========================================================================
 // extern "C"
 // ===========================================================================
-static int phj_grouped(hjgpu_ctx *ctx, uint32_t G, uint32_t chunks, const uint32_t *rk, const uint32_t *rv, size_t inner,
-                       const uint32_t *sk, const uint32_t *sv, size_t outer, const hjgpu_phj_params *prm, const hjgpu_output *out, hipStream_t stream);
+static int phj_grouped(hjgpu_ctx *ctx, uint32_t G, uint32_t chunks, const Rel &R, const Rel &S, const hjgpu_phj_params *prm, const hjgpu_output *out,
+                       hipStream_t stream);
 static void grouped_caps(const hjgpu_ctx *ctx, uint32_t G, size_t inner, size_t outer, size_t *cap_r, size_t *cap_s, size_t *plan_inner);
 
 extern "C" {
@@ -1340,11 +1418,11 @@ int hjgpu_reserve(hjgpu_ctx *ctx, size_t inner, size_t outer)
         size_t cap_r, cap_s, plan_inner;
         grouped_caps(ctx, groups, inner, outer, &cap_r, &cap_s, &plan_inner);
         CHK(grouped_twins(ctx, group_layout(groups), inner, outer));
-        CHK(phj_prepare(ctx, cap_r, cap_s, &prm, 8, &pl, false, -1, plan_inner));
+        CHK(phj_prepare(ctx, cap_r, cap_s, &prm, 8, &pl, {.plan_inner = plan_inner}));
     } else {
         CHK(phj_prepare(ctx, inner, outer, &prm, 8, &pl));     // 8 chunks = largest meta
         // the blocking join's claimed probe side: optimistic regions, a little larger than the relation
-        if (claimed_probe_allowed(ctx)) CHK(phj_prepare(ctx, inner, outer, &prm, 1, &pl, false, -1, 0, true));
+        if (claimed_probe_allowed(ctx)) CHK(phj_prepare(ctx, inner, outer, &prm, 1, &pl, {.claim_s = true}));
     }
     size_t buckets; uint32_t factor;
     CHK(npj_prepare(ctx, inner, nullptr, &buckets, &factor));
@@ -1451,12 +1529,12 @@ int hjgpu_get_async_status(hjgpu_ctx *ctx, void *stream_)
         ctx->grp_last.valid = false;
         const hjgpu_phj_params *prm = c.has_prm ? &c.prm : nullptr;
         const hjgpu_output *out = c.has_out ? &c.out : nullptr;
-        const uint32_t groups = grouped_groups(ctx, c.inner, c.outer, prm);
-        if (groups > 1) CHK(phj_grouped(ctx, groups, c.chunks, c.rk, c.rv, c.inner, c.sk, c.sv, c.outer, prm, out, stream));
+        const uint32_t groups = grouped_groups(ctx, c.R.rows, c.S.rows, prm);
+        if (groups > 1) CHK(phj_grouped(ctx, groups, c.chunks, c.R, c.S, prm, out, stream));
         else {
             PhjPlan pl;
-            CHK(phj_prepare(ctx, c.inner, c.outer, prm, c.chunks, &pl));
-            CHK(phj_enqueue(ctx, pl, c.rk, c.rv, c.inner, c.sk, c.sv, c.outer, out, stream));
+            CHK(phj_prepare(ctx, c.R.rows, c.S.rows, prm, c.chunks, &pl));
+            CHK(phj_enqueue(ctx, pl, c.R, c.S, stream, {.out = out}));
         }
         if (c.d_result) HIPCHK(ctx, hj_copy_async(c.d_result, ctx->state.p, sizeof(hjgpu_result), stream));
         CHK(read_state(ctx, h, stream));
@@ -1726,11 +1804,10 @@ static bool broadcast_applies(const HjTuning &tune, size_t inner, size_t outer, 
     return inner && outer && inner <= broadcast_rows(tune, true) && inner <= 16383;
 }
 
-static int broadcast_enqueue(hjgpu_ctx *ctx, const uint32_t *rk, const uint32_t *rv, size_t inner,
-                             const uint32_t *sk, const uint32_t *sv, size_t outer,
-                             const hjgpu_phj_params *prm, const hjgpu_output *out, hipStream_t stream,
+static int broadcast_enqueue(hjgpu_ctx *ctx, const Rel &R, const Rel &S, const hjgpu_phj_params *prm, const hjgpu_output *out, hipStream_t stream,
                              hipEvent_t inner_ready)
 {
+    const size_t inner = R.rows, outer = S.rows;
     CHK(refuse_capture(ctx, stream));
     ctx->prepared = false;
     const uint32_t tf0 = (prm && prm->table_factor[0]) ? prm->table_factor[0] : DEFAULT_TF0;
@@ -1769,15 +1846,15 @@ static int broadcast_enqueue(hjgpu_ctx *ctx, const uint32_t *rk, const uint32_t 
     if (inner_ready) HIPCHK(ctx, hipStreamWaitEvent(stream, inner_ready, 0));
     record(ctx, EV_WAITED, stream);
     record(ctx, EV_R_HIST, stream);
-    CHK(hj_launch_broadcast_meta(rk, inner, outer, (uint32_t)nslices, (uint32_t)groups, bm, stream));
+    CHK(hj_launch_broadcast_meta(R.keys, inner, outer, (uint32_t)nslices, (uint32_t)groups, bm, stream));
     for (int e : {EV_R_PLAN, EV_R_SC1, EV_R_SC2}) record(ctx, e, stream);
     JoinArgs ja{};
-    ja.rk = rk; ja.rv = rv; ja.sk = sk; ja.sv = sv;
+    ja.rk = R.keys; ja.rv = R.vals; ja.sk = S.keys; ja.sv = S.vals;
     ja.roff = bm.roff; ja.rend = bm.rend; ja.soff = bm.soff; ja.send = bm.send;
     ja.slice_prefix = bm.slice_prefix; ja.slices = bm.slices; ja.item_part = item_part;
     ja.P = 1; ja.chunks = 1; ja.f1 = ja.f2 = 1; ja.F1 = ja.F2 = 1;
     ja.tf0 = tf0; ja.tf1 = tf1;
-    ja.s_align = align_of(sk); ja.packed = 0;
+    ja.s_align = align_of(S.keys); ja.packed = 0;
     ja.broadcast = 1; ja.sentinel = bm.sentinel; ja.big_tables = big ? 1u : 0u; ja.unique = first_match ? 1u : 0u; ja.mode = jmode;
     ja.result = &st->result; ja.work_counter = &st->work_counter; ja.work_counter2 = &st->work_counter2;
     ja.multi_fill = &st->pad;                           // always 0: a broadcast join's build side is one table fill by construction
@@ -1809,15 +1886,13 @@ static uint32_t pass0_factor(const hjgpu_phj_params *prm)
     return DEFAULT_F0;
 }
 
-static int phj_grouped(hjgpu_ctx *ctx, uint32_t G, uint32_t chunks,
-                       const uint32_t *rk, const uint32_t *rv, size_t inner,
-                       const uint32_t *sk, const uint32_t *sv, size_t outer,
-                       const hjgpu_phj_params *prm, const hjgpu_output *out, hipStream_t stream)
+static int phj_grouped(hjgpu_ctx *ctx, uint32_t G, uint32_t chunks, const Rel &R, const Rel &S, const hjgpu_phj_params *prm, const hjgpu_output *out,
+                       hipStream_t stream)
 {
     const GroupLayout l = group_layout(G);
     {
         ReserveClock clock(ctx);
-        CHK(grouped_twins(ctx, l, inner, outer));
+        CHK(grouped_twins(ctx, l, R.rows, S.rows));
     }
     uint32_t *g_rk = (uint32_t *)ctx->grp[0].p, *g_rv = (uint32_t *)ctx->grp[1].p;
     uint32_t *g_sk = (uint32_t *)ctx->grp[2].p, *g_sv = (uint32_t *)ctx->grp[3].p;
@@ -1827,10 +1902,10 @@ static int phj_grouped(hjgpu_ctx *ctx, uint32_t G, uint32_t chunks,
     // pass 0: the probe side first, like the join itself (a build side that is still arriving is not supported here)
     const uint32_t f0 = pass0_factor(prm);
     const PartitionForm pass0 = {.group_bins = l.bins};
-    CHK(partition_op(ctx, sk, sv, outer, f0, l.F0, g_sk, g_sv, reinterpret_cast<uint64_t *>(d_off + (l.F0 + 1)), pass0, stream));
+    CHK(partition_op(ctx, S.keys, S.vals, S.rows, f0, l.F0, g_sk, g_sv, reinterpret_cast<uint64_t *>(d_off + (l.F0 + 1)), pass0, stream));
     CHK(hjgpu_get_stats(ctx, &one));
     sum.ms_scatter0 += one.ms_total;
-    CHK(partition_op(ctx, rk, rv, inner, f0, l.F0, g_rk, g_rv, reinterpret_cast<uint64_t *>(d_off), pass0, stream));
+    CHK(partition_op(ctx, R.keys, R.vals, R.rows, f0, l.F0, g_rk, g_rv, reinterpret_cast<uint64_t *>(d_off), pass0, stream));
     std::vector<u64> off((size_t)2 * (l.F0 + 1));
     HIPCHK(ctx, hipMemcpyAsync(off.data(), d_off, off.size() * sizeof(u64), hipMemcpyDeviceToHost, stream));
     CHK(hjgpu_get_stats(ctx, &one));                        // waits for the operator's last event
@@ -1874,13 +1949,13 @@ static int phj_grouped(hjgpu_ctx *ctx, uint32_t G, uint32_t chunks,
                 vout = &view;
             }
         }
+        const Rel g_s = {g_sk + pc[g].s0, g_sv + pc[g].s0, pc[g].sn};
         if (pc[g].rn == 0) {
             // an anti- or left outer join's group without build rows: all of its probe rows (a broadcast join with no fill)
-            CHK(broadcast_enqueue(ctx, g_rk, g_rv, 0, g_sk + pc[g].s0, g_sv + pc[g].s0, pc[g].sn, prm, vout, stream, nullptr));
+            CHK(broadcast_enqueue(ctx, {g_rk, g_rv, 0}, g_s, prm, vout, stream, nullptr));
         } else {
             CHK(phj_prepare(ctx, pc[g].rn, pc[g].sn, prm, chunks, &pl));
-            CHK(phj_enqueue(ctx, pl, g_rk + pc[g].r0, g_rv + pc[g].r0, pc[g].rn, g_sk + pc[g].s0, g_sv + pc[g].s0, pc[g].sn,
-                            vout, stream));
+            CHK(phj_enqueue(ctx, pl, {g_rk + pc[g].r0, g_rv + pc[g].r0, pc[g].rn}, g_s, stream, {.out = vout}));
         }
         DevState h;
         CHK(read_state(ctx, h, stream));
@@ -1923,11 +1998,10 @@ static void grouped_caps(const hjgpu_ctx *ctx, uint32_t G, size_t inner, size_t 
     *plan_inner = inner / G + inner / G / 10 + 1;
 }
 
-static int phj_grouped_device(hjgpu_ctx *ctx, uint32_t G, uint32_t chunks,
-                              const uint32_t *rk, const uint32_t *rv, size_t inner,
-                              const uint32_t *sk, const uint32_t *sv, size_t outer,
-                              const hjgpu_phj_params *prm, const hjgpu_output *out, hjgpu_result *d_result, hipStream_t stream, hipEvent_t inner_ready)
+static int phj_grouped_device(hjgpu_ctx *ctx, uint32_t G, uint32_t chunks, const Rel &R, const Rel &S, const hjgpu_phj_params *prm,
+                              const hjgpu_output *out, hjgpu_result *d_result, hipStream_t stream, hipEvent_t inner_ready)
 {
+    const size_t inner = R.rows, outer = S.rows;
     const GroupLayout l = group_layout(G);
     size_t cap_r, cap_s, plan_inner;
     grouped_caps(ctx, G, inner, outer, &cap_r, &cap_s, &plan_inner);
@@ -1935,9 +2009,8 @@ static int phj_grouped_device(hjgpu_ctx *ctx, uint32_t G, uint32_t chunks,
     {
         ReserveClock clock(ctx);
         CHK(grouped_twins(ctx, l, inner, outer));
-        CHK(phj_prepare(ctx, cap_r, cap_s, prm, chunks, &pl, false, -1, plan_inner));
-        // (a group's plan is the merged one: no batched probe-side partitioning, option "batch_tuples")
-        pl.batch_ranges = pl.batch_cap = pl.batch_tile_cap = 0; pl.tdesc_b_cap = 0; pl.batch_bytes = 0;
+        CHK(phj_prepare(ctx, cap_r, cap_s, prm, chunks, &pl, {.plan_inner = plan_inner}));
+        pl.no_batches();        // (a group's plan is the merged one: no batched probe-side partitioning, option "batch_tuples")
     }
     // one set of phase events per group (made once, kept): nobody waits between the groups, hjgpu_get_stats adds their spans up afterwards
     while (ctx->grp_ev.size() < (size_t)G * EV_COUNT) {
@@ -1957,9 +2030,9 @@ static int phj_grouped_device(hjgpu_ctx *ctx, uint32_t G, uint32_t chunks,
     CHK(setup_output(ctx, out, workers, &bs, &bl, pl.mode));
     HIPCHK(ctx, hipEventRecord(ctx->grp_ev_pass0[0], stream));
     // pass 0: the probe side first; the build side may still be arriving (hjgpu_phj_overlapped_async)
-    CHK(partition_op(ctx, sk, sv, outer, f0, l.F0, g_sk, g_sv, reinterpret_cast<uint64_t *>(d_off + (l.F0 + 1)), pass0, stream));
+    CHK(partition_op(ctx, S.keys, S.vals, outer, f0, l.F0, g_sk, g_sv, reinterpret_cast<uint64_t *>(d_off + (l.F0 + 1)), pass0, stream));
     if (inner_ready) HIPCHK(ctx, hipStreamWaitEvent(stream, inner_ready, 0));
-    CHK(partition_op(ctx, rk, rv, inner, f0, l.F0, g_rk, g_rv, reinterpret_cast<uint64_t *>(d_off), pass0, stream));
+    CHK(partition_op(ctx, R.keys, R.vals, inner, f0, l.F0, g_rk, g_rv, reinterpret_cast<uint64_t *>(d_off), pass0, stream));
     // the grouped join's state: cleared ONCE; every wave's output cursor "no block yet"
     HIPCHK(ctx, hj_zero_async(st, sizeof(DevState), stream));
     if (bs) HIPCHK(ctx, hj_fill_async(ctx->final_offsets.p, 0xFFFFFFFFu, (size_t)workers * sizeof(u64), stream));
@@ -1969,7 +2042,7 @@ static int phj_grouped_device(hjgpu_ctx *ctx, uint32_t G, uint32_t chunks,
     for (uint32_t g = 0; g < G; ++g) {
         const GroupRun run = {d_desc + 4 * (size_t)g};
         ctx->ev_cur = ctx->grp_ev.data() + (size_t)g * EV_COUNT;
-        const int rc = phj_enqueue(ctx, pl, g_rk, g_rv, cap_r, g_sk, g_sv, cap_s, bs ? out : nullptr, stream, nullptr, PHJ_WHOLE, nullptr, &run);
+        const int rc = phj_enqueue(ctx, pl, {g_rk, g_rv, cap_r}, {g_sk, g_sv, cap_s}, stream, {.out = bs ? out : nullptr, .grp = &run});
         ctx->ev_cur = nullptr;
         CHK(rc);
     }
@@ -1989,18 +2062,16 @@ static int phj_grouped_device(hjgpu_ctx *ctx, uint32_t G, uint32_t chunks,
 // does a grouped plan of this context run device-planned?  (option "audit" reads every stage's output with host-known sizes: host-planned)
 static bool grouped_on_device(const hjgpu_ctx *ctx) { return ctx->tune.group_device && !ctx->tune.audit && !ctx->tune.scatter_prof; }
 
-static int phj_like(hjgpu_ctx *ctx, uint32_t chunks,
-                    const uint32_t *rk, const uint32_t *rv, size_t inner,
-                    const uint32_t *sk, const uint32_t *sv, size_t outer,
-                    const hjgpu_phj_params *prm, hjgpu_result *result, hjgpu_result *d_result,
+static int phj_like(hjgpu_ctx *ctx, uint32_t chunks, const Rel &R, const Rel &S, const hjgpu_phj_params *prm, hjgpu_result *result, hjgpu_result *d_result,
                     const hjgpu_output *out, void *stream_, bool blocking, void *inner_ready = nullptr, bool local_join = false)
 {
     if (!ctx) return HJGPU_EINVAL;
     if (!blocking) out = take_async_output(ctx, out);    // consumed by this call even if it fails below (see hjgpu_npj_async)
     PlainRows plain(ctx, blocking);
     if (prm) CHK(check_join_mode(ctx, prm->flags));
-    CHK(check_columns(ctx, rk, rv, inner));
-    CHK(check_columns(ctx, sk, sv, outer));
+    const size_t inner = R.rows, outer = S.rows;
+    CHK(check_columns(ctx, R.keys, R.vals, inner));
+    CHK(check_columns(ctx, S.keys, S.vals, outer));
     if (chunks < 1 || chunks > HJ_MAX_CHUNKS) return fail(ctx, HJGPU_EINVAL, "chunks must be in [1, 256]");
     hipStream_t stream = (hipStream_t)stream_;
     HIPCHK(ctx, hipSetDevice(ctx->device));
@@ -2012,11 +2083,11 @@ static int phj_like(hjgpu_ctx *ctx, uint32_t chunks,
     // deadline or not at all)
     const bool anti_all = prm && hj_mode_keeps_unmatched(hj_join_mode(prm->flags)) && inner == 0 && outer;     // broadcast_applies
     if (groups > 1 && outer && !anti_all && (grouped_on_device(ctx) || local_join)) {
-        CHK(phj_grouped_device(ctx, groups, chunks, rk, rv, inner, sk, sv, outer, prm, out, d_result, stream, (hipEvent_t)inner_ready));
+        CHK(phj_grouped_device(ctx, groups, chunks, R, S, prm, out, d_result, stream, (hipEvent_t)inner_ready));
         if (!blocking) {
             // what hjgpu_get_async_status needs to do the join again, host-planned, should a group have been larger than its workspace
             hjgpu_ctx::GroupedCall &c = ctx->grp_last;
-            c.valid = true; c.chunks = chunks; c.rk = rk; c.rv = rv; c.sk = sk; c.sv = sv; c.inner = inner; c.outer = outer;
+            c.valid = true; c.chunks = chunks; c.R = R; c.S = S;
             c.has_prm = prm != nullptr; c.has_out = out != nullptr; c.d_result = d_result;
             if (prm) c.prm = *prm;
             if (out) c.out = *out;
@@ -2026,20 +2097,21 @@ static int phj_like(hjgpu_ctx *ctx, uint32_t chunks,
         CHK(read_state(ctx, h, stream));
         if (!h.group_skew) return finish_blocking(ctx, result, out, stream);
         // a group was larger than the plan's workspace (heavy duplicates): the host-planned form sizes every group's join from its rows
-        CHK(phj_grouped(ctx, groups, chunks, rk, rv, inner, sk, sv, outer, prm, out, stream));
+        CHK(phj_grouped(ctx, groups, chunks, R, S, prm, out, stream));
         return finish_blocking(ctx, result, out, stream);
     }
     if (groups > 1 && outer && !anti_all) {
         // option "group_device" = 0 (or "audit"): this thread waits for pass 0 and for every group - never inside a multi-GPU call, whose
         // rank threads wait with a deadline (hjgpu_phj_overlapped_async is hjgpu_phj_multi's / hjgpu_cpra_multi's local join)
-        CHK(phj_grouped(ctx, groups, chunks, rk, rv, inner, sk, sv, outer, prm, out, stream));
+        CHK(phj_grouped(ctx, groups, chunks, R, S, prm, out, stream));
     } else if (broadcast_applies(ctx->tune, inner, outer, chunks, prm)) {
-        CHK(broadcast_enqueue(ctx, rk, rv, inner, sk, sv, outer, prm, out, stream, (hipEvent_t)inner_ready));
+        CHK(broadcast_enqueue(ctx, R, S, prm, out, stream, (hipEvent_t)inner_ready));
     } else {
         PhjPlan pl;
         const bool claim = blocking && chunks == 1 && !inner_ready && !local_join && !d_result && claimed_probe_allowed(ctx);
-        CHK(phj_prepare(ctx, inner, outer, prm, chunks, &pl, false, -1, 0, claim));
-        CHK(phj_enqueue(ctx, pl, rk, rv, inner, sk, sv, outer, out, stream, (hipEvent_t)inner_ready));
+        const EnqueueOpts whole = {.out = out, .inner_ready = (hipEvent_t)inner_ready};
+        CHK(phj_prepare(ctx, inner, outer, prm, chunks, &pl, {.claim_s = claim}));
+        CHK(phj_enqueue(ctx, pl, R, S, stream, whole));
         if (pl.claim_s) {
             DevState h;
             CHK(read_state(ctx, h, stream));
@@ -2049,7 +2121,7 @@ static int phj_like(hjgpu_ctx *ctx, uint32_t chunks,
             ctx->probe_exact = true;
             ++ctx->probe_fallbacks;
             CHK(phj_prepare(ctx, inner, outer, prm, chunks, &pl));
-            CHK(phj_enqueue(ctx, pl, rk, rv, inner, sk, sv, outer, out, stream, (hipEvent_t)inner_ready));
+            CHK(phj_enqueue(ctx, pl, R, S, stream, whole));
         }
     }
     if (d_result)
@@ -2062,14 +2134,14 @@ int hjgpu_phj(hjgpu_ctx *ctx, const uint32_t *rk, const uint32_t *rv, size_t inn
               const uint32_t *sk, const uint32_t *sv, size_t outer,
               const hjgpu_phj_params *prm, hjgpu_result *result, const hjgpu_output *out, void *stream)
 {
-    return phj_like(ctx, 1, rk, rv, inner, sk, sv, outer, prm, result, nullptr, out, stream, true);
+    return phj_like(ctx, 1, {rk, rv, inner}, {sk, sv, outer}, prm, result, nullptr, out, stream, true);
 }
 
 int hjgpu_phj_async(hjgpu_ctx *ctx, const uint32_t *rk, const uint32_t *rv, size_t inner,
                     const uint32_t *sk, const uint32_t *sv, size_t outer,
                     const hjgpu_phj_params *prm, hjgpu_result *d_result, void *stream)
 {
-    return phj_like(ctx, 1, rk, rv, inner, sk, sv, outer, prm, nullptr, d_result, nullptr, stream, false);
+    return phj_like(ctx, 1, {rk, rv, inner}, {sk, sv, outer}, prm, nullptr, d_result, nullptr, stream, false);
 }
 
 int hjgpu_phj_overlapped_async(hjgpu_ctx *ctx, const uint32_t *rk, const uint32_t *rv, size_t inner,
@@ -2077,8 +2149,7 @@ int hjgpu_phj_overlapped_async(hjgpu_ctx *ctx, const uint32_t *rk, const uint32_
                                const hjgpu_phj_params *prm, hjgpu_result *d_result, void *stream,
                                void *inner_ready_event)
 {
-    return phj_like(ctx, 1, rk, rv, inner, sk, sv, outer, prm, nullptr, d_result, nullptr, stream, false,
-                    inner_ready_event, true);
+    return phj_like(ctx, 1, {rk, rv, inner}, {sk, sv, outer}, prm, nullptr, d_result, nullptr, stream, false, inner_ready_event, true);
 }
 
 // ---- build side prepared once, probed by any number of batches ---------------------------------
@@ -2093,7 +2164,7 @@ int hjgpu_phj_build(hjgpu_ctx *ctx, const uint32_t *rk, const uint32_t *rv, size
     PhjPlan pl;
     CHK(refuse_capture(ctx, stream));
     CHK(phj_prepare(ctx, inner, max_outer, prm, 1, &pl));        // workspace and plan for the largest batch
-    CHK(phj_enqueue(ctx, pl, rk, rv, inner, nullptr, nullptr, 0, nullptr, stream, nullptr, PHJ_BUILD_ONLY));
+    CHK(phj_enqueue(ctx, pl, {rk, rv, inner}, {}, stream, {.stages = PHJ_BUILD_ONLY}));
     memcpy(ctx->prepared_plan, &pl, sizeof(pl));
     ctx->prepared_inner = inner; ctx->prepared_max_outer = max_outer;
     ctx->prepared = true;
@@ -2119,7 +2190,7 @@ static int phj_probe_prepared(hjgpu_ctx *ctx, const uint32_t *sk, const uint32_t
     memcpy(&pl, ctx->prepared_plan, sizeof(pl));
     ctx->last_had_output = out && out->d_keys;
     // the build columns themselves are not read again: their partitions live in the workspace
-    CHK(phj_enqueue(ctx, pl, nullptr, nullptr, ctx->prepared_inner, sk, sv, outer, out, stream, nullptr, PHJ_PROBE_ONLY));
+    CHK(phj_enqueue(ctx, pl, {.rows = ctx->prepared_inner}, {sk, sv, outer}, stream, {.stages = PHJ_PROBE_ONLY, .out = out}));
     if (d_result)
         HIPCHK(ctx, hj_copy_async(d_result, ctx->state.p, sizeof(hjgpu_result), stream));
     if (blocking) return finish_blocking(ctx, result, out, stream);
@@ -2143,7 +2214,7 @@ int hjgpu_cpra(hjgpu_ctx *ctx, const uint32_t *rk, const uint32_t *rv, size_t in
                const hjgpu_phj_params *prm, hjgpu_result *result, const hjgpu_output *out, void *stream)
 {
     const uint32_t chunks = (prm && prm->chunks) ? prm->chunks : 8;
-    return phj_like(ctx, chunks, rk, rv, inner, sk, sv, outer, prm, result, nullptr, out, stream, true);
+    return phj_like(ctx, chunks, {rk, rv, inner}, {sk, sv, outer}, prm, result, nullptr, out, stream, true);
 }
 
 int hjgpu_cpra_async(hjgpu_ctx *ctx, const uint32_t *rk, const uint32_t *rv, size_t inner,
@@ -2151,7 +2222,7 @@ int hjgpu_cpra_async(hjgpu_ctx *ctx, const uint32_t *rk, const uint32_t *rv, siz
                      const hjgpu_phj_params *prm, hjgpu_result *d_result, void *stream)
 {
     const uint32_t chunks = (prm && prm->chunks) ? prm->chunks : 8;
-    return phj_like(ctx, chunks, rk, rv, inner, sk, sv, outer, prm, nullptr, d_result, nullptr, stream, false);
+    return phj_like(ctx, chunks, {rk, rv, inner}, {sk, sv, outer}, prm, nullptr, d_result, nullptr, stream, false);
 }
 
 }  // extern "C"

@@ -21,6 +21,11 @@ struct DevBuf {
     size_t cap = 0;
 };
 
+namespace hjapi {
+// a relation on the device: its key and payload columns (a prepared or pre-partitioned relation has none) and its rows
+struct Rel { const uint32_t *keys = nullptr, *vals = nullptr; size_t rows = 0; };
+}
+
 // Small device-resident state of one join.
 struct DevState {
     hjgpu_result result;
@@ -98,8 +103,7 @@ struct hjgpu_ctx {
     struct GroupedCall {
         bool valid = false;
         uint32_t chunks = 1;
-        const uint32_t *rk = nullptr, *rv = nullptr, *sk = nullptr, *sv = nullptr;
-        size_t inner = 0, outer = 0;
+        hjapi::Rel R, S;
         bool has_prm = false, has_out = false;
         hjgpu_phj_params prm;
         hjgpu_output out;
@@ -268,11 +272,12 @@ struct PhjPlan {
     uint32_t batch_tile_cap; // tiles per range the batch buffers are sized for
     size_t tdesc_b_cap;      // pass-2 tile descriptors per batch
     size_t batch_bytes;      // one batch buffer (packed tuples)
+    void no_batches() { batch_ranges = batch_cap = batch_tile_cap = 0; tdesc_b_cap = 0; batch_bytes = 0; }
     // pre-partitioned relations (hjgpu_phj_build_prepartitioned): pass 1 was the exchange-level partitioning of the
     // multi-GPU CPRA; F1 = this rank's share k of its fan-out pre_F1tot, partitions [pre_base, pre_base + k)
     uint32_t pre;            // 1: the relations arrive pass-1-partitioned
     uint32_t pre_f1, pre_F1tot, pre_base;
-    // claimed probe side (blocking whole joins, phj_prepare's claim_s): no K4 of S; pass 1 of S writes regions of cap1 tuples per pass-1
+    // claimed probe side (blocking whole joins, PrepareOpts::claim_s): no K4 of S; pass 1 of S writes regions of cap1 tuples per pass-1
     // partition, pass 2 final regions of cap2 tuples (both optimistic, line multiples)
     uint32_t claim_s;
     u64 cap1, cap2;
@@ -286,34 +291,49 @@ struct PrePieces {
     // delivered with the exchange (hjgpu_phj_probe_prepartitioned_counted_async): K4p is skipped
     const u64 *counts[2] = {nullptr, nullptr};
 };
-enum PhjMode { PHJ_WHOLE = 0, PHJ_BUILD_ONLY = 1, PHJ_PROBE_ONLY = 2 };
+// which stages a phj_enqueue call runs: the whole join, the build side's partitioning (hjgpu_phj_build*), or the probe side's and the join
+enum PhjStages { PHJ_WHOLE = 0, PHJ_BUILD_ONLY = 1, PHJ_PROBE_ONLY = 2 };
 
-// plan_inner > 0: the fan-out is planned for a build side of that many rows while the workspace holds `inner` (device-planned groups: the
-// mean group decides the partitions, the largest group the plan allows decides the buffers)
-// claim_s: the probe side may be partitioned without its histogram pass (a blocking whole join, see claimed_probe_allowed); the plan
-// says in PhjPlan::claim_s whether it is
-int phj_prepare(hjgpu_ctx *ctx, size_t inner, size_t outer, const hjgpu_phj_params *prm, uint32_t chunks, PhjPlan *pl, bool pre = false,
-                int big_override = -1, size_t plan_inner = 0, bool claim_s = false);
+struct PrepareOpts {
+    bool pre = false;           // the relations arrive pass-1-partitioned: no pass-1 twins
+    int big_tables = -1;        // 0 / 1: 16 K-slot tables off / on, whatever the fan-out's choice (-1) would be
+    size_t plan_inner = 0;      // > 0: the fan-out is planned for a build side of that many rows while the workspace holds `inner` (device-planned
+                                // groups: the mean group decides the partitions, the largest group the plan allows decides the buffers)
+    bool claim_s = false;       // the probe side may be partitioned without its histogram pass (a blocking whole join, see
+                                // claimed_probe_allowed); the plan says in PhjPlan::claim_s whether it is
+};
+int phj_prepare(hjgpu_ctx *ctx, size_t inner, size_t outer, const hjgpu_phj_params *prm, uint32_t chunks, PhjPlan *pl, const PrepareOpts &o = {});
 // One group of a device-planned grouped join: desc = {build first row, build rows, probe first row, probe rows} in device memory; the
-// columns handed to phj_enqueue are the pass-0 twins, `inner` / `outer` the CAPACITY the plan was prepared for.  The join's state
+// columns handed to phj_enqueue are the pass-0 twins, their rows the CAPACITY the plan was prepared for.  The join's state
 // (aggregates, block counter, open output blocks) is the whole grouped join's: phj_enqueue neither clears it nor closes the gaps.
 struct GroupRun { const u64 *desc; };
-int phj_enqueue(hjgpu_ctx *ctx, const PhjPlan &pl, const uint32_t *rk, const uint32_t *rv, size_t inner,
-                const uint32_t *sk, const uint32_t *sv, size_t outer, const hjgpu_output *out, hipStream_t stream,
-                hipEvent_t inner_ready = nullptr, PhjMode mode = PHJ_WHOLE, const PrePieces *pre = nullptr, const GroupRun *grp = nullptr);
+struct EnqueueOpts {
+    PhjStages stages = PHJ_WHOLE;
+    const hjgpu_output *out = nullptr;      // result rows (NULL: aggregates only)
+    hipEvent_t inner_ready = nullptr;       // the build columns are complete once this event has happened
+    const PrePieces *pre = nullptr;         // the relations arrive pass-1-partitioned (a plan with PrepareOpts::pre)
+    const GroupRun *grp = nullptr;
+};
+int phj_enqueue(hjgpu_ctx *ctx, const PhjPlan &pl, const Rel &R, const Rel &S, hipStream_t stream, const EnqueueOpts &o = {});
 int finish_blocking(hjgpu_ctx *ctx, hjgpu_result *result, const hjgpu_output *out, hipStream_t stream);
 bool npj_unique(const hjgpu_ctx *ctx, const hjgpu_npj_params *prm);
 uint32_t npj_mode(const hjgpu_npj_params *prm);
 int npj_prepare(hjgpu_ctx *ctx, size_t inner, const hjgpu_npj_params *prm, size_t *buckets, uint32_t *factor);
-int npj_probe_enqueue(hjgpu_ctx *ctx, const uint32_t *sk, const uint32_t *sv, size_t outer, const u64 *table, size_t buckets, uint32_t factor,
-                      const hjgpu_output *out, hipStream_t stream, bool line_hash = false, bool unique = false, uint32_t mode = HJ_MODE_INNER,
-                      uint32_t *bucket_bits = nullptr /* right / full outer joins of hjgpu_npj*: the zeroed bucket bitmap; the tail follows the probe */);
+// a built NPJ table: its buckets, the hash factor, and which hash placed the tuples (line_hash: whole joins' 64-byte lines of 8 buckets;
+// else the reference's, hjgpu_npj_build)
+struct NpjTable { const u64 *slots; size_t buckets; uint32_t factor; bool line_hash; };
+struct NpjProbeOpts {
+    bool unique = false;
+    uint32_t mode = HJ_MODE_INNER;
+    uint32_t *bucket_bits = nullptr;        // right / full outer joins of hjgpu_npj*: the zeroed bucket bitmap; the tail follows the probe
+};
+int npj_probe_enqueue(hjgpu_ctx *ctx, const Rel &S, const NpjTable &t, const hjgpu_output *out, hipStream_t stream, const NpjProbeOpts &o);
 int npj_enqueue(hjgpu_ctx *ctx, const uint32_t *rk, const uint32_t *rv, size_t inner, const uint32_t *sk, const uint32_t *sv, size_t outer,
                 size_t buckets, uint32_t factor, const hjgpu_output *out, hipStream_t stream, bool unique, uint32_t mode = HJ_MODE_INNER);
 const hjgpu_output *take_async_output(hjgpu_ctx *ctx, const hjgpu_output *given);
 // the positional look-up in a built table (hjgpu_npj_lookup*: npj_kernels.hip); ctx->state zeroed by the caller, EV_BEGIN / EV_R_HIST recorded
-int npj_lookup_enqueue(hjgpu_ctx *ctx, const uint32_t *sk, size_t outer, const u64 *table, size_t buckets, uint32_t factor,
-                       uint32_t *vals_out, uint32_t *match_bits, hipStream_t stream, bool line_hash);
+int npj_lookup_enqueue(hjgpu_ctx *ctx, const uint32_t *sk, size_t outer, const NpjTable &t, uint32_t *vals_out, uint32_t *match_bits,
+                       hipStream_t stream);
 int check_lookup_columns(hjgpu_ctx *ctx, const uint32_t *sk, size_t outer, const uint32_t *vals_out, const uint32_t *match_bits);
 // hjgpu_ops.hip: the partition operator on one relation (hjgpu_partition*, hjgpu_partition_packed_*; pass 0 of a grouped plan) - what
 // differs between its forms

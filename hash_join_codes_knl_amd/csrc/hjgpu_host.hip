@@ -259,6 +259,9 @@ static int join_host_batched(hjgpu_ctx *ctx, int algorithm, const uint32_t *ik, 
     const bool line = !ctx->tune.npj_refhash, unique = npj && npj_unique(ctx, np);
     DevState *st = reinterpret_cast<DevState *>(ctx->state.p);
     u64 *table = reinterpret_cast<u64 *>(ctx->table.p);
+    const NpjTable built = {table, buckets, factor, line};
+    const Rel prepared = {.rows = inner};        // the build side lives in the workspace (PHJ_BUILD_ONLY below)
+    auto batch_in = [&](int slot, size_t m) { return Rel{(const uint32_t *)d_s[slot][0], (const uint32_t *)d_s[slot][1], m}; };
     if (rows && !cursor) retry_alone = [&](size_t j, const DevState &hs, u64 need) -> bool {
         (void)hs;
         const int slot = (int)(j & 1);
@@ -281,11 +284,11 @@ static int join_host_batched(hjgpu_ctx *ctx, int algorithm, const uint32_t *ik, 
                  hj_zero_async(&st->block_counter, 3 * sizeof(u64), run) == hipSuccess &&
                  hj_zero_async(&st->overflow, sizeof(uint32_t), run) == hipSuccess &&
                  hj_zero_async(&st->nmoves, sizeof(uint32_t), run) == hipSuccess &&
-                 npj_probe_enqueue(ctx, (const uint32_t *)d_s[slot][0], (const uint32_t *)d_s[slot][1], m, table, buckets, factor, &o, run, line, unique) == HJGPU_OK &&
+                 npj_probe_enqueue(ctx, batch_in(slot, m), built, &o, run, {.unique = unique}) == HJGPU_OK &&
                  hipMemcpyAsync(&again, ctx->state.p, sizeof(DevState), hipMemcpyDeviceToHost, run) == hipSuccess &&
                  hj_copy_async(&st->result, saved, sizeof(hjgpu_result), run) == hipSuccess;
         } else if (ok) {
-            ok = phj_enqueue(ctx, pl, nullptr, nullptr, inner, (const uint32_t *)d_s[slot][0], (const uint32_t *)d_s[slot][1], m, &o, run, nullptr, PHJ_PROBE_ONLY) == HJGPU_OK &&
+            ok = phj_enqueue(ctx, pl, prepared, batch_in(slot, m), run, {.stages = PHJ_PROBE_ONLY, .out = &o}) == HJGPU_OK &&
                  hj_copy_async(static_cast<hjgpu_result *>(d_res) + j, ctx->state.p, sizeof(hjgpu_result), run) == hipSuccess &&
                  hipMemcpyAsync(&again, ctx->state.p, sizeof(DevState), hipMemcpyDeviceToHost, run) == hipSuccess;
         }
@@ -330,7 +333,7 @@ static int join_host_batched(hjgpu_ctx *ctx, int algorithm, const uint32_t *ik, 
             hip_ok(hipEventRecord(b1, run), "hipEventRecord");
         } else if (rc == HJGPU_OK) {
             hip_ok(hipEventRecord(b0, run), "hipEventRecord");
-            rc = phj_enqueue(ctx, pl, (const uint32_t *)d_r[0], (const uint32_t *)d_r[1], inner, nullptr, nullptr, 0, nullptr, run, nullptr, PHJ_BUILD_ONLY);
+            rc = phj_enqueue(ctx, pl, {(const uint32_t *)d_r[0], (const uint32_t *)d_r[1], inner}, {}, run, {.stages = PHJ_BUILD_ONLY});
             hip_ok(hipEventRecord(b1, run), "hipEventRecord");
         }
         for (size_t i = 0; i < nb && rc == HJGPU_OK; ++i) {
@@ -354,16 +357,14 @@ static int join_host_batched(hjgpu_ctx *ctx, int algorithm, const uint32_t *ik, 
                     hip_ok(hj_zero_async(&st->overflow, sizeof(uint32_t), run), "clearing the overflow flag");
                     hip_ok(hj_zero_async(&st->nmoves, sizeof(uint32_t), run), "clearing the move count");
                 }
-                rc = npj_probe_enqueue(ctx, (const uint32_t *)d_s[slot][0], (const uint32_t *)d_s[slot][1], m, table, buckets, factor,
-                                       rows ? &dev_out[slot] : nullptr, run, line, unique);
+                rc = npj_probe_enqueue(ctx, batch_in(slot, m), built, rows ? &dev_out[slot] : nullptr, run, {.unique = unique});
                 ctx->stats.fanout1 = ctx->stats.fanout2 = 0; ctx->stats.buckets = buckets; ctx->last_algo = 0;
                 if (rows) {
                     hip_ok(hipMemcpyAsync(&h_state[i], ctx->state.p, sizeof(DevState), hipMemcpyDeviceToHost, run), "hipMemcpyAsync(state)");
                     hip_ok(hipEventRecord(joined[slot], run), "hipEventRecord");
                 }
             } else if (rc == HJGPU_OK) {
-                rc = phj_enqueue(ctx, pl, nullptr, nullptr, inner, (const uint32_t *)d_s[slot][0], (const uint32_t *)d_s[slot][1], m,
-                                 rows ? &dev_out[slot] : nullptr, run, nullptr, PHJ_PROBE_ONLY);
+                rc = phj_enqueue(ctx, pl, prepared, batch_in(slot, m), run, {.stages = PHJ_PROBE_ONLY, .out = rows ? &dev_out[slot] : nullptr});
                 hip_ok(hj_copy_async(static_cast<hjgpu_result *>(d_res) + i, ctx->state.p, sizeof(hjgpu_result), run),
                        "hipMemcpyAsync(result)");
                 if (rows) {
@@ -539,7 +540,7 @@ static int join_host_impl(hjgpu_ctx *ctx, int algorithm,
                 if (rc == HJGPU_OK) rc = npj_enqueue(ctx, rk, rv, inner, sk, sv, outer, buckets, factor, out, run, npj_unique(ctx, np));
             } else {
                 hip_ok(hipStreamWaitEvent(run, s_ready, 0), "hipStreamWaitEvent");
-                if (rc == HJGPU_OK) rc = phj_enqueue(ctx, pl, rk, rv, inner, sk, sv, outer, out, run, r_ready);
+                if (rc == HJGPU_OK) rc = phj_enqueue(ctx, pl, {rk, rv, inner}, {sk, sv, outer}, run, {.out = out, .inner_ready = r_ready});
             }
         }
         if (rc == HJGPU_OK) {

@@ -213,7 +213,8 @@ int hjgpu_npj_probe(hjgpu_ctx *ctx, const uint32_t *d_keys, const uint32_t *d_va
     CHK(ensure(ctx, ctx->state, sizeof(DevState)));
     HIPCHK(ctx, hj_zero_async(ctx->state.p, sizeof(DevState), stream));
     record(ctx, EV_BEGIN, stream); record(ctx, EV_R_HIST, stream);
-    CHK(npj_probe_enqueue(ctx, d_keys, d_vals, n, (const u64 *)d_table, buckets, factor, out, stream, false, ctx->tune.unique));
+    const NpjTable table = {.slots = (const u64 *)d_table, .buckets = buckets, .factor = factor, .line_hash = false};      // hjgpu_npj_build's: the reference's hash
+    CHK(npj_probe_enqueue(ctx, {d_keys, d_vals, n}, table, out, stream, {.unique = ctx->tune.unique}));
     ctx->last_algo = 0;
     return finish_blocking(ctx, result, out, stream);
 }
@@ -230,7 +231,8 @@ int hjgpu_npj_lookup_table(hjgpu_ctx *ctx, const uint32_t *d_keys, size_t n, con
     CHK(ensure(ctx, ctx->state, sizeof(DevState)));
     HIPCHK(ctx, hj_zero_async(ctx->state.p, sizeof(DevState), stream));
     record(ctx, EV_BEGIN, stream); record(ctx, EV_R_HIST, stream);
-    CHK(npj_lookup_enqueue(ctx, d_keys, n, (const u64 *)d_table, buckets, factor, d_vals_out, d_match_bits, stream, false));
+    const NpjTable table = {.slots = (const u64 *)d_table, .buckets = buckets, .factor = factor, .line_hash = false};      // hjgpu_npj_build's: the reference's hash
+    CHK(npj_lookup_enqueue(ctx, d_keys, n, table, d_vals_out, d_match_bits, stream));
     return finish_blocking(ctx, result, nullptr, stream);
 }
 
@@ -326,10 +328,10 @@ int hjgpu_phj_build_prepartitioned(hjgpu_ctx *ctx, const uint64_t *d_tuples, con
     prepartitioned_plan(ctx, inner, k, &p2, &F2, &big);
     p2.fanout1 = k; p2.fanout2 = F2;
     PhjPlan pl;
-    CHK(phj_prepare(ctx, inner, max_outer, &p2, lay->chunks, &pl, true, big ? 1 : 0));
+    CHK(phj_prepare(ctx, inner, max_outer, &p2, lay->chunks, &pl, {.pre = true, .big_tables = big ? 1 : 0}));
     pl.pre_f1 = lay->factor1; pl.pre_F1tot = lay->fanout1_total; pl.pre_base = lay->first_partition;
     if (pl.f2 == pl.pre_f1) return fail(ctx, HJGPU_EINVAL, "factor2 must differ from the exchange-level factor1 (same factor: the second pass would not split)");
-    CHK(phj_enqueue(ctx, pl, nullptr, nullptr, inner, nullptr, nullptr, 0, nullptr, stream, nullptr, PHJ_BUILD_ONLY, &pre));
+    CHK(phj_enqueue(ctx, pl, {.rows = inner}, {}, stream, {.stages = PHJ_BUILD_ONLY, .pre = &pre}));
     memcpy(ctx->prepared_plan, &pl, sizeof(pl));
     ctx->prepared_inner = inner; ctx->prepared_max_outer = max_outer;
     ctx->prepared = true;
@@ -373,7 +375,7 @@ static int probe_prepartitioned(hjgpu_ctx *ctx, const uint64_t *d_tuples, const 
     hipStream_t stream = (hipStream_t)stream_;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     ctx->last_had_output = out && out->d_keys;
-    CHK(phj_enqueue(ctx, pl, nullptr, nullptr, ctx->prepared_inner, nullptr, nullptr, outer, out, stream, nullptr, PHJ_PROBE_ONLY, &pre));
+    CHK(phj_enqueue(ctx, pl, {.rows = ctx->prepared_inner}, {.rows = outer}, stream, {.stages = PHJ_PROBE_ONLY, .out = out, .pre = &pre}));
     if (d_result)
         HIPCHK(ctx, hj_copy_async(d_result, ctx->state.p, sizeof(hjgpu_result), stream));
     return HJGPU_OK;
