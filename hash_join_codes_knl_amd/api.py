@@ -35,7 +35,7 @@ EXPORTS = [
     "hjgpu_host_alloc", "hjgpu_host_free",
     "hjgpu_histogram", "hjgpu_partition", "hjgpu_partition_async", "hjgpu_join_partitions",
     "hjgpu_npj_build", "hjgpu_npj_probe",
-    "hjgpu_npj_lookup", "hjgpu_npj_lookup_async", "hjgpu_npj_lookup_table",
+    "hjgpu_npj_lookup", "hjgpu_npj_lookup_async", "hjgpu_npj_lookup_table", "hjgpu_lookup", "hjgpu_lookup_async",
     "hjgpu_npj", "hjgpu_phj", "hjgpu_cpra",
     "hjgpu_npj_async", "hjgpu_phj_async", "hjgpu_cpra_async", "hjgpu_phj_overlapped_async",
     "hjgpu_phj_build", "hjgpu_phj_probe", "hjgpu_phj_probe_async",
@@ -258,6 +258,8 @@ def load_library(build_if_missing=True):
                                   C.POINTER(Output), vp]
     L.hjgpu_npj_lookup.argtypes = [vp, vp, vp, sz, vp, sz, C.POINTER(NpjParams), vp, vp, C.POINTER(Result), vp]
     L.hjgpu_npj_lookup_async.argtypes = [vp, vp, vp, sz, vp, sz, C.POINTER(NpjParams), vp, vp, vp, vp]
+    L.hjgpu_lookup.argtypes = [vp, vp, vp, sz, vp, sz, C.POINTER(NpjParams), vp, vp, C.POINTER(Result), vp]
+    L.hjgpu_lookup_async.argtypes = [vp, vp, vp, sz, vp, sz, C.POINTER(NpjParams), vp, vp, vp, vp]
     L.hjgpu_npj_lookup_table.argtypes = [vp, vp, sz, vp, sz, u32, vp, vp, C.POINTER(Result), vp]
     join = [vp, vp, vp, sz, vp, vp, sz]
     L.hjgpu_npj.argtypes = join + [C.POINTER(NpjParams), C.POINTER(Result), C.POINTER(Output), vp]
@@ -402,7 +404,8 @@ class HjGpu:
         return s.as_dict()
 
     def counter(self, name):
-        """hjgpu_get_counter: "probe_fallbacks" (claimed probe sides done again exactly), "probe_exact" (1: exact path from now on)."""
+        """hjgpu_get_counter: "probe_fallbacks" (claimed probe sides done again exactly), "probe_exact" (1: exact path from now on),
+        "lookup_lds_rows" (largest build side that hjgpu_lookup answers from LDS tables; 0 under option no_broadcast)."""
         v = C.c_uint64()
         self._check(self.lib.hjgpu_get_counter(self.handle, name.encode(), C.byref(v)))
         return v.value
@@ -493,6 +496,19 @@ class HjGpu:
         self._check(self.lib.hjgpu_npj_lookup_table(self.handle, self._ptr(sk), n, self._ptr(d_table), buckets, factor,
                                                     self._ptr(vals_out), self._ptr(match_bits), C.byref(r), stream))
         return r.as_tuple()
+
+    def lookup(self, rk, rv, inner, sk, outer, params=None, vals_out=None, match_bits=None, stream=None):
+        """hjgpu_lookup: npj_lookup's contract; build sides of up to counter("lookup_lds_rows") rows are answered from LDS tables"""
+        r = Result()
+        self._check(self.lib.hjgpu_lookup(self.handle, self._ptr(rk), self._ptr(rv), inner, self._ptr(sk), outer,
+                                          C.byref(params) if params is not None else None,
+                                          self._ptr(vals_out), self._ptr(match_bits), C.byref(r), stream))
+        return r.as_tuple()
+
+    def lookup_async(self, rk, rv, inner, sk, outer, params, vals_out, match_bits, d_result, stream=None):
+        self._check(self.lib.hjgpu_lookup_async(self.handle, self._ptr(rk), self._ptr(rv), inner, self._ptr(sk), outer,
+                                                C.byref(params) if params is not None else None,
+                                                self._ptr(vals_out), self._ptr(match_bits), self._ptr(d_result), stream))
 
     # ---- whole joins ------------------------------------------------------------------
     def _join(self, fn, params, rk, rv, inner, sk, sv, outer, out, stream):

@@ -446,6 +446,23 @@ struct NpjLookupArgs {
     uint32_t *match_bits;
 };
 int hj_launch_npj_lookup(const NpjLookupArgs &a, int cus, hipStream_t stream);
+// LDS look-up (hjgpu_lookup*, join_kernels.hip lds_lookup_kernel): NpjLookupArgs' outputs and aggregates for a build side that fits one LDS
+// table (inner <= 4096: the 8 K-slot table, two workgroups per CU; up to hj_join_config_big().cap(): the 16 K-slot table, one).  Every
+// workgroup of one persistent grid fills its own table from rk / rv, then streams `keys`.  A build key 0 raises *zero_key and is skipped.
+// keys, vals_out and match_bits are 16-byte aligned; either output may be NULL.  One launch; inner == 0 && n == 0 launches nothing.
+struct LdsLookupArgs {
+    const uint32_t *rk, *rv;             // the caller's build columns
+    const uint32_t *keys;                // the probe column
+    size_t n;
+    uint32_t inner;
+    uint32_t tf0, tf1;                   // table hash / step multipliers (odd)
+    uint32_t force_chained;              // tests: skip the cuckoo fast path (option "force_chained")
+    hjgpu_result *result;
+    uint32_t *zero_key;                  // DevState::zero_key
+    uint32_t *vals_out;
+    uint32_t *match_bits;
+};
+int hj_launch_lds_lookup(const LdsLookupArgs &a, int cus, hipStream_t stream);
 
 // K9: compact the per-wave partially filled tail blocks (npj.cpp:475-514).
 // moves: scratch of 2*HJ_MAX_WORKERS entries of 24 bytes + HJ_MAX_WORKERS entries of 8 bytes.

@@ -1429,12 +1429,14 @@ int hjgpu_reserve(hjgpu_ctx *ctx, size_t inner, size_t outer)
     return HJGPU_OK;
 }
 
+static size_t lds_lookup_rows(const HjTuning &tune);
 int hjgpu_get_counter(hjgpu_ctx *ctx, const char *name, uint64_t *value)
 {
     if (!ctx || !name || !value) return HJGPU_EINVAL;
     if (strcmp(name, "probe_fallbacks") == 0) { *value = ctx->probe_fallbacks; return HJGPU_OK; }
     if (strcmp(name, "probe_exact") == 0) { *value = (ctx->tune.exact_probe_counts || ctx->probe_exact) ? 1u : 0u; return HJGPU_OK; }
-    return fail(ctx, HJGPU_EINVAL, "unknown counter (probe_fallbacks, probe_exact)");
+    if (strcmp(name, "lookup_lds_rows") == 0) { *value = lds_lookup_rows(ctx->tune); return HJGPU_OK; }
+    return fail(ctx, HJGPU_EINVAL, "unknown counter (probe_fallbacks, probe_exact, lookup_lds_rows)");
 }
 
 // the workspace's side of hjgpu_stats: what the context has spent growing it, and its last placement search
@@ -1790,6 +1792,69 @@ int hjgpu_npj_lookup(hjgpu_ctx *ctx, const uint32_t *rk, const uint32_t *rv, siz
 static size_t broadcast_rows(const HjTuning &tune, bool big_tables)
 {
     return big_tables ? (size_t)(hj_join_config_big().cap() * 0.85) : (size_t)tune.join.cap();
+}
+
+// Largest build side of the LDS look-up (hjgpu_lookup*; hjgpu_get_counter "lookup_lds_rows"): the broadcast join's, 0 under "no_broadcast"
+static size_t lds_lookup_rows(const HjTuning &tune)
+{
+    return tune.no_broadcast ? 0 : broadcast_rows(tune, true);
+}
+
+// hjgpu_lookup*: the positional look-up, by the road the build side's size asks for.  Up to lds_lookup_rows() build rows: the LDS look-up
+// (join_kernels.hip lds_lookup_kernel) - the state's clear plus ONE launch; no table in memory, no meta kernel (the empty sentinel is key
+// 0), no setup_output, no close_gaps.  The events of the phases that do not exist are recorded at the head (ms_build 0, ms_join = the
+// kernel), the two that bracket close_gaps back to back.  Everything else: npj_lookup_whole as it is.
+static int lookup_whole(hjgpu_ctx *ctx, const uint32_t *rk, const uint32_t *rv, size_t inner, const uint32_t *sk, size_t outer,
+                        const hjgpu_npj_params *prm, uint32_t *vals_out, uint32_t *match_bits, hipStream_t stream, const char *entry)
+{
+    if (inner > lds_lookup_rows(ctx->tune)) return npj_lookup_whole(ctx, rk, rv, inner, sk, outer, prm, vals_out, match_bits, stream, entry);
+    // (HJGPU_FLAG_UNIQUE is what the look-up is by definition: ignored; load and factor belong to the NPJ table)
+    if (prm) CHK(refuse_join_mode(ctx, prm->flags, entry));
+    CHK(check_columns(ctx, rk, rv, inner));
+    CHK(check_lookup_columns(ctx, sk, outer, vals_out, match_bits));
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    CHK(refuse_capture(ctx, stream));                    // before anything is allocated
+    {
+        ReserveClock clock(ctx);
+        CHK(ensure(ctx, ctx->state, sizeof(DevState)));
+    }
+    DevState *st = reinterpret_cast<DevState *>(ctx->state.p);
+    record(ctx, EV_BEGIN, stream);
+    HIPCHK(ctx, hj_zero_async(st, sizeof(DevState), stream));
+    for (int e : {EV_S_HIST, EV_S_PLAN, EV_S_SC1, EV_S_SC2, EV_WAITED, EV_R_HIST, EV_R_PLAN, EV_R_SC1, EV_R_SC2}) record(ctx, e, stream);
+    LdsLookupArgs la;
+    memset(&la, 0, sizeof(la));
+    la.rk = rk; la.rv = rv; la.inner = (uint32_t)inner; la.keys = sk; la.n = outer;
+    la.tf0 = DEFAULT_TF0; la.tf1 = DEFAULT_TF1; la.force_chained = ctx->tune.force_chained ? 1u : 0u;
+    la.result = &st->result; la.zero_key = &st->zero_key; la.vals_out = vals_out; la.match_bits = match_bits;
+    CHK(hj_launch_lds_lookup(la, ctx->cus, stream));
+    record(ctx, EV_JOIN, stream);
+    record(ctx, EV_GAPS, stream);
+    ctx->stats.fanout1 = ctx->stats.fanout2 = 1; ctx->stats.buckets = 0; ctx->stats.batches = 0;
+    ctx->last_algo = 1;
+    ctx->last_had_output = false;
+    ctx->last_lookup = true;
+    return HJGPU_OK;
+}
+
+int hjgpu_lookup_async(hjgpu_ctx *ctx, const uint32_t *rk, const uint32_t *rv, size_t inner, const uint32_t *sk, size_t outer,
+                       const hjgpu_npj_params *prm, uint32_t *vals_out, uint32_t *match_bits, hjgpu_result *d_result, void *stream_)
+{
+    if (!ctx) return HJGPU_EINVAL;
+    hipStream_t stream = (hipStream_t)stream_;
+    CHK(lookup_whole(ctx, rk, rv, inner, sk, outer, prm, vals_out, match_bits, stream, "hjgpu_lookup_async"));
+    if (d_result)
+        HIPCHK(ctx, hj_copy_async(d_result, ctx->state.p, sizeof(hjgpu_result), stream));
+    return HJGPU_OK;
+}
+
+int hjgpu_lookup(hjgpu_ctx *ctx, const uint32_t *rk, const uint32_t *rv, size_t inner, const uint32_t *sk, size_t outer,
+                 const hjgpu_npj_params *prm, uint32_t *vals_out, uint32_t *match_bits, hjgpu_result *result, void *stream_)
+{
+    if (!ctx) return HJGPU_EINVAL;
+    hipStream_t stream = (hipStream_t)stream_;
+    CHK(lookup_whole(ctx, rk, rv, inner, sk, outer, prm, vals_out, match_bits, stream, "hjgpu_lookup"));
+    return finish_blocking(ctx, result, nullptr, stream);
 }
 
 static bool broadcast_applies(const HjTuning &tune, size_t inner, size_t outer, uint32_t chunks, const hjgpu_phj_params *prm)

@@ -368,6 +368,35 @@ int  hjgpu_npj_lookup_table(hjgpu_ctx *ctx, const uint32_t *d_keys, size_t n,
                             uint32_t *d_vals_out, uint32_t *d_match_bits,
                             hjgpu_result *result, void *stream);
 
+/* ---- positional look-up, road chosen by the build side's size ---------------------------
+ * hjgpu_npj_lookup's contract, word for word: d_vals_out, d_match_bits, the aggregates, either output may be NULL, nothing is written
+ * at index >= outer / at word >= (outer + 31) / 32, the last word's high bits are 0; a build key 0 is HJGPU_EZEROKEY (the blocking
+ * form returns it, hjgpu_get_async_status / hjgpu_accumulate_async_status report it after the _async form), a probe key 0 matches
+ * nothing, inner == 0 gives all NULL and all bits 0; d_outer_keys, d_vals_out and d_match_bits 16-byte aligned (HJGPU_EALIGN); any
+ * join-mode flag is HJGPU_EINVAL naming the flag, HJGPU_FLAG_UNIQUE is ignored; a capturing stream is refused.
+ * The road: a build side of at most L rows - L = hjgpu_get_counter(ctx, "lookup_lds_rows"): the largest build side of a
+ * broadcast join; 0 under option "no_broadcast" - takes the LDS look-up: every workgroup of one persistent grid keeps the whole
+ * build side in a hash table of its own in LDS and streams the probe column once; ONE launch.  params->load and params->factor are
+ * ignored there.  Every larger build side is hjgpu_npj_lookup with `params`, exactly.
+ * Duplicated build keys: which copy answers is unspecified, as for hjgpu_npj_lookup; on the LDS road two POSITIONS with the same probe
+ * key may even receive different copies, because every workgroup fills its own table.
+ * hjgpu_get_stats after the LDS road: fanout1 = fanout2 = 1 and buckets = 0 (as after a broadcast join: how a caller sees which road
+ * ran), ms_build 0, ms_close_gaps 0, ms_join the kernel; the clear of the device state that precedes the kernel is counted in
+ * ms_histogram (a few microseconds, as after a broadcast join) and in ms_total. */
+int  hjgpu_lookup(hjgpu_ctx *ctx,
+                  const uint32_t *d_inner_keys, const uint32_t *d_inner_vals, size_t inner,
+                  const uint32_t *d_outer_keys, size_t outer,
+                  const hjgpu_npj_params *params,
+                  uint32_t *d_vals_out,      /* outer uint32, or NULL */
+                  uint32_t *d_match_bits,    /* (outer + 31) / 32 uint32, or NULL */
+                  hjgpu_result *result, void *stream);
+int  hjgpu_lookup_async(hjgpu_ctx *ctx,
+                        const uint32_t *d_inner_keys, const uint32_t *d_inner_vals, size_t inner,
+                        const uint32_t *d_outer_keys, size_t outer,
+                        const hjgpu_npj_params *params,
+                        uint32_t *d_vals_out, uint32_t *d_match_bits,
+                        hjgpu_result *d_result, void *stream);
+
 /* ---- whole joins on HBM-resident columns (replace run()/run_hj()) ---------------- */
 /* run(), npj.cpp:769-927 */
 int  hjgpu_npj(hjgpu_ctx *ctx,
