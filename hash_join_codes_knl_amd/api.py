@@ -36,6 +36,7 @@ EXPORTS = [
     "hjgpu_histogram", "hjgpu_partition", "hjgpu_partition_async", "hjgpu_join_partitions",
     "hjgpu_npj_build", "hjgpu_npj_probe",
     "hjgpu_npj_lookup", "hjgpu_npj_lookup_async", "hjgpu_npj_lookup_table", "hjgpu_lookup", "hjgpu_lookup_async",
+    "hjgpu_lookup_selected", "hjgpu_lookup_selected_async", "hjgpu_npj_lookup_table_selected",
     "hjgpu_npj", "hjgpu_phj", "hjgpu_cpra",
     "hjgpu_npj_async", "hjgpu_phj_async", "hjgpu_cpra_async", "hjgpu_phj_overlapped_async",
     "hjgpu_phj_build", "hjgpu_phj_probe", "hjgpu_phj_probe_async",
@@ -261,6 +262,9 @@ def load_library(build_if_missing=True):
     L.hjgpu_lookup.argtypes = [vp, vp, vp, sz, vp, sz, C.POINTER(NpjParams), vp, vp, C.POINTER(Result), vp]
     L.hjgpu_lookup_async.argtypes = [vp, vp, vp, sz, vp, sz, C.POINTER(NpjParams), vp, vp, vp, vp]
     L.hjgpu_npj_lookup_table.argtypes = [vp, vp, sz, vp, sz, u32, vp, vp, C.POINTER(Result), vp]
+    L.hjgpu_lookup_selected.argtypes = [vp, vp, vp, sz, vp, sz, C.POINTER(NpjParams), vp, vp, vp, C.POINTER(Result), vp]
+    L.hjgpu_lookup_selected_async.argtypes = [vp, vp, vp, sz, vp, sz, C.POINTER(NpjParams), vp, vp, vp, vp, vp]
+    L.hjgpu_npj_lookup_table_selected.argtypes = [vp, vp, sz, vp, sz, u32, vp, vp, vp, C.POINTER(Result), vp]
     join = [vp, vp, vp, sz, vp, vp, sz]
     L.hjgpu_npj.argtypes = join + [C.POINTER(NpjParams), C.POINTER(Result), C.POINTER(Output), vp]
     L.hjgpu_phj.argtypes = join + [C.POINTER(PhjParams), C.POINTER(Result), C.POINTER(Output), vp]
@@ -509,6 +513,28 @@ class HjGpu:
         self._check(self.lib.hjgpu_lookup_async(self.handle, self._ptr(rk), self._ptr(rv), inner, self._ptr(sk), outer,
                                                 C.byref(params) if params is not None else None,
                                                 self._ptr(vals_out), self._ptr(match_bits), self._ptr(d_result), stream))
+
+    # ---- selected look-up: select_bits (match_bits' layout, or None) says which rows are looked up; match_bits may be select_bits ----
+    def lookup_selected(self, rk, rv, inner, sk, outer, params=None, select_bits=None, vals_out=None, match_bits=None, stream=None):
+        """hjgpu_lookup_selected: lookup for the rows whose bit is set in select_bits; the others get NULL and bit 0 and cost no table access"""
+        r = Result()
+        self._check(self.lib.hjgpu_lookup_selected(self.handle, self._ptr(rk), self._ptr(rv), inner, self._ptr(sk), outer,
+                                                   C.byref(params) if params is not None else None, self._ptr(select_bits),
+                                                   self._ptr(vals_out), self._ptr(match_bits), C.byref(r), stream))
+        return r.as_tuple()
+
+    def lookup_selected_async(self, rk, rv, inner, sk, outer, params, select_bits, vals_out, match_bits, d_result, stream=None):
+        self._check(self.lib.hjgpu_lookup_selected_async(self.handle, self._ptr(rk), self._ptr(rv), inner, self._ptr(sk), outer,
+                                                         C.byref(params) if params is not None else None, self._ptr(select_bits),
+                                                         self._ptr(vals_out), self._ptr(match_bits), self._ptr(d_result), stream))
+
+    def npj_lookup_table_selected(self, sk, n, d_table, buckets, factor, select_bits=None, vals_out=None, match_bits=None, stream=None):
+        """hjgpu_npj_lookup_table_selected: the selected look-up in a table that npj_build made"""
+        r = Result()
+        self._check(self.lib.hjgpu_npj_lookup_table_selected(self.handle, self._ptr(sk), n, self._ptr(d_table), buckets, factor,
+                                                             self._ptr(select_bits), self._ptr(vals_out), self._ptr(match_bits),
+                                                             C.byref(r), stream))
+        return r.as_tuple()
 
     # ---- whole joins ------------------------------------------------------------------
     def _join(self, fn, params, rk, rv, inner, sk, sv, outer, out, stream):

@@ -463,6 +463,38 @@ struct LdsLookupArgs {
     uint32_t *match_bits;
 };
 int hj_launch_lds_lookup(const LdsLookupArgs &a, int cus, hipStream_t stream);
+// Selected look-ups (hjgpu_lookup_selected*, hjgpu_npj_lookup_table_selected; DESIGN.md section 5 "Selected look-up"): the two look-ups
+// above for the rows whose bit is set in select_bits (match_bits' layout, (n + 31) / 32 words, 16-byte aligned, never NULL here: without a
+// mask the entry points take the plain launchers).  An unselected row gets HJGPU_NULL_VAL and bit 0, is counted in no aggregate and costs
+// no table access.  match_bits may be select_bits itself: a wave reads the words it will store, and before it stores them.  Structs of
+// their own - the old fields plus the mask - so that NpjLookupArgs and LdsLookupArgs, and with them every existing kernel, stay as they are.
+struct NpjLookupSelArgs {
+    const uint32_t *keys;
+    size_t n;
+    const u64 *table;
+    size_t buckets;
+    uint32_t factor;
+    uint32_t line_hash;
+    hjgpu_result *result;
+    uint32_t *vals_out;
+    uint32_t *match_bits;
+    const uint32_t *select_bits;
+};
+int hj_launch_npj_lookup_sel(const NpjLookupSelArgs &a, int cus, hipStream_t stream);
+struct LdsLookupSelArgs {
+    const uint32_t *rk, *rv;
+    const uint32_t *keys;
+    size_t n;
+    uint32_t inner;
+    uint32_t tf0, tf1;
+    uint32_t force_chained;
+    hjgpu_result *result;
+    uint32_t *zero_key;
+    uint32_t *vals_out;
+    uint32_t *match_bits;
+    const uint32_t *select_bits;
+};
+int hj_launch_lds_lookup_sel(const LdsLookupSelArgs &a, int cus, hipStream_t stream);
 
 // K9: compact the per-wave partially filled tail blocks (npj.cpp:475-514).
 // moves: scratch of 2*HJ_MAX_WORKERS entries of 24 bytes + HJ_MAX_WORKERS entries of 8 bytes.

@@ -1224,23 +1224,45 @@ int npj_enqueue(hjgpu_ctx *ctx, const uint32_t *rk, const uint32_t *rv, size_t i
     return HJGPU_OK;
 }
 
-// The positional look-up behind a built table (hjgpu_npj_lookup*): one kernel.  No setup_output, no final_offsets, no close_gaps - the
-// two events that bracket close_gaps elsewhere are recorded back to back (ms_close_gaps 0).  ctx->state is zeroed by the caller.
-int npj_lookup_enqueue(hjgpu_ctx *ctx, const uint32_t *sk, size_t outer, const NpjTable &t, uint32_t *vals_out, uint32_t *match_bits,
-                       hipStream_t stream)
+// what every look-up leaves behind its kernel: the two events that bracket close_gaps elsewhere, and the stats that tell the roads apart
+// (LDS road: fanout 1 x 1 and no buckets, as after a broadcast join; NPJ road: the table's buckets)
+static void lookup_done(hjgpu_ctx *ctx, hipStream_t stream, bool lds, size_t buckets)
 {
-    DevState *st = reinterpret_cast<DevState *>(ctx->state.p);
-    NpjLookupArgs la;
+    record(ctx, EV_JOIN, stream);
+    record(ctx, EV_GAPS, stream);
+    ctx->stats.fanout1 = ctx->stats.fanout2 = lds ? 1 : 0; ctx->stats.buckets = buckets; ctx->stats.batches = 0;
+    ctx->last_algo = lds ? 1 : 0;
+    ctx->last_had_output = false;
+    ctx->last_lookup = true;
+}
+
+// the fields NpjLookupArgs and NpjLookupSelArgs share
+template <class Args>
+static Args npj_lookup_args(const uint32_t *sk, size_t outer, const NpjTable &t, DevState *st, uint32_t *vals_out, uint32_t *match_bits)
+{
+    Args la;
     memset(&la, 0, sizeof(la));
     la.keys = sk; la.n = outer; la.table = t.slots; la.buckets = t.buckets; la.factor = t.factor; la.line_hash = t.line_hash ? 1u : 0u;
     la.result = &st->result; la.vals_out = vals_out; la.match_bits = match_bits;
-    if (outer) CHK(hj_launch_npj_lookup(la, ctx->cus, stream));
-    record(ctx, EV_JOIN, stream);
-    record(ctx, EV_GAPS, stream);
-    ctx->stats.fanout1 = ctx->stats.fanout2 = 0; ctx->stats.buckets = t.buckets; ctx->stats.batches = 0;
-    ctx->last_algo = 0;
-    ctx->last_had_output = false;
-    ctx->last_lookup = true;
+    return la;
+}
+
+// The positional look-up behind a built table (hjgpu_npj_lookup*): one kernel.  No setup_output, no final_offsets, no close_gaps - the
+// two events that bracket close_gaps elsewhere are recorded back to back (ms_close_gaps 0).  ctx->state is zeroed by the caller.
+// select_bits != NULL: the selected look-up (hjgpu_*_selected), kernels of its own; NULL: the plain one
+int npj_lookup_enqueue(hjgpu_ctx *ctx, const uint32_t *sk, size_t outer, const NpjTable &t, uint32_t *vals_out, uint32_t *match_bits,
+                       hipStream_t stream, const uint32_t *select_bits)
+{
+    DevState *st = reinterpret_cast<DevState *>(ctx->state.p);
+    if (select_bits) {
+        NpjLookupSelArgs la = npj_lookup_args<NpjLookupSelArgs>(sk, outer, t, st, vals_out, match_bits);
+        la.select_bits = select_bits;
+        if (outer) CHK(hj_launch_npj_lookup_sel(la, ctx->cus, stream));
+    } else {
+        const NpjLookupArgs la = npj_lookup_args<NpjLookupArgs>(sk, outer, t, st, vals_out, match_bits);
+        if (outer) CHK(hj_launch_npj_lookup(la, ctx->cus, stream));
+    }
+    lookup_done(ctx, stream, false, t.buckets);
     return HJGPU_OK;
 }
 
@@ -1254,20 +1276,34 @@ int check_lookup_columns(hjgpu_ctx *ctx, const uint32_t *sk, size_t outer, const
     return HJGPU_OK;
 }
 
+// what the selected look-ups check of their mask (NULL: no mask).  d_match_bits may be d_select_bits itself - the kernels read a word of
+// the mask in the wave that stores it, before it stores it -; two bitmaps that overlap in any other way would be read after they were
+// written
+int check_select_bits(hjgpu_ctx *ctx, const uint32_t *select_bits, const uint32_t *match_bits, size_t outer)
+{
+    if ((uintptr_t)select_bits & 15) return fail(ctx, HJGPU_EALIGN, "d_select_bits must be 16-byte aligned");
+    const uintptr_t s = (uintptr_t)select_bits, m = (uintptr_t)match_bits, bytes = (outer + 31) / 32 * sizeof(uint32_t);
+    if (select_bits && match_bits && s != m && s < m + bytes && m < s + bytes)
+        return fail(ctx, HJGPU_EINVAL, "d_match_bits overlaps d_select_bits: it may be the very pointer d_select_bits (in place), any other overlap of the two bitmaps is refused");
+    return HJGPU_OK;
+}
+
 static int npj_lookup_whole(hjgpu_ctx *ctx, const uint32_t *rk, const uint32_t *rv, size_t inner, const uint32_t *sk, size_t outer,
-                            const hjgpu_npj_params *prm, uint32_t *vals_out, uint32_t *match_bits, hipStream_t stream, const char *entry)
+                            const hjgpu_npj_params *prm, uint32_t *vals_out, uint32_t *match_bits, hipStream_t stream, const char *entry,
+                            const uint32_t *select_bits = nullptr)
 {
     // (HJGPU_FLAG_UNIQUE is what the look-up is by definition: ignored)
     if (prm) CHK(refuse_join_mode(ctx, prm->flags, entry));
     CHK(check_columns(ctx, rk, rv, inner));
     CHK(check_lookup_columns(ctx, sk, outer, vals_out, match_bits));
+    CHK(check_select_bits(ctx, select_bits, match_bits, outer));
     HIPCHK(ctx, hipSetDevice(ctx->device));
     size_t buckets; uint32_t factor;
     CHK(refuse_capture(ctx, stream));                    // before anything is allocated or probed
     CHK(npj_prepare(ctx, inner, prm, &buckets, &factor));     // (no mode flag is left in prm: no bucket bitmap)
     const bool line = !ctx->tune.npj_refhash;
     CHK(npj_build_enqueue(ctx, rk, rv, inner, buckets, factor, stream, line));
-    return npj_lookup_enqueue(ctx, sk, outer, {reinterpret_cast<const u64 *>(ctx->table.p), buckets, factor, line}, vals_out, match_bits, stream);
+    return npj_lookup_enqueue(ctx, sk, outer, {reinterpret_cast<const u64 *>(ctx->table.p), buckets, factor, line}, vals_out, match_bits, stream, select_bits);
 }
 
 // hjgpu_accumulate_async_status: the two flags of the last join -> two running uint64 counters
@@ -1804,14 +1840,19 @@ static size_t lds_lookup_rows(const HjTuning &tune)
 // (join_kernels.hip lds_lookup_kernel) - the state's clear plus ONE launch; no table in memory, no meta kernel (the empty sentinel is key
 // 0), no setup_output, no close_gaps.  The events of the phases that do not exist are recorded at the head (ms_build 0, ms_join = the
 // kernel), the two that bracket close_gaps back to back.  Everything else: npj_lookup_whole as it is.
+// select_bits (hjgpu_lookup_selected*; NULL: none): only the rows whose bit is set are looked up - the same roads, chosen by `inner` alone,
+// with the selected kernels (lds_lookup_sel_kernel, npj_lookup_sel_*_kernel)
 static int lookup_whole(hjgpu_ctx *ctx, const uint32_t *rk, const uint32_t *rv, size_t inner, const uint32_t *sk, size_t outer,
-                        const hjgpu_npj_params *prm, uint32_t *vals_out, uint32_t *match_bits, hipStream_t stream, const char *entry)
+                        const hjgpu_npj_params *prm, uint32_t *vals_out, uint32_t *match_bits, hipStream_t stream, const char *entry,
+                        const uint32_t *select_bits = nullptr)
 {
-    if (inner > lds_lookup_rows(ctx->tune)) return npj_lookup_whole(ctx, rk, rv, inner, sk, outer, prm, vals_out, match_bits, stream, entry);
+    if (inner > lds_lookup_rows(ctx->tune))
+        return npj_lookup_whole(ctx, rk, rv, inner, sk, outer, prm, vals_out, match_bits, stream, entry, select_bits);
     // (HJGPU_FLAG_UNIQUE is what the look-up is by definition: ignored; load and factor belong to the NPJ table)
     if (prm) CHK(refuse_join_mode(ctx, prm->flags, entry));
     CHK(check_columns(ctx, rk, rv, inner));
     CHK(check_lookup_columns(ctx, sk, outer, vals_out, match_bits));
+    CHK(check_select_bits(ctx, select_bits, match_bits, outer));
     HIPCHK(ctx, hipSetDevice(ctx->device));
     CHK(refuse_capture(ctx, stream));                    // before anything is allocated
     {
@@ -1822,18 +1863,22 @@ static int lookup_whole(hjgpu_ctx *ctx, const uint32_t *rk, const uint32_t *rv, 
     record(ctx, EV_BEGIN, stream);
     HIPCHK(ctx, hj_zero_async(st, sizeof(DevState), stream));
     for (int e : {EV_S_HIST, EV_S_PLAN, EV_S_SC1, EV_S_SC2, EV_WAITED, EV_R_HIST, EV_R_PLAN, EV_R_SC1, EV_R_SC2}) record(ctx, e, stream);
-    LdsLookupArgs la;
-    memset(&la, 0, sizeof(la));
-    la.rk = rk; la.rv = rv; la.inner = (uint32_t)inner; la.keys = sk; la.n = outer;
-    la.tf0 = DEFAULT_TF0; la.tf1 = DEFAULT_TF1; la.force_chained = ctx->tune.force_chained ? 1u : 0u;
-    la.result = &st->result; la.zero_key = &st->zero_key; la.vals_out = vals_out; la.match_bits = match_bits;
-    CHK(hj_launch_lds_lookup(la, ctx->cus, stream));
-    record(ctx, EV_JOIN, stream);
-    record(ctx, EV_GAPS, stream);
-    ctx->stats.fanout1 = ctx->stats.fanout2 = 1; ctx->stats.buckets = 0; ctx->stats.batches = 0;
-    ctx->last_algo = 1;
-    ctx->last_had_output = false;
-    ctx->last_lookup = true;
+    // the fields LdsLookupArgs and LdsLookupSelArgs share
+    auto args = [&](auto la) {
+        memset(&la, 0, sizeof(la));
+        la.rk = rk; la.rv = rv; la.inner = (uint32_t)inner; la.keys = sk; la.n = outer;
+        la.tf0 = DEFAULT_TF0; la.tf1 = DEFAULT_TF1; la.force_chained = ctx->tune.force_chained ? 1u : 0u;
+        la.result = &st->result; la.zero_key = &st->zero_key; la.vals_out = vals_out; la.match_bits = match_bits;
+        return la;
+    };
+    if (select_bits) {
+        LdsLookupSelArgs la = args(LdsLookupSelArgs{});
+        la.select_bits = select_bits;
+        CHK(hj_launch_lds_lookup_sel(la, ctx->cus, stream));
+    } else {
+        CHK(hj_launch_lds_lookup(args(LdsLookupArgs{}), ctx->cus, stream));
+    }
+    lookup_done(ctx, stream, true, 0);
     return HJGPU_OK;
 }
 
@@ -1854,6 +1899,29 @@ int hjgpu_lookup(hjgpu_ctx *ctx, const uint32_t *rk, const uint32_t *rv, size_t 
     if (!ctx) return HJGPU_EINVAL;
     hipStream_t stream = (hipStream_t)stream_;
     CHK(lookup_whole(ctx, rk, rv, inner, sk, outer, prm, vals_out, match_bits, stream, "hjgpu_lookup"));
+    return finish_blocking(ctx, result, nullptr, stream);
+}
+
+// hjgpu_lookup_selected*: hjgpu_lookup* for the rows whose bit is set in d_select_bits (NULL: every row - the plain call itself)
+int hjgpu_lookup_selected_async(hjgpu_ctx *ctx, const uint32_t *rk, const uint32_t *rv, size_t inner, const uint32_t *sk, size_t outer,
+                                const hjgpu_npj_params *prm, const uint32_t *select_bits, uint32_t *vals_out, uint32_t *match_bits,
+                                hjgpu_result *d_result, void *stream_)
+{
+    if (!ctx) return HJGPU_EINVAL;
+    hipStream_t stream = (hipStream_t)stream_;
+    CHK(lookup_whole(ctx, rk, rv, inner, sk, outer, prm, vals_out, match_bits, stream, "hjgpu_lookup_selected_async", select_bits));
+    if (d_result)
+        HIPCHK(ctx, hj_copy_async(d_result, ctx->state.p, sizeof(hjgpu_result), stream));
+    return HJGPU_OK;
+}
+
+int hjgpu_lookup_selected(hjgpu_ctx *ctx, const uint32_t *rk, const uint32_t *rv, size_t inner, const uint32_t *sk, size_t outer,
+                          const hjgpu_npj_params *prm, const uint32_t *select_bits, uint32_t *vals_out, uint32_t *match_bits,
+                          hjgpu_result *result, void *stream_)
+{
+    if (!ctx) return HJGPU_EINVAL;
+    hipStream_t stream = (hipStream_t)stream_;
+    CHK(lookup_whole(ctx, rk, rv, inner, sk, outer, prm, vals_out, match_bits, stream, "hjgpu_lookup_selected", select_bits));
     return finish_blocking(ctx, result, nullptr, stream);
 }
 

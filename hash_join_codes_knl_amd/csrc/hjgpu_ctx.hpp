@@ -332,9 +332,11 @@ int npj_enqueue(hjgpu_ctx *ctx, const uint32_t *rk, const uint32_t *rv, size_t i
                 size_t buckets, uint32_t factor, const hjgpu_output *out, hipStream_t stream, bool unique, uint32_t mode = HJ_MODE_INNER);
 const hjgpu_output *take_async_output(hjgpu_ctx *ctx, const hjgpu_output *given);
 // the positional look-up in a built table (hjgpu_npj_lookup*: npj_kernels.hip); ctx->state zeroed by the caller, EV_BEGIN / EV_R_HIST recorded
+// select_bits: the mask of a selected look-up (NULL: none, every row is looked up)
 int npj_lookup_enqueue(hjgpu_ctx *ctx, const uint32_t *sk, size_t outer, const NpjTable &t, uint32_t *vals_out, uint32_t *match_bits,
-                       hipStream_t stream);
+                       hipStream_t stream, const uint32_t *select_bits = nullptr);
 int check_lookup_columns(hjgpu_ctx *ctx, const uint32_t *sk, size_t outer, const uint32_t *vals_out, const uint32_t *match_bits);
+int check_select_bits(hjgpu_ctx *ctx, const uint32_t *select_bits, const uint32_t *match_bits, size_t outer);
 // hjgpu_ops.hip: the partition operator on one relation (hjgpu_partition*, hjgpu_partition_packed_*; pass 0 of a grouped plan) - what
 // differs between its forms
 struct PartitionForm {

@@ -222,9 +222,17 @@ int hjgpu_npj_probe(hjgpu_ctx *ctx, const uint32_t *d_keys, const uint32_t *d_va
 int hjgpu_npj_lookup_table(hjgpu_ctx *ctx, const uint32_t *d_keys, size_t n, const uint64_t *d_table, size_t buckets, uint32_t factor,
                            uint32_t *d_vals_out, uint32_t *d_match_bits, hjgpu_result *result, void *stream_)
 {
+    return hjgpu_npj_lookup_table_selected(ctx, d_keys, n, d_table, buckets, factor, nullptr, d_vals_out, d_match_bits, result, stream_);
+}
+
+// the look-up in a built table for the rows whose bit is set in d_select_bits (NULL: every row - the plain look-up, its kernels)
+int hjgpu_npj_lookup_table_selected(hjgpu_ctx *ctx, const uint32_t *d_keys, size_t n, const uint64_t *d_table, size_t buckets, uint32_t factor,
+                                    const uint32_t *d_select_bits, uint32_t *d_vals_out, uint32_t *d_match_bits, hjgpu_result *result, void *stream_)
+{
     if (!ctx || !d_table || buckets == 0) return fail(ctx, HJGPU_EINVAL, "null pointer");
     if ((uintptr_t)d_table & 7) return fail(ctx, HJGPU_EALIGN, "the table must be 8-byte aligned");
     CHK(check_lookup_columns(ctx, d_keys, n, d_vals_out, d_match_bits));
+    CHK(check_select_bits(ctx, d_select_bits, d_match_bits, n));
     hipStream_t stream = (hipStream_t)stream_;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     CHK(refuse_capture(ctx, stream));
@@ -232,7 +240,7 @@ int hjgpu_npj_lookup_table(hjgpu_ctx *ctx, const uint32_t *d_keys, size_t n, con
     HIPCHK(ctx, hj_zero_async(ctx->state.p, sizeof(DevState), stream));
     record(ctx, EV_BEGIN, stream); record(ctx, EV_R_HIST, stream);
     const NpjTable table = {.slots = (const u64 *)d_table, .buckets = buckets, .factor = factor, .line_hash = false};      // hjgpu_npj_build's: the reference's hash
-    CHK(npj_lookup_enqueue(ctx, d_keys, n, table, d_vals_out, d_match_bits, stream));
+    CHK(npj_lookup_enqueue(ctx, d_keys, n, table, d_vals_out, d_match_bits, stream, d_select_bits));
     return finish_blocking(ctx, result, nullptr, stream);
 }
 

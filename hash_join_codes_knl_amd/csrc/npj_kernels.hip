@@ -17,6 +17,7 @@
 #include "hj_device.hpp"
 #include "hj_internal.hpp"
 #include "hj_emit.hpp"
+#include "hj_lookup_sel.hpp"
 
 __device__ __forceinline__ u64 npj_bucket(uint32_t key, uint32_t factor, u64 buckets)
 {
@@ -1031,6 +1032,212 @@ int hj_launch_npj_lookup(const NpjLookupArgs &a, int cus, hipStream_t stream)
         hj_with_bool(a.match_bits != nullptr, [&](auto bits) {
             constexpr bool V = decltype(vals)::value, M = decltype(bits)::value;
             kernel = a.line_hash ? npj_lookup_line_kernel<V, M> : grouped ? npj_lookup_kernel<true, V, M> : npj_lookup_kernel<false, V, M>;
+        });
+    });
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(NPJ_PROBE_BLOCK), 0, stream, a);
+    return hipGetLastError() == hipSuccess ? HJGPU_OK : HJGPU_EHIP;
+}
+
+// --------------------------------------------------------------------------
+// Selected look-up (hjgpu_lookup_selected*, hjgpu_npj_lookup_table_selected; DESIGN.md section 5 "Selected look-up"): the two look-up
+// kernels above for the rows whose bit is set in a.select_bits.  An unselected row is never active: no load of the table is issued for
+// it, it leaves as HJGPU_NULL_VAL with bit 0 and is counted nowhere.  Kernels of their own beside the plain ones, which stay as they
+// are; the head and the end of a trip are hj_lookup_sel.hpp's, where the in-place rule (match_bits == select_bits) is kept.
+// NPJ_SEL_BATCH wave trips per loop iteration: their select words are loaded first, then their keys (sel_fetch).
+// --------------------------------------------------------------------------
+constexpr int NPJ_SEL_BATCH = 2;
+
+template <int OWNER>
+__device__ __forceinline__ uint32_t quad_bcast(uint32_t x)           // the value of lane OWNER of the quad
+{
+    return quad_perm<OWNER * 0x55>(x);
+}
+
+// The line walk for ONE owner lane of the quad: its four keys, all four lines in flight (npj_lookup_line_kernel's round, B = 4).  A quad
+// none of whose owner's keys is selected skips the round; where that holds for every quad of the wave the round issues nothing.
+template <int OWNER>
+__device__ __forceinline__ void npj_sel_line_round(const uint4 *__restrict__ t4, u64 lines, uint32_t factor, uint32_t sub, const uint32_t (&kc)[4],
+                                                   uint32_t sel, uint32_t (&res)[4], uint32_t &nib)
+{
+    const uint32_t on = quad_bcast<OWNER>(sel);                     // the owner's select nibble: quad-uniform
+    if (on == 0u) return;
+    uint32_t key[4];
+    bool act[4];
+    u64 ln[4];
+    uint4 q[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        key[i] = quad_bcast<OWNER>(kc[i]);
+        act[i] = (on >> i) & 1u;
+        ln[i] = npj_bucket(key[i], factor, lines);
+        q[i] = make_uint4(0, 0, 0, 0);
+        if (act[i]) q[i] = t4[4 * ln[i] + sub];                     // 4 lanes x 16 bytes = the key's line
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        uint32_t pay = 0;                                           // the first match's payload, in the lane that holds its bucket
+        bool got = false;                                           // the walk found a match (quad-uniform)
+        while (act[i]) {                                            // uniform inside the quad
+            uint32_t fe = q[i].x == 0u ? 2 * sub : (q[i].z == 0u ? 2 * sub + 1 : 8u);      // first empty bucket of the line, over the quad
+            fe = min(fe, quad_perm<0xB1>(fe));
+            fe = min(fe, quad_perm<0x4E>(fe));
+            const bool m0 = q[i].x == key[i] && 2 * sub < fe;
+            const bool m1 = q[i].z == key[i] && 2 * sub + 1 < fe;
+            uint32_t fm = m0 ? 2 * sub : (m1 ? 2 * sub + 1 : 8u);   // only the FIRST match counts: the lowest matching bucket of the line
+            const uint32_t mine = fm;
+            fm = min(fm, quad_perm<0xB1>(fm));
+            fm = min(fm, quad_perm<0x4E>(fm));
+            got = fm < 8u;
+            if (got && mine == fm) pay = m0 ? q[i].y : q[i].w;
+            if (fe < 8u || got) break;                              // the walk ends at the first match or the first empty bucket
+            if (++ln[i] == lines) ln[i] = 0;                        // full line: the walk goes on in the next one
+            q[i] = t4[4 * ln[i] + sub];
+        }
+        pay |= quad_perm<0xB1>(pay);                                // to the owner
+        pay |= quad_perm<0x4E>(pay);
+        if (got && sub == (uint32_t)OWNER) { res[i] = pay; nib |= 1u << i; }
+    }
+}
+
+template <bool VALS, bool BITS>
+__global__ __launch_bounds__(NPJ_PROBE_BLOCK) void npj_lookup_sel_line_kernel(NpjLookupSelArgs a)
+{
+    constexpr int NW = NPJ_PROBE_WAVES;
+    constexpr int BATCH = NPJ_SEL_BATCH;
+    __shared__ u64 red[4][NW];
+    const uint4 *__restrict__ k4 = reinterpret_cast<const uint4 *>(a.keys);
+    const u64 n = a.n, nvec = (n + 3) >> 2, stride = (u64)gridDim.x * NPJ_PROBE_BLOCK;
+    const uint4 *__restrict__ t4 = reinterpret_cast<const uint4 *>(a.table);
+    const u64 lines = a.buckets >> 3;
+    const uint32_t factor = a.factor;
+    const uint32_t sub = threadIdx.x & 3;                  // my quarter of the line: buckets 2*sub, 2*sub + 1
+
+    u64 acc_n = 0, acc_k = 0, acc_i = 0;
+    // whole waves iterate together (the quad exchanges and the bitmaps' words need all lanes)
+    for (u64 v0 = (u64)blockIdx.x * NPJ_PROBE_BLOCK + (threadIdx.x & ~63u); v0 < nvec; v0 += stride * BATCH) {
+        uint32_t sel[BATCH];
+        uint4 kk[BATCH];
+        sel_fetch<BATCH>(a.select_bits, k4, v0, stride, n, sel, kk);
+#pragma unroll
+        for (int u = 0; u < BATCH; ++u) {
+            if (v0 + (u64)u * stride >= nvec) break;                     // the wave's trip lies beyond the column (the same for all its lanes)
+            const u64 v = v0 + (u64)u * stride + hj_lane();
+            const uint32_t kc[4] = {kk[u].x, kk[u].y, kk[u].z, kk[u].w};
+            uint32_t res[4] = {HJGPU_NULL_VAL, HJGPU_NULL_VAL, HJGPU_NULL_VAL, HJGPU_NULL_VAL};
+            uint32_t nib = 0;
+            if (__ballot(sel[u] != 0u) != 0ull) {                        // a trip without a selected row: straight to the stores
+                npj_sel_line_round<0>(t4, lines, factor, sub, kc, sel[u], res, nib);
+                npj_sel_line_round<1>(t4, lines, factor, sub, kc, sel[u], res, nib);
+                npj_sel_line_round<2>(t4, lines, factor, sub, kc, sel[u], res, nib);
+                npj_sel_line_round<3>(t4, lines, factor, sub, kc, sel[u], res, nib);
+            }
+            sel_leave<VALS, BITS>(a.vals_out, a.match_bits, n, v, kc, res, nib, acc_n, acc_k, acc_i);
+        }
+    }
+    hj_add_to_result(red, a.result, acc_n, acc_k, 0ull, acc_i);
+}
+
+// Tables with the reference's hash: npj_lookup_kernel's walks, every lane its own four rows, act[j] only where row j is selected.
+template <bool GROUPED, bool VALS, bool BITS>
+__global__ __launch_bounds__(NPJ_PROBE_BLOCK) void npj_lookup_sel_kernel(NpjLookupSelArgs a)
+{
+    constexpr int NW = NPJ_PROBE_WAVES;
+    constexpr int BATCH = NPJ_SEL_BATCH;
+    __shared__ u64 red[4][NW];
+    const uint4 *__restrict__ k4 = reinterpret_cast<const uint4 *>(a.keys);
+    const u64 n = a.n, nvec = (n + 3) >> 2, stride = (u64)gridDim.x * NPJ_PROBE_BLOCK;
+    const u64 *__restrict__ table = a.table;
+    const u64 buckets = a.buckets;
+    const uint32_t factor = a.factor;
+
+    u64 acc_n = 0, acc_k = 0, acc_i = 0;
+    // whole waves iterate together (the bitmaps' words need all lanes)
+    for (u64 v0 = (u64)blockIdx.x * NPJ_PROBE_BLOCK + (threadIdx.x & ~63u); v0 < nvec; v0 += stride * BATCH) {
+        uint32_t sel[BATCH];
+        uint4 kk[BATCH];
+        sel_fetch<BATCH>(a.select_bits, k4, v0, stride, n, sel, kk);
+#pragma unroll
+        for (int u = 0; u < BATCH; ++u) {
+            if (v0 + (u64)u * stride >= nvec) break;                     // the wave's trip lies beyond the column (the same for all its lanes)
+            const u64 v = v0 + (u64)u * stride + hj_lane();
+            const uint32_t key[4] = {kk[u].x, kk[u].y, kk[u].z, kk[u].w};
+            uint32_t res[4] = {HJGPU_NULL_VAL, HJGPU_NULL_VAL, HJGPU_NULL_VAL, HJGPU_NULL_VAL};
+            uint32_t nib = 0;
+            u64 h[4];
+            bool act[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                act[j] = (sel[u] >> j) & 1u;
+                h[j] = npj_bucket(key[j], factor, buckets);
+            }
+            if (GROUPED) {
+                const uint4 *__restrict__ t4 = reinterpret_cast<const uint4 *>(table);
+                while (act[0] | act[1] | act[2] | act[3]) {
+                    uint4 lo[4], hi[4];
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {           // all group loads of the 4 chains in flight together
+                        lo[j] = make_uint4(0, 0, 0, 0); hi[j] = lo[j];
+                        if (act[j]) { const u64 grp = h[j] >> 2; lo[j] = t4[2 * grp]; hi[j] = t4[2 * grp + 1]; }
+                    }
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        if (act[j]) {
+                            const uint32_t bk[4] = {lo[j].x, lo[j].z, hi[j].x, hi[j].z};   // keys of the group
+                            const uint32_t bv[4] = {lo[j].y, lo[j].w, hi[j].y, hi[j].w};   // payloads
+                            const uint32_t first = (uint32_t)h[j] & 3u;
+                            bool open = true;                                              // neither an empty bucket nor a match seen yet
+#pragma unroll
+                            for (int b = 0; b < 4; ++b) {
+                                const bool inb = open && ((uint32_t)b >= first);
+                                if (inb && bk[b] == 0u) open = false;
+                                else if (inb && bk[b] == key[j]) { res[j] = bv[b]; nib |= 1u << j; open = false; }
+                            }
+                            if (!open) act[j] = false;
+                            else { h[j] = (h[j] & ~3ull) + 4; if (h[j] >= buckets) h[j] = 0; }
+                        }
+                    }
+                }
+            } else {
+                u64 t[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) t[j] = act[j] ? table[h[j]] : 0ull;
+                while (act[0] | act[1] | act[2] | act[3]) {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        if (act[j]) {
+                            if ((uint32_t)t[j] == 0u) {
+                                act[j] = false;
+                            } else if ((uint32_t)t[j] == key[j]) {
+                                res[j] = (uint32_t)(t[j] >> 32); nib |= 1u << j;
+                                act[j] = false;
+                            } else {
+                                if (++h[j] == buckets) h[j] = 0;
+                                t[j] = table[h[j]];
+                            }
+                        }
+                    }
+                }
+            }
+            sel_leave<VALS, BITS>(a.vals_out, a.match_bits, n, v, key, res, nib, acc_n, acc_k, acc_i);
+        }
+    }
+    hj_add_to_result(red, a.result, acc_n, acc_k, 0ull, acc_i);
+}
+
+// hj_launch_npj_lookup's checks plus the mask's; the same grid
+int hj_launch_npj_lookup_sel(const NpjLookupSelArgs &a, int cus, hipStream_t stream)
+{
+    if (a.n == 0) return HJGPU_OK;
+    if (!a.keys || !a.table || !a.result || !a.select_bits || a.buckets == 0) return HJGPU_EINVAL;
+    if ((((uintptr_t)a.keys | (uintptr_t)a.vals_out | (uintptr_t)a.match_bits | (uintptr_t)a.select_bits) & 15) || ((uintptr_t)a.table & 7)) return HJGPU_EINVAL;
+    if (a.line_hash && (a.buckets % 8 != 0 || ((uintptr_t)a.table & 63))) return HJGPU_EINVAL;
+    const int grid = hj_npj_probe_grid(cus, a.n);
+    const bool grouped = (a.buckets % 4 == 0) && (((uintptr_t)a.table & 31) == 0);
+    void (*kernel)(NpjLookupSelArgs) = nullptr;
+    hj_with_bool(a.vals_out != nullptr, [&](auto vals) {
+        hj_with_bool(a.match_bits != nullptr, [&](auto bits) {
+            constexpr bool V = decltype(vals)::value, M = decltype(bits)::value;
+            kernel = a.line_hash ? npj_lookup_sel_line_kernel<V, M> : grouped ? npj_lookup_sel_kernel<true, V, M> : npj_lookup_sel_kernel<false, V, M>;
         });
     });
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(NPJ_PROBE_BLOCK), 0, stream, a);

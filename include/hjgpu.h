@@ -397,6 +397,40 @@ int  hjgpu_lookup_async(hjgpu_ctx *ctx,
                         uint32_t *d_vals_out, uint32_t *d_match_bits,
                         hjgpu_result *d_result, void *stream);
 
+/* ---- selected positional look-up: a bitmap of the rows to look up ----------------------
+ * hjgpu_lookup / hjgpu_lookup_async / hjgpu_npj_lookup_table with an input bitmap in d_match_bits' layout - what the next dimension
+ * of a star query takes from the one before it: only the rows whose bit is set are looked up, and an unselected row costs no table
+ * access.  The contract is the plain entry point's, word for word, plus:
+ *   d_select_bits    (outer + 31) / 32 words; bit i & 31 of word i >> 5 says whether row i is selected.  Bits of the last word at
+ *                    positions >= outer are ignored (they may hold anything), no word at index >= (outer + 31) / 32 is read.  16-byte
+ *                    aligned (HJGPU_EALIGN).  NULL: every row is selected - the call IS the plain entry point, same kernels.
+ *   an unselected row i: d_vals_out[i] = HJGPU_NULL_VAL, match bit 0, counted in no aggregate.
+ *   a selected row: exactly what the plain look-up gives it.
+ *   result           count, sum_keys and sum_inner_vals over the selected rows with a match; sum_outer_vals 0.
+ *   in place         d_match_bits may be the very pointer d_select_bits: afterwards the bitmap is select AND match (the last word's high
+ *                    bits 0), so a chain of dimensions narrows ONE bitmap.  Any other overlap of the two bitmaps is HJGPU_EINVAL.
+ * A build key 0 is HJGPU_EZEROKEY whatever the mask says; outer == 0: nothing is written and nothing is read of the mask.  The road
+ * is chosen by `inner` alone, as for hjgpu_lookup; hjgpu_get_stats tells the roads apart as there. */
+int  hjgpu_lookup_selected(hjgpu_ctx *ctx,
+                           const uint32_t *d_inner_keys, const uint32_t *d_inner_vals, size_t inner,
+                           const uint32_t *d_outer_keys, size_t outer,
+                           const hjgpu_npj_params *params,
+                           const uint32_t *d_select_bits,   /* (outer + 31) / 32 uint32, or NULL */
+                           uint32_t *d_vals_out, uint32_t *d_match_bits,
+                           hjgpu_result *result, void *stream);
+int  hjgpu_lookup_selected_async(hjgpu_ctx *ctx,
+                                 const uint32_t *d_inner_keys, const uint32_t *d_inner_vals, size_t inner,
+                                 const uint32_t *d_outer_keys, size_t outer,
+                                 const hjgpu_npj_params *params,
+                                 const uint32_t *d_select_bits,
+                                 uint32_t *d_vals_out, uint32_t *d_match_bits,
+                                 hjgpu_result *d_result, void *stream);
+int  hjgpu_npj_lookup_table_selected(hjgpu_ctx *ctx, const uint32_t *d_keys, size_t n,
+                                     const uint64_t *d_table, size_t buckets, uint32_t factor,
+                                     const uint32_t *d_select_bits,
+                                     uint32_t *d_vals_out, uint32_t *d_match_bits,
+                                     hjgpu_result *result, void *stream);
+
 /* ---- whole joins on HBM-resident columns (replace run()/run_hj()) ---------------- */
 /* run(), npj.cpp:769-927 */
 int  hjgpu_npj(hjgpu_ctx *ctx,
