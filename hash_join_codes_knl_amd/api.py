@@ -37,6 +37,7 @@ EXPORTS = [
     "hjgpu_npj_build", "hjgpu_npj_probe",
     "hjgpu_npj_lookup", "hjgpu_npj_lookup_async", "hjgpu_npj_lookup_table", "hjgpu_lookup", "hjgpu_lookup_async",
     "hjgpu_lookup_selected", "hjgpu_lookup_selected_async", "hjgpu_npj_lookup_table_selected",
+    "hjgpu_compact_selected", "hjgpu_compact_selected_async",
     "hjgpu_npj", "hjgpu_phj", "hjgpu_cpra",
     "hjgpu_npj_async", "hjgpu_phj_async", "hjgpu_cpra_async", "hjgpu_phj_overlapped_async",
     "hjgpu_phj_build", "hjgpu_phj_probe", "hjgpu_phj_probe_async",
@@ -264,6 +265,8 @@ def load_library(build_if_missing=True):
     L.hjgpu_npj_lookup_table.argtypes = [vp, vp, sz, vp, sz, u32, vp, vp, C.POINTER(Result), vp]
     L.hjgpu_lookup_selected.argtypes = [vp, vp, vp, sz, vp, sz, C.POINTER(NpjParams), vp, vp, vp, C.POINTER(Result), vp]
     L.hjgpu_lookup_selected_async.argtypes = [vp, vp, vp, sz, vp, sz, C.POINTER(NpjParams), vp, vp, vp, vp, vp]
+    L.hjgpu_compact_selected.argtypes = [vp, vp, sz, u32, C.POINTER(vp), C.POINTER(vp), vp, sz, u64p, vp]
+    L.hjgpu_compact_selected_async.argtypes = [vp, vp, sz, u32, C.POINTER(vp), C.POINTER(vp), vp, sz, vp, vp]
     L.hjgpu_npj_lookup_table_selected.argtypes = [vp, vp, sz, vp, sz, u32, vp, vp, vp, C.POINTER(Result), vp]
     join = [vp, vp, vp, sz, vp, vp, sz]
     L.hjgpu_npj.argtypes = join + [C.POINTER(NpjParams), C.POINTER(Result), C.POINTER(Output), vp]
@@ -409,7 +412,8 @@ class HjGpu:
 
     def counter(self, name):
         """hjgpu_get_counter: "probe_fallbacks" (claimed probe sides done again exactly), "probe_exact" (1: exact path from now on),
-        "lookup_lds_rows" (largest build side that hjgpu_lookup answers from LDS tables; 0 under option no_broadcast)."""
+        "lookup_lds_rows" (largest build side that hjgpu_lookup answers from LDS tables; 0 under option no_broadcast),
+        "compact_ranges" / "compact_chunk_rows" (compact_selected's geometry: its ranges, and the rows of a chunk)."""
         v = C.c_uint64()
         self._check(self.lib.hjgpu_get_counter(self.handle, name.encode(), C.byref(v)))
         return v.value
@@ -535,6 +539,42 @@ class HjGpu:
                                                              self._ptr(select_bits), self._ptr(vals_out), self._ptr(match_bits),
                                                              C.byref(r), stream))
         return r.as_tuple()
+
+    # ---- compaction by bitmap: the selected rows of the columns, dense and in input order ----------------------------------------
+    def _compact_args(self, cols_in, cols_out, rows_out, capacity):
+        cols_in, cols_out = list(cols_in or ()), list(cols_out or ())
+        if len(cols_in) != len(cols_out):
+            raise ValueError("compact_selected: %d input columns, %d output columns" % (len(cols_in), len(cols_out)))
+        if capacity is None:                # the shortest output
+            outs = cols_out + ([rows_out] if rows_out is not None else [])
+            if not all(isinstance(c, DeviceColumn) for c in outs):
+                raise ValueError("compact_selected: capacity is needed with outputs given as plain pointers")
+            capacity = min([c.n for c in outs], default=0)
+        if not cols_in:                     # no columns: NULL arrays
+            return 0, None, None, capacity
+        arr = C.c_void_p * len(cols_in)
+        return len(cols_in), arr(*[self._ptr(c) for c in cols_in]), arr(*[self._ptr(c) for c in cols_out]), capacity
+
+    def compact_selected(self, select_bits, n, cols_in, cols_out, rows_out=None, capacity=None, stream=None):
+        """hjgpu_compact_selected: cols_out[c][j] = cols_in[c][i_j], rows_out[j] = i_j for the rows i_0 < i_1 < ... whose bit is set in
+        select_bits (match_bits' layout) and j < capacity (default: the shortest output); returns their number J.  J > capacity raises
+        HjGpuError(HJGPU_EOVERFLOW) that carries .count = J; the first capacity rows of every output are valid then."""
+        ncols, ins, outs, capacity = self._compact_args(cols_in, cols_out, rows_out, capacity)
+        count = C.c_uint64()
+        st = self.lib.hjgpu_compact_selected(self.handle, self._ptr(select_bits), n, ncols, ins, outs, self._ptr(rows_out), capacity,
+                                             C.byref(count), stream)
+        if st != OK:
+            e = HjGpuError(st, "%s: %s" % (self.lib.hjgpu_status_string(st).decode(), self.lib.hjgpu_last_error(self.handle).decode()))
+            e.count = count.value
+            raise e
+        return count.value
+
+    def compact_selected_async(self, select_bits, n, cols_in, cols_out, rows_out, capacity, d_count, stream=None):
+        """hjgpu_compact_selected_async: enqueue only; the number of selected rows goes to d_count (uint64 in device memory), which the
+        caller compares with capacity (None: the shortest output)"""
+        ncols, ins, outs, capacity = self._compact_args(cols_in, cols_out, rows_out, capacity)
+        self._check(self.lib.hjgpu_compact_selected_async(self.handle, self._ptr(select_bits), n, ncols, ins, outs, self._ptr(rows_out),
+                                                          capacity, self._ptr(d_count), stream))
 
     # ---- whole joins ------------------------------------------------------------------
     def _join(self, fn, params, rk, rv, inner, sk, sv, outer, out, stream):

@@ -12,6 +12,7 @@
 // goal (the host-side oracle generator covers that, oracle/hj_oracle.c).
 #include "hj_device.hpp"
 #include "hj_internal.hpp"
+#include "hj_lookup_sel.hpp"
 #include <algorithm>
 #include <math.h>
 
@@ -386,5 +387,221 @@ int hj_launch_fill_probe(void *p, size_t bytes, hipStream_t stream)
 {
     if (((uintptr_t)p & 15) || bytes < 16) return HJGPU_EINVAL;
     hipLaunchKernelGGL(fill_probe_kernel, dim3(1024), dim3(1024), 0, stream, (uint4 *)p, (u64)(bytes / 16));
+    return hipGetLastError() == hipSuccess ? HJGPU_OK : HJGPU_EHIP;
+}
+
+// ---- compaction by bitmap (hjgpu_compact_selected; DESIGN.md section 5 "Compaction by bitmap") ----------------------------------------
+// Two launches, ordered by the stream; no workgroup ever waits for another.  Both have one workgroup per range of compact_layout.hpp.
+// Launch 1: workgroup g counts the set bits of its range's mask words, counts[g].  16-byte non-temporal loads while whole vectors lie inside
+// the range's whole words, single words behind them: nothing at or beyond word (n + 31) / 32 is read; the last word's bits at n and beyond do
+// not count.  An empty range stores 0.
+__global__ __launch_bounds__(256) void compact_count_kernel(const uint32_t *__restrict__ select_bits, hj_compact::Layout lay, u64 *counts)
+{
+    __shared__ u64 red[4];
+    const u64 rb = lay.begin(blockIdx.x), re = lay.end(blockIdx.x);
+    u64 c = 0;
+    if (re > rb) {
+        const u64 w0 = rb >> 5, w1 = (re + 31) >> 5;                    // rb is a multiple of 256 rows: word w0 is 16-byte aligned
+        const u64 vecs = ((re >> 5) - w0) >> 2;                        // whole vectors of whole words: a partial last word is never among them
+        const uint4 *v4 = reinterpret_cast<const uint4 *>(select_bits + w0);
+        u64 i = threadIdx.x;
+        uint32_t s = 0;
+        for (; i + 768 < vecs; i += 1024) {
+            const uint4 a = hj_load_nt(v4 + i), b = hj_load_nt(v4 + i + 256), d = hj_load_nt(v4 + i + 512), e = hj_load_nt(v4 + i + 768);
+            s += __popc(a.x) + __popc(a.y) + __popc(a.z) + __popc(a.w) + __popc(b.x) + __popc(b.y) + __popc(b.z) + __popc(b.w);
+            s += __popc(d.x) + __popc(d.y) + __popc(d.z) + __popc(d.w) + __popc(e.x) + __popc(e.y) + __popc(e.z) + __popc(e.w);
+            c += s; s = 0;
+        }
+        for (; i < vecs; i += 256) { const uint4 a = hj_load_nt(v4 + i); s += __popc(a.x) + __popc(a.y) + __popc(a.z) + __popc(a.w); }
+        // the words behind the last whole vector (at most 4), the range's last word cut at its last row
+        const u64 w = w0 + vecs * 4 + threadIdx.x;
+        if (w < w1) {
+            uint32_t x = hj_load_nt(select_bits + w);
+            if (w == w1 - 1 && (re & 31)) x &= (1u << (uint32_t)(re & 31)) - 1u;
+            s += __popc(x);
+        }
+        c += s;
+    }
+    c = wave_reduce_sum(c);
+    if (hj_lane() == 0) red[threadIdx.x >> 6] = c;
+    __syncthreads();
+    if (threadIdx.x == 0) hj_store(&counts[blockIdx.x], red[0] + red[1] + red[2] + red[3]);
+}
+
+// The count alone (ncols == 0 and no row numbers): *d_count = the sum of counts[0 .. ranges)
+__global__ __launch_bounds__(256) void compact_total_kernel(const u64 *__restrict__ counts, uint32_t ranges, u64 *d_count)
+{
+    __shared__ u64 red[4];
+    u64 s = 0;
+    for (uint32_t t = threadIdx.x; t < ranges; t += 256) s += counts[t];
+    s = wave_reduce_sum(s);
+    if (hj_lane() == 0) red[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) hj_store(d_count, red[0] + red[1] + red[2] + red[3]);
+}
+
+// orders this wave's LDS traffic for the compiler (the hardware performs a wave's LDS instructions in the order they were issued)
+__device__ __forceinline__ void compact_wave_sync()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+__device__ __forceinline__ uint32_t compact_elem(const uint4 &v, int j) { return j == 0 ? v.x : j == 1 ? v.y : j == 2 ? v.z : v.w; }
+
+// Launch 2: workgroup g adds up counts[0 .. g) - where its range's first survivor goes; workgroup 0 adds up all of them and stores *d_count -
+// and walks its range chunk by chunk.  Wave w owns the chunk's rows [w * VEC * 256, (w + 1) * VEC * 256) in VEC trips of hj_lookup_sel.hpp's
+// layout: lane L owns rows 4 L ... 4 L + 3 of a trip, a group of 8 lanes one mask word and one 128-byte line of every column.  The mask
+// words of all trips are loaded first, then the columns; a group whose word is 0 loads no column; a row at n or beyond is never selected
+// (sel_fetch's nibble), and the last, partial vector of a column is loaded by words: nothing at row n or beyond is read.  popcount per lane ->
+// prefix over the wave (DPP) -> the four waves' totals through LDS, one LDS-only barrier per chunk (the totals alternate between two slots:
+// a wave that is a chunk ahead writes the other one).  The output is in input order whatever the grid.
+// STAGED: a wave's survivors of one column go to the wave's own piece of LDS in output order and leave as 4-byte stores of 64 consecutive
+// lanes, 256 contiguous bytes per instruction; else every lane stores its own rows (up to four 4-byte stores, dense across the workgroup).
+// Rows whose output index is capacity or beyond are not stored.  NCOLS, ROWS and STAGED are template parameters: no store behind a run-time flag.
+template <int NCOLS, bool ROWS, bool STAGED>
+__global__ __launch_bounds__(256) void compact_kernel(CompactArgs a)
+{
+    constexpr int VEC = hj_compact::VEC;
+    constexpr int WAVE_ROWS = VEC * 256;
+    __shared__ u64 red[4];
+    __shared__ __attribute__((aligned(16))) uint32_t tot[2][4];
+    __shared__ uint32_t stage[STAGED ? 4 : 1][STAGED ? WAVE_ROWS : 1];
+    const uint32_t g = blockIdx.x, wave = threadIdx.x >> 6, lane = hj_lane();
+    u64 s = 0;
+    const uint32_t lim = g ? g : a.lay.ranges;
+    for (uint32_t t = threadIdx.x; t < lim; t += 256) s += a.counts[t];
+    s = wave_reduce_sum(s);
+    if (lane == 0) red[wave] = s;
+    __syncthreads();
+    s = red[0] + red[1] + red[2] + red[3];
+    if (g == 0 && a.d_count && threadIdx.x == 0) hj_store(a.d_count, s);
+    u64 run = g ? hj_uniform(s) : 0;                                   // output index of the chunk's first survivor
+    const u64 n = a.lay.n, rb = a.lay.begin(g), re = a.lay.end(g), nvec = (n + 3) >> 2;
+    uint32_t par = 0;
+    for (u64 row0 = rb; row0 < re; row0 += hj_compact::CHUNK_ROWS, par ^= 1u) {
+        const u64 v0 = (row0 >> 2) + (u64)wave * (VEC * 64) + lane;
+        uint32_t w[VEC], nib[VEC];
+        uint4 kk[NCOLS ? NCOLS : 1][VEC];
+#pragma unroll
+        for (int u = 0; u < VEC; ++u) {
+            const u64 v = v0 + (u64)u * 64;
+            w[u] = 0;
+            if (v < nvec) w[u] = hj_load_nt(a.select_bits + (v >> 3));   // (v < nvec: row 4 v < n, and word v / 8 starts at or before it)
+        }
+#pragma unroll
+        for (int u = 0; u < VEC; ++u) {
+            const u64 v = v0 + (u64)u * 64, r0 = v << 2;
+            const uint32_t rows = r0 + 4 <= n ? 15u : r0 < n ? (1u << (uint32_t)(n - r0)) - 1u : 0u;
+            nib[u] = (w[u] >> ((threadIdx.x & 7u) * 4)) & rows;
+#pragma unroll
+            for (int c = 0; c < NCOLS; ++c) {
+                kk[c][u] = make_uint4(0, 0, 0, 0);
+                if (w[u] != 0u) {                                        // (w != 0 only where v < nvec)
+                    if (rows == 15u) kk[c][u] = hj_load_nt(reinterpret_cast<const uint4 *>(a.in[c]) + v);
+                    else {                                               // the column's last, partial vector
+                        if (rows & 1u) kk[c][u].x = hj_load_nt(a.in[c] + r0);
+                        if (rows & 2u) kk[c][u].y = hj_load_nt(a.in[c] + r0 + 1);
+                        if (rows & 4u) kk[c][u].z = hj_load_nt(a.in[c] + r0 + 2);
+                    }
+                }
+            }
+        }
+        // where this lane's survivors go: [loc[u], loc[u] + popcount(nib[u])) of the wave's, the wave's from `before` of the chunk's
+        uint32_t loc[VEC], wtotal = 0;
+#pragma unroll
+        for (int u = 0; u < VEC; ++u) {
+            const uint32_t cnt = __popc(nib[u]), inc = wave_inclusive_scan(cnt);
+            loc[u] = wtotal + inc - cnt;
+            wtotal += (uint32_t)__builtin_amdgcn_readlane((int)inc, 63);
+        }
+        if (lane == 0) tot[par][wave] = wtotal;
+        hj_barrier_lds();
+        const uint4 t4 = *reinterpret_cast<const uint4 *>(tot[par]);
+        const uint32_t before = hj_uniform((wave > 0 ? t4.x : 0u) + (wave > 1 ? t4.y : 0u) + (wave > 2 ? t4.z : 0u));
+        const u64 wbase = run + before;
+        run += hj_uniform(t4.x + t4.y + t4.z + t4.w);
+        if constexpr (STAGED) {
+            constexpr int OUTS = NCOLS + (ROWS ? 1 : 0);
+#pragma unroll
+            for (int c = 0; c < OUTS; ++c) {
+#pragma unroll
+                for (int u = 0; u < VEC; ++u) {
+                    uint32_t at = loc[u];
+#pragma unroll
+                    for (int j = 0; j < 4; ++j)
+                        if ((nib[u] >> j) & 1u) {
+                            uint32_t x;
+                            if (c < NCOLS) x = compact_elem(kk[c < NCOLS ? c : 0][u], j);
+                            else x = (uint32_t)(((v0 + (u64)u * 64) << 2) + j);
+                            stage[wave][at++] = x;
+                        }
+                }
+                compact_wave_sync();
+                uint32_t *out = c < NCOLS ? a.out[c < NCOLS ? c : 0] : a.rows_out;
+                for (uint32_t e = lane; e < wtotal; e += 64) {
+                    const uint32_t x = stage[wave][e];
+                    if (wbase + e < a.capacity) hj_store(out + wbase + e, x);
+                }
+                compact_wave_sync();
+            }
+        } else {
+#pragma unroll
+            for (int u = 0; u < VEC; ++u) {
+                u64 o = wbase + loc[u];
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if ((nib[u] >> j) & 1u) {
+                        if (o < a.capacity) {
+#pragma unroll
+                            for (int c = 0; c < NCOLS; ++c) hj_store(a.out[c] + o, compact_elem(kk[c][u], j));
+                            if constexpr (ROWS) hj_store(a.rows_out + o, (uint32_t)(((v0 + (u64)u * 64) << 2) + j));
+                        }
+                        ++o;
+                    }
+            }
+        }
+    }
+}
+
+// how the survivors reach memory (see compact_kernel; DESIGN.md section 5 records both)
+#ifndef HJ_COMPACT_STAGED
+#define HJ_COMPACT_STAGED 1
+#endif
+
+template <int NCOLS, bool ROWS>
+static void compact_launch(const CompactArgs &a, hipStream_t stream)
+{
+    hipLaunchKernelGGL((compact_kernel<NCOLS, ROWS, HJ_COMPACT_STAGED != 0>), dim3(a.lay.ranges), dim3(hj_compact::BLOCK), 0, stream, a);
+}
+
+int hj_launch_compact_count(const uint32_t *select_bits, const hj_compact::Layout &lay, u64 *counts, hipStream_t stream)
+{
+    hipLaunchKernelGGL(compact_count_kernel, dim3(lay.ranges), dim3(hj_compact::BLOCK), 0, stream, select_bits, lay, counts);
+    return hipGetLastError() == hipSuccess ? HJGPU_OK : HJGPU_EHIP;
+}
+
+int hj_launch_compact_total(const u64 *counts, uint32_t ranges, u64 *d_count, hipStream_t stream)
+{
+    hipLaunchKernelGGL(compact_total_kernel, dim3(1), dim3(256), 0, stream, counts, ranges, d_count);
+    return hipGetLastError() == hipSuccess ? HJGPU_OK : HJGPU_EHIP;
+}
+
+// one launch: ncols <= HJ_COMPACT_LAUNCH_COLS columns (a.in / a.out [0 .. ncols)), the row numbers when a.rows_out is set; never neither
+int hj_launch_compact(const CompactArgs &a, uint32_t ncols, hipStream_t stream)
+{
+    const bool rows = a.rows_out != nullptr;
+    if (ncols > HJ_COMPACT_LAUNCH_COLS || (ncols == 0 && !rows)) return HJGPU_EINVAL;
+    hj_with_bool(rows, [&](auto r) {
+        constexpr bool R = decltype(r)::value;
+        switch (ncols) {
+        case 0: if constexpr (R) compact_launch<0, true>(a, stream); break;
+        case 1: compact_launch<1, R>(a, stream); break;
+        case 2: compact_launch<2, R>(a, stream); break;
+        case 3: compact_launch<3, R>(a, stream); break;
+        default: compact_launch<4, R>(a, stream); break;
+        }
+    });
     return hipGetLastError() == hipSuccess ? HJGPU_OK : HJGPU_EHIP;
 }

@@ -5,6 +5,7 @@
 #include <stdint.h>
 #include <type_traits>
 #include "../../include/hjgpu.h"
+#include "compact_layout.hpp"
 
 typedef unsigned long long u64;
 
@@ -495,6 +496,26 @@ struct LdsLookupSelArgs {
     const uint32_t *select_bits;
 };
 int hj_launch_lds_lookup_sel(const LdsLookupSelArgs &a, int cus, hipStream_t stream);
+
+// Compaction by bitmap (hjgpu_compact_selected*, gen_kernels.hip; DESIGN.md section 5 "Compaction by bitmap"): two launches over the ranges of
+// compact_layout.hpp.  hj_launch_compact_count: counts[g] = the selected rows of range g (select_bits 16-byte aligned, (n + 31) / 32 words).
+// hj_launch_compact: out[c][j] = in[c][i_j], rows_out[j] = i_j for the selected rows i_0 < i_1 < ... and j < capacity, from the counts of
+// the count launch; workgroup 0 stores their sum to d_count unless that is NULL (the second launch of a call with more than
+// HJ_COMPACT_LAUNCH_COLS columns).  hj_launch_compact_total: the sum alone.  All columns and rows_out 16-byte aligned.
+constexpr uint32_t HJ_COMPACT_LAUNCH_COLS = 4;
+struct CompactArgs {
+    const uint32_t *select_bits;
+    hj_compact::Layout lay;
+    const u64 *counts;                   // [lay.ranges]
+    u64 *d_count;
+    u64 capacity;
+    const uint32_t *in[HJ_COMPACT_LAUNCH_COLS];
+    uint32_t *out[HJ_COMPACT_LAUNCH_COLS];
+    uint32_t *rows_out;                  // NULL: no row numbers
+};
+int hj_launch_compact_count(const uint32_t *select_bits, const hj_compact::Layout &lay, u64 *counts, hipStream_t stream);
+int hj_launch_compact(const CompactArgs &a, uint32_t ncols, hipStream_t stream);
+int hj_launch_compact_total(const u64 *counts, uint32_t ranges, u64 *d_count, hipStream_t stream);
 
 // K9: compact the per-wave partially filled tail blocks (npj.cpp:475-514).
 // moves: scratch of 2*HJ_MAX_WORKERS entries of 24 bytes + HJ_MAX_WORKERS entries of 8 bytes.

@@ -472,6 +472,117 @@ int hjgpu_column_sums(hjgpu_ctx *ctx, const uint32_t *d_keys, size_t n, uint32_t
     return HJGPU_OK;
 }
 
+// ---- compaction by bitmap ---------------------------------------------------------
+// hjgpu_compact_selected / _async (DESIGN.md section 5 "Compaction by bitmap").  Every refusal is decided here, from the arguments alone, before
+// anything is allocated or enqueued.
+static bool ranges_overlap(const void *p, size_t pbytes, const void *q, size_t qbytes)
+{
+    const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
+    return pbytes && qbytes && a < b + qbytes && b < a + pbytes;
+}
+
+static int check_compact(hjgpu_ctx *ctx, const uint32_t *bits, size_t n, uint32_t ncols, const uint32_t *const *in, uint32_t *const *out,
+                         const uint32_t *rows_out, size_t capacity, const uint64_t *count, bool device_count)
+{
+    if (!count) return fail(ctx, HJGPU_EINVAL, "null count pointer");
+    if (device_count && ((uintptr_t)count & 7)) return fail(ctx, HJGPU_EALIGN, "d_count must be 8-byte aligned");
+    if (ncols > HJGPU_COMPACT_MAX_COLS) return fail(ctx, HJGPU_EINVAL, "ncols must not exceed HJGPU_COMPACT_MAX_COLS (8)");
+    if (n == 0) return HJGPU_OK;                         // nothing is read, nothing but the count is written: anything else may be NULL
+    if (!bits) return fail(ctx, HJGPU_EINVAL, "null d_select_bits (a compaction of every row is a copy)");
+    if ((uintptr_t)bits & 15) return fail(ctx, HJGPU_EALIGN, "d_select_bits must be 16-byte aligned");
+    if (ncols && (!in || !out)) return fail(ctx, HJGPU_EINVAL, "null column array");
+    for (uint32_t c = 0; c < ncols; ++c) {
+        if (!in[c] || !out[c]) return fail(ctx, HJGPU_EINVAL, "null column pointer");
+        if (((uintptr_t)in[c] & 15) || ((uintptr_t)out[c] & 15)) return fail(ctx, HJGPU_EALIGN, "input and output columns must be 16-byte aligned");
+    }
+    if ((uintptr_t)rows_out & 15) return fail(ctx, HJGPU_EALIGN, "d_rows_out must be 16-byte aligned");
+    if (rows_out && n > 0xFFFFFFFFull) return fail(ctx, HJGPU_EINVAL, "d_rows_out holds 32-bit row numbers: n must not exceed 0xFFFFFFFF");
+    // not in place: no output may share a byte with the mask, an input column or another output
+    const void *outs[HJGPU_COMPACT_MAX_COLS + 1];
+    uint32_t nouts = 0;
+    for (uint32_t c = 0; c < ncols; ++c) outs[nouts++] = out[c];
+    if (rows_out) outs[nouts++] = rows_out;
+    const size_t obytes = capacity * sizeof(uint32_t), mbytes = (n + 31) / 32 * sizeof(uint32_t);
+    for (uint32_t o = 0; o < nouts; ++o) {
+        if (ranges_overlap(outs[o], obytes, bits, mbytes)) return fail(ctx, HJGPU_EINVAL, "an output overlaps d_select_bits (the compaction is not in place)");
+        for (uint32_t c = 0; c < ncols; ++c)
+            if (ranges_overlap(outs[o], obytes, in[c], n * sizeof(uint32_t)))
+                return fail(ctx, HJGPU_EINVAL, "an output overlaps an input column (the compaction is not in place)");
+        for (uint32_t q = 0; q < o; ++q)
+            if (ranges_overlap(outs[o], obytes, outs[q], obytes)) return fail(ctx, HJGPU_EINVAL, "an output overlaps another output");
+    }
+    return HJGPU_OK;
+}
+
+// the two launches (three beyond HJ_COMPACT_LAUNCH_COLS columns) behind the checks; d_count in device memory
+static int compact_enqueue(hjgpu_ctx *ctx, const uint32_t *bits, size_t n, uint32_t ncols, const uint32_t *const *in, uint32_t *const *out,
+                           uint32_t *rows_out, size_t capacity, u64 *counts, u64 *d_count, hipStream_t stream)
+{
+    const hj_compact::Layout lay = hj_compact::layout(n, hj_compact::ranges_of(ctx->cus));
+    if (n == 0) { ncols = 0; rows_out = nullptr; }
+    // hjgpu_get_stats afterwards: ms_histogram = the counting launch, ms_join = the compaction, ms_total = both
+    for (int i = 0; i < EV_COUNT; ++i) ctx->ev_valid[i] = false;
+    ctx->last_algo = 3;
+    record(ctx, EV_BEGIN, stream);
+    CHK(hj_launch_compact_count(bits, lay, counts, stream));
+    record(ctx, EV_S_HIST, stream);
+    if (ncols == 0 && !rows_out) CHK(hj_launch_compact_total(counts, lay.ranges, d_count, stream));
+    for (uint32_t c0 = 0; c0 < ncols || (c0 == 0 && rows_out); c0 += HJ_COMPACT_LAUNCH_COLS) {
+        CompactArgs a{};
+        a.select_bits = bits; a.lay = lay; a.counts = counts; a.capacity = capacity;
+        a.d_count = c0 == 0 ? d_count : nullptr;
+        a.rows_out = c0 == 0 ? rows_out : nullptr;
+        const uint32_t k = std::min<uint32_t>(ncols - c0, HJ_COMPACT_LAUNCH_COLS);
+        for (uint32_t c = 0; c < k; ++c) { a.in[c] = in[c0 + c]; a.out[c] = out[c0 + c]; }
+        CHK(hj_launch_compact(a, k, stream));
+    }
+    record(ctx, EV_JOIN, stream);
+    record(ctx, EV_GAPS, stream);
+    return HJGPU_OK;
+}
+
+// the context's constant-size workspace of the compaction: the ranges' counts, and the blocking form's count behind them
+static int compact_workspace(hjgpu_ctx *ctx, u64 **counts)
+{
+    CHK(ensure(ctx, ctx->compact, ((size_t)hj_compact::MAX_RANGES + 1) * sizeof(u64)));
+    *counts = reinterpret_cast<u64 *>(ctx->compact.p);
+    return HJGPU_OK;
+}
+
+int hjgpu_compact_selected_async(hjgpu_ctx *ctx, const uint32_t *d_select_bits, size_t n, uint32_t ncols, const uint32_t *const *d_cols_in,
+                                 uint32_t *const *d_cols_out, uint32_t *d_rows_out, size_t capacity, uint64_t *d_count, void *stream_)
+{
+    if (!ctx) return HJGPU_EINVAL;
+    CHK(check_compact(ctx, d_select_bits, n, ncols, d_cols_in, d_cols_out, d_rows_out, capacity, d_count, true));
+    hipStream_t stream = (hipStream_t)stream_;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    CHK(refuse_capture(ctx, stream));
+    u64 *counts = nullptr;
+    CHK(compact_workspace(ctx, &counts));
+    return compact_enqueue(ctx, d_select_bits, n, ncols, d_cols_in, d_cols_out, d_rows_out, capacity, counts, reinterpret_cast<u64 *>(d_count), stream);
+}
+
+int hjgpu_compact_selected(hjgpu_ctx *ctx, const uint32_t *d_select_bits, size_t n, uint32_t ncols, const uint32_t *const *d_cols_in,
+                           uint32_t *const *d_cols_out, uint32_t *d_rows_out, size_t capacity, uint64_t *count, void *stream_)
+{
+    if (!ctx) return HJGPU_EINVAL;
+    CHK(check_compact(ctx, d_select_bits, n, ncols, d_cols_in, d_cols_out, d_rows_out, capacity, count, false));
+    hipStream_t stream = (hipStream_t)stream_;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    CHK(refuse_capture(ctx, stream));
+    u64 *counts = nullptr;
+    CHK(compact_workspace(ctx, &counts));
+    u64 *d_count = counts + hj_compact::MAX_RANGES;
+    CHK(compact_enqueue(ctx, d_select_bits, n, ncols, d_cols_in, d_cols_out, d_rows_out, capacity, counts, d_count, stream));
+    u64 got = 0;
+    HIPCHK(ctx, hipMemcpyAsync(&got, d_count, sizeof(got), hipMemcpyDeviceToHost, stream));
+    HIPCHK(ctx, hipStreamSynchronize(stream));
+    *count = got;
+    if (n && (ncols || d_rows_out) && got > capacity)
+        return fail(ctx, HJGPU_EOVERFLOW, "hjgpu_compact_selected: more selected rows than capacity (*count holds their number, the first capacity rows of every output are valid)");
+    return HJGPU_OK;
+}
+
 int hjgpu_stream_read_ms(hjgpu_ctx *ctx, const void *d_ptr, size_t bytes, float *ms, void *stream_)
 {
     if (!ctx || !d_ptr || !ms) return HJGPU_EINVAL;

@@ -263,7 +263,10 @@ int  hjgpu_get_stats(hjgpu_ctx *ctx, hjgpu_stats *stats);
 /* Counters of the context (HJGPU_EINVAL for an unknown name):
  *   "probe_fallbacks"  blocking PHJ joins whose claimed probe side (partitioned without its histogram pass, into optimistic regions)
  *                      overflowed and that were therefore done again on the exact path; their results are the exact path's
- *   "probe_exact"      1 when the context's blocking joins take the exact path (option "exact_probe_counts", or after a fallback) */
+ *   "probe_exact"      1 when the context's blocking joins take the exact path (option "exact_probe_counts", or after a fallback)
+ *   "lookup_lds_rows"  the largest build side that hjgpu_lookup answers from LDS tables (0 under option "no_broadcast")
+ *   "compact_ranges", "compact_chunk_rows"   hjgpu_compact_selected's geometry: the ranges (= workgroups) its rows are cut into, and the
+ *                      rows of a chunk, of which every range holds a whole number */
 int  hjgpu_get_counter(hjgpu_ctx *ctx, const char *name, uint64_t *value);
 
 /* ---- device memory helpers for hosts that do not link HIP (mamalloc/free,
@@ -430,6 +433,47 @@ int  hjgpu_npj_lookup_table_selected(hjgpu_ctx *ctx, const uint32_t *d_keys, siz
                                      const uint32_t *d_select_bits,
                                      uint32_t *d_vals_out, uint32_t *d_match_bits,
                                      hjgpu_result *result, void *stream);
+
+/* ---- compaction by bitmap: the selected rows of up to 8 columns, dense and in order ----------------------
+ * What turns a bitmap in d_match_bits' layout and full-length columns into dense rows - at the end of a chain of selected look-ups (the
+ * bitmap and the K value columns become the result rows) and in front of a join (a filter bitmap and the probe columns become the dense
+ * probe columns that hjgpu_phj / hjgpu_npj take; the row numbers can ride along as the payload).  Ordered (stable), so the output is
+ * bit-for-bit reproducible.  Let the selected rows be i_0 < i_1 < ... < i_(J-1):
+ *   d_cols_out[c][j] = d_cols_in[c][i_j] and d_rows_out[j] = (uint32_t) i_j for j < min(J, capacity); nothing is written at index
+ *   >= min(J, capacity) of any output; the mask and the input columns are never written.
+ *   d_select_bits    hjgpu_lookup_selected's mask, word for word: (n + 31) / 32 words, bit i & 31 of word i >> 5 selects row i, bits of the
+ *                    last word at positions >= n are ignored, no word at index >= (n + 31) / 32 is read.  16-byte aligned (HJGPU_EALIGN).
+ *                    NOT NULL when n > 0 (HJGPU_EINVAL; unlike the look-ups: a compaction of every row is a copy, which the caller has).
+ *   d_cols_in, d_cols_out   HOST arrays of ncols device pointers, copied by value into the kernel arguments.  ncols may be 0;
+ *                    ncols > HJGPU_COMPACT_MAX_COLS and a NULL entry among the first ncols of either array are HJGPU_EINVAL.  The same
+ *                    input column may be given twice.  No row at n or beyond is read of any input.
+ *   d_rows_out       the selected row numbers, or NULL.  With it, n > 0xFFFFFFFF is HJGPU_EINVAL; without it any n is legal.  ncols == 0
+ *                    with d_rows_out: the positions alone; without: the count alone (capacity is then ignored).
+ *   count            *count (blocking form, host memory) / *d_count (_async form, device memory, 8-byte aligned: HJGPU_EALIGN) = J, exact
+ *                    whatever capacity is.
+ *   overflow         J > capacity: the blocking form returns HJGPU_EOVERFLOW with *count = J, and the first `capacity` rows of every output
+ *                    are valid (the order makes that well defined).  The _async form cannot report it: its caller compares *d_count with
+ *                    capacity.  Neither form touches what hjgpu_get_async_status / hjgpu_accumulate_async_status report: those belong to
+ *                    the context's last join.
+ *   alignment        every input column, output column and d_rows_out 16-byte aligned (HJGPU_EALIGN).
+ *   not in place     an output's bytes [p, p + 4 * capacity) that overlap the mask, an input column's [p, p + 4 * n) or another output:
+ *                    HJGPU_EINVAL, "overlaps" in hjgpu_last_error.
+ *   n == 0           reads nothing, writes nothing but the count (0), accepts NULL everywhere else.
+ * Every refusal is decided from the arguments alone, before anything is enqueued or allocated; a capturing stream is HJGPU_EINVAL.  The
+ * _async form only enqueues and needs no hjgpu_reserve: the only workspace is a constant-size buffer of a few KiB per context, made the
+ * first time either form runs, so several compactions may be queued back to back on one stream of one context (one context per stream,
+ * as everywhere).  Two launches ordered by the stream - a count over the mask alone, then the compaction - and no workgroup waits for
+ * another.  hjgpu_get_stats afterwards: ms_total = both launches, ms_histogram = the counting launch, ms_join = the compaction, every
+ * other phase 0, fanout1 = fanout2 = buckets = groups = 0.  hjgpu_get_counter "compact_ranges" / "compact_chunk_rows": the geometry -
+ * the rows are cut into that many contiguous ranges of whole chunks of that many rows (one workgroup each, the tail in the last
+ * non-empty one). */
+#define HJGPU_COMPACT_MAX_COLS 8u
+int  hjgpu_compact_selected(hjgpu_ctx *ctx, const uint32_t *d_select_bits, size_t n,
+                            uint32_t ncols, const uint32_t *const *d_cols_in, uint32_t *const *d_cols_out,
+                            uint32_t *d_rows_out, size_t capacity, uint64_t *count, void *stream);
+int  hjgpu_compact_selected_async(hjgpu_ctx *ctx, const uint32_t *d_select_bits, size_t n,
+                                  uint32_t ncols, const uint32_t *const *d_cols_in, uint32_t *const *d_cols_out,
+                                  uint32_t *d_rows_out, size_t capacity, uint64_t *d_count, void *stream);
 
 /* ---- whole joins on HBM-resident columns (replace run()/run_hj()) ---------------- */
 /* run(), npj.cpp:769-927 */
