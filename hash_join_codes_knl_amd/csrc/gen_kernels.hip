@@ -12,7 +12,7 @@
 // goal (the host-side oracle generator covers that, oracle/hj_oracle.c).
 #include "hj_device.hpp"
 #include "hj_internal.hpp"
-#include "hj_lookup_sel.hpp"
+#include "hj_lookup.hpp"
 #include <algorithm>
 #include <math.h>
 
@@ -451,10 +451,10 @@ __device__ __forceinline__ void compact_wave_sync()
 __device__ __forceinline__ uint32_t compact_elem(const uint4 &v, int j) { return j == 0 ? v.x : j == 1 ? v.y : j == 2 ? v.z : v.w; }
 
 // Launch 2: workgroup g adds up counts[0 .. g) - where its range's first survivor goes; workgroup 0 adds up all of them and stores *d_count -
-// and walks its range chunk by chunk.  Wave w owns the chunk's rows [w * VEC * 256, (w + 1) * VEC * 256) in VEC trips of hj_lookup_sel.hpp's
+// and walks its range chunk by chunk.  Wave w owns the chunk's rows [w * VEC * 256, (w + 1) * VEC * 256) in VEC trips of hj_lookup.hpp's
 // layout: lane L owns rows 4 L ... 4 L + 3 of a trip, a group of 8 lanes one mask word and one 128-byte line of every column.  The mask
 // words of all trips are loaded first, then the columns; a group whose word is 0 loads no column; a row at n or beyond is never selected
-// (sel_fetch's nibble), and the last, partial vector of a column is loaded by words: nothing at row n or beyond is read.  popcount per lane ->
+// (lookup_fetch's nibble), and the last, partial vector of a column is loaded by words: nothing at row n or beyond is read.  popcount per lane ->
 // prefix over the wave (DPP) -> the four waves' totals through LDS, one LDS-only barrier per chunk (the totals alternate between two slots:
 // a wave that is a chunk ahead writes the other one).  The output is in input order whatever the grid.
 // STAGED: a wave's survivors of one column go to the wave's own piece of LDS in output order and leave as 4-byte stores of 64 consecutive

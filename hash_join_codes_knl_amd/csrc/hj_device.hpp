@@ -56,6 +56,14 @@ __device__ __forceinline__ void hj_barrier_lds()
     asm volatile("" ::: "memory");
 }
 
+// x of the lane that DPP control CTRL names (v_mov_b32_dpp, all rows and banks, 0 where the control names no lane): 0x00 ... 0xFF
+// quad_perm, 0x141 row_half_mirror
+template <int CTRL>
+__device__ __forceinline__ uint32_t hj_dpp(uint32_t x)
+{
+    return (uint32_t)__builtin_amdgcn_mov_dpp((int)x, CTRL, 0xF, 0xF, true);
+}
+
 // Inclusive scan across the 64 lanes of a wave.
 template <typename T>
 __device__ __forceinline__ T wave_inclusive_scan(T x)

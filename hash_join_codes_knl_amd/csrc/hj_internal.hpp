@@ -446,7 +446,6 @@ struct NpjLookupArgs {
     uint32_t *vals_out;
     uint32_t *match_bits;
 };
-int hj_launch_npj_lookup(const NpjLookupArgs &a, int cus, hipStream_t stream);
 // LDS look-up (hjgpu_lookup*, join_kernels.hip lds_lookup_kernel): NpjLookupArgs' outputs and aggregates for a build side that fits one LDS
 // table (inner <= 4096: the 8 K-slot table, two workgroups per CU; up to hj_join_config_big().cap(): the 16 K-slot table, one).  Every
 // workgroup of one persistent grid fills its own table from rk / rv, then streams `keys`.  A build key 0 raises *zero_key and is skipped.
@@ -463,39 +462,17 @@ struct LdsLookupArgs {
     uint32_t *vals_out;
     uint32_t *match_bits;
 };
-int hj_launch_lds_lookup(const LdsLookupArgs &a, int cus, hipStream_t stream);
 // Selected look-ups (hjgpu_lookup_selected*, hjgpu_npj_lookup_table_selected; DESIGN.md section 5 "Selected look-up"): the two look-ups
-// above for the rows whose bit is set in select_bits (match_bits' layout, (n + 31) / 32 words, 16-byte aligned, never NULL here: without a
-// mask the entry points take the plain launchers).  An unselected row gets HJGPU_NULL_VAL and bit 0, is counted in no aggregate and costs
-// no table access.  match_bits may be select_bits itself: a wave reads the words it will store, and before it stores them.  Structs of
-// their own - the old fields plus the mask - so that NpjLookupArgs and LdsLookupArgs, and with them every existing kernel, stay as they are.
-struct NpjLookupSelArgs {
-    const uint32_t *keys;
-    size_t n;
-    const u64 *table;
-    size_t buckets;
-    uint32_t factor;
-    uint32_t line_hash;
-    hjgpu_result *result;
-    uint32_t *vals_out;
-    uint32_t *match_bits;
-    const uint32_t *select_bits;
-};
-int hj_launch_npj_lookup_sel(const NpjLookupSelArgs &a, int cus, hipStream_t stream);
-struct LdsLookupSelArgs {
-    const uint32_t *rk, *rv;
-    const uint32_t *keys;
-    size_t n;
-    uint32_t inner;
-    uint32_t tf0, tf1;
-    uint32_t force_chained;
-    hjgpu_result *result;
-    uint32_t *zero_key;
-    uint32_t *vals_out;
-    uint32_t *match_bits;
-    const uint32_t *select_bits;
-};
-int hj_launch_lds_lookup_sel(const LdsLookupSelArgs &a, int cus, hipStream_t stream);
+// above for the rows whose bit is set in select_bits (match_bits' layout, (n + 31) / 32 words, 16-byte aligned).  An unselected row gets
+// HJGPU_NULL_VAL and bit 0, is counted in no aggregate and costs no table access.  match_bits may be select_bits itself: a wave reads the
+// words it will store, and before it stores them.  The launchers take these structs; select_bits == NULL launches the plain kernel on the
+// base slice (both bases end on a pointer: the mask follows at their size).
+struct NpjLookupSelArgs : NpjLookupArgs { const uint32_t *select_bits; };
+struct LdsLookupSelArgs : LdsLookupArgs { const uint32_t *select_bits; };
+static_assert(sizeof(NpjLookupArgs) == 64 && sizeof(NpjLookupSelArgs) == sizeof(NpjLookupArgs) + sizeof(void *), "kernel argument layout: the mask at offset 64");
+static_assert(sizeof(LdsLookupArgs) == 80 && sizeof(LdsLookupSelArgs) == sizeof(LdsLookupArgs) + sizeof(void *), "kernel argument layout: the mask at offset 80");
+int hj_launch_npj_lookup(const NpjLookupSelArgs &a, int cus, hipStream_t stream);
+int hj_launch_lds_lookup(const LdsLookupSelArgs &a, int cus, hipStream_t stream);
 
 // Compaction by bitmap (hjgpu_compact_selected*, gen_kernels.hip; DESIGN.md section 5 "Compaction by bitmap"): two launches over the ranges of
 // compact_layout.hpp.  hj_launch_compact_count: counts[g] = the selected rows of range g (select_bits 16-byte aligned, (n + 31) / 32 words).

@@ -1236,32 +1236,18 @@ static void lookup_done(hjgpu_ctx *ctx, hipStream_t stream, bool lds, size_t buc
     ctx->last_lookup = true;
 }
 
-// the fields NpjLookupArgs and NpjLookupSelArgs share
-template <class Args>
-static Args npj_lookup_args(const uint32_t *sk, size_t outer, const NpjTable &t, DevState *st, uint32_t *vals_out, uint32_t *match_bits)
-{
-    Args la;
-    memset(&la, 0, sizeof(la));
-    la.keys = sk; la.n = outer; la.table = t.slots; la.buckets = t.buckets; la.factor = t.factor; la.line_hash = t.line_hash ? 1u : 0u;
-    la.result = &st->result; la.vals_out = vals_out; la.match_bits = match_bits;
-    return la;
-}
-
 // The positional look-up behind a built table (hjgpu_npj_lookup*): one kernel.  No setup_output, no final_offsets, no close_gaps - the
 // two events that bracket close_gaps elsewhere are recorded back to back (ms_close_gaps 0).  ctx->state is zeroed by the caller.
-// select_bits != NULL: the selected look-up (hjgpu_*_selected), kernels of its own; NULL: the plain one
+// select_bits != NULL: the selected look-up (hjgpu_*_selected); NULL: the plain one
 int npj_lookup_enqueue(hjgpu_ctx *ctx, const uint32_t *sk, size_t outer, const NpjTable &t, uint32_t *vals_out, uint32_t *match_bits,
                        hipStream_t stream, const uint32_t *select_bits)
 {
     DevState *st = reinterpret_cast<DevState *>(ctx->state.p);
-    if (select_bits) {
-        NpjLookupSelArgs la = npj_lookup_args<NpjLookupSelArgs>(sk, outer, t, st, vals_out, match_bits);
-        la.select_bits = select_bits;
-        if (outer) CHK(hj_launch_npj_lookup_sel(la, ctx->cus, stream));
-    } else {
-        const NpjLookupArgs la = npj_lookup_args<NpjLookupArgs>(sk, outer, t, st, vals_out, match_bits);
-        if (outer) CHK(hj_launch_npj_lookup(la, ctx->cus, stream));
-    }
+    NpjLookupSelArgs la;
+    memset(&la, 0, sizeof(la));
+    la.keys = sk; la.n = outer; la.table = t.slots; la.buckets = t.buckets; la.factor = t.factor; la.line_hash = t.line_hash ? 1u : 0u;
+    la.result = &st->result; la.vals_out = vals_out; la.match_bits = match_bits; la.select_bits = select_bits;
+    if (outer) CHK(hj_launch_npj_lookup(la, ctx->cus, stream));
     lookup_done(ctx, stream, false, t.buckets);
     return HJGPU_OK;
 }
@@ -1874,21 +1860,12 @@ static int lookup_whole(hjgpu_ctx *ctx, const uint32_t *rk, const uint32_t *rv, 
     record(ctx, EV_BEGIN, stream);
     HIPCHK(ctx, hj_zero_async(st, sizeof(DevState), stream));
     for (int e : {EV_S_HIST, EV_S_PLAN, EV_S_SC1, EV_S_SC2, EV_WAITED, EV_R_HIST, EV_R_PLAN, EV_R_SC1, EV_R_SC2}) record(ctx, e, stream);
-    // the fields LdsLookupArgs and LdsLookupSelArgs share
-    auto args = [&](auto la) {
-        memset(&la, 0, sizeof(la));
-        la.rk = rk; la.rv = rv; la.inner = (uint32_t)inner; la.keys = sk; la.n = outer;
-        la.tf0 = DEFAULT_TF0; la.tf1 = DEFAULT_TF1; la.force_chained = ctx->tune.force_chained ? 1u : 0u;
-        la.result = &st->result; la.zero_key = &st->zero_key; la.vals_out = vals_out; la.match_bits = match_bits;
-        return la;
-    };
-    if (select_bits) {
-        LdsLookupSelArgs la = args(LdsLookupSelArgs{});
-        la.select_bits = select_bits;
-        CHK(hj_launch_lds_lookup_sel(la, ctx->cus, stream));
-    } else {
-        CHK(hj_launch_lds_lookup(args(LdsLookupArgs{}), ctx->cus, stream));
-    }
+    LdsLookupSelArgs la;
+    memset(&la, 0, sizeof(la));
+    la.rk = rk; la.rv = rv; la.inner = (uint32_t)inner; la.keys = sk; la.n = outer;
+    la.tf0 = DEFAULT_TF0; la.tf1 = DEFAULT_TF1; la.force_chained = ctx->tune.force_chained ? 1u : 0u;
+    la.result = &st->result; la.zero_key = &st->zero_key; la.vals_out = vals_out; la.match_bits = match_bits; la.select_bits = select_bits;
+    CHK(hj_launch_lds_lookup(la, ctx->cus, stream));
     lookup_done(ctx, stream, true, 0);
     return HJGPU_OK;
 }

@@ -34,7 +34,7 @@
 #include "hj_device.hpp"
 #include "hj_internal.hpp"
 #include "hj_emit.hpp"
-#include "hj_lookup_sel.hpp"
+#include "hj_lookup.hpp"
 
 // PACKED: the relations arrive as payload << 32 | key tuples (the library's own
 // partition passes); !PACKED: separate key / payload columns (hjgpu_join_partitions).
@@ -1202,224 +1202,13 @@ int hj_launch_join(const JoinArgs &a, const HjTuning &t, int cus, hipStream_t st
 // The probe's LDS reads: one ds_read_b64 per slot, key and payload together (bank = (address / 4) % 64 over each half of the wave; the
 // slots are hashed, so the conflicts are those of 32 independent addresses over 32 slot-wide bank pairs, whatever the layout - a split
 // key / payload layout halves the bytes per slot but pays a second, dependent read per hit and loses the 64-bit exchange of the fill).
-// The end of a trip is npj_lookup_leave's, kept here as a copy (lds_lookup_leave): sharing it through a header would put the function in
-// front of npj_kernels.hip's kernels, whose machine code is to stay as it is.
-// --------------------------------------------------------------------------
-template <int CTRL>
-__device__ __forceinline__ uint32_t lds_dpp(uint32_t x)
-{
-    return (uint32_t)__builtin_amdgcn_mov_dpp((int)x, CTRL, 0xF, 0xF, true);
-}
-
-// all 64 lanes (the bitmap's words are combined across lanes): v = this lane's vector, res / nib = the answers and match bits of its four
-// rows (nib is 0 for every row at n and beyond, so the last word's high bits leave as 0)
-template <bool VALS, bool BITS>
-__device__ __forceinline__ void lds_lookup_leave(const LdsLookupArgs &a, u64 v, const uint32_t (&kc)[4], const uint32_t (&res)[4], uint32_t nib,
-                                                 u64 &acc_n, u64 &acc_k, u64 &acc_i)
-{
-    const u64 n = a.n, g = v << 2;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const bool hit = (nib >> j) & 1u;
-        acc_n += hit ? 1u : 0u; acc_k += hit ? kc[j] : 0u; acc_i += hit ? res[j] : 0u;
-    }
-    if constexpr (VALS) {
-        if (g + 4 <= n) hj_store(reinterpret_cast<uint4 *>(a.vals_out) + v, make_uint4(res[0], res[1], res[2], res[3]));
-        else {                                                  // the last, partial vector: nothing at n and beyond is written
-#pragma unroll
-            for (int j = 0; j < 3; ++j) if (g + j < n) hj_store(a.vals_out + g + j, res[j]);
-        }
-    }
-    if constexpr (BITS) {
-        // 8 lanes x 4 rows = one word: OR over each group of 8 lanes, its first lane stores
-        uint32_t w = nib << ((threadIdx.x & 7u) * 4);
-        w |= lds_dpp<0xB1>(w);                                  // quad_perm: lanes 0<->1, 2<->3
-        w |= lds_dpp<0x4E>(w);                                  // quad_perm: lanes 0<->2, 1<->3
-        w |= lds_dpp<0x141>(w);                                 // row_half_mirror: lane i <-> 7 - i of the group, the other quad
-        // (v is a multiple of 8 in the storing lane: word v / 8 starts at row 4 v; a word whose first row is at n or beyond is not stored)
-        if ((threadIdx.x & 7u) == 0 && g < n) hj_store(a.match_bits + (v >> 3), w);
-    }
-}
-
-template <int BLOCK, int LOG2SLOTS, bool VALS, bool BITS>
-__global__ __launch_bounds__(BLOCK, hj_join_waves_per_simd(BLOCK, LOG2SLOTS)) void lds_lookup_kernel(LdsLookupArgs a)
-{
-    constexpr uint32_t SLOTS = 1u << LOG2SLOTS;
-    constexpr uint32_t MASK = SLOTS - 1;
-    constexpr int SHIFT = 32 - LOG2SLOTS;
-    constexpr int NW = BLOCK / 64;
-    constexpr int RB = 8;                        // build rows a lane loads before inserting
-    constexpr int BATCH = 2;                     // probe vectors (wave trips) in flight per lane
-    constexpr int CUCKOO_MAX_EVICTIONS = 64;
-    __shared__ u64 tab64[SLOTS];                 // low word = key (0: empty), high word = build payload
-    __shared__ u64 red[4][NW];
-    __shared__ uint32_t cuckoo_failed;
-    uint2 *tab = reinterpret_cast<uint2 *>(tab64);   // chained view: .x = key, .y = payload
-    const uint32_t tid = threadIdx.x;
-    const uint32_t tf0 = a.tf0, tf1 = a.tf1, inner = a.inner;
-
-    // every row of the build side, a lane's RB loads issued before its first insert
-    auto for_each_build_row = [&](auto insert) {
-        for (uint32_t base = 0; base < inner; base += (uint32_t)BLOCK * RB) {
-            uint32_t k[RB], v[RB];
-#pragma unroll
-            for (int j = 0; j < RB; ++j) {
-                const uint32_t i = base + (uint32_t)j * BLOCK + tid;
-                k[j] = 0; v[j] = 0;
-                if (i < inner) { k[j] = a.rk[i]; v[j] = a.rv[i]; }
-            }
-#pragma unroll
-            for (int j = 0; j < RB; ++j) {
-                const uint32_t i = base + (uint32_t)j * BLOCK + tid;
-                if (i < inner) insert(k[j], v[j]);
-            }
-        }
-    };
-
-    // ---- the one fill: clear + cuckoo build ----------------------------------
-    for (uint32_t i = tid; i < SLOTS; i += BLOCK) tab64[i] = 0;
-    if (tid == 0) cuckoo_failed = a.force_chained;
-    __syncthreads();
-    for_each_build_row([&](uint32_t k, uint32_t v) {
-        if (k == 0) { atomicOr(a.zero_key, 1u); return; }                // 0 is "empty": refused (HJGPU_EZEROKEY), the row is skipped
-        u64 cur = (u64)k | ((u64)v << 32);
-        uint32_t loc = (k * tf0) >> SHIFT;
-        int it = 0;
-        for (; it < CUCKOO_MAX_EVICTIONS; ++it) {
-            const u64 old = atomicExch(&tab64[loc], cur);                // ds_wrxchg_rtn_b64
-            if ((uint32_t)old == 0u) break;                              // slot was free
-            // `old` was evicted: it moves to the other one of its two slots
-            const uint2 a12 = hj_cuckoo_slots<LOG2SLOTS>((uint32_t)old, tf0, tf1);
-            loc = (loc == a12.x) ? a12.y : a12.x;
-            cur = old;
-        }
-        if (it == CUCKOO_MAX_EVICTIONS) cuckoo_failed = 1;               // a tuple is left in hand
-    });
-    __syncthreads();
-    const bool chained = hj_uniform(cuckoo_failed) != 0;
-    if (chained) {
-        // ---- fallback: the table again as double-hashing chains, one copy per key ----
-        for (uint32_t i = tid; i < SLOTS; i += BLOCK) tab64[i] = 0;
-        __syncthreads();
-        for_each_build_row([&](uint32_t k, uint32_t v) {
-            if (k == 0) return;
-            uint32_t slot = (k * tf0) >> SHIFT;
-            const uint32_t step = ((k * tf1) >> SHIFT) | 1u;
-            for (;;) {
-                const uint32_t old = atomicCAS(&tab[slot].x, 0u, k);     // ds_cmpst_rtn_b32
-                if (old == 0u) { tab[slot].y = v; break; }
-                if (old == k) break;                                     // a copy of this key is in the table already
-                slot = (slot + step) & MASK;
-            }
-        });
-        __syncthreads();
-    }
-
-    // ---- probe: whole waves iterate together (the bitmap's words need all lanes) ----
-    const uint4 *__restrict__ k4 = reinterpret_cast<const uint4 *>(a.keys);
-    const u64 n = a.n, nvec = (n + 3) >> 2, stride = (u64)gridDim.x * BLOCK;
-    u64 acc_n = 0, acc_k = 0, acc_i = 0;
-    for (u64 v0 = (u64)blockIdx.x * BLOCK + (tid & ~63u); v0 < nvec; v0 += stride * BATCH) {
-        uint4 kk[BATCH];
-#pragma unroll
-        for (int u = 0; u < BATCH; ++u) {
-            const u64 v = v0 + (u64)u * stride + hj_lane();
-            kk[u] = make_uint4(0, 0, 0, 0);
-            if (v < nvec) kk[u] = hj_load_nt(k4 + v);                    // the probe column is read exactly once
-        }
-#pragma unroll
-        for (int u = 0; u < BATCH; ++u) {
-            if (v0 + (u64)u * stride >= nvec) break;                     // the wave's trip lies beyond the column (the same for all its lanes)
-            const u64 v = v0 + (u64)u * stride + hj_lane(), g = v << 2;
-            const uint32_t key[4] = {kk[u].x, kk[u].y, kk[u].z, kk[u].w};
-            uint32_t res[4] = {HJGPU_NULL_VAL, HJGPU_NULL_VAL, HJGPU_NULL_VAL, HJGPU_NULL_VAL};
-            uint32_t nib = 0;
-            bool valid[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) valid[j] = key[j] != 0u && g + j < n;
-            if (!chained) {
-                // cuckoo table: a key lives in one of two slots - two independent reads per key, no loop
-                u64 t1[4], t2[4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const uint2 at = hj_cuckoo_slots<LOG2SLOTS>(key[j], tf0, tf1);
-                    t1[j] = tab64[at.x];
-                    t2[j] = tab64[at.y];
-                }
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const bool h1 = valid[j] && (uint32_t)t1[j] == key[j], h2 = valid[j] && (uint32_t)t2[j] == key[j];
-                    if (h1 || h2) { res[j] = (uint32_t)((h1 ? t1[j] : t2[j]) >> 32); nib |= 1u << j; }
-                }
-            } else {
-                // chains: 4 walks per lane in lock step, each to the key's copy or to the first empty slot
-                uint32_t slot[4], step[4];
-                uint2 t[4];
-                bool live[4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    live[j] = valid[j];
-                    slot[j] = (key[j] * tf0) >> SHIFT;
-                    step[j] = ((key[j] * tf1) >> SHIFT) | 1u;
-                    t[j] = make_uint2(0u, 0u);
-                    if (live[j]) t[j] = tab[slot[j]];
-                }
-                for (;;) {
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        const bool hit = live[j] && t[j].x == key[j];
-                        if (hit) { res[j] = t[j].y; nib |= 1u << j; }
-                        live[j] = live[j] && t[j].x != 0u && !hit;
-                        slot[j] = (slot[j] + step[j]) & MASK;
-                    }
-                    if (!(live[0] | live[1] | live[2] | live[3])) break;
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) if (live[j]) t[j] = tab[slot[j]];
-                }
-            }
-            lds_lookup_leave<VALS, BITS>(a, v, key, res, nib, acc_n, acc_k, acc_i);
-        }
-    }
-    hj_add_to_result(red, a.result, acc_n, acc_k, 0ull, acc_i);
-}
-
-// <512, 13> for build sides of up to 4096 rows (two workgroups per CU), <1024, 14> above (one): the broadcast join's pair, whatever
-// option "join_cfg" says.  One persistent grid, no larger than the probe column has wave trips for; always at least one workgroup - the
-// fill is what finds a build key 0, also when there is nothing to probe.
-template <int B, int L>
-static int launch_lds_lookup_at(const LdsLookupArgs &a, int cus, hipStream_t stream)
-{
-    const u64 nvec = ((u64)a.n + 3) >> 2, need = (nvec + B - 1) / B, full = (u64)cus * hj_join_wgs_per_cu(B, L);
-    const u64 grid = need < 1 ? 1 : need < full ? need : full;
-    void (*kernel)(LdsLookupArgs) = nullptr;
-    hj_with_bool(a.vals_out != nullptr, [&](auto vals) {
-        hj_with_bool(a.match_bits != nullptr, [&](auto bits) { kernel = lds_lookup_kernel<B, L, decltype(vals)::value, decltype(bits)::value>; });
-    });
-    hipLaunchKernelGGL(kernel, dim3((uint32_t)grid), dim3(B), 0, stream, a);
-    return hipGetLastError() == hipSuccess ? HJGPU_OK : HJGPU_EHIP;
-}
-
-int hj_launch_lds_lookup(const LdsLookupArgs &a, int cus, hipStream_t stream)
-{
-    if (a.inner == 0 && a.n == 0) return HJGPU_OK;
-    if (!a.result || !a.zero_key || (a.n && !a.keys) || (a.inner && (!a.rk || !a.rv)) || cus < 1) return HJGPU_EINVAL;
-    if (a.inner > (uint32_t)hj_join_config_big().cap() || !(a.tf0 & 1u) || !(a.tf1 & 1u)) return HJGPU_EINVAL;
-    if (((uintptr_t)a.keys | (uintptr_t)a.vals_out | (uintptr_t)a.match_bits) & 15) return HJGPU_EINVAL;
-    if (a.inner <= 4096) return launch_lds_lookup_at<512, 13>(a, cus, stream);
-    return launch_lds_lookup_at<1024, 14>(a, cus, stream);
-}
-
-// --------------------------------------------------------------------------
-// Selected LDS look-up (hjgpu_lookup_selected*, DESIGN.md section 5 "Selected look-up"): lds_lookup_kernel for the rows whose bit is set
-// in a.select_bits.  The same two geometries and the same fill, which never looks at the mask - it is what finds a build key 0.  An
+// Selected LDS look-up (hjgpu_lookup_selected*, DESIGN.md section 5 "Selected look-up"), SEL: the same body for the rows whose bit is set
+// in select_bits.  The same two geometries and the same fill, which never looks at the mask - it is what finds a build key 0.  An
 // unselected row is never valid: no read of the table, HJGPU_NULL_VAL, bit 0, counted nowhere.  The head and the end of a trip are
-// hj_lookup_sel.hpp's, where the in-place rule (match_bits == select_bits) is kept.
+// hj_lookup.hpp's, where the in-place rule (match_bits == select_bits) is kept.
 // --------------------------------------------------------------------------
-// The one fill of a workgroup's table - clear, cuckoo build, and the table again as double-hashing chains when that does not converge or
-// under force_chained - as a function: lds_lookup_kernel's fill, statement for statement.  (lds_lookup_kernel keeps its own inline copy:
-// calling this function there changed the register allocation of all its eight instances, and their machine code is the yardstick of
-// the selected look-up's measurement.)  All threads of the workgroup; returns whether the table is chained.  A build key 0 raises
-// *zero_key and is skipped.
+// The one fill of a workgroup's table: clear, cuckoo build, and the table again as double-hashing chains when that does not converge or
+// under force_chained.  All threads of the workgroup; returns whether the table is chained.  A build key 0 raises *zero_key and is skipped.
 struct LdsFill { const uint32_t *rk, *rv; uint32_t inner, tf0, tf1, force_chained; uint32_t *zero_key; };
 template <int BLOCK, int LOG2SLOTS>
 __device__ __forceinline__ bool lds_lookup_fill(const LdsFill &a, u64 *tab64, uint32_t &cuckoo_failed)
@@ -1493,8 +1282,8 @@ __device__ __forceinline__ bool lds_lookup_fill(const LdsFill &a, u64 *tab64, ui
     return chained;
 }
 
-template <int BLOCK, int LOG2SLOTS, bool VALS, bool BITS>
-__global__ __launch_bounds__(BLOCK, hj_join_waves_per_simd(BLOCK, LOG2SLOTS)) void lds_lookup_sel_kernel(LdsLookupSelArgs a)
+template <bool SEL, int BLOCK, int LOG2SLOTS, bool VALS, bool BITS>
+__device__ __forceinline__ void lds_lookup_body(const LdsLookupArgs &a, const uint32_t *select_bits)
 {
     constexpr uint32_t SLOTS = 1u << LOG2SLOTS;
     constexpr uint32_t MASK = SLOTS - 1;
@@ -1509,14 +1298,14 @@ __global__ __launch_bounds__(BLOCK, hj_join_waves_per_simd(BLOCK, LOG2SLOTS)) vo
     const uint32_t tf0 = a.tf0, tf1 = a.tf1;
     const bool chained = lds_lookup_fill<BLOCK, LOG2SLOTS>({a.rk, a.rv, a.inner, tf0, tf1, a.force_chained, a.zero_key}, tab64, cuckoo_failed);
 
-    // ---- probe: whole waves iterate together (the bitmaps' words need all lanes) ----
+    // ---- probe: whole waves iterate together (the bitmaps' words need all lanes); the probe column is read exactly once ----
     const uint4 *__restrict__ k4 = reinterpret_cast<const uint4 *>(a.keys);
     const u64 n = a.n, nvec = (n + 3) >> 2, stride = (u64)gridDim.x * BLOCK;
     u64 acc_n = 0, acc_k = 0, acc_i = 0;
     for (u64 v0 = (u64)blockIdx.x * BLOCK + (tid & ~63u); v0 < nvec; v0 += stride * BATCH) {
-        uint32_t sel[BATCH];
+        uint32_t look[BATCH];
         uint4 kk[BATCH];
-        sel_fetch<BATCH>(a.select_bits, k4, v0, stride, n, sel, kk);
+        lookup_fetch<SEL, BATCH>(select_bits, k4, v0, stride, n, look, kk);
 #pragma unroll
         for (int u = 0; u < BATCH; ++u) {
             if (v0 + (u64)u * stride >= nvec) break;                     // the wave's trip lies beyond the column (the same for all its lanes)
@@ -1526,14 +1315,17 @@ __global__ __launch_bounds__(BLOCK, hj_join_waves_per_simd(BLOCK, LOG2SLOTS)) vo
             uint32_t nib = 0;
             bool valid[4];
 #pragma unroll
-            for (int j = 0; j < 4; ++j) valid[j] = key[j] != 0u && ((sel[u] >> j) & 1u);
+            for (int j = 0; j < 4; ++j) valid[j] = key[j] != 0u && ((look[u] >> j) & 1u);
             if (!chained) {
-                // cuckoo table: a key lives in one of two slots - two independent reads per selected key, no loop
+                // cuckoo table: a key lives in one of two slots - two independent reads per key, no loop.  The plain kernel issues them
+                // for every key, the selected one for the valid keys only
                 u64 t1[4], t2[4];
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     t1[j] = 0; t2[j] = 0;
-                    if (valid[j]) {
+                    bool read = true;
+                    if constexpr (SEL) read = valid[j];
+                    if (read) {
                         const uint2 at = hj_cuckoo_slots<LOG2SLOTS>(key[j], tf0, tf1);
                         t1[j] = tab64[at.x];
                         t2[j] = tab64[at.y];
@@ -1570,33 +1362,52 @@ __global__ __launch_bounds__(BLOCK, hj_join_waves_per_simd(BLOCK, LOG2SLOTS)) vo
                     for (int j = 0; j < 4; ++j) if (live[j]) t[j] = tab[slot[j]];
                 }
             }
-            sel_leave<VALS, BITS>(a.vals_out, a.match_bits, n, v, key, res, nib, acc_n, acc_k, acc_i);
+            lookup_leave<VALS, BITS>(a.vals_out, a.match_bits, n, v, key, res, nib, acc_n, acc_k, acc_i);
         }
     }
     hj_add_to_result(red, a.result, acc_n, acc_k, 0ull, acc_i);
 }
 
-// launch_lds_lookup_at's geometries and grid rule
+template <int BLOCK, int LOG2SLOTS, bool VALS, bool BITS>
+__global__ __launch_bounds__(BLOCK, hj_join_waves_per_simd(BLOCK, LOG2SLOTS)) void lds_lookup_kernel(LdsLookupArgs a)
+{
+    lds_lookup_body<false, BLOCK, LOG2SLOTS, VALS, BITS>(a, nullptr);
+}
+
+template <int BLOCK, int LOG2SLOTS, bool VALS, bool BITS>
+__global__ __launch_bounds__(BLOCK, hj_join_waves_per_simd(BLOCK, LOG2SLOTS)) void lds_lookup_sel_kernel(LdsLookupSelArgs a)
+{
+    lds_lookup_body<true, BLOCK, LOG2SLOTS, VALS, BITS>(a, a.select_bits);
+}
+
+// <512, 13> for build sides of up to 4096 rows (two workgroups per CU), <1024, 14> above (one): the broadcast join's pair, whatever
+// option "join_cfg" says.  One persistent grid, no larger than the probe column has wave trips for; always at least one workgroup - the
+// fill is what finds a build key 0, also when there is nothing to probe.  a.select_bits == NULL: the plain kernel on the base slice.
 template <int B, int L>
-static int launch_lds_lookup_sel_at(const LdsLookupSelArgs &a, int cus, hipStream_t stream)
+static int launch_lds_lookup_at(const LdsLookupSelArgs &a, int cus, hipStream_t stream)
 {
     const u64 nvec = ((u64)a.n + 3) >> 2, need = (nvec + B - 1) / B, full = (u64)cus * hj_join_wgs_per_cu(B, L);
     const u64 grid = need < 1 ? 1 : need < full ? need : full;
-    void (*kernel)(LdsLookupSelArgs) = nullptr;
+    void (*plain)(LdsLookupArgs) = nullptr;
+    void (*selected)(LdsLookupSelArgs) = nullptr;
     hj_with_bool(a.vals_out != nullptr, [&](auto vals) {
-        hj_with_bool(a.match_bits != nullptr, [&](auto bits) { kernel = lds_lookup_sel_kernel<B, L, decltype(vals)::value, decltype(bits)::value>; });
+        hj_with_bool(a.match_bits != nullptr, [&](auto bits) {
+            constexpr bool V = decltype(vals)::value, M = decltype(bits)::value;
+            plain = lds_lookup_kernel<B, L, V, M>;
+            selected = lds_lookup_sel_kernel<B, L, V, M>;
+        });
     });
-    hipLaunchKernelGGL(kernel, dim3((uint32_t)grid), dim3(B), 0, stream, a);
+    if (a.select_bits) hipLaunchKernelGGL(selected, dim3((uint32_t)grid), dim3(B), 0, stream, a);
+    else hipLaunchKernelGGL(plain, dim3((uint32_t)grid), dim3(B), 0, stream, static_cast<const LdsLookupArgs &>(a));
     return hipGetLastError() == hipSuccess ? HJGPU_OK : HJGPU_EHIP;
 }
 
-// hj_launch_lds_lookup's checks plus the mask's
-int hj_launch_lds_lookup_sel(const LdsLookupSelArgs &a, int cus, hipStream_t stream)
+int hj_launch_lds_lookup(const LdsLookupSelArgs &a, int cus, hipStream_t stream)
 {
     if (a.inner == 0 && a.n == 0) return HJGPU_OK;
-    if (!a.result || !a.zero_key || (a.n && (!a.keys || !a.select_bits)) || (a.inner && (!a.rk || !a.rv)) || cus < 1) return HJGPU_EINVAL;
+    if (!a.result || !a.zero_key || (a.n && !a.keys) || (a.inner && (!a.rk || !a.rv)) || cus < 1) return HJGPU_EINVAL;
     if (a.inner > (uint32_t)hj_join_config_big().cap() || !(a.tf0 & 1u) || !(a.tf1 & 1u)) return HJGPU_EINVAL;
     if (((uintptr_t)a.keys | (uintptr_t)a.vals_out | (uintptr_t)a.match_bits | (uintptr_t)a.select_bits) & 15) return HJGPU_EINVAL;
-    if (a.inner <= 4096) return launch_lds_lookup_sel_at<512, 13>(a, cus, stream);
-    return launch_lds_lookup_sel_at<1024, 14>(a, cus, stream);
+    if (a.inner <= 4096) return launch_lds_lookup_at<512, 13>(a, cus, stream);
+    return launch_lds_lookup_at<1024, 14>(a, cus, stream);
 }

@@ -17,7 +17,7 @@
 #include "hj_device.hpp"
 #include "hj_internal.hpp"
 #include "hj_emit.hpp"
-#include "hj_lookup_sel.hpp"
+#include "hj_lookup.hpp"
 
 __device__ __forceinline__ u64 npj_bucket(uint32_t key, uint32_t factor, u64 buckets)
 {
@@ -350,9 +350,12 @@ __global__ __launch_bounds__(NPJ_PROBE_BLOCK) void npj_outer_kernel(NpjProbeArgs
 // request even when it hits the same line (fit: 12.9 ms per G memory-side requests + 4.5 ms
 // per G L2 requests).
 template <int CTRL>
-__device__ __forceinline__ uint32_t quad_perm(uint32_t x)
+__device__ __forceinline__ uint32_t quad_perm(uint32_t x) { return hj_dpp<CTRL>(x); }
+
+template <int OWNER>
+__device__ __forceinline__ uint32_t quad_bcast(uint32_t x)           // the value of lane OWNER of the quad
 {
-    return (uint32_t)__builtin_amdgcn_mov_dpp((int)x, CTRL, 0xF, 0xF, true);
+    return quad_perm<OWNER * 0x55>(x);
 }
 
 // The quad's line walk of every join mode but the inner join (npj_probe_line_kernel below, for the same reason as npj_probe_kernel).
@@ -814,252 +817,26 @@ int hj_launch_npj_probe(const NpjProbeArgs &a, int cus, hipStream_t stream, int 
 // hj_add_to_result.  The key column is 16-byte aligned (the entry points refuse anything else): vector v holds rows 4 v ... 4 v + 3.
 // VALS / BITS are template parameters for npj_probe_line_body's reason for MATERIALIZE, and so that no store sits behind a run-time flag
 // (tests/test_store_policy_isa.py); <false, false> is the aggregate-only instance.
-// --------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t half_row_mirror(uint32_t x)
-{
-    return (uint32_t)__builtin_amdgcn_mov_dpp((int)x, 0x141, 0xF, 0xF, true);          // row_half_mirror: inside every 8 lanes
-}
-
-// The end of a wave trip, all 64 lanes (the bitmap's words are combined across lanes): v = this lane's vector, res / nib = the answers and
-// match bits of its four rows (nib is 0 for every row at n and beyond, so the last word's high bits leave as 0).
-template <bool VALS, bool BITS>
-__device__ __forceinline__ void npj_lookup_leave(const NpjLookupArgs &a, u64 v, const uint32_t (&kc)[4], const uint32_t (&res)[4], uint32_t nib,
-                                                 u64 &acc_n, u64 &acc_k, u64 &acc_i)
-{
-    const u64 n = a.n, g = v << 2;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const bool hit = (nib >> j) & 1u;
-        acc_n += hit ? 1u : 0u; acc_k += hit ? kc[j] : 0u; acc_i += hit ? res[j] : 0u;
-    }
-    if constexpr (VALS) {
-        if (g + 4 <= n) hj_store(reinterpret_cast<uint4 *>(a.vals_out) + v, make_uint4(res[0], res[1], res[2], res[3]));
-        else {                                                  // the last, partial vector: nothing at n and beyond is written
-#pragma unroll
-            for (int j = 0; j < 3; ++j) if (g + j < n) hj_store(a.vals_out + g + j, res[j]);
-        }
-    }
-    if constexpr (BITS) {
-        // 8 lanes x 4 rows = one word: OR over each group of 8 lanes, its first lane stores
-        uint32_t w = nib << ((threadIdx.x & 7u) * 4);
-        w |= quad_perm<0xB1>(w);                                // lanes 0<->1, 2<->3
-        w |= quad_perm<0x4E>(w);                                // lanes 0<->2, 1<->3
-        w |= half_row_mirror(w);                                // lane i <-> 7 - i of the group: the other quad
-        // (v is a multiple of 8 in the storing lane: word v / 8 starts at row 4 v; a word whose first row is at n or beyond is not stored)
-        if ((threadIdx.x & 7u) == 0 && g < n) hj_store(a.match_bits + (v >> 3), w);
-    }
-}
-
-// The library's own line-hashed tables: the quad walk of npj_probe_line_body with the first-match rule, without the payload column.  After
-// its walk tuple r of the quad's 16 has its answer in ONE lane - the one whose bucket is the first match - and the answer belongs to lane
-// r / 4 of the quad, component r & 3: a quad OR of (mine ? payload : 0) takes it there (`found` is quad-uniform already: it comes out
-// of the quad's min-reduction of the first matching bucket).
-template <bool VALS, bool BITS>
-__global__ __launch_bounds__(NPJ_PROBE_BLOCK) void npj_lookup_line_kernel(NpjLookupArgs a)
-{
-    constexpr int NW = NPJ_PROBE_WAVES;
-    constexpr int B = 4;                                   // lines in flight per quad
-    __shared__ u64 red[4][NW];
-    const uint4 *__restrict__ k4 = reinterpret_cast<const uint4 *>(a.keys);
-    const u64 n = a.n, nvec = (n + 3) >> 2, stride = (u64)gridDim.x * NPJ_PROBE_BLOCK;
-    const uint4 *__restrict__ t4 = reinterpret_cast<const uint4 *>(a.table);
-    const u64 lines = a.buckets >> 3;
-    const uint32_t factor = a.factor;
-    const uint32_t sub = threadIdx.x & 3;                  // my quarter of the line: buckets 2*sub, 2*sub + 1
-
-    u64 acc_n = 0, acc_k = 0, acc_i = 0;
-    // whole waves iterate together (the quad exchanges and the bitmap's words need all lanes)
-    for (u64 v0 = (u64)blockIdx.x * NPJ_PROBE_BLOCK + (threadIdx.x & ~63u); v0 < nvec; v0 += stride) {
-        const u64 v = v0 + hj_lane();
-        uint4 kk = make_uint4(0, 0, 0, 0);
-        if (v < nvec) kk = k4[v];
-        const u64 g = v << 2;
-        const uint32_t kc[4] = {kk.x, kk.y, kk.z, kk.w};
-        uint32_t okc[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) okc[j] = (g + j < n) ? 1u : 0u;
-        uint32_t res[4] = {HJGPU_NULL_VAL, HJGPU_NULL_VAL, HJGPU_NULL_VAL, HJGPU_NULL_VAL};
-        uint32_t nib = 0;
-
-        // the quad's 16 tuples (4 lanes x 4 components), B at a time
-#pragma unroll
-        for (int r0 = 0; r0 < 16; r0 += B) {
-            uint32_t key[B];
-            bool act[B];
-            u64 ln[B];
-            uint4 q[B];
-#pragma unroll
-            for (int i = 0; i < B; ++i) {
-                const int r = r0 + i, comp = r & 3;                     // static after unrolling
-                // the tuple's owner is lane r / 4 of the quad: broadcast its key and validity
-                if (r < 4) { key[i] = quad_perm<0x00>(kc[comp]); act[i] = quad_perm<0x00>(okc[comp]) != 0; }
-                else if (r < 8) { key[i] = quad_perm<0x55>(kc[comp]); act[i] = quad_perm<0x55>(okc[comp]) != 0; }
-                else if (r < 12) { key[i] = quad_perm<0xAA>(kc[comp]); act[i] = quad_perm<0xAA>(okc[comp]) != 0; }
-                else { key[i] = quad_perm<0xFF>(kc[comp]); act[i] = quad_perm<0xFF>(okc[comp]) != 0; }
-                ln[i] = npj_bucket(key[i], factor, lines);
-                q[i] = make_uint4(0, 0, 0, 0);
-                if (act[i]) {
-                    q[i] = t4[4 * ln[i] + sub];                         // 4 lanes x 16 bytes = the key's line
-                }
-            }
-#pragma unroll
-            for (int i = 0; i < B; ++i) {
-                uint32_t pay = 0;                                       // the first match's payload, in the lane that holds its bucket
-                bool got = false;                                       // the walk found a match (quad-uniform)
-                while (act[i]) {                                        // uniform inside the quad
-                    // first empty bucket of the line, over the quad
-                    uint32_t fe = q[i].x == 0u ? 2 * sub : (q[i].z == 0u ? 2 * sub + 1 : 8u);
-                    fe = min(fe, quad_perm<0xB1>(fe));                  // lanes 0<->1, 2<->3
-                    fe = min(fe, quad_perm<0x4E>(fe));                  // lanes 0<->2, 1<->3
-                    const bool m0 = q[i].x == key[i] && 2 * sub < fe;
-                    const bool m1 = q[i].z == key[i] && 2 * sub + 1 < fe;
-                    // only the FIRST match of the walk counts: the lowest matching bucket of the line
-                    uint32_t fm = m0 ? 2 * sub : (m1 ? 2 * sub + 1 : 8u);
-                    const uint32_t mine = fm;
-                    fm = min(fm, quad_perm<0xB1>(fm));
-                    fm = min(fm, quad_perm<0x4E>(fm));
-                    got = fm < 8u;
-                    if (got && mine == fm) pay = m0 ? q[i].y : q[i].w;
-                    if (fe < 8u || got) break;                          // the walk ends at the first match or the first empty bucket
-                    if (++ln[i] == lines) ln[i] = 0;                    // full line: the walk goes on in the next one
-                    q[i] = t4[4 * ln[i] + sub];
-                }
-                // to the owner (a probe key 0 and a row at n or beyond: no match, pay 0)
-                pay |= quad_perm<0xB1>(pay);
-                pay |= quad_perm<0x4E>(pay);
-                const int r = r0 + i, comp = r & 3;
-                if (got && sub == (uint32_t)(r >> 2)) { res[comp] = pay; nib |= 1u << comp; }
-            }
-        }
-        npj_lookup_leave<VALS, BITS>(a, v, kc, res, nib, acc_n, acc_k, acc_i);
-    }
-    hj_add_to_result(red, a.result, acc_n, acc_k, 0ull, acc_i);
-}
-
-// Tables with the reference's hash (hjgpu_npj_lookup_table; whole look-ups under option "npj_refhash"): the bucket / group walk of
-// npj_probe_body with the first-match rule.  Every lane walks its own four rows: nothing to route.  GROUPED as there.
-template <bool GROUPED, bool VALS, bool BITS>
-__global__ __launch_bounds__(NPJ_PROBE_BLOCK) void npj_lookup_kernel(NpjLookupArgs a)
-{
-    constexpr int NW = NPJ_PROBE_WAVES;
-    __shared__ u64 red[4][NW];
-    const uint4 *__restrict__ k4 = reinterpret_cast<const uint4 *>(a.keys);
-    const u64 n = a.n, nvec = (n + 3) >> 2, stride = (u64)gridDim.x * NPJ_PROBE_BLOCK;
-    const u64 *__restrict__ table = a.table;
-    const u64 buckets = a.buckets;
-    const uint32_t factor = a.factor;
-
-    u64 acc_n = 0, acc_k = 0, acc_i = 0;
-    // whole waves iterate together (the bitmap's words need all lanes)
-    for (u64 v0 = (u64)blockIdx.x * NPJ_PROBE_BLOCK + (threadIdx.x & ~63u); v0 < nvec; v0 += stride) {
-        const u64 v = v0 + hj_lane();
-        uint4 kk = make_uint4(0, 0, 0, 0);
-        if (v < nvec) kk = k4[v];
-        const u64 g = v << 2;
-        const uint32_t key[4] = {kk.x, kk.y, kk.z, kk.w};
-        uint32_t res[4] = {HJGPU_NULL_VAL, HJGPU_NULL_VAL, HJGPU_NULL_VAL, HJGPU_NULL_VAL};
-        uint32_t nib = 0;
-        u64 h[4];
-        bool act[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            act[j] = g + j < n;
-            h[j] = npj_bucket(key[j], factor, buckets);
-        }
-        if (GROUPED) {
-            const uint4 *__restrict__ t4 = reinterpret_cast<const uint4 *>(table);
-            while (act[0] | act[1] | act[2] | act[3]) {
-                uint4 lo[4], hi[4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {           // all group loads of the 4 chains in flight together
-                    lo[j] = make_uint4(0, 0, 0, 0); hi[j] = lo[j];
-                    if (act[j]) { const u64 grp = h[j] >> 2; lo[j] = t4[2 * grp]; hi[j] = t4[2 * grp + 1]; }
-                }
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    if (act[j]) {
-                        const uint32_t bk[4] = {lo[j].x, lo[j].z, hi[j].x, hi[j].z};   // keys of the group
-                        const uint32_t bv[4] = {lo[j].y, lo[j].w, hi[j].y, hi[j].w};   // payloads
-                        const uint32_t first = (uint32_t)h[j] & 3u;
-                        bool open = true;                                              // neither an empty bucket nor a match seen yet
-#pragma unroll
-                        for (int b = 0; b < 4; ++b) {
-                            const bool inb = open && ((uint32_t)b >= first);
-                            if (inb && bk[b] == 0u) open = false;
-                            else if (inb && bk[b] == key[j]) { res[j] = bv[b]; nib |= 1u << j; open = false; }
-                        }
-                        if (!open) act[j] = false;
-                        else { h[j] = (h[j] & ~3ull) + 4; if (h[j] >= buckets) h[j] = 0; }
-                    }
-                }
-            }
-        } else {
-            u64 t[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) t[j] = act[j] ? table[h[j]] : 0ull;
-            while (act[0] | act[1] | act[2] | act[3]) {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    if (act[j]) {
-                        if ((uint32_t)t[j] == 0u) {
-                            act[j] = false;
-                        } else if ((uint32_t)t[j] == key[j]) {
-                            res[j] = (uint32_t)(t[j] >> 32); nib |= 1u << j;
-                            act[j] = false;
-                        } else {
-                            if (++h[j] == buckets) h[j] = 0;
-                            t[j] = table[h[j]];
-                        }
-                    }
-                }
-            }
-        }
-        npj_lookup_leave<VALS, BITS>(a, v, key, res, nib, acc_n, acc_k, acc_i);
-    }
-    hj_add_to_result(red, a.result, acc_n, acc_k, 0ull, acc_i);
-}
-
-int hj_launch_npj_lookup(const NpjLookupArgs &a, int cus, hipStream_t stream)
-{
-    if (a.n == 0) return HJGPU_OK;
-    if (!a.keys || !a.table || !a.result || a.buckets == 0) return HJGPU_EINVAL;
-    if ((((uintptr_t)a.keys | (uintptr_t)a.vals_out | (uintptr_t)a.match_bits) & 15) || ((uintptr_t)a.table & 7)) return HJGPU_EINVAL;
-    if (a.line_hash && (a.buckets % 8 != 0 || ((uintptr_t)a.table & 63))) return HJGPU_EINVAL;
-    const int grid = hj_npj_probe_grid(cus, a.n);
-    const bool grouped = (a.buckets % 4 == 0) && (((uintptr_t)a.table & 31) == 0);
-    void (*kernel)(NpjLookupArgs) = nullptr;
-    hj_with_bool(a.vals_out != nullptr, [&](auto vals) {
-        hj_with_bool(a.match_bits != nullptr, [&](auto bits) {
-            constexpr bool V = decltype(vals)::value, M = decltype(bits)::value;
-            kernel = a.line_hash ? npj_lookup_line_kernel<V, M> : grouped ? npj_lookup_kernel<true, V, M> : npj_lookup_kernel<false, V, M>;
-        });
-    });
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(NPJ_PROBE_BLOCK), 0, stream, a);
-    return hipGetLastError() == hipSuccess ? HJGPU_OK : HJGPU_EHIP;
-}
-
-// --------------------------------------------------------------------------
-// Selected look-up (hjgpu_lookup_selected*, hjgpu_npj_lookup_table_selected; DESIGN.md section 5 "Selected look-up"): the two look-up
-// kernels above for the rows whose bit is set in a.select_bits.  An unselected row is never active: no load of the table is issued for
-// it, it leaves as HJGPU_NULL_VAL with bit 0 and is counted nowhere.  Kernels of their own beside the plain ones, which stay as they
-// are; the head and the end of a trip are hj_lookup_sel.hpp's, where the in-place rule (match_bits == select_bits) is kept.
-// NPJ_SEL_BATCH wave trips per loop iteration: their select words are loaded first, then their keys (sel_fetch).
+// Selected look-up (hjgpu_lookup_selected*, hjgpu_npj_lookup_table_selected; DESIGN.md section 5 "Selected look-up"), SEL: the same walks
+// for the rows whose bit is set in select_bits.  An unselected row is never active: no load of the table is issued for it, it leaves as
+// HJGPU_NULL_VAL with bit 0 and is counted nowhere.  One body per walk behind thin named kernels (DESIGN.md "One body per look-up walk");
+// the head and the end of a trip are hj_lookup.hpp's, where the in-place rule (match_bits == select_bits) is kept.  The head hands every
+// lane the nibble of its rows that are to be looked up: the select bits with SEL, the rows below n without.
+// NPJ_SEL_BATCH wave trips per loop iteration of a selected kernel: their select words are loaded first, then their keys; a plain kernel
+// makes one trip per iteration.
 // --------------------------------------------------------------------------
 constexpr int NPJ_SEL_BATCH = 2;
 
+// The line walk for ONE owner lane of the quad: its four keys, all four lines in flight - the quad walk of npj_probe_line_body with the
+// first-match rule, without the payload column.  `look` is the owner's nibble of rows to look up.  After its walk a key has its answer in
+// ONE lane - the one whose bucket is the first match - and a quad OR of (mine ? payload : 0) takes it to the owner (`got` is quad-uniform
+// already: it comes out of the quad's min-reduction of the first matching bucket).  A quad none of whose owner's keys is to be looked up
+// skips the round; where that holds for every quad of the wave the round issues nothing.
 template <int OWNER>
-__device__ __forceinline__ uint32_t quad_bcast(uint32_t x)           // the value of lane OWNER of the quad
+__device__ __forceinline__ void npj_line_round(const uint4 *__restrict__ t4, u64 lines, uint32_t factor, uint32_t sub, const uint32_t (&kc)[4],
+                                               uint32_t look, uint32_t (&res)[4], uint32_t &nib)
 {
-    return quad_perm<OWNER * 0x55>(x);
-}
-
-// The line walk for ONE owner lane of the quad: its four keys, all four lines in flight (npj_lookup_line_kernel's round, B = 4).  A quad
-// none of whose owner's keys is selected skips the round; where that holds for every quad of the wave the round issues nothing.
-template <int OWNER>
-__device__ __forceinline__ void npj_sel_line_round(const uint4 *__restrict__ t4, u64 lines, uint32_t factor, uint32_t sub, const uint32_t (&kc)[4],
-                                                   uint32_t sel, uint32_t (&res)[4], uint32_t &nib)
-{
-    const uint32_t on = quad_bcast<OWNER>(sel);                     // the owner's select nibble: quad-uniform
+    const uint32_t on = quad_bcast<OWNER>(look);                    // the owner's nibble: quad-uniform
     if (on == 0u) return;
     uint32_t key[4];
     bool act[4];
@@ -1079,8 +856,8 @@ __device__ __forceinline__ void npj_sel_line_round(const uint4 *__restrict__ t4,
         bool got = false;                                           // the walk found a match (quad-uniform)
         while (act[i]) {                                            // uniform inside the quad
             uint32_t fe = q[i].x == 0u ? 2 * sub : (q[i].z == 0u ? 2 * sub + 1 : 8u);      // first empty bucket of the line, over the quad
-            fe = min(fe, quad_perm<0xB1>(fe));
-            fe = min(fe, quad_perm<0x4E>(fe));
+            fe = min(fe, quad_perm<0xB1>(fe));                      // lanes 0<->1, 2<->3
+            fe = min(fe, quad_perm<0x4E>(fe));                      // lanes 0<->2, 1<->3
             const bool m0 = q[i].x == key[i] && 2 * sub < fe;
             const bool m1 = q[i].z == key[i] && 2 * sub + 1 < fe;
             uint32_t fm = m0 ? 2 * sub : (m1 ? 2 * sub + 1 : 8u);   // only the FIRST match counts: the lowest matching bucket of the line
@@ -1093,17 +870,18 @@ __device__ __forceinline__ void npj_sel_line_round(const uint4 *__restrict__ t4,
             if (++ln[i] == lines) ln[i] = 0;                        // full line: the walk goes on in the next one
             q[i] = t4[4 * ln[i] + sub];
         }
-        pay |= quad_perm<0xB1>(pay);                                // to the owner
+        pay |= quad_perm<0xB1>(pay);                                // to the owner (a probe key 0: no match, pay 0)
         pay |= quad_perm<0x4E>(pay);
         if (got && sub == (uint32_t)OWNER) { res[i] = pay; nib |= 1u << i; }
     }
 }
 
-template <bool VALS, bool BITS>
-__global__ __launch_bounds__(NPJ_PROBE_BLOCK) void npj_lookup_sel_line_kernel(NpjLookupSelArgs a)
+// The library's own line-hashed tables: the quad's 16 keys (4 lanes x 4 components) in four rounds, one per owner lane
+template <bool SEL, bool VALS, bool BITS>
+__device__ __forceinline__ void npj_lookup_line_body(const NpjLookupArgs &a, const uint32_t *select_bits)
 {
     constexpr int NW = NPJ_PROBE_WAVES;
-    constexpr int BATCH = NPJ_SEL_BATCH;
+    constexpr int BATCH = SEL ? NPJ_SEL_BATCH : 1;
     __shared__ u64 red[4][NW];
     const uint4 *__restrict__ k4 = reinterpret_cast<const uint4 *>(a.keys);
     const u64 n = a.n, nvec = (n + 3) >> 2, stride = (u64)gridDim.x * NPJ_PROBE_BLOCK;
@@ -1115,9 +893,9 @@ __global__ __launch_bounds__(NPJ_PROBE_BLOCK) void npj_lookup_sel_line_kernel(Np
     u64 acc_n = 0, acc_k = 0, acc_i = 0;
     // whole waves iterate together (the quad exchanges and the bitmaps' words need all lanes)
     for (u64 v0 = (u64)blockIdx.x * NPJ_PROBE_BLOCK + (threadIdx.x & ~63u); v0 < nvec; v0 += stride * BATCH) {
-        uint32_t sel[BATCH];
+        uint32_t look[BATCH];
         uint4 kk[BATCH];
-        sel_fetch<BATCH>(a.select_bits, k4, v0, stride, n, sel, kk);
+        lookup_fetch<SEL, BATCH, SEL>(select_bits, k4, v0, stride, n, look, kk);
 #pragma unroll
         for (int u = 0; u < BATCH; ++u) {
             if (v0 + (u64)u * stride >= nvec) break;                     // the wave's trip lies beyond the column (the same for all its lanes)
@@ -1125,24 +903,40 @@ __global__ __launch_bounds__(NPJ_PROBE_BLOCK) void npj_lookup_sel_line_kernel(Np
             const uint32_t kc[4] = {kk[u].x, kk[u].y, kk[u].z, kk[u].w};
             uint32_t res[4] = {HJGPU_NULL_VAL, HJGPU_NULL_VAL, HJGPU_NULL_VAL, HJGPU_NULL_VAL};
             uint32_t nib = 0;
-            if (__ballot(sel[u] != 0u) != 0ull) {                        // a trip without a selected row: straight to the stores
-                npj_sel_line_round<0>(t4, lines, factor, sub, kc, sel[u], res, nib);
-                npj_sel_line_round<1>(t4, lines, factor, sub, kc, sel[u], res, nib);
-                npj_sel_line_round<2>(t4, lines, factor, sub, kc, sel[u], res, nib);
-                npj_sel_line_round<3>(t4, lines, factor, sub, kc, sel[u], res, nib);
+            bool any = true;
+            if constexpr (SEL) any = __ballot(look[u] != 0u) != 0ull;    // a trip without a selected row: straight to the stores
+            if (any) {
+                npj_line_round<0>(t4, lines, factor, sub, kc, look[u], res, nib);
+                npj_line_round<1>(t4, lines, factor, sub, kc, look[u], res, nib);
+                npj_line_round<2>(t4, lines, factor, sub, kc, look[u], res, nib);
+                npj_line_round<3>(t4, lines, factor, sub, kc, look[u], res, nib);
             }
-            sel_leave<VALS, BITS>(a.vals_out, a.match_bits, n, v, kc, res, nib, acc_n, acc_k, acc_i);
+            lookup_leave<VALS, BITS>(a.vals_out, a.match_bits, n, v, kc, res, nib, acc_n, acc_k, acc_i);
         }
     }
     hj_add_to_result(red, a.result, acc_n, acc_k, 0ull, acc_i);
 }
 
-// Tables with the reference's hash: npj_lookup_kernel's walks, every lane its own four rows, act[j] only where row j is selected.
-template <bool GROUPED, bool VALS, bool BITS>
-__global__ __launch_bounds__(NPJ_PROBE_BLOCK) void npj_lookup_sel_kernel(NpjLookupSelArgs a)
+template <bool VALS, bool BITS>
+__global__ __launch_bounds__(NPJ_PROBE_BLOCK) void npj_lookup_line_kernel(NpjLookupArgs a)
+{
+    npj_lookup_line_body<false, VALS, BITS>(a, nullptr);
+}
+
+template <bool VALS, bool BITS>
+__global__ __launch_bounds__(NPJ_PROBE_BLOCK) void npj_lookup_sel_line_kernel(NpjLookupSelArgs a)
+{
+    npj_lookup_line_body<true, VALS, BITS>(a, a.select_bits);
+}
+
+// Tables with the reference's hash (hjgpu_npj_lookup_table*; whole look-ups under option "npj_refhash"): the bucket / group walk of
+// npj_probe_body with the first-match rule.  Every lane walks its own four rows: nothing to route.  GROUPED as there.  The two walks stand
+// in the body itself: behind a function of their own the grouped one compiled to a quarter more instructions and a wave per SIMD less.
+template <bool SEL, bool GROUPED, bool VALS, bool BITS>
+__device__ __forceinline__ void npj_lookup_body(const NpjLookupArgs &a, const uint32_t *select_bits)
 {
     constexpr int NW = NPJ_PROBE_WAVES;
-    constexpr int BATCH = NPJ_SEL_BATCH;
+    constexpr int BATCH = SEL ? NPJ_SEL_BATCH : 1;
     __shared__ u64 red[4][NW];
     const uint4 *__restrict__ k4 = reinterpret_cast<const uint4 *>(a.keys);
     const u64 n = a.n, nvec = (n + 3) >> 2, stride = (u64)gridDim.x * NPJ_PROBE_BLOCK;
@@ -1153,9 +947,9 @@ __global__ __launch_bounds__(NPJ_PROBE_BLOCK) void npj_lookup_sel_kernel(NpjLook
     u64 acc_n = 0, acc_k = 0, acc_i = 0;
     // whole waves iterate together (the bitmaps' words need all lanes)
     for (u64 v0 = (u64)blockIdx.x * NPJ_PROBE_BLOCK + (threadIdx.x & ~63u); v0 < nvec; v0 += stride * BATCH) {
-        uint32_t sel[BATCH];
+        uint32_t look[BATCH];
         uint4 kk[BATCH];
-        sel_fetch<BATCH>(a.select_bits, k4, v0, stride, n, sel, kk);
+        lookup_fetch<SEL, BATCH, SEL>(select_bits, k4, v0, stride, n, look, kk);
 #pragma unroll
         for (int u = 0; u < BATCH; ++u) {
             if (v0 + (u64)u * stride >= nvec) break;                     // the wave's trip lies beyond the column (the same for all its lanes)
@@ -1167,7 +961,7 @@ __global__ __launch_bounds__(NPJ_PROBE_BLOCK) void npj_lookup_sel_kernel(NpjLook
             bool act[4];
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                act[j] = (sel[u] >> j) & 1u;
+                act[j] = (look[u] >> j) & 1u;
                 h[j] = npj_bucket(key[j], factor, buckets);
             }
             if (GROUPED) {
@@ -1218,29 +1012,44 @@ __global__ __launch_bounds__(NPJ_PROBE_BLOCK) void npj_lookup_sel_kernel(NpjLook
                     }
                 }
             }
-            sel_leave<VALS, BITS>(a.vals_out, a.match_bits, n, v, key, res, nib, acc_n, acc_k, acc_i);
+            lookup_leave<VALS, BITS>(a.vals_out, a.match_bits, n, v, key, res, nib, acc_n, acc_k, acc_i);
         }
     }
     hj_add_to_result(red, a.result, acc_n, acc_k, 0ull, acc_i);
 }
 
-// hj_launch_npj_lookup's checks plus the mask's; the same grid
-int hj_launch_npj_lookup_sel(const NpjLookupSelArgs &a, int cus, hipStream_t stream)
+template <bool GROUPED, bool VALS, bool BITS>
+__global__ __launch_bounds__(NPJ_PROBE_BLOCK) void npj_lookup_kernel(NpjLookupArgs a)
+{
+    npj_lookup_body<false, GROUPED, VALS, BITS>(a, nullptr);
+}
+
+template <bool GROUPED, bool VALS, bool BITS>
+__global__ __launch_bounds__(NPJ_PROBE_BLOCK) void npj_lookup_sel_kernel(NpjLookupSelArgs a)
+{
+    npj_lookup_body<true, GROUPED, VALS, BITS>(a, a.select_bits);
+}
+
+// a.select_bits == NULL: the plain kernels on the base slice of the arguments
+int hj_launch_npj_lookup(const NpjLookupSelArgs &a, int cus, hipStream_t stream)
 {
     if (a.n == 0) return HJGPU_OK;
-    if (!a.keys || !a.table || !a.result || !a.select_bits || a.buckets == 0) return HJGPU_EINVAL;
+    if (!a.keys || !a.table || !a.result || a.buckets == 0) return HJGPU_EINVAL;
     if ((((uintptr_t)a.keys | (uintptr_t)a.vals_out | (uintptr_t)a.match_bits | (uintptr_t)a.select_bits) & 15) || ((uintptr_t)a.table & 7)) return HJGPU_EINVAL;
     if (a.line_hash && (a.buckets % 8 != 0 || ((uintptr_t)a.table & 63))) return HJGPU_EINVAL;
     const int grid = hj_npj_probe_grid(cus, a.n);
     const bool grouped = (a.buckets % 4 == 0) && (((uintptr_t)a.table & 31) == 0);
-    void (*kernel)(NpjLookupSelArgs) = nullptr;
+    void (*plain)(NpjLookupArgs) = nullptr;
+    void (*selected)(NpjLookupSelArgs) = nullptr;
     hj_with_bool(a.vals_out != nullptr, [&](auto vals) {
         hj_with_bool(a.match_bits != nullptr, [&](auto bits) {
             constexpr bool V = decltype(vals)::value, M = decltype(bits)::value;
-            kernel = a.line_hash ? npj_lookup_sel_line_kernel<V, M> : grouped ? npj_lookup_sel_kernel<true, V, M> : npj_lookup_sel_kernel<false, V, M>;
+            plain = a.line_hash ? npj_lookup_line_kernel<V, M> : grouped ? npj_lookup_kernel<true, V, M> : npj_lookup_kernel<false, V, M>;
+            selected = a.line_hash ? npj_lookup_sel_line_kernel<V, M> : grouped ? npj_lookup_sel_kernel<true, V, M> : npj_lookup_sel_kernel<false, V, M>;
         });
     });
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(NPJ_PROBE_BLOCK), 0, stream, a);
+    if (a.select_bits) hipLaunchKernelGGL(selected, dim3(grid), dim3(NPJ_PROBE_BLOCK), 0, stream, a);
+    else hipLaunchKernelGGL(plain, dim3(grid), dim3(NPJ_PROBE_BLOCK), 0, stream, static_cast<const NpjLookupArgs &>(a));
     return hipGetLastError() == hipSuccess ? HJGPU_OK : HJGPU_EHIP;
 }
 

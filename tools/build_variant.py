@@ -24,7 +24,12 @@ def main():
         src = os.path.join(tmp, "hash_join_codes_knl_amd", "csrc")
         os.makedirs(src)
         os.makedirs(os.path.join(tmp, "include"))
-        files = ["include/hjgpu.h"] + ["hash_join_codes_knl_amd/csrc/" + f for f in os.listdir(B.CSRC)]
+        csrc = "hash_join_codes_knl_amd/csrc/"
+        if rev:                                   # the revision's own files: a header may have another name there
+            names = subprocess.check_output(["git", "ls-tree", "--name-only", rev, csrc], cwd=ROOT, text=True).split()
+        else:
+            names = [csrc + f for f in os.listdir(B.CSRC)]
+        files = ["include/hjgpu.h"] + names
         for f in files:
             dst = os.path.join(tmp, f)
             if rev:
