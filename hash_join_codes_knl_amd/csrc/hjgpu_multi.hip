@@ -849,12 +849,31 @@ int check_rows(hjgpu_comm *c, const hjgpu_shard_rows *rows)
     return HJGPU_OK;
 }
 
+// every rank's own count (reduce_results left it in hp_local()) -> rows[l].rows; false: some rank's columns are too small for its rows
+bool read_rank_rows(hjgpu_comm *c, hjgpu_shard_rows *rows)
+{
+    bool fit = true;
+    if (rows) for (size_t l = 0; l < c->ranks.size(); ++l) {
+        rows[l].rows = hp_local(c->ranks[l], (size_t)c->nranks)[0];
+        if (rows[l].rows > rows[l].out.capacity) fit = false;
+    }
+    return fit;
+}
+
+// the inputs are being uploaded (hjgpu_join_host_multi): the build side's partitioning waits for ev_up_r, the probe slices' for
+// ev_up_s - or, with slice_events, slice i for its own upload event ev_up_slice[i] (the shard then arrives in the same `slices`
+// pieces, build side first: slice i is partitioned, exchanged and joined while the later slices are on the bus)
+struct JoinOpts {
+    bool from_host = false;
+    bool slice_events = false;
+};
+
 // ---- PHJ / NPJ: replicated build side, sharded probe side ---------------------------------------------
 // `inner_ready[l]` (optional): an event after which rank l's columns are valid (hjgpu_join_host_multi's uploads) -
 // the probe shard's for every rank, the build columns' as well on the root.
 int replicated_join(hjgpu_comm *c, int algorithm, const hjgpu_shard *shards, hjgpu_shard_rows *rows, int root,
                     const hjgpu_phj_params *pp, const hjgpu_npj_params *np, hjgpu_result *result,
-                    hjgpu_multi_stats *stats, bool from_host = false)
+                    hjgpu_multi_stats *stats, JoinOpts opts = {})
 {
     if (!c || !shards) return HJGPU_EINVAL;
     CHKM(refuse_broken(c));
@@ -862,7 +881,6 @@ int replicated_join(hjgpu_comm *c, int algorithm, const hjgpu_shard *shards, hjg
     CHKM(check_rows(c, rows));
     const auto t0 = std::chrono::steady_clock::now();
     const int L = (int)c->ranks.size();
-    const size_t G = (size_t)c->nranks;
     const size_t inner = shards[0].inner;
     for (int l = 0; l < L; ++l) {
         if (shards[l].inner != inner) return cfail(c, HJGPU_EINVAL, "the build side has the same size on every rank");
@@ -881,7 +899,7 @@ int replicated_join(hjgpu_comm *c, int algorithm, const hjgpu_shard *shards, hjg
         HIPM(c, hipSetDevice(r.device));
         HIPM(c, hj_zero_async(r.d_res.p, 12 * sizeof(u64), r.main));
         HIPM(c, hipEventRecord(r.ev_x0, r.comm));
-        if (from_host) {
+        if (opts.from_host) {
             HIPM(c, hipStreamWaitEvent(r.main, r.ev_up_s, 0));       // the probe shard is in HBM
             if (r.global == root) HIPM(c, hipStreamWaitEvent(r.comm, r.ev_up_r, 0));
         }
@@ -901,7 +919,7 @@ int replicated_join(hjgpu_comm *c, int algorithm, const hjgpu_shard *shards, hjg
         const uint32_t *rk = static_cast<const uint32_t *>(r.rbuf.p), *rv = rk + stride;
         u64 *acc = static_cast<u64 *>(r.d_res.p);
         hjgpu_result *d_res = reinterpret_cast<hjgpu_result *>(acc);
-        if (from_host) HIPM(c, hipEventRecord(r.ev_t0, r.main));    // the join starts here: before the upload has ended?
+        if (opts.from_host) HIPM(c, hipEventRecord(r.ev_t0, r.main));    // the join starts here: before the upload has ended?
         if (rows) JOINM(c, r.join, hjgpu_set_async_output(r.join, &rows[l].out));
         if (algorithm == 1) {
             // the probe shard is histogrammed and partitioned while the build side is still arriving
@@ -920,7 +938,7 @@ int replicated_join(hjgpu_comm *c, int algorithm, const hjgpu_shard *shards, hjg
     }));
     const int status = reduce_results(c, result);
     if (status != HJGPU_OK && status != HJGPU_EZEROKEY && status != HJGPU_EOVERFLOW) return status;
-    if (rows) for (int l = 0; l < L; ++l) rows[l].rows = hp_local(c->ranks[l], G)[0];
+    (void)read_rank_rows(c, rows);
     if (stats) {
         memset(stats, 0, sizeof(*stats));
         Rank &r = c->ranks[0];
@@ -955,27 +973,47 @@ ExchangeBufs bufs_of(Rank &r, int which)
     return {&r.send_k[slot], &r.send_v[slot], &r.recv_k[slot], &r.recv_v[slot], r.ev_xchg[slot]};
 }
 
+// What the local ranks received in one exchange: local rank l has rows[l] rows, piece p of them (from rank p) = rows
+// [pieces[l][p], pieces[l][p + 1]) of the array base[l], the first of them at row pieces[l][0].  One-level road, exchange in
+// place: the array is the rank's SEND buffer - its own partitions were written last (hjgpu_partition_packed_own_last_async),
+// the other ranks' pieces are received right behind them: piece 0 = the own one, never copied; pieces 1.. = the other ranks in order.
+struct Arrived {
+    std::vector<u64> rows;
+    std::vector<std::vector<u64>> pieces;
+    std::vector<const void *> base;
+};
+
+// The road of a CPRA step ("Roads of a CPRA step").  Every rank has to take the same one - it decides the
+// shape of the exchange - so it is decided once, from what every rank knows (CpraRun::agree_on_road).
+// One-level (1 <= G <= 8): the exchange-level partitioning has fan-out G * k and packed output - it IS pass 1 of the join (the
+// reference's own-chunk partitioning is the join's partitioning, cpra2.cpp:1757-1827; ownership 1868-1872): rank g owns
+// partitions [g k, (g + 1) k), the receiver runs pass 2 + build / probe on the pieces as they arrived
+// (hjgpu_phj_build_prepartitioned).  Two-level: round 2's plan (fan-out G in separate columns, complete local PHJ).
+// Grouped: the two-level exchange with the probe side in ONE slice, then the rank's complete local join - whose plan groups.
+struct CpraRoad {
+    enum Kind { ONE_LEVEL, TWO_LEVEL, GROUPED } kind = TWO_LEVEL;
+    uint32_t k = 0;                                 // ONE_LEVEL: partitions per rank of the exchange-level pass; else 0
+    bool own_last = false;                          // ONE_LEVEL: a rank keeps its own partitions where its partitioning wrote them (last)
+    size_t tuple_bytes = sizeof(uint32_t);          // what one all-to-all-v moves per row: a packed tuple (ONE_LEVEL) or one column's word
+};
+
+// the arguments of one all-to-all-v, an entry per local rank
+struct Wire {
+    std::vector<const void *> ks, vs;
+    std::vector<void *> kr, vr;
+    std::vector<const u64 *> so, sc, ro, rc;
+};
+
 struct CpraStep {
     hjgpu_comm *c;
     int L, G;
     std::vector<std::vector<u64>> soff, scnt, roff, rcnt;    // [local rank][peer]
-    std::vector<u64> recv_total;
     hjgpu_multi_stats *stats;
-    // the pieces of what local rank l received in the LAST exchange: piece p (from rank p) = rows [pieces[l][p], pieces[l][p + 1])
-    std::vector<std::vector<u64>> pieces;
-    // ... of the array `base[l]`, the first of them at row pieces[l][0].  One-level plan, exchange in place: the array is the
-    // rank's SEND buffer - its own partitions were written last (hjgpu_partition_packed_own_last_async), the other ranks'
-    // pieces are received right behind them: piece 0 = the own one, never copied; pieces 1.. = the other ranks in order.
-    std::vector<const void *> base;
+    Arrived last;                                             // of the LAST exchange
+    CpraRoad road;
     bool exchange_in_flight = false;                          // local rank 0's ev_x0 / ev_x1 hold an unread exchange
-    bool from_host = false;                                   // the inputs are being uploaded (hjgpu_join_host_multi)
     float exchange_ms = 0;
-    // One-level plan (1 <= G <= 8): the exchange-level partitioning has fan-out G * k and packed output - it IS pass 1 of
-    // the join (the reference's own-chunk partitioning is the join's partitioning, cpra2.cpp:1757-1827; ownership
-    // 1868-1872): rank g owns partitions [g k, (g + 1) k), the receiver runs pass 2 + build / probe on the pieces as
-    // they arrived (hjgpu_phj_build_prepartitioned).  k = 0: round 2's two-level plan (fan-out G, complete local PHJ).
-    uint32_t k = 0;
-    uint32_t fanout() const { return k ? (uint32_t)G * k : (uint32_t)G; }
+    uint32_t fanout() const { return road.k ? (uint32_t)G * road.k : (uint32_t)G; }
     // Counts published with the partitions (cpra2.cpp:1783-1840): when the whole fused histogram G * k * F2 fits K4's LDS
     // (<= 32768 counters; F2 = what the largest receiver's build side needs, the same on every rank) the SENDER's
     // histogram pass counts the receivers' final partitions in the same read of its keys, the histograms travel with the
@@ -983,11 +1021,12 @@ struct CpraStep {
     // per tuple at world 1).  Probe slices only (the build side's K4p reads 1 / 16 of the bytes).
     bool fused = false;
     uint32_t F2 = 0, factor2 = 0;
+    bool counted(int which) const { return fused && which; }     // this exchange carries fused counts
     std::vector<char> counts_usable = std::vector<char>(2, 0);   // [slot] the last exchange through the slot delivered counts
     CpraStep(hjgpu_comm *comm, hjgpu_multi_stats *st)
         : c(comm), L((int)comm->ranks.size()), G(comm->nranks), soff(L, std::vector<u64>(G)), scnt(L, std::vector<u64>(G)),
-          roff(L, std::vector<u64>(G)), rcnt(L, std::vector<u64>(G)), recv_total(L), stats(st), pieces(L, std::vector<u64>(G + 1)),
-          base(L, nullptr) {}
+          roff(L, std::vector<u64>(G)), rcnt(L, std::vector<u64>(G)), stats(st),
+          last{std::vector<u64>(L), std::vector<std::vector<u64>>(L, std::vector<u64>(G + 1)), std::vector<const void *>(L, nullptr)} {}
 
     // call when local rank 0's exchange stream is known to be idle
     void note_exchange()
@@ -1015,8 +1054,8 @@ struct CpraStep {
     {
         const size_t Gs = (size_t)G;
         const size_t F = fanout();                                  // partitions of the exchange-level pass
-        const size_t tuple_bytes = k ? sizeof(u64) : sizeof(uint32_t);
-        const bool own_last = k && c->exchange_in_place && !c->self_via_rccl;
+        const uint32_t k = road.k;
+        const bool own_last = road.own_last;
         return each_rank(L, [&](int l) -> int {
             Rank &r = c->ranks[l];
             ExchangeBufs b = bufs_of(r, which);
@@ -1027,7 +1066,7 @@ struct CpraStep {
                 const u64 guess = (u64)in[l].n + (u64)in[l].n / Gs * (Gs - 1) * 9 / 8 + 4096;
                 hold = (size_t)(r.want_rows[which] > guess ? r.want_rows[which] : guess);
             }
-            CHKM(ensure_scatter_target(c, r, *b.sk, (hold + 16) * tuple_bytes));
+            CHKM(ensure_scatter_target(c, r, *b.sk, (hold + 16) * road.tuple_bytes));
             if (!k) CHKM(ensure(c, r, *b.sv, (in[l].n + 4) * sizeof(uint32_t)));
             u64 *d_off = static_cast<u64 *>(r.d_off.p) + (size_t)slot * OFF_WORDS;
             u64 *h_off = hp_off(r, Gs, slot);
@@ -1041,13 +1080,12 @@ struct CpraStep {
             }
             // in place: the slot's previous slice has been joined (its own piece lives in this buffer)
             if (own_last && which) HIPM(c, hipStreamWaitEvent(r.prep, r.ev_join[slot], 0));
-            const bool counted = fused && which;
-            if (counted) {
+            if (counted(which)) {
                 CHKM(ensure(c, r, r.cnt2[slot], F * F2 * sizeof(u64)));
                 CHKM(ensure(c, r, r.cnt2_all[slot], Gs * F * F2 * sizeof(u64)));
                 CHKM(ensure(c, r, r.cnt_recv[slot], Gs * k * F2 * sizeof(u64)));
             }
-            if (in[l].n && counted)
+            if (in[l].n && counted(which))
                 JOINM(c, r.part, hjgpu_partition_packed_counted_async(r.part, in[l].keys, in[l].vals, in[l].n, TOP_LEVEL_FACTOR, (uint32_t)F,
                                                                       own_last ? (uint32_t)r.global * k : 0u, own_last ? k : 0u, factor2, F2,
                                                                       static_cast<uint64_t *>(b.sk->p), reinterpret_cast<uint64_t *>(d_off),
@@ -1065,7 +1103,7 @@ struct CpraStep {
                                                        reinterpret_cast<uint64_t *>(d_off), r.prep));
             else {
                 HIPM(c, hj_zero_async(d_off, (F + 1) * sizeof(u64), r.prep));
-                if (counted) HIPM(c, hj_zero_async(r.cnt2[slot].p, F * F2 * sizeof(u64), r.prep));
+                if (counted(which)) HIPM(c, hj_zero_async(r.cnt2[slot].p, F * F2 * sizeof(u64), r.prep));
             }
             HIPM(c, hipMemcpyAsync(h_off, d_off, (F + 1) * sizeof(u64), hipMemcpyDeviceToHost, r.prep));
             HIPM(c, hipEventRecord(r.ev_part[slot], r.prep));
@@ -1077,21 +1115,44 @@ struct CpraStep {
     // exchange them, the transfers are enqueued
     int finish_exchange(const std::vector<Slice> &in, int which, int slot)
     {
-        const size_t Gs = (size_t)G;
-        const size_t tuple_bytes = k ? sizeof(u64) : sizeof(uint32_t);
-        const bool own_last = k && c->exchange_in_place && !c->self_via_rccl;
+        CHKM(send_layouts(in, slot));
+        const std::vector<hipStream_t> comms = streams_of(c, &Rank::comm);
+        CHKM(gather_counts(which, slot, comms));
+        Wire w;
+        for (int l = 0; l < L; ++l) {
+            Rank &r = c->ranks[l];
+            bool in_place = false;
+            CHKM(place_receive(l, (u64)in[l].n, which, &w, &in_place));
+            HIPM(c, hipStreamWaitEvent(r.comm, r.ev_part[slot], 0));
+            if (which) HIPM(c, hipStreamWaitEvent(r.comm, r.ev_join[slot], 0));   // the slot's previous slice has been joined
+            if (counted(which)) CHKM(take_histogram_rows(r, slot, in_place));
+            if (l == 0) HIPM(c, hipEventRecord(r.ev_x0, r.comm));
+        }
+        return transfer(w, which, comms);
+    }
+
+    // the host waits for every rank's partition offsets: what it sends to whom, from where
+    int send_layouts(const std::vector<Slice> &in, int slot)
+    {
         for (int l = 0; l < L; ++l) {
             Rank &r = c->ranks[l];
             CHKM(wait_stream(c, l, r.prep, "partitioning"));
-            const u64 *h_off = hp_off(r, Gs, slot);
-            hj_exchange::send_layout(h_off, k, G, r.global, (u64)in[l].n, own_last, soff[l].data(), scnt[l].data());
+            const u64 *h_off = hp_off(r, (size_t)G, slot);
+            hj_exchange::send_layout(h_off, road.k, G, r.global, (u64)in[l].n, road.own_last, soff[l].data(), scnt[l].data());
             if (l == 0 && stats) {
                 hjgpu_stats ps;
                 if (in[l].n && hjgpu_get_stats(r.part, &ps) == HJGPU_OK) stats->ms_partition += ps.ms_total;
                 for (int p = 0; p < G; ++p) if (p != r.global) stats->bytes_sent += scnt[l][p] * 8;
             }
         }
-        // counts first, payload second: one small all-gather gives every rank the G x G matrix of message sizes
+        return HJGPU_OK;
+    }
+
+    // counts first, payload second: one small all-gather gives every rank the G x G matrix of message sizes (on its way to the
+    // host when this returns); with fused counts every rank's histogram of its slice goes to every rank as well
+    int gather_counts(int which, int slot, const std::vector<hipStream_t> &comms)
+    {
+        const size_t Gs = (size_t)G;
         std::vector<const void *> csend;
         std::vector<void *> crecv;
         for (int l = 0; l < L; ++l) {
@@ -1103,80 +1164,83 @@ struct CpraStep {
             HIPM(c, hipMemcpyAsync(d_cnt, h_cnt, Gs * sizeof(u64), hipMemcpyHostToDevice, r.comm));
             csend.push_back(d_cnt); crecv.push_back(d_cnt + Gs);
         }
-        const std::vector<hipStream_t> comms = streams_of(c, &Rank::comm);
         CHKM(c->transport->all_gather(csend.data(), crecv.data(), Gs * sizeof(u64), comms.data()));
-        const bool counted = fused && which;
-        if (counted) {
-            // every rank's fused histogram of its slice to every rank (the partitioning streams have been waited for above)
+        if (counted(which)) {
+            // (the partitioning streams have been waited for: send_layouts)
             std::vector<const void *> hs;
             std::vector<void *> hr;
             for (int l = 0; l < L; ++l) { hs.push_back(c->ranks[l].cnt2[slot].p); hr.push_back(c->ranks[l].cnt2_all[slot].p); }
             CHKM(c->transport->all_gather(hs.data(), hr.data(), (size_t)fanout() * F2 * sizeof(u64), comms.data()));
         }
-        if (which) counts_usable[slot] = counted;
+        if (which) counts_usable[slot] = counted(which);
         for (int l = 0; l < L; ++l) {
             Rank &r = c->ranks[l];
             HIPM(c, hipSetDevice(r.device));
             HIPM(c, hipMemcpyAsync(hp_matrix(r, Gs), static_cast<u64 *>(r.d_cnt.p) + Gs, Gs * Gs * sizeof(u64),
                                    hipMemcpyDeviceToHost, r.comm));
         }
-        std::vector<const void *> ks, vs;
-        std::vector<void *> kr, vr;
-        std::vector<const u64 *> so, sc, ro, rc;
-        for (int l = 0; l < L; ++l) {
-            Rank &r = c->ranks[l];
-            ExchangeBufs b = bufs_of(r, which);
-            CHKM(wait_stream(c, l, r.comm, "exchange"));            // also: the previous exchange has left the links
-            HIPM(c, hipSetDevice(r.device));
-            if (l == 0) note_exchange();
-            const u64 *matrix = hp_matrix(r, Gs);                   // matrix[src][dst]
-            // (the transport is told nothing about a message that stays: in place, counts for itself are 0 on both sides)
-            const hj_exchange::Receive rx = hj_exchange::receive_layout(matrix, G, r.global, (u64)in[l].n, own_last,
-                                                                        b.sk->cap / tuple_bytes > 16 ? b.sk->cap / tuple_bytes - 16 : 0,
-                                                                        roff[l].data(), rcnt[l].data(), pieces[l].data());
-            const u64 at = rx.rows;
-            recv_total[l] = at;
-            // too small this time (the others sent more than this rank's own chunk suggested): the copying path, and the
-            // buffer grows before the next exchange through it
-            if (own_last) r.want_rows[which] = rx.in_place ? (r.want_rows[which] > rx.need ? r.want_rows[which] : rx.need) : rx.need + rx.need / 4;
-            if (rx.in_place) {
-                scnt[l][r.global] = 0;
-                base[l] = b.sk->p;
-                ks.push_back(b.sk->p); vs.push_back(b.sv->p); kr.push_back(b.sk->p); vr.push_back(b.rv->p);
-            } else {
-                // a quarter of headroom: the next slices rarely need a new allocation (hipFree waits for the device)
-                if ((at + 16) * tuple_bytes > b.rk->cap) CHKM(ensure(c, r, *b.rk, (at + at / 4 + 16) * tuple_bytes));
-                if (!k && (at + 4) * sizeof(uint32_t) > b.rv->cap) CHKM(ensure(c, r, *b.rv, (at + at / 4 + 4) * sizeof(uint32_t)));
-                base[l] = b.rk->p;
-                if (l == 0 && stats && rcnt[l][r.global]) stats->self_copies += 1;
-                ks.push_back(b.sk->p); vs.push_back(b.sv->p); kr.push_back(b.rk->p); vr.push_back(b.rv->p);
-            }
-            so.push_back(soff[l].data()); sc.push_back(scnt[l].data()); ro.push_back(roff[l].data()); rc.push_back(rcnt[l].data());
-            HIPM(c, hipStreamWaitEvent(r.comm, r.ev_part[slot], 0));
-            if (which) HIPM(c, hipStreamWaitEvent(r.comm, r.ev_join[slot], 0));   // the slot's previous slice has been joined
-            if (counted) {
-                // the rows of the senders' histograms that describe MY partitions, in the order of my pieces (in place: the
-                // own piece first, then the other ranks in order; else rank order): what K4p would have counted
-                const size_t mine = (size_t)k * F2, all = (size_t)fanout() * F2;
-                int piece = 0;
-                auto take = [&](int sender) -> int {
-                    HIPM(c, hj_copy_async(static_cast<u64 *>(r.cnt_recv[slot].p) + (size_t)piece * mine,
-                                           static_cast<const u64 *>(r.cnt2_all[slot].p) + (size_t)sender * all + (size_t)r.global * mine,
-                                           mine * sizeof(u64), r.comm));
-                    ++piece;
-                    return HJGPU_OK;
-                };
-                if (rx.in_place) {
-                    CHKM(take(r.global));
-                    for (int p = 0; p < G; ++p) if (p != r.global) CHKM(take(p));
-                } else
-                    for (int p = 0; p < G; ++p) CHKM(take(p));
-            }
-            if (l == 0) HIPM(c, hipEventRecord(r.ev_x0, r.comm));
+        return HJGPU_OK;
+    }
+
+    // where local rank l receives: behind its own partitions in its send buffer when they fit there (in place), else in its
+    // receive buffer, grown as needed; the rank's entry of the all-to-all-v's arguments
+    int place_receive(int l, u64 n, int which, Wire *w, bool *in_place)
+    {
+        Rank &r = c->ranks[l];
+        ExchangeBufs b = bufs_of(r, which);
+        const size_t tuple_bytes = road.tuple_bytes;
+        CHKM(wait_stream(c, l, r.comm, "exchange"));            // also: the previous exchange has left the links
+        HIPM(c, hipSetDevice(r.device));
+        if (l == 0) note_exchange();
+        const u64 *matrix = hp_matrix(r, (size_t)G);            // matrix[src][dst]
+        // (the transport is told nothing about a message that stays: in place, counts for itself are 0 on both sides)
+        const hj_exchange::Receive rx = hj_exchange::receive_layout(matrix, G, r.global, n, road.own_last,
+                                                                    b.sk->cap / tuple_bytes > 16 ? b.sk->cap / tuple_bytes - 16 : 0,
+                                                                    roff[l].data(), rcnt[l].data(), last.pieces[l].data());
+        const u64 at = rx.rows;
+        last.rows[l] = at;
+        // too small this time (the others sent more than this rank's own chunk suggested): the copying path, and the
+        // buffer grows before the next exchange through it
+        if (road.own_last) r.want_rows[which] = rx.in_place ? (r.want_rows[which] > rx.need ? r.want_rows[which] : rx.need) : rx.need + rx.need / 4;
+        if (rx.in_place) {
+            scnt[l][r.global] = 0;
+            last.base[l] = b.sk->p;
+            w->ks.push_back(b.sk->p); w->vs.push_back(b.sv->p); w->kr.push_back(b.sk->p); w->vr.push_back(b.rv->p);
+        } else {
+            // a quarter of headroom: the next slices rarely need a new allocation (hipFree waits for the device)
+            if ((at + 16) * tuple_bytes > b.rk->cap) CHKM(ensure(c, r, *b.rk, (at + at / 4 + 16) * tuple_bytes));
+            if (!road.k && (at + 4) * sizeof(uint32_t) > b.rv->cap) CHKM(ensure(c, r, *b.rv, (at + at / 4 + 4) * sizeof(uint32_t)));
+            last.base[l] = b.rk->p;
+            if (l == 0 && stats && rcnt[l][r.global]) stats->self_copies += 1;
+            w->ks.push_back(b.sk->p); w->vs.push_back(b.sv->p); w->kr.push_back(b.rk->p); w->vr.push_back(b.rv->p);
         }
-        // packed tuples: keys and payloads travel together, ONE all-to-all-v per slice
-        CHKM(c->transport->all_to_all_v(ks.data(), so.data(), sc.data(), kr.data(), ro.data(), rc.data(), tuple_bytes, comms.data()));
-        if (!k) CHKM(c->transport->all_to_all_v(vs.data(), so.data(), sc.data(), vr.data(), ro.data(), rc.data(), sizeof(uint32_t), comms.data()));
+        w->so.push_back(soff[l].data()); w->sc.push_back(scnt[l].data()); w->ro.push_back(roff[l].data()); w->rc.push_back(rcnt[l].data());
+        *in_place = rx.in_place;
+        return HJGPU_OK;
+    }
+
+    // the rows of the senders' histograms that describe MY partitions, in the order of my pieces (in place: the own piece
+    // first, then the other ranks in order; else rank order): what K4p would have counted
+    int take_histogram_rows(Rank &r, int slot, bool in_place)
+    {
+        const size_t mine = (size_t)road.k * F2, all = (size_t)fanout() * F2;
+        int piece = 0;
+        for (int p = in_place ? -1 : 0; p < G; ++p) {
+            if (p == r.global && in_place) continue;
+            const int sender = p < 0 ? r.global : p;
+            HIPM(c, hj_copy_async(static_cast<u64 *>(r.cnt_recv[slot].p) + (size_t)piece * mine,
+                                   static_cast<const u64 *>(r.cnt2_all[slot].p) + (size_t)sender * all + (size_t)r.global * mine,
+                                   mine * sizeof(u64), r.comm));
+            ++piece;
+        }
+        return HJGPU_OK;
+    }
+
+    // packed tuples: keys and payloads travel together, ONE all-to-all-v per slice
+    int transfer(const Wire &w, int which, const std::vector<hipStream_t> &comms)
+    {
+        CHKM(c->transport->all_to_all_v(w.ks.data(), w.so.data(), w.sc.data(), w.kr.data(), w.ro.data(), w.rc.data(), road.tuple_bytes, comms.data()));
+        if (!road.k) CHKM(c->transport->all_to_all_v(w.vs.data(), w.so.data(), w.sc.data(), w.vr.data(), w.ro.data(), w.rc.data(), sizeof(uint32_t), comms.data()));
         for (int l = 0; l < L; ++l) {
             Rank &r = c->ranks[l];
             HIPM(c, hipSetDevice(r.device));
@@ -1187,240 +1251,53 @@ struct CpraStep {
     }
 };
 
-// from_host: the shards are being uploaded (hjgpu_join_host_multi): the build side's partitioning waits for ev_up_r, the probe
-// slices' for ev_up_s - or, with slice_events, slice i for its own upload event ev_up_slice[i] (the shard then arrives in the
-// same `slices` pieces, build side first: slice i is partitioned, exchanged and joined while the later slices are on the bus)
-int cpra_join(hjgpu_comm *c, const hjgpu_shard *shards, hjgpu_shard_rows *rows, const hjgpu_phj_params *prm, int slices,
-              hjgpu_result *result, hjgpu_multi_stats *stats, bool from_host = false, bool slice_events = false)
+// the layout of what local rank l received (pieces = one per source rank), rows [lo, hi) of it
+hjgpu_prepartitioned layout_of(const hjgpu_comm *c, int l, uint32_t k, const std::vector<u64> &pieces, u64 lo, u64 hi)
 {
-    if (!c || !shards) return HJGPU_EINVAL;
-    CHKM(refuse_broken(c));
-    // slices exist to overlap the exchange with the local passes; a world of one has nothing to overlap and every slice
-    // costs ~0.6 ms of launches, ramps and tails (world 1, 64 M x 1 G: 10.6 / 11.2 / 12.6 / 15.0 ms with 1 / 2 / 4 / 8 slices)
-    if (slices <= 0) slices = c->nranks == 1 ? 1 : 4;
-    if (slices > 4096) return cfail(c, HJGPU_EINVAL, "at most 4096 slices");
-    CHKM(check_rows(c, rows));
-    const auto t0 = std::chrono::steady_clock::now();
-    if (stats) memset(stats, 0, sizeof(*stats));
-    const int L = (int)c->ranks.size();
-    const size_t G = (size_t)c->nranks;
-    for (int l = 0; l < L; ++l) {
-        const hjgpu_shard &s = shards[l];
-        if ((s.inner && (!s.d_inner_keys || !s.d_inner_vals)) || (s.outer && (!s.d_outer_keys || !s.d_outer_vals)))
-            return cfail(c, HJGPU_EINVAL, "null column in a shard");
-    }
-    CpraStep step(c, stats);
-    // option "debug_forensics": where this step's audit records start in every rank's two contexts
-    std::vector<uint64_t> seq_part((size_t)L, 0), seq_join((size_t)L, 0);
-    if (c->debug_forensics)
+    hjgpu_prepartitioned lay;
+    memset(&lay, 0, sizeof(lay));
+    lay.factor1 = TOP_LEVEL_FACTOR; lay.fanout1_total = (uint32_t)c->nranks * k; lay.fanout1 = k;
+    lay.first_partition = (uint32_t)c->ranks[l].global * k; lay.chunks = (uint32_t)c->nranks;
+    for (int p = 0; p <= c->nranks; ++p) { const u64 x = pieces[(size_t)p]; lay.chunk_offsets[p] = x < lo ? lo : (x > hi ? hi : x); }
+    for (int p = c->nranks + 1; p < 9; ++p) lay.chunk_offsets[p] = lay.chunk_offsets[c->nranks];
+    return lay;
+}
+
+// Option "debug_forensics": the audit records of a CPRA step (option "audit" is on in every rank's two contexts).  With the
+// option at 0 nothing here does anything.
+struct CpraForensics {
+    hjgpu_comm *c;
+    int L;
+    std::vector<uint64_t> seq_part, seq_join;       // where this step's records start in every rank's two contexts
+    explicit CpraForensics(hjgpu_comm *comm) : c(comm), L((int)comm->ranks.size()), seq_part((size_t)L, 0), seq_join((size_t)L, 0) {}
+
+    void mark()
+    {
+        if (!c->debug_forensics) return;
         for (int l = 0; l < L; ++l) {
             (void)hjgpu_audit_read(c->ranks[l].part, &seq_part[(size_t)l], 0, 0, nullptr, nullptr);
             (void)hjgpu_audit_read(c->ranks[l].join, &seq_join[(size_t)l], 0, 0, nullptr, nullptr);
         }
-    // A rank's share beyond two passes' reach (a build side of ~228 M rows per rank and more, with a probe side large enough for a
-    // third pass to pay: hjgpu_grouped_plan, the rule of hjgpu_phj) is joined by a GROUPED plan.  Every rank has to take the same
-    // road - it decides the shape of the exchange - so the rule is fed what every rank can know: the relations' TOTAL sizes (one
-    // all-reduce of two words), a rank's share taken as 1 / G of them.  The grouped road: exchange with fan-out G in separate
-    // columns (round 2's two-level plan), the probe side in ONE slice, then the rank's complete local join - whose plan groups.
-    bool grouped = false;
-    const int asked_slices = slices;
-    if (c->cpra_grouped) {
-        std::vector<u64 *> words;
+    }
+
+    void begin_slices() { if (c->debug_forensics >= 2) c->frozen.clear(); }
+
+    // "debug_forensics" = 2 (see hjgpu_comm::frozen), every rank: partition(part_slice) - the host has just waited for its counts -
+    // and join(join_slice) - waited for here, the next join is not enqueued yet; a slice < 0: there is none
+    int check_slice(int part_slice, int join_slice)
+    {
+        if (c->debug_forensics < 2) return HJGPU_OK;
         for (int l = 0; l < L; ++l) {
-            Rank &r = c->ranks[l];
-            HIPM(c, hipSetDevice(r.device));
-            u64 *h = hp_result(r, G);
-            h[0] = shards[l].inner; h[1] = shards[l].outer;
-            HIPM(c, hipMemcpyAsync(r.d_cnt.p, h, 2 * sizeof(u64), hipMemcpyHostToDevice, r.comm));
-            words.push_back(static_cast<u64 *>(r.d_cnt.p));
+            if (part_slice >= 0) CHKM(freeze_check(l, 0, part_slice));
+            if (join_slice >= 0) CHKM(freeze_check(l, 1, join_slice));
         }
-        const std::vector<hipStream_t> comms = streams_of(c, &Rank::comm);
-        CHKM(c->transport->all_reduce_u64(words.data(), 2, comms.data()));
-        for (int l = 0; l < L; ++l) {
-            Rank &r = c->ranks[l];
-            HIPM(c, hipSetDevice(r.device));
-            HIPM(c, hipMemcpyAsync(hp_result(r, G), r.d_cnt.p, 2 * sizeof(u64), hipMemcpyDeviceToHost, r.comm));
-        }
-        for (int l = 0; l < L; ++l) CHKM(wait_stream(c, l, c->ranks[l].comm, "sizes"));
-        const u64 *tot = hp_result(c->ranks[0], G);
-        uint32_t groups = 0;
-        JOINM(c, c->ranks[0].join, hjgpu_grouped_plan(c->ranks[0].join, (size_t)(tot[0] / G), (size_t)(tot[1] / G), prm, &groups));
-        grouped = groups > 1;
-        // (1: only where the road's extra pass pays - exchange_layout.hpp grouped_road_pays says why and where)
-        if (grouped && c->cpra_grouped == 1 && !hj_exchange::grouped_road_pays(tot[0] / G, tot[1] / G, HJGPU_MAX_PARTS)) grouped = false;
-        if (grouped) slices = 1;
-    }
-    // one-level plan while the receiver can take one piece per source rank (<= 8 pieces): fan-out G * k with G * k <= 192,
-    // the widest pass 1 whose whole-line carry still fits beside a 16 K-tuple tile
-    if (c->nranks <= 8 && !c->cpra_two_level && !grouped) step.k = (uint32_t)(c->cpra_k > 0 && c->cpra_k * c->nranks <= 192 ? c->cpra_k : 192 / c->nranks);
-    const uint32_t K = step.k;
-    // the layout of what local rank l received (pieces = one per source rank), rows [lo, hi) of it
-    auto layout_of = [&](int l, const std::vector<u64> &pieces, u64 lo, u64 hi) {
-        hjgpu_prepartitioned lay;
-        memset(&lay, 0, sizeof(lay));
-        lay.factor1 = TOP_LEVEL_FACTOR; lay.fanout1_total = (uint32_t)c->nranks * K; lay.fanout1 = K;
-        lay.first_partition = (uint32_t)c->ranks[l].global * K; lay.chunks = (uint32_t)c->nranks;
-        for (int p = 0; p <= c->nranks; ++p) { const u64 x = pieces[(size_t)p]; lay.chunk_offsets[p] = x < lo ? lo : (x > hi ? hi : x); }
-        for (int p = c->nranks + 1; p < 9; ++p) lay.chunk_offsets[p] = lay.chunk_offsets[c->nranks];
-        return lay;
-    };
-    for (Rank &r : c->ranks) {
-        HIPM(c, hipSetDevice(r.device));
-        HIPM(c, hj_zero_async(r.d_res.p, 12 * sizeof(u64), r.main));
-        // timing events of the slices' waits, one pair per slice, read after the step (nobody waits in between)
-        while (r.ev_w.size() < 2 * (size_t)slices) {
-            hipEvent_t e = nullptr;
-            HIPM(c, hipEventCreate(&e));
-            r.ev_w.push_back(e);
-        }
-    }
-    // ---- build side: partition the own chunk -> exchange -> prepared once for all probe slices ---------
-    std::vector<Slice> in(L);
-    for (int l = 0; l < L; ++l) in[l] = {shards[l].d_inner_keys, shards[l].d_inner_vals, shards[l].inner};
-    CHKM(step.exchange(in, 0, 0, from_host ? &Rank::ev_up_r : nullptr));
-    const std::vector<u64> inner_recv = step.recv_total;
-    const std::vector<std::vector<u64>> inner_pieces = step.pieces;
-    const std::vector<const void *> inner_base = step.base;
-    // counts published with the partitions (CpraStep::fused): every rank reads the same G x G matrix of the build exchange,
-    // so every rank arrives at the same F2 - what the receiver with the largest build side needs
-    hjgpu_phj_params prm_fused;
-    if (K && c->cpra_fused_counts) {
-        const u64 *mx = hp_matrix(c->ranks[0], G);
-        u64 most = 0;
-        for (size_t dst = 0; dst < G; ++dst) {
-            u64 rows_of_dst = 0;
-            for (size_t src = 0; src < G; ++src) rows_of_dst += mx[src * G + dst];
-            most = most > rows_of_dst ? most : rows_of_dst;
-        }
-        uint32_t f2 = 0, m2 = 0;
-        if (most && hjgpu_prepartitioned_plan(c->ranks[0].join, (size_t)most, K, prm, &f2, &m2) == HJGPU_OK &&
-            (u64)G * K * f2 <= 32768 && m2 != TOP_LEVEL_FACTOR) {
-            step.fused = true; step.F2 = f2; step.factor2 = m2;
-            memset(&prm_fused, 0, sizeof(prm_fused));
-            if (prm) prm_fused = *prm;
-            prm_fused.fanout2 = f2;                         // every receiver plans the same second level
-            prm = &prm_fused;
-        }
-    }
-    std::vector<size_t> max_outer(L);
-    for (int l = 0; l < L; ++l) {
-        Rank &r = c->ranks[l];
-        // batches are the slices this rank RECEIVES: about one local slice when the hash spreads the keys evenly;
-        // the workspace is sized for 1.5 of that, larger batches are probed in pieces
-        const size_t per = shards[l].outer / (size_t)slices + 16;
-        max_outer[l] = (per * 3 / 2 > ((size_t)1 << 20) ? per * 3 / 2 : ((size_t)1 << 20)) & ~size_t(15);
-        if (grouped) max_outer[l] = ~size_t(0) >> 1;         // the local join takes what arrived in one call
-        HIPM(c, hipSetDevice(r.device));
-        // (the grouped road enqueues nothing here: its one local join waits for the probe side's exchange, which the exchange stream
-        // runs after the build side's)
-        if (!grouped) HIPM(c, hipStreamWaitEvent(r.main, r.ev_rx, 0));
-        if (from_host && l == 0) HIPM(c, hipEventRecord(r.ev_t0, r.main));
-        if (grouped) continue;                               // no prepared build side: the local join is one whole hjgpu_phj
-        if (inner_recv[l] && K) {
-            const hjgpu_prepartitioned lay = layout_of(l, inner_pieces[l], inner_pieces[l][0], inner_pieces[l][0] + inner_recv[l]);
-            JOINM(c, r.join, hjgpu_phj_build_prepartitioned(r.join, static_cast<const uint64_t *>(inner_base[l]), &lay, max_outer[l], prm, r.main));
-        } else if (inner_recv[l])
-            JOINM(c, r.join, hjgpu_phj_build(r.join, static_cast<const uint32_t *>(r.rrecv_k.p), static_cast<const uint32_t *>(r.rrecv_v.p),
-                                             (size_t)inner_recv[l], max_outer[l], prm, r.main));
-    }
-    // Phase times of local rank 0's joins: the BUILD and the LAST probe batch are measured (stats->joins /
-    // tuples_joined describe exactly those).  The context's events are re-recorded by every call, so reading a
-    // slice's times means waiting for that slice - which would hold the single driving host thread until join(i-1)
-    // has finished before partition(i+1) can be enqueued, i.e. the pipeline would be measured out of shape.
-    // The build's times are read when the host blocks anyway (the first probe slice's partition counts).
-    bool build_stats_pending = stats && inner_recv[0] && !grouped;
-    // ---- probe side in slices: partition(i+1) | exchange(i) | join(i-1) ----------------------------------
-    // R join S = union_i (R join S_i): the slice results add up (add_result_kernel).
-    // Materialised rows: a slice's rows follow the rows of the slices before it in the rank's result columns; where
-    // they start is known on the host once the previous join has finished (its count), which is long before this
-    // slice has arrived.
-    std::vector<u64> used(L, 0);                 // rows in the rank's result columns so far
-    std::vector<char> row_pending(L, 0);         // hp_local()[0] will hold the rank's running count (char: the ranks' threads write their own element)
-    u64 measured = 0;
-    auto join_slice = [&](int i, int slot, const std::vector<u64> &got, const std::vector<std::vector<u64>> &got_pieces,
-                          const std::vector<const void *> &got_base) -> int {
-        measured = 0;
-        CHKM(each_rank(L, [&](int l) -> int {
-            Rank &r = c->ranks[l];
-            HIPM(c, hipSetDevice(r.device));
-            if (c->debug_serialize & 8) {            // the join waits for whatever the partitioning stream has been given so far
-                HIPM(c, hipEventRecord(r.ev_dbg2, r.prep));
-                HIPM(c, hipStreamWaitEvent(r.main, r.ev_dbg2, 0));
-            }
-            HIPM(c, hipEventRecord(r.ev_w[2 * (size_t)i], r.main));
-            HIPM(c, hipStreamWaitEvent(r.main, r.ev_xchg[slot], 0));
-            HIPM(c, hipEventRecord(r.ev_w[2 * (size_t)i + 1], r.main));
-            const uint32_t *sk = static_cast<const uint32_t *>(r.recv_k[slot].p), *sv = static_cast<const uint32_t *>(r.recv_v[slot].p);
-            u64 *acc = static_cast<u64 *>(r.d_res.p);
-            if (inner_recv[l])
-                for (u64 b = 0; b < got[l]; b += max_outer[l]) {
-                    const size_t m = got[l] - b < max_outer[l] ? (size_t)(got[l] - b) : max_outer[l];
-                    if (rows) {
-                        if (row_pending[l]) {                       // the rows so far: the previous batch's running count
-                            CHKM(wait_stream(c, l, r.main, "join"));
-                            used[l] = hp_local(r, G)[0];
-                            row_pending[l] = false;
-                        }
-                        const hjgpu_output &o = rows[l].out;
-                        const size_t bs = o.block_size ? o.block_size : 65536;
-                        hjgpu_output piece = o;
-                        piece.block_size = bs;
-                        if (used[l] + bs <= o.capacity) {
-                            piece.d_keys = o.d_keys + used[l]; piece.d_outer_vals = o.d_outer_vals + used[l]; piece.d_inner_vals = o.d_inner_vals + used[l];
-                            piece.capacity = (o.capacity - used[l]) / bs * bs;
-                            JOINM(c, r.join, hjgpu_set_async_output(r.join, &piece));
-                        } else {
-                            // no block left in this rank's columns: the batch is joined WITHOUT output (its count still joins
-                            // the running count: hjgpu_shard_rows.rows reports what the rank needs) and the overflow flag is
-                            // raised here.  (Pointing the batch at the last block relied on the emitter to flag the overflow,
-                            // which it does only when a second block is claimed: a batch with few matches overwrote valid rows
-                            // of earlier slices and the call returned HJGPU_OK.)
-                            hipLaunchKernelGGL(bump_kernel, dim3(1), dim3(1), 0, r.main, acc + 5);
-                            HIPM(c, hipGetLastError());
-                        }
-                    }
-                    if (K) {
-                        // a batch = rows [b, b + m) of what arrived: a contiguous piece of the pieces (still sorted by partition)
-                        const u64 first = got_pieces[l][0];
-                        const hjgpu_prepartitioned lay = layout_of(l, got_pieces[l], first + b, first + b + m);
-                        // the senders' counts describe WHOLE pieces: a slice that is joined in one batch needs no K4p
-                        if (step.fused && step.counts_usable[slot] && b == 0 && m == got[l])
-                            JOINM(c, r.join, hjgpu_phj_probe_prepartitioned_counted_async(r.join, static_cast<const uint64_t *>(got_base[l]), &lay,
-                                                                                          static_cast<const uint64_t *>(r.cnt_recv[slot].p),
-                                                                                          reinterpret_cast<hjgpu_result *>(acc + 8), r.main));
-                        else
-                        JOINM(c, r.join, hjgpu_phj_probe_prepartitioned_async(r.join, static_cast<const uint64_t *>(got_base[l]), &lay,
-                                                                              reinterpret_cast<hjgpu_result *>(acc + 8), r.main));
-                    } else if (grouped)
-                        // the rank's whole local join; its plan groups where the share needs it (the build side has arrived: the exchange
-                        // stream received it before the probe side, whose arrival this stream has just waited for)
-                    {
-                        JOINM(c, r.join, hjgpu_phj_overlapped_async(r.join, static_cast<const uint32_t *>(r.rrecv_k.p), static_cast<const uint32_t *>(r.rrecv_v.p),
-                                                                    (size_t)inner_recv[l], sk + b, sv + b, m, prm,
-                                                                    reinterpret_cast<hjgpu_result *>(acc + 8), r.main, nullptr));
-                        const int sg = settle_grouped_local_join(c, l, r, (size_t)inner_recv[l], m, prm);
-                        if (sg != HJGPU_OK) return sg;
-                    }
-                    else
-                    JOINM(c, r.join, hjgpu_phj_probe_async(r.join, sk + b, sv + b, m, reinterpret_cast<hjgpu_result *>(acc + 8), r.main));
-                    hipLaunchKernelGGL(add_result_kernel, dim3(1), dim3(64), 0, r.main, acc, acc + 8);
-                    HIPM(c, hipGetLastError());
-                    if (rows) {
-                        JOINM(c, r.join, hjgpu_accumulate_async_status(r.join, reinterpret_cast<uint64_t *>(acc + 4), r.main));
-                        HIPM(c, hipMemcpyAsync(hp_local(r, G), acc, sizeof(u64), hipMemcpyDeviceToHost, r.main));
-                        row_pending[l] = true;
-                    }
-                    if (l == 0) measured = m;                        // the context's events describe its LAST batch
-                }
-            HIPM(c, hipEventRecord(r.ev_join[slot], r.main));
-            return HJGPU_OK;
-        }));
-        if (c->debug_serialize & 1) for (int l = 0; l < L; ++l) CHKM(wait_stream(c, l, c->ranks[l].main, "join"));
         return HJGPU_OK;
-    };
-    // option "debug_forensics" = 2 (see hjgpu_comm::frozen): the last record of a context, read behind `stream`; when a partition check of it
-    // differs from what the call read - or a probe's result from the batch it read - the checks are done again at once, device quiet
-    auto freeze_check = [&](int l, int which, int slice) -> int {
+    }
+
+    // the last record of a context, read behind its stream; when a partition check of it differs from what the call read - or a
+    // probe's result from the batch it read - the checks are done again at once, device quiet
+    int freeze_check(int l, int which, int slice)
+    {
         Rank &r = c->ranks[l];
         hjgpu_ctx *ctx = which ? r.join : r.part;
         HIPM(c, hipSetDevice(r.device));
@@ -1453,51 +1330,12 @@ int cpra_join(hjgpu_comm *c, const hjgpu_shard *shards, hjgpu_shard_rows *rows, 
         memcpy(c->frozen.data() + at + 4, rec, sizeof(rec));
         if (n) JOINM(c, ctx, hjgpu_audit_recheck(ctx, reinterpret_cast<uint64_t *>(c->frozen.data() + at + 36), n, &n));
         return HJGPU_OK;
-    };
-    if (c->debug_forensics >= 2) c->frozen.clear();
-    std::vector<u64> pending;
-    std::vector<std::vector<u64>> pending_pieces;
-    std::vector<const void *> pending_base;
-    int pending_slice = -1;
-    for (int i = 0; i < slices; ++i) {
-        const int slot = i & 1;
-        for (int l = 0; l < L; ++l) {
-            size_t b, e;
-            range_of(shards[l].outer, 16, (size_t)i, (size_t)slices, &b, &e);
-            in[l] = {shards[l].outer ? shards[l].d_outer_keys + b : nullptr, shards[l].outer ? shards[l].d_outer_vals + b : nullptr, e - b};
-        }
-        // partition(i) is enqueued first, then join(i-1) - which the device starts as soon as exchange(i-1) has arrived -
-        // and only then does the host wait for partition(i)'s counts: the device works on join(i-1) and partition(i)
-        // while the host and the ranks settle the sizes of exchange(i) (with the join enqueued after that wait, every
-        // slice cost a world of one ~0.15-0.2 ms of idle device: 4 slices 13.0 -> 12.2-12.6 ms, 8 slices 16.7 -> 14.9-15.0 ms)
-        // (host path with an event per uploaded slice: the one slice of a grouped join is the whole shard - its last upload)
-        CHKM(step.begin_exchange(in, 1 + slot, slot, from_host ? &Rank::ev_up_s : nullptr,
-                                 from_host && slice_events ? (grouped ? asked_slices - 1 : i) : -1));
-        if (pending_slice >= 0) CHKM(join_slice(pending_slice, pending_slice & 1, pending, pending_pieces, pending_base));
-        CHKM(step.finish_exchange(in, 1 + slot, slot));
-        if (c->debug_forensics >= 2)
-            for (int l = 0; l < L; ++l) {
-                CHKM(freeze_check(l, 0, i));                            // partition(i): the host has just waited for its counts
-                if (pending_slice >= 0) CHKM(freeze_check(l, 1, pending_slice));           // join(i - 1): waited for here; join(i) is not enqueued yet
-            }
-        if (build_stats_pending && i == 0) {
-            // the host has just waited for this slice's partition counts and the counts gather; the build was enqueued
-            // before both and is (nearly always) done: reading its events costs the pipeline nothing
-            hjgpu_stats js;
-            if (hjgpu_get_stats(c->ranks[0].join, &js) == HJGPU_OK) { add_stats(&stats->join, js); stats->joins += 1; stats->tuples_joined += inner_recv[0]; }
-            build_stats_pending = false;
-        }
-        pending = step.recv_total;
-        pending_pieces = step.pieces;
-        pending_base = step.base;
-        pending_slice = i;
     }
-    CHKM(join_slice(pending_slice, pending_slice & 1, pending, pending_pieces, pending_base));
-    if (c->debug_forensics >= 2) for (int l = 0; l < L; ++l) CHKM(freeze_check(l, 1, pending_slice));
-    const int status = reduce_results(c, result);
-    if (status != HJGPU_OK && status != HJGPU_EOVERFLOW) return status;
-    if (c->debug_forensics) {
-        // every stage's checksum of this step (the streams are idle: reduce_results waited for them)
+
+    // every stage's checksum of this step (call with the streams idle: after reduce_results)
+    int collect()
+    {
+        if (!c->debug_forensics) return HJGPU_OK;
         c->forensics.clear();
         for (int l = 0; l < L; ++l) {
             Rank &r = c->ranks[l];
@@ -1511,26 +1349,364 @@ int cpra_join(hjgpu_comm *c, const hjgpu_shard *shards, hjgpu_shard_rows *rows, 
             JOINM(c, r.part, hjgpu_audit_read(r.part, nullptr, seq_part[(size_t)l], np, reinterpret_cast<uint64_t *>(c->forensics.data() + at + 3), r.prep));
             JOINM(c, r.join, hjgpu_audit_read(r.join, nullptr, seq_join[(size_t)l], nj, reinterpret_cast<uint64_t *>(c->forensics.data() + at + 3 + (size_t)np * 32), r.main));
         }
+        return HJGPU_OK;
     }
-    bool rows_fit = true;
-    if (rows) for (int l = 0; l < L; ++l) {
-        rows[l].rows = hp_local(c->ranks[l], G)[0];
-        if (rows[l].rows > rows[l].out.capacity) rows_fit = false;
+};
+
+// One CPRA step: the state its stages share (cpra_join is the list of them).
+struct CpraRun {
+    hjgpu_comm *c;
+    const hjgpu_shard *shards;
+    hjgpu_shard_rows *rows;
+    const hjgpu_phj_params *prm;
+    int slices;
+    hjgpu_result *result;
+    hjgpu_multi_stats *stats;
+    JoinOpts opts;
+    const int L;
+    const size_t G;
+    CpraStep step;
+    CpraForensics forensics;
+    std::chrono::steady_clock::time_point t0;
+    int asked_slices = 0;
+    std::vector<Slice> in;                       // every local rank's slice on its way into the exchange
+    Arrived inner;                               // the build side as it arrived
+    hjgpu_phj_params prm_fused;
+    std::vector<size_t> max_outer;               // [local rank] the probe batch its prepared build side takes
+    bool build_stats_pending = false;
+    std::vector<u64> used;                       // rows in the rank's result columns so far
+    std::vector<char> row_pending;               // hp_local()[0] will hold the rank's running count (char: the ranks' threads write their own element)
+    u64 measured = 0;
+
+    CpraRun(hjgpu_comm *comm, const hjgpu_shard *sh, hjgpu_shard_rows *rw, const hjgpu_phj_params *p, int sl, hjgpu_result *res,
+            hjgpu_multi_stats *st, JoinOpts o)
+        : c(comm), shards(sh), rows(rw), prm(p), slices(sl), result(res), stats(st), opts(o), L((int)comm->ranks.size()),
+          G((size_t)comm->nranks), step(comm, st), forensics(comm), in(L), max_outer(L), used(L, 0), row_pending(L, 0) {}
+    CpraRun(const CpraRun &) = delete;           // (prm may point at prm_fused)
+
+    int check()
+    {
+        CHKM(refuse_broken(c));
+        // slices exist to overlap the exchange with the local passes; a world of one has nothing to overlap and every slice
+        // costs ~0.6 ms of launches, ramps and tails (world 1, 64 M x 1 G: 10.6 / 11.2 / 12.6 / 15.0 ms with 1 / 2 / 4 / 8 slices)
+        if (slices <= 0) slices = c->nranks == 1 ? 1 : 4;
+        if (slices > 4096) return cfail(c, HJGPU_EINVAL, "at most 4096 slices");
+        CHKM(check_rows(c, rows));
+        t0 = std::chrono::steady_clock::now();
+        if (stats) memset(stats, 0, sizeof(*stats));
+        for (int l = 0; l < L; ++l) {
+            const hjgpu_shard &s = shards[l];
+            if ((s.inner && (!s.d_inner_keys || !s.d_inner_vals)) || (s.outer && (!s.d_outer_keys || !s.d_outer_vals)))
+                return cfail(c, HJGPU_EINVAL, "null column in a shard");
+        }
+        asked_slices = slices;
+        return HJGPU_OK;
     }
-    step.note_exchange();
-    if (stats) {
-        Rank &r = c->ranks[0];
-        HIPM(c, hipSetDevice(r.device));
-        hjgpu_stats js;
-        if (measured && hjgpu_get_stats(r.join, &js) == HJGPU_OK) { add_stats(&stats->join, js); stats->joins += 1; stats->tuples_joined += measured; }
-        for (int i = 0; i < slices; ++i) stats->ms_exchange_wait += elapsed(r.ev_w[2 * (size_t)i], r.ev_w[2 * (size_t)i + 1]);
-        stats->ms_exchange = step.exchange_ms;
-        stats->ms_wall = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+
+    // A rank's share beyond two passes' reach (a build side of ~228 M rows per rank and more, with a probe side large enough for a
+    // third pass to pay: hjgpu_grouped_plan, the rule of hjgpu_phj) is joined by a GROUPED plan.  Every rank has to take the same
+    // road, so the rule is fed what every rank can know: the relations' TOTAL sizes (one all-reduce of two words), a rank's share
+    // taken as 1 / G of them.  The grouped road takes the probe side in ONE slice.
+    int agree_on_road()
+    {
+        bool grouped = false;
+        if (c->cpra_grouped) {
+            std::vector<u64 *> words;
+            for (int l = 0; l < L; ++l) {
+                Rank &r = c->ranks[l];
+                HIPM(c, hipSetDevice(r.device));
+                u64 *h = hp_result(r, G);
+                h[0] = shards[l].inner; h[1] = shards[l].outer;
+                HIPM(c, hipMemcpyAsync(r.d_cnt.p, h, 2 * sizeof(u64), hipMemcpyHostToDevice, r.comm));
+                words.push_back(static_cast<u64 *>(r.d_cnt.p));
+            }
+            const std::vector<hipStream_t> comms = streams_of(c, &Rank::comm);
+            CHKM(c->transport->all_reduce_u64(words.data(), 2, comms.data()));
+            for (int l = 0; l < L; ++l) {
+                Rank &r = c->ranks[l];
+                HIPM(c, hipSetDevice(r.device));
+                HIPM(c, hipMemcpyAsync(hp_result(r, G), r.d_cnt.p, 2 * sizeof(u64), hipMemcpyDeviceToHost, r.comm));
+            }
+            for (int l = 0; l < L; ++l) CHKM(wait_stream(c, l, c->ranks[l].comm, "sizes"));
+            const u64 *tot = hp_result(c->ranks[0], G);
+            uint32_t groups = 0;
+            JOINM(c, c->ranks[0].join, hjgpu_grouped_plan(c->ranks[0].join, (size_t)(tot[0] / G), (size_t)(tot[1] / G), prm, &groups));
+            grouped = groups > 1;
+            // (1: only where the road's extra pass pays - exchange_layout.hpp grouped_road_pays says why and where)
+            if (grouped && c->cpra_grouped == 1 && !hj_exchange::grouped_road_pays(tot[0] / G, tot[1] / G, HJGPU_MAX_PARTS)) grouped = false;
+        }
+        CpraRoad &road = step.road;
+        if (grouped) {
+            road.kind = CpraRoad::GROUPED;
+            slices = 1;
+        } else if (c->nranks <= 8 && !c->cpra_two_level) {
+            // one-level plan while the receiver can take one piece per source rank (<= 8 pieces): fan-out G * k with G * k <= 192,
+            // the widest pass 1 whose whole-line carry still fits beside a 16 K-tuple tile
+            road.kind = CpraRoad::ONE_LEVEL;
+            road.k = (uint32_t)(c->cpra_k > 0 && c->cpra_k * c->nranks <= 192 ? c->cpra_k : 192 / c->nranks);
+            road.own_last = c->exchange_in_place && !c->self_via_rccl;
+            road.tuple_bytes = sizeof(u64);
+        }
+        return HJGPU_OK;
     }
-    // belt and braces: whatever the flags say, more rows than a rank's columns hold is an overflow
-    if (status == HJGPU_OK && !rows_fit)
-        return cfail(c, HJGPU_EOVERFLOW, "materialised output exceeded the capacity of a local rank's result columns (rows needed per rank: hjgpu_shard_rows.rows)");
-    return status;
+
+    int zero_results()
+    {
+        for (Rank &r : c->ranks) {
+            HIPM(c, hipSetDevice(r.device));
+            HIPM(c, hj_zero_async(r.d_res.p, 12 * sizeof(u64), r.main));
+            // timing events of the slices' waits, one pair per slice, read after the step (nobody waits in between)
+            while (r.ev_w.size() < 2 * (size_t)slices) {
+                hipEvent_t e = nullptr;
+                HIPM(c, hipEventCreate(&e));
+                r.ev_w.push_back(e);
+            }
+        }
+        return HJGPU_OK;
+    }
+
+    // build side: partition the own chunk -> exchange (-> prepared once for all probe slices: prepare_build)
+    int exchange_build()
+    {
+        for (int l = 0; l < L; ++l) in[l] = {shards[l].d_inner_keys, shards[l].d_inner_vals, shards[l].inner};
+        CHKM(step.exchange(in, 0, 0, opts.from_host ? &Rank::ev_up_r : nullptr));
+        inner = step.last;
+        return HJGPU_OK;
+    }
+
+    // counts published with the partitions (CpraStep::fused): every rank reads the same G x G matrix of the build exchange,
+    // so every rank arrives at the same F2 - what the receiver with the largest build side needs
+    void choose_fused_counts()
+    {
+        const uint32_t K = step.road.k;
+        if (!K || !c->cpra_fused_counts) return;
+        const u64 *mx = hp_matrix(c->ranks[0], G);
+        u64 most = 0;
+        for (size_t dst = 0; dst < G; ++dst) {
+            u64 rows_of_dst = 0;
+            for (size_t src = 0; src < G; ++src) rows_of_dst += mx[src * G + dst];
+            most = most > rows_of_dst ? most : rows_of_dst;
+        }
+        uint32_t f2 = 0, m2 = 0;
+        if (most && hjgpu_prepartitioned_plan(c->ranks[0].join, (size_t)most, K, prm, &f2, &m2) == HJGPU_OK &&
+            (u64)G * K * f2 <= 32768 && m2 != TOP_LEVEL_FACTOR) {
+            step.fused = true; step.F2 = f2; step.factor2 = m2;
+            memset(&prm_fused, 0, sizeof(prm_fused));
+            if (prm) prm_fused = *prm;
+            prm_fused.fanout2 = f2;                         // every receiver plans the same second level
+            prm = &prm_fused;
+        }
+    }
+
+    int prepare_build()
+    {
+        const bool grouped = step.road.kind == CpraRoad::GROUPED;
+        for (int l = 0; l < L; ++l) {
+            Rank &r = c->ranks[l];
+            // batches are the slices this rank RECEIVES: about one local slice when the hash spreads the keys evenly;
+            // the workspace is sized for 1.5 of that, larger batches are probed in pieces
+            const size_t per = shards[l].outer / (size_t)slices + 16;
+            max_outer[l] = (per * 3 / 2 > ((size_t)1 << 20) ? per * 3 / 2 : ((size_t)1 << 20)) & ~size_t(15);
+            if (grouped) max_outer[l] = ~size_t(0) >> 1;         // the local join takes what arrived in one call
+            HIPM(c, hipSetDevice(r.device));
+            // (the grouped road enqueues nothing here: its one local join waits for the probe side's exchange, which the exchange stream
+            // runs after the build side's)
+            if (!grouped) HIPM(c, hipStreamWaitEvent(r.main, r.ev_rx, 0));
+            if (opts.from_host && l == 0) HIPM(c, hipEventRecord(r.ev_t0, r.main));
+            if (grouped) continue;                               // no prepared build side: the local join is one whole hjgpu_phj
+            if (inner.rows[l] && step.road.k) {
+                const hjgpu_prepartitioned lay = layout_of(c, l, step.road.k, inner.pieces[l], inner.pieces[l][0], inner.pieces[l][0] + inner.rows[l]);
+                JOINM(c, r.join, hjgpu_phj_build_prepartitioned(r.join, static_cast<const uint64_t *>(inner.base[l]), &lay, max_outer[l], prm, r.main));
+            } else if (inner.rows[l])
+                JOINM(c, r.join, hjgpu_phj_build(r.join, static_cast<const uint32_t *>(r.rrecv_k.p), static_cast<const uint32_t *>(r.rrecv_v.p),
+                                                 (size_t)inner.rows[l], max_outer[l], prm, r.main));
+        }
+        // Phase times of local rank 0's joins: the BUILD and the LAST probe batch are measured (stats->joins /
+        // tuples_joined describe exactly those).  The context's events are re-recorded by every call, so reading a
+        // slice's times means waiting for that slice - which would hold the single driving host thread until join(i-1)
+        // has finished before partition(i+1) can be enqueued, i.e. the pipeline would be measured out of shape.
+        // The build's times are read when the host blocks anyway (the first probe slice's partition counts).
+        build_stats_pending = stats && inner.rows[0] && !grouped;
+        return HJGPU_OK;
+    }
+
+    // ---- probe side in slices: partition(i+1) | exchange(i) | join(i-1) ----------------------------------
+    // R join S = union_i (R join S_i): the slice results add up (add_result_kernel).
+    // Materialised rows: a slice's rows follow the rows of the slices before it in the rank's result columns; where
+    // they start is known on the host once the previous join has finished (its count), which is long before this
+    // slice has arrived.
+    int probe_slices()
+    {
+        const bool grouped = step.road.kind == CpraRoad::GROUPED;
+        forensics.begin_slices();
+        Arrived pending;
+        int pending_slice = -1;
+        for (int i = 0; i < slices; ++i) {
+            const int slot = i & 1;
+            for (int l = 0; l < L; ++l) {
+                size_t b, e;
+                range_of(shards[l].outer, 16, (size_t)i, (size_t)slices, &b, &e);
+                in[l] = {shards[l].outer ? shards[l].d_outer_keys + b : nullptr, shards[l].outer ? shards[l].d_outer_vals + b : nullptr, e - b};
+            }
+            // partition(i) is enqueued first, then join(i-1) - which the device starts as soon as exchange(i-1) has arrived -
+            // and only then does the host wait for partition(i)'s counts: the device works on join(i-1) and partition(i)
+            // while the host and the ranks settle the sizes of exchange(i) (with the join enqueued after that wait, every
+            // slice cost a world of one ~0.15-0.2 ms of idle device: 4 slices 13.0 -> 12.2-12.6 ms, 8 slices 16.7 -> 14.9-15.0 ms)
+            // (host path with an event per uploaded slice: the one slice of a grouped join is the whole shard - its last upload)
+            CHKM(step.begin_exchange(in, 1 + slot, slot, opts.from_host ? &Rank::ev_up_s : nullptr,
+                                     opts.from_host && opts.slice_events ? (grouped ? asked_slices - 1 : i) : -1));
+            if (pending_slice >= 0) CHKM(join_slice(pending_slice, pending));
+            CHKM(step.finish_exchange(in, 1 + slot, slot));
+            CHKM(forensics.check_slice(i, pending_slice));
+            if (build_stats_pending && i == 0) {
+                // the host has just waited for this slice's partition counts and the counts gather; the build was enqueued
+                // before both and is (nearly always) done: reading its events costs the pipeline nothing
+                hjgpu_stats js;
+                if (hjgpu_get_stats(c->ranks[0].join, &js) == HJGPU_OK) { add_stats(&stats->join, js); stats->joins += 1; stats->tuples_joined += inner.rows[0]; }
+                build_stats_pending = false;
+            }
+            pending = step.last;
+            pending_slice = i;
+        }
+        CHKM(join_slice(pending_slice, pending));
+        return forensics.check_slice(-1, pending_slice);
+    }
+
+    // the local joins of slice i, which arrived as `got`, in batches of at most max_outer rows
+    int join_slice(int i, const Arrived &got)
+    {
+        const int slot = i & 1;
+        measured = 0;
+        CHKM(each_rank(L, [&](int l) -> int {
+            Rank &r = c->ranks[l];
+            HIPM(c, hipSetDevice(r.device));
+            if (c->debug_serialize & 8) {            // the join waits for whatever the partitioning stream has been given so far
+                HIPM(c, hipEventRecord(r.ev_dbg2, r.prep));
+                HIPM(c, hipStreamWaitEvent(r.main, r.ev_dbg2, 0));
+            }
+            HIPM(c, hipEventRecord(r.ev_w[2 * (size_t)i], r.main));
+            HIPM(c, hipStreamWaitEvent(r.main, r.ev_xchg[slot], 0));
+            HIPM(c, hipEventRecord(r.ev_w[2 * (size_t)i + 1], r.main));
+            u64 *acc = static_cast<u64 *>(r.d_res.p);
+            if (inner.rows[l])
+                for (u64 b = 0; b < got.rows[l]; b += max_outer[l]) {
+                    const size_t m = got.rows[l] - b < max_outer[l] ? (size_t)(got.rows[l] - b) : max_outer[l];
+                    if (rows) CHKM(place_rows(l));
+                    CHKM(join_batch(l, slot, got, b, m));
+                    hipLaunchKernelGGL(add_result_kernel, dim3(1), dim3(64), 0, r.main, acc, acc + 8);
+                    HIPM(c, hipGetLastError());
+                    if (rows) {
+                        JOINM(c, r.join, hjgpu_accumulate_async_status(r.join, reinterpret_cast<uint64_t *>(acc + 4), r.main));
+                        HIPM(c, hipMemcpyAsync(hp_local(r, G), acc, sizeof(u64), hipMemcpyDeviceToHost, r.main));
+                        row_pending[l] = true;
+                    }
+                    if (l == 0) measured = m;                        // the context's events describe its LAST batch
+                }
+            HIPM(c, hipEventRecord(r.ev_join[slot], r.main));
+            return HJGPU_OK;
+        }));
+        if (c->debug_serialize & 1) for (int l = 0; l < L; ++l) CHKM(wait_stream(c, l, c->ranks[l].main, "join"));
+        return HJGPU_OK;
+    }
+
+    // where the next batch's rows go: behind the rows so far in local rank l's result columns
+    int place_rows(int l)
+    {
+        Rank &r = c->ranks[l];
+        if (row_pending[l]) {                       // the rows so far: the previous batch's running count
+            CHKM(wait_stream(c, l, r.main, "join"));
+            used[l] = hp_local(r, G)[0];
+            row_pending[l] = false;
+        }
+        const hjgpu_output &o = rows[l].out;
+        const size_t bs = o.block_size ? o.block_size : 65536;
+        hjgpu_output piece = o;
+        piece.block_size = bs;
+        if (used[l] + bs <= o.capacity) {
+            piece.d_keys = o.d_keys + used[l]; piece.d_outer_vals = o.d_outer_vals + used[l]; piece.d_inner_vals = o.d_inner_vals + used[l];
+            piece.capacity = (o.capacity - used[l]) / bs * bs;
+            JOINM(c, r.join, hjgpu_set_async_output(r.join, &piece));
+        } else {
+            // no block left in this rank's columns: the batch is joined WITHOUT output (its count still joins
+            // the running count: hjgpu_shard_rows.rows reports what the rank needs) and the overflow flag is
+            // raised here.  (Pointing the batch at the last block relied on the emitter to flag the overflow,
+            // which it does only when a second block is claimed: a batch with few matches overwrote valid rows
+            // of earlier slices and the call returned HJGPU_OK.)
+            hipLaunchKernelGGL(bump_kernel, dim3(1), dim3(1), 0, r.main, static_cast<u64 *>(r.d_res.p) + 5);
+            HIPM(c, hipGetLastError());
+        }
+        return HJGPU_OK;
+    }
+
+    // one batch - rows [b, b + m) of what local rank l received through `slot` - joined by the call's road; its aggregates go to d_res[8..]
+    int join_batch(int l, int slot, const Arrived &got, u64 b, size_t m)
+    {
+        Rank &r = c->ranks[l];
+        hjgpu_result *d_batch = reinterpret_cast<hjgpu_result *>(static_cast<u64 *>(r.d_res.p) + 8);
+        const uint32_t *sk = static_cast<const uint32_t *>(r.recv_k[slot].p), *sv = static_cast<const uint32_t *>(r.recv_v[slot].p);
+        switch (step.road.kind) {
+        case CpraRoad::ONE_LEVEL: {
+            // a batch = a contiguous piece of the pieces (still sorted by partition)
+            const u64 first = got.pieces[l][0];
+            const hjgpu_prepartitioned lay = layout_of(c, l, step.road.k, got.pieces[l], first + b, first + b + m);
+            // the senders' counts describe WHOLE pieces: a slice that is joined in one batch needs no K4p
+            if (step.fused && step.counts_usable[slot] && b == 0 && m == got.rows[l])
+                JOINM(c, r.join, hjgpu_phj_probe_prepartitioned_counted_async(r.join, static_cast<const uint64_t *>(got.base[l]), &lay,
+                                                                              static_cast<const uint64_t *>(r.cnt_recv[slot].p), d_batch, r.main));
+            else
+                JOINM(c, r.join, hjgpu_phj_probe_prepartitioned_async(r.join, static_cast<const uint64_t *>(got.base[l]), &lay, d_batch, r.main));
+            return HJGPU_OK;
+        }
+        case CpraRoad::GROUPED:
+            // the rank's whole local join; its plan groups where the share needs it (the build side has arrived: the exchange
+            // stream received it before the probe side, whose arrival this stream has just waited for)
+            JOINM(c, r.join, hjgpu_phj_overlapped_async(r.join, static_cast<const uint32_t *>(r.rrecv_k.p), static_cast<const uint32_t *>(r.rrecv_v.p),
+                                                        (size_t)inner.rows[l], sk + b, sv + b, m, prm, d_batch, r.main, nullptr));
+            return settle_grouped_local_join(c, l, r, (size_t)inner.rows[l], m, prm);
+        case CpraRoad::TWO_LEVEL:
+            JOINM(c, r.join, hjgpu_phj_probe_async(r.join, sk + b, sv + b, m, d_batch, r.main));
+        }
+        return HJGPU_OK;
+    }
+
+    // reduce, the rows check, statistics
+    int finish()
+    {
+        const int status = reduce_results(c, result);
+        if (status != HJGPU_OK && status != HJGPU_EOVERFLOW) return status;
+        CHKM(forensics.collect());
+        const bool rows_fit = read_rank_rows(c, rows);
+        step.note_exchange();
+        if (stats) {
+            Rank &r = c->ranks[0];
+            HIPM(c, hipSetDevice(r.device));
+            hjgpu_stats js;
+            if (measured && hjgpu_get_stats(r.join, &js) == HJGPU_OK) { add_stats(&stats->join, js); stats->joins += 1; stats->tuples_joined += measured; }
+            for (int i = 0; i < slices; ++i) stats->ms_exchange_wait += elapsed(r.ev_w[2 * (size_t)i], r.ev_w[2 * (size_t)i + 1]);
+            stats->ms_exchange = step.exchange_ms;
+            stats->ms_wall = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        }
+        // belt and braces: whatever the flags say, more rows than a rank's columns hold is an overflow
+        if (status == HJGPU_OK && !rows_fit)
+            return cfail(c, HJGPU_EOVERFLOW, "materialised output exceeded the capacity of a local rank's result columns (rows needed per rank: hjgpu_shard_rows.rows)");
+        return status;
+    }
+};
+
+int cpra_join(hjgpu_comm *c, const hjgpu_shard *shards, hjgpu_shard_rows *rows, const hjgpu_phj_params *prm, int slices,
+              hjgpu_result *result, hjgpu_multi_stats *stats, JoinOpts opts = {})
+{
+    if (!c || !shards) return HJGPU_EINVAL;
+    CpraRun run(c, shards, rows, prm, slices, result, stats, opts);
+    CHKM(run.check());
+    run.forensics.mark();
+    CHKM(run.agree_on_road());
+    CHKM(run.zero_results());
+    CHKM(run.exchange_build());
+    run.choose_fused_counts();
+    CHKM(run.prepare_build());
+    CHKM(run.probe_slices());
+    return run.finish();
 }
 
 int new_comm(int nranks, hjgpu_comm **out, hjgpu_comm **c)
@@ -2028,29 +2204,51 @@ int hjgpu_cpra_multi_rows(hjgpu_comm *c, const hjgpu_shard *shards, hjgpu_shard_
 // ~0.6 ms of launches; the upload of 1 / 8 of a shard takes ~10 ms at the PCIe rate)
 constexpr int HOST_CPRA_SLICES = 8;
 
-static int join_host_multi_impl(hjgpu_comm *c, int algorithm,
-                                const uint32_t *ik, const uint32_t *iv, size_t inner,
-                                const uint32_t *ok, const uint32_t *ov, size_t outer,
-                                const hjgpu_phj_params *pp, const hjgpu_npj_params *np,
-                                const hjgpu_host_rows *host_rows, hjgpu_result *result, hjgpu_multi_stats *stats)
-{
-    if (!c || algorithm < 0 || algorithm > 2) return HJGPU_EINVAL;
-    CHKM(refuse_broken(c));
-    if ((int)c->ranks.size() != c->nranks) return cfail(c, HJGPU_EINVAL, "hjgpu_join_host_multi needs a local communicator");
-    if (pp) CHKM(refuse_join_mode_multi(c, pp->flags, "hjgpu_join_host_multi"));
-    if (np) CHKM(refuse_join_mode_multi(c, np->flags, "hjgpu_join_host_multi"));
-    if ((inner && (!ik || !iv)) || (outer && (!ok || !ov))) return cfail(c, HJGPU_EINVAL, "null column");
-    if (host_rows && (!result || (host_rows->capacity && (!host_rows->keys || !host_rows->outer_vals || !host_rows->inner_vals))))
-        return cfail(c, HJGPU_EINVAL, "hjgpu_join_host_rows_multi: result and the three result columns are required");
-    const int G = c->nranks;
-    const auto t0 = std::chrono::steady_clock::now();
-    if (host_rows && algorithm != 2 && c->host_rows_batched && inner && outer) {
-        // Replicated build side with rows: every rank runs the ONE-GPU host pipeline on its probe shard (npj.cpp:1013-1039
-        // reads the columns, 997-1000 sizes the output: here per GPU) - the build side read from the host by every GPU
-        // (SURVEY 8e), the shard in batches behind the DMA, a batch's dense rows going home while the next is joined and the
-        // one after it uploaded - and all ranks append to the caller's columns through one atomic cursor: the concatenation
-        // is the result, in the order the batches finish.  A rank whose rows do not fit (a skewed batch, or the capacity)
-        // counts them: the call then reports the needed rows, or starts over on the whole-shard path below.
+namespace {
+
+// One hjgpu_join_host_multi / hjgpu_join_host_rows_multi call: its arguments and what its stages share.
+struct HostJoin {
+    hjgpu_comm *c;
+    int algorithm;
+    const uint32_t *ik, *iv;
+    size_t inner;
+    const uint32_t *ok, *ov;
+    size_t outer;
+    const hjgpu_phj_params *pp;
+    const hjgpu_npj_params *np;
+    const hjgpu_host_rows *host_rows;
+    hjgpu_result *result;
+    hjgpu_multi_stats *stats;
+    int G = 0;
+    std::chrono::steady_clock::time_point t0;
+    std::vector<hjgpu_shard> shards;                // [rank] its share of the columns, in the communicator's buffers
+    std::vector<hjgpu_shard_rows> rows;             // [rank] its result columns (host_rows)
+
+    int check()
+    {
+        CHKM(refuse_broken(c));
+        if ((int)c->ranks.size() != c->nranks) return cfail(c, HJGPU_EINVAL, "hjgpu_join_host_multi needs a local communicator");
+        if (pp) CHKM(refuse_join_mode_multi(c, pp->flags, "hjgpu_join_host_multi"));
+        if (np) CHKM(refuse_join_mode_multi(c, np->flags, "hjgpu_join_host_multi"));
+        if ((inner && (!ik || !iv)) || (outer && (!ok || !ov))) return cfail(c, HJGPU_EINVAL, "null column");
+        if (host_rows && (!result || (host_rows->capacity && (!host_rows->keys || !host_rows->outer_vals || !host_rows->inner_vals))))
+            return cfail(c, HJGPU_EINVAL, "hjgpu_join_host_rows_multi: result and the three result columns are required");
+        G = c->nranks;
+        t0 = std::chrono::steady_clock::now();
+        return HJGPU_OK;
+    }
+
+    // Replicated build side with rows: every rank runs the ONE-GPU host pipeline on its probe shard (npj.cpp:1013-1039
+    // reads the columns, 997-1000 sizes the output: here per GPU) - the build side read from the host by every GPU
+    // (SURVEY 8e), the shard in batches behind the DMA, a batch's dense rows going home while the next is joined and the
+    // one after it uploaded - and all ranks append to the caller's columns through one atomic cursor: the concatenation
+    // is the result, in the order the batches finish.  A rank whose rows do not fit (a skewed batch, or the capacity)
+    // counts them: the call then reports the needed rows, or starts over on the whole-shard path.
+    // *done = false: this call does not take the road, or has to start over on whole shards.
+    int batched_rows(bool *done)
+    {
+        *done = false;
+        if (!(host_rows && algorithm != 2 && c->host_rows_batched && inner && outer)) return HJGPU_OK;
         uint64_t cursor = 0;
         std::vector<hjgpu_result> res((size_t)G);
         std::vector<hjgpu_stats> st((size_t)G);
@@ -2074,71 +2272,86 @@ static int join_host_multi_impl(hjgpu_comm *c, int algorithm,
             sum.count += res[(size_t)g].count; sum.sum_keys += res[(size_t)g].sum_keys;
             sum.sum_outer_vals += res[(size_t)g].sum_outer_vals; sum.sum_inner_vals += res[(size_t)g].sum_inner_vals;
         }
-        if (!overflow || sum.count > host_rows->capacity) {
-            *result = sum;
-            if (stats) {
-                memset(stats, 0, sizeof(*stats));
-                stats->join = st[0]; stats->ms_upload = st[0].ms_upload; stats->joins = st[0].batches ? st[0].batches : 1;
-                stats->tuples_joined = inner + outer / (size_t)G;
-                stats->ms_wall = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-            }
-            if (overflow) return cfail(c, HJGPU_EOVERFLOW, "hjgpu_join_host_rows_multi: the result has more rows than rows->capacity (see result->count)");
-            return HJGPU_OK;
+        // a batch outgrew its device columns although the whole fits the capacity (skew): whole shards
+        if (overflow && sum.count <= host_rows->capacity) return HJGPU_OK;
+        *done = true;
+        *result = sum;
+        if (stats) {
+            memset(stats, 0, sizeof(*stats));
+            stats->join = st[0]; stats->ms_upload = st[0].ms_upload; stats->joins = st[0].batches ? st[0].batches : 1;
+            stats->tuples_joined = inner + outer / (size_t)G;
+            stats->ms_wall = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
         }
-        // a batch outgrew its device columns although the whole fits the capacity (skew): whole shards, below
+        if (overflow) return cfail(c, HJGPU_EOVERFLOW, "hjgpu_join_host_rows_multi: the result has more rows than rows->capacity (see result->count)");
+        return HJGPU_OK;
     }
-    std::vector<hjgpu_shard> shards((size_t)G);
-    for (int g = 0; g < G; ++g) {
-        Rank &r = c->ranks[(size_t)g];
-        hjgpu_shard &s = shards[(size_t)g];
-        memset(&s, 0, sizeof(s));
-        size_t sb, se, rb = 0, re = 0;
-        range_of(outer, 16, (size_t)g, (size_t)G, &sb, &se);            // thread_beg / thread_end with T = ranks
-        s.outer = se - sb;
-        if (algorithm == 2) { range_of(inner, 16, (size_t)g, (size_t)G, &rb, &re); s.inner = re - rb; }
-        else { s.inner = inner; if (g == 0) { rb = 0; re = inner; } }
-        const uint32_t *h[4] = {ik + rb, iv + rb, ok + sb, ov + sb};
-        const size_t n[4] = {re - rb, re - rb, s.outer, s.outer};
-        for (int i = 0; i < 4; ++i) CHKM(ensure(c, r, r.shard[i], (n[i] + 4) * sizeof(uint32_t)));
-        HIPM(c, hipSetDevice(r.device));
-        // pinned columns (hjgpu_host_alloc) are DMA'd; the GPUs' uploads run side by side
-        if (algorithm == 2) {
-            // CPRA needs the build side first (its exchange and the prepared build come before any probe slice), then the
-            // probe shard arrives in the slices the join takes it in: slice i is partitioned, exchanged and joined while the
-            // later slices are still on the bus (the reference reads all four columns before its clock starts,
-            // cpra2.cpp:2110-2136; here the upload is most of a call: 8.5 GB at the PCIe rate against ~15 ms of join)
-            while (r.ev_up_slice.size() < (size_t)HOST_CPRA_SLICES) {
-                hipEvent_t e = nullptr;
-                HIPM(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-                r.ev_up_slice.push_back(e);
+
+    // every rank's share of the columns on its way into the rank's buffers, on the rank's upload stream
+    int upload_shards()
+    {
+        shards.resize((size_t)G);
+        for (int g = 0; g < G; ++g) {
+            Rank &r = c->ranks[(size_t)g];
+            hjgpu_shard &s = shards[(size_t)g];
+            memset(&s, 0, sizeof(s));
+            size_t sb, se, rb = 0, re = 0;
+            range_of(outer, 16, (size_t)g, (size_t)G, &sb, &se);            // thread_beg / thread_end with T = ranks
+            s.outer = se - sb;
+            if (algorithm == 2) { range_of(inner, 16, (size_t)g, (size_t)G, &rb, &re); s.inner = re - rb; }
+            else { s.inner = inner; if (g == 0) { rb = 0; re = inner; } }
+            const uint32_t *h[4] = {ik + rb, iv + rb, ok + sb, ov + sb};
+            const size_t n[4] = {re - rb, re - rb, s.outer, s.outer};
+            for (int i = 0; i < 4; ++i) CHKM(ensure(c, r, r.shard[i], (n[i] + 4) * sizeof(uint32_t)));
+            HIPM(c, hipSetDevice(r.device));
+            // pinned columns (hjgpu_host_alloc) are DMA'd; the GPUs' uploads run side by side
+            if (algorithm == 2) {
+                // CPRA needs the build side first (its exchange and the prepared build come before any probe slice), then the
+                // probe shard arrives in the slices the join takes it in: slice i is partitioned, exchanged and joined while the
+                // later slices are still on the bus (the reference reads all four columns before its clock starts,
+                // cpra2.cpp:2110-2136; here the upload is most of a call: 8.5 GB at the PCIe rate against ~15 ms of join)
+                while (r.ev_up_slice.size() < (size_t)HOST_CPRA_SLICES) {
+                    hipEvent_t e = nullptr;
+                    HIPM(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+                    r.ev_up_slice.push_back(e);
+                }
+                for (int i : {0, 1}) if (n[i]) HIPM(c, hipMemcpyAsync(r.shard[i].p, h[i], n[i] * sizeof(uint32_t), hipMemcpyHostToDevice, r.up));
+                HIPM(c, hipEventRecord(r.ev_up_r, r.up));
+                for (int i = 0; i < HOST_CPRA_SLICES; ++i) {
+                    size_t b, e;
+                    range_of(s.outer, 16, (size_t)i, (size_t)HOST_CPRA_SLICES, &b, &e);       // the slices of cpra_join
+                    for (int col : {2, 3})
+                        if (e > b) HIPM(c, hipMemcpyAsync(static_cast<uint32_t *>(r.shard[col].p) + b, h[col] + b, (e - b) * sizeof(uint32_t), hipMemcpyHostToDevice, r.up));
+                    HIPM(c, hipEventRecord(r.ev_up_slice[(size_t)i], r.up));
+                }
+                HIPM(c, hipEventRecord(r.ev_up_s, r.up));
+            } else {
+                // PHJ / NPJ: probe side first - it is partitioned while the build side is still arriving
+                for (int i : {2, 3, 0, 1}) {
+                    if (n[i]) HIPM(c, hipMemcpyAsync(r.shard[i].p, h[i], n[i] * sizeof(uint32_t), hipMemcpyHostToDevice, r.up));
+                    if (i == 3) HIPM(c, hipEventRecord(r.ev_up_s, r.up));
+                }
+                HIPM(c, hipEventRecord(r.ev_up_r, r.up));
             }
-            for (int i : {0, 1}) if (n[i]) HIPM(c, hipMemcpyAsync(r.shard[i].p, h[i], n[i] * sizeof(uint32_t), hipMemcpyHostToDevice, r.up));
-            HIPM(c, hipEventRecord(r.ev_up_r, r.up));
-            for (int i = 0; i < HOST_CPRA_SLICES; ++i) {
-                size_t b, e;
-                range_of(s.outer, 16, (size_t)i, (size_t)HOST_CPRA_SLICES, &b, &e);       // the slices of cpra_join
-                for (int col : {2, 3})
-                    if (e > b) HIPM(c, hipMemcpyAsync(static_cast<uint32_t *>(r.shard[col].p) + b, h[col] + b, (e - b) * sizeof(uint32_t), hipMemcpyHostToDevice, r.up));
-                HIPM(c, hipEventRecord(r.ev_up_slice[(size_t)i], r.up));
-            }
-            HIPM(c, hipEventRecord(r.ev_up_s, r.up));
-        } else {
-            // PHJ / NPJ: probe side first - it is partitioned while the build side is still arriving
-            for (int i : {2, 3, 0, 1}) {
-                if (n[i]) HIPM(c, hipMemcpyAsync(r.shard[i].p, h[i], n[i] * sizeof(uint32_t), hipMemcpyHostToDevice, r.up));
-                if (i == 3) HIPM(c, hipEventRecord(r.ev_up_s, r.up));
-            }
-            HIPM(c, hipEventRecord(r.ev_up_r, r.up));
+            HIPM(c, hipEventRecord(r.ev_t1, r.up));
+            s.d_outer_keys = static_cast<const uint32_t *>(r.shard[2].p); s.d_outer_vals = static_cast<const uint32_t *>(r.shard[3].p);
+            if (re > rb) { s.d_inner_keys = static_cast<const uint32_t *>(r.shard[0].p); s.d_inner_vals = static_cast<const uint32_t *>(r.shard[1].p); }
         }
-        HIPM(c, hipEventRecord(r.ev_t1, r.up));
-        s.d_outer_keys = static_cast<const uint32_t *>(r.shard[2].p); s.d_outer_vals = static_cast<const uint32_t *>(r.shard[3].p);
-        if (re > rb) { s.d_inner_keys = static_cast<const uint32_t *>(r.shard[0].p); s.d_inner_vals = static_cast<const uint32_t *>(r.shard[1].p); }
+        return HJGPU_OK;
     }
-    std::vector<hjgpu_shard_rows> rows;
-    int rc = HJGPU_OK;
-    if (host_rows) {
-        // result columns per rank: its share of the caller's capacity with a quarter of headroom; a rank that needs
-        // more says how much (rows[l].rows) and the join is run once more with exactly that
+
+    // the join of the uploaded shards; `uploading`: the uploads are in flight (the join's stages wait for their events)
+    int join(hjgpu_shard_rows *out, bool uploading)
+    {
+        const JoinOpts feed = {.from_host = uploading, .slice_events = uploading};
+        if (algorithm == 2) return cpra_join(c, shards.data(), out, pp, HOST_CPRA_SLICES, result, stats, feed);
+        return replicated_join(c, algorithm, shards.data(), out, 0, pp, np, result, stats, feed);
+    }
+
+    // result columns per rank: its share of the caller's capacity with a quarter of headroom; a rank that needs
+    // more says how much (rows[l].rows) and the join is run once more with exactly that
+    int join_into_row_columns()
+    {
+        int rc = HJGPU_OK;
         rows.resize((size_t)G);
         const size_t bs = host_rows->capacity >= (64u << 20) ? 65536 : 1024;
         for (int attempt = 0; attempt < 2; ++attempt) {
@@ -2153,28 +2366,30 @@ static int join_host_multi_impl(hjgpu_comm *c, int algorithm,
                 o.d_inner_vals = static_cast<uint32_t *>(r.rows_col[2].p);
                 o.capacity = cap; o.block_size = bs;
             }
-            if (algorithm == 2) rc = cpra_join(c, shards.data(), rows.data(), pp, HOST_CPRA_SLICES, result, stats, attempt == 0, attempt == 0);
-            else rc = replicated_join(c, algorithm, shards.data(), rows.data(), 0, pp, np, result, stats, attempt == 0);
+            rc = join(rows.data(), attempt == 0);
             if (rc != HJGPU_EOVERFLOW) break;
         }
-    } else {
-        if (algorithm == 2) rc = cpra_join(c, shards.data(), nullptr, pp, HOST_CPRA_SLICES, result, stats, true, true);
-        else rc = replicated_join(c, algorithm, shards.data(), nullptr, 0, pp, np, result, stats, true);
+        return rc;
     }
-    if (rc != HJGPU_OK) { if (!c->broken) (void)sync_all(c); return rc; }
-    if (stats) {
-        // local rank 0: how long its columns took to arrive, and whether its first join kernel started before that
+
+    // local rank 0: how long its columns took to arrive, and whether its first join kernel started before that
+    int upload_stats()
+    {
+        if (!stats) return HJGPU_OK;
         Rank &r = c->ranks[0];
         HIPM(c, hipSetDevice(r.device));
         stats->ms_upload = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count() - stats->ms_wall;
         if (stats->ms_upload < 0) stats->ms_upload = 0;
         // > 0: the join's first kernel was on the device this long BEFORE the last byte of the upload arrived
         stats->ms_overlap = elapsed(r.ev_t0, r.ev_t1);
+        return HJGPU_OK;
     }
-    if (host_rows) {
+
+    // concatenation = result: rank g's rows follow the rows of the ranks before it
+    int download_rows()
+    {
         if (result->count > host_rows->capacity)
             return cfail(c, HJGPU_EOVERFLOW, "hjgpu_join_host_rows_multi: the result has more rows than rows->capacity (see result->count)");
-        // concatenation = result: rank g's rows follow the rows of the ranks before it
         const auto d0 = std::chrono::steady_clock::now();
         u64 at = 0;
         for (int g = 0; g < G; ++g) {
@@ -2189,8 +2404,29 @@ static int join_host_multi_impl(hjgpu_comm *c, int algorithm,
         CHKM(sync_all(c));
         if (at != result->count) return cfail(c, HJGPU_EHIP, "internal: the ranks' rows do not add up to the global count");
         if (stats) stats->join.ms_download = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - d0).count();
+        return HJGPU_OK;
     }
-    return HJGPU_OK;
+};
+
+}  // namespace
+
+static int join_host_multi_impl(hjgpu_comm *c, int algorithm,
+                                const uint32_t *ik, const uint32_t *iv, size_t inner,
+                                const uint32_t *ok, const uint32_t *ov, size_t outer,
+                                const hjgpu_phj_params *pp, const hjgpu_npj_params *np,
+                                const hjgpu_host_rows *host_rows, hjgpu_result *result, hjgpu_multi_stats *stats)
+{
+    if (!c || algorithm < 0 || algorithm > 2) return HJGPU_EINVAL;
+    HostJoin h{c, algorithm, ik, iv, inner, ok, ov, outer, pp, np, host_rows, result, stats};
+    CHKM(h.check());
+    bool done = false;
+    CHKM(h.batched_rows(&done));
+    if (done) return HJGPU_OK;
+    CHKM(h.upload_shards());
+    const int rc = host_rows ? h.join_into_row_columns() : h.join(nullptr, true);
+    if (rc != HJGPU_OK) { if (!c->broken) (void)sync_all(c); return rc; }
+    CHKM(h.upload_stats());
+    return host_rows ? h.download_rows() : HJGPU_OK;
 }
 
 int hjgpu_join_host_multi(hjgpu_comm *c, int algorithm,

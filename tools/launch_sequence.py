@@ -3,6 +3,11 @@
     rocprofv3 --kernel-trace --output-format csv -d DIR -- python tools/launch_sequence.py
     python tools/launch_sequence.py --summarise DIR/.../*_kernel_trace.csv > profiles/r14_launch_sequence.txt
 
+With --multi in both forms: the roads of the multi-GPU joins instead ("Roads of a CPRA step"), on ONE device - the
+loopback transport puts the ranks of a world of 2 or 3 on device 0, RCCL runs at world 1 - through HjComm.  With more than one rank
+every rank enqueues from its own host thread, so the order between the ranks' launches is timing: those roads' lines are printed sorted.
+tests/test_gpu_cpra_roads.py checks what they compute.
+
 The first form runs the roads against the library HJGPU_LIBRARY names (default: the tree's own).  One column_sums_kernel launch
 precedes every road, so the second form can cut the kernel trace into roads and print, per road, the ordered list of
 (kernel, grid, workgroup, LDS bytes).  Two builds enqueue the same work exactly when their lists are equal (plain diff).
@@ -24,6 +29,7 @@ INNER, OUTER, OUTER_BATCHED = 5_003, 40_009, 7_300_003      # (the batched road 
 BATCH_TUPLES = 300_000                                      # test_gpu_shapes.py test_batched_probe_side_partitioning
 GROUP_FROM, GROUP_INNER = 1000, 5000                        # test_gpu_grouped.py: 2 groups of the 5 003 build rows
 FACTOR1 = 0x2C1B3C6D                                        # the exchange-level hash of the pre-partitioned road
+GROUP_INNER_SHARE = 1250                                    # a rank's share of the build side at world 2 (2 501 rows): 2 groups or more
 DELIMITER = "column_sums_kernel"
 
 
@@ -235,6 +241,136 @@ def roads():
     return table
 
 
+# ---- the multi-GPU roads: fn(MultiRun) -> {"agg": aggregates, "rows": (keys, outer_vals, inner_vals) or None, "stats": hjgpu_multi_stats} ---
+def bounds(n, parts, alignment=16):
+    """thread_beg / thread_end (npj.cpp:516-529): how the hosts cut a relation into the ranks' chunks"""
+    part = (n // parts) & ~(alignment - 1)
+    return [(part * t, n if t + 1 == parts else part * (t + 1)) for t in range(parts)]
+
+
+class MultiRun:
+    """one road's communicator (fresh buffers), relations and device columns"""
+
+    def __init__(self, world, transport, rel, comm_options=(), ctx_options=()):
+        import hash_join_codes_knl_amd as H
+        self.H, self.made, self.rel = H, [], rel
+        self.comm = H.HjComm.local(world, [0] * world, H.TRANSPORT_RCCL if transport == "rccl" else H.TRANSPORT_LOOPBACK)
+        for ctx in self.comm.ctx:
+            for k, v in (("placement", 1),) + tuple(ctx_options):
+                ctx.set_option(k, v)
+        for k, v in comm_options:
+            self.comm.set_option(k, v)
+
+    def col(self, g, a):
+        c = self.comm.ctx[g].column(np.concatenate([a, np.zeros(4, a.dtype)]))
+        self.made.append(c)
+        return c
+
+    def chunked(self, rcuts=None, scuts=None):
+        """both relations in chunks, one per rank"""
+        ik, iv, ok, ov = self.rel
+        G = self.comm.nranks
+        rcuts, scuts = rcuts or bounds(len(ik), G), scuts or bounds(len(ok), G)
+        return [(self.col(g, ik[rb:re]), self.col(g, iv[rb:re]), re - rb, self.col(g, ok[sb:se]), self.col(g, ov[sb:se]), se - sb)
+                for g, ((rb, re), (sb, se)) in enumerate(zip(rcuts, scuts))]
+
+    def replicated(self, root=0):
+        """the build side on the root, the probe side in chunks"""
+        ik, iv, ok, ov = self.rel
+        return [(self.col(g, ik) if g == root else None, self.col(g, iv) if g == root else None, len(ik), self.col(g, ok[sb:se]), self.col(g, ov[sb:se]), se - sb)
+                for g, (sb, se) in enumerate(bounds(len(ok), self.comm.nranks))]
+
+    def rows_out(self, shards, rows, block=256):
+        outs = []
+        for g, sh in enumerate(shards):
+            cap = self.comm.ctx[g].output_capacity(1, sh[5], rows, block)
+            outs.append(tuple(self.col(g, np.zeros(max(cap, 4), np.uint32)) for _ in range(3)) + (cap, block))
+        return outs
+
+    def close(self):
+        for c in self.made:
+            c.free()
+        self.comm.close()
+
+
+def mroad_cpra(m, params=None, cuts=None):
+    agg, st = m.comm.cpra_multi(m.chunked(*(cuts or ())), params or prm(), 3)
+    return {"agg": agg, "stats": st}
+
+
+def mroad_cpra_rows(m):
+    """every rank's columns hold the whole result: a rank's rows are the first `counts[g]` of its columns"""
+    shards = m.chunked()
+    outs = m.rows_out(shards, 2 * len(m.rel[2]))
+    agg, st, counts = m.comm.cpra_multi_rows(shards, outs, prm(), 3)
+    cols = tuple(np.concatenate([o[i].download(n) for o, n in zip(outs, counts)]) for i in range(3))
+    return {"agg": agg, "rows": cols, "stats": st}
+
+
+def mroad_replicated(m, algorithm):
+    shards = m.replicated()
+    agg, st = m.comm.phj_multi(shards, 0, prm()) if algorithm else m.comm.npj_multi(shards, 0)
+    return {"agg": agg, "stats": st}
+
+
+def mroad_join_host(m, algorithm, rows):
+    ik, iv, ok, ov = m.rel
+    if not rows:
+        agg, st = m.comm.join_host_multi(algorithm, ik, iv, ok, ov, prm())
+        return {"agg": agg, "stats": st}
+    agg, st, cols = m.comm.join_host_rows_multi(algorithm, ik, iv, ok, ov, 2 * len(ok), prm())
+    return {"agg": agg, "rows": cols, "stats": st}
+
+
+def _one_rank_empty(world=3):
+    """rank 1 holds nothing of either relation"""
+    def cuts(n):
+        (b0, e0), (_, e1) = bounds(n, world - 1)
+        return [(b0, e0), (e0, e0), (e0, e1)]
+    return cuts(INNER), cuts(OUTER)
+
+
+MULTI_NAMES = ["20a cpra loopback 2 in place", "20b cpra loopback 2 exchange_in_place 0", "20c cpra loopback 2 cpra_fused_counts 0",
+               "20d cpra loopback 2 cpra_two_level 1", "20e cpra loopback 2 grouped", "20f cpra loopback 2 rows", "21 cpra loopback 3 one rank empty",
+               "22a cpra rccl 1 cpra_k 24", "22b cpra rccl 1 self_via_rccl", "23a join_host_multi cpra", "23b join_host_multi phj",
+               "23c join_host_rows_multi cpra", "23d join_host_rows_multi phj", "24a phj_multi loopback 2", "24b npj_multi loopback 2"]
+# more than one rank: the ranks' host threads enqueue side by side, the summary sorts the road's lines
+SORTED = {n for n in MULTI_NAMES if not n.startswith("22")}
+
+
+def multi_roads():
+    """[(name, world, transport, communicator options, context options, fn)] in the order of MULTI_NAMES; all on the relations of roads()"""
+    import hash_join_codes_knl_amd as H
+    grouped = (("group_from", GROUP_FROM), ("group_always", 1), ("group_inner", GROUP_INNER_SHARE))
+    table = [
+        ("20a cpra loopback 2 in place", 2, "loopback", (), (), mroad_cpra),
+        ("20b cpra loopback 2 exchange_in_place 0", 2, "loopback", (("exchange_in_place", 0),), (), mroad_cpra),
+        ("20c cpra loopback 2 cpra_fused_counts 0", 2, "loopback", (("cpra_fused_counts", 0),), (), mroad_cpra),
+        ("20d cpra loopback 2 cpra_two_level 1", 2, "loopback", (("cpra_two_level", 1),), (), mroad_cpra),
+        ("20e cpra loopback 2 grouped", 2, "loopback", (("cpra_grouped", 2),), grouped, lambda m: mroad_cpra(m, H.PhjParams())),
+        ("20f cpra loopback 2 rows", 2, "loopback", (), (), mroad_cpra_rows),
+        ("21 cpra loopback 3 one rank empty", 3, "loopback", (), (), lambda m: mroad_cpra(m, cuts=_one_rank_empty())),
+        ("22a cpra rccl 1 cpra_k 24", 1, "rccl", (("cpra_k", 24),), (), mroad_cpra),
+        ("22b cpra rccl 1 self_via_rccl", 1, "rccl", (("self_via_rccl", 1),), (), mroad_cpra),
+        ("23a join_host_multi cpra", 2, "loopback", (), (), lambda m: mroad_join_host(m, 2, False)),
+        ("23b join_host_multi phj", 2, "loopback", (), (), lambda m: mroad_join_host(m, 1, False)),
+        ("23c join_host_rows_multi cpra", 2, "loopback", (), (), lambda m: mroad_join_host(m, 2, True)),
+        ("23d join_host_rows_multi phj", 2, "loopback", (), (), lambda m: mroad_join_host(m, 1, True)),
+        ("24a phj_multi loopback 2", 2, "loopback", (), (), lambda m: mroad_replicated(m, 1)),
+        ("24b npj_multi loopback 2", 2, "loopback", (), (), lambda m: mroad_replicated(m, 0)),
+    ]
+    assert [t[0] for t in table] == MULTI_NAMES
+    return table
+
+
+def run_multi_road(world, transport, comm_options, ctx_options, fn, rel=None):
+    m = MultiRun(world, transport, rel or relations(), comm_options, ctx_options)
+    try:
+        return fn(m)
+    finally:
+        m.close()
+
+
 def run_road(options, rel, fn):
     r = Run(rel, options)
     try:
@@ -243,7 +379,7 @@ def run_road(options, rel, fn):
         r.close()
 
 
-def main():
+def main(multi=False):
     try:
         import torch                    # (its own HIP runtime has to initialise first where both live in one process, as in bench.py)
         torch.cuda.init()
@@ -253,7 +389,13 @@ def main():
     print("library", H.build.lib_path(), "hash", H.library_hash())
     with H.HjGpu(0) as mark:
         d = mark.column(np.arange(1024, dtype=np.uint32))
-        for name, options, rel, fn in roads():
+        for name, world, transport, comm_options, ctx_options, fn in (multi_roads() if multi else ()):
+            mark.column_sums(d, 1024, 1, 3)              # the delimiter in front of the road
+            mark.synchronize()
+            got = run_multi_road(world, transport, comm_options, ctx_options, fn)
+            st = got["stats"]
+            print("%-40s agg %s joins %d self_copies %d groups %d" % (name, got["agg"], st["joins"], st["self_copies"], st["join"]["groups"]), flush=True)
+        for name, options, rel, fn in (() if multi else roads()):
             mark.column_sums(d, 1024, 1, 3)              # the delimiter in front of the road
             mark.synchronize()
             got = run_road(options, rel, fn)
@@ -262,26 +404,30 @@ def main():
         d.free()
 
 
-def summarise(path):
+def summarise(path, names=NAMES):
     """the kernel trace of main() -> one block per road"""
     with open(path, newline="") as fh:
         trace = sorted(csv.DictReader(fh), key=lambda t: int(t["Dispatch_Id"]))
-    road = -1
+    blocks = []
     for t in trace:
         kernel = t["Kernel_Name"]
         if DELIMITER in kernel:
-            road += 1
-            print("\n== %s" % (NAMES[road] if road < len(NAMES) else "road %d" % road))
+            blocks.append((names[len(blocks)] if len(blocks) < len(names) else "road %d" % len(blocks), []))
             continue
-        if road < 0:
+        if not blocks:
             continue
         grid = "x".join(t["Grid_Size_" + a] for a in "XYZ")
         wg = "x".join(t["Workgroup_Size_" + a] for a in "XYZ")
-        print("%s grid %s wg %s lds %s" % (kernel, grid, wg, t.get("LDS_Block_Size", t.get("Group_Segment_Size", "?"))))
+        blocks[-1][1].append("%s grid %s wg %s lds %s" % (kernel, grid, wg, t.get("LDS_Block_Size", t.get("Group_Segment_Size", "?"))))
+    for name, lines in blocks:
+        print("\n== %s%s" % (name, " (sorted)" if name in SORTED else ""))
+        print("\n".join(sorted(lines) if name in SORTED else lines))
 
 
 if __name__ == "__main__":
-    if len(sys.argv) == 3 and sys.argv[1] == "--summarise":
-        summarise(sys.argv[2])
+    args = [a for a in sys.argv[1:] if a != "--multi"]
+    multi = "--multi" in sys.argv[1:]
+    if len(args) == 2 and args[0] == "--summarise":
+        summarise(args[1], MULTI_NAMES if multi else NAMES)
     else:
-        main()
+        main(multi)
