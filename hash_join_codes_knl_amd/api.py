@@ -38,6 +38,7 @@ EXPORTS = [
     "hjgpu_npj_lookup", "hjgpu_npj_lookup_async", "hjgpu_npj_lookup_table", "hjgpu_lookup", "hjgpu_lookup_async",
     "hjgpu_lookup_selected", "hjgpu_lookup_selected_async", "hjgpu_npj_lookup_table_selected",
     "hjgpu_compact_selected", "hjgpu_compact_selected_async",
+    "hjgpu_group_sum", "hjgpu_group_sum_async",
     "hjgpu_npj", "hjgpu_phj", "hjgpu_cpra",
     "hjgpu_npj_async", "hjgpu_phj_async", "hjgpu_cpra_async", "hjgpu_phj_overlapped_async",
     "hjgpu_phj_build", "hjgpu_phj_probe", "hjgpu_phj_probe_async",
@@ -267,6 +268,9 @@ def load_library(build_if_missing=True):
     L.hjgpu_lookup_selected_async.argtypes = [vp, vp, vp, sz, vp, sz, C.POINTER(NpjParams), vp, vp, vp, vp, vp]
     L.hjgpu_compact_selected.argtypes = [vp, vp, sz, u32, C.POINTER(vp), C.POINTER(vp), vp, sz, u64p, vp]
     L.hjgpu_compact_selected_async.argtypes = [vp, vp, sz, u32, C.POINTER(vp), C.POINTER(vp), vp, sz, vp, vp]
+    group = [vp, vp, sz, u32, C.POINTER(vp), u32, C.POINTER(vp), C.POINTER(vp), vp, C.POINTER(vp), sz]
+    L.hjgpu_group_sum.argtypes = group + [u64p, vp]
+    L.hjgpu_group_sum_async.argtypes = group + [vp, vp]
     L.hjgpu_npj_lookup_table_selected.argtypes = [vp, vp, sz, vp, sz, u32, vp, vp, vp, C.POINTER(Result), vp]
     join = [vp, vp, vp, sz, vp, vp, sz]
     L.hjgpu_npj.argtypes = join + [C.POINTER(NpjParams), C.POINTER(Result), C.POINTER(Output), vp]
@@ -413,7 +417,8 @@ class HjGpu:
     def counter(self, name):
         """hjgpu_get_counter: "probe_fallbacks" (claimed probe sides done again exactly), "probe_exact" (1: exact path from now on),
         "lookup_lds_rows" (largest build side that hjgpu_lookup answers from LDS tables; 0 under option no_broadcast),
-        "compact_ranges" / "compact_chunk_rows" (compact_selected's geometry: its ranges, and the rows of a chunk)."""
+        "compact_ranges" / "compact_chunk_rows" (compact_selected's geometry: its ranges, and the rows of a chunk),
+        "group_lds_groups" (the distinct groups a workgroup's LDS table of group_sum holds before further ones go to device memory)."""
         v = C.c_uint64()
         self._check(self.lib.hjgpu_get_counter(self.handle, name.encode(), C.byref(v)))
         return v.value
@@ -575,6 +580,45 @@ class HjGpu:
         ncols, ins, outs, capacity = self._compact_args(cols_in, cols_out, rows_out, capacity)
         self._check(self.lib.hjgpu_compact_selected_async(self.handle, self._ptr(select_bits), n, ncols, ins, outs, self._ptr(rows_out),
                                                           capacity, self._ptr(d_count), stream))
+
+    # ---- grouped aggregation: GROUP BY keys COUNT(*), SUM(vals) over the selected rows -------------------------------------------
+    def _group_args(self, keys_in, vals_in, keys_out, sums_out, counts_out, capacity):
+        keys_in, vals_in, keys_out, sums_out = list(keys_in or ()), list(vals_in or ()), list(keys_out or ()), list(sums_out or ())
+        if len(keys_in) != len(keys_out) or len(vals_in) != len(sums_out):
+            raise ValueError("group_sum: %d key columns with %d outputs, %d measure columns with %d outputs"
+                             % (len(keys_in), len(keys_out), len(vals_in), len(sums_out)))
+        if capacity is None:                # the shortest output
+            outs = keys_out + sums_out + ([counts_out] if counts_out is not None else [])
+            if not all(isinstance(c, DeviceColumn) for c in outs):
+                raise ValueError("group_sum: capacity is needed with outputs given as plain pointers")
+            capacity = min([c.n for c in outs], default=0)
+
+        def arr(cols):
+            return (C.c_void_p * len(cols))(*[self._ptr(c) for c in cols]) if cols else None
+        return (len(keys_in), arr(keys_in), len(vals_in), arr(vals_in), arr(keys_out), self._ptr(counts_out), arr(sums_out), capacity)
+
+    def group_sum(self, select_bits, n, keys_in, vals_in, keys_out, sums_out, counts_out=None, capacity=None, stream=None):
+        """hjgpu_group_sum: the rows whose bit is set in select_bits (match_bits' layout; None: every row) grouped by the tuple of the one
+        or two keys_in columns; for every distinct tuple one index j < J with keys_out[c][j] = the tuple, counts_out[j] (uint64; None: no
+        counts) = its rows, sums_out[v][j] (uint64) = the sum of vals_in[v] over them.  The order of the groups is unspecified.  Returns J;
+        J > capacity (default: the shortest output) raises HjGpuError(HJGPU_EOVERFLOW) that carries .count, a lower bound of J that
+        exceeds capacity; the outputs are unspecified then."""
+        nk, kin, nv, vin, kout, cout, sout, capacity = self._group_args(keys_in, vals_in, keys_out, sums_out, counts_out, capacity)
+        count = C.c_uint64()
+        st = self.lib.hjgpu_group_sum(self.handle, self._ptr(select_bits), n, nk, kin, nv, vin, kout, cout, sout, capacity,
+                                      C.byref(count), stream)
+        if st != OK:
+            e = HjGpuError(st, "%s: %s" % (self.lib.hjgpu_status_string(st).decode(), self.lib.hjgpu_last_error(self.handle).decode()))
+            e.count = count.value
+            raise e
+        return count.value
+
+    def group_sum_async(self, select_bits, n, keys_in, vals_in, keys_out, sums_out, counts_out, capacity, d_ngroups, stream=None):
+        """hjgpu_group_sum_async: enqueue only; the number of groups goes to d_ngroups (uint64 in device memory), which the caller
+        compares with capacity (None: the shortest output)"""
+        nk, kin, nv, vin, kout, cout, sout, capacity = self._group_args(keys_in, vals_in, keys_out, sums_out, counts_out, capacity)
+        self._check(self.lib.hjgpu_group_sum_async(self.handle, self._ptr(select_bits), n, nk, kin, nv, vin, kout, cout, sout, capacity,
+                                                   self._ptr(d_ngroups), stream))
 
     # ---- whole joins ------------------------------------------------------------------
     def _join(self, fn, params, rk, rv, inner, sk, sv, outer, out, stream):

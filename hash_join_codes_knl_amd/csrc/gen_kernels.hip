@@ -605,3 +605,223 @@ int hj_launch_compact(const CompactArgs &a, uint32_t ncols, hipStream_t stream)
     });
     return hipGetLastError() == hipSuccess ? HJGPU_OK : HJGPU_EHIP;
 }
+
+// ---- grouped aggregation (hjgpu_group_sum; DESIGN.md section 5 "Grouped aggregation") -------------------------------------------------
+// GROUP BY (key 0 [, key 1]) COUNT(*), SUM(measure 0 ... nvals - 1) over the rows a bitmap selects.  The tables are group_layout.hpp's: a
+// slot is the tuple in one 64-bit word, a count and four sums; a hashed slot is occupied when that word is not 0, the tuple 0 has the
+// slot behind the hashed ones.  Insert-or-find is ONE 64-bit compare-and-swap of the tuple word (ds_cmpst_rtn_b64 in LDS,
+// global_atomic_cmpswap_x2 in the merge table): a slot is never half written, so nobody waits - a claim-then-publish state word would make
+// the lanes of a wave wait for one another.  Counts and sums are 64-bit atomic adds.  The kernel has no global store at all.
+constexpr u64 GROUP_NO_SLOT = 1ull << 62;               // a row whose tuple found no slot in the merge table (the overflow word is raised)
+constexpr u64 GROUP_IN_LDS = 1ull << 63;                // a location in the workgroup's table: this bit and the slot's index
+
+// The slot of tuple t (hash h) in the workgroup's table, GROUP_NO_SLOT when the row has to go to the merge table: after LDS_PROBES slots
+// that hold other tuples, or at an empty slot once the table has claimed LDS_GROUPS hashed slots (`used` is a ticket: taken before the
+// claim and handed back when the claim fails, so the table never holds more).
+__device__ __forceinline__ u64 group_lds_slot(hj_group::Slot *tab, uint32_t *used, u64 t, u64 h)
+{
+    using namespace hj_group;
+    if (t == 0) return GROUP_IN_LDS | LDS_SLOTS;
+    uint32_t s = lds_home(h);
+#pragma unroll 1
+    for (uint32_t p = 0; p < LDS_PROBES; ++p) {
+        u64 cur = __hip_atomic_load(&tab[s].tuple, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        if (cur == 0) {
+            if (__hip_atomic_load(used, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) >= LDS_GROUPS) return GROUP_NO_SLOT;   // (a broadcast read: no ticket traffic once the table is full)
+            if (atomicAdd(used, 1u) >= LDS_GROUPS) { atomicSub(used, 1u); return GROUP_NO_SLOT; }
+            cur = atomicCAS(&tab[s].tuple, 0ull, t);                    // ds_cmpst_rtn_b64
+            if (cur == 0) return GROUP_IN_LDS | s;
+            atomicSub(used, 1u);
+        }
+        if (cur == t) return GROUP_IN_LDS | s;
+        s = (s + 1) & (LDS_SLOTS - 1);
+    }
+    return GROUP_NO_SLOT;
+}
+
+// The slot of tuple t in the merge table: linear probing bounded by the slot count.  A tuple that finds the table full raises the
+// overflow word; whoever sees it raised gives up at once - the call has overflowed, what it leaves below capacity is unspecified, and
+// the full table is the lower bound of the group count - so an overflowing call does not walk a full table once per row.
+__device__ __forceinline__ u64 group_merge_slot(const GroupArgs &a, u64 t, u64 h)
+{
+    if (t == 0) return a.merge_mask + 1;
+    if (__hip_atomic_load(a.overflow, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return GROUP_NO_SLOT;
+    u64 s = h & a.merge_mask;
+    for (u64 p = 0; p <= a.merge_mask; ++p) {
+        u64 cur = __hip_atomic_load(&a.merge[s].tuple, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (cur == 0) cur = atomicCAS(&a.merge[s].tuple, 0ull, t);
+        if (cur == 0 || cur == t) return s;
+        s = (s + 1) & a.merge_mask;
+    }
+    atomicOr(a.overflow, 1u);
+    return GROUP_NO_SLOT;
+}
+
+// adds x to word `word` (0: the count, 1 + c: sum c) of the slot at `loc`
+__device__ __forceinline__ void group_add(hj_group::Slot *tab, const GroupArgs &a, u64 loc, uint32_t word, u64 x)
+{
+    if (loc & GROUP_IN_LDS) __hip_atomic_fetch_add(&tab[(uint32_t)loc].count + word, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);   // ds_add_u64
+    else if (loc != GROUP_NO_SLOT) atomicAdd(&a.merge[loc].count + word, x);                   // global_atomic_add_x2
+}
+
+// One persistent grid.  An iteration is BATCH wave trips of hj_lookup.hpp's layout (lane L owns rows 4 L ... 4 L + 3 of a trip): the mask
+// words first, then key column 0 (lookup_fetch), then key column 1 and, one after the other, the measure columns for the lanes that have a
+// selected row - a group of 8 lanes whose mask word is 0 loads nothing from any column; everything non-temporal; the last, partial vector
+// of a column is loaded whole and masked, as lookup_fetch does.  A lane folds those of its four rows that carry the same tuple (cls: for
+// every row the set of rows it leads, a nibble each), finds the leaders' slots - the workgroup's table, else the merge table - and adds the
+// counts; then, per measure column (nvals is a uniform run-time bound), it loads the column and adds each leader's sum to its slot.  At the
+// end the workgroup adds its occupied slots to the merge table.  No workgroup waits for another.
+template <int NKEYS, bool SEL>
+__global__ __launch_bounds__(hj_group::BLOCK) void group_sum_kernel(GroupArgs a)
+{
+    using namespace hj_group;
+    constexpr int BATCH = 2, ROWS = 4 * BATCH;
+    __shared__ Slot tab[LDS_SLOTS + 1];
+    __shared__ uint32_t used;
+    const uint32_t tid = threadIdx.x;
+    {
+        u64 *raw = reinterpret_cast<u64 *>(tab);
+        for (uint32_t i = tid; i < (LDS_SLOTS + 1) * (uint32_t)(sizeof(Slot) / 8); i += BLOCK) raw[i] = 0;
+        if (tid == 0) used = 0;
+    }
+    __syncthreads();
+    const uint4 *k4 = reinterpret_cast<const uint4 *>(a.keys[0]);
+    const uint4 *k4b = reinterpret_cast<const uint4 *>(a.keys[NKEYS - 1]);
+    const u64 n = a.n, nvec = (n + 3) >> 2, stride = (u64)gridDim.x * BLOCK;
+    const uint32_t nvals = a.nvals;
+    for (u64 v0 = (u64)blockIdx.x * BLOCK + (tid & ~63u); v0 < nvec; v0 += stride * BATCH) {
+        uint32_t nib[BATCH];
+        uint4 k0[BATCH], k1[BATCH];
+        lookup_fetch<SEL, BATCH, true>(a.select_bits, k4, v0, stride, n, nib, k0);
+#pragma unroll
+        for (int u = 0; u < BATCH; ++u) {
+            k1[u] = make_uint4(0, 0, 0, 0);
+            if constexpr (NKEYS == 2) { if (nib[u]) k1[u] = hj_load_nt(k4b + v0 + (u64)u * stride + hj_lane()); }
+        }
+        // the fold: row q = 4 u + j of the lane leads the rows of its trip that carry its tuple and that no earlier row leads
+        u64 t[ROWS], loc[ROWS];
+        uint32_t cls = 0, lead = 0;                     // cls: a nibble per row, the rows (of its trip) it leads; lead: the rows that lead any
+#pragma unroll
+        for (int u = 0; u < BATCH; ++u) {
+            t[4 * u] = tuple_of(k0[u].x, k1[u].x); t[4 * u + 1] = tuple_of(k0[u].y, k1[u].y);
+            t[4 * u + 2] = tuple_of(k0[u].z, k1[u].z); t[4 * u + 3] = tuple_of(k0[u].w, k1[u].w);
+            uint32_t left = nib[u];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                loc[4 * u + j] = GROUP_NO_SLOT;
+                uint32_t m = 0;
+#pragma unroll
+                for (int i = j; i < 4; ++i) if (((left >> i) & 1u) && t[4 * u + i] == t[4 * u + j]) m |= 1u << i;
+                if (!((left >> j) & 1u)) m = 0;
+                left &= ~m;
+                cls |= m << (4 * (4 * u + j));
+                lead |= (m ? 1u : 0u) << (4 * u + j);
+            }
+        }
+        // the leaders' slots and counts: one copy of the probe code, whichever row it serves
+        for (uint32_t work = lead; work; work &= work - 1) {
+            const uint32_t q = __ffs(work) - 1;
+            u64 tu[4] = {t[0], t[1], t[2], t[3]};       // the trip's, then the row's
+#pragma unroll
+            for (int u = 1; u < BATCH; ++u)
+                if ((int)(q >> 2) == u) { tu[0] = t[4 * u]; tu[1] = t[4 * u + 1]; tu[2] = t[4 * u + 2]; tu[3] = t[4 * u + 3]; }
+            const uint32_t qj = q & 3u;
+            const u64 tq = qj == 0 ? tu[0] : qj == 1 ? tu[1] : qj == 2 ? tu[2] : tu[3];
+            const u64 h = mix(tq);
+            u64 at = group_lds_slot(tab, &used, tq, h);
+            if (at == GROUP_NO_SLOT) at = group_merge_slot(a, tq, h);
+            group_add(tab, a, at, 0, (u64)__popc((cls >> (4 * q)) & 15u));
+#pragma unroll
+            for (int r = 0; r < ROWS; ++r) loc[r] = q == r ? at : loc[r];
+        }
+        for (uint32_t c = 0; c < nvals; ++c) {
+            const uint4 *x4 = reinterpret_cast<const uint4 *>(a.vals[c]);
+            uint4 x[BATCH];
+#pragma unroll
+            for (int u = 0; u < BATCH; ++u) {
+                x[u] = make_uint4(0, 0, 0, 0);
+                if (nib[u]) x[u] = hj_load_nt(x4 + v0 + (u64)u * stride + hj_lane());
+            }
+            for (uint32_t work = lead; work; work &= work - 1) {
+                const uint32_t q = __ffs(work) - 1, m = (cls >> (4 * q)) & 15u;
+                uint4 xq = x[0];
+#pragma unroll
+                for (int u = 1; u < BATCH; ++u) if ((int)(q >> 2) == u) xq = x[u];
+                u64 at = loc[0];
+#pragma unroll
+                for (int r = 1; r < ROWS; ++r) at = q == r ? loc[r] : at;
+                const u64 sum = (u64)((m & 1u) ? xq.x : 0u) + ((m & 2u) ? xq.y : 0u) + ((m & 4u) ? xq.z : 0u) + ((m & 8u) ? xq.w : 0u);
+                group_add(tab, a, at, 1 + c, sum);
+            }
+        }
+    }
+    __syncthreads();
+    for (uint32_t i = tid; i <= LDS_SLOTS; i += BLOCK) {
+        const u64 t = tab[i].tuple, cnt = tab[i].count;
+        if (i < LDS_SLOTS ? t != 0 : cnt != 0) {
+            const u64 at = group_merge_slot(a, t, mix(t));
+            if (at != GROUP_NO_SLOT) {
+                atomicAdd(&a.merge[at].count, cnt);
+                for (uint32_t c = 0; c < nvals; ++c) atomicAdd(&a.merge[at].sums[c], tab[i].sums[c]);
+            }
+        }
+    }
+}
+
+// The occupied slots of the merge table go to the dense outputs, a wave's through one atomic add to the cursor, which is the count word
+// itself (0 before the launch): behind the launch it holds the number of occupied slots - the group count J, or, when the overflow word
+// was raised, the full table: a lower bound of J that is greater than capacity (the table has at least 2 * capacity slots).  Rows at
+// capacity and beyond are counted and not written.
+__global__ __launch_bounds__(256) void group_emit_kernel(GroupEmitArgs a)
+{
+    const uint32_t lane = hj_lane();
+    const u64 total = a.slots + 1, stride = (u64)gridDim.x * 256;
+    for (u64 i0 = (u64)blockIdx.x * 256 + (threadIdx.x & ~63u); i0 < total; i0 += stride) {
+        const u64 i = i0 + lane;
+        u64 t = 0, cnt = 0;
+        if (i < total) { t = a.merge[i].tuple; cnt = a.merge[i].count; }
+        const bool occ = i < a.slots ? t != 0 : i == a.slots && cnt != 0;
+        const u64 vote = __ballot(occ);
+        if (vote == 0) continue;
+        u64 base = 0;
+        if (lane == 0) base = atomicAdd(a.d_ngroups, (u64)__popcll(vote));
+        base = hj_uniform(base);
+        const u64 j = base + __popcll(vote & ((1ull << lane) - 1ull));
+        if (occ && j < a.capacity) {
+            hj_store(a.keys_out[0] + j, (uint32_t)t);
+            if (a.nkeys > 1) hj_store(a.keys_out[1] + j, (uint32_t)(t >> 32));
+            if (a.counts_out) hj_store(a.counts_out + j, cnt);
+#pragma unroll
+            for (uint32_t c = 0; c < hj_group::MAX_VALS; ++c)
+                if (c < a.nvals) hj_store(a.sums_out[c] + j, a.merge[i].sums[c]);
+        }
+    }
+}
+
+// one workgroup per compute unit (its table takes most of the unit's LDS), no more than the rows have wave trips for
+int hj_launch_group_sum(const GroupArgs &a, int cus, hipStream_t stream)
+{
+    using namespace hj_group;
+    if (a.n == 0) return HJGPU_OK;
+    if (a.nkeys < 1 || a.nkeys > MAX_KEYS || a.nvals > MAX_VALS || !a.merge || !a.overflow || (a.merge_mask & (a.merge_mask + 1)) || cus < 1) return HJGPU_EINVAL;
+    uintptr_t all = (uintptr_t)a.select_bits;
+    for (uint32_t c = 0; c < a.nkeys; ++c) { if (!a.keys[c]) return HJGPU_EINVAL; all |= (uintptr_t)a.keys[c]; }
+    for (uint32_t c = 0; c < a.nvals; ++c) { if (!a.vals[c]) return HJGPU_EINVAL; all |= (uintptr_t)a.vals[c]; }
+    if (all & 15) return HJGPU_EINVAL;
+    const u64 nvec = (a.n + 3) >> 2, need = (nvec + BLOCK - 1) / BLOCK;
+    const dim3 grid((uint32_t)std::min<u64>(need, (u64)cus));
+    hj_with_bool(a.select_bits != nullptr, [&](auto sel) {
+        constexpr bool S = decltype(sel)::value;
+        if (a.nkeys == 1) hipLaunchKernelGGL((group_sum_kernel<1, S>), grid, dim3(BLOCK), 0, stream, a);
+        else hipLaunchKernelGGL((group_sum_kernel<2, S>), grid, dim3(BLOCK), 0, stream, a);
+    });
+    return hipGetLastError() == hipSuccess ? HJGPU_OK : HJGPU_EHIP;
+}
+
+int hj_launch_group_emit(const GroupEmitArgs &a, int cus, hipStream_t stream)
+{
+    if (!a.merge || !a.d_ngroups || a.nkeys < 1 || a.nkeys > hj_group::MAX_KEYS || a.nvals > hj_group::MAX_VALS || cus < 1) return HJGPU_EINVAL;
+    const u64 need = (a.slots + 1 + 255) / 256;
+    hipLaunchKernelGGL(group_emit_kernel, dim3((uint32_t)std::min<u64>(need, (u64)cus * 8)), dim3(256), 0, stream, a);
+    return hipGetLastError() == hipSuccess ? HJGPU_OK : HJGPU_EHIP;
+}

@@ -6,6 +6,7 @@
 #include <type_traits>
 #include "../../include/hjgpu.h"
 #include "compact_layout.hpp"
+#include "group_layout.hpp"
 
 typedef unsigned long long u64;
 
@@ -493,6 +494,34 @@ struct CompactArgs {
 int hj_launch_compact_count(const uint32_t *select_bits, const hj_compact::Layout &lay, u64 *counts, hipStream_t stream);
 int hj_launch_compact(const CompactArgs &a, uint32_t ncols, hipStream_t stream);
 int hj_launch_compact_total(const u64 *counts, uint32_t ranges, u64 *d_count, hipStream_t stream);
+
+// Grouped aggregation (hjgpu_group_sum*, gen_kernels.hip; DESIGN.md section 5 "Grouped aggregation"): the tables of group_layout.hpp.
+// hj_launch_group_sum: one persistent grid; every selected row (select_bits NULL: every row) of the key and measure columns is added to
+// its tuple's slot of the merge table - `merge` holds merge_mask + 1 hashed slots and the slot of tuple 0 behind them, all zero before the
+// launch, as is *overflow, which is raised when a tuple finds no slot.  hj_launch_group_emit: the occupied slots go to the dense outputs
+// (rows below capacity only) and their number is added to *d_ngroups, which is 0 before the launch.  All columns 16-byte aligned.
+struct GroupArgs {
+    const uint32_t *select_bits;         // NULL: every row
+    u64 n;
+    const uint32_t *keys[hj_group::MAX_KEYS];
+    const uint32_t *vals[hj_group::MAX_VALS];
+    uint32_t nkeys, nvals;
+    hj_group::Slot *merge;
+    u64 merge_mask;
+    uint32_t *overflow;
+};
+struct GroupEmitArgs {
+    const hj_group::Slot *merge;
+    u64 slots;                           // the hashed slots; the slot of tuple 0 is merge[slots]
+    uint32_t nkeys, nvals;
+    uint32_t *keys_out[hj_group::MAX_KEYS];
+    u64 *counts_out;                     // NULL: no counts
+    u64 *sums_out[hj_group::MAX_VALS];
+    u64 capacity;
+    u64 *d_ngroups;
+};
+int hj_launch_group_sum(const GroupArgs &a, int cus, hipStream_t stream);
+int hj_launch_group_emit(const GroupEmitArgs &a, int cus, hipStream_t stream);
 
 // K9: compact the per-wave partially filled tail blocks (npj.cpp:475-514).
 // moves: scratch of 2*HJ_MAX_WORKERS entries of 24 bytes + HJ_MAX_WORKERS entries of 8 bytes.

@@ -583,6 +583,137 @@ int hjgpu_compact_selected(hjgpu_ctx *ctx, const uint32_t *d_select_bits, size_t
     return HJGPU_OK;
 }
 
+// ---- grouped aggregation ----------------------------------------------------------
+// hjgpu_group_sum / _async (DESIGN.md section 5 "Grouped aggregation").  Every refusal is decided here, from the arguments alone, before
+// anything is allocated or enqueued.
+struct GroupCall {
+    const uint32_t *bits;
+    size_t n;
+    uint32_t nkeys, nvals;
+    const uint32_t *const *keys_in, *const *vals_in;
+    uint32_t *const *keys_out;
+    uint64_t *counts_out;
+    uint64_t *const *sums_out;
+    size_t capacity;
+};
+
+static int check_group(hjgpu_ctx *ctx, const GroupCall &g, const uint64_t *ngroups, bool device_count)
+{
+    if (!ngroups) return fail(ctx, HJGPU_EINVAL, "null group count pointer");
+    if (device_count && ((uintptr_t)ngroups & 7)) return fail(ctx, HJGPU_EALIGN, "d_ngroups must be 8-byte aligned");
+    if (g.nkeys == 0 || g.nkeys > HJGPU_GROUP_MAX_KEYS) return fail(ctx, HJGPU_EINVAL, "nkeys must be 1 to HJGPU_GROUP_MAX_KEYS (2)");
+    if (g.nvals > HJGPU_GROUP_MAX_VALS) return fail(ctx, HJGPU_EINVAL, "nvals must not exceed HJGPU_GROUP_MAX_VALS (4)");
+    if (hj_group::merge_slots(g.capacity) == 0) return fail(ctx, HJGPU_EINVAL, "capacity must not exceed 2^40 groups");
+    if (g.n == 0) return HJGPU_OK;                       // nothing is read, nothing but the count is written: anything else may be NULL
+    if ((uintptr_t)g.bits & 15) return fail(ctx, HJGPU_EALIGN, "d_select_bits must be 16-byte aligned");
+    if (!g.keys_in || !g.keys_out || (g.nvals && (!g.vals_in || !g.sums_out))) return fail(ctx, HJGPU_EINVAL, "null column array");
+    for (uint32_t c = 0; c < g.nkeys; ++c) {
+        if (!g.keys_in[c] || !g.keys_out[c]) return fail(ctx, HJGPU_EINVAL, "null key column pointer");
+        if (((uintptr_t)g.keys_in[c] | (uintptr_t)g.keys_out[c]) & 15) return fail(ctx, HJGPU_EALIGN, "key columns must be 16-byte aligned");
+    }
+    for (uint32_t c = 0; c < g.nvals; ++c) {
+        if (!g.vals_in[c] || !g.sums_out[c]) return fail(ctx, HJGPU_EINVAL, "null measure column pointer");
+        if (((uintptr_t)g.vals_in[c] | (uintptr_t)g.sums_out[c]) & 15) return fail(ctx, HJGPU_EALIGN, "measure and sum columns must be 16-byte aligned");
+    }
+    if ((uintptr_t)g.counts_out & 15) return fail(ctx, HJGPU_EALIGN, "d_counts_out must be 16-byte aligned");
+    // no output may share a byte with the mask, an input column or another output (the device count word is an output)
+    struct Range { const void *p; size_t bytes; };
+    Range outs[HJGPU_GROUP_MAX_KEYS + HJGPU_GROUP_MAX_VALS + 2], ins[HJGPU_GROUP_MAX_KEYS + HJGPU_GROUP_MAX_VALS + 1];
+    uint32_t nouts = 0, nins = 0;
+    for (uint32_t c = 0; c < g.nkeys; ++c) { outs[nouts++] = {g.keys_out[c], g.capacity * sizeof(uint32_t)}; ins[nins++] = {g.keys_in[c], g.n * sizeof(uint32_t)}; }
+    for (uint32_t c = 0; c < g.nvals; ++c) { outs[nouts++] = {g.sums_out[c], g.capacity * sizeof(uint64_t)}; ins[nins++] = {g.vals_in[c], g.n * sizeof(uint32_t)}; }
+    if (g.counts_out) outs[nouts++] = {g.counts_out, g.capacity * sizeof(uint64_t)};
+    if (device_count) outs[nouts++] = {ngroups, sizeof(uint64_t)};
+    if (g.bits) ins[nins++] = {g.bits, (g.n + 31) / 32 * sizeof(uint32_t)};
+    for (uint32_t o = 0; o < nouts; ++o) {
+        for (uint32_t i = 0; i < nins; ++i)
+            if (ranges_overlap(outs[o].p, outs[o].bytes, ins[i].p, ins[i].bytes))
+                return fail(ctx, HJGPU_EINVAL, i + 1 == nins && g.bits ? "an output overlaps d_select_bits" : "an output overlaps an input column");
+        for (uint32_t q = 0; q < o; ++q)
+            if (ranges_overlap(outs[o].p, outs[o].bytes, outs[q].p, outs[q].bytes)) return fail(ctx, HJGPU_EINVAL, "an output overlaps another output");
+    }
+    return HJGPU_OK;
+}
+
+// the three enqueues behind the checks: the clears (the count word; for n > 0 the overflow word and the merge table), the aggregation, the
+// emit.  hjgpu_get_stats afterwards: ms_histogram = the clears, ms_join = the aggregation, ms_close_gaps = the emit, ms_total = all of them
+static int group_enqueue(hjgpu_ctx *ctx, const GroupCall &g, u64 *d_ngroups, hipStream_t stream)
+{
+    const u64 slots = hj_group::merge_slots(g.capacity);
+    char *ws = reinterpret_cast<char *>(ctx->group.p);
+    for (int i = 0; i < EV_COUNT; ++i) ctx->ev_valid[i] = false;
+    ctx->last_algo = 4;
+    record(ctx, EV_BEGIN, stream);
+    HIPCHK(ctx, hj_zero_async(d_ngroups, sizeof(u64), stream));
+    if (g.n) HIPCHK(ctx, hj_zero_async(ws + sizeof(u64), (size_t)(hj_group::workspace_bytes(slots) - sizeof(u64)), stream));
+    record(ctx, EV_S_HIST, stream);
+    if (g.n) {
+        GroupArgs a{};
+        a.select_bits = g.bits; a.n = g.n; a.nkeys = g.nkeys; a.nvals = g.nvals;
+        for (uint32_t c = 0; c < g.nkeys; ++c) a.keys[c] = g.keys_in[c];
+        for (uint32_t c = 0; c < g.nvals; ++c) a.vals[c] = g.vals_in[c];
+        a.merge = reinterpret_cast<hj_group::Slot *>(ws + hj_group::WORKSPACE_HEAD);
+        a.merge_mask = slots - 1;
+        a.overflow = reinterpret_cast<uint32_t *>(ws + sizeof(u64));
+        CHK(hj_launch_group_sum(a, ctx->cus, stream));
+    }
+    record(ctx, EV_JOIN, stream);
+    if (g.n) {
+        GroupEmitArgs e{};
+        e.merge = reinterpret_cast<const hj_group::Slot *>(ws + hj_group::WORKSPACE_HEAD);
+        e.slots = slots; e.nkeys = g.nkeys; e.nvals = g.nvals; e.capacity = g.capacity; e.counts_out = reinterpret_cast<u64 *>(g.counts_out);
+        for (uint32_t c = 0; c < g.nkeys; ++c) e.keys_out[c] = g.keys_out[c];
+        for (uint32_t c = 0; c < g.nvals; ++c) e.sums_out[c] = reinterpret_cast<u64 *>(g.sums_out[c]);
+        e.d_ngroups = d_ngroups;
+        CHK(hj_launch_group_emit(e, ctx->cus, stream));
+    }
+    record(ctx, EV_GAPS, stream);
+    return HJGPU_OK;
+}
+
+// the context's merge table, sized from the capacity: it grows the first time a capacity is seen (hjgpu_stats.ms_reserve)
+static int group_workspace(hjgpu_ctx *ctx, size_t capacity)
+{
+    ReserveClock clock(ctx);
+    return ensure(ctx, ctx->group, (size_t)hj_group::workspace_bytes(hj_group::merge_slots(capacity)));
+}
+
+int hjgpu_group_sum_async(hjgpu_ctx *ctx, const uint32_t *d_select_bits, size_t n, uint32_t nkeys, const uint32_t *const *d_keys_in,
+                          uint32_t nvals, const uint32_t *const *d_vals_in, uint32_t *const *d_keys_out, uint64_t *d_counts_out,
+                          uint64_t *const *d_sums_out, size_t capacity, uint64_t *d_ngroups, void *stream_)
+{
+    if (!ctx) return HJGPU_EINVAL;
+    const GroupCall g{d_select_bits, n, nkeys, nvals, d_keys_in, d_vals_in, d_keys_out, d_counts_out, d_sums_out, capacity};
+    CHK(check_group(ctx, g, d_ngroups, true));
+    hipStream_t stream = (hipStream_t)stream_;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    CHK(refuse_capture(ctx, stream));
+    CHK(group_workspace(ctx, capacity));
+    return group_enqueue(ctx, g, reinterpret_cast<u64 *>(d_ngroups), stream);
+}
+
+int hjgpu_group_sum(hjgpu_ctx *ctx, const uint32_t *d_select_bits, size_t n, uint32_t nkeys, const uint32_t *const *d_keys_in,
+                    uint32_t nvals, const uint32_t *const *d_vals_in, uint32_t *const *d_keys_out, uint64_t *d_counts_out,
+                    uint64_t *const *d_sums_out, size_t capacity, uint64_t *ngroups, void *stream_)
+{
+    if (!ctx) return HJGPU_EINVAL;
+    const GroupCall g{d_select_bits, n, nkeys, nvals, d_keys_in, d_vals_in, d_keys_out, d_counts_out, d_sums_out, capacity};
+    CHK(check_group(ctx, g, ngroups, false));
+    hipStream_t stream = (hipStream_t)stream_;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    CHK(refuse_capture(ctx, stream));
+    CHK(group_workspace(ctx, capacity));
+    u64 *d_ngroups = reinterpret_cast<u64 *>(ctx->group.p);           // the workspace's first word
+    CHK(group_enqueue(ctx, g, d_ngroups, stream));
+    u64 got = 0;
+    HIPCHK(ctx, hipMemcpyAsync(&got, d_ngroups, sizeof(got), hipMemcpyDeviceToHost, stream));
+    HIPCHK(ctx, hipStreamSynchronize(stream));
+    *ngroups = got;
+    if (got > capacity)
+        return fail(ctx, HJGPU_EOVERFLOW, "hjgpu_group_sum: more groups than capacity (*ngroups holds a lower bound of their number that exceeds capacity; the outputs are unspecified)");
+    return HJGPU_OK;
+}
+
 int hjgpu_stream_read_ms(hjgpu_ctx *ctx, const void *d_ptr, size_t bytes, float *ms, void *stream_)
 {
     if (!ctx || !d_ptr || !ms) return HJGPU_EINVAL;

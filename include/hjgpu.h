@@ -266,7 +266,9 @@ int  hjgpu_get_stats(hjgpu_ctx *ctx, hjgpu_stats *stats);
  *   "probe_exact"      1 when the context's blocking joins take the exact path (option "exact_probe_counts", or after a fallback)
  *   "lookup_lds_rows"  the largest build side that hjgpu_lookup answers from LDS tables (0 under option "no_broadcast")
  *   "compact_ranges", "compact_chunk_rows"   hjgpu_compact_selected's geometry: the ranges (= workgroups) its rows are cut into, and the
- *                      rows of a chunk, of which every range holds a whole number */
+ *                      rows of a chunk, of which every range holds a whole number
+ *   "group_lds_groups" the distinct groups a workgroup's LDS table of hjgpu_group_sum holds before its further groups go straight to the
+ *                      merge table in device memory */
 int  hjgpu_get_counter(hjgpu_ctx *ctx, const char *name, uint64_t *value);
 
 /* ---- device memory helpers for hosts that do not link HIP (mamalloc/free,
@@ -474,6 +476,54 @@ int  hjgpu_compact_selected(hjgpu_ctx *ctx, const uint32_t *d_select_bits, size_
 int  hjgpu_compact_selected_async(hjgpu_ctx *ctx, const uint32_t *d_select_bits, size_t n,
                                   uint32_t ncols, const uint32_t *const *d_cols_in, uint32_t *const *d_cols_out,
                                   uint32_t *d_rows_out, size_t capacity, uint64_t *d_count, void *stream);
+
+/* ---- grouped aggregation: GROUP BY one or two columns, COUNT(*) and up to four SUMs over a bitmap's rows -------
+ * What ends a chain of selected look-ups: the bitmap says which rows count, the looked-up value columns are the group keys in place, and
+ * the answer is a few thousand rows.  The selected rows i are grouped by the tuple (d_keys_in[0][i] [, d_keys_in[1][i]]); for every
+ * distinct tuple there is exactly one output index j < J:
+ *   d_keys_out[c][j] = the tuple's column c, d_counts_out[j] = the number of its selected rows, d_sums_out[v][j] = the sum of
+ *   d_vals_in[v][i] over them in uint64 modulo 2^64.  The ORDER of the groups is unspecified, as the order of a join's rows is; counts and
+ *   sums are exact integers, so the set of (tuple, count, sums) is reproducible bit for bit.
+ *   d_select_bits    hjgpu_lookup_selected's mask, word for word: (n + 31) / 32 words, bit i & 31 of word i >> 5 selects row i, bits of the
+ *                    last word at positions >= n are ignored, no word at index >= (n + 31) / 32 is read.  16-byte aligned (HJGPU_EALIGN).
+ *                    NULL selects every row (unlike the compaction: an aggregate over all rows is a real query).
+ *   key values       every key value is legal, 0 and 0xFFFFFFFF included; HJGPU_NULL_VAL from an unmatched but selected row is an
+ *                    ordinary group.
+ *   d_keys_in, d_vals_in, d_keys_out, d_sums_out   HOST arrays of nkeys / nvals device pointers, copied by value into the kernel
+ *                    arguments; input columns hold n uint32, d_keys_out columns capacity uint32, d_sums_out columns capacity uint64.
+ *                    nkeys is 1 or 2, nvals 0 to 4 (0: counts only; the value arrays may then be NULL).  nkeys == 0,
+ *                    nkeys > HJGPU_GROUP_MAX_KEYS, nvals > HJGPU_GROUP_MAX_VALS and a NULL entry among the first nkeys / nvals of an
+ *                    array are HJGPU_EINVAL.  The same input column may be given twice.
+ *   d_counts_out     capacity uint64, or NULL: no counts.
+ *   count            *ngroups (blocking form, host memory) / *d_ngroups (_async form, device memory, 8-byte aligned: HJGPU_EALIGN) = J.
+ *   overflow         J > capacity: the blocking form returns HJGPU_EOVERFLOW, and *ngroups is then a lower bound of J that is greater than
+ *                    capacity (J itself while the merge table holds every group: it has at least twice capacity slots).  Nothing at index
+ *                    >= capacity is written; the contents below capacity are unspecified.  The _async form's caller compares *d_ngroups
+ *                    with capacity.  Neither form touches what hjgpu_get_async_status / hjgpu_accumulate_async_status report.
+ *                    capacity == 0 is legal: an overflow unless J is 0.  capacity > 2^40 is HJGPU_EINVAL.
+ *   alignment        every input column, every output column and the mask 16-byte aligned (HJGPU_EALIGN).
+ *   overlap          an output's byte range (the _async form's count word included) that overlaps the mask, an input column or another
+ *                    output: HJGPU_EINVAL, "overlaps" in hjgpu_last_error.  The mask and the inputs are never written; no input row at n
+ *                    or beyond is read, except inside the last 16-byte vector of a column.
+ *   n == 0           reads nothing, writes nothing but the count (0), accepts NULL everywhere else.
+ * Every refusal is decided from the arguments alone, before anything is enqueued or allocated; a capturing stream is HJGPU_EINVAL.  Calls
+ * on one stream of one context may be queued back to back.  The workspace is the merge table in the context, sized from capacity (a power
+ * of two of at least 2 * capacity and at least 1024 slots of 48 bytes); it grows the first time a capacity is seen (hjgpu_stats.ms_reserve).
+ * Three enqueues ordered by the stream - the clears, the aggregation (one pass over the mask, the key and the measure columns; each
+ * workgroup pre-aggregates in an LDS table and adds what it holds to the merge table), the emit - and no workgroup waits for another.
+ * hjgpu_get_stats afterwards: ms_total = all launches, ms_histogram = the clears, ms_join = the aggregation, ms_close_gaps = the emit,
+ * every other phase 0, fanout1 = fanout2 = buckets = groups = 0.  hjgpu_get_counter "group_lds_groups": the distinct groups a
+ * workgroup's LDS table holds; correctness never depends on the number of groups. */
+#define HJGPU_GROUP_MAX_KEYS 2u
+#define HJGPU_GROUP_MAX_VALS 4u
+int  hjgpu_group_sum(hjgpu_ctx *ctx, const uint32_t *d_select_bits, size_t n,
+                     uint32_t nkeys, const uint32_t *const *d_keys_in, uint32_t nvals, const uint32_t *const *d_vals_in,
+                     uint32_t *const *d_keys_out, uint64_t *d_counts_out, uint64_t *const *d_sums_out,
+                     size_t capacity, uint64_t *ngroups, void *stream);
+int  hjgpu_group_sum_async(hjgpu_ctx *ctx, const uint32_t *d_select_bits, size_t n,
+                           uint32_t nkeys, const uint32_t *const *d_keys_in, uint32_t nvals, const uint32_t *const *d_vals_in,
+                           uint32_t *const *d_keys_out, uint64_t *d_counts_out, uint64_t *const *d_sums_out,
+                           size_t capacity, uint64_t *d_ngroups, void *stream);
 
 /* ---- whole joins on HBM-resident columns (replace run()/run_hj()) ---------------- */
 /* run(), npj.cpp:769-927 */
