@@ -7,6 +7,7 @@
 #include "../../include/hjgpu.h"
 #include "compact_layout.hpp"
 #include "group_layout.hpp"
+#include "scatter_layout.hpp"
 
 typedef unsigned long long u64;
 
@@ -14,9 +15,7 @@ typedef unsigned long long u64;
 // Scatter tile = block * vectors_per_thread * 4 tuples.  Pass 1 of the join pipeline
 // (packed output) runs in whole-line mode when its carry buffers fit the LDS beside the
 // tile, which decides the tile size from the fan-out; see hj_scatter_config().
-constexpr uint32_t HJ_LINE_TUPLES = 16;          // packed (8-byte) tuples per 128-byte line
-constexpr uint32_t HJ_STREAM_UNIT = 256;         // output slots one 16-lane group streams out at a time
-constexpr uint32_t HJ_MAX_HEAVY = 128;           // listed units per tile: <= (16384 + 30 * 209) / HJ_STREAM_UNIT (carry + line offsets)
+// (HJ_LINE_TUPLES, HJ_STREAM_UNIT, HJ_MAX_HEAVY and the LDS layout of a K6 workgroup: scatter_layout.hpp)
 struct ScatterConfig { int block, vpt; bool carry; };
 struct HjTuning;
 ScatterConfig hj_scatter_config(const HjTuning &t, int pass, uint32_t F, bool out_packed);

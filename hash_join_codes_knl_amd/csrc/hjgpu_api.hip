@@ -281,7 +281,7 @@ void choose_fanout(const HjTuning &tune, size_t inner, const hjgpu_phj_params *p
             while ((double)f1 * f1 * 2.0 < parts) f1 <<= 1;          // f1 ~ sqrt(parts) within a factor sqrt(2)
             if (f1 > 256) f1 = 256;
             // ... but as soon as pass 2 still keeps >= 64 partitions, pass 1 takes 192: its cost is flat while the
-            // whole-line carry fits beside a 16 K-tuple tile (F <= 209), and every partition less in pass 2 means
+            // whole-line carry fits beside a 16 K-tuple tile (F <= 216), and every partition less in pass 2 means
             // longer runs per tile, i.e. fewer < 16-tuple tails written into partial lines.  64 M x 1 G, one process:
             // 128 x 144 8.64 ms (2.98 + 3.20), 160 x 116 8.59, 192 x 96 8.55 (3.00 + 3.07), 208 x 89 8.59,
             // 256 x 72 8.71 (3.21 + 3.00: 12 K-tuple tiles in pass 1), 96 x 192 8.74, 64 x 288 8.96

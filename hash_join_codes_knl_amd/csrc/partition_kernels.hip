@@ -995,30 +995,40 @@ int hj_launch_offsets_to_counts(const u64 *off, u64 *counts, uint32_t P, hipStre
 // tile emits whole lines only (one returning atomic per (tile, partition), issued when the counts exist, consumed after the sort),
 // and the workgroup's last < 16 tuples of a partition go to the back of the region when it runs out of tiles.  A claim that
 // would make front and back cross sets *claim_overflow and writes nothing: every store stays inside its partition's region.
+
+// The array at byte `off` of hj_scatter::layout(), reached from the array `from` at byte `from_off` in whole elements of `from`: every
+// array then inherits what the compiler knows of smem's 16-byte alignment (the scan reads wsum in 16-byte pieces), and the addresses
+// are computed as they were when the kernel carved by hand (same machine code).
+template <class T, class U>
+__device__ __forceinline__ T *lds_step(U *from, int from_off, int off)
+{
+    return reinterpret_cast<T *>(from + (off - from_off) / (int)sizeof(U));
+}
+
 template <int BLOCK, int VPT, bool RANGED, bool IN_PACKED, bool OUT_PACKED, bool CARRY, bool NTP = true, bool CLAIM = false>
 __global__ __launch_bounds__(BLOCK) void scatter_kernel(ScatterArgs a)
 {
     static_assert(!CARRY || (RANGED && OUT_PACKED), "carry needs private cursors and packed output");
     static_assert(!CLAIM || CARRY, "claimed pass-1 lines need the whole-line carry");
     constexpr int TILE = BLOCK * VPT * 4;
-    constexpr int NW = BLOCK / 64;
     constexpr int BPT = (1024 + BLOCK - 1) / BLOCK;                 // max bins per thread (F <= 1024)
     constexpr uint32_t LINE = HJ_LINE_TUPLES;                       // packed tuples per 128-byte line
     constexpr uint32_t UNIT = HJ_STREAM_UNIT;                       // output slots a 16-lane group moves at a time
     extern __shared__ __align__(16) unsigned char smem[];
     const uint32_t F = a.F;
-    const uint32_t Fpad = (F + 3) & ~3u;
-    u64 *delta = reinterpret_cast<u64 *>(smem);                     // [Fpad]  packed out: output position of the run; else output - local position
-    u64 *stage = delta + Fpad;                                      // [TILE]  payload << 32 | key, sorted by partition
-    u64 *carry = stage + TILE;                                      // CARRY: [Fpad][LINE] tails waiting for their line
-    u64 *tinfo = carry;                                             // pass 2: [Fpad] (position of the run's tail << 4) | tail tuples
-    uint32_t *hist = reinterpret_cast<uint32_t *>(carry + (CARRY ? Fpad * LINE : (RANGED ? 0 : Fpad)));   // [Fpad]  counts, then local bases
-    uint32_t *meta = hist + Fpad;                                   // [Fpad] tuples leaving this tile | carried ones among them << 16
-    uint32_t *left = meta + Fpad;                                   // CARRY: [Fpad] first staying index | carry offset << 16 | count << 20
-    uint32_t *wsum = left + (CARRY ? Fpad : 0);                     // [NW + 6]; [NW + 1] = number of runs longer than one unit, [NW + 4..5] = tickets,
-                                                                    // [NW + 2] = this tile's heavy partition (count << 10 | bin, 0 = none),
-                                                                    // [NW + 3] = the same for the next tile
-    uint32_t *heavy = wsum + NW + 6;                                // [HJ_MAX_HEAVY] partitions whose run is longer than one unit
+    // the LDS, carved from hj_scatter::layout() and from nothing else (scatter_layout.hpp has the table of who writes and reads what)
+    const hj_scatter::Layout l = hj_scatter::layout(BLOCK, VPT, F, CARRY, !RANGED);
+    u64 *delta = reinterpret_cast<u64 *>(smem + l.delta);           // [Fpad]  packed out: output position of the run; else output - local position
+    u64 *stage = lds_step<u64>(delta, l.delta, l.stage);            // [TILE]  payload << 32 | key, sorted by partition
+    u64 *carry = lds_step<u64>(stage, l.stage, l.carry);            // CARRY: [Fpad][LINE] tails waiting for their line
+    u64 *tinfo = lds_step<u64>(carry, l.carry, l.tinfo);            // pass 2: [Fpad] (position of the run's tail << 4) | tail tuples
+    uint32_t *hist = lds_step<uint32_t>(tinfo, l.tinfo, l.hist);    // [Fpad]  counts, then local bases
+    uint32_t *meta = lds_step<uint32_t>(hist, l.hist, l.meta);      // [Fpad] tuples leaving this tile | carried ones among them << 16
+    uint32_t *left = lds_step<uint32_t>(meta, l.meta, l.left);      // CARRY: [Fpad] first staying index | carry offset << 16 | count << 20
+    uint32_t *wsum = lds_step<uint32_t>(left, l.left, l.wsum);      // [BLOCK / 64] the scan's wave totals; the scan leaves the tile's count behind them, in ctl[CTL_TILE_COUNT]
+    uint32_t *ctl = lds_step<uint32_t>(wsum, l.wsum, l.ctl);        // [CTL_WORDS] the control words, hj_scatter::CTL_*
+    uint32_t *heavy = lds_step<uint32_t>(ctl, l.ctl, l.heavy);      // [HJ_MAX_HEAVY] partitions whose run is longer than one unit
+    using namespace hj_scatter;                                     // CTL_*
 
     const int tid = threadIdx.x;
     // pass 1 of a device-planned group (ScatterArgs::dyn): first row and rows of the input come from device memory (uniform: scalar loads)
@@ -1051,7 +1061,7 @@ __global__ __launch_bounds__(BLOCK) void scatter_kernel(ScatterArgs a)
     // Tickets are prefetched: thread 0 issues the atomic for ticket n+2 when ticket n+1 is taken
     // and deposits it in LDS a few barriers later, so nobody ever waits for an atomic.
     struct Tile { u64 gb, ge, g0, cursor_row; uint32_t range; bool new_range, last_in_range, empty, valid; };
-    uint32_t *claim = wsum + NW + 4;                                 // [2] prefetched tickets
+    uint32_t *claim = ctl + CTL_TICKETS;                            // [2] prefetched tickets
     int claim_parity = 0;
     uint32_t pending_ticket = 0;                                    // thread 0: ticket on its way
     int pending_slot = -1;                                          // thread 0: where it goes (-1: none)
@@ -1166,7 +1176,7 @@ __global__ __launch_bounds__(BLOCK) void scatter_kernel(ScatterArgs a)
     if (!cur.valid) return;
     load_tile(cur);
     bool have_left = false;                                         // CARRY: the previous tile may have left tails in `stage`
-    bool have_left_or_prev = false;                                 // a previous tile exists (its skew verdict is in wsum[NW + 3])
+    bool have_left_or_prev = false;                                 // a previous tile exists (its skew verdict is in ctl[CTL_NEXT_HOT])
     // diagnostics: thread 0 adds the s_memtime ticks between consecutive barriers to prof[phase]
     u64 t_prev = (a.prof && tid == 0) ? __builtin_amdgcn_s_memtime() : 0;
     auto stamp = [&](int phase) {
@@ -1178,10 +1188,11 @@ __global__ __launch_bounds__(BLOCK) void scatter_kernel(ScatterArgs a)
     };
     // A run longer than one stream-out unit gets its further units listed (partition | unit << 16): the
     // stream-out deals the partitions' first units and these round-robin to the 16-lane groups.
+    // (the list has no bounds check: HJ_MAX_HEAVY holds what any tile that fits the LDS can list, scatter_layout.hpp)
     auto add_units = [&](uint32_t bin, uint32_t slots) {
         if (slots > UNIT) {
             const uint32_t extra = (slots - 1) / UNIT;
-            const uint32_t at = atomicAdd(&wsum[NW + 1], extra);
+            const uint32_t at = atomicAdd(&ctl[CTL_EXTRA_UNITS], extra);
             for (uint32_t u = 0; u < extra; ++u) heavy[at + u] = bin | ((u + 1) << 16);
         }
     };
@@ -1204,7 +1215,7 @@ __global__ __launch_bounds__(BLOCK) void scatter_kernel(ScatterArgs a)
             }
         }
         for (uint32_t i = tid; i < F; i += BLOCK) hist[i] = 0;
-        if (tid == 0) { wsum[NW + 1] = 0; wsum[NW + 2] = have_left_or_prev ? wsum[NW + 3] : 0; wsum[NW + 3] = 0; }
+        if (tid == 0) { ctl[CTL_EXTRA_UNITS] = 0; ctl[CTL_HOT] = have_left_or_prev ? ctl[CTL_NEXT_HOT] : 0; ctl[CTL_NEXT_HOT] = 0; }
         hj_barrier_lds();
         stamp(0);
         // the next tile's descriptor (pass 2: one read of K5's table; a scalar load, which the next
@@ -1216,7 +1227,7 @@ __global__ __launch_bounds__(BLOCK) void scatter_kernel(ScatterArgs a)
         // probe side) many lanes of an instruction add to the SAME LDS word and the adds serialise.
         // The previous tile names its largest partition when that held > 1/16 of the tile; its lanes
         // are then served by ONE add of the group's size, with ranks from mbcnt.
-        const uint32_t hot_word = wsum[NW + 2];
+        const uint32_t hot_word = ctl[CTL_HOT];
         const bool hot = hot_word != 0;
         const uint32_t hot_p = hot_word & 1023u;
         uint32_t pr[VPT * 4];
@@ -1348,7 +1359,7 @@ __global__ __launch_bounds__(BLOCK) void scatter_kernel(ScatterArgs a)
         for (int i = 0; i < BPT; ++i)
             if (cnt[i] > (uint32_t)TILE / 16) biggest = max(biggest, (cnt[i] << 10) | (tid * bpt + i));
         uint32_t run = block_exclusive_scan<BLOCK, uint32_t, true>(sum, wsum);
-        if (biggest) atomicMax(&wsum[NW + 3], biggest);                 // rare; nobody reads it before the next tile
+        if (biggest) atomicMax(&ctl[CTL_NEXT_HOT], biggest);            // rare; nobody reads it before the next tile
 #pragma unroll
         for (int i = 0; i < BPT; ++i) {
             const uint32_t bin = tid * bpt + i;
@@ -1369,7 +1380,7 @@ __global__ __launch_bounds__(BLOCK) void scatter_kernel(ScatterArgs a)
         }
         hj_barrier_lds();
         stamp(2);
-        const uint32_t tile_count = wsum[NW];
+        const uint32_t tile_count = ctl[CTL_TILE_COUNT];
 
         // ---- counting sort inside LDS --------------------------------------------
         if (interior) {                                                // every tuple of the tile is valid
@@ -1499,7 +1510,7 @@ __global__ __launch_bounds__(BLOCK) void scatter_kernel(ScatterArgs a)
                 }
                 if (s < s_end) k6_store8<NTP>(out64 + base + s, src[s]);            // the run ends on an even slot
             };
-            const uint32_t nunits = F + wsum[NW + 1];
+            const uint32_t nunits = F + ctl[CTL_EXTRA_UNITS];
             for (uint32_t u = gid; u < nunits; u += NG) {
                 if (u < F) move_unit(u, 0);
                 else { const uint32_t h = heavy[u - F]; move_unit(h & 0xFFFFu, h >> 16); }
@@ -1566,16 +1577,8 @@ __global__ __launch_bounds__(BLOCK) void scatter_kernel(ScatterArgs a)
 }
 
 // ---- geometry of a pass: workgroup size, vectors per thread, whole-line mode -------
-static size_t scatter_lds(int block, int vpt, uint32_t F, bool carry, bool pass2 = false)
-{
-    const size_t Fpad = (F + 3) & ~3u;
-    return Fpad * 16 + (size_t)block * vpt * 4 * 8 + (carry ? Fpad * (HJ_LINE_TUPLES * 8 + 4) : 0) + (pass2 ? Fpad * 8 : 0) +
-           (block / 64 + 6) * 4 + HJ_MAX_HEAVY * 4 + 16;
-}
-constexpr size_t HJ_LDS_LIMIT = 160 * 1024;          // gfx950: 160 KiB per CU, all of it usable by one workgroup
-
-// pass 1: the largest tile whose stage + carry buffers fit the LDS (F <= 209: 16384 tuples,
-// <= 421: 12288, <= 640: 8192); beyond that, and for separate output columns, no carry.
+// pass 1: the largest tile whose stage + carry buffers fit the LDS (F <= 216: 16384 tuples,
+// <= 436: 12288, <= 660: 8192; tests/cpp_scatter_layout.cpp); beyond that, and for separate output columns, no carry.
 // pass 2: 16384-tuple tiles, shared atomic cursors (a workgroup visits a segment about once,
 // so there is no "next tile" to complete a line).
 // options "scatter_cfg" / "scatter2_cfg" = "block,vpt[,carry]" override (tuning).
@@ -1585,12 +1588,12 @@ ScatterConfig hj_scatter_config(const HjTuning &t, int pass, uint32_t F, bool ou
     const int *o = t.scatter_cfg[pass == 1 ? 0 : 1];
     if (o[0] > 0) {
         cfg.block = o[0]; cfg.vpt = o[1];
-        cfg.carry = pass == 1 && out_packed && o[2] != 0 && scatter_lds(o[0], o[1], F, true) <= HJ_LDS_LIMIT;
+        cfg.carry = pass == 1 && out_packed && o[2] != 0 && hj_scatter::carry_fits(o[0], o[1], F);
         return cfg;
     }
     if (pass == 1 && out_packed) {
         for (int vpt = 4; vpt >= 2; --vpt)
-            if (scatter_lds(1024, vpt, F, true) <= HJ_LDS_LIMIT) { cfg.vpt = vpt; cfg.carry = true; break; }
+            if (hj_scatter::carry_fits(1024, vpt, F)) { cfg.vpt = vpt; cfg.carry = true; break; }
     }
     return cfg;
 }
@@ -1604,7 +1607,8 @@ int hj_scatter_tile(const HjTuning &t, int pass, uint32_t F, bool out_packed)
 template <int BLOCK, int VPT, bool RANGED, bool IN_PACKED, bool OUT_PACKED, bool CARRY, bool NTP = true, bool CLAIM = false>
 static int launch_scatter_t(const ScatterArgs &a, bool want_prof, int cus, hipStream_t stream)
 {
-    const size_t lds = scatter_lds(BLOCK, VPT, a.F, CARRY, !RANGED);
+    constexpr size_t HJ_LDS_LIMIT = hj_scatter::LDS_LIMIT;
+    const size_t lds = hj_scatter::layout(BLOCK, VPT, a.F, CARRY, !RANGED).bytes;
     if (lds > HJ_LDS_LIMIT) return HJGPU_EINVAL;
     static HjPerDeviceOnce once;
     if (hj_allow_dynamic_lds(reinterpret_cast<const void *>(&scatter_kernel<BLOCK, VPT, RANGED, IN_PACKED, OUT_PACKED, CARRY, NTP, CLAIM>),
@@ -1641,46 +1645,45 @@ static int launch_scatter_t(const ScatterArgs &a, bool want_prof, int cus, hipSt
     return hipGetLastError() == hipSuccess ? HJGPU_OK : HJGPU_EHIP;
 }
 
-// pass 1: separate columns in, ranged; out packed (join pipeline, whole-line mode when it
-//         fits) or separate (hjgpu_partition)
-// pass 2: packed in, packed out, atomic cursors
-#define SCATTER_CASE(B, V)                                                                   \
-    if (c.block == B && c.vpt == V) {                                                        \
-        if (a.ranged && !a.in_packed && a.out_packed && c.carry)                                                                                            \
-            return a.nt_partial ? launch_scatter_t<B, V, true, false, true, true, true>(a, t.scatter_prof, cus, stream)                                     \
-                                : launch_scatter_t<B, V, true, false, true, true, false>(a, t.scatter_prof, cus, stream);                                    \
-        if (a.ranged && !a.in_packed && a.out_packed)                                                                                                        \
-            return a.nt_partial ? launch_scatter_t<B, V, true, false, true, false, true>(a, t.scatter_prof, cus, stream)                                    \
-                                : launch_scatter_t<B, V, true, false, true, false, false>(a, t.scatter_prof, cus, stream);                                   \
-        if (a.ranged && !a.in_packed && !a.out_packed) return launch_scatter_t<B, V, true, false, false, false>(a, t.scatter_prof, cus, stream); \
-        if (!a.ranged && a.in_packed && a.out_packed)                                                                                                        \
-            return a.nt_partial ? launch_scatter_t<B, V, false, true, true, false, true>(a, t.scatter_prof, cus, stream)                                    \
-                                : launch_scatter_t<B, V, false, true, true, false, false>(a, t.scatter_prof, cus, stream);                                   \
-        return HJGPU_EINVAL;                                                                 \
-    }
+// The instances of one (block, vpt) pair, by the launch's shape:
+//   pass 1: separate columns in, ranged; out packed (join pipeline, whole-line mode when it fits; claimed: without range bases,
+//           1024 x {4, 3} only) or separate columns (hjgpu_partition: no 8-byte stores, so only the NTP instance exists)
+//   pass 2: packed in, packed out, atomic cursors
+template <int B, int V>
+static int launch_scatter_shape(const ScatterArgs &a, bool carry, bool claim, bool prof, int cus, hipStream_t stream)
+{
+    const bool pass1 = a.ranged && !a.in_packed, pass2 = !a.ranged && a.in_packed && a.out_packed;
+    int rc = HJGPU_EINVAL;
+    hj_with_bool(a.nt_partial != 0, [&](auto ntp) {
+        constexpr bool NTP = decltype(ntp)::value;
+        if (claim) {
+            if constexpr (B == 1024 && (V == 4 || V == 3)) rc = launch_scatter_t<B, V, true, false, true, true, NTP, true>(a, prof, cus, stream);
+        } else if (pass1 && a.out_packed) {
+            hj_with_bool(carry, [&](auto c) { rc = launch_scatter_t<B, V, true, false, true, decltype(c)::value, NTP>(a, prof, cus, stream); });
+        } else if (pass1) rc = launch_scatter_t<B, V, true, false, false, false>(a, prof, cus, stream);
+        else if (pass2) rc = launch_scatter_t<B, V, false, true, true, false, NTP>(a, prof, cus, stream);
+    });
+    return rc;
+}
 
 int hj_launch_scatter(const ScatterArgs &a, const HjTuning &t, int cus, hipStream_t stream)
 {
     if (a.F == 0 || a.F > HJGPU_MAX_FANOUT) return HJGPU_EINVAL;
     const ScatterConfig c = hj_scatter_config(t, a.ranged ? 1 : 2, a.F, a.out_packed != 0);
     if (a.ranged && a.geom.tile != (uint32_t)(c.block * c.vpt * 4)) return HJGPU_EINVAL;
-    if (a.claim_cursors) {
-        // claimed pass 1 (the probe side of a blocking join): 1024-thread workgroups with the whole-line carry only
-        if (!a.ranged || a.in_packed || !a.out_packed || !c.carry || c.block != 1024 || !a.claim_overflow || !a.claim_cap) return HJGPU_EINVAL;
-        if (c.vpt == 4) return a.nt_partial ? launch_scatter_t<1024, 4, true, false, true, true, true, true>(a, t.scatter_prof, cus, stream)
-                                            : launch_scatter_t<1024, 4, true, false, true, true, false, true>(a, t.scatter_prof, cus, stream);
-        if (c.vpt == 3) return a.nt_partial ? launch_scatter_t<1024, 3, true, false, true, true, true, true>(a, t.scatter_prof, cus, stream)
-                                            : launch_scatter_t<1024, 3, true, false, true, true, false, true>(a, t.scatter_prof, cus, stream);
-        return HJGPU_EINVAL;
-    }
-    SCATTER_CASE(1024, 4)
-    SCATTER_CASE(1024, 3)
-    SCATTER_CASE(1024, 2)
-    SCATTER_CASE(512, 4)
-    SCATTER_CASE(512, 3)
-    SCATTER_CASE(512, 2)
-    SCATTER_CASE(256, 4)
-    SCATTER_CASE(256, 2)
+    const bool claim = a.claim_cursors != nullptr;
+    // claimed pass 1 (the probe side of a blocking join): 1024-thread workgroups with the whole-line carry only
+    if (claim && (!a.ranged || a.in_packed || !a.out_packed || !c.carry || c.block != 1024 || !a.claim_overflow || !a.claim_cap)) return HJGPU_EINVAL;
+    // the built (block, vpt) pairs
+    const bool prof = t.scatter_prof;
+    if (c.block == 1024 && c.vpt == 4) return launch_scatter_shape<1024, 4>(a, c.carry, claim, prof, cus, stream);
+    if (c.block == 1024 && c.vpt == 3) return launch_scatter_shape<1024, 3>(a, c.carry, claim, prof, cus, stream);
+    if (c.block == 1024 && c.vpt == 2) return launch_scatter_shape<1024, 2>(a, c.carry, claim, prof, cus, stream);
+    if (c.block == 512 && c.vpt == 4) return launch_scatter_shape<512, 4>(a, c.carry, claim, prof, cus, stream);
+    if (c.block == 512 && c.vpt == 3) return launch_scatter_shape<512, 3>(a, c.carry, claim, prof, cus, stream);
+    if (c.block == 512 && c.vpt == 2) return launch_scatter_shape<512, 2>(a, c.carry, claim, prof, cus, stream);
+    if (c.block == 256 && c.vpt == 4) return launch_scatter_shape<256, 4>(a, c.carry, claim, prof, cus, stream);
+    if (c.block == 256 && c.vpt == 2) return launch_scatter_shape<256, 2>(a, c.carry, claim, prof, cus, stream);
     return HJGPU_EINVAL;
 }
 

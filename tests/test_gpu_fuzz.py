@@ -3,7 +3,7 @@ selectivities and output modes drawn from a seeded generator, every result compa
 with an independent numpy definition of the join (helpers.numpy_join / materialised_rows).
 
 The fan-outs are chosen so that every geometry of K6 runs: whole-line mode with 16 K-, 12 K- and
-8 K-tuple tiles (fan-out <= 209 / <= 421 / <= 640), no carry beyond that, single-pass plans, runs
+8 K-tuple tiles (fan-out <= 216 / <= 436 / <= 660), no carry beyond that, single-pass plans, runs
 longer than one stream-out unit (tiny fan-outs, heavy hitters), ranges without tiles (small inputs)."""
 import os
 

@@ -136,14 +136,38 @@ def test_joins_match_oracle(hj, oracle, name):
         assert res == want, "%s on %s: got %r want %r" % (algo, name, res, want)
 
 
-@pytest.mark.parametrize("f1,f2", [(2, 1), (3, 1), (64, 1), (5, 7), (64, 64), (128, 100), (1000, 32)])
-def test_phj_cpra_any_fanout(hj, oracle, f1, f2):
+@pytest.fixture(scope="module")
+def fanout_case(oracle):
+    """the relations of the fan-out tests and their join by the oracle's definition, computed once"""
     ik, iv, ok, ov = oracle.generate(200_000, 30_000, seed=11)
-    want = oracle.join_definition(ik, iv, ok, ov)
+    return ik, iv, ok, ov, oracle.join_definition(ik, iv, ok, ov)
+
+
+# (216 / 436 / 660: the last fan-outs at which pass 1's whole-line carry fits the LDS beside a tile of 4 / 3 / 2 vectors per thread,
+# csrc/scatter_layout.hpp - where a mistake in K6's LDS layout shows first; one more takes the next geometry)
+@pytest.mark.parametrize("f1,f2", [(2, 1), (3, 1), (64, 1), (5, 7), (64, 64), (128, 100), (1000, 32),
+                                   (216, 2), (217, 2), (436, 2), (437, 2), (660, 2), (661, 2)])
+def test_phj_cpra_any_fanout(hj, fanout_case, f1, f2):
+    ik, iv, ok, ov, want = fanout_case
     for chunks in (1, 3, 8):
         prm = H.PhjParams(fanout1=f1, fanout2=f2, chunks=chunks)
         got = _join_all(hj, ik, iv, ok, ov, phj_params=prm, algos=("phj", "cpra"))
         assert got["phj"] == want and got["cpra"] == want, (f1, f2, chunks, got, want)
+
+
+@pytest.mark.parametrize("f1,f2", [(64, 8), (1000, 4)])
+@pytest.mark.parametrize("cfg", ["512,4,1", "512,2,0", "256,4,1", "256,2,0"])
+def test_phj_cpra_scatter_geometry_options(hj, fanout_case, cfg, f1, f2):
+    """Options scatter_cfg / scatter2_cfg: the K6 instances of 512 and 256 threads, which no planned geometry reaches, and (fan-out 1000)
+    their loops over several bins per thread.  (A context of its own: the session's keeps its planned geometry.)"""
+    ik, iv, ok, ov, want = fanout_case
+    with H.HjGpu() as ctx:
+        ctx.set_option("scatter_cfg", cfg)
+        ctx.set_option("scatter2_cfg", cfg)
+        for chunks in (1, 3):
+            prm = H.PhjParams(fanout1=f1, fanout2=f2, chunks=chunks)
+            got = _join_all(ctx, ik, iv, ok, ov, phj_params=prm, algos=("phj", "cpra"))
+            assert got["phj"] == want and got["cpra"] == want, (cfg, f1, f2, chunks, got, want)
 
 
 def test_phj_overflow_partitions_multi_fill(hj, oracle):
