@@ -26,6 +26,9 @@ FLAG_FULL_OUTER = FLAG_LEFT_OUTER | FLAG_RIGHT_OUTER     # HJGPU_FLAG_FULL_OUTER
 FLAG_RIGHT_SEMI = 32    # HJGPU_FLAG_RIGHT_SEMI: one row (key, inner_val) per build tuple whose key a probe tuple carries
 FLAG_RIGHT_ANTI = 64    # HJGPU_FLAG_RIGHT_ANTI: one row (key, inner_val) per build tuple whose key no probe tuple carries
 NULL_VAL = 0xFFFFFFFF   # HJGPU_NULL_VAL: the value on the side without a match in an outer join's NULL row
+FILTER_MAX_PREDS = 4    # HJGPU_FILTER_MAX_PREDS
+PRED_NOT = 1            # HJGPU_PRED_NOT: the rows OUTSIDE [lo, hi] pass
+PRED_SIGNED = 2         # HJGPU_PRED_SIGNED: lo, hi and the column are int32 (two's complement order)
 
 EXPORTS = [
     "hjgpu_kernel_hash", "hjgpu_library_hash", "hjgpu_device_count", "hjgpu_create", "hjgpu_destroy", "hjgpu_last_error", "hjgpu_status_string",
@@ -37,6 +40,7 @@ EXPORTS = [
     "hjgpu_npj_build", "hjgpu_npj_probe",
     "hjgpu_npj_lookup", "hjgpu_npj_lookup_async", "hjgpu_npj_lookup_table", "hjgpu_lookup", "hjgpu_lookup_async",
     "hjgpu_lookup_selected", "hjgpu_lookup_selected_async", "hjgpu_npj_lookup_table_selected",
+    "hjgpu_filter_selected", "hjgpu_filter_selected_async",
     "hjgpu_compact_selected", "hjgpu_compact_selected_async",
     "hjgpu_group_sum", "hjgpu_group_sum_async",
     "hjgpu_npj", "hjgpu_phj", "hjgpu_cpra",
@@ -80,6 +84,19 @@ class PhjParams(C.Structure):
 
 class NpjParams(C.Structure):
     _fields_ = [("load", C.c_double), ("factor", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class Predicate(C.Structure):
+    """hjgpu_predicate: lo <= x <= hi, both ends inclusive; flags: PRED_NOT, PRED_SIGNED (lo and hi are then given as their uint32 bit
+    patterns or as negative Python ints, which Predicate.of wraps)."""
+    _fields_ = [("lo", C.c_uint32), ("hi", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+    @classmethod
+    def of(cls, p):
+        if isinstance(p, cls):
+            return p
+        lo, hi, flags = tuple(p) if len(p) == 3 else tuple(p) + (0,)
+        return cls(int(lo) & 0xFFFFFFFF, int(hi) & 0xFFFFFFFF, int(flags), 0)
 
 
 class Stats(C.Structure):
@@ -266,6 +283,8 @@ def load_library(build_if_missing=True):
     L.hjgpu_npj_lookup_table.argtypes = [vp, vp, sz, vp, sz, u32, vp, vp, C.POINTER(Result), vp]
     L.hjgpu_lookup_selected.argtypes = [vp, vp, vp, sz, vp, sz, C.POINTER(NpjParams), vp, vp, vp, C.POINTER(Result), vp]
     L.hjgpu_lookup_selected_async.argtypes = [vp, vp, vp, sz, vp, sz, C.POINTER(NpjParams), vp, vp, vp, vp, vp]
+    L.hjgpu_filter_selected.argtypes = [vp, vp, sz, u32, C.POINTER(vp), C.POINTER(Predicate), vp, u64p, vp]
+    L.hjgpu_filter_selected_async.argtypes = [vp, vp, sz, u32, C.POINTER(vp), C.POINTER(Predicate), vp, vp, vp]
     L.hjgpu_compact_selected.argtypes = [vp, vp, sz, u32, C.POINTER(vp), C.POINTER(vp), vp, sz, u64p, vp]
     L.hjgpu_compact_selected_async.argtypes = [vp, vp, sz, u32, C.POINTER(vp), C.POINTER(vp), vp, sz, vp, vp]
     group = [vp, vp, sz, u32, C.POINTER(vp), u32, C.POINTER(vp), C.POINTER(vp), vp, C.POINTER(vp), sz]
@@ -418,7 +437,8 @@ class HjGpu:
         """hjgpu_get_counter: "probe_fallbacks" (claimed probe sides done again exactly), "probe_exact" (1: exact path from now on),
         "lookup_lds_rows" (largest build side that hjgpu_lookup answers from LDS tables; 0 under option no_broadcast),
         "compact_ranges" / "compact_chunk_rows" (compact_selected's geometry: its ranges, and the rows of a chunk),
-        "group_lds_groups" (the distinct groups a workgroup's LDS table of group_sum holds before further ones go to device memory)."""
+        "group_lds_groups" (the distinct groups a workgroup's LDS table of group_sum holds before further ones go to device memory),
+        "filter_step_rows" (the rows filter_selected's whole grid covers in one iteration of its loop)."""
         v = C.c_uint64()
         self._check(self.lib.hjgpu_get_counter(self.handle, name.encode(), C.byref(v)))
         return v.value
@@ -544,6 +564,34 @@ class HjGpu:
                                                              self._ptr(select_bits), self._ptr(vals_out), self._ptr(match_bits),
                                                              C.byref(r), stream))
         return r.as_tuple()
+
+    # ---- filter: range predicates over columns into a bitmap (match_bits' layout), in place or not ---------------------------------
+    def _filter_args(self, cols, preds):
+        cols, preds = list(cols or ()), list(preds or ())
+        if len(cols) != len(preds):
+            raise ValueError("filter_selected: %d columns, %d predicates" % (len(cols), len(preds)))
+        if not cols:                        # (the library refuses npreds == 0)
+            return 0, None, None
+        return (len(cols), (C.c_void_p * len(cols))(*[self._ptr(c) for c in cols]),
+                (Predicate * len(preds))(*[Predicate.of(p) for p in preds]))
+
+    def filter_selected(self, select_bits, n, cols, preds, bits_out=None, stream=None):
+        """hjgpu_filter_selected: row i passes when its bit is set in select_bits (match_bits' layout; None: every row) and every
+        predicate holds on its column: preds[p] = (lo, hi[, flags]) or a Predicate says lo <= cols[p][i] <= hi, both ends inclusive, unsigned
+        or - PRED_SIGNED - as int32, inverted under PRED_NOT; lo > hi is the empty range.  bits_out ((n + 31) // 32 uint32, or None: the
+        count alone) receives the passing rows' bitmap and may be select_bits itself.  Put the most selective predicate first: a later
+        column is read only where an earlier one left a row.  Returns the number of passing rows."""
+        npreds, dcols, dpreds = self._filter_args(cols, preds)
+        count = C.c_uint64()
+        self._check(self.lib.hjgpu_filter_selected(self.handle, self._ptr(select_bits), n, npreds, dcols, dpreds, self._ptr(bits_out),
+                                                   C.byref(count), stream))
+        return count.value
+
+    def filter_selected_async(self, select_bits, n, cols, preds, bits_out, d_count, stream=None):
+        """hjgpu_filter_selected_async: enqueue only; the number of passing rows goes to d_count (uint64 in device memory, or None)"""
+        npreds, dcols, dpreds = self._filter_args(cols, preds)
+        self._check(self.lib.hjgpu_filter_selected_async(self.handle, self._ptr(select_bits), n, npreds, dcols, dpreds, self._ptr(bits_out),
+                                                         self._ptr(d_count), stream))
 
     # ---- compaction by bitmap: the selected rows of the columns, dense and in input order ----------------------------------------
     def _compact_args(self, cols_in, cols_out, rows_out, capacity):

@@ -825,3 +825,99 @@ int hj_launch_group_emit(const GroupEmitArgs &a, int cus, hipStream_t stream)
     hipLaunchKernelGGL(group_emit_kernel, dim3((uint32_t)std::min<u64>(need, (u64)cus * 8)), dim3(256), 0, stream, a);
     return hipGetLastError() == hipSuccess ? HJGPU_OK : HJGPU_EHIP;
 }
+
+// ---- filter (hjgpu_filter_selected; DESIGN.md section 5 "Filter") -----------------------------------------------------------------------
+// Range predicates over columns into a bitmap: row i passes when it is selected and, for every p < NPREDS, filter_layout.hpp's passes()
+// holds on cols[p][i].  One persistent grid; an iteration is BATCH wave trips of hj_lookup.hpp's layout (lane L owns rows 4 L ... 4 L + 3
+// of a trip, a group of 8 lanes one word of either bitmap and one 128-byte line of every column).  The head is lookup_fetch: both trips'
+// mask words (SEL), then column 0 - a group whose word is 0 loads nothing -, the nibble cut at n.  Column p >= 1 is loaded only by the
+// lanes whose nibble is still not 0 behind predicates 0 ... p - 1, both trips' loads before either is tested: the caller's order is the
+// evaluation order, and a column line none of whose 32 rows can still pass is never fetched.  Everything non-temporal; the last, partial
+// vector of a column is loaded whole and masked, as lookup_fetch does.
+// The bitmap word: lookup_leave's combine - three DPP steps OR the 8 lanes' nibbles, the group's first lane stores the word when its first
+// row is below n, so the last word's high bits leave as 0 and nothing at word (n + 31) / 32 or beyond is written.  hj_lookup.hpp's IN-PLACE
+// RULE holds: bits_out may be select_bits, a word is read only by the wave that stores it and before it stores it (the store depends on
+// the load); neither pointer is __restrict__.  The count: popcount per lane, the wave's sum, the four waves' through 32 bytes of LDS - the
+// kernel's only LDS, behind the loop -, ONE 64-bit atomic add per workgroup.  No workgroup waits for another.
+__device__ __forceinline__ uint32_t filter_nibble(const uint4 &x, const hj_filter::Norm &p)
+{
+    return (hj_filter::passes(p, x.x) ? 1u : 0u) | (hj_filter::passes(p, x.y) ? 2u : 0u) | (hj_filter::passes(p, x.z) ? 4u : 0u) |
+           (hj_filter::passes(p, x.w) ? 8u : 0u);
+}
+
+template <int NPREDS, bool SEL>
+__global__ __launch_bounds__(hj_filter::BLOCK) void filter_kernel(FilterArgs a)
+{
+    using namespace hj_filter;
+    __shared__ u64 red[BLOCK / 64];
+    const uint32_t tid = threadIdx.x;
+    const u64 n = a.n, nvec = (n + 3) >> 2, stride = (u64)gridDim.x * BLOCK;
+    const uint4 *c0 = reinterpret_cast<const uint4 *>(a.cols[0]);
+    u64 passed = 0;
+    for (u64 v0 = (u64)blockIdx.x * BLOCK + (tid & ~63u); v0 < nvec; v0 += stride * BATCH) {
+        uint32_t nib[BATCH];
+        uint4 x[BATCH];
+        lookup_fetch<SEL, (int)BATCH, true>(a.select_bits, c0, v0, stride, n, nib, x);
+#pragma unroll
+        for (int u = 0; u < (int)BATCH; ++u) nib[u] &= filter_nibble(x[u], a.preds[0]);
+#pragma unroll
+        for (int p = 1; p < NPREDS; ++p) {
+            const uint4 *cp = reinterpret_cast<const uint4 *>(a.cols[p]);
+#pragma unroll
+            for (int u = 0; u < (int)BATCH; ++u) {
+                x[u] = make_uint4(0, 0, 0, 0);
+                if (nib[u]) x[u] = hj_load_nt(cp + v0 + (u64)u * stride + hj_lane());      // (nib != 0 only where the vector starts below n)
+            }
+#pragma unroll
+            for (int u = 0; u < (int)BATCH; ++u) nib[u] &= filter_nibble(x[u], a.preds[p]);
+        }
+#pragma unroll
+        for (int u = 0; u < (int)BATCH; ++u) {
+            passed += __popc(nib[u]);
+            if (a.bits_out) {
+                const u64 v = v0 + (u64)u * stride + hj_lane();
+                // 8 lanes x 4 rows = one word: OR over each group of 8 lanes, its first lane stores (all 64 lanes are here: v0 is the wave's)
+                uint32_t w = nib[u] << ((tid & 7u) * 4);
+                w |= hj_dpp<0xB1>(w);                                   // quad_perm: lanes 0<->1, 2<->3
+                w |= hj_dpp<0x4E>(w);                                   // quad_perm: lanes 0<->2, 1<->3
+                w |= hj_dpp<0x141>(w);                                  // row_half_mirror: lane i <-> 7 - i of the group, the other quad
+                // (v is a multiple of 8 in the storing lane: word v / 8 starts at row 4 v; a word whose first row is at n or beyond is not stored)
+                if ((tid & 7u) == 0 && (v << 2) < n) hj_store(a.bits_out + (v >> 3), w);
+            }
+        }
+    }
+    if (a.count) {
+        passed = wave_reduce_sum(passed);
+        if (hj_lane() == 0) red[tid >> 6] = passed;
+        __syncthreads();
+        if (tid == 0) {
+            u64 s = 0;
+#pragma unroll
+            for (uint32_t w = 0; w < BLOCK / 64; ++w) s += red[w];
+            if (s) atomicAdd(a.count, s);
+        }
+    }
+}
+
+// filter_layout.hpp's grid, no more workgroups than the rows have wave trips for
+int hj_launch_filter(const FilterArgs &a, uint32_t npreds, int cus, hipStream_t stream)
+{
+    using namespace hj_filter;
+    if (a.n == 0) return HJGPU_OK;
+    if (npreds < 1 || npreds > MAX_PREDS || (!a.bits_out && !a.count) || cus < 1) return HJGPU_EINVAL;
+    uintptr_t all = (uintptr_t)a.select_bits | (uintptr_t)a.bits_out;
+    for (uint32_t p = 0; p < npreds; ++p) { if (!a.cols[p]) return HJGPU_EINVAL; all |= (uintptr_t)a.cols[p]; }
+    if ((all & 15) || ((uintptr_t)a.count & 7)) return HJGPU_EINVAL;
+    const u64 nvec = (a.n + 3) >> 2, need = (nvec + BLOCK - 1) / BLOCK;
+    const dim3 grid((uint32_t)std::min<u64>(need, (u64)grid_of(cus)));
+    hj_with_bool(a.select_bits != nullptr, [&](auto sel) {
+        constexpr bool S = decltype(sel)::value;
+        switch (npreds) {
+        case 1: hipLaunchKernelGGL((filter_kernel<1, S>), grid, dim3(BLOCK), 0, stream, a); break;
+        case 2: hipLaunchKernelGGL((filter_kernel<2, S>), grid, dim3(BLOCK), 0, stream, a); break;
+        case 3: hipLaunchKernelGGL((filter_kernel<3, S>), grid, dim3(BLOCK), 0, stream, a); break;
+        default: hipLaunchKernelGGL((filter_kernel<4, S>), grid, dim3(BLOCK), 0, stream, a); break;
+        }
+    });
+    return hipGetLastError() == hipSuccess ? HJGPU_OK : HJGPU_EHIP;
+}

@@ -6,6 +6,7 @@
 #include <type_traits>
 #include "../../include/hjgpu.h"
 #include "compact_layout.hpp"
+#include "filter_layout.hpp"
 #include "group_layout.hpp"
 #include "scatter_layout.hpp"
 
@@ -521,6 +522,20 @@ struct GroupEmitArgs {
 };
 int hj_launch_group_sum(const GroupArgs &a, int cus, hipStream_t stream);
 int hj_launch_group_emit(const GroupEmitArgs &a, int cus, hipStream_t stream);
+
+// Filter (hjgpu_filter_selected*, gen_kernels.hip; DESIGN.md section 5 "Filter"): one persistent grid of filter_layout.hpp's geometry.  Row
+// i < n passes when it is selected (select_bits NULL: every row) and preds[p] holds on cols[p][i] for every p < npreds; bits_out (NULL:
+// no bitmap; it may be select_bits itself) receives the passing rows in match_bits' layout, and their number is ADDED to *count (NULL:
+// no count), which is 0 before the launch.  The mask and all columns 16-byte aligned; n == 0 launches nothing.
+struct FilterArgs {
+    const uint32_t *select_bits;         // NULL: every row
+    uint32_t *bits_out;                  // NULL: the count alone
+    u64 *count;                          // NULL: the bitmap alone
+    u64 n;
+    const uint32_t *cols[hj_filter::MAX_PREDS];
+    hj_filter::Norm preds[hj_filter::MAX_PREDS];
+};
+int hj_launch_filter(const FilterArgs &a, uint32_t npreds, int cus, hipStream_t stream);
 
 // K9: compact the per-wave partially filled tail blocks (npj.cpp:475-514).
 // moves: scratch of 2*HJ_MAX_WORKERS entries of 24 bytes + HJ_MAX_WORKERS entries of 8 bytes.

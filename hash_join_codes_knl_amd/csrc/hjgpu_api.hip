@@ -1382,7 +1382,7 @@ int hjgpu_destroy(hjgpu_ctx *ctx)
     (void)hipDeviceSynchronize();
     DevBuf *all[] = {&ctx->tmp[0], &ctx->tmp[1], &ctx->tmp[2], &ctx->tmp[3], &ctx->tmp[4], &ctx->tmp[5],
                      &ctx->tmp[6], &ctx->tmp[7], &ctx->meta, &ctx->table, &ctx->state, &ctx->moves,
-                     &ctx->final_offsets, &ctx->build_bits, &ctx->grp[0], &ctx->grp[1], &ctx->grp[2], &ctx->grp[3], &ctx->grp_off, &ctx->audit, &ctx->audit_lay, &ctx->compact, &ctx->group};
+                     &ctx->final_offsets, &ctx->build_bits, &ctx->grp[0], &ctx->grp[1], &ctx->grp[2], &ctx->grp[3], &ctx->grp_off, &ctx->audit, &ctx->audit_lay, &ctx->compact, &ctx->group, &ctx->filter};
     for (DevBuf *b : all) if (b->p) (void)hipFree(b->p);
     for (int i = 0; i < EV_COUNT; ++i) (void)hipEventDestroy(ctx->ev[i]);
     if (ctx->aux) (void)hipStreamDestroy(ctx->aux);
@@ -1461,7 +1461,8 @@ int hjgpu_get_counter(hjgpu_ctx *ctx, const char *name, uint64_t *value)
     if (strcmp(name, "compact_ranges") == 0) { *value = hj_compact::ranges_of(ctx->cus); return HJGPU_OK; }
     if (strcmp(name, "compact_chunk_rows") == 0) { *value = hj_compact::CHUNK_ROWS; return HJGPU_OK; }
     if (strcmp(name, "group_lds_groups") == 0) { *value = hj_group::LDS_GROUPS; return HJGPU_OK; }
-    return fail(ctx, HJGPU_EINVAL, "unknown counter (probe_fallbacks, probe_exact, lookup_lds_rows, compact_ranges, compact_chunk_rows, group_lds_groups)");
+    if (strcmp(name, "filter_step_rows") == 0) { *value = hj_filter::step_rows(ctx->cus); return HJGPU_OK; }
+    return fail(ctx, HJGPU_EINVAL, "unknown counter (probe_fallbacks, probe_exact, lookup_lds_rows, compact_ranges, compact_chunk_rows, group_lds_groups, filter_step_rows)");
 }
 
 // the workspace's side of hjgpu_stats: what the context has spent growing it, and its last placement search
@@ -1537,6 +1538,15 @@ int hjgpu_get_stats(hjgpu_ctx *ctx, hjgpu_stats *s)
         r.ms_histogram = span(EV_BEGIN, EV_S_HIST);
         r.ms_join = span(EV_S_HIST, EV_JOIN);
         r.ms_close_gaps = span(EV_JOIN, EV_GAPS);
+        fill_reserve(ctx, &r);
+        *s = r;
+        return HJGPU_OK;
+    }
+    if (ctx->last_algo == 5) {                 // hjgpu_filter_selected: the clear of the count word, then the kernel
+        memset(&r, 0, sizeof(r));
+        r.ms_total = span(EV_BEGIN, EV_GAPS);
+        r.ms_histogram = span(EV_BEGIN, EV_S_HIST);
+        r.ms_join = span(EV_S_HIST, EV_JOIN);
         fill_reserve(ctx, &r);
         *s = r;
         return HJGPU_OK;

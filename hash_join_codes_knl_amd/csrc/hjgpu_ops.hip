@@ -714,6 +714,114 @@ int hjgpu_group_sum(hjgpu_ctx *ctx, const uint32_t *d_select_bits, size_t n, uin
     return HJGPU_OK;
 }
 
+// ---- filter -----------------------------------------------------------------------
+// hjgpu_filter_selected / _async (DESIGN.md section 5 "Filter").  Every refusal is decided here, from the arguments alone, before anything is
+// allocated or enqueued.
+struct FilterCall {
+    const uint32_t *bits;
+    size_t n;
+    uint32_t npreds;
+    const uint32_t *const *cols;
+    const hjgpu_predicate *preds;
+    uint32_t *bits_out;
+};
+
+static int check_filter(hjgpu_ctx *ctx, const FilterCall &f, const uint64_t *count, bool device_count)
+{
+    if (device_count && ((uintptr_t)count & 7)) return fail(ctx, HJGPU_EALIGN, "d_count must be 8-byte aligned");
+    if (f.npreds == 0 || f.npreds > HJGPU_FILTER_MAX_PREDS) return fail(ctx, HJGPU_EINVAL, "npreds must be 1 to HJGPU_FILTER_MAX_PREDS (4)");
+    if (f.n == 0) return HJGPU_OK;                       // nothing is read, nothing but the count is written: anything else may be NULL
+    if (!f.bits_out && !count) return fail(ctx, HJGPU_EINVAL, "d_bits_out and the count are both null: nothing to compute");
+    if ((uintptr_t)f.bits & 15) return fail(ctx, HJGPU_EALIGN, "d_select_bits must be 16-byte aligned");
+    if ((uintptr_t)f.bits_out & 15) return fail(ctx, HJGPU_EALIGN, "d_bits_out must be 16-byte aligned");
+    if (!f.cols || !f.preds) return fail(ctx, HJGPU_EINVAL, "null column or predicate array");
+    for (uint32_t p = 0; p < f.npreds; ++p) {
+        if (!f.cols[p]) return fail(ctx, HJGPU_EINVAL, "null column pointer");
+        if ((uintptr_t)f.cols[p] & 15) return fail(ctx, HJGPU_EALIGN, "columns must be 16-byte aligned");
+        if (f.preds[p].flags & ~(HJGPU_PRED_NOT | HJGPU_PRED_SIGNED)) return fail(ctx, HJGPU_EINVAL, "unknown predicate flag (HJGPU_PRED_NOT and HJGPU_PRED_SIGNED are defined)");
+        if (f.preds[p].reserved) return fail(ctx, HJGPU_EINVAL, "a predicate's reserved word must be 0");
+    }
+    // in place: d_bits_out may be the very pointer d_select_bits - the kernel reads a word of the mask in the wave that stores it, before
+    // it stores it -; two bitmaps that overlap in any other way would be read after they were written
+    const size_t mbytes = (f.n + 31) / 32 * sizeof(uint32_t), cbytes = f.n * sizeof(uint32_t);
+    if (f.bits && f.bits_out && f.bits != f.bits_out && ranges_overlap(f.bits_out, mbytes, f.bits, mbytes))
+        return fail(ctx, HJGPU_EINVAL, "d_bits_out overlaps d_select_bits: it may be the very pointer d_select_bits (in place), any other overlap of the two bitmaps is refused");
+    // no output may share a byte with a column or with the other output; the device count word none with the mask either
+    for (uint32_t p = 0; p < f.npreds; ++p) {
+        if (ranges_overlap(f.bits_out, f.bits_out ? mbytes : 0, f.cols[p], cbytes)) return fail(ctx, HJGPU_EINVAL, "d_bits_out overlaps a column");
+        if (device_count && ranges_overlap(count, count ? sizeof(uint64_t) : 0, f.cols[p], cbytes)) return fail(ctx, HJGPU_EINVAL, "d_count overlaps a column");
+    }
+    if (device_count && count) {
+        if (ranges_overlap(count, sizeof(uint64_t), f.bits_out, f.bits_out ? mbytes : 0)) return fail(ctx, HJGPU_EINVAL, "d_count overlaps d_bits_out");
+        if (ranges_overlap(count, sizeof(uint64_t), f.bits, f.bits ? mbytes : 0)) return fail(ctx, HJGPU_EINVAL, "d_count overlaps d_select_bits");
+    }
+    return HJGPU_OK;
+}
+
+// the context's count word (the blocking form's; made by the first call of either form)
+static int filter_workspace(hjgpu_ctx *ctx, u64 **word)
+{
+    CHK(ensure(ctx, ctx->filter, sizeof(u64)));
+    *word = reinterpret_cast<u64 *>(ctx->filter.p);
+    return HJGPU_OK;
+}
+
+// the two enqueues behind the checks: the clear of the count word (d_count NULL: none), the kernel (n == 0: none).  hjgpu_get_stats
+// afterwards: ms_histogram = the clear, ms_join = the kernel, ms_total = both
+static int filter_enqueue(hjgpu_ctx *ctx, const FilterCall &f, u64 *d_count, hipStream_t stream)
+{
+    for (int i = 0; i < EV_COUNT; ++i) ctx->ev_valid[i] = false;
+    ctx->last_algo = 5;
+    record(ctx, EV_BEGIN, stream);
+    if (d_count) HIPCHK(ctx, hj_zero_async(d_count, sizeof(u64), stream));
+    record(ctx, EV_S_HIST, stream);
+    if (f.n) {
+        FilterArgs a{};
+        a.select_bits = f.bits; a.bits_out = f.bits_out; a.count = d_count; a.n = f.n;
+        for (uint32_t p = 0; p < f.npreds; ++p) {
+            a.cols[p] = f.cols[p];
+            a.preds[p] = hj_filter::normalise(f.preds[p].lo, f.preds[p].hi, f.preds[p].flags);
+        }
+        CHK(hj_launch_filter(a, f.npreds, ctx->cus, stream));
+    }
+    record(ctx, EV_JOIN, stream);
+    record(ctx, EV_GAPS, stream);
+    return HJGPU_OK;
+}
+
+int hjgpu_filter_selected_async(hjgpu_ctx *ctx, const uint32_t *d_select_bits, size_t n, uint32_t npreds, const uint32_t *const *d_cols,
+                                const hjgpu_predicate *preds, uint32_t *d_bits_out, uint64_t *d_count, void *stream_)
+{
+    if (!ctx) return HJGPU_EINVAL;
+    const FilterCall f{d_select_bits, n, npreds, d_cols, preds, d_bits_out};
+    CHK(check_filter(ctx, f, d_count, true));
+    hipStream_t stream = (hipStream_t)stream_;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    CHK(refuse_capture(ctx, stream));
+    u64 *word = nullptr;
+    CHK(filter_workspace(ctx, &word));
+    return filter_enqueue(ctx, f, reinterpret_cast<u64 *>(d_count), stream);
+}
+
+int hjgpu_filter_selected(hjgpu_ctx *ctx, const uint32_t *d_select_bits, size_t n, uint32_t npreds, const uint32_t *const *d_cols,
+                          const hjgpu_predicate *preds, uint32_t *d_bits_out, uint64_t *count, void *stream_)
+{
+    if (!ctx) return HJGPU_EINVAL;
+    const FilterCall f{d_select_bits, n, npreds, d_cols, preds, d_bits_out};
+    CHK(check_filter(ctx, f, count, false));
+    hipStream_t stream = (hipStream_t)stream_;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    CHK(refuse_capture(ctx, stream));
+    u64 *word = nullptr;
+    CHK(filter_workspace(ctx, &word));
+    CHK(filter_enqueue(ctx, f, count ? word : nullptr, stream));
+    u64 got = 0;
+    if (count) HIPCHK(ctx, hipMemcpyAsync(&got, word, sizeof(got), hipMemcpyDeviceToHost, stream));
+    HIPCHK(ctx, hipStreamSynchronize(stream));
+    if (count) *count = got;
+    return HJGPU_OK;
+}
+
 int hjgpu_stream_read_ms(hjgpu_ctx *ctx, const void *d_ptr, size_t bytes, float *ms, void *stream_)
 {
     if (!ctx || !d_ptr || !ms) return HJGPU_EINVAL;

@@ -268,7 +268,9 @@ int  hjgpu_get_stats(hjgpu_ctx *ctx, hjgpu_stats *stats);
  *   "compact_ranges", "compact_chunk_rows"   hjgpu_compact_selected's geometry: the ranges (= workgroups) its rows are cut into, and the
  *                      rows of a chunk, of which every range holds a whole number
  *   "group_lds_groups" the distinct groups a workgroup's LDS table of hjgpu_group_sum holds before its further groups go straight to the
- *                      merge table in device memory */
+ *                      merge table in device memory
+ *   "filter_step_rows" the rows that hjgpu_filter_selected's whole grid covers in one iteration of its loop (the grid is smaller when the
+ *                      rows are fewer) */
 int  hjgpu_get_counter(hjgpu_ctx *ctx, const char *name, uint64_t *value);
 
 /* ---- device memory helpers for hosts that do not link HIP (mamalloc/free,
@@ -435,6 +437,56 @@ int  hjgpu_npj_lookup_table_selected(hjgpu_ctx *ctx, const uint32_t *d_keys, siz
                                      const uint32_t *d_select_bits,
                                      uint32_t *d_vals_out, uint32_t *d_match_bits,
                                      hjgpu_result *result, void *stream);
+
+/* ---- filter: range predicates over up to 4 columns into a bitmap --------------------------------------------
+ * What makes, or narrows, a bitmap in d_match_bits' layout from the fact table's own columns - lo_discount BETWEEN 1 AND 3 AND lo_quantity
+ * < 25, a date range, a status code - and from a looked-up value column (d_year BETWEEN 1992 AND 1997): the other half of a star query's
+ * WHERE clause, in front of, between and behind the selected look-ups.  Row i < n PASSES when it is selected and every predicate p < npreds
+ * holds on d_cols[p][i]:
+ *   a predicate      {lo, hi, flags, reserved} holds on x when lo <= x <= hi, BOTH ENDS INCLUSIVE; the compare is unsigned, or - HJGPU_PRED_SIGNED
+ *                    - lo, hi and the column are int32 (two's complement order).  HJGPU_PRED_NOT inverts the predicate: the rows outside
+ *                    [lo, hi] pass.  lo > hi in the predicate's order is the empty range and is legal: nothing passes, or everything under
+ *                    HJGPU_PRED_NOT.  Equality is lo == hi, "x < c" is [0, c - 1] (signed: [INT32_MIN, c - 1]).  A flag bit outside the two
+ *                    defined, or reserved != 0, is HJGPU_EINVAL.
+ *   HJGPU_NULL_VAL   in a looked-up column is the ordinary value 0xFFFFFFFF: an unsigned range with hi < 0xFFFFFFFF drops the unmatched rows, a
+ *                    signed one sees them as -1.
+ *   d_bits_out       (n + 31) / 32 words in d_match_bits' layout: bit i & 31 of word i >> 5 is 1 exactly when row i passes.  The last word's
+ *                    bits at positions >= n are written 0, no word at index >= (n + 31) / 32 is written.  16-byte aligned (HJGPU_EALIGN).
+ *   count            *count (blocking form, host memory) / *d_count (_async form, device memory, 8-byte aligned: HJGPU_EALIGN) = the number
+ *                    of passing rows, exact.  Either d_bits_out or the count may be NULL - the count alone, the bitmap alone -; both NULL
+ *                    with n > 0 is HJGPU_EINVAL.
+ *   d_select_bits    hjgpu_lookup_selected's mask, word for word: (n + 31) / 32 words, bit i & 31 of word i >> 5 selects row i, bits of the
+ *                    last word at positions >= n are ignored, no word at index >= (n + 31) / 32 is read.  16-byte aligned (HJGPU_EALIGN).
+ *                    NULL selects every row.
+ *   in place         d_bits_out may be the very pointer d_select_bits: afterwards the bitmap is select AND pass (the last word's high bits
+ *                    0), as the selected look-ups narrow theirs.  Any other overlap of the two bitmaps is HJGPU_EINVAL.
+ *   d_cols, preds    HOST arrays of npreds entries, copied by value into the kernel arguments.  npreds is 1 to HJGPU_FILTER_MAX_PREDS; 0,
+ *                    more, and a NULL column among the first npreds are HJGPU_EINVAL.  The same column may appear twice (two ranges on one
+ *                    column, for example two HJGPU_PRED_NOT ranges).  Columns hold n uint32 and are 16-byte aligned (HJGPU_EALIGN); no row
+ *                    at n or beyond is read, except inside a column's last 16-byte vector.  Columns and the mask are never written.
+ *   order            the predicates are evaluated in the caller's order, and column p >= 1 is read only where a row of its 128-byte line
+ *                    has passed the mask and predicates 0 ... p - 1: MOST SELECTIVE FIRST.  The result does not depend on the order.
+ *   overlap          d_bits_out's bytes, or the _async form's count word, that overlap a column's [p, p + 4 * n) or each other (the count
+ *                    word: or the mask): HJGPU_EINVAL, "overlaps" in hjgpu_last_error.
+ *   n == 0           reads nothing, writes nothing but the count (0), accepts NULL everywhere else.
+ * OR between predicates is one elementwise OR of two bitmaps, which the caller has; an IN-list is a look-up.
+ * Every refusal is decided from the arguments alone, before anything is enqueued or allocated; a capturing stream is HJGPU_EINVAL.  Neither
+ * form touches what hjgpu_get_async_status / hjgpu_accumulate_async_status report.  The _async form only enqueues and needs no
+ * hjgpu_reserve: the only workspace is one count word per context, made the first time either form runs, so calls may be queued back to
+ * back on one stream of one context.  Two enqueues ordered by the stream - the clear of the count word, then ONE kernel on a persistent grid
+ * that streams the mask and the columns once - and no workgroup waits for another.  hjgpu_get_stats afterwards: ms_total = both,
+ * ms_histogram = the clear, ms_join = the kernel, every other phase 0, fanout1 = fanout2 = buckets = groups = 0.  hjgpu_get_counter
+ * "filter_step_rows": the rows the whole grid covers in one iteration of its loop. */
+#define HJGPU_FILTER_MAX_PREDS 4u
+#define HJGPU_PRED_NOT    1u   /* the rows OUTSIDE [lo, hi] pass */
+#define HJGPU_PRED_SIGNED 2u   /* lo, hi and the column are int32 (two's complement order) */
+typedef struct { uint32_t lo, hi, flags, reserved; } hjgpu_predicate;
+int  hjgpu_filter_selected(hjgpu_ctx *ctx, const uint32_t *d_select_bits, size_t n,
+                           uint32_t npreds, const uint32_t *const *d_cols, const hjgpu_predicate *preds,
+                           uint32_t *d_bits_out, uint64_t *count, void *stream);
+int  hjgpu_filter_selected_async(hjgpu_ctx *ctx, const uint32_t *d_select_bits, size_t n,
+                                 uint32_t npreds, const uint32_t *const *d_cols, const hjgpu_predicate *preds,
+                                 uint32_t *d_bits_out, uint64_t *d_count, void *stream);
 
 /* ---- compaction by bitmap: the selected rows of up to 8 columns, dense and in order ----------------------
  * What turns a bitmap in d_match_bits' layout and full-length columns into dense rows - at the end of a chain of selected look-ups (the
