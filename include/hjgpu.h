@@ -314,7 +314,9 @@ int  hjgpu_partition_async(hjgpu_ctx *ctx, const uint32_t *d_keys, const uint32_
  * R rows [d_inner_offsets[p], [p+1]) are loaded into an LDS hash table and S rows
  * [d_outer_offsets[p], [p+1]) probe it.  (factor1, fanout1, factor2, fanout2)
  * must be the passes that produced the partitions (needed to pick a per-partition
- * empty sentinel, phj.cpp:1886-1897; fanout2 = 1 for a single pass). */
+ * empty sentinel, phj.cpp:1886-1897; fanout2 = 1 for a single pass).
+ * The offsets need not start at 0 nor end where the columns do: only rows [d_*_offsets[0], d_*_offsets[P]) of a relation take
+ * part, whatever lies in front of and behind them (P = fanout1 * fanout2; P + 1 non-decreasing offsets per relation). */
 int  hjgpu_join_partitions(hjgpu_ctx *ctx,
                            const uint32_t *d_inner_keys, const uint32_t *d_inner_vals,
                            const uint64_t *d_inner_offsets,
