@@ -13,7 +13,7 @@ import numpy as np
 
 from . import build as _build
 
-OK, EINVAL, EALIGN, ENOMEM, EHIP, EZEROKEY, EOVERFLOW, ENODEVICE, ERCCL = range(9)
+OK, EINVAL, EALIGN, ENOMEM, EHIP, EZEROKEY, EOVERFLOW, ENODEVICE, ERCCL, ERANGE = range(10)
 TRANSPORT_RCCL, TRANSPORT_LOOPBACK = 0, 1
 MAX_FANOUT = 1024
 MAX_PARTS = 32768
@@ -29,6 +29,7 @@ NULL_VAL = 0xFFFFFFFF   # HJGPU_NULL_VAL: the value on the side without a match 
 FILTER_MAX_PREDS = 4    # HJGPU_FILTER_MAX_PREDS
 PRED_NOT = 1            # HJGPU_PRED_NOT: the rows OUTSIDE [lo, hi] pass
 PRED_SIGNED = 2         # HJGPU_PRED_SIGNED: lo, hi and the column are int32 (two's complement order)
+GATHER_MAX_COLS = 4     # HJGPU_GATHER_MAX_COLS
 
 EXPORTS = [
     "hjgpu_kernel_hash", "hjgpu_library_hash", "hjgpu_device_count", "hjgpu_create", "hjgpu_destroy", "hjgpu_last_error", "hjgpu_status_string",
@@ -41,6 +42,7 @@ EXPORTS = [
     "hjgpu_npj_lookup", "hjgpu_npj_lookup_async", "hjgpu_npj_lookup_table", "hjgpu_lookup", "hjgpu_lookup_async",
     "hjgpu_lookup_selected", "hjgpu_lookup_selected_async", "hjgpu_npj_lookup_table_selected",
     "hjgpu_filter_selected", "hjgpu_filter_selected_async",
+    "hjgpu_gather_selected", "hjgpu_gather_selected_async",
     "hjgpu_compact_selected", "hjgpu_compact_selected_async",
     "hjgpu_group_sum", "hjgpu_group_sum_async",
     "hjgpu_npj", "hjgpu_phj", "hjgpu_cpra",
@@ -285,6 +287,8 @@ def load_library(build_if_missing=True):
     L.hjgpu_lookup_selected_async.argtypes = [vp, vp, vp, sz, vp, sz, C.POINTER(NpjParams), vp, vp, vp, vp, vp]
     L.hjgpu_filter_selected.argtypes = [vp, vp, sz, u32, C.POINTER(vp), C.POINTER(Predicate), vp, u64p, vp]
     L.hjgpu_filter_selected_async.argtypes = [vp, vp, sz, u32, C.POINTER(vp), C.POINTER(Predicate), vp, vp, vp]
+    L.hjgpu_gather_selected.argtypes = [vp, vp, vp, sz, u32, C.POINTER(vp), sz, C.POINTER(vp), vp, u64p, vp]
+    L.hjgpu_gather_selected_async.argtypes = [vp, vp, vp, sz, u32, C.POINTER(vp), sz, C.POINTER(vp), vp, vp, vp]
     L.hjgpu_compact_selected.argtypes = [vp, vp, sz, u32, C.POINTER(vp), C.POINTER(vp), vp, sz, u64p, vp]
     L.hjgpu_compact_selected_async.argtypes = [vp, vp, sz, u32, C.POINTER(vp), C.POINTER(vp), vp, sz, vp, vp]
     group = [vp, vp, sz, u32, C.POINTER(vp), u32, C.POINTER(vp), C.POINTER(vp), vp, C.POINTER(vp), sz]
@@ -438,7 +442,8 @@ class HjGpu:
         "lookup_lds_rows" (largest build side that hjgpu_lookup answers from LDS tables; 0 under option no_broadcast),
         "compact_ranges" / "compact_chunk_rows" (compact_selected's geometry: its ranges, and the rows of a chunk),
         "group_lds_groups" (the distinct groups a workgroup's LDS table of group_sum holds before further ones go to device memory),
-        "filter_step_rows" (the rows filter_selected's whole grid covers in one iteration of its loop)."""
+        "filter_step_rows" / "gather_step_rows" (the rows filter_selected's / gather_selected's whole grid covers in one iteration of its
+        loop)."""
         v = C.c_uint64()
         self._check(self.lib.hjgpu_get_counter(self.handle, name.encode(), C.byref(v)))
         return v.value
@@ -592,6 +597,40 @@ class HjGpu:
         npreds, dcols, dpreds = self._filter_args(cols, preds)
         self._check(self.lib.hjgpu_filter_selected_async(self.handle, self._ptr(select_bits), n, npreds, dcols, dpreds, self._ptr(bits_out),
                                                          self._ptr(d_count), stream))
+
+    # ---- gather by row number: columns fetched by an index column under a bitmap, in position --------------------------------------
+    def _gather_args(self, src_cols, cols_out):
+        src_cols, cols_out = list(src_cols or ()), list(cols_out or ())
+        if len(src_cols) != len(cols_out):
+            raise ValueError("gather_selected: %d source columns, %d output columns" % (len(src_cols), len(cols_out)))
+        if not src_cols:                    # (the library refuses ncols == 0)
+            return 0, None, None
+        arr = C.c_void_p * len(src_cols)
+        return len(src_cols), arr(*[self._ptr(c) for c in src_cols]), arr(*[self._ptr(c) for c in cols_out])
+
+    def gather_selected(self, select_bits, idx, n, src_cols, src_rows, cols_out, bits_out=None, stream=None):
+        """hjgpu_gather_selected: cols_out[c][i] = src_cols[c][idx[i]] for every row i < n whose bit is set in select_bits (match_bits'
+        layout; None: every row) and whose index is below src_rows; every other row gets NULL_VAL and reads no source element.  bits_out
+        ((n + 31) // 32 uint32, or None) receives the gathered rows' bitmap and may be select_bits itself; one of cols_out may be idx
+        itself.  Up to GATHER_MAX_COLS columns.  Returns (gathered, out_of_range); a selected row whose index is neither below src_rows nor
+        NULL_VAL raises HjGpuError(HJGPU_ERANGE) that carries .counts = (gathered, out_of_range) - every output is complete then, such rows
+        written as NULL rows."""
+        ncols, srcs, outs = self._gather_args(src_cols, cols_out)
+        counts = (C.c_uint64 * 2)()
+        st = self.lib.hjgpu_gather_selected(self.handle, self._ptr(select_bits), self._ptr(idx), n, ncols, srcs, src_rows, outs,
+                                            self._ptr(bits_out), counts, stream)
+        if st != OK:
+            e = HjGpuError(st, "%s: %s" % (self.lib.hjgpu_status_string(st).decode(), self.lib.hjgpu_last_error(self.handle).decode()))
+            e.counts = (counts[0], counts[1])
+            raise e
+        return counts[0], counts[1]
+
+    def gather_selected_async(self, select_bits, idx, n, src_cols, src_rows, cols_out, bits_out, d_counts, stream=None):
+        """hjgpu_gather_selected_async: enqueue only; (gathered, out_of_range) go to d_counts (two uint64 in device memory, 16-byte aligned,
+        or None), where the caller reads what the blocking form reports as HJGPU_ERANGE"""
+        ncols, srcs, outs = self._gather_args(src_cols, cols_out)
+        self._check(self.lib.hjgpu_gather_selected_async(self.handle, self._ptr(select_bits), self._ptr(idx), n, ncols, srcs, src_rows, outs,
+                                                         self._ptr(bits_out), self._ptr(d_counts), stream))
 
     # ---- compaction by bitmap: the selected rows of the columns, dense and in input order ----------------------------------------
     def _compact_args(self, cols_in, cols_out, rows_out, capacity):

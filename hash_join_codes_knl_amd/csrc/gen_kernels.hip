@@ -921,3 +921,114 @@ int hj_launch_filter(const FilterArgs &a, uint32_t npreds, int cus, hipStream_t 
     });
     return hipGetLastError() == hipSuccess ? HJGPU_OK : HJGPU_EHIP;
 }
+
+// ---- gather by row number (hjgpu_gather_selected; DESIGN.md section 5 "Gather by row number") -------------------------------------------------
+// The positional look-up whose table is an array: out[c][i] = src[c][idx[i]] for every c < NCOLS where row i is gathered - selected and
+// idx[i] < src_rows, gather_layout.hpp's classify() -, HJGPU_NULL_VAL and bit 0 everywhere else.  One persistent grid; an iteration is
+// BATCH wave trips of hj_lookup.hpp's layout (lane L owns rows 4 L ... 4 L + 3 of a trip, a group of 8 lanes one word of either bitmap and
+// one 128-byte line of the index and of every output column).  The head is lookup_fetch with the index column in the key column's place:
+// all trips' mask words (SEL), then the index vectors, non-temporal, none where a group's mask word is 0, the nibble cut at n.  Then every
+// row is classified and only a gathered row forms an address - in 64 bits: 4 * idx does not fit 32 from 2^30 source rows on - and issues
+// its NCOLS loads; all 4 * BATCH * NCOLS loads of the iteration are issued before the first value is used.  They are ordinary cached
+// loads: the rows of a dimension are read again and again, unlike the streamed index.  A row that is not gathered issues no load, so no
+// index, whatever it holds, makes the kernel read outside a source column.
+// The stores are lookup_leave's pattern: one 16-byte hj_store per lane, trip and column, the last, partial vector by up to three 4-byte
+// stores, and the bitmap word by three DPP steps and the group's first lane - hj_lookup.hpp's IN-PLACE RULE for bits_out == select_bits.
+// The counts: popcounts per lane, the wave's sums, the four waves' through 64 bytes of LDS - the kernel's only LDS, behind the loop -, one
+// 64-bit atomic add per workgroup and count word.  No workgroup waits for another.
+template <int NCOLS, bool SEL>
+__global__ __launch_bounds__(hj_gather::BLOCK) void gather_kernel(GatherArgs a)
+{
+    using namespace hj_gather;
+    __shared__ u64 red[2][BLOCK / 64];
+    const uint32_t tid = threadIdx.x;
+    const u64 n = a.n, nvec = (n + 3) >> 2, stride = (u64)gridDim.x * BLOCK;
+    const uint4 *i4 = reinterpret_cast<const uint4 *>(a.idx);
+    u64 gathered = 0, beyond = 0;
+    for (u64 v0 = (u64)blockIdx.x * BLOCK + (tid & ~63u); v0 < nvec; v0 += stride * BATCH) {
+        uint32_t nib[BATCH], hit[BATCH];
+        uint4 ii[BATCH];
+        uint32_t val[BATCH][NCOLS][4];
+        lookup_fetch<SEL, (int)BATCH, true>(a.select_bits, i4, v0, stride, n, nib, ii);
+#pragma unroll
+        for (int u = 0; u < (int)BATCH; ++u) {
+            const uint32_t ix[4] = {ii[u].x, ii[u].y, ii[u].z, ii[u].w};
+            uint32_t bad = 0;
+            hit[u] = 0;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const Row r = classify((nib[u] >> j) & 1u, ix[j], a.src_rows);
+                hit[u] |= (r == ROW_GATHERED ? 1u : 0u) << j;
+                bad |= (r == ROW_OUT_OF_RANGE ? 1u : 0u) << j;
+#pragma unroll
+                for (int c = 0; c < NCOLS; ++c) val[u][c][j] = NULL_VAL;
+                if (r == ROW_GATHERED) {
+#pragma unroll
+                    for (int c = 0; c < NCOLS; ++c) val[u][c][j] = a.src[c][(u64)ix[j]];
+                }
+            }
+            gathered += __popc(hit[u]);
+            beyond += __popc(bad);
+        }
+#pragma unroll
+        for (int u = 0; u < (int)BATCH; ++u) {
+            const u64 v = v0 + (u64)u * stride + hj_lane(), g = v << 2;
+#pragma unroll
+            for (int c = 0; c < NCOLS; ++c) {
+                if (g + 4 <= n) hj_store(reinterpret_cast<uint4 *>(a.out[c]) + v, make_uint4(val[u][c][0], val[u][c][1], val[u][c][2], val[u][c][3]));
+                else {                                              // the last, partial vector: nothing at n and beyond is written
+#pragma unroll
+                    for (int j = 0; j < 3; ++j) if (g + j < n) hj_store(a.out[c] + g + j, val[u][c][j]);
+                }
+            }
+            if (a.bits_out) {
+                // 8 lanes x 4 rows = one word: OR over each group of 8 lanes, its first lane stores (all 64 lanes are here: v0 is the wave's)
+                uint32_t w = hit[u] << ((tid & 7u) * 4);
+                w |= hj_dpp<0xB1>(w);                                   // quad_perm: lanes 0<->1, 2<->3
+                w |= hj_dpp<0x4E>(w);                                   // quad_perm: lanes 0<->2, 1<->3
+                w |= hj_dpp<0x141>(w);                                  // row_half_mirror: lane i <-> 7 - i of the group, the other quad
+                // (v is a multiple of 8 in the storing lane: word v / 8 starts at row 4 v; a word whose first row is at n or beyond is not stored)
+                if ((tid & 7u) == 0 && g < n) hj_store(a.bits_out + (v >> 3), w);
+            }
+        }
+    }
+    if (a.counts) {
+        gathered = wave_reduce_sum(gathered);
+        beyond = wave_reduce_sum(beyond);
+        if (hj_lane() == 0) { red[0][tid >> 6] = gathered; red[1][tid >> 6] = beyond; }
+        __syncthreads();
+        if (tid == 0) {
+            u64 s0 = 0, s1 = 0;
+#pragma unroll
+            for (uint32_t w = 0; w < BLOCK / 64; ++w) { s0 += red[0][w]; s1 += red[1][w]; }
+            if (s0) atomicAdd(a.counts, s0);
+            if (s1) atomicAdd(a.counts + 1, s1);
+        }
+    }
+}
+
+// gather_layout.hpp's grid, no more workgroups than the rows have wave trips for
+int hj_launch_gather(const GatherArgs &a, uint32_t ncols, int cus, hipStream_t stream)
+{
+    using namespace hj_gather;
+    if (a.n == 0) return HJGPU_OK;
+    if (ncols < 1 || ncols > MAX_COLS || !a.idx || cus < 1) return HJGPU_EINVAL;
+    uintptr_t all = (uintptr_t)a.select_bits | (uintptr_t)a.idx | (uintptr_t)a.bits_out | (uintptr_t)a.counts;
+    for (uint32_t c = 0; c < ncols; ++c) {
+        if (!a.src[c] || !a.out[c]) return HJGPU_EINVAL;
+        all |= (uintptr_t)a.src[c] | (uintptr_t)a.out[c];
+    }
+    if (all & 15) return HJGPU_EINVAL;
+    const u64 nvec = (a.n + 3) >> 2, need = (nvec + BLOCK - 1) / BLOCK;
+    const dim3 grid((uint32_t)std::min<u64>(need, (u64)grid_of(cus)));
+    hj_with_bool(a.select_bits != nullptr, [&](auto sel) {
+        constexpr bool S = decltype(sel)::value;
+        switch (ncols) {
+        case 1: hipLaunchKernelGGL((gather_kernel<1, S>), grid, dim3(BLOCK), 0, stream, a); break;
+        case 2: hipLaunchKernelGGL((gather_kernel<2, S>), grid, dim3(BLOCK), 0, stream, a); break;
+        case 3: hipLaunchKernelGGL((gather_kernel<3, S>), grid, dim3(BLOCK), 0, stream, a); break;
+        default: hipLaunchKernelGGL((gather_kernel<4, S>), grid, dim3(BLOCK), 0, stream, a); break;
+        }
+    });
+    return hipGetLastError() == hipSuccess ? HJGPU_OK : HJGPU_EHIP;
+}

@@ -7,6 +7,7 @@
 #include "../../include/hjgpu.h"
 #include "compact_layout.hpp"
 #include "filter_layout.hpp"
+#include "gather_layout.hpp"
 #include "group_layout.hpp"
 #include "scatter_layout.hpp"
 
@@ -536,6 +537,24 @@ struct FilterArgs {
     hj_filter::Norm preds[hj_filter::MAX_PREDS];
 };
 int hj_launch_filter(const FilterArgs &a, uint32_t npreds, int cus, hipStream_t stream);
+
+// Gather by row number (hjgpu_gather_selected*, gen_kernels.hip; DESIGN.md section 5 "Gather by row number"): one persistent grid of
+// gather_layout.hpp's geometry.  Row i < n is gathered when it is selected (select_bits NULL: every row) and idx[i] < src_rows: then
+// out[c][i] = src[c][idx[i]] for every c < ncols and bit i of bits_out (NULL: no bitmap; it may be select_bits itself) is 1; every other
+// row gets HJGPU_NULL_VAL and bit 0 and reads no source element.  At most one out[c] may be idx itself.  The gathered rows are ADDED to
+// counts[0] and the selected rows whose index is neither below src_rows nor HJGPU_NULL_VAL to counts[1] (NULL: no counts), which are 0
+// before the launch.  Every pointer 16-byte aligned; n == 0 launches nothing.
+struct GatherArgs {
+    const uint32_t *select_bits;         // NULL: every row
+    const uint32_t *idx;
+    uint32_t *bits_out;                  // NULL: no bitmap
+    u64 *counts;                         // NULL: no counts
+    u64 n;
+    uint32_t src_rows;
+    const uint32_t *src[hj_gather::MAX_COLS];
+    uint32_t *out[hj_gather::MAX_COLS];
+};
+int hj_launch_gather(const GatherArgs &a, uint32_t ncols, int cus, hipStream_t stream);
 
 // K9: compact the per-wave partially filled tail blocks (npj.cpp:475-514).
 // moves: scratch of 2*HJ_MAX_WORKERS entries of 24 bytes + HJ_MAX_WORKERS entries of 8 bytes.

@@ -7,6 +7,10 @@
 // it stores it: lookup_fetch loads word v / 8 in the 8 lanes whose vectors make it up, lookup_leave stores it from the first of them, and
 // the store is issued behind the walk that waited for the load.  Neither pointer is __restrict__: the compiler keeps a load of select_bits
 // in front of every earlier store through match_bits.
+// The same rule for a COLUMN: gather_kernel (gen_kernels.hip) hands lookup_fetch its index column in the key column's place, and one of
+// its output columns may be that very pointer.  Vector v of the index is loaded by one lane only, the lane that stores vector v of every
+// output column, and lookup_fetch has loaded all vectors of an iteration before the iteration's first store: a lane reads its index
+// vector before it stores the same vector, and no other lane, wave or iteration ever reads it.
 #pragma once
 #include "hj_device.hpp"
 

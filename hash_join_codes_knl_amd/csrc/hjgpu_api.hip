@@ -1330,6 +1330,7 @@ const char *hjgpu_status_string(int s)
     case HJGPU_EOVERFLOW: return "output capacity exceeded";
     case HJGPU_ENODEVICE: return "no GPU device";
     case HJGPU_ERCCL: return "RCCL / communicator error";
+    case HJGPU_ERANGE: return "row number out of range";
     default: return "unknown status";
     }
 }
@@ -1382,7 +1383,7 @@ int hjgpu_destroy(hjgpu_ctx *ctx)
     (void)hipDeviceSynchronize();
     DevBuf *all[] = {&ctx->tmp[0], &ctx->tmp[1], &ctx->tmp[2], &ctx->tmp[3], &ctx->tmp[4], &ctx->tmp[5],
                      &ctx->tmp[6], &ctx->tmp[7], &ctx->meta, &ctx->table, &ctx->state, &ctx->moves,
-                     &ctx->final_offsets, &ctx->build_bits, &ctx->grp[0], &ctx->grp[1], &ctx->grp[2], &ctx->grp[3], &ctx->grp_off, &ctx->audit, &ctx->audit_lay, &ctx->compact, &ctx->group, &ctx->filter};
+                     &ctx->final_offsets, &ctx->build_bits, &ctx->grp[0], &ctx->grp[1], &ctx->grp[2], &ctx->grp[3], &ctx->grp_off, &ctx->audit, &ctx->audit_lay, &ctx->compact, &ctx->group, &ctx->filter, &ctx->gather};
     for (DevBuf *b : all) if (b->p) (void)hipFree(b->p);
     for (int i = 0; i < EV_COUNT; ++i) (void)hipEventDestroy(ctx->ev[i]);
     if (ctx->aux) (void)hipStreamDestroy(ctx->aux);
@@ -1462,7 +1463,8 @@ int hjgpu_get_counter(hjgpu_ctx *ctx, const char *name, uint64_t *value)
     if (strcmp(name, "compact_chunk_rows") == 0) { *value = hj_compact::CHUNK_ROWS; return HJGPU_OK; }
     if (strcmp(name, "group_lds_groups") == 0) { *value = hj_group::LDS_GROUPS; return HJGPU_OK; }
     if (strcmp(name, "filter_step_rows") == 0) { *value = hj_filter::step_rows(ctx->cus); return HJGPU_OK; }
-    return fail(ctx, HJGPU_EINVAL, "unknown counter (probe_fallbacks, probe_exact, lookup_lds_rows, compact_ranges, compact_chunk_rows, group_lds_groups, filter_step_rows)");
+    if (strcmp(name, "gather_step_rows") == 0) { *value = hj_gather::step_rows(ctx->cus); return HJGPU_OK; }
+    return fail(ctx, HJGPU_EINVAL, "unknown counter (probe_fallbacks, probe_exact, lookup_lds_rows, compact_ranges, compact_chunk_rows, group_lds_groups, filter_step_rows, gather_step_rows)");
 }
 
 // the workspace's side of hjgpu_stats: what the context has spent growing it, and its last placement search
@@ -1542,7 +1544,7 @@ int hjgpu_get_stats(hjgpu_ctx *ctx, hjgpu_stats *s)
         *s = r;
         return HJGPU_OK;
     }
-    if (ctx->last_algo == 5) {                 // hjgpu_filter_selected: the clear of the count word, then the kernel
+    if (ctx->last_algo == 5 || ctx->last_algo == 6) {      // hjgpu_filter_selected, hjgpu_gather_selected: the clear of the count words, then the kernel
         memset(&r, 0, sizeof(r));
         r.ms_total = span(EV_BEGIN, EV_GAPS);
         r.ms_histogram = span(EV_BEGIN, EV_S_HIST);

@@ -61,11 +61,12 @@ struct hjgpu_ctx {
     DevBuf compact;         // hjgpu_compact_selected: the ranges' counts and the blocking form's count (constant size, made by the first call)
     DevBuf group;           // hjgpu_group_sum: the blocking form's count word, the overflow word and the merge table (group_layout.hpp; grows with the capacity)
     DevBuf filter;          // hjgpu_filter_selected: the count word that the kernel adds to - the blocking form reads it back (8 bytes, made by the first call)
+    DevBuf gather;          // hjgpu_gather_selected: the two count words that the kernel adds to - the blocking form reads them back (16 bytes, made by the first call)
     DevBuf build_bits;      // right / full outer joins: one bit per row of the partitioned build array (PHJ / CPRA) or per bucket (NPJ)
     hipEvent_t ev[EV_COUNT];
     bool ev_valid[EV_COUNT];
     hjgpu_stats stats;
-    int last_algo = -1;     // 0 npj, 1 phj/cpra, 2 one kernel (hjgpu_column_sums ...), 3 hjgpu_compact_selected, 4 hjgpu_group_sum, 5 hjgpu_filter_selected
+    int last_algo = -1;     // 0 npj, 1 phj/cpra, 2 one kernel (hjgpu_column_sums ...), 3 hjgpu_compact_selected, 4 hjgpu_group_sum, 5 hjgpu_filter_selected, 6 hjgpu_gather_selected
     bool last_lookup = false;   // the last operation was a positional look-up (hjgpu_npj_lookup*): no close_gaps, ms_close_gaps is 0
     // hjgpu_phj_build: the partitioned build side (tmp[0] / tmp[4]) and its plan (meta) stay valid until
     // another entry point uses the workspace

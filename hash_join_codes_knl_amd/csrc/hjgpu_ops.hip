@@ -822,6 +822,136 @@ int hjgpu_filter_selected(hjgpu_ctx *ctx, const uint32_t *d_select_bits, size_t 
     return HJGPU_OK;
 }
 
+// ---- gather by row number -----------------------------------------------------------
+// hjgpu_gather_selected / _async (DESIGN.md section 5 "Gather by row number").  Every refusal is decided here, from the arguments alone, before
+// anything is allocated or enqueued.
+struct GatherCall {
+    const uint32_t *bits;
+    const uint32_t *idx;
+    size_t n;
+    uint32_t ncols;
+    const uint32_t *const *src;
+    size_t src_rows;
+    uint32_t *const *out;
+    uint32_t *bits_out;
+};
+
+static int check_gather(hjgpu_ctx *ctx, const GatherCall &g, const uint64_t *d_counts)
+{
+    if ((uintptr_t)d_counts & 15) return fail(ctx, HJGPU_EALIGN, "d_counts must be 16-byte aligned");
+    if (g.ncols == 0 || g.ncols > HJGPU_GATHER_MAX_COLS) return fail(ctx, HJGPU_EINVAL, "ncols must be 1 to HJGPU_GATHER_MAX_COLS (4)");
+    if (g.src_rows > 0xFFFFFFFFull) return fail(ctx, HJGPU_EINVAL, "src_rows must not exceed 0xFFFFFFFF: an index is a uint32 and HJGPU_NULL_VAL is never a legal one");
+    if (g.n == 0) return HJGPU_OK;                       // nothing is read, nothing but the counts is written: anything else may be NULL
+    if (!g.idx) return fail(ctx, HJGPU_EINVAL, "null d_idx");
+    if ((uintptr_t)g.bits & 15) return fail(ctx, HJGPU_EALIGN, "d_select_bits must be 16-byte aligned");
+    if ((uintptr_t)g.idx & 15) return fail(ctx, HJGPU_EALIGN, "d_idx must be 16-byte aligned");
+    if ((uintptr_t)g.bits_out & 15) return fail(ctx, HJGPU_EALIGN, "d_bits_out must be 16-byte aligned");
+    if (!g.src || !g.out) return fail(ctx, HJGPU_EINVAL, "null column array");
+    for (uint32_t c = 0; c < g.ncols; ++c) {
+        if (!g.src[c] || !g.out[c]) return fail(ctx, HJGPU_EINVAL, "null column pointer");
+        if ((uintptr_t)g.src[c] & 15) return fail(ctx, HJGPU_EALIGN, "source columns must be 16-byte aligned");
+        if ((uintptr_t)g.out[c] & 15) return fail(ctx, HJGPU_EALIGN, "output columns must be 16-byte aligned");
+    }
+    const size_t mbytes = (g.n + 31) / 32 * sizeof(uint32_t), cbytes = g.n * sizeof(uint32_t), sbytes = g.src_rows * sizeof(uint32_t);
+    // in place: an output column may be the very pointer d_idx - a lane reads its index vector before it stores the same vector - and, being
+    // an output, only one can; d_bits_out may be the very pointer d_select_bits (hj_lookup.hpp's IN-PLACE RULE).  Every other shared byte
+    // between an output and anything else would be read after it was written, or written twice
+    for (uint32_t c = 0; c < g.ncols; ++c) {
+        if (g.out[c] != g.idx && ranges_overlap(g.out[c], cbytes, g.idx, cbytes))
+            return fail(ctx, HJGPU_EINVAL, "an output column overlaps d_idx: it may be the very pointer d_idx (in place), any other overlap is refused");
+        for (uint32_t q = 0; q < c; ++q)
+            if (ranges_overlap(g.out[c], cbytes, g.out[q], cbytes)) return fail(ctx, HJGPU_EINVAL, "an output column overlaps another output column");
+        for (uint32_t q = 0; q < g.ncols; ++q)
+            if (ranges_overlap(g.out[c], cbytes, g.src[q], sbytes)) return fail(ctx, HJGPU_EINVAL, "an output column overlaps a source column");
+        if (ranges_overlap(g.out[c], cbytes, g.bits, g.bits ? mbytes : 0)) return fail(ctx, HJGPU_EINVAL, "an output column overlaps d_select_bits");
+    }
+    if (g.bits_out) {
+        if (g.bits && g.bits != g.bits_out && ranges_overlap(g.bits_out, mbytes, g.bits, mbytes))
+            return fail(ctx, HJGPU_EINVAL, "d_bits_out overlaps d_select_bits: it may be the very pointer d_select_bits (in place), any other overlap of the two bitmaps is refused");
+        if (ranges_overlap(g.bits_out, mbytes, g.idx, cbytes)) return fail(ctx, HJGPU_EINVAL, "d_bits_out overlaps d_idx");
+        for (uint32_t c = 0; c < g.ncols; ++c) {
+            if (ranges_overlap(g.bits_out, mbytes, g.out[c], cbytes)) return fail(ctx, HJGPU_EINVAL, "d_bits_out overlaps an output column");
+            if (ranges_overlap(g.bits_out, mbytes, g.src[c], sbytes)) return fail(ctx, HJGPU_EINVAL, "d_bits_out overlaps a source column");
+        }
+    }
+    if (d_counts) {
+        const size_t wbytes = 2 * sizeof(uint64_t);
+        if (ranges_overlap(d_counts, wbytes, g.bits, g.bits ? mbytes : 0)) return fail(ctx, HJGPU_EINVAL, "d_counts overlaps d_select_bits");
+        if (ranges_overlap(d_counts, wbytes, g.idx, cbytes)) return fail(ctx, HJGPU_EINVAL, "d_counts overlaps d_idx");
+        if (ranges_overlap(d_counts, wbytes, g.bits_out, g.bits_out ? mbytes : 0)) return fail(ctx, HJGPU_EINVAL, "d_counts overlaps d_bits_out");
+        for (uint32_t c = 0; c < g.ncols; ++c) {
+            if (ranges_overlap(d_counts, wbytes, g.out[c], cbytes)) return fail(ctx, HJGPU_EINVAL, "d_counts overlaps an output column");
+            if (ranges_overlap(d_counts, wbytes, g.src[c], sbytes)) return fail(ctx, HJGPU_EINVAL, "d_counts overlaps a source column");
+        }
+    }
+    return HJGPU_OK;
+}
+
+// the context's two count words (the blocking form's; made by the first call of either form)
+static int gather_workspace(hjgpu_ctx *ctx, u64 **words)
+{
+    CHK(ensure(ctx, ctx->gather, 2 * sizeof(u64)));
+    *words = reinterpret_cast<u64 *>(ctx->gather.p);
+    return HJGPU_OK;
+}
+
+// the two enqueues behind the checks: the clear of the count words (d_counts NULL: none), the kernel (n == 0: none).  hjgpu_get_stats
+// afterwards: ms_histogram = the clear, ms_join = the kernel, ms_total = both
+static int gather_enqueue(hjgpu_ctx *ctx, const GatherCall &g, u64 *d_counts, hipStream_t stream)
+{
+    for (int i = 0; i < EV_COUNT; ++i) ctx->ev_valid[i] = false;
+    ctx->last_algo = 6;
+    record(ctx, EV_BEGIN, stream);
+    if (d_counts) HIPCHK(ctx, hj_zero_async(d_counts, 2 * sizeof(u64), stream));
+    record(ctx, EV_S_HIST, stream);
+    if (g.n) {
+        GatherArgs a{};
+        a.select_bits = g.bits; a.idx = g.idx; a.bits_out = g.bits_out; a.counts = d_counts; a.n = g.n; a.src_rows = (uint32_t)g.src_rows;
+        for (uint32_t c = 0; c < g.ncols; ++c) { a.src[c] = g.src[c]; a.out[c] = g.out[c]; }
+        CHK(hj_launch_gather(a, g.ncols, ctx->cus, stream));
+    }
+    record(ctx, EV_JOIN, stream);
+    record(ctx, EV_GAPS, stream);
+    return HJGPU_OK;
+}
+
+int hjgpu_gather_selected_async(hjgpu_ctx *ctx, const uint32_t *d_select_bits, const uint32_t *d_idx, size_t n, uint32_t ncols,
+                                const uint32_t *const *d_src_cols, size_t src_rows, uint32_t *const *d_cols_out, uint32_t *d_bits_out,
+                                uint64_t *d_counts, void *stream_)
+{
+    if (!ctx) return HJGPU_EINVAL;
+    const GatherCall g{d_select_bits, d_idx, n, ncols, d_src_cols, src_rows, d_cols_out, d_bits_out};
+    CHK(check_gather(ctx, g, d_counts));
+    hipStream_t stream = (hipStream_t)stream_;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    CHK(refuse_capture(ctx, stream));
+    u64 *words = nullptr;
+    CHK(gather_workspace(ctx, &words));
+    return gather_enqueue(ctx, g, reinterpret_cast<u64 *>(d_counts), stream);
+}
+
+int hjgpu_gather_selected(hjgpu_ctx *ctx, const uint32_t *d_select_bits, const uint32_t *d_idx, size_t n, uint32_t ncols,
+                          const uint32_t *const *d_src_cols, size_t src_rows, uint32_t *const *d_cols_out, uint32_t *d_bits_out,
+                          uint64_t counts[2], void *stream_)
+{
+    if (!ctx) return HJGPU_EINVAL;
+    const GatherCall g{d_select_bits, d_idx, n, ncols, d_src_cols, src_rows, d_cols_out, d_bits_out};
+    CHK(check_gather(ctx, g, nullptr));
+    hipStream_t stream = (hipStream_t)stream_;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    CHK(refuse_capture(ctx, stream));
+    u64 *words = nullptr;
+    CHK(gather_workspace(ctx, &words));
+    CHK(gather_enqueue(ctx, g, words, stream));          // (the context's words also when counts is NULL: HJGPU_ERANGE is read from them)
+    u64 got[2] = {0, 0};
+    HIPCHK(ctx, hipMemcpyAsync(got, words, sizeof(got), hipMemcpyDeviceToHost, stream));
+    HIPCHK(ctx, hipStreamSynchronize(stream));
+    if (counts) { counts[0] = got[0]; counts[1] = got[1]; }
+    if (got[1])
+        return fail(ctx, HJGPU_ERANGE, "hjgpu_gather_selected: selected rows hold an index that is neither below src_rows nor HJGPU_NULL_VAL (counts[1] holds their number; they were written as NULL rows, every output is complete)");
+    return HJGPU_OK;
+}
+
 int hjgpu_stream_read_ms(hjgpu_ctx *ctx, const void *d_ptr, size_t bytes, float *ms, void *stream_)
 {
     if (!ctx || !d_ptr || !ms) return HJGPU_EINVAL;

@@ -270,7 +270,8 @@ int  hjgpu_get_stats(hjgpu_ctx *ctx, hjgpu_stats *stats);
  *   "group_lds_groups" the distinct groups a workgroup's LDS table of hjgpu_group_sum holds before its further groups go straight to the
  *                      merge table in device memory
  *   "filter_step_rows" the rows that hjgpu_filter_selected's whole grid covers in one iteration of its loop (the grid is smaller when the
- *                      rows are fewer) */
+ *                      rows are fewer)
+ *   "gather_step_rows" the same for hjgpu_gather_selected */
 int  hjgpu_get_counter(hjgpu_ctx *ctx, const char *name, uint64_t *value);
 
 /* ---- device memory helpers for hosts that do not link HIP (mamalloc/free,
@@ -489,6 +490,64 @@ int  hjgpu_filter_selected(hjgpu_ctx *ctx, const uint32_t *d_select_bits, size_t
 int  hjgpu_filter_selected_async(hjgpu_ctx *ctx, const uint32_t *d_select_bits, size_t n,
                                  uint32_t npreds, const uint32_t *const *d_cols, const hjgpu_predicate *preds,
                                  uint32_t *d_bits_out, uint64_t *d_count, void *stream);
+
+/* ---- gather by row number: up to 4 columns fetched by an index column, under a bitmap ------------------------
+ * What turns a row number back into column values - the positional look-up whose table is an array.  A look-up or a join carries ONE
+ * 32-bit payload per side; when that payload is the row number (a dimension's row in hjgpu_lookup_selected's build payload, a relation's
+ * row in hjgpu_phj's payload columns, hjgpu_compact_selected's d_rows_out), this call fetches any further columns of that row: the second
+ * attribute of a dimension (filter on c_region, group by c_nation), the other columns of a join's result rows.  Its contract is
+ * hjgpu_lookup_selected's wherever the two meet.  For every row i < n, in position (output row i belongs to input row i):
+ *   a gathered row   row i is GATHERED when it is selected and d_idx[i] < src_rows.  Then d_cols_out[c][i] = d_src_cols[c][d_idx[i]] for
+ *                    every c < ncols, and bit i of d_bits_out is 1.
+ *   every other row  gets HJGPU_NULL_VAL in every output column and bit 0, and NO SOURCE ELEMENT IS READ FOR IT: an unselected row,
+ *                    whatever its index holds (garbage is legal there and is not counted); a selected row whose index is HJGPU_NULL_VAL -
+ *                    the NULL of a look-up or of an outer join passes through -; a selected row whose index is out of range, that is
+ *                    >= src_rows and not HJGPU_NULL_VAL.  No index, whatever it holds, makes the call read outside a source column.
+ *                    Every element < n of every output column is written, and nothing at n or beyond.
+ *   d_bits_out       (n + 31) / 32 words in d_match_bits' layout: bit i & 31 of word i >> 5 is 1 exactly when row i is gathered - what
+ *                    tells a NULL from a genuine 0xFFFFFFFF in a source column.  The last word's bits at positions >= n are written 0,
+ *                    no word at index >= (n + 31) / 32 is written.  16-byte aligned (HJGPU_EALIGN).  It may be NULL.
+ *   counts           counts[0] = the gathered rows, counts[1] = the out-of-range rows, both exact: host memory in the blocking form,
+ *                    device memory (two words, 16-byte aligned: HJGPU_EALIGN) in the _async form.  May be NULL.
+ *   HJGPU_ERANGE     the blocking form returns it when counts[1] != 0 - also when counts is NULL: it reads the context's own count
+ *                    words.  All outputs are still written completely and validly, as HJGPU_EOVERFLOW leaves a valid prefix.  The _async
+ *                    form cannot report it: its caller reads d_counts[1].
+ *   d_select_bits    hjgpu_lookup_selected's mask, word for word: (n + 31) / 32 words, bit i & 31 of word i >> 5 selects row i, bits of the
+ *                    last word at positions >= n are ignored, no word at index >= (n + 31) / 32 is read.  16-byte aligned (HJGPU_EALIGN).
+ *                    NULL selects every row.
+ *   d_idx            n uint32 row numbers, 16-byte aligned (HJGPU_EALIGN); no row at n or beyond is read, except inside the last 16-byte
+ *                    vector.  The 32 rows of a mask word that is 0 are not read at all.
+ *   sources          d_src_cols[c] holds src_rows uint32, 16-byte aligned (HJGPU_EALIGN), and is never written.  src_rows <= 0xFFFFFFFF -
+ *                    larger is HJGPU_EINVAL: an index is a uint32, and HJGPU_NULL_VAL must never be a legal one.  src_rows == 0 is legal:
+ *                    nothing is gathered and no source byte is read.  The same source column may be given twice.
+ *   d_src_cols,      HOST arrays of ncols entries, copied by value into the kernel arguments.  ncols is 1 to HJGPU_GATHER_MAX_COLS; 0,
+ *   d_cols_out       more, and a NULL entry among the first ncols of either array are HJGPU_EINVAL.  Output columns hold n uint32 and are
+ *                    16-byte aligned (HJGPU_EALIGN).
+ *   in place         d_bits_out may be the very pointer d_select_bits: afterwards the bitmap is select AND gathered, as the selected
+ *                    look-ups narrow theirs.  At most one output column may be the very pointer d_idx: the row numbers are replaced by
+ *                    the values.
+ *   overlap          any other overlap is HJGPU_EINVAL, "overlaps" in hjgpu_last_error: an output column with the index, another output
+ *                    column, a source column or the mask; d_bits_out with anything but the very pointer d_select_bits; the _async
+ *                    form's count words with anything.
+ *   n == 0           reads nothing, writes nothing but the counts (0, 0), accepts NULL everywhere else.
+ * Every refusal is decided from the arguments alone, before anything is enqueued or allocated; a capturing stream is HJGPU_EINVAL.  Neither
+ * form touches what hjgpu_get_async_status / hjgpu_accumulate_async_status report.  The _async form only enqueues and needs no
+ * hjgpu_reserve: the only workspace is two count words per context, made the first time either form runs, so calls may be queued back to
+ * back on one stream of one context.  Two enqueues ordered by the stream - the clear of the count words, then ONE kernel on a persistent
+ * grid that streams the mask and the index once and fetches the source elements with ordinary cached loads - and no workgroup waits for
+ * another.  hjgpu_get_stats afterwards: ms_total = both, ms_histogram = the clear, ms_join = the kernel, every other phase 0, fanout1 =
+ * fanout2 = buckets = groups = 0.  hjgpu_get_counter "gather_step_rows": the rows the whole grid covers in one iteration of its loop.
+ * More than HJGPU_GATHER_MAX_COLS columns are further calls, each of which reads the index again. */
+#define HJGPU_GATHER_MAX_COLS 4u
+#define HJGPU_ERANGE 9   /* gather: a selected row's index is neither HJGPU_NULL_VAL nor below src_rows */
+int  hjgpu_gather_selected(hjgpu_ctx *ctx, const uint32_t *d_select_bits, const uint32_t *d_idx, size_t n,
+                           uint32_t ncols, const uint32_t *const *d_src_cols, size_t src_rows,
+                           uint32_t *const *d_cols_out, uint32_t *d_bits_out,
+                           uint64_t counts[2], void *stream);
+int  hjgpu_gather_selected_async(hjgpu_ctx *ctx, const uint32_t *d_select_bits, const uint32_t *d_idx, size_t n,
+                                 uint32_t ncols, const uint32_t *const *d_src_cols, size_t src_rows,
+                                 uint32_t *const *d_cols_out, uint32_t *d_bits_out,
+                                 uint64_t *d_counts, void *stream);
 
 /* ---- compaction by bitmap: the selected rows of up to 8 columns, dense and in order ----------------------
  * What turns a bitmap in d_match_bits' layout and full-length columns into dense rows - at the end of a chain of selected look-ups (the
