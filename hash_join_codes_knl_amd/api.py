@@ -403,12 +403,30 @@ class HjGpu:
     def __exit__(self, *a):
         self.close()
 
-    def _check(self, st):
+    def _check(self, st, **carried):
+        """raises HjGpuError for a status other than OK; carried: attributes of the error (.count of an overflow, .counts of a gather -
+        read by the caller after the library call that made st, as arguments are evaluated left to right)"""
         if st != OK:
-            raise HjGpuError(st, "%s: %s" % (self.lib.hjgpu_status_string(st).decode(),
-                                             self.lib.hjgpu_last_error(self.handle).decode()))
+            e = HjGpuError(st, "%s: %s" % (self.lib.hjgpu_status_string(st).decode(),
+                                           self.lib.hjgpu_last_error(self.handle).decode()))
+            for name, value in carried.items():
+                setattr(e, name, value)
+            raise e
 
     # ---- helpers -----------------------------------------------------------------
+    def _ptr_array(self, cols):
+        """a host array of the columns' device pointers (an empty list: NULL)"""
+        return (C.c_void_p * len(cols))(*[self._ptr(c) for c in cols]) if cols else None
+
+    @staticmethod
+    def _default_capacity(capacity, outs, entry):
+        """the capacity of a column operator's outputs: as given, else the shortest of them"""
+        if capacity is not None:
+            return capacity
+        if not all(isinstance(c, DeviceColumn) for c in outs):
+            raise ValueError("%s: capacity is needed with outputs given as plain pointers" % entry)
+        return min([c.n for c in outs], default=0)
+
     def column(self, host_or_n, dtype=np.uint32, placed=False):
         """placed: hjgpu_malloc_placed (result columns of a gigabyte and more: the placement search of the workspace)"""
         if isinstance(host_or_n, (int, np.integer)):
@@ -575,10 +593,8 @@ class HjGpu:
         cols, preds = list(cols or ()), list(preds or ())
         if len(cols) != len(preds):
             raise ValueError("filter_selected: %d columns, %d predicates" % (len(cols), len(preds)))
-        if not cols:                        # (the library refuses npreds == 0)
-            return 0, None, None
-        return (len(cols), (C.c_void_p * len(cols))(*[self._ptr(c) for c in cols]),
-                (Predicate * len(preds))(*[Predicate.of(p) for p in preds]))
+        # (no column: NULL arrays - the library refuses npreds == 0)
+        return len(cols), self._ptr_array(cols), (Predicate * len(preds))(*[Predicate.of(p) for p in preds]) if preds else None
 
     def filter_selected(self, select_bits, n, cols, preds, bits_out=None, stream=None):
         """hjgpu_filter_selected: row i passes when its bit is set in select_bits (match_bits' layout; None: every row) and every
@@ -603,10 +619,8 @@ class HjGpu:
         src_cols, cols_out = list(src_cols or ()), list(cols_out or ())
         if len(src_cols) != len(cols_out):
             raise ValueError("gather_selected: %d source columns, %d output columns" % (len(src_cols), len(cols_out)))
-        if not src_cols:                    # (the library refuses ncols == 0)
-            return 0, None, None
-        arr = C.c_void_p * len(src_cols)
-        return len(src_cols), arr(*[self._ptr(c) for c in src_cols]), arr(*[self._ptr(c) for c in cols_out])
+        # (no column: NULL arrays - the library refuses ncols == 0)
+        return len(src_cols), self._ptr_array(src_cols), self._ptr_array(cols_out)
 
     def gather_selected(self, select_bits, idx, n, src_cols, src_rows, cols_out, bits_out=None, stream=None):
         """hjgpu_gather_selected: cols_out[c][i] = src_cols[c][idx[i]] for every row i < n whose bit is set in select_bits (match_bits'
@@ -617,12 +631,8 @@ class HjGpu:
         written as NULL rows."""
         ncols, srcs, outs = self._gather_args(src_cols, cols_out)
         counts = (C.c_uint64 * 2)()
-        st = self.lib.hjgpu_gather_selected(self.handle, self._ptr(select_bits), self._ptr(idx), n, ncols, srcs, src_rows, outs,
-                                            self._ptr(bits_out), counts, stream)
-        if st != OK:
-            e = HjGpuError(st, "%s: %s" % (self.lib.hjgpu_status_string(st).decode(), self.lib.hjgpu_last_error(self.handle).decode()))
-            e.counts = (counts[0], counts[1])
-            raise e
+        self._check(self.lib.hjgpu_gather_selected(self.handle, self._ptr(select_bits), self._ptr(idx), n, ncols, srcs, src_rows, outs,
+                                                   self._ptr(bits_out), counts, stream), counts=(counts[0], counts[1]))
         return counts[0], counts[1]
 
     def gather_selected_async(self, select_bits, idx, n, src_cols, src_rows, cols_out, bits_out, d_counts, stream=None):
@@ -637,15 +647,8 @@ class HjGpu:
         cols_in, cols_out = list(cols_in or ()), list(cols_out or ())
         if len(cols_in) != len(cols_out):
             raise ValueError("compact_selected: %d input columns, %d output columns" % (len(cols_in), len(cols_out)))
-        if capacity is None:                # the shortest output
-            outs = cols_out + ([rows_out] if rows_out is not None else [])
-            if not all(isinstance(c, DeviceColumn) for c in outs):
-                raise ValueError("compact_selected: capacity is needed with outputs given as plain pointers")
-            capacity = min([c.n for c in outs], default=0)
-        if not cols_in:                     # no columns: NULL arrays
-            return 0, None, None, capacity
-        arr = C.c_void_p * len(cols_in)
-        return len(cols_in), arr(*[self._ptr(c) for c in cols_in]), arr(*[self._ptr(c) for c in cols_out]), capacity
+        capacity = self._default_capacity(capacity, cols_out + ([rows_out] if rows_out is not None else []), "compact_selected")
+        return len(cols_in), self._ptr_array(cols_in), self._ptr_array(cols_out), capacity      # (no columns: NULL arrays)
 
     def compact_selected(self, select_bits, n, cols_in, cols_out, rows_out=None, capacity=None, stream=None):
         """hjgpu_compact_selected: cols_out[c][j] = cols_in[c][i_j], rows_out[j] = i_j for the rows i_0 < i_1 < ... whose bit is set in
@@ -653,12 +656,8 @@ class HjGpu:
         HjGpuError(HJGPU_EOVERFLOW) that carries .count = J; the first capacity rows of every output are valid then."""
         ncols, ins, outs, capacity = self._compact_args(cols_in, cols_out, rows_out, capacity)
         count = C.c_uint64()
-        st = self.lib.hjgpu_compact_selected(self.handle, self._ptr(select_bits), n, ncols, ins, outs, self._ptr(rows_out), capacity,
-                                             C.byref(count), stream)
-        if st != OK:
-            e = HjGpuError(st, "%s: %s" % (self.lib.hjgpu_status_string(st).decode(), self.lib.hjgpu_last_error(self.handle).decode()))
-            e.count = count.value
-            raise e
+        self._check(self.lib.hjgpu_compact_selected(self.handle, self._ptr(select_bits), n, ncols, ins, outs, self._ptr(rows_out), capacity,
+                                                    C.byref(count), stream), count=count.value)
         return count.value
 
     def compact_selected_async(self, select_bits, n, cols_in, cols_out, rows_out, capacity, d_count, stream=None):
@@ -674,14 +673,8 @@ class HjGpu:
         if len(keys_in) != len(keys_out) or len(vals_in) != len(sums_out):
             raise ValueError("group_sum: %d key columns with %d outputs, %d measure columns with %d outputs"
                              % (len(keys_in), len(keys_out), len(vals_in), len(sums_out)))
-        if capacity is None:                # the shortest output
-            outs = keys_out + sums_out + ([counts_out] if counts_out is not None else [])
-            if not all(isinstance(c, DeviceColumn) for c in outs):
-                raise ValueError("group_sum: capacity is needed with outputs given as plain pointers")
-            capacity = min([c.n for c in outs], default=0)
-
-        def arr(cols):
-            return (C.c_void_p * len(cols))(*[self._ptr(c) for c in cols]) if cols else None
+        capacity = self._default_capacity(capacity, keys_out + sums_out + ([counts_out] if counts_out is not None else []), "group_sum")
+        arr = self._ptr_array
         return (len(keys_in), arr(keys_in), len(vals_in), arr(vals_in), arr(keys_out), self._ptr(counts_out), arr(sums_out), capacity)
 
     def group_sum(self, select_bits, n, keys_in, vals_in, keys_out, sums_out, counts_out=None, capacity=None, stream=None):
@@ -692,12 +685,8 @@ class HjGpu:
         exceeds capacity; the outputs are unspecified then."""
         nk, kin, nv, vin, kout, cout, sout, capacity = self._group_args(keys_in, vals_in, keys_out, sums_out, counts_out, capacity)
         count = C.c_uint64()
-        st = self.lib.hjgpu_group_sum(self.handle, self._ptr(select_bits), n, nk, kin, nv, vin, kout, cout, sout, capacity,
-                                      C.byref(count), stream)
-        if st != OK:
-            e = HjGpuError(st, "%s: %s" % (self.lib.hjgpu_status_string(st).decode(), self.lib.hjgpu_last_error(self.handle).decode()))
-            e.count = count.value
-            raise e
+        self._check(self.lib.hjgpu_group_sum(self.handle, self._ptr(select_bits), n, nk, kin, nv, vin, kout, cout, sout, capacity,
+                                             C.byref(count), stream), count=count.value)
         return count.value
 
     def group_sum_async(self, select_bits, n, keys_in, vals_in, keys_out, sums_out, counts_out, capacity, d_ngroups, stream=None):

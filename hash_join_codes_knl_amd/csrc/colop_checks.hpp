@@ -1,0 +1,234 @@
+// colop_checks.hpp - what the column operators (hjgpu_compact_selected, hjgpu_group_sum, hjgpu_filter_selected, hjgpu_gather_selected: hjgpu_colops.hip)
+// and the selected look-ups refuse from their arguments alone, before anything is allocated or enqueued (DESIGN.md section 5 "Argument checks
+// of the column operators").  Plain host C++, no HIP and no context: a check returns {status, text}, its caller hands that to fail().
+// tests/test_colop_checks.py compiles it with g++ and compares every decision with the hand-written checkers it replaced.
+//
+// A check is its operator's own head - the count pointer, the limits, the n == 0 accept, the required pointers - and then ONE rule over a
+// table of the pointers the kernels will read and write: every one aligned, and no written range shares a byte with any other range, except
+// that a written operand may be the very pointer of the one read operand it names (in place).  No device pointer is dereferenced.
+#pragma once
+#include <stdarg.h>
+#include <stddef.h>
+#include <stdint.h>
+#include <stdio.h>
+
+#include "../../include/hjgpu.h"
+#include "group_layout.hpp"
+
+namespace colop {
+
+struct Verdict {
+    int status;
+    char text[192];                                     // (inside the value: fail() copies it)
+};
+
+inline Verdict no_objection()
+{
+    Verdict v;
+    v.status = HJGPU_OK; v.text[0] = 0;
+    return v;
+}
+
+#if defined(__GNUC__)
+__attribute__((format(printf, 2, 3)))
+#endif
+inline Verdict refuse(int status, const char *fmt, ...)
+{
+    Verdict v;
+    v.status = status;
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(v.text, sizeof(v.text), fmt, ap);
+    va_end(ap);
+    return v;
+}
+
+struct Operand {
+    const void *p;                                      // NULL: an absent optional operand, it takes no part
+    size_t bytes;
+    bool written;
+    uint32_t align;
+    const char *name;
+    int in_place;                                       // a written operand: the read operand it may coincide with exactly, or -1
+};
+
+struct Operands {
+    Operand v[2 * HJGPU_COMPACT_MAX_COLS + 2];          // the largest table: the mask, 8 inputs, 8 outputs and the row numbers of a compaction
+    int n = 0;
+    int read(const void *p, size_t bytes, uint32_t align, const char *name) { v[n] = {p, bytes, false, align, name, -1}; return n++; }
+    int write(const void *p, size_t bytes, uint32_t align, const char *name, int in_place = -1) { v[n] = {p, bytes, true, align, name, in_place}; return n++; }
+};
+
+inline bool ranges_overlap(const void *p, size_t pbytes, const void *q, size_t qbytes)
+{
+    const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
+    return p && q && pbytes && qbytes && a < b + qbytes && b < a + pbytes;
+}
+
+// The one rule.  All alignments first; then every written operand against every read operand and every earlier written one.  In place: a
+// kernel reads a vector (a bitmap word, an index vector) in the lane that stores it, before it stores it, so the very pointer is safe - any
+// other shared byte would be read after it was written, or written twice.
+inline Verdict check_operands(const Operands &t)
+{
+    for (int i = 0; i < t.n; ++i)
+        if ((uintptr_t)t.v[i].p & (t.v[i].align - 1)) return refuse(HJGPU_EALIGN, "%s must be %u-byte aligned", t.v[i].name, t.v[i].align);
+    for (int i = 0; i < t.n; ++i) {
+        const Operand &w = t.v[i];
+        if (!w.written) continue;
+        for (int j = 0; j < t.n; ++j) {
+            const Operand &o = t.v[j];
+            if (j == i || (o.written && j > i) || !ranges_overlap(w.p, w.bytes, o.p, o.bytes)) continue;
+            if (w.in_place != j) return refuse(HJGPU_EINVAL, "%s overlaps %s", w.name, o.name);
+            if (w.p != o.p)
+                return refuse(HJGPU_EINVAL, "%s overlaps %s: it may be the very pointer %s (in place), any other overlap is refused", w.name, o.name, o.name);
+        }
+    }
+    return no_objection();
+}
+
+inline size_t bitmap_bytes(size_t n) { return (n + 31) / 32 * sizeof(uint32_t); }
+
+// ---- the selected look-ups' mask (NULL: no mask): d_match_bits may be d_select_bits itself ---------------------------------------------
+inline Verdict check_select_bits(const uint32_t *select_bits, const uint32_t *match_bits, size_t outer)
+{
+    Operands t;
+    const int mask = t.read(select_bits, bitmap_bytes(outer), 16, "d_select_bits");
+    t.write(match_bits, bitmap_bytes(outer), 1, "d_match_bits", mask);       // (its alignment: check_lookup_columns)
+    return check_operands(t);
+}
+
+// ---- hjgpu_compact_selected ---------------------------------------------------------------------------------------------------------------
+struct CompactCall {
+    const uint32_t *bits;
+    size_t n;
+    uint32_t ncols;
+    const uint32_t *const *in;
+    uint32_t *const *out;
+    uint32_t *rows_out;
+    size_t capacity;
+};
+
+inline Verdict check_compact(const CompactCall &c, const uint64_t *count, bool device_count)
+{
+    if (!count) return refuse(HJGPU_EINVAL, "null count pointer");
+    if (device_count && ((uintptr_t)count & 7)) return refuse(HJGPU_EALIGN, "d_count must be 8-byte aligned");
+    if (c.ncols > HJGPU_COMPACT_MAX_COLS) return refuse(HJGPU_EINVAL, "ncols must not exceed HJGPU_COMPACT_MAX_COLS (8)");
+    if (c.n == 0) return no_objection();                      // nothing is read, nothing but the count is written: anything else may be NULL
+    if (!c.bits) return refuse(HJGPU_EINVAL, "null d_select_bits (a compaction of every row is a copy)");
+    if (c.ncols && (!c.in || !c.out)) return refuse(HJGPU_EINVAL, "null column array");
+    for (uint32_t k = 0; k < c.ncols; ++k)
+        if (!c.in[k] || !c.out[k]) return refuse(HJGPU_EINVAL, "null column pointer");
+    if (c.rows_out && c.n > 0xFFFFFFFFull) return refuse(HJGPU_EINVAL, "d_rows_out holds 32-bit row numbers: n must not exceed 0xFFFFFFFF");
+    // not in place.  (d_count is not in the table: the other three operators refuse a device count word that overlaps an operand, this one
+    // never has - a follow-up, it would refuse calls that are accepted today)
+    Operands t;
+    const size_t obytes = c.capacity * sizeof(uint32_t);
+    t.read(c.bits, bitmap_bytes(c.n), 16, "d_select_bits");
+    for (uint32_t k = 0; k < c.ncols; ++k) t.read(c.in[k], c.n * sizeof(uint32_t), 16, "an input column");
+    for (uint32_t k = 0; k < c.ncols; ++k) t.write(c.out[k], obytes, 16, "an output column");
+    t.write(c.rows_out, obytes, 16, "d_rows_out");
+    return check_operands(t);
+}
+
+// ---- hjgpu_group_sum ------------------------------------------------------------------------------------------------------------------------
+struct GroupCall {
+    const uint32_t *bits;
+    size_t n;
+    uint32_t nkeys, nvals;
+    const uint32_t *const *keys_in, *const *vals_in;
+    uint32_t *const *keys_out;
+    uint64_t *counts_out;
+    uint64_t *const *sums_out;
+    size_t capacity;
+};
+
+inline Verdict check_group(const GroupCall &g, const uint64_t *ngroups, bool device_count)
+{
+    if (!ngroups) return refuse(HJGPU_EINVAL, "null group count pointer");
+    if (device_count && ((uintptr_t)ngroups & 7)) return refuse(HJGPU_EALIGN, "d_ngroups must be 8-byte aligned");
+    if (g.nkeys == 0 || g.nkeys > HJGPU_GROUP_MAX_KEYS) return refuse(HJGPU_EINVAL, "nkeys must be 1 to HJGPU_GROUP_MAX_KEYS (2)");
+    if (g.nvals > HJGPU_GROUP_MAX_VALS) return refuse(HJGPU_EINVAL, "nvals must not exceed HJGPU_GROUP_MAX_VALS (4)");
+    if (hj_group::merge_slots(g.capacity) == 0) return refuse(HJGPU_EINVAL, "capacity must not exceed 2^40 groups");
+    if (g.n == 0) return no_objection();                      // nothing is read, nothing but the count is written: anything else may be NULL
+    if (!g.keys_in || !g.keys_out || (g.nvals && (!g.vals_in || !g.sums_out))) return refuse(HJGPU_EINVAL, "null column array");
+    for (uint32_t k = 0; k < g.nkeys; ++k)
+        if (!g.keys_in[k] || !g.keys_out[k]) return refuse(HJGPU_EINVAL, "null key column pointer");
+    for (uint32_t k = 0; k < g.nvals; ++k)
+        if (!g.vals_in[k] || !g.sums_out[k]) return refuse(HJGPU_EINVAL, "null measure column pointer");
+    Operands t;
+    t.read(g.bits, bitmap_bytes(g.n), 16, "d_select_bits");
+    for (uint32_t k = 0; k < g.nkeys; ++k) t.read(g.keys_in[k], g.n * sizeof(uint32_t), 16, "a key column");
+    for (uint32_t k = 0; k < g.nvals; ++k) t.read(g.vals_in[k], g.n * sizeof(uint32_t), 16, "a measure column");
+    for (uint32_t k = 0; k < g.nkeys; ++k) t.write(g.keys_out[k], g.capacity * sizeof(uint32_t), 16, "a key output column");
+    for (uint32_t k = 0; k < g.nvals; ++k) t.write(g.sums_out[k], g.capacity * sizeof(uint64_t), 16, "a sum column");
+    t.write(g.counts_out, g.capacity * sizeof(uint64_t), 16, "d_counts_out");
+    if (device_count) t.write(ngroups, sizeof(uint64_t), 8, "d_ngroups");
+    return check_operands(t);
+}
+
+// ---- hjgpu_filter_selected ------------------------------------------------------------------------------------------------------------------
+struct FilterCall {
+    const uint32_t *bits;
+    size_t n;
+    uint32_t npreds;
+    const uint32_t *const *cols;
+    const hjgpu_predicate *preds;
+    uint32_t *bits_out;
+};
+
+inline Verdict check_filter(const FilterCall &f, const uint64_t *count, bool device_count)
+{
+    if (device_count && ((uintptr_t)count & 7)) return refuse(HJGPU_EALIGN, "d_count must be 8-byte aligned");
+    if (f.npreds == 0 || f.npreds > HJGPU_FILTER_MAX_PREDS) return refuse(HJGPU_EINVAL, "npreds must be 1 to HJGPU_FILTER_MAX_PREDS (4)");
+    if (f.n == 0) return no_objection();                      // nothing is read, nothing but the count is written: anything else may be NULL
+    if (!f.bits_out && !count) return refuse(HJGPU_EINVAL, "d_bits_out and the count are both null: nothing to compute");
+    if (!f.cols || !f.preds) return refuse(HJGPU_EINVAL, "null column or predicate array");
+    for (uint32_t p = 0; p < f.npreds; ++p) {
+        if (!f.cols[p]) return refuse(HJGPU_EINVAL, "null column pointer");
+        if (f.preds[p].flags & ~(HJGPU_PRED_NOT | HJGPU_PRED_SIGNED)) return refuse(HJGPU_EINVAL, "unknown predicate flag (HJGPU_PRED_NOT and HJGPU_PRED_SIGNED are defined)");
+        if (f.preds[p].reserved) return refuse(HJGPU_EINVAL, "a predicate's reserved word must be 0");
+    }
+    Operands t;
+    const int mask = t.read(f.bits, bitmap_bytes(f.n), 16, "d_select_bits");
+    for (uint32_t p = 0; p < f.npreds; ++p) t.read(f.cols[p], f.n * sizeof(uint32_t), 16, "a column");
+    t.write(f.bits_out, bitmap_bytes(f.n), 16, "d_bits_out", mask);
+    if (device_count) t.write(count, sizeof(uint64_t), 8, "d_count");        // (the blocking form's count is the caller's own word in host memory)
+    return check_operands(t);
+}
+
+// ---- hjgpu_gather_selected ------------------------------------------------------------------------------------------------------------------
+struct GatherCall {
+    const uint32_t *bits;
+    const uint32_t *idx;
+    size_t n;
+    uint32_t ncols;
+    const uint32_t *const *src;
+    size_t src_rows;
+    uint32_t *const *out;
+    uint32_t *bits_out;
+};
+
+// d_counts: the device form's two count words (NULL: none, and the blocking form, whose words are the context's)
+inline Verdict check_gather(const GatherCall &g, const uint64_t *d_counts)
+{
+    if ((uintptr_t)d_counts & 15) return refuse(HJGPU_EALIGN, "d_counts must be 16-byte aligned");
+    if (g.ncols == 0 || g.ncols > HJGPU_GATHER_MAX_COLS) return refuse(HJGPU_EINVAL, "ncols must be 1 to HJGPU_GATHER_MAX_COLS (4)");
+    if (g.src_rows > 0xFFFFFFFFull) return refuse(HJGPU_EINVAL, "src_rows must not exceed 0xFFFFFFFF: an index is a uint32 and HJGPU_NULL_VAL is never a legal one");
+    if (g.n == 0) return no_objection();                      // nothing is read, nothing but the counts is written: anything else may be NULL
+    if (!g.idx) return refuse(HJGPU_EINVAL, "null d_idx");
+    if (!g.src || !g.out) return refuse(HJGPU_EINVAL, "null column array");
+    for (uint32_t k = 0; k < g.ncols; ++k)
+        if (!g.src[k] || !g.out[k]) return refuse(HJGPU_EINVAL, "null column pointer");
+    // (every output column names d_idx; being outputs, only one of them can be it)
+    Operands t;
+    const size_t cbytes = g.n * sizeof(uint32_t);
+    const int mask = t.read(g.bits, bitmap_bytes(g.n), 16, "d_select_bits");
+    const int idx = t.read(g.idx, cbytes, 16, "d_idx");
+    for (uint32_t k = 0; k < g.ncols; ++k) t.read(g.src[k], g.src_rows * sizeof(uint32_t), 16, "a source column");
+    for (uint32_t k = 0; k < g.ncols; ++k) t.write(g.out[k], cbytes, 16, "an output column", idx);
+    t.write(g.bits_out, bitmap_bytes(g.n), 16, "d_bits_out", mask);
+    t.write(d_counts, 2 * sizeof(uint64_t), 16, "d_counts");
+    return check_operands(t);
+}
+
+}  // namespace colop

@@ -1084,7 +1084,7 @@ int phj_enqueue(hjgpu_ctx *ctx, const PhjPlan &pl, const Rel &R, const Rel &S, h
     if (bs && run.road.joins && !o.grp) CHK(close_gaps(ctx, o.out, workers, bs, run.st, stream, pl.mode));
     record(ctx, EV_GAPS, stream);
     ctx->stats.fanout1 = pl.F1; ctx->stats.fanout2 = pl.F2; ctx->stats.buckets = 0; ctx->stats.batches = run.batches_used;
-    ctx->last_algo = 1;
+    ctx->last_algo = ALGO_PHJ;
     return HJGPU_OK;
 }
 
@@ -1220,7 +1220,7 @@ int npj_enqueue(hjgpu_ctx *ctx, const uint32_t *rk, const uint32_t *rv, size_t i
     const NpjTable table = {reinterpret_cast<const u64 *>(ctx->table.p), buckets, factor, line};
     CHK(npj_probe_enqueue(ctx, {sk, sv, outer}, table, out, stream, {.unique = unique, .mode = mode, .bucket_bits = bits}));
     ctx->stats.fanout1 = ctx->stats.fanout2 = 0; ctx->stats.buckets = buckets; ctx->stats.batches = 0;
-    ctx->last_algo = 0;
+    ctx->last_algo = ALGO_NPJ;
     return HJGPU_OK;
 }
 
@@ -1231,7 +1231,7 @@ static void lookup_done(hjgpu_ctx *ctx, hipStream_t stream, bool lds, size_t buc
     record(ctx, EV_JOIN, stream);
     record(ctx, EV_GAPS, stream);
     ctx->stats.fanout1 = ctx->stats.fanout2 = lds ? 1 : 0; ctx->stats.buckets = buckets; ctx->stats.batches = 0;
-    ctx->last_algo = lds ? 1 : 0;
+    ctx->last_algo = lds ? ALGO_PHJ : ALGO_NPJ;
     ctx->last_had_output = false;
     ctx->last_lookup = true;
 }
@@ -1262,16 +1262,10 @@ int check_lookup_columns(hjgpu_ctx *ctx, const uint32_t *sk, size_t outer, const
     return HJGPU_OK;
 }
 
-// what the selected look-ups check of their mask (NULL: no mask).  d_match_bits may be d_select_bits itself - the kernels read a word of
-// the mask in the wave that stores it, before it stores it -; two bitmaps that overlap in any other way would be read after they were
-// written
+// what the selected look-ups check of their mask (NULL: no mask): d_match_bits may be d_select_bits itself, the in-place rule of colop_checks.hpp
 int check_select_bits(hjgpu_ctx *ctx, const uint32_t *select_bits, const uint32_t *match_bits, size_t outer)
 {
-    if ((uintptr_t)select_bits & 15) return fail(ctx, HJGPU_EALIGN, "d_select_bits must be 16-byte aligned");
-    const uintptr_t s = (uintptr_t)select_bits, m = (uintptr_t)match_bits, bytes = (outer + 31) / 32 * sizeof(uint32_t);
-    if (select_bits && match_bits && s != m && s < m + bytes && m < s + bytes)
-        return fail(ctx, HJGPU_EINVAL, "d_match_bits overlaps d_select_bits: it may be the very pointer d_select_bits (in place), any other overlap of the two bitmaps is refused");
-    return HJGPU_OK;
+    return refused(ctx, colop::check_select_bits(select_bits, match_bits, outer));
 }
 
 static int npj_lookup_whole(hjgpu_ctx *ctx, const uint32_t *rk, const uint32_t *rv, size_t inner, const uint32_t *sk, size_t outer,
@@ -1383,7 +1377,7 @@ int hjgpu_destroy(hjgpu_ctx *ctx)
     (void)hipDeviceSynchronize();
     DevBuf *all[] = {&ctx->tmp[0], &ctx->tmp[1], &ctx->tmp[2], &ctx->tmp[3], &ctx->tmp[4], &ctx->tmp[5],
                      &ctx->tmp[6], &ctx->tmp[7], &ctx->meta, &ctx->table, &ctx->state, &ctx->moves,
-                     &ctx->final_offsets, &ctx->build_bits, &ctx->grp[0], &ctx->grp[1], &ctx->grp[2], &ctx->grp[3], &ctx->grp_off, &ctx->audit, &ctx->audit_lay, &ctx->compact, &ctx->group, &ctx->filter, &ctx->gather};
+                     &ctx->final_offsets, &ctx->build_bits, &ctx->grp[0], &ctx->grp[1], &ctx->grp[2], &ctx->grp[3], &ctx->grp_off, &ctx->audit, &ctx->audit_lay, &ctx->compact, &ctx->group, &ctx->count_words};
     for (DevBuf *b : all) if (b->p) (void)hipFree(b->p);
     for (int i = 0; i < EV_COUNT; ++i) (void)hipEventDestroy(ctx->ev[i]);
     if (ctx->aux) (void)hipStreamDestroy(ctx->aux);
@@ -1518,42 +1512,20 @@ int hjgpu_get_stats(hjgpu_ctx *ctx, hjgpu_stats *s)
     r.ms_total = span(EV_BEGIN, EV_GAPS);
     r.ms_inner_wait = 0;
     fill_reserve(ctx, &r);
-    if (ctx->last_algo == 2) {                 // hjgpu_column_sums: one kernel
-        memset(&r, 0, sizeof(r));
-        r.ms_total = span(EV_BEGIN, EV_GAPS);
-        fill_reserve(ctx, &r);
-        *s = r;
-        return HJGPU_OK;
-    }
-    if (ctx->last_algo == 3) {                 // hjgpu_compact_selected: the counting launch, then the compaction
+    if (ctx->last_algo >= ALGO_ONE_KERNEL) {
+        // one operator (hjgpu_partition*, hjgpu_column_sums, the column operators): the stages it has are the events it recorded - a span to
+        // or from an event it did not record is 0.  Compaction, filter and gather record EV_JOIN and EV_GAPS back to back: only the grouped
+        // aggregation has a stage (the emit) between them
         memset(&r, 0, sizeof(r));
         r.ms_total = span(EV_BEGIN, EV_GAPS);
         r.ms_histogram = span(EV_BEGIN, EV_S_HIST);
         r.ms_join = span(EV_S_HIST, EV_JOIN);
+        if (ctx->last_algo == ALGO_GROUP_SUM) r.ms_close_gaps = span(EV_JOIN, EV_GAPS);
         fill_reserve(ctx, &r);
         *s = r;
         return HJGPU_OK;
     }
-    if (ctx->last_algo == 4) {                 // hjgpu_group_sum: the clears, the aggregation, the emit
-        memset(&r, 0, sizeof(r));
-        r.ms_total = span(EV_BEGIN, EV_GAPS);
-        r.ms_histogram = span(EV_BEGIN, EV_S_HIST);
-        r.ms_join = span(EV_S_HIST, EV_JOIN);
-        r.ms_close_gaps = span(EV_JOIN, EV_GAPS);
-        fill_reserve(ctx, &r);
-        *s = r;
-        return HJGPU_OK;
-    }
-    if (ctx->last_algo == 5 || ctx->last_algo == 6) {      // hjgpu_filter_selected, hjgpu_gather_selected: the clear of the count words, then the kernel
-        memset(&r, 0, sizeof(r));
-        r.ms_total = span(EV_BEGIN, EV_GAPS);
-        r.ms_histogram = span(EV_BEGIN, EV_S_HIST);
-        r.ms_join = span(EV_S_HIST, EV_JOIN);
-        fill_reserve(ctx, &r);
-        *s = r;
-        return HJGPU_OK;
-    }
-    if (ctx->last_algo == 0) {
+    if (ctx->last_algo == ALGO_NPJ) {
         r.ms_build = span(EV_BEGIN, EV_R_HIST);
         r.ms_join = span(EV_R_HIST, EV_JOIN);
         r.ms_histogram = r.ms_plan = r.ms_scatter1 = r.ms_scatter2 = 0;
@@ -2008,7 +1980,7 @@ static int broadcast_enqueue(hjgpu_ctx *ctx, const Rel &R, const Rel &S, const h
     if (bs) CHK(close_gaps(ctx, out, workers, bs, st, stream, jmode));
     record(ctx, EV_GAPS, stream);
     ctx->stats.fanout1 = 1; ctx->stats.fanout2 = 1; ctx->stats.buckets = 0; ctx->stats.batches = 0;
-    ctx->last_algo = 1;
+    ctx->last_algo = ALGO_PHJ;
     return HJGPU_OK;
 }
 
@@ -2120,7 +2092,7 @@ static int phj_grouped(hjgpu_ctx *ctx, uint32_t G, uint32_t chunks, const Rel &R
     sum.groups = G;
     ctx->stats = sum;
     ctx->stats_override = true;
-    ctx->last_algo = 1;
+    ctx->last_algo = ALGO_PHJ;
     return HJGPU_OK;
 }
 
@@ -2199,7 +2171,7 @@ static int phj_grouped_device(hjgpu_ctx *ctx, uint32_t G, uint32_t chunks, const
     record(ctx, EV_GAPS, stream);
     ctx->grp_ev_groups = G;
     ctx->stats.fanout1 = pl.F1; ctx->stats.fanout2 = pl.F2; ctx->stats.buckets = 0; ctx->stats.batches = 0;
-    ctx->last_algo = 1;
+    ctx->last_algo = ALGO_PHJ;
     return HJGPU_OK;
 }
 

@@ -1,0 +1,248 @@
+// hjgpu_colops.hip - the column operators of include/hjgpu.h over a bitmap's rows: hjgpu_compact_selected, hjgpu_group_sum,
+// hjgpu_filter_selected, hjgpu_gather_selected and their _async forms.  What they refuse from their arguments alone is
+// colop_checks.hpp; their kernels are gen_kernels.hip's.  The blocking and the enqueue-only form of an operator are ONE path (X_call): they
+// differ in where the count words lie - the context's, or the caller's in device memory - and in the blocking form's tail.
+#include "hjgpu_ctx.hpp"
+
+using namespace hjapi;
+using namespace colop;
+
+// what every call does between its checks and its enqueues: nothing is allocated or enqueued for a refused call or on a capturing stream
+static int colop_begin(hjgpu_ctx *ctx, const Verdict &checked, hipStream_t stream, DevBuf &workspace, size_t bytes)
+{
+    CHK(refused(ctx, checked));
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    CHK(refuse_capture(ctx, stream));
+    ReserveClock clock(ctx);                             // (hjgpu_stats.ms_reserve: the merge table grows the first time a capacity is seen)
+    return ensure(ctx, workspace, bytes);
+}
+
+// the blocking forms' tail: k count words come back once the stream is through, to `got` and - if the caller wants them - to `out`
+static int read_back(hjgpu_ctx *ctx, const u64 *d_words, uint32_t k, u64 got[2], uint64_t *out, hipStream_t stream)
+{
+    got[0] = got[1] = 0;
+    if (k) HIPCHK(ctx, hipMemcpyAsync(got, d_words, k * sizeof(u64), hipMemcpyDeviceToHost, stream));
+    HIPCHK(ctx, hipStreamSynchronize(stream));
+    for (uint32_t i = 0; out && i < k; ++i) out[i] = got[i];
+    return HJGPU_OK;
+}
+
+// ---- compaction by bitmap ---------------------------------------------------------
+// the two launches (three beyond HJ_COMPACT_LAUNCH_COLS columns); d_count in device memory.  hjgpu_get_stats afterwards: ms_histogram = the
+// counting launch, ms_join = the compaction, ms_total = both
+static int compact_enqueue(hjgpu_ctx *ctx, const CompactCall &c, u64 *counts, u64 *d_count, hipStream_t stream)
+{
+    const hj_compact::Layout lay = hj_compact::layout(c.n, hj_compact::ranges_of(ctx->cus));
+    const uint32_t ncols = c.n ? c.ncols : 0;
+    uint32_t *rows_out = c.n ? c.rows_out : nullptr;
+    begin_span(ctx, ALGO_COMPACT, stream);
+    CHK(hj_launch_compact_count(c.bits, lay, counts, stream));
+    record(ctx, EV_S_HIST, stream);
+    if (ncols == 0 && !rows_out) CHK(hj_launch_compact_total(counts, lay.ranges, d_count, stream));
+    for (uint32_t c0 = 0; c0 < ncols || (c0 == 0 && rows_out); c0 += HJ_COMPACT_LAUNCH_COLS) {
+        CompactArgs a{};
+        a.select_bits = c.bits; a.lay = lay; a.counts = counts; a.capacity = c.capacity;
+        a.d_count = c0 == 0 ? d_count : nullptr;
+        a.rows_out = c0 == 0 ? rows_out : nullptr;
+        const uint32_t k = std::min<uint32_t>(ncols - c0, HJ_COMPACT_LAUNCH_COLS);
+        for (uint32_t i = 0; i < k; ++i) { a.in[i] = c.in[c0 + i]; a.out[i] = c.out[c0 + i]; }
+        CHK(hj_launch_compact(a, k, stream));
+    }
+    record(ctx, EV_JOIN, stream);
+    record(ctx, EV_GAPS, stream);
+    return HJGPU_OK;
+}
+
+// the context's workspace (constant size): the ranges' counts, and the blocking form's count behind them
+static int compact_call(hjgpu_ctx *ctx, const CompactCall &c, uint64_t *count, bool device_count, void *stream_)
+{
+    if (!ctx) return HJGPU_EINVAL;
+    hipStream_t stream = (hipStream_t)stream_;
+    CHK(colop_begin(ctx, check_compact(c, count, device_count), stream, ctx->compact, ((size_t)hj_compact::MAX_RANGES + 1) * sizeof(u64)));
+    u64 *counts = reinterpret_cast<u64 *>(ctx->compact.p);
+    u64 *d_count = device_count ? reinterpret_cast<u64 *>(count) : counts + hj_compact::MAX_RANGES;
+    CHK(compact_enqueue(ctx, c, counts, d_count, stream));
+    if (device_count) return HJGPU_OK;
+    u64 got[2];
+    CHK(read_back(ctx, d_count, 1, got, count, stream));
+    if (c.n && (c.ncols || c.rows_out) && got[0] > c.capacity)
+        return fail(ctx, HJGPU_EOVERFLOW, "hjgpu_compact_selected: more selected rows than capacity (*count holds their number, the first capacity rows of every output are valid)");
+    return HJGPU_OK;
+}
+
+// ---- grouped aggregation ----------------------------------------------------------
+// the three enqueues: the clears (the count word; for n > 0 the overflow word and the merge table), the aggregation, the emit.
+// hjgpu_get_stats afterwards: ms_histogram = the clears, ms_join = the aggregation, ms_close_gaps = the emit, ms_total = all of them
+static int group_enqueue(hjgpu_ctx *ctx, const GroupCall &g, u64 *d_ngroups, hipStream_t stream)
+{
+    const u64 slots = hj_group::merge_slots(g.capacity);
+    char *ws = reinterpret_cast<char *>(ctx->group.p);
+    begin_span(ctx, ALGO_GROUP_SUM, stream);
+    HIPCHK(ctx, hj_zero_async(d_ngroups, sizeof(u64), stream));
+    if (g.n) HIPCHK(ctx, hj_zero_async(ws + sizeof(u64), (size_t)(hj_group::workspace_bytes(slots) - sizeof(u64)), stream));
+    record(ctx, EV_S_HIST, stream);
+    if (g.n) {
+        GroupArgs a{};
+        a.select_bits = g.bits; a.n = g.n; a.nkeys = g.nkeys; a.nvals = g.nvals;
+        for (uint32_t c = 0; c < g.nkeys; ++c) a.keys[c] = g.keys_in[c];
+        for (uint32_t c = 0; c < g.nvals; ++c) a.vals[c] = g.vals_in[c];
+        a.merge = reinterpret_cast<hj_group::Slot *>(ws + hj_group::WORKSPACE_HEAD);
+        a.merge_mask = slots - 1;
+        a.overflow = reinterpret_cast<uint32_t *>(ws + sizeof(u64));
+        CHK(hj_launch_group_sum(a, ctx->cus, stream));
+    }
+    record(ctx, EV_JOIN, stream);
+    if (g.n) {
+        GroupEmitArgs e{};
+        e.merge = reinterpret_cast<const hj_group::Slot *>(ws + hj_group::WORKSPACE_HEAD);
+        e.slots = slots; e.nkeys = g.nkeys; e.nvals = g.nvals; e.capacity = g.capacity; e.counts_out = reinterpret_cast<u64 *>(g.counts_out);
+        for (uint32_t c = 0; c < g.nkeys; ++c) e.keys_out[c] = g.keys_out[c];
+        for (uint32_t c = 0; c < g.nvals; ++c) e.sums_out[c] = reinterpret_cast<u64 *>(g.sums_out[c]);
+        e.d_ngroups = d_ngroups;
+        CHK(hj_launch_group_emit(e, ctx->cus, stream));
+    }
+    record(ctx, EV_GAPS, stream);
+    return HJGPU_OK;
+}
+
+// the context's workspace (group_layout.hpp; sized from the capacity): the blocking form's count word first, the overflow word, the merge table
+static int group_call(hjgpu_ctx *ctx, const GroupCall &g, uint64_t *ngroups, bool device_count, void *stream_)
+{
+    if (!ctx) return HJGPU_EINVAL;
+    hipStream_t stream = (hipStream_t)stream_;
+    CHK(colop_begin(ctx, check_group(g, ngroups, device_count), stream, ctx->group, (size_t)hj_group::workspace_bytes(hj_group::merge_slots(g.capacity))));
+    u64 *d_ngroups = reinterpret_cast<u64 *>(device_count ? (void *)ngroups : ctx->group.p);
+    CHK(group_enqueue(ctx, g, d_ngroups, stream));
+    if (device_count) return HJGPU_OK;
+    u64 got[2];
+    CHK(read_back(ctx, d_ngroups, 1, got, ngroups, stream));
+    if (got[0] > g.capacity)
+        return fail(ctx, HJGPU_EOVERFLOW, "hjgpu_group_sum: more groups than capacity (*ngroups holds a lower bound of their number that exceeds capacity; the outputs are unspecified)");
+    return HJGPU_OK;
+}
+
+// ---- filter -----------------------------------------------------------------------
+// the two enqueues: the clear of the count word (d_count NULL: none), the kernel (n == 0: none).  hjgpu_get_stats afterwards: ms_histogram =
+// the clear, ms_join = the kernel, ms_total = both
+static int filter_enqueue(hjgpu_ctx *ctx, const FilterCall &f, u64 *d_count, hipStream_t stream)
+{
+    begin_span(ctx, ALGO_FILTER, stream);
+    if (d_count) HIPCHK(ctx, hj_zero_async(d_count, sizeof(u64), stream));
+    record(ctx, EV_S_HIST, stream);
+    if (f.n) {
+        FilterArgs a{};
+        a.select_bits = f.bits; a.bits_out = f.bits_out; a.count = d_count; a.n = f.n;
+        for (uint32_t p = 0; p < f.npreds; ++p) {
+            a.cols[p] = f.cols[p];
+            a.preds[p] = hj_filter::normalise(f.preds[p].lo, f.preds[p].hi, f.preds[p].flags);
+        }
+        CHK(hj_launch_filter(a, f.npreds, ctx->cus, stream));
+    }
+    record(ctx, EV_JOIN, stream);
+    record(ctx, EV_GAPS, stream);
+    return HJGPU_OK;
+}
+
+// the context's count words (made by the first call of either form, of the filter or of the gather): the blocking form's count is the first
+static int filter_call(hjgpu_ctx *ctx, const FilterCall &f, uint64_t *count, bool device_count, void *stream_)
+{
+    if (!ctx) return HJGPU_EINVAL;
+    hipStream_t stream = (hipStream_t)stream_;
+    CHK(colop_begin(ctx, check_filter(f, count, device_count), stream, ctx->count_words, 2 * sizeof(u64)));
+    u64 *word = reinterpret_cast<u64 *>(ctx->count_words.p);
+    if (device_count) return filter_enqueue(ctx, f, reinterpret_cast<u64 *>(count), stream);
+    CHK(filter_enqueue(ctx, f, count ? word : nullptr, stream));
+    u64 got[2];
+    return read_back(ctx, word, count ? 1 : 0, got, count, stream);
+}
+
+// ---- gather by row number -----------------------------------------------------------
+// the two enqueues: the clear of the count words (d_counts NULL: none), the kernel (n == 0: none).  hjgpu_get_stats afterwards: ms_histogram =
+// the clear, ms_join = the kernel, ms_total = both
+static int gather_enqueue(hjgpu_ctx *ctx, const GatherCall &g, u64 *d_counts, hipStream_t stream)
+{
+    begin_span(ctx, ALGO_GATHER, stream);
+    if (d_counts) HIPCHK(ctx, hj_zero_async(d_counts, 2 * sizeof(u64), stream));
+    record(ctx, EV_S_HIST, stream);
+    if (g.n) {
+        GatherArgs a{};
+        a.select_bits = g.bits; a.idx = g.idx; a.bits_out = g.bits_out; a.counts = d_counts; a.n = g.n; a.src_rows = (uint32_t)g.src_rows;
+        for (uint32_t c = 0; c < g.ncols; ++c) { a.src[c] = g.src[c]; a.out[c] = g.out[c]; }
+        CHK(hj_launch_gather(a, g.ncols, ctx->cus, stream));
+    }
+    record(ctx, EV_JOIN, stream);
+    record(ctx, EV_GAPS, stream);
+    return HJGPU_OK;
+}
+
+// the blocking form counts in the context's words also when counts is NULL: HJGPU_ERANGE is read from them
+static int gather_call(hjgpu_ctx *ctx, const GatherCall &g, uint64_t *counts, bool device_count, void *stream_)
+{
+    if (!ctx) return HJGPU_EINVAL;
+    hipStream_t stream = (hipStream_t)stream_;
+    CHK(colop_begin(ctx, check_gather(g, device_count ? counts : nullptr), stream, ctx->count_words, 2 * sizeof(u64)));
+    u64 *words = reinterpret_cast<u64 *>(ctx->count_words.p);
+    CHK(gather_enqueue(ctx, g, device_count ? reinterpret_cast<u64 *>(counts) : words, stream));
+    if (device_count) return HJGPU_OK;
+    u64 got[2];
+    CHK(read_back(ctx, words, 2, got, counts, stream));
+    if (got[1])
+        return fail(ctx, HJGPU_ERANGE, "hjgpu_gather_selected: selected rows hold an index that is neither below src_rows nor HJGPU_NULL_VAL (counts[1] holds their number; they were written as NULL rows, every output is complete)");
+    return HJGPU_OK;
+}
+
+extern "C" {
+
+int hjgpu_compact_selected_async(hjgpu_ctx *ctx, const uint32_t *d_select_bits, size_t n, uint32_t ncols, const uint32_t *const *d_cols_in,
+                                 uint32_t *const *d_cols_out, uint32_t *d_rows_out, size_t capacity, uint64_t *d_count, void *stream)
+{
+    return compact_call(ctx, {d_select_bits, n, ncols, d_cols_in, d_cols_out, d_rows_out, capacity}, d_count, true, stream);
+}
+
+int hjgpu_compact_selected(hjgpu_ctx *ctx, const uint32_t *d_select_bits, size_t n, uint32_t ncols, const uint32_t *const *d_cols_in,
+                           uint32_t *const *d_cols_out, uint32_t *d_rows_out, size_t capacity, uint64_t *count, void *stream)
+{
+    return compact_call(ctx, {d_select_bits, n, ncols, d_cols_in, d_cols_out, d_rows_out, capacity}, count, false, stream);
+}
+
+int hjgpu_group_sum_async(hjgpu_ctx *ctx, const uint32_t *d_select_bits, size_t n, uint32_t nkeys, const uint32_t *const *d_keys_in,
+                          uint32_t nvals, const uint32_t *const *d_vals_in, uint32_t *const *d_keys_out, uint64_t *d_counts_out,
+                          uint64_t *const *d_sums_out, size_t capacity, uint64_t *d_ngroups, void *stream)
+{
+    return group_call(ctx, {d_select_bits, n, nkeys, nvals, d_keys_in, d_vals_in, d_keys_out, d_counts_out, d_sums_out, capacity}, d_ngroups, true, stream);
+}
+
+int hjgpu_group_sum(hjgpu_ctx *ctx, const uint32_t *d_select_bits, size_t n, uint32_t nkeys, const uint32_t *const *d_keys_in,
+                    uint32_t nvals, const uint32_t *const *d_vals_in, uint32_t *const *d_keys_out, uint64_t *d_counts_out,
+                    uint64_t *const *d_sums_out, size_t capacity, uint64_t *ngroups, void *stream)
+{
+    return group_call(ctx, {d_select_bits, n, nkeys, nvals, d_keys_in, d_vals_in, d_keys_out, d_counts_out, d_sums_out, capacity}, ngroups, false, stream);
+}
+
+int hjgpu_filter_selected_async(hjgpu_ctx *ctx, const uint32_t *d_select_bits, size_t n, uint32_t npreds, const uint32_t *const *d_cols,
+                                const hjgpu_predicate *preds, uint32_t *d_bits_out, uint64_t *d_count, void *stream)
+{
+    return filter_call(ctx, {d_select_bits, n, npreds, d_cols, preds, d_bits_out}, d_count, true, stream);
+}
+
+int hjgpu_filter_selected(hjgpu_ctx *ctx, const uint32_t *d_select_bits, size_t n, uint32_t npreds, const uint32_t *const *d_cols,
+                          const hjgpu_predicate *preds, uint32_t *d_bits_out, uint64_t *count, void *stream)
+{
+    return filter_call(ctx, {d_select_bits, n, npreds, d_cols, preds, d_bits_out}, count, false, stream);
+}
+
+int hjgpu_gather_selected_async(hjgpu_ctx *ctx, const uint32_t *d_select_bits, const uint32_t *d_idx, size_t n, uint32_t ncols,
+                                const uint32_t *const *d_src_cols, size_t src_rows, uint32_t *const *d_cols_out, uint32_t *d_bits_out,
+                                uint64_t *d_counts, void *stream)
+{
+    return gather_call(ctx, {d_select_bits, d_idx, n, ncols, d_src_cols, src_rows, d_cols_out, d_bits_out}, d_counts, true, stream);
+}
+
+int hjgpu_gather_selected(hjgpu_ctx *ctx, const uint32_t *d_select_bits, const uint32_t *d_idx, size_t n, uint32_t ncols,
+                          const uint32_t *const *d_src_cols, size_t src_rows, uint32_t *const *d_cols_out, uint32_t *d_bits_out,
+                          uint64_t counts[2], void *stream)
+{
+    return gather_call(ctx, {d_select_bits, d_idx, n, ncols, d_src_cols, src_rows, d_cols_out, d_bits_out}, counts, false, stream);
+}
+
+}  // extern "C"

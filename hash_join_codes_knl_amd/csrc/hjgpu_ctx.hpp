@@ -1,6 +1,6 @@
 // hjgpu_ctx.hpp - what the translation units behind include/hjgpu.h share: the context, its workspace layout, the plan of a
-// PHJ / CPRA join, and the planning / enqueue functions of hjgpu_api.hip that the operator-level entry points (hjgpu_ops.hip)
-// and the host pipelines (hjgpu_host.hip) call.  Internal: nothing outside csrc/ includes it.
+// PHJ / CPRA join, and the planning / enqueue functions of hjgpu_api.hip that the operator-level entry points (hjgpu_ops.hip), the
+// column operators (hjgpu_colops.hip) and the host pipelines (hjgpu_host.hip) call.  Internal: nothing outside csrc/ includes it.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "hj_internal.hpp"
+#include "colop_checks.hpp"
 
 
 struct DevBuf {
@@ -46,6 +47,11 @@ struct DevState {
 enum { EV_BEGIN = 0, EV_S_HIST, EV_S_PLAN, EV_S_SC1, EV_S_SC2, EV_WAITED,
        EV_R_HIST, EV_R_PLAN, EV_R_SC1, EV_R_SC2, EV_JOIN, EV_GAPS, EV_COUNT };
 
+// what the context ran last: hjgpu_get_stats reads the events by it.  From ALGO_ONE_KERNEL on, one operator between EV_BEGIN and EV_GAPS
+// (begin_span) that records EV_S_HIST and EV_JOIN where it has stages
+enum Algo { ALGO_NONE = -1, ALGO_NPJ = 0, ALGO_PHJ = 1,        // (PHJ, CPRA and the LDS-road look-up)
+            ALGO_ONE_KERNEL = 2,                               // hjgpu_partition*, hjgpu_column_sums, the hjgpu_*_ms probes
+            ALGO_COMPACT = 3, ALGO_GROUP_SUM = 4, ALGO_FILTER = 5, ALGO_GATHER = 6 };
 
 struct hjgpu_ctx {
     int device = 0;
@@ -60,13 +66,13 @@ struct hjgpu_ctx {
     DevBuf final_offsets;   // per-wave end cursors
     DevBuf compact;         // hjgpu_compact_selected: the ranges' counts and the blocking form's count (constant size, made by the first call)
     DevBuf group;           // hjgpu_group_sum: the blocking form's count word, the overflow word and the merge table (group_layout.hpp; grows with the capacity)
-    DevBuf filter;          // hjgpu_filter_selected: the count word that the kernel adds to - the blocking form reads it back (8 bytes, made by the first call)
-    DevBuf gather;          // hjgpu_gather_selected: the two count words that the kernel adds to - the blocking form reads them back (16 bytes, made by the first call)
+    DevBuf count_words;     // hjgpu_filter_selected (the first word) and hjgpu_gather_selected (both): the count words that the kernel adds to - the blocking
+                            // forms read them back (16 bytes, made by the first call of either)
     DevBuf build_bits;      // right / full outer joins: one bit per row of the partitioned build array (PHJ / CPRA) or per bucket (NPJ)
     hipEvent_t ev[EV_COUNT];
     bool ev_valid[EV_COUNT];
     hjgpu_stats stats;
-    int last_algo = -1;     // 0 npj, 1 phj/cpra, 2 one kernel (hjgpu_column_sums ...), 3 hjgpu_compact_selected, 4 hjgpu_group_sum, 5 hjgpu_filter_selected, 6 hjgpu_gather_selected
+    Algo last_algo = ALGO_NONE;
     bool last_lookup = false;   // the last operation was a positional look-up (hjgpu_npj_lookup*): no close_gaps, ms_close_gaps is 0
     // hjgpu_phj_build: the partitioned build side (tmp[0] / tmp[4]) and its plan (meta) stay valid until
     // another entry point uses the workspace
@@ -136,6 +142,8 @@ const uint32_t DEFAULT_NPJ_FACTOR = 0x9E3779B1u;
 const uint32_t DEFAULT_F0 = 0x7FEB352Du;      // grouped plans: pass 0 (phj_grouped takes another one when a pass factor of the join equals it)
 
 int fail(hjgpu_ctx *ctx, int status, const char *what, hipError_t e = hipSuccess);
+// a check of colop_checks.hpp as the context's error: HJGPU_OK, or its status with its text in hjgpu_last_error
+inline int refused(hjgpu_ctx *ctx, const colop::Verdict &v) { return v.status == HJGPU_OK ? HJGPU_OK : fail(ctx, v.status, v.text); }
 
 // The partial-line stores (K6) of a SOLO join - a blocking call of a context with option "solo": the caller waits for it and promises
 // that nothing else runs on the device beside it - are plain; every other join (enqueue-only, host batches, multi-GPU slices, and
@@ -249,6 +257,13 @@ int check_join_mode(hjgpu_ctx *ctx, uint32_t flags);
 int refuse_join_mode(hjgpu_ctx *ctx, uint32_t flags, const char *entry);
 void choose_fanout(const HjTuning &tune, size_t inner, const hjgpu_phj_params *prm, uint32_t *F1, uint32_t *F2, bool *big_tables);
 void record(hjgpu_ctx *ctx, int which, hipStream_t s);
+// an operator's timed span begins: whatever events the last one left are void, hjgpu_get_stats reads the new ones as `op`'s
+inline void begin_span(hjgpu_ctx *ctx, Algo op, hipStream_t s)
+{
+    for (int i = 0; i < EV_COUNT; ++i) ctx->ev_valid[i] = false;
+    ctx->last_algo = op;
+    record(ctx, EV_BEGIN, s);
+}
 int audit_begin(hjgpu_ctx *ctx, int kind, size_t inner, size_t outer, hipStream_t stream, u64 **rec);
 // hj_audit_partitions into stage `stage` of the call's record, remembered for hjgpu_audit_recheck
 int audit_partitions(hjgpu_ctx *ctx, int stage, const u64 *tuples, const u64 *beg, const u64 *end, uint32_t parts, const HjAuditHash &h, u64 *rec,

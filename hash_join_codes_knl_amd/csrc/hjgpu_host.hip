@@ -358,7 +358,7 @@ static int join_host_batched(hjgpu_ctx *ctx, int algorithm, const uint32_t *ik, 
                     hip_ok(hj_zero_async(&st->nmoves, sizeof(uint32_t), run), "clearing the move count");
                 }
                 rc = npj_probe_enqueue(ctx, batch_in(slot, m), built, rows ? &dev_out[slot] : nullptr, run, {.unique = unique});
-                ctx->stats.fanout1 = ctx->stats.fanout2 = 0; ctx->stats.buckets = buckets; ctx->last_algo = 0;
+                ctx->stats.fanout1 = ctx->stats.fanout2 = 0; ctx->stats.buckets = buckets; ctx->last_algo = ALGO_NPJ;
                 if (rows) {
                     hip_ok(hipMemcpyAsync(&h_state[i], ctx->state.p, sizeof(DevState), hipMemcpyDeviceToHost, run), "hipMemcpyAsync(state)");
                     hip_ok(hipEventRecord(joined[slot], run), "hipEventRecord");

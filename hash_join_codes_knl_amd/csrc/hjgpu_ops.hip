@@ -1,6 +1,7 @@
 // hjgpu_ops.hip - the operator-level entry points of include/hjgpu.h (the reference's operators one by one: histogram /
 // partition / build / probe, phj.cpp:693-1231, npj.cpp:190-364), the relations that arrive pass-1-partitioned (the receiving
-// side of the multi-GPU CPRA), and the generator / measurement helpers.  Context, planning and whole joins: hjgpu_api.hip.
+// side of the multi-GPU CPRA), and the generator / measurement helpers.  Context, planning and whole joins: hjgpu_api.hip; the
+// column operators over a bitmap's rows (compaction, grouped aggregation, filter, gather): hjgpu_colops.hip.
 #include "hjgpu_ctx.hpp"
 
 using namespace hjapi;
@@ -32,10 +33,8 @@ int partition_op(hjgpu_ctx *ctx, const uint32_t *d_keys, const uint32_t *d_vals,
     CHK(ensure(ctx, ctx->meta, sz.total_bytes));
     MetaLayout m = carve(ctx->meta.p, 1, fanout, fanout, geom.ranges_per_chunk);
     // hjgpu_get_stats().ms_total afterwards = duration of the whole operator (histogram + plan + scatter)
-    for (int i = 0; i < EV_COUNT; ++i) ctx->ev_valid[i] = false;
-    ctx->last_algo = 2;
-    record(ctx, EV_BEGIN, stream);
-    u64 *audit = nullptr;                  // option "audit", packed form: stage 0 the columns as read, stage 1 the packed output where it lies
+    begin_span(ctx, ALGO_ONE_KERNEL, stream);
+    u64 *audit = nullptr;                 // option "audit", packed form: stage 0 the columns as read, stage 1 the packed output where it lies
     if (form.packed) CHK(audit_begin(ctx, 3, n, 0, stream, &audit));
     HIPCHK(ctx, hj_zero_async(m.counts[0], m.counts_bytes, stream));
     if (form.counts2) {
@@ -182,7 +181,7 @@ int hjgpu_join_partitions(hjgpu_ctx *ctx,
     record(ctx, EV_JOIN, stream);
     if (bs) CHK(close_gaps(ctx, out, workers, bs, st, stream));
     record(ctx, EV_GAPS, stream);
-    ctx->last_algo = 1;
+    ctx->last_algo = ALGO_PHJ;
     return finish_blocking(ctx, result, out, stream);
 }
 
@@ -215,7 +214,7 @@ int hjgpu_npj_probe(hjgpu_ctx *ctx, const uint32_t *d_keys, const uint32_t *d_va
     record(ctx, EV_BEGIN, stream); record(ctx, EV_R_HIST, stream);
     const NpjTable table = {.slots = (const u64 *)d_table, .buckets = buckets, .factor = factor, .line_hash = false};      // hjgpu_npj_build's: the reference's hash
     CHK(npj_probe_enqueue(ctx, {d_keys, d_vals, n}, table, out, stream, {.unique = ctx->tune.unique}));
-    ctx->last_algo = 0;
+    ctx->last_algo = ALGO_NPJ;
     return finish_blocking(ctx, result, out, stream);
 }
 
@@ -462,493 +461,11 @@ int hjgpu_column_sums(hjgpu_ctx *ctx, const uint32_t *d_keys, size_t n, uint32_t
     CHK(ensure(ctx, ctx->moves, 64));
     u64 *d = (u64 *)ctx->moves.p;
     // hjgpu_get_stats().ms_total afterwards = duration of this one streaming read
-    for (int i = 0; i < EV_COUNT; ++i) ctx->ev_valid[i] = false;
-    ctx->last_algo = 2;
-    record(ctx, EV_BEGIN, stream);
+    begin_span(ctx, ALGO_ONE_KERNEL, stream);
     CHK(hj_launch_column_sums(d_keys, n, fa, fb, d, stream));
     record(ctx, EV_GAPS, stream);
     HIPCHK(ctx, hipMemcpyAsync(sums, d, 3 * sizeof(u64), hipMemcpyDeviceToHost, stream));
     HIPCHK(ctx, hipStreamSynchronize(stream));
-    return HJGPU_OK;
-}
-
-// ---- compaction by bitmap ---------------------------------------------------------
-// hjgpu_compact_selected / _async (DESIGN.md section 5 "Compaction by bitmap").  Every refusal is decided here, from the arguments alone, before
-// anything is allocated or enqueued.
-static bool ranges_overlap(const void *p, size_t pbytes, const void *q, size_t qbytes)
-{
-    const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
-    return pbytes && qbytes && a < b + qbytes && b < a + pbytes;
-}
-
-static int check_compact(hjgpu_ctx *ctx, const uint32_t *bits, size_t n, uint32_t ncols, const uint32_t *const *in, uint32_t *const *out,
-                         const uint32_t *rows_out, size_t capacity, const uint64_t *count, bool device_count)
-{
-    if (!count) return fail(ctx, HJGPU_EINVAL, "null count pointer");
-    if (device_count && ((uintptr_t)count & 7)) return fail(ctx, HJGPU_EALIGN, "d_count must be 8-byte aligned");
-    if (ncols > HJGPU_COMPACT_MAX_COLS) return fail(ctx, HJGPU_EINVAL, "ncols must not exceed HJGPU_COMPACT_MAX_COLS (8)");
-    if (n == 0) return HJGPU_OK;                         // nothing is read, nothing but the count is written: anything else may be NULL
-    if (!bits) return fail(ctx, HJGPU_EINVAL, "null d_select_bits (a compaction of every row is a copy)");
-    if ((uintptr_t)bits & 15) return fail(ctx, HJGPU_EALIGN, "d_select_bits must be 16-byte aligned");
-    if (ncols && (!in || !out)) return fail(ctx, HJGPU_EINVAL, "null column array");
-    for (uint32_t c = 0; c < ncols; ++c) {
-        if (!in[c] || !out[c]) return fail(ctx, HJGPU_EINVAL, "null column pointer");
-        if (((uintptr_t)in[c] & 15) || ((uintptr_t)out[c] & 15)) return fail(ctx, HJGPU_EALIGN, "input and output columns must be 16-byte aligned");
-    }
-    if ((uintptr_t)rows_out & 15) return fail(ctx, HJGPU_EALIGN, "d_rows_out must be 16-byte aligned");
-    if (rows_out && n > 0xFFFFFFFFull) return fail(ctx, HJGPU_EINVAL, "d_rows_out holds 32-bit row numbers: n must not exceed 0xFFFFFFFF");
-    // not in place: no output may share a byte with the mask, an input column or another output
-    const void *outs[HJGPU_COMPACT_MAX_COLS + 1];
-    uint32_t nouts = 0;
-    for (uint32_t c = 0; c < ncols; ++c) outs[nouts++] = out[c];
-    if (rows_out) outs[nouts++] = rows_out;
-    const size_t obytes = capacity * sizeof(uint32_t), mbytes = (n + 31) / 32 * sizeof(uint32_t);
-    for (uint32_t o = 0; o < nouts; ++o) {
-        if (ranges_overlap(outs[o], obytes, bits, mbytes)) return fail(ctx, HJGPU_EINVAL, "an output overlaps d_select_bits (the compaction is not in place)");
-        for (uint32_t c = 0; c < ncols; ++c)
-            if (ranges_overlap(outs[o], obytes, in[c], n * sizeof(uint32_t)))
-                return fail(ctx, HJGPU_EINVAL, "an output overlaps an input column (the compaction is not in place)");
-        for (uint32_t q = 0; q < o; ++q)
-            if (ranges_overlap(outs[o], obytes, outs[q], obytes)) return fail(ctx, HJGPU_EINVAL, "an output overlaps another output");
-    }
-    return HJGPU_OK;
-}
-
-// the two launches (three beyond HJ_COMPACT_LAUNCH_COLS columns) behind the checks; d_count in device memory
-static int compact_enqueue(hjgpu_ctx *ctx, const uint32_t *bits, size_t n, uint32_t ncols, const uint32_t *const *in, uint32_t *const *out,
-                           uint32_t *rows_out, size_t capacity, u64 *counts, u64 *d_count, hipStream_t stream)
-{
-    const hj_compact::Layout lay = hj_compact::layout(n, hj_compact::ranges_of(ctx->cus));
-    if (n == 0) { ncols = 0; rows_out = nullptr; }
-    // hjgpu_get_stats afterwards: ms_histogram = the counting launch, ms_join = the compaction, ms_total = both
-    for (int i = 0; i < EV_COUNT; ++i) ctx->ev_valid[i] = false;
-    ctx->last_algo = 3;
-    record(ctx, EV_BEGIN, stream);
-    CHK(hj_launch_compact_count(bits, lay, counts, stream));
-    record(ctx, EV_S_HIST, stream);
-    if (ncols == 0 && !rows_out) CHK(hj_launch_compact_total(counts, lay.ranges, d_count, stream));
-    for (uint32_t c0 = 0; c0 < ncols || (c0 == 0 && rows_out); c0 += HJ_COMPACT_LAUNCH_COLS) {
-        CompactArgs a{};
-        a.select_bits = bits; a.lay = lay; a.counts = counts; a.capacity = capacity;
-        a.d_count = c0 == 0 ? d_count : nullptr;
-        a.rows_out = c0 == 0 ? rows_out : nullptr;
-        const uint32_t k = std::min<uint32_t>(ncols - c0, HJ_COMPACT_LAUNCH_COLS);
-        for (uint32_t c = 0; c < k; ++c) { a.in[c] = in[c0 + c]; a.out[c] = out[c0 + c]; }
-        CHK(hj_launch_compact(a, k, stream));
-    }
-    record(ctx, EV_JOIN, stream);
-    record(ctx, EV_GAPS, stream);
-    return HJGPU_OK;
-}
-
-// the context's constant-size workspace of the compaction: the ranges' counts, and the blocking form's count behind them
-static int compact_workspace(hjgpu_ctx *ctx, u64 **counts)
-{
-    CHK(ensure(ctx, ctx->compact, ((size_t)hj_compact::MAX_RANGES + 1) * sizeof(u64)));
-    *counts = reinterpret_cast<u64 *>(ctx->compact.p);
-    return HJGPU_OK;
-}
-
-int hjgpu_compact_selected_async(hjgpu_ctx *ctx, const uint32_t *d_select_bits, size_t n, uint32_t ncols, const uint32_t *const *d_cols_in,
-                                 uint32_t *const *d_cols_out, uint32_t *d_rows_out, size_t capacity, uint64_t *d_count, void *stream_)
-{
-    if (!ctx) return HJGPU_EINVAL;
-    CHK(check_compact(ctx, d_select_bits, n, ncols, d_cols_in, d_cols_out, d_rows_out, capacity, d_count, true));
-    hipStream_t stream = (hipStream_t)stream_;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    CHK(refuse_capture(ctx, stream));
-    u64 *counts = nullptr;
-    CHK(compact_workspace(ctx, &counts));
-    return compact_enqueue(ctx, d_select_bits, n, ncols, d_cols_in, d_cols_out, d_rows_out, capacity, counts, reinterpret_cast<u64 *>(d_count), stream);
-}
-
-int hjgpu_compact_selected(hjgpu_ctx *ctx, const uint32_t *d_select_bits, size_t n, uint32_t ncols, const uint32_t *const *d_cols_in,
-                           uint32_t *const *d_cols_out, uint32_t *d_rows_out, size_t capacity, uint64_t *count, void *stream_)
-{
-    if (!ctx) return HJGPU_EINVAL;
-    CHK(check_compact(ctx, d_select_bits, n, ncols, d_cols_in, d_cols_out, d_rows_out, capacity, count, false));
-    hipStream_t stream = (hipStream_t)stream_;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    CHK(refuse_capture(ctx, stream));
-    u64 *counts = nullptr;
-    CHK(compact_workspace(ctx, &counts));
-    u64 *d_count = counts + hj_compact::MAX_RANGES;
-    CHK(compact_enqueue(ctx, d_select_bits, n, ncols, d_cols_in, d_cols_out, d_rows_out, capacity, counts, d_count, stream));
-    u64 got = 0;
-    HIPCHK(ctx, hipMemcpyAsync(&got, d_count, sizeof(got), hipMemcpyDeviceToHost, stream));
-    HIPCHK(ctx, hipStreamSynchronize(stream));
-    *count = got;
-    if (n && (ncols || d_rows_out) && got > capacity)
-        return fail(ctx, HJGPU_EOVERFLOW, "hjgpu_compact_selected: more selected rows than capacity (*count holds their number, the first capacity rows of every output are valid)");
-    return HJGPU_OK;
-}
-
-// ---- grouped aggregation ----------------------------------------------------------
-// hjgpu_group_sum / _async (DESIGN.md section 5 "Grouped aggregation").  Every refusal is decided here, from the arguments alone, before
-// anything is allocated or enqueued.
-struct GroupCall {
-    const uint32_t *bits;
-    size_t n;
-    uint32_t nkeys, nvals;
-    const uint32_t *const *keys_in, *const *vals_in;
-    uint32_t *const *keys_out;
-    uint64_t *counts_out;
-    uint64_t *const *sums_out;
-    size_t capacity;
-};
-
-static int check_group(hjgpu_ctx *ctx, const GroupCall &g, const uint64_t *ngroups, bool device_count)
-{
-    if (!ngroups) return fail(ctx, HJGPU_EINVAL, "null group count pointer");
-    if (device_count && ((uintptr_t)ngroups & 7)) return fail(ctx, HJGPU_EALIGN, "d_ngroups must be 8-byte aligned");
-    if (g.nkeys == 0 || g.nkeys > HJGPU_GROUP_MAX_KEYS) return fail(ctx, HJGPU_EINVAL, "nkeys must be 1 to HJGPU_GROUP_MAX_KEYS (2)");
-    if (g.nvals > HJGPU_GROUP_MAX_VALS) return fail(ctx, HJGPU_EINVAL, "nvals must not exceed HJGPU_GROUP_MAX_VALS (4)");
-    if (hj_group::merge_slots(g.capacity) == 0) return fail(ctx, HJGPU_EINVAL, "capacity must not exceed 2^40 groups");
-    if (g.n == 0) return HJGPU_OK;                       // nothing is read, nothing but the count is written: anything else may be NULL
-    if ((uintptr_t)g.bits & 15) return fail(ctx, HJGPU_EALIGN, "d_select_bits must be 16-byte aligned");
-    if (!g.keys_in || !g.keys_out || (g.nvals && (!g.vals_in || !g.sums_out))) return fail(ctx, HJGPU_EINVAL, "null column array");
-    for (uint32_t c = 0; c < g.nkeys; ++c) {
-        if (!g.keys_in[c] || !g.keys_out[c]) return fail(ctx, HJGPU_EINVAL, "null key column pointer");
-        if (((uintptr_t)g.keys_in[c] | (uintptr_t)g.keys_out[c]) & 15) return fail(ctx, HJGPU_EALIGN, "key columns must be 16-byte aligned");
-    }
-    for (uint32_t c = 0; c < g.nvals; ++c) {
-        if (!g.vals_in[c] || !g.sums_out[c]) return fail(ctx, HJGPU_EINVAL, "null measure column pointer");
-        if (((uintptr_t)g.vals_in[c] | (uintptr_t)g.sums_out[c]) & 15) return fail(ctx, HJGPU_EALIGN, "measure and sum columns must be 16-byte aligned");
-    }
-    if ((uintptr_t)g.counts_out & 15) return fail(ctx, HJGPU_EALIGN, "d_counts_out must be 16-byte aligned");
-    // no output may share a byte with the mask, an input column or another output (the device count word is an output)
-    struct Range { const void *p; size_t bytes; };
-    Range outs[HJGPU_GROUP_MAX_KEYS + HJGPU_GROUP_MAX_VALS + 2], ins[HJGPU_GROUP_MAX_KEYS + HJGPU_GROUP_MAX_VALS + 1];
-    uint32_t nouts = 0, nins = 0;
-    for (uint32_t c = 0; c < g.nkeys; ++c) { outs[nouts++] = {g.keys_out[c], g.capacity * sizeof(uint32_t)}; ins[nins++] = {g.keys_in[c], g.n * sizeof(uint32_t)}; }
-    for (uint32_t c = 0; c < g.nvals; ++c) { outs[nouts++] = {g.sums_out[c], g.capacity * sizeof(uint64_t)}; ins[nins++] = {g.vals_in[c], g.n * sizeof(uint32_t)}; }
-    if (g.counts_out) outs[nouts++] = {g.counts_out, g.capacity * sizeof(uint64_t)};
-    if (device_count) outs[nouts++] = {ngroups, sizeof(uint64_t)};
-    if (g.bits) ins[nins++] = {g.bits, (g.n + 31) / 32 * sizeof(uint32_t)};
-    for (uint32_t o = 0; o < nouts; ++o) {
-        for (uint32_t i = 0; i < nins; ++i)
-            if (ranges_overlap(outs[o].p, outs[o].bytes, ins[i].p, ins[i].bytes))
-                return fail(ctx, HJGPU_EINVAL, i + 1 == nins && g.bits ? "an output overlaps d_select_bits" : "an output overlaps an input column");
-        for (uint32_t q = 0; q < o; ++q)
-            if (ranges_overlap(outs[o].p, outs[o].bytes, outs[q].p, outs[q].bytes)) return fail(ctx, HJGPU_EINVAL, "an output overlaps another output");
-    }
-    return HJGPU_OK;
-}
-
-// the three enqueues behind the checks: the clears (the count word; for n > 0 the overflow word and the merge table), the aggregation, the
-// emit.  hjgpu_get_stats afterwards: ms_histogram = the clears, ms_join = the aggregation, ms_close_gaps = the emit, ms_total = all of them
-static int group_enqueue(hjgpu_ctx *ctx, const GroupCall &g, u64 *d_ngroups, hipStream_t stream)
-{
-    const u64 slots = hj_group::merge_slots(g.capacity);
-    char *ws = reinterpret_cast<char *>(ctx->group.p);
-    for (int i = 0; i < EV_COUNT; ++i) ctx->ev_valid[i] = false;
-    ctx->last_algo = 4;
-    record(ctx, EV_BEGIN, stream);
-    HIPCHK(ctx, hj_zero_async(d_ngroups, sizeof(u64), stream));
-    if (g.n) HIPCHK(ctx, hj_zero_async(ws + sizeof(u64), (size_t)(hj_group::workspace_bytes(slots) - sizeof(u64)), stream));
-    record(ctx, EV_S_HIST, stream);
-    if (g.n) {
-        GroupArgs a{};
-        a.select_bits = g.bits; a.n = g.n; a.nkeys = g.nkeys; a.nvals = g.nvals;
-        for (uint32_t c = 0; c < g.nkeys; ++c) a.keys[c] = g.keys_in[c];
-        for (uint32_t c = 0; c < g.nvals; ++c) a.vals[c] = g.vals_in[c];
-        a.merge = reinterpret_cast<hj_group::Slot *>(ws + hj_group::WORKSPACE_HEAD);
-        a.merge_mask = slots - 1;
-        a.overflow = reinterpret_cast<uint32_t *>(ws + sizeof(u64));
-        CHK(hj_launch_group_sum(a, ctx->cus, stream));
-    }
-    record(ctx, EV_JOIN, stream);
-    if (g.n) {
-        GroupEmitArgs e{};
-        e.merge = reinterpret_cast<const hj_group::Slot *>(ws + hj_group::WORKSPACE_HEAD);
-        e.slots = slots; e.nkeys = g.nkeys; e.nvals = g.nvals; e.capacity = g.capacity; e.counts_out = reinterpret_cast<u64 *>(g.counts_out);
-        for (uint32_t c = 0; c < g.nkeys; ++c) e.keys_out[c] = g.keys_out[c];
-        for (uint32_t c = 0; c < g.nvals; ++c) e.sums_out[c] = reinterpret_cast<u64 *>(g.sums_out[c]);
-        e.d_ngroups = d_ngroups;
-        CHK(hj_launch_group_emit(e, ctx->cus, stream));
-    }
-    record(ctx, EV_GAPS, stream);
-    return HJGPU_OK;
-}
-
-// the context's merge table, sized from the capacity: it grows the first time a capacity is seen (hjgpu_stats.ms_reserve)
-static int group_workspace(hjgpu_ctx *ctx, size_t capacity)
-{
-    ReserveClock clock(ctx);
-    return ensure(ctx, ctx->group, (size_t)hj_group::workspace_bytes(hj_group::merge_slots(capacity)));
-}
-
-int hjgpu_group_sum_async(hjgpu_ctx *ctx, const uint32_t *d_select_bits, size_t n, uint32_t nkeys, const uint32_t *const *d_keys_in,
-                          uint32_t nvals, const uint32_t *const *d_vals_in, uint32_t *const *d_keys_out, uint64_t *d_counts_out,
-                          uint64_t *const *d_sums_out, size_t capacity, uint64_t *d_ngroups, void *stream_)
-{
-    if (!ctx) return HJGPU_EINVAL;
-    const GroupCall g{d_select_bits, n, nkeys, nvals, d_keys_in, d_vals_in, d_keys_out, d_counts_out, d_sums_out, capacity};
-    CHK(check_group(ctx, g, d_ngroups, true));
-    hipStream_t stream = (hipStream_t)stream_;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    CHK(refuse_capture(ctx, stream));
-    CHK(group_workspace(ctx, capacity));
-    return group_enqueue(ctx, g, reinterpret_cast<u64 *>(d_ngroups), stream);
-}
-
-int hjgpu_group_sum(hjgpu_ctx *ctx, const uint32_t *d_select_bits, size_t n, uint32_t nkeys, const uint32_t *const *d_keys_in,
-                    uint32_t nvals, const uint32_t *const *d_vals_in, uint32_t *const *d_keys_out, uint64_t *d_counts_out,
-                    uint64_t *const *d_sums_out, size_t capacity, uint64_t *ngroups, void *stream_)
-{
-    if (!ctx) return HJGPU_EINVAL;
-    const GroupCall g{d_select_bits, n, nkeys, nvals, d_keys_in, d_vals_in, d_keys_out, d_counts_out, d_sums_out, capacity};
-    CHK(check_group(ctx, g, ngroups, false));
-    hipStream_t stream = (hipStream_t)stream_;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    CHK(refuse_capture(ctx, stream));
-    CHK(group_workspace(ctx, capacity));
-    u64 *d_ngroups = reinterpret_cast<u64 *>(ctx->group.p);           // the workspace's first word
-    CHK(group_enqueue(ctx, g, d_ngroups, stream));
-    u64 got = 0;
-    HIPCHK(ctx, hipMemcpyAsync(&got, d_ngroups, sizeof(got), hipMemcpyDeviceToHost, stream));
-    HIPCHK(ctx, hipStreamSynchronize(stream));
-    *ngroups = got;
-    if (got > capacity)
-        return fail(ctx, HJGPU_EOVERFLOW, "hjgpu_group_sum: more groups than capacity (*ngroups holds a lower bound of their number that exceeds capacity; the outputs are unspecified)");
-    return HJGPU_OK;
-}
-
-// ---- filter -----------------------------------------------------------------------
-// hjgpu_filter_selected / _async (DESIGN.md section 5 "Filter").  Every refusal is decided here, from the arguments alone, before anything is
-// allocated or enqueued.
-struct FilterCall {
-    const uint32_t *bits;
-    size_t n;
-    uint32_t npreds;
-    const uint32_t *const *cols;
-    const hjgpu_predicate *preds;
-    uint32_t *bits_out;
-};
-
-static int check_filter(hjgpu_ctx *ctx, const FilterCall &f, const uint64_t *count, bool device_count)
-{
-    if (device_count && ((uintptr_t)count & 7)) return fail(ctx, HJGPU_EALIGN, "d_count must be 8-byte aligned");
-    if (f.npreds == 0 || f.npreds > HJGPU_FILTER_MAX_PREDS) return fail(ctx, HJGPU_EINVAL, "npreds must be 1 to HJGPU_FILTER_MAX_PREDS (4)");
-    if (f.n == 0) return HJGPU_OK;                       // nothing is read, nothing but the count is written: anything else may be NULL
-    if (!f.bits_out && !count) return fail(ctx, HJGPU_EINVAL, "d_bits_out and the count are both null: nothing to compute");
-    if ((uintptr_t)f.bits & 15) return fail(ctx, HJGPU_EALIGN, "d_select_bits must be 16-byte aligned");
-    if ((uintptr_t)f.bits_out & 15) return fail(ctx, HJGPU_EALIGN, "d_bits_out must be 16-byte aligned");
-    if (!f.cols || !f.preds) return fail(ctx, HJGPU_EINVAL, "null column or predicate array");
-    for (uint32_t p = 0; p < f.npreds; ++p) {
-        if (!f.cols[p]) return fail(ctx, HJGPU_EINVAL, "null column pointer");
-        if ((uintptr_t)f.cols[p] & 15) return fail(ctx, HJGPU_EALIGN, "columns must be 16-byte aligned");
-        if (f.preds[p].flags & ~(HJGPU_PRED_NOT | HJGPU_PRED_SIGNED)) return fail(ctx, HJGPU_EINVAL, "unknown predicate flag (HJGPU_PRED_NOT and HJGPU_PRED_SIGNED are defined)");
-        if (f.preds[p].reserved) return fail(ctx, HJGPU_EINVAL, "a predicate's reserved word must be 0");
-    }
-    // in place: d_bits_out may be the very pointer d_select_bits - the kernel reads a word of the mask in the wave that stores it, before
-    // it stores it -; two bitmaps that overlap in any other way would be read after they were written
-    const size_t mbytes = (f.n + 31) / 32 * sizeof(uint32_t), cbytes = f.n * sizeof(uint32_t);
-    if (f.bits && f.bits_out && f.bits != f.bits_out && ranges_overlap(f.bits_out, mbytes, f.bits, mbytes))
-        return fail(ctx, HJGPU_EINVAL, "d_bits_out overlaps d_select_bits: it may be the very pointer d_select_bits (in place), any other overlap of the two bitmaps is refused");
-    // no output may share a byte with a column or with the other output; the device count word none with the mask either
-    for (uint32_t p = 0; p < f.npreds; ++p) {
-        if (ranges_overlap(f.bits_out, f.bits_out ? mbytes : 0, f.cols[p], cbytes)) return fail(ctx, HJGPU_EINVAL, "d_bits_out overlaps a column");
-        if (device_count && ranges_overlap(count, count ? sizeof(uint64_t) : 0, f.cols[p], cbytes)) return fail(ctx, HJGPU_EINVAL, "d_count overlaps a column");
-    }
-    if (device_count && count) {
-        if (ranges_overlap(count, sizeof(uint64_t), f.bits_out, f.bits_out ? mbytes : 0)) return fail(ctx, HJGPU_EINVAL, "d_count overlaps d_bits_out");
-        if (ranges_overlap(count, sizeof(uint64_t), f.bits, f.bits ? mbytes : 0)) return fail(ctx, HJGPU_EINVAL, "d_count overlaps d_select_bits");
-    }
-    return HJGPU_OK;
-}
-
-// the context's count word (the blocking form's; made by the first call of either form)
-static int filter_workspace(hjgpu_ctx *ctx, u64 **word)
-{
-    CHK(ensure(ctx, ctx->filter, sizeof(u64)));
-    *word = reinterpret_cast<u64 *>(ctx->filter.p);
-    return HJGPU_OK;
-}
-
-// the two enqueues behind the checks: the clear of the count word (d_count NULL: none), the kernel (n == 0: none).  hjgpu_get_stats
-// afterwards: ms_histogram = the clear, ms_join = the kernel, ms_total = both
-static int filter_enqueue(hjgpu_ctx *ctx, const FilterCall &f, u64 *d_count, hipStream_t stream)
-{
-    for (int i = 0; i < EV_COUNT; ++i) ctx->ev_valid[i] = false;
-    ctx->last_algo = 5;
-    record(ctx, EV_BEGIN, stream);
-    if (d_count) HIPCHK(ctx, hj_zero_async(d_count, sizeof(u64), stream));
-    record(ctx, EV_S_HIST, stream);
-    if (f.n) {
-        FilterArgs a{};
-        a.select_bits = f.bits; a.bits_out = f.bits_out; a.count = d_count; a.n = f.n;
-        for (uint32_t p = 0; p < f.npreds; ++p) {
-            a.cols[p] = f.cols[p];
-            a.preds[p] = hj_filter::normalise(f.preds[p].lo, f.preds[p].hi, f.preds[p].flags);
-        }
-        CHK(hj_launch_filter(a, f.npreds, ctx->cus, stream));
-    }
-    record(ctx, EV_JOIN, stream);
-    record(ctx, EV_GAPS, stream);
-    return HJGPU_OK;
-}
-
-int hjgpu_filter_selected_async(hjgpu_ctx *ctx, const uint32_t *d_select_bits, size_t n, uint32_t npreds, const uint32_t *const *d_cols,
-                                const hjgpu_predicate *preds, uint32_t *d_bits_out, uint64_t *d_count, void *stream_)
-{
-    if (!ctx) return HJGPU_EINVAL;
-    const FilterCall f{d_select_bits, n, npreds, d_cols, preds, d_bits_out};
-    CHK(check_filter(ctx, f, d_count, true));
-    hipStream_t stream = (hipStream_t)stream_;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    CHK(refuse_capture(ctx, stream));
-    u64 *word = nullptr;
-    CHK(filter_workspace(ctx, &word));
-    return filter_enqueue(ctx, f, reinterpret_cast<u64 *>(d_count), stream);
-}
-
-int hjgpu_filter_selected(hjgpu_ctx *ctx, const uint32_t *d_select_bits, size_t n, uint32_t npreds, const uint32_t *const *d_cols,
-                          const hjgpu_predicate *preds, uint32_t *d_bits_out, uint64_t *count, void *stream_)
-{
-    if (!ctx) return HJGPU_EINVAL;
-    const FilterCall f{d_select_bits, n, npreds, d_cols, preds, d_bits_out};
-    CHK(check_filter(ctx, f, count, false));
-    hipStream_t stream = (hipStream_t)stream_;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    CHK(refuse_capture(ctx, stream));
-    u64 *word = nullptr;
-    CHK(filter_workspace(ctx, &word));
-    CHK(filter_enqueue(ctx, f, count ? word : nullptr, stream));
-    u64 got = 0;
-    if (count) HIPCHK(ctx, hipMemcpyAsync(&got, word, sizeof(got), hipMemcpyDeviceToHost, stream));
-    HIPCHK(ctx, hipStreamSynchronize(stream));
-    if (count) *count = got;
-    return HJGPU_OK;
-}
-
-// ---- gather by row number -----------------------------------------------------------
-// hjgpu_gather_selected / _async (DESIGN.md section 5 "Gather by row number").  Every refusal is decided here, from the arguments alone, before
-// anything is allocated or enqueued.
-struct GatherCall {
-    const uint32_t *bits;
-    const uint32_t *idx;
-    size_t n;
-    uint32_t ncols;
-    const uint32_t *const *src;
-    size_t src_rows;
-    uint32_t *const *out;
-    uint32_t *bits_out;
-};
-
-static int check_gather(hjgpu_ctx *ctx, const GatherCall &g, const uint64_t *d_counts)
-{
-    if ((uintptr_t)d_counts & 15) return fail(ctx, HJGPU_EALIGN, "d_counts must be 16-byte aligned");
-    if (g.ncols == 0 || g.ncols > HJGPU_GATHER_MAX_COLS) return fail(ctx, HJGPU_EINVAL, "ncols must be 1 to HJGPU_GATHER_MAX_COLS (4)");
-    if (g.src_rows > 0xFFFFFFFFull) return fail(ctx, HJGPU_EINVAL, "src_rows must not exceed 0xFFFFFFFF: an index is a uint32 and HJGPU_NULL_VAL is never a legal one");
-    if (g.n == 0) return HJGPU_OK;                       // nothing is read, nothing but the counts is written: anything else may be NULL
-    if (!g.idx) return fail(ctx, HJGPU_EINVAL, "null d_idx");
-    if ((uintptr_t)g.bits & 15) return fail(ctx, HJGPU_EALIGN, "d_select_bits must be 16-byte aligned");
-    if ((uintptr_t)g.idx & 15) return fail(ctx, HJGPU_EALIGN, "d_idx must be 16-byte aligned");
-    if ((uintptr_t)g.bits_out & 15) return fail(ctx, HJGPU_EALIGN, "d_bits_out must be 16-byte aligned");
-    if (!g.src || !g.out) return fail(ctx, HJGPU_EINVAL, "null column array");
-    for (uint32_t c = 0; c < g.ncols; ++c) {
-        if (!g.src[c] || !g.out[c]) return fail(ctx, HJGPU_EINVAL, "null column pointer");
-        if ((uintptr_t)g.src[c] & 15) return fail(ctx, HJGPU_EALIGN, "source columns must be 16-byte aligned");
-        if ((uintptr_t)g.out[c] & 15) return fail(ctx, HJGPU_EALIGN, "output columns must be 16-byte aligned");
-    }
-    const size_t mbytes = (g.n + 31) / 32 * sizeof(uint32_t), cbytes = g.n * sizeof(uint32_t), sbytes = g.src_rows * sizeof(uint32_t);
-    // in place: an output column may be the very pointer d_idx - a lane reads its index vector before it stores the same vector - and, being
-    // an output, only one can; d_bits_out may be the very pointer d_select_bits (hj_lookup.hpp's IN-PLACE RULE).  Every other shared byte
-    // between an output and anything else would be read after it was written, or written twice
-    for (uint32_t c = 0; c < g.ncols; ++c) {
-        if (g.out[c] != g.idx && ranges_overlap(g.out[c], cbytes, g.idx, cbytes))
-            return fail(ctx, HJGPU_EINVAL, "an output column overlaps d_idx: it may be the very pointer d_idx (in place), any other overlap is refused");
-        for (uint32_t q = 0; q < c; ++q)
-            if (ranges_overlap(g.out[c], cbytes, g.out[q], cbytes)) return fail(ctx, HJGPU_EINVAL, "an output column overlaps another output column");
-        for (uint32_t q = 0; q < g.ncols; ++q)
-            if (ranges_overlap(g.out[c], cbytes, g.src[q], sbytes)) return fail(ctx, HJGPU_EINVAL, "an output column overlaps a source column");
-        if (ranges_overlap(g.out[c], cbytes, g.bits, g.bits ? mbytes : 0)) return fail(ctx, HJGPU_EINVAL, "an output column overlaps d_select_bits");
-    }
-    if (g.bits_out) {
-        if (g.bits && g.bits != g.bits_out && ranges_overlap(g.bits_out, mbytes, g.bits, mbytes))
-            return fail(ctx, HJGPU_EINVAL, "d_bits_out overlaps d_select_bits: it may be the very pointer d_select_bits (in place), any other overlap of the two bitmaps is refused");
-        if (ranges_overlap(g.bits_out, mbytes, g.idx, cbytes)) return fail(ctx, HJGPU_EINVAL, "d_bits_out overlaps d_idx");
-        for (uint32_t c = 0; c < g.ncols; ++c) {
-            if (ranges_overlap(g.bits_out, mbytes, g.out[c], cbytes)) return fail(ctx, HJGPU_EINVAL, "d_bits_out overlaps an output column");
-            if (ranges_overlap(g.bits_out, mbytes, g.src[c], sbytes)) return fail(ctx, HJGPU_EINVAL, "d_bits_out overlaps a source column");
-        }
-    }
-    if (d_counts) {
-        const size_t wbytes = 2 * sizeof(uint64_t);
-        if (ranges_overlap(d_counts, wbytes, g.bits, g.bits ? mbytes : 0)) return fail(ctx, HJGPU_EINVAL, "d_counts overlaps d_select_bits");
-        if (ranges_overlap(d_counts, wbytes, g.idx, cbytes)) return fail(ctx, HJGPU_EINVAL, "d_counts overlaps d_idx");
-        if (ranges_overlap(d_counts, wbytes, g.bits_out, g.bits_out ? mbytes : 0)) return fail(ctx, HJGPU_EINVAL, "d_counts overlaps d_bits_out");
-        for (uint32_t c = 0; c < g.ncols; ++c) {
-            if (ranges_overlap(d_counts, wbytes, g.out[c], cbytes)) return fail(ctx, HJGPU_EINVAL, "d_counts overlaps an output column");
-            if (ranges_overlap(d_counts, wbytes, g.src[c], sbytes)) return fail(ctx, HJGPU_EINVAL, "d_counts overlaps a source column");
-        }
-    }
-    return HJGPU_OK;
-}
-
-// the context's two count words (the blocking form's; made by the first call of either form)
-static int gather_workspace(hjgpu_ctx *ctx, u64 **words)
-{
-    CHK(ensure(ctx, ctx->gather, 2 * sizeof(u64)));
-    *words = reinterpret_cast<u64 *>(ctx->gather.p);
-    return HJGPU_OK;
-}
-
-// the two enqueues behind the checks: the clear of the count words (d_counts NULL: none), the kernel (n == 0: none).  hjgpu_get_stats
-// afterwards: ms_histogram = the clear, ms_join = the kernel, ms_total = both
-static int gather_enqueue(hjgpu_ctx *ctx, const GatherCall &g, u64 *d_counts, hipStream_t stream)
-{
-    for (int i = 0; i < EV_COUNT; ++i) ctx->ev_valid[i] = false;
-    ctx->last_algo = 6;
-    record(ctx, EV_BEGIN, stream);
-    if (d_counts) HIPCHK(ctx, hj_zero_async(d_counts, 2 * sizeof(u64), stream));
-    record(ctx, EV_S_HIST, stream);
-    if (g.n) {
-        GatherArgs a{};
-        a.select_bits = g.bits; a.idx = g.idx; a.bits_out = g.bits_out; a.counts = d_counts; a.n = g.n; a.src_rows = (uint32_t)g.src_rows;
-        for (uint32_t c = 0; c < g.ncols; ++c) { a.src[c] = g.src[c]; a.out[c] = g.out[c]; }
-        CHK(hj_launch_gather(a, g.ncols, ctx->cus, stream));
-    }
-    record(ctx, EV_JOIN, stream);
-    record(ctx, EV_GAPS, stream);
-    return HJGPU_OK;
-}
-
-int hjgpu_gather_selected_async(hjgpu_ctx *ctx, const uint32_t *d_select_bits, const uint32_t *d_idx, size_t n, uint32_t ncols,
-                                const uint32_t *const *d_src_cols, size_t src_rows, uint32_t *const *d_cols_out, uint32_t *d_bits_out,
-                                uint64_t *d_counts, void *stream_)
-{
-    if (!ctx) return HJGPU_EINVAL;
-    const GatherCall g{d_select_bits, d_idx, n, ncols, d_src_cols, src_rows, d_cols_out, d_bits_out};
-    CHK(check_gather(ctx, g, d_counts));
-    hipStream_t stream = (hipStream_t)stream_;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    CHK(refuse_capture(ctx, stream));
-    u64 *words = nullptr;
-    CHK(gather_workspace(ctx, &words));
-    return gather_enqueue(ctx, g, reinterpret_cast<u64 *>(d_counts), stream);
-}
-
-int hjgpu_gather_selected(hjgpu_ctx *ctx, const uint32_t *d_select_bits, const uint32_t *d_idx, size_t n, uint32_t ncols,
-                          const uint32_t *const *d_src_cols, size_t src_rows, uint32_t *const *d_cols_out, uint32_t *d_bits_out,
-                          uint64_t counts[2], void *stream_)
-{
-    if (!ctx) return HJGPU_EINVAL;
-    const GatherCall g{d_select_bits, d_idx, n, ncols, d_src_cols, src_rows, d_cols_out, d_bits_out};
-    CHK(check_gather(ctx, g, nullptr));
-    hipStream_t stream = (hipStream_t)stream_;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    CHK(refuse_capture(ctx, stream));
-    u64 *words = nullptr;
-    CHK(gather_workspace(ctx, &words));
-    CHK(gather_enqueue(ctx, g, words, stream));          // (the context's words also when counts is NULL: HJGPU_ERANGE is read from them)
-    u64 got[2] = {0, 0};
-    HIPCHK(ctx, hipMemcpyAsync(got, words, sizeof(got), hipMemcpyDeviceToHost, stream));
-    HIPCHK(ctx, hipStreamSynchronize(stream));
-    if (counts) { counts[0] = got[0]; counts[1] = got[1]; }
-    if (got[1])
-        return fail(ctx, HJGPU_ERANGE, "hjgpu_gather_selected: selected rows hold an index that is neither below src_rows nor HJGPU_NULL_VAL (counts[1] holds their number; they were written as NULL rows, every output is complete)");
     return HJGPU_OK;
 }
 
@@ -958,13 +475,11 @@ int hjgpu_stream_read_ms(hjgpu_ctx *ctx, const void *d_ptr, size_t bytes, float 
     hipStream_t stream = (hipStream_t)stream_;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     CHK(ensure(ctx, ctx->moves, 64));
-    for (int i = 0; i < EV_COUNT; ++i) ctx->ev_valid[i] = false;
-    record(ctx, EV_BEGIN, stream);
+    begin_span(ctx, ALGO_ONE_KERNEL, stream);
     CHK(hj_launch_stream_read(d_ptr, bytes, ctx->moves.p, ctx->cus, stream));
     record(ctx, EV_GAPS, stream);
     HIPCHK(ctx, hipEventSynchronize(ctx->ev[EV_GAPS]));
     HIPCHK(ctx, hipEventElapsedTime(ms, ctx->ev[EV_BEGIN], ctx->ev[EV_GAPS]));
-    ctx->last_algo = 2;
     return HJGPU_OK;
 }
 
@@ -974,13 +489,11 @@ int hjgpu_random_line_read_ms(hjgpu_ctx *ctx, const void *d_ptr, size_t bytes, s
     hipStream_t stream = (hipStream_t)stream_;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     CHK(ensure(ctx, ctx->moves, 64));
-    for (int i = 0; i < EV_COUNT; ++i) ctx->ev_valid[i] = false;
-    record(ctx, EV_BEGIN, stream);
+    begin_span(ctx, ALGO_ONE_KERNEL, stream);
     CHK(hj_launch_random_line_read(d_ptr, bytes, reads, ctx->moves.p, ctx->cus, stream));
     record(ctx, EV_GAPS, stream);
     HIPCHK(ctx, hipEventSynchronize(ctx->ev[EV_GAPS]));
     HIPCHK(ctx, hipEventElapsedTime(ms, ctx->ev[EV_BEGIN], ctx->ev[EV_GAPS]));
-    ctx->last_algo = 2;
     return HJGPU_OK;
 }
 
@@ -991,13 +504,11 @@ int hjgpu_random_cas_ms(hjgpu_ctx *ctx, void *d_ptr, size_t bytes, size_t ops, i
     HIPCHK(ctx, hipSetDevice(ctx->device));
     CHK(ensure(ctx, ctx->moves, 64));
     HIPCHK(ctx, hj_zero_async(d_ptr, bytes, stream));              // every bucket empty: outside the timed span
-    for (int i = 0; i < EV_COUNT; ++i) ctx->ev_valid[i] = false;
-    record(ctx, EV_BEGIN, stream);
+    begin_span(ctx, ALGO_ONE_KERNEL, stream);
     CHK(hj_launch_random_cas(d_ptr, bytes, ops, in_flight, load_first != 0, ctx->moves.p, ctx->cus, stream));
     record(ctx, EV_GAPS, stream);
     HIPCHK(ctx, hipEventSynchronize(ctx->ev[EV_GAPS]));
     HIPCHK(ctx, hipEventElapsedTime(ms, ctx->ev[EV_BEGIN], ctx->ev[EV_GAPS]));
-    ctx->last_algo = 2;
     return HJGPU_OK;
 }
 

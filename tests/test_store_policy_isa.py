@@ -21,7 +21,7 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "hash_join_codes_knl_amd", "csrc")
 SOURCES = ["partition_kernels.hip", "join_kernels.hip", "npj_kernels.hip", "gen_kernels.hip", "audit_kernels.hip",
-           "hjgpu_api.hip", "hjgpu_ops.hip", "hjgpu_host.hip", "hjgpu_multi.hip"]
+           "hjgpu_api.hip", "hjgpu_ops.hip", "hjgpu_colops.hip", "hjgpu_host.hip", "hjgpu_multi.hip"]
 STORE = re.compile(r"^(global|flat|buffer)_store_\w+")
 
 
