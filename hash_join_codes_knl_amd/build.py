@@ -30,7 +30,7 @@ def _hipcc():
 
 # the kernels AND the plan that launches them (fan-out defaults, grid geometry, placement, reserve_cus live in hjgpu_api.hip)
 KERNEL_HASH_FILES = ["partition_kernels.hip", "join_kernels.hip", "npj_kernels.hip", "hj_device.hpp",
-                     "hj_emit.hpp", "hj_lookup.hpp", "hj_internal.hpp", "scatter_layout.hpp", "hjgpu_ctx.hpp", "hjgpu_api.hip", "hjgpu_ops.hip",
+                     "hj_emit.hpp", "hj_lookup.hpp", "hj_internal.hpp", "scatter_layout.hpp", "build_beside_layout.hpp", "hjgpu_ctx.hpp", "hjgpu_api.hip", "hjgpu_ops.hip",
                      "hjgpu_colops.hip", "colop_checks.hpp"]
 
 

@@ -303,7 +303,7 @@ void record(hjgpu_ctx *ctx, int which, hipStream_t s)
             (void)hipEventRecord(ctx->ev_cur[which], s);
         return;
     }
-    if (which == EV_BEGIN) { ctx->stats_override = false; ctx->grp_ev_groups = 0; ctx->last_lookup = false; }
+    if (which == EV_BEGIN) { ctx->stats_override = false; ctx->grp_ev_groups = 0; ctx->last_lookup = false; ctx->last_beside = false; }
     ctx->ev_valid[which] = (hipEventRecord(ctx->ev[which], s) == hipSuccess);
 }
 
@@ -720,6 +720,9 @@ struct PhjRoad {
     bool merged;    // both relations are there from the start: their stages run side by side, ONE set of plan launches (a group: always)
     bool claim;     // merged, and the probe side is partitioned without its histogram (PhjPlan::claim_s)
     bool joins;     // the call runs a join: there are build rows, and probe rows or a mode that reports build rows alone
+    bool beside;    // claimed, both relations have rows, option "build_beside", not a solo join: the build side's chain runs on the context's side stream while
+                    // the probe side goes through its passes on the caller's (partition_beside), on split.build / split.probe CUs
+    hj_beside::Split split;
 };
 
 PhjRoad phj_road(const hjgpu_ctx *ctx, const PhjPlan &pl, const Rel &R, const Rel &S, const EnqueueOpts &o)
@@ -731,6 +734,10 @@ PhjRoad phj_road(const hjgpu_ctx *ctx, const PhjPlan &pl, const Rel &R, const Re
     w.merged = o.grp || (resident && !pl.batch_ranges && ctx->tune.merged_plan);
     w.claim = w.merged && !o.grp && pl.claim_s && !audited && pl.C == 1 && w.pad2;
     w.joins = R.rows && (S.rows || hj_mode_build_alone(pl.mode)) && o.stages != PHJ_BUILD_ONLY;
+    w.split = hj_beside::split(scatter_cus(ctx), ctx->build_cus, R.rows, S.rows);
+    // (a SOLO join - option "solo", PlainRows - writes K6's partial lines with plain stores on the caller's promise of one stream: it keeps it)
+    w.beside = w.claim && w.joins && ctx->build_beside && !ctx->rows_plain && w.split.overlap();
+    if (!w.beside) w.split = hj_beside::Split{0, scatter_cus(ctx)};
     return w;
 }
 
@@ -752,6 +759,10 @@ struct PhjRun {
     u64 *audit = nullptr;                // option "audit": this call's record (else NULL: no audit stage is enqueued)
     bool p_major = false;
     uint32_t batches_used = 0;
+    // where relation r's own stages (K4, K5b, K6) are enqueued and how many CUs their grids take: the caller's stream and the whole chip,
+    // except in partition_beside
+    hipStream_t on[2];
+    int hist_cus[2], k6_cus[2];
 
     PhjRun(hjgpu_ctx *c, const PhjPlan &p, const Rel &R, const Rel &S, const EnqueueOpts &opts, hipStream_t s)
         : ctx(c), pl(p), o(opts), road(phj_road(c, p, R, S, opts)), stream(s),
@@ -761,7 +772,8 @@ struct PhjRun {
           in_k{R.keys, S.keys}, in_v{R.vals, S.vals}, nn{R.rows, S.rows},
           t1{(uint32_t *)c->tmp[0].p, nullptr, (uint32_t *)c->tmp[2].p, nullptr},
           t2{(uint32_t *)c->tmp[4].p, nullptr, (uint32_t *)c->tmp[6].p, nullptr},
-          dyn{opts.grp ? opts.grp->desc : nullptr, opts.grp ? opts.grp->desc + 2 : nullptr} {}
+          dyn{opts.grp ? opts.grp->desc : nullptr, opts.grp ? opts.grp->desc + 2 : nullptr},
+          on{s, s}, hist_cus{c->cus, c->cus}, k6_cus{scatter_cus(c), scatter_cus(c)} {}
 
     bool pieces(int r) const { return o.pre && o.pre->tuples[r]; }
 
@@ -844,19 +856,20 @@ struct PhjRun {
     {
         if (!nn[r]) return HJGPU_OK;
         return hj_launch_hist2(in_k[r], geom[r], pl.f1, pl.F1, pl.f2, pl.F2, m.counts[r],
-                               m.range_counts[r], m.tickets + HJ_TICKET_K4 + HJ_MAX_CHUNKS * r, ctx->cus, stream, 0, dyn[r]);
+                               m.range_counts[r], m.tickets + HJ_TICKET_K4 + HJ_MAX_CHUNKS * r, hist_cus[r], on[r], 0, dyn[r]);
     }
     // K5 (+ the join's work items where the mask says so)
-    int plan(uint32_t mask)
+    int plan(uint32_t mask) { return plan(mask, stream); }
+    int plan(uint32_t mask, hipStream_t s)
     {
         pa.mask = mask;
-        return hj_launch_plan(pa, stream);
+        return hj_launch_plan(pa, s);
     }
     // K5b
     int range_bases(int r)
     {
         if (!nn[r]) return HJGPU_OK;
-        return hj_launch_range_base(m.range_counts[r], m.off1[r], m.range_base[r], pl.C, geom[r].ranges_per_chunk, pl.F1, stream);
+        return hj_launch_range_base(m.range_counts[r], m.off1[r], m.range_base[r], pl.C, geom[r].ranges_per_chunk, pl.F1, on[r]);
     }
     // K6 pass 1: caller's columns -> tmp[0..3]
     int pass1(int r)
@@ -868,7 +881,7 @@ struct PhjRun {
             sa.range_base = nullptr;
             sa.claim_cursors = m.claim1; sa.claim_cap = pl.cap1; sa.claim_overflow = &st->probe_overflow;
         }
-        return hj_launch_scatter(sa, ctx->tune, scatter_cus(ctx), stream);
+        return hj_launch_scatter(sa, ctx->tune, k6_cus[r], on[r]);
     }
     // K6 pass 2: packed tuples `in` -> tmp[4..7] - pass 1's output in tmp[0..3], the pieces of a pre-partitioned relation, or the buffer of
     // one batch of the probe side (batch >= 0)
@@ -888,7 +901,7 @@ struct PhjRun {
             sa.tile_prefix = m.claim_total; sa.nseg = 0; sa.seg_off = nullptr;
             sa.claim_overflow = &st->probe_overflow;
         }
-        return hj_launch_scatter(sa, ctx->tune, scatter_cus(ctx), stream);
+        return hj_launch_scatter(sa, ctx->tune, k6_cus[r], on[r]);
     }
 
     // The relation arrives pass-1-partitioned (the exchange-level partitioning of the multi-GPU CPRA was pass 1, cpra2.cpp:1757-1827): pass 2
@@ -1014,6 +1027,67 @@ struct PhjRun {
         return HJGPU_OK;
     }
 
+    // The merged, claimed road as a fork and a join inside the call (PhjRoad::beside): nothing the probe side does before its pass 2
+    // depends on the build side, and K6 does not need every CU, so the build side's whole chain runs on the context's side stream, on
+    // road.split.build CUs, while the probe side goes through its passes on the caller's stream on the others.
+    //   caller's stream:  (zeros) fork | pass 1 S, claimed-desc | wait "plan done" | pass 2 S | wait "R done" | (claimed-pieces, J)
+    //   side stream:      wait fork | K4 R | K5 (7u) | "plan done" | K5b R | pass 1 R | pass 2 R | "R done"
+    // Edges (PlanArgs / ScatterArgs): the zeros of begin() before everything (fork); K5 writes off2 / end2 / cur2 of BOTH relations and the
+    // join's work items - pass 2 of S reads the probe side's ("plan done"), the join all of it and R's final partitions ("R done").  Pass 1
+    // of S reads its claim cursors and its ticket (zeros) and nothing K5 writes; claimed-desc reads those cursors and writes S's tile
+    // descriptors and claim_total.  The words both chains touch while they run side by side are listed in DESIGN section 3.
+    // Whatever way this function is left once the fork is recorded, the caller's stream waits for the side stream (Joined).
+    int partition_beside()
+    {
+        if (!ctx->side) HIPCHK(ctx, hipStreamCreateWithFlags(&ctx->side, hipStreamNonBlocking));
+        for (hipEvent_t &e : ctx->beside_ev) if (!e) HIPCHK(ctx, hipEventCreate(&e));
+        hipEvent_t *ev = ctx->beside_ev;
+        const hipStream_t side = ctx->side;
+        on[0] = side; hist_cus[0] = k6_cus[0] = road.split.build; k6_cus[1] = road.split.probe;
+        HIPCHK(ctx, hipEventRecord(ev[hjgpu_ctx::BESIDE_FORK], stream));
+        HIPCHK(ctx, hipStreamWaitEvent(side, ev[hjgpu_ctx::BESIDE_FORK], 0));
+        struct Joined {
+            hipEvent_t done; hipStream_t side, main; bool armed = true;
+            // (should the event or the wait fail, the host waits for the side stream instead: never R-chain work unjoined)
+            hipError_t now()
+            {
+                armed = false;
+                hipError_t e = hipEventRecord(done, side);
+                if (e == hipSuccess) e = hipStreamWaitEvent(main, done, 0);
+                if (e != hipSuccess) (void)hipStreamSynchronize(side);
+                return e;
+            }
+            ~Joined() { if (armed) (void)now(); }       // an error's way out
+        } joined{ev[hjgpu_ctx::BESIDE_R_DONE], side, stream};
+        // the probe side's pass 1 first: it is the long one, and the device is idle until the first launch arrives
+        record(ctx, EV_S_HIST, stream);
+        record(ctx, EV_S_PLAN, stream);
+        CHK(pass1(1));
+        // the build side's chain
+        CHK(histogram(0));
+        record(ctx, EV_R_HIST, side);
+        CHK(plan(7u, side));
+        HIPCHK(ctx, hipEventRecord(ev[hjgpu_ctx::BESIDE_PLAN_DONE], side));
+        CHK(range_bases(0));
+        record(ctx, EV_R_PLAN, side);
+        CHK(pass1(0));
+        record(ctx, EV_R_SC1, side);
+        CHK(pass2(0, t1[0], -1));
+        record(ctx, EV_R_SC2, side);
+        // the rest of the probe side's
+        CHK(hj_launch_claimed_desc(m.claim1, pl.cap1, pl.F1, pl.F2, pa.tile2, m.tdesc[1], (uint32_t)m.tdesc_cap, m.claim_total,
+                                   &st->probe_overflow, stream));
+        record(ctx, EV_S_SC1, stream);
+        HIPCHK(ctx, hipStreamWaitEvent(stream, ev[hjgpu_ctx::BESIDE_PLAN_DONE], 0));
+        CHK(pass2(1, t1[2], -1));
+        record(ctx, EV_S_SC2, stream);
+        HIPCHK(ctx, joined.now());
+        record(ctx, EV_WAITED, stream);
+        ctx->last_beside = true;
+        ++ctx->beside_joins;
+        return HJGPU_OK;
+    }
+
     // K7+K8 over the final partitions.  Modes that mark build rows: the bitmap's clear in front and a tail kernel behind (without probe
     // rows the tail alone; right semi- / anti-joins: launches that only mark, then hj_launch_build_rows)
     int join(u64 bs, u64 bl, uint32_t workers)
@@ -1077,7 +1151,7 @@ int phj_enqueue(hjgpu_ctx *ctx, const PhjPlan &pl, const Rel &R, const Rel &S, h
     CHK(run.setup());
     record(ctx, EV_BEGIN, stream);
     CHK(run.begin());
-    CHK(run.road.merged ? run.partition_merged() : run.partition_in_turn());
+    CHK(run.road.beside ? run.partition_beside() : run.road.merged ? run.partition_merged() : run.partition_in_turn());
     if (hj_mode_marks_build(pl.mode) && (o.pre || o.stages != PHJ_WHOLE)) return fail(ctx, HJGPU_EINVAL, "internal: a join that marks its build rows is a whole join");
     if (run.road.joins) CHK(run.join(bs, bl, workers));
     record(ctx, EV_JOIN, stream);
@@ -1310,6 +1384,26 @@ static int phj_grouped(hjgpu_ctx *ctx, uint32_t G, uint32_t chunks, const Rel &R
                        hipStream_t stream);
 static void grouped_caps(const hjgpu_ctx *ctx, uint32_t G, size_t inner, size_t outer, size_t *cap_r, size_t *cap_s, size_t *plan_inner);
 
+// options "build_beside" and "build_cus" belong to the enqueue path, not to a kernel's tuning: the context keeps them itself
+static bool beside_option(hjgpu_ctx *ctx, const char *name, const char *value, bool *ok)
+{
+    const bool flag = strcmp(name, "build_beside") == 0;
+    if (!flag && strcmp(name, "build_cus") != 0) return false;
+    char *end = nullptr;
+    const long x = strtol(value, &end, 10);
+    *ok = end != value && !*end && x >= 0 && (flag || x < ctx->cus || x == 0);
+    if (*ok && flag) ctx->build_beside = x != 0;
+    if (*ok && !flag) ctx->build_cus = (int)x;
+    return true;
+}
+
+static void beside_option_from_env(hjgpu_ctx *ctx, const char *name, const char *env)
+{
+    const char *v = getenv(env);
+    bool ok = true;
+    if (v && *v && beside_option(ctx, name, v, &ok) && !ok) fprintf(stderr, "hjgpu: ignoring malformed %s=%s\n", env, v);
+}
+
 extern "C" {
 
 const char *hjgpu_status_string(int s)
@@ -1361,7 +1455,10 @@ int hjgpu_create(int device, hjgpu_ctx **out)
     if (hipSetDevice(device) != hipSuccess ||
         hipGetDeviceProperties(&ctx->prop, device) != hipSuccess) { delete ctx; return HJGPU_ENODEVICE; }
     ctx->cus = ctx->prop.multiProcessorCount;
-    hj_tuning_from_env(&ctx->tune);          // the only place the library looks at the environment
+    // the only place the library looks at the environment: the kernels' tuning, and the two options the context keeps itself
+    hj_tuning_from_env(&ctx->tune);
+    beside_option_from_env(ctx, "build_beside", "HJGPU_BUILD_BESIDE");
+    beside_option_from_env(ctx, "build_cus", "HJGPU_BUILD_CUS");
     for (int i = 0; i < EV_COUNT; ++i) {
         ctx->ev_valid[i] = false;
         if (hipEventCreate(&ctx->ev[i]) != hipSuccess) { delete ctx; return HJGPU_EHIP; }
@@ -1381,6 +1478,8 @@ int hjgpu_destroy(hjgpu_ctx *ctx)
     for (DevBuf *b : all) if (b->p) (void)hipFree(b->p);
     for (int i = 0; i < EV_COUNT; ++i) (void)hipEventDestroy(ctx->ev[i]);
     if (ctx->aux) (void)hipStreamDestroy(ctx->aux);
+    for (hipEvent_t e : ctx->beside_ev) if (e) (void)hipEventDestroy(e);
+    if (ctx->side) (void)hipStreamDestroy(ctx->side);
     for (hipEvent_t e : ctx->grp_ev) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : ctx->grp_ev_pass0) if (e) (void)hipEventDestroy(e);
     for (int b = 0; b < 4; ++b) {
@@ -1397,6 +1496,9 @@ const char *hjgpu_last_error(const hjgpu_ctx *ctx) { return ctx ? ctx->err : "nu
 int hjgpu_set_option(hjgpu_ctx *ctx, const char *name, const char *value)
 {
     if (!ctx || !name || !value) return HJGPU_EINVAL;
+    bool ok = false;
+    if (beside_option(ctx, name, value, &ok))
+        return ok ? HJGPU_OK : fail(ctx, HJGPU_EINVAL, "hjgpu_set_option: build_beside is 0 or 1, build_cus 0 (the library's choice) or 1 ... CUs - 1");
     HjTuning t = ctx->tune;
     if (!hj_tuning_set(&t, name, value)) return fail(ctx, HJGPU_EINVAL, "hjgpu_set_option: unknown option or malformed value");
     // the join kernels exist in a fixed set of geometries, _UNIQUE instances in some of them
@@ -1451,6 +1553,7 @@ int hjgpu_get_counter(hjgpu_ctx *ctx, const char *name, uint64_t *value)
 {
     if (!ctx || !name || !value) return HJGPU_EINVAL;
     if (strcmp(name, "probe_fallbacks") == 0) { *value = ctx->probe_fallbacks; return HJGPU_OK; }
+    if (strcmp(name, "build_beside") == 0) { *value = ctx->beside_joins; return HJGPU_OK; }
     if (strcmp(name, "probe_exact") == 0) { *value = (ctx->tune.exact_probe_counts || ctx->probe_exact) ? 1u : 0u; return HJGPU_OK; }
     if (strcmp(name, "lookup_lds_rows") == 0) { *value = lds_lookup_rows(ctx->tune); return HJGPU_OK; }
     if (strcmp(name, "compact_ranges") == 0) { *value = hj_compact::ranges_of(ctx->cus); return HJGPU_OK; }
@@ -1458,7 +1561,7 @@ int hjgpu_get_counter(hjgpu_ctx *ctx, const char *name, uint64_t *value)
     if (strcmp(name, "group_lds_groups") == 0) { *value = hj_group::LDS_GROUPS; return HJGPU_OK; }
     if (strcmp(name, "filter_step_rows") == 0) { *value = hj_filter::step_rows(ctx->cus); return HJGPU_OK; }
     if (strcmp(name, "gather_step_rows") == 0) { *value = hj_gather::step_rows(ctx->cus); return HJGPU_OK; }
-    return fail(ctx, HJGPU_EINVAL, "unknown counter (probe_fallbacks, probe_exact, lookup_lds_rows, compact_ranges, compact_chunk_rows, group_lds_groups, filter_step_rows, gather_step_rows)");
+    return fail(ctx, HJGPU_EINVAL, "unknown counter (probe_fallbacks, probe_exact, build_beside, lookup_lds_rows, compact_ranges, compact_chunk_rows, group_lds_groups, filter_step_rows, gather_step_rows)");
 }
 
 // the workspace's side of hjgpu_stats: what the context has spent growing it, and its last placement search
@@ -1529,6 +1632,17 @@ int hjgpu_get_stats(hjgpu_ctx *ctx, hjgpu_stats *s)
         r.ms_build = span(EV_BEGIN, EV_R_HIST);
         r.ms_join = span(EV_R_HIST, EV_JOIN);
         r.ms_histogram = r.ms_plan = r.ms_scatter1 = r.ms_scatter2 = 0;
+    } else if (ctx->last_beside) {
+        // the build side ran beside the probe side (partition_beside): its chain's own spans on the side stream, from the fork; the probe
+        // side's passes on the caller's stream; and what that stream then waited for "R done".  The phases overlap: they do not add up
+        float ms = 0;
+        r.ms_histogram = (ctx->ev_valid[EV_R_HIST] && hipEventElapsedTime(&ms, ctx->beside_ev[hjgpu_ctx::BESIDE_FORK], ctx->ev[EV_R_HIST]) == hipSuccess) ? ms : 0.f;
+        r.ms_plan = span(EV_R_HIST, EV_R_PLAN);
+        r.ms_scatter1 = span(EV_S_PLAN, EV_S_SC1);
+        r.ms_scatter2 = span(EV_S_SC1, EV_S_SC2);
+        r.ms_inner_wait = span(EV_S_SC2, EV_WAITED);
+        r.ms_join = span(EV_WAITED, EV_JOIN);
+        r.ms_build = 0;
     } else {
         r.ms_histogram = span(EV_BEGIN, EV_S_HIST) + span(EV_WAITED, EV_R_HIST);
         r.ms_plan = span(EV_S_HIST, EV_S_PLAN) + span(EV_R_HIST, EV_R_PLAN);

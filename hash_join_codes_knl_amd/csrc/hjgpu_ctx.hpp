@@ -15,6 +15,7 @@
 
 #include "hj_internal.hpp"
 #include "colop_checks.hpp"
+#include "build_beside_layout.hpp"
 
 
 struct DevBuf {
@@ -96,6 +97,17 @@ struct hjgpu_ctx {
     // blocking join of the context takes the exact path at once (hjgpu_get_counter "probe_fallbacks" / "probe_exact")
     uint64_t probe_fallbacks = 0;
     bool probe_exact = false;
+    // Build side beside the probe side (PhjRun::partition_beside): the context's side stream (non-blocking, made by the first join
+    // that takes the form) and the events of the fork and the join inside one call; option "build_beside" (default 1; 0: the one-stream order)
+    // and option "build_cus" (0: hj_beside's choice); joins that took the form (hjgpu_get_counter "build_beside"); and whether the last
+    // join did, which is how hjgpu_get_stats reads its events
+    enum { BESIDE_FORK = 0, BESIDE_PLAN_DONE, BESIDE_R_DONE, BESIDE_EVENTS };
+    hipStream_t side = nullptr;
+    hipEvent_t beside_ev[BESIDE_EVENTS] = {nullptr, nullptr, nullptr};
+    bool build_beside = true;
+    int build_cus = 0;
+    uint64_t beside_joins = 0;
+    bool last_beside = false;
     bool rows_plain = false;        // the join being enqueued is SOLO - a blocking call of a context with option "solo": plain partial-line stores
                                     // in K6 (k6_store8) and plain result rows (join_kernel<..., NTROWS = false>); every other launch writes them non-temporal
     // grouped plans: pass-0 twins of the four columns, the groups' offsets and (device-planned) descriptors, and the call's accumulated

@@ -159,18 +159,25 @@ typedef struct {
     uint32_t flags;            /* HJGPU_FLAG_*                                               */
 } hjgpu_npj_params;
 
-/* Per-phase device times of the last join on this context (hipEvent based). */
+/* Per-phase device times of the last join on this context (hipEvent based).
+ * A blocking hjgpu_phj whose build side was partitioned BESIDE its probe side (option "build_beside", below; hjgpu_get_counter
+ * "build_beside" counts these joins) has phases on two streams that overlap: they no longer add up to ms_total.  For such a join
+ * ms_total is the span from the first to the last event on the caller's stream; ms_scatter1 / ms_scatter2 are the PROBE side's passes
+ * on the caller's stream; ms_histogram / ms_plan are the BUILD side's own spans on the side stream (K4 from the fork on; K5 and K5b),
+ * whose K6 passes are not reported apart; ms_inner_wait is what the caller's stream then waited for the build side behind the probe
+ * side's pass 2. */
 typedef struct {
-    float    ms_total;
-    float    ms_histogram;     /* K4: fused two-level histogram, R and S                     */
-    float    ms_plan;          /* K5: prefix sums / cursors                                  */
-    float    ms_scatter1;      /* K6 pass 1, R and S                                         */
-    float    ms_scatter2;      /* K6 pass 2, R and S                                         */
+    float    ms_total;         /* first to last event on the caller's stream                 */
+    float    ms_histogram;     /* K4: fused two-level histogram, R and S (build beside: R, on the side stream) */
+    float    ms_plan;          /* K5: prefix sums / cursors (build beside: on the side stream) */
+    float    ms_scatter1;      /* K6 pass 1, R and S (build beside: S alone)                 */
+    float    ms_scatter2;      /* K6 pass 2, R and S (build beside: S alone)                 */
     float    ms_join;          /* K7+K8 (PHJ/CPRA) or K3 probe (NPJ)                         */
     float    ms_build;         /* NPJ: K1 clear + K2 build                                   */
     float    ms_close_gaps;    /* K9                                                         */
-    float    ms_inner_wait;    /* stream time spent waiting for the build side to arrive
-                                  (hjgpu_phj_overlapped_async), 0 otherwise                  */
+    float    ms_inner_wait;    /* stream time spent waiting for the build side: to arrive
+                                  (hjgpu_phj_overlapped_async), or to be partitioned on the side
+                                  stream (build beside); 0 otherwise                         */
     float    ms_upload;        /* hjgpu_join_host: host columns -> HBM (wall clock, pipelined
                                   with the probe side's partitioning for PHJ / CPRA)         */
     float    ms_download;      /* hjgpu_join_host_rows: result columns -> host (wall clock)  */
@@ -231,7 +238,13 @@ int  hjgpu_get_device_info(hjgpu_ctx *ctx, hjgpu_device_info *info);
  * twin, 1..16; "placement_ms": the search's wall-clock budget, default 500, 0 = none; "placement_log" 1: every candidate's fill time on stderr); "batch_tuples" (n, 0 = off); "group_from" / "group_inner" (tuples), "group_always" and "group_device" (0 / 1), "group_slack" (per cent): the
  * grouped plans of hjgpu_phj / hjgpu_cpra (below); "exact_probe_counts" (0 / 1, default 0: a blocking two-pass hjgpu_phj of one chunk
  * partitions its probe side without the histogram pass, into optimistic regions, and joins again exactly when one is full -
- * hjgpu_get_counter; 1: always the exact path) and "probe_slack" (per cent of slack in those regions, default 12, 0 = none); "solo" (0 / 1, default 0: the caller promises that nothing else runs on the device beside this context's BLOCKING joins - one process,
+ * hjgpu_get_counter; 1: always the exact path) and "probe_slack" (per cent of slack in those regions, default 12, 0 = none);
+ * "build_beside" (0 / 1, default 1: such a join, when both relations have rows, partitions its build side on a second stream of the
+ * context while the probe side goes through its passes on the caller's - a fork and a join inside the call; 0: one stream, the build
+ * side first; a join under option "solo" never forks: its plain stores rest on the promise of one stream) and "build_cus" (the CUs the
+ * build side's kernels get while the probe side's passes keep the others: 0 = the library's choice, which steps aside on small chips,
+ * for probe sides below 2^20 rows and for probe sides of fewer than 12 rows per build row; 1 ... CUs - 1: that many, at any size and
+ * ratio); "solo" (0 / 1, default 0: the caller promises that nothing else runs on the device beside this context's BLOCKING joins - one process,
  * one stream, as the reference's programs: the joins' partial-line and row stores then stay plain, 4 % faster; without the
  * promise every store that could sit dirty in an L2 is non-temporal, because plain stores ARE lost beside other queues' kernel
  * boundaries: 1.5 in 10^4 steps of the multi-GPU pipeline, DESIGN section 3 "Round 5"); diagnostics: "audit" (0 / 1: every stage of a join leaves a checksum of its output,
@@ -264,6 +277,8 @@ int  hjgpu_get_stats(hjgpu_ctx *ctx, hjgpu_stats *stats);
  *   "probe_fallbacks"  blocking PHJ joins whose claimed probe side (partitioned without its histogram pass, into optimistic regions)
  *                      overflowed and that were therefore done again on the exact path; their results are the exact path's
  *   "probe_exact"      1 when the context's blocking joins take the exact path (option "exact_probe_counts", or after a fallback)
+ *   "build_beside"     blocking PHJ joins whose build side was partitioned on the context's side stream beside the probe side's passes
+ *                      (option "build_beside")
  *   "lookup_lds_rows"  the largest build side that hjgpu_lookup answers from LDS tables (0 under option "no_broadcast")
  *   "compact_ranges", "compact_chunk_rows"   hjgpu_compact_selected's geometry: the ranges (= workgroups) its rows are cut into, and the
  *                      rows of a chunk, of which every range holds a whole number
