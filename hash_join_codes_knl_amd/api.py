@@ -30,6 +30,12 @@ FILTER_MAX_PREDS = 4    # HJGPU_FILTER_MAX_PREDS
 PRED_NOT = 1            # HJGPU_PRED_NOT: the rows OUTSIDE [lo, hi] pass
 PRED_SIGNED = 2         # HJGPU_PRED_SIGNED: lo, hi and the column are int32 (two's complement order)
 GATHER_MAX_COLS = 4     # HJGPU_GATHER_MAX_COLS
+AGG_SUM = 0             # HJGPU_AGG_SUM: SUM(a)
+AGG_SUM_MUL = 1         # HJGPU_AGG_SUM_MUL: SUM(a * b), the exact 64-bit product of the two 32-bit values
+AGG_MIN = 2             # HJGPU_AGG_MIN: MIN(a)
+AGG_MAX = 3             # HJGPU_AGG_MAX: MAX(a)
+AGG_SIGNED = 1          # HJGPU_AGG_SIGNED: a (and b) are int32
+AGG_MAX_AGGS = 4        # HJGPU_AGG_MAX_AGGS
 
 EXPORTS = [
     "hjgpu_kernel_hash", "hjgpu_library_hash", "hjgpu_device_count", "hjgpu_create", "hjgpu_destroy", "hjgpu_last_error", "hjgpu_status_string",
@@ -45,6 +51,7 @@ EXPORTS = [
     "hjgpu_gather_selected", "hjgpu_gather_selected_async",
     "hjgpu_compact_selected", "hjgpu_compact_selected_async",
     "hjgpu_group_sum", "hjgpu_group_sum_async",
+    "hjgpu_group_agg", "hjgpu_group_agg_async",
     "hjgpu_npj", "hjgpu_phj", "hjgpu_cpra",
     "hjgpu_npj_async", "hjgpu_phj_async", "hjgpu_cpra_async", "hjgpu_phj_overlapped_async",
     "hjgpu_phj_build", "hjgpu_phj_probe", "hjgpu_phj_probe_async",
@@ -99,6 +106,12 @@ class Predicate(C.Structure):
             return p
         lo, hi, flags = tuple(p) if len(p) == 3 else tuple(p) + (0,)
         return cls(int(lo) & 0xFFFFFFFF, int(hi) & 0xFFFFFFFF, int(flags), 0)
+
+
+class Aggregate(C.Structure):
+    """hjgpu_aggregate: fn (AGG_SUM, AGG_SUM_MUL, AGG_MIN, AGG_MAX) over the device column d_a - and d_b, the second factor, under
+    AGG_SUM_MUL alone; flags: AGG_SIGNED (the columns are int32)."""
+    _fields_ = [("fn", C.c_uint32), ("flags", C.c_uint32), ("d_a", C.c_void_p), ("d_b", C.c_void_p)]
 
 
 class Stats(C.Structure):
@@ -294,6 +307,9 @@ def load_library(build_if_missing=True):
     group = [vp, vp, sz, u32, C.POINTER(vp), u32, C.POINTER(vp), C.POINTER(vp), vp, C.POINTER(vp), sz]
     L.hjgpu_group_sum.argtypes = group + [u64p, vp]
     L.hjgpu_group_sum_async.argtypes = group + [vp, vp]
+    agg = [vp, vp, sz, u32, C.POINTER(vp), u32, C.POINTER(Aggregate), C.POINTER(vp), vp, C.POINTER(vp), sz]
+    L.hjgpu_group_agg.argtypes = agg + [u64p, vp]
+    L.hjgpu_group_agg_async.argtypes = agg + [vp, vp]
     L.hjgpu_npj_lookup_table_selected.argtypes = [vp, vp, sz, vp, sz, u32, vp, vp, vp, C.POINTER(Result), vp]
     join = [vp, vp, vp, sz, vp, vp, sz]
     L.hjgpu_npj.argtypes = join + [C.POINTER(NpjParams), C.POINTER(Result), C.POINTER(Output), vp]
@@ -461,7 +477,7 @@ class HjGpu:
         "compact_ranges" / "compact_chunk_rows" (compact_selected's geometry: its ranges, and the rows of a chunk),
         "group_lds_groups" (the distinct groups a workgroup's LDS table of group_sum holds before further ones go to device memory),
         "filter_step_rows" / "gather_step_rows" (the rows filter_selected's / gather_selected's whole grid covers in one iteration of its
-        loop)."""
+        loop), "agg_step_rows" / "agg_scalar_step_rows" (the same for group_agg with key columns / without)."""
         v = C.c_uint64()
         self._check(self.lib.hjgpu_get_counter(self.handle, name.encode(), C.byref(v)))
         return v.value
@@ -694,6 +710,42 @@ class HjGpu:
         compares with capacity (None: the shortest output)"""
         nk, kin, nv, vin, kout, cout, sout, capacity = self._group_args(keys_in, vals_in, keys_out, sums_out, counts_out, capacity)
         self._check(self.lib.hjgpu_group_sum_async(self.handle, self._ptr(select_bits), n, nk, kin, nv, vin, kout, cout, sout, capacity,
+                                                   self._ptr(d_ngroups), stream))
+
+    # ---- aggregate functions: GROUP BY nothing, one or two keys; COUNT(*), SUM(a), SUM(a * b), MIN(a), MAX(a) ----------------------
+    def _agg_args(self, keys_in, aggs, keys_out, aggs_out, counts_out, capacity):
+        keys_in, aggs, keys_out, aggs_out = list(keys_in or ()), list(aggs or ()), list(keys_out or ()), list(aggs_out or ())
+        if len(keys_in) != len(keys_out) or len(aggs) != len(aggs_out):
+            raise ValueError("group_agg: %d key columns with %d outputs, %d aggregates with %d outputs"
+                             % (len(keys_in), len(keys_out), len(aggs), len(aggs_out)))
+        capacity = self._default_capacity(capacity, keys_out + aggs_out + ([counts_out] if counts_out is not None else []), "group_agg")
+        rows = []
+        for g in aggs:                                                  # (fn, a[, b[, flags]]) or an Aggregate
+            if not isinstance(g, Aggregate):
+                fn, a, b, flags = tuple(g) + ((None, 0), (0,), ())[len(g) - 2]
+                g = Aggregate(int(fn), int(flags), self._ptr(a), self._ptr(b))
+            rows.append(g)
+        arr = self._ptr_array
+        return (len(keys_in), arr(keys_in), len(rows), (Aggregate * len(rows))(*rows) if rows else None, arr(keys_out), self._ptr(counts_out),
+                arr(aggs_out), capacity)
+
+    def group_agg(self, select_bits, n, keys_in, aggs, keys_out, aggs_out, counts_out=None, capacity=None, stream=None):
+        """hjgpu_group_agg: group_sum with no, one or two keys_in columns and, per aggregate aggs[c] = (fn, a[, b[, flags]]) or an
+        Aggregate, aggs_out[c][j] (uint64) = SUM(a), SUM(a * b) (the exact 64-bit product), MIN(a) or MAX(a) over the group's rows;
+        under AGG_SIGNED the columns are int32 and the word is read as int64.  No key column: the scalar aggregate, J = 1 when a row is
+        selected and 0 when none is.  Returns J; J > capacity (default: the shortest output) raises HjGpuError(HJGPU_EOVERFLOW) that
+        carries .count; the outputs are unspecified then."""
+        nk, kin, na, ag, kout, cout, aout, capacity = self._agg_args(keys_in, aggs, keys_out, aggs_out, counts_out, capacity)
+        count = C.c_uint64()
+        self._check(self.lib.hjgpu_group_agg(self.handle, self._ptr(select_bits), n, nk, kin, na, ag, kout, cout, aout, capacity,
+                                             C.byref(count), stream), count=count.value)
+        return count.value
+
+    def group_agg_async(self, select_bits, n, keys_in, aggs, keys_out, aggs_out, counts_out, capacity, d_ngroups, stream=None):
+        """hjgpu_group_agg_async: enqueue only; the number of groups goes to d_ngroups (uint64 in device memory), which the caller
+        compares with capacity (None: the shortest output)"""
+        nk, kin, na, ag, kout, cout, aout, capacity = self._agg_args(keys_in, aggs, keys_out, aggs_out, counts_out, capacity)
+        self._check(self.lib.hjgpu_group_agg_async(self.handle, self._ptr(select_bits), n, nk, kin, na, ag, kout, cout, aout, capacity,
                                                    self._ptr(d_ngroups), stream))
 
     # ---- whole joins ------------------------------------------------------------------

@@ -1,4 +1,4 @@
-// colop_checks.hpp - what the column operators (hjgpu_compact_selected, hjgpu_group_sum, hjgpu_filter_selected, hjgpu_gather_selected: hjgpu_colops.hip)
+// colop_checks.hpp - what the column operators (hjgpu_compact_selected, hjgpu_group_sum, hjgpu_group_agg, hjgpu_filter_selected, hjgpu_gather_selected: hjgpu_colops.hip)
 // and the selected look-ups refuse from their arguments alone, before anything is allocated or enqueued (DESIGN.md section 5 "Argument checks
 // of the column operators").  Plain host C++, no HIP and no context: a check returns {status, text}, its caller hands that to fail().
 // tests/test_colop_checks.py compiles it with g++ and compares every decision with the hand-written checkers it replaced.
@@ -52,8 +52,13 @@ struct Operand {
     int in_place;                                       // a written operand: the read operand it may coincide with exactly, or -1
 };
 
+// the largest table, hjgpu_group_agg_async's: the mask, 2 keys, 4 aggregates' a and b, 2 key outputs, 4 aggregate outputs, the counts and
+// the count word (19; a compaction has the mask, 8 inputs, 8 outputs and the row numbers: 18)
+constexpr int MAX_OPERANDS = 1 + 2 * HJGPU_GROUP_MAX_KEYS + 3 * HJGPU_AGG_MAX_AGGS + 2;
+static_assert(MAX_OPERANDS >= 2 * HJGPU_COMPACT_MAX_COLS + 2, "the operand table holds a compaction's operands");
+
 struct Operands {
-    Operand v[2 * HJGPU_COMPACT_MAX_COLS + 2];          // the largest table: the mask, 8 inputs, 8 outputs and the row numbers of a compaction
+    Operand v[MAX_OPERANDS];
     int n = 0;
     int read(const void *p, size_t bytes, uint32_t align, const char *name) { v[n] = {p, bytes, false, align, name, -1}; return n++; }
     int write(const void *p, size_t bytes, uint32_t align, const char *name, int in_place = -1) { v[n] = {p, bytes, true, align, name, in_place}; return n++; }
@@ -161,6 +166,53 @@ inline Verdict check_group(const GroupCall &g, const uint64_t *ngroups, bool dev
     for (uint32_t k = 0; k < g.nvals; ++k) t.read(g.vals_in[k], g.n * sizeof(uint32_t), 16, "a measure column");
     for (uint32_t k = 0; k < g.nkeys; ++k) t.write(g.keys_out[k], g.capacity * sizeof(uint32_t), 16, "a key output column");
     for (uint32_t k = 0; k < g.nvals; ++k) t.write(g.sums_out[k], g.capacity * sizeof(uint64_t), 16, "a sum column");
+    t.write(g.counts_out, g.capacity * sizeof(uint64_t), 16, "d_counts_out");
+    if (device_count) t.write(ngroups, sizeof(uint64_t), 8, "d_ngroups");
+    return check_operands(t);
+}
+
+// ---- hjgpu_group_agg ------------------------------------------------------------------------------------------------------------------------
+struct GroupAggCall {
+    const uint32_t *bits;
+    size_t n;
+    uint32_t nkeys, naggs;
+    const uint32_t *const *keys_in;
+    const hjgpu_aggregate *aggs;                        // a host array, copied by value
+    uint32_t *const *keys_out;
+    uint64_t *counts_out;
+    uint64_t *const *aggs_out;
+    size_t capacity;
+};
+
+// check_group's head with nkeys == 0 legal (the scalar aggregate: the key arrays may then be NULL), then every aggregate by its index
+inline Verdict check_group_agg(const GroupAggCall &g, const uint64_t *ngroups, bool device_count)
+{
+    if (!ngroups) return refuse(HJGPU_EINVAL, "null group count pointer");
+    if (device_count && ((uintptr_t)ngroups & 7)) return refuse(HJGPU_EALIGN, "d_ngroups must be 8-byte aligned");
+    if (g.nkeys > HJGPU_GROUP_MAX_KEYS) return refuse(HJGPU_EINVAL, "nkeys must not exceed HJGPU_GROUP_MAX_KEYS (2)");
+    if (g.naggs > HJGPU_AGG_MAX_AGGS) return refuse(HJGPU_EINVAL, "naggs must not exceed HJGPU_AGG_MAX_AGGS (4)");
+    if (hj_group::merge_slots(g.capacity) == 0) return refuse(HJGPU_EINVAL, "capacity must not exceed 2^40 groups");
+    if (g.n == 0) return no_objection();                      // nothing is read, nothing but the count is written: anything else may be NULL
+    if ((g.nkeys && (!g.keys_in || !g.keys_out)) || (g.naggs && !g.aggs_out)) return refuse(HJGPU_EINVAL, "null column array");
+    if (g.naggs && !g.aggs) return refuse(HJGPU_EINVAL, "null aggregate array");
+    for (uint32_t k = 0; k < g.nkeys; ++k)
+        if (!g.keys_in[k] || !g.keys_out[k]) return refuse(HJGPU_EINVAL, "null key column pointer");
+    for (uint32_t c = 0; c < g.naggs; ++c) {
+        const hjgpu_aggregate &a = g.aggs[c];
+        if (a.fn > HJGPU_AGG_MAX) return refuse(HJGPU_EINVAL, "aggregate %u: unknown function %u (HJGPU_AGG_SUM, _SUM_MUL, _MIN and _MAX are defined)", c, a.fn);
+        if (a.flags & ~HJGPU_AGG_SIGNED) return refuse(HJGPU_EINVAL, "aggregate %u: unknown flag (HJGPU_AGG_SIGNED is defined)", c);
+        if (!a.d_a) return refuse(HJGPU_EINVAL, "aggregate %u: null d_a", c);
+        if (a.fn == HJGPU_AGG_SUM_MUL && !a.d_b) return refuse(HJGPU_EINVAL, "aggregate %u: null d_b under HJGPU_AGG_SUM_MUL", c);
+        if (a.fn != HJGPU_AGG_SUM_MUL && a.d_b) return refuse(HJGPU_EINVAL, "aggregate %u: d_b must be NULL unless the function is HJGPU_AGG_SUM_MUL", c);
+        if (!g.aggs_out[c]) return refuse(HJGPU_EINVAL, "aggregate %u: null output column pointer", c);
+    }
+    Operands t;
+    t.read(g.bits, bitmap_bytes(g.n), 16, "d_select_bits");
+    for (uint32_t k = 0; k < g.nkeys; ++k) t.read(g.keys_in[k], g.n * sizeof(uint32_t), 16, "a key column");
+    for (uint32_t c = 0; c < g.naggs; ++c) t.read(g.aggs[c].d_a, g.n * sizeof(uint32_t), 16, "an aggregate's column d_a");
+    for (uint32_t c = 0; c < g.naggs; ++c) t.read(g.aggs[c].d_b, g.n * sizeof(uint32_t), 16, "an aggregate's column d_b");
+    for (uint32_t k = 0; k < g.nkeys; ++k) t.write(g.keys_out[k], g.capacity * sizeof(uint32_t), 16, "a key output column");
+    for (uint32_t c = 0; c < g.naggs; ++c) t.write(g.aggs_out[c], g.capacity * sizeof(uint64_t), 16, "an aggregate output column");
     t.write(g.counts_out, g.capacity * sizeof(uint64_t), 16, "d_counts_out");
     if (device_count) t.write(ngroups, sizeof(uint64_t), 8, "d_ngroups");
     return check_operands(t);

@@ -826,6 +826,353 @@ int hj_launch_group_emit(const GroupEmitArgs &a, int cus, hipStream_t stream)
     return hipGetLastError() == hipSuccess ? HJGPU_OK : HJGPU_EHIP;
 }
 
+// ---- aggregate functions (hjgpu_group_agg; DESIGN.md section 5 "Aggregate functions") ---------------------------------------------------
+// GROUP BY (nothing | key 0 [, key 1]) COUNT(*) and up to four of SUM(a), SUM(a * b), MIN(a), MAX(a) over the rows a bitmap selects.  The
+// grouped road is group_sum_kernel's body with two differences: what a row contributes to an aggregate's word of its slot, and how words
+// are combined - agg_layout.hpp's term() and combine(): a sum is added, an extreme is an unsigned maximum of a transformed value whose
+// neutral word is the tables' initial 0 (ds_max_u64 in LDS, global_atomic_umax_x2 in the merge table).  fn and flags are uniform run-time
+// values per aggregate: every branch on them is a scalar branch.  The tables, insert-or-find, the fold, the spill rule and the flush are
+// group_sum_kernel's own (group_lds_slot, group_merge_slot, group_add).
+
+// combines x into word `word` (1 + c: aggregate c) of the slot at `loc`: group_add for a sum, the unsigned maximum for an extreme
+__device__ __forceinline__ void agg_combine(hj_group::Slot *tab, const GroupArgs &a, u64 loc, uint32_t word, bool extreme, u64 x)
+{
+    if (!extreme) group_add(tab, a, loc, word, x);
+    else if (loc & GROUP_IN_LDS) __hip_atomic_fetch_max(&tab[(uint32_t)loc].count + word, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);   // ds_max_u64
+    else if (loc != GROUP_NO_SLOT) __hip_atomic_fetch_max(&a.merge[loc].count + word, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);          // global_atomic_umax_x2
+}
+
+// the terms of the rows of nibble m of one vector, combined: a row outside m contributes the neutral 0.  Straight-line code: the terms of
+// all four rows are computed and chosen by the nibble's bits
+template <int KIND>
+__device__ __forceinline__ u64 agg_fold(const hj_agg::Norm &p, uint32_t m, const uint4 &x, const uint4 &y)
+{
+    using namespace hj_agg;
+    u64 acc = (m & 1u) ? term<KIND>(p, x.x, y.x) : 0ull;
+    acc = combine<KIND>(acc, (m & 2u) ? term<KIND>(p, x.y, y.y) : 0ull);
+    acc = combine<KIND>(acc, (m & 4u) ? term<KIND>(p, x.z, y.z) : 0ull);
+    return combine<KIND>(acc, (m & 8u) ? term<KIND>(p, x.w, y.w) : 0ull);
+}
+
+// agg_fold under the aggregate's own kind: fn is uniform, so this is a scalar branch to one of three straight-line bodies
+__device__ __forceinline__ u64 agg_fold_of(uint32_t fn, const hj_agg::Norm &p, uint32_t m, const uint4 &x, const uint4 &y)
+{
+    using namespace hj_agg;
+    if (fn == SUM) return agg_fold<KIND_VALUE>(p, m, x, y);
+    if (fn == SUM_MUL) return agg_fold<KIND_PRODUCT>(p, m, x, y);
+    return agg_fold<KIND_EXTREME>(p, m, x, y);
+}
+
+// The scalar road's body for one aggregate of one kind: the vectors of a - and of b, KIND_PRODUCT only - of the lane's trips (v: the first
+// trip's vector) for the lanes whose nibble is not 0 (nib != 0 only where the vector starts below n), then their folded terms, combined.
+// The loads sit inside the body, so the three kinds are three real branches and a row costs the arithmetic of its own kind alone.
+template <int KIND, int BATCH>
+__device__ __forceinline__ u64 agg_scalar_part(const hj_agg::Norm &p, const uint32_t (&nib)[BATCH], const uint4 *x4, const uint4 *y4, u64 v, u64 stride)
+{
+    uint4 x[BATCH], y[BATCH];
+#pragma unroll
+    for (int u = 0; u < BATCH; ++u) {
+        x[u] = make_uint4(0, 0, 0, 0);
+        if (nib[u]) x[u] = hj_load_nt(x4 + v + (u64)u * stride);
+    }
+#pragma unroll
+    for (int u = 0; u < BATCH; ++u) {
+        y[u] = make_uint4(0, 0, 0, 0);
+        if constexpr (KIND == hj_agg::KIND_PRODUCT) { if (nib[u]) y[u] = hj_load_nt(y4 + v + (u64)u * stride); }
+    }
+    u64 part = 0;
+#pragma unroll
+    for (int u = 0; u < BATCH; ++u) part = hj_agg::combine<KIND>(part, agg_fold<KIND>(p, nib[u], x[u], y[u]));
+    return part;
+}
+
+// group_sum_kernel's iteration up to the leaders' slots and counts; then, per aggregate (naggs is a uniform run-time bound), column a - and
+// column b under SUM_MUL - loaded as the measure columns are: non-temporal, only by the lanes whose nibble is not 0, the last partial vector
+// whole and masked by the nibble; each leader's folded term goes to its slot.  The flush combines the workgroup's occupied slots into the
+// merge table, word by word under the word's own combine.  No global store; no workgroup waits for another.
+template <int NKEYS, bool SEL>
+__global__ __launch_bounds__(hj_group::BLOCK) void agg_group_kernel(AggArgs aa)
+{
+    using namespace hj_group;
+    constexpr int BATCH = (int)hj_agg::GROUP_BATCH, ROWS = 4 * BATCH;
+    const GroupArgs &a = aa.g;
+    __shared__ Slot tab[LDS_SLOTS + 1];
+    __shared__ uint32_t used;
+    const uint32_t tid = threadIdx.x;
+    {
+        u64 *raw = reinterpret_cast<u64 *>(tab);
+        for (uint32_t i = tid; i < (LDS_SLOTS + 1) * (uint32_t)(sizeof(Slot) / 8); i += BLOCK) raw[i] = 0;
+        if (tid == 0) used = 0;
+    }
+    __syncthreads();
+    const uint4 *k4 = reinterpret_cast<const uint4 *>(a.keys[0]);
+    const uint4 *k4b = reinterpret_cast<const uint4 *>(a.keys[NKEYS - 1]);
+    const u64 n = a.n, nvec = (n + 3) >> 2, stride = (u64)gridDim.x * BLOCK;
+    const uint32_t naggs = a.nvals;
+    for (u64 v0 = (u64)blockIdx.x * BLOCK + (tid & ~63u); v0 < nvec; v0 += stride * BATCH) {
+        uint32_t nib[BATCH];
+        uint4 k0[BATCH], k1[BATCH];
+        lookup_fetch<SEL, BATCH, true>(a.select_bits, k4, v0, stride, n, nib, k0);
+#pragma unroll
+        for (int u = 0; u < BATCH; ++u) {
+            k1[u] = make_uint4(0, 0, 0, 0);
+            if constexpr (NKEYS == 2) { if (nib[u]) k1[u] = hj_load_nt(k4b + v0 + (u64)u * stride + hj_lane()); }
+        }
+        // the fold: row q = 4 u + j of the lane leads the rows of its trip that carry its tuple and that no earlier row leads
+        u64 t[ROWS], loc[ROWS];
+        uint32_t cls = 0, lead = 0;                     // cls: a nibble per row, the rows (of its trip) it leads; lead: the rows that lead any
+#pragma unroll
+        for (int u = 0; u < BATCH; ++u) {
+            t[4 * u] = tuple_of(k0[u].x, k1[u].x); t[4 * u + 1] = tuple_of(k0[u].y, k1[u].y);
+            t[4 * u + 2] = tuple_of(k0[u].z, k1[u].z); t[4 * u + 3] = tuple_of(k0[u].w, k1[u].w);
+            uint32_t left = nib[u];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                loc[4 * u + j] = GROUP_NO_SLOT;
+                uint32_t m = 0;
+#pragma unroll
+                for (int i = j; i < 4; ++i) if (((left >> i) & 1u) && t[4 * u + i] == t[4 * u + j]) m |= 1u << i;
+                if (!((left >> j) & 1u)) m = 0;
+                left &= ~m;
+                cls |= m << (4 * (4 * u + j));
+                lead |= (m ? 1u : 0u) << (4 * u + j);
+            }
+        }
+        // the leaders' slots and counts: one copy of the probe code, whichever row it serves
+        for (uint32_t work = lead; work; work &= work - 1) {
+            const uint32_t q = __ffs(work) - 1;
+            u64 tu[4] = {t[0], t[1], t[2], t[3]};       // the trip's, then the row's
+#pragma unroll
+            for (int u = 1; u < BATCH; ++u)
+                if ((int)(q >> 2) == u) { tu[0] = t[4 * u]; tu[1] = t[4 * u + 1]; tu[2] = t[4 * u + 2]; tu[3] = t[4 * u + 3]; }
+            const uint32_t qj = q & 3u;
+            const u64 tq = qj == 0 ? tu[0] : qj == 1 ? tu[1] : qj == 2 ? tu[2] : tu[3];
+            const u64 h = mix(tq);
+            u64 at = group_lds_slot(tab, &used, tq, h);
+            if (at == GROUP_NO_SLOT) at = group_merge_slot(a, tq, h);
+            group_add(tab, a, at, 0, (u64)__popc((cls >> (4 * q)) & 15u));
+#pragma unroll
+            for (int r = 0; r < ROWS; ++r) loc[r] = q == r ? at : loc[r];
+        }
+        for (uint32_t c = 0; c < naggs; ++c) {
+            const uint32_t fn = aa.fn[c];
+            const hj_agg::Norm norm = hj_agg::normalise(fn, aa.flags[c]);
+            const uint4 *x4 = reinterpret_cast<const uint4 *>(a.vals[c]);
+            const uint4 *y4 = reinterpret_cast<const uint4 *>(aa.b[c]);
+            uint4 x[BATCH], y[BATCH];
+#pragma unroll
+            for (int u = 0; u < BATCH; ++u) {
+                x[u] = make_uint4(0, 0, 0, 0);
+                if (nib[u]) x[u] = hj_load_nt(x4 + v0 + (u64)u * stride + hj_lane());
+            }
+#pragma unroll
+            for (int u = 0; u < BATCH; ++u) {
+                y[u] = make_uint4(0, 0, 0, 0);
+                if (fn == hj_agg::SUM_MUL && nib[u]) y[u] = hj_load_nt(y4 + v0 + (u64)u * stride + hj_lane());
+            }
+            const bool extreme = hj_agg::is_extreme(fn);
+            for (uint32_t work = lead; work; work &= work - 1) {
+                const uint32_t q = __ffs(work) - 1, m = (cls >> (4 * q)) & 15u;
+                uint4 xq = x[0], yq = y[0];
+#pragma unroll
+                for (int u = 1; u < BATCH; ++u) if ((int)(q >> 2) == u) { xq = x[u]; yq = y[u]; }
+                u64 at = loc[0];
+#pragma unroll
+                for (int r = 1; r < ROWS; ++r) at = q == r ? loc[r] : at;
+                agg_combine(tab, a, at, 1 + c, extreme, agg_fold_of(fn, norm, m, xq, yq));
+            }
+        }
+    }
+    __syncthreads();
+    for (uint32_t i = tid; i <= LDS_SLOTS; i += BLOCK) {
+        const u64 t = tab[i].tuple, cnt = tab[i].count;
+        if (i < LDS_SLOTS ? t != 0 : cnt != 0) {
+            const u64 at = group_merge_slot(a, t, mix(t));
+            if (at != GROUP_NO_SLOT) {
+                atomicAdd(&a.merge[at].count, cnt);
+                for (uint32_t c = 0; c < naggs; ++c) {
+                    if (hj_agg::is_extreme(aa.fn[c])) __hip_atomic_fetch_max(&a.merge[at].sums[c], tab[i].sums[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    else atomicAdd(&a.merge[at].sums[c], tab[i].sums[c]);
+                }
+            }
+        }
+    }
+}
+
+__device__ __forceinline__ u64 agg_wave_reduce(bool extreme, u64 x)
+{
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        const u64 y = __shfl_down(x, d, 64);
+        x = extreme ? (y > x ? y : x) : x + y;
+    }
+    return x;   // valid in lane 0
+}
+
+// The scalar road (nkeys == 0): no table.  One persistent grid of agg_layout.hpp's scalar geometry; an iteration is BATCH wave trips of
+// hj_lookup.hpp's layout: the mask words first (SEL; lookup_fetch's nibble, cut at n), then, per aggregate, column a - and column b under
+// SUM_MUL - for the lanes whose nibble is not 0: a group of 8 lanes whose mask word is 0 loads nothing; everything non-temporal; the last,
+// partial vector of a column is loaded whole and masked by the nibble.  A lane keeps the count and the aggregates' words in registers over
+// its whole loop; at the end a wave combines them across its lanes, the workgroup's waves through LDS - the kernel's only LDS, behind the
+// loop - and one lane combines them into the merge table's slot of tuple 0 (a.g.merge[a.g.merge_mask + 1]), which the emit kernel turns
+// into J = 1 when its count is not 0.  No global store; no workgroup waits for another.
+template <bool SEL>
+__global__ __launch_bounds__(hj_agg::SCALAR_BLOCK) void agg_scalar_kernel(AggArgs aa)
+{
+    using namespace hj_agg;
+    constexpr int BATCH = (int)SCALAR_BATCH, NW = SCALAR_BLOCK / 64;
+    __shared__ u64 red[NW][1 + MAX_AGGS];
+    const GroupArgs &a = aa.g;
+    const uint32_t tid = threadIdx.x;
+    const u64 n = a.n, nvec = (n + 3) >> 2, stride = (u64)gridDim.x * SCALAR_BLOCK;
+    const uint32_t naggs = a.nvals;
+    u64 count = 0, acc[MAX_AGGS] = {0, 0, 0, 0};
+    for (u64 v0 = (u64)blockIdx.x * SCALAR_BLOCK + (tid & ~63u); v0 < nvec; v0 += stride * BATCH) {
+        uint32_t nib[BATCH];
+#pragma unroll
+        for (int u = 0; u < BATCH; ++u) {
+            const u64 v = v0 + (u64)u * stride + hj_lane(), g = v << 2;
+            const uint32_t rows = g + 4 <= n ? 15u : g < n ? (1u << (uint32_t)(n - g)) - 1u : 0u;
+            nib[u] = rows;
+            if constexpr (SEL) {
+                uint32_t w = 0;
+                if (v < nvec) w = hj_load_nt(a.select_bits + (v >> 3));     // (v < nvec: row 4 v < n, and word v / 8 starts at or before it)
+                nib[u] = (w >> ((tid & 7u) * 4)) & rows;
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < BATCH; ++u) count += __popc(nib[u]);
+        // (one copy of the body for whichever aggregate it serves, as the measure loop of group_sum_kernel: unrolled copies would keep
+        // every aggregate's vectors in registers at once and halve the waves per SIMD)
+#pragma unroll 1
+        for (uint32_t c = 0; c < naggs; ++c) {
+            const uint32_t fn = aa.fn[c];
+            const Norm norm = normalise(fn, aa.flags[c]);
+            const uint4 *x4 = reinterpret_cast<const uint4 *>(a.vals[c]);
+            const uint4 *y4 = reinterpret_cast<const uint4 *>(aa.b[c]);
+            const u64 v = v0 + hj_lane();
+            u64 part;
+            if (fn == SUM) part = agg_scalar_part<KIND_VALUE, BATCH>(norm, nib, x4, y4, v, stride);
+            else if (fn == SUM_MUL) part = agg_scalar_part<KIND_PRODUCT, BATCH>(norm, nib, x4, y4, v, stride);
+            else part = agg_scalar_part<KIND_EXTREME, BATCH>(norm, nib, x4, y4, v, stride);
+#pragma unroll
+            for (uint32_t k = 0; k < MAX_AGGS; ++k) acc[k] = k == c ? combine(fn, acc[k], part) : acc[k];   // (c is uniform: a scalar compare, no indexed register)
+        }
+    }
+    count = wave_reduce_sum(count);
+#pragma unroll
+    for (uint32_t c = 0; c < MAX_AGGS; ++c)
+        if (c < naggs) acc[c] = agg_wave_reduce(is_extreme(aa.fn[c]), acc[c]);
+    if (hj_lane() == 0) {
+        red[tid >> 6][0] = count;
+#pragma unroll
+        for (uint32_t c = 0; c < MAX_AGGS; ++c) red[tid >> 6][1 + c] = acc[c];
+    }
+    __syncthreads();
+    if (tid == 0) {
+        hj_group::Slot *slot = a.merge + (a.merge_mask + 1);
+        u64 rows = 0;
+#pragma unroll
+        for (int w = 0; w < NW; ++w) rows += red[w][0];
+        if (rows) {                                                     // (no selected row: nothing to combine, and the count stays 0)
+            atomicAdd(&slot->count, rows);
+#pragma unroll
+            for (uint32_t c = 0; c < MAX_AGGS; ++c) {
+                if (c >= naggs) break;
+                const uint32_t fn = aa.fn[c];
+                u64 x = 0;
+#pragma unroll
+                for (int w = 0; w < NW; ++w) x = combine(fn, x, red[w][1 + c]);
+                if (is_extreme(fn)) __hip_atomic_fetch_max(&slot->sums[c], x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                else atomicAdd(&slot->sums[c], x);
+            }
+        }
+    }
+}
+
+// group_emit_kernel with no, one or two key columns and agg_layout.hpp's result() per aggregate column: the sums leave as they are, the
+// extremes in the column's own values
+__global__ __launch_bounds__(256) void agg_emit_kernel(AggEmitArgs ae)
+{
+    const GroupEmitArgs &a = ae.g;
+    const uint32_t lane = hj_lane();
+    const u64 total = a.slots + 1, stride = (u64)gridDim.x * 256;
+    for (u64 i0 = (u64)blockIdx.x * 256 + (threadIdx.x & ~63u); i0 < total; i0 += stride) {
+        const u64 i = i0 + lane;
+        u64 t = 0, cnt = 0;
+        if (i < total) { t = a.merge[i].tuple; cnt = a.merge[i].count; }
+        const bool occ = i < a.slots ? t != 0 : i == a.slots && cnt != 0;
+        const u64 vote = __ballot(occ);
+        if (vote == 0) continue;
+        u64 base = 0;
+        if (lane == 0) base = atomicAdd(a.d_ngroups, (u64)__popcll(vote));
+        base = hj_uniform(base);
+        const u64 j = base + __popcll(vote & ((1ull << lane) - 1ull));
+        if (occ && j < a.capacity) {
+            if (a.nkeys > 0) hj_store(a.keys_out[0] + j, (uint32_t)t);
+            if (a.nkeys > 1) hj_store(a.keys_out[1] + j, (uint32_t)(t >> 32));
+            if (a.counts_out) hj_store(a.counts_out + j, cnt);
+#pragma unroll
+            for (uint32_t c = 0; c < hj_agg::MAX_AGGS; ++c)
+                if (c < a.nvals) hj_store(a.sums_out[c] + j, hj_agg::result(ae.fn[c], ae.flags[c], a.merge[i].sums[c]));
+        }
+    }
+}
+
+static bool agg_args_valid(const AggArgs &aa, uint32_t min_keys, uint32_t max_keys, int cus)
+{
+    const GroupArgs &a = aa.g;
+    if (a.nkeys < min_keys || a.nkeys > max_keys || a.nvals > hj_agg::MAX_AGGS || !a.merge || !a.overflow || (a.merge_mask & (a.merge_mask + 1)) || cus < 1) return false;
+    uintptr_t all = (uintptr_t)a.select_bits;
+    for (uint32_t c = 0; c < a.nkeys; ++c) { if (!a.keys[c]) return false; all |= (uintptr_t)a.keys[c]; }
+    for (uint32_t c = 0; c < a.nvals; ++c) {
+        if (aa.fn[c] > hj_agg::MAX || (aa.flags[c] & ~hj_agg::SIGNED) || !a.vals[c] || (aa.fn[c] == hj_agg::SUM_MUL) != (aa.b[c] != nullptr)) return false;
+        all |= (uintptr_t)a.vals[c] | (uintptr_t)aa.b[c];
+    }
+    return !(all & 15);
+}
+
+// hj_launch_group_sum's grid: one workgroup per compute unit, no more than the rows have wave trips for
+int hj_launch_agg_group(const AggArgs &aa, int cus, hipStream_t stream)
+{
+    using namespace hj_group;
+    static_assert(hj_agg::MAX_AGGS == MAX_VALS && hj_agg::GROUP_BLOCK == BLOCK, "an aggregate is a slot word; the grouped road's geometry is group_sum_kernel's");
+    if (aa.g.n == 0) return HJGPU_OK;
+    if (!agg_args_valid(aa, 1, MAX_KEYS, cus)) return HJGPU_EINVAL;
+    const u64 nvec = (aa.g.n + 3) >> 2, need = (nvec + BLOCK - 1) / BLOCK;
+    const dim3 grid((uint32_t)std::min<u64>(need, (u64)cus));
+    hj_with_bool(aa.g.select_bits != nullptr, [&](auto sel) {
+        constexpr bool S = decltype(sel)::value;
+        if (aa.g.nkeys == 1) hipLaunchKernelGGL((agg_group_kernel<1, S>), grid, dim3(BLOCK), 0, stream, aa);
+        else hipLaunchKernelGGL((agg_group_kernel<2, S>), grid, dim3(BLOCK), 0, stream, aa);
+    });
+    return hipGetLastError() == hipSuccess ? HJGPU_OK : HJGPU_EHIP;
+}
+
+// agg_layout.hpp's scalar grid, no more workgroups than the rows have wave trips for
+int hj_launch_agg_scalar(const AggArgs &aa, int cus, hipStream_t stream)
+{
+    using namespace hj_agg;
+    if (aa.g.n == 0) return HJGPU_OK;
+    if (!agg_args_valid(aa, 0, 0, cus)) return HJGPU_EINVAL;
+    const u64 nvec = (aa.g.n + 3) >> 2, need = (nvec + SCALAR_BLOCK - 1) / SCALAR_BLOCK;
+    const dim3 grid((uint32_t)std::min<u64>(need, (u64)scalar_grid_of(cus)));
+    hj_with_bool(aa.g.select_bits != nullptr, [&](auto sel) {
+        constexpr bool S = decltype(sel)::value;
+        hipLaunchKernelGGL((agg_scalar_kernel<S>), grid, dim3(SCALAR_BLOCK), 0, stream, aa);
+    });
+    return hipGetLastError() == hipSuccess ? HJGPU_OK : HJGPU_EHIP;
+}
+
+int hj_launch_agg_emit(const AggEmitArgs &ae, int cus, hipStream_t stream)
+{
+    const GroupEmitArgs &a = ae.g;
+    if (!a.merge || !a.d_ngroups || a.nkeys > hj_group::MAX_KEYS || a.nvals > hj_agg::MAX_AGGS || cus < 1) return HJGPU_EINVAL;
+    const u64 need = (a.slots + 1 + 255) / 256;
+    hipLaunchKernelGGL(agg_emit_kernel, dim3((uint32_t)std::min<u64>(need, (u64)cus * 8)), dim3(256), 0, stream, ae);
+    return hipGetLastError() == hipSuccess ? HJGPU_OK : HJGPU_EHIP;
+}
+
 // ---- filter (hjgpu_filter_selected; DESIGN.md section 5 "Filter") -----------------------------------------------------------------------
 // Range predicates over columns into a bitmap: row i passes when it is selected and, for every p < NPREDS, filter_layout.hpp's passes()
 // holds on cols[p][i].  One persistent grid; an iteration is BATCH wave trips of hj_lookup.hpp's layout (lane L owns rows 4 L ... 4 L + 3

@@ -5,6 +5,7 @@
 #include <stdint.h>
 #include <type_traits>
 #include "../../include/hjgpu.h"
+#include "agg_layout.hpp"
 #include "compact_layout.hpp"
 #include "filter_layout.hpp"
 #include "gather_layout.hpp"
@@ -523,6 +524,24 @@ struct GroupEmitArgs {
 };
 int hj_launch_group_sum(const GroupArgs &a, int cus, hipStream_t stream);
 int hj_launch_group_emit(const GroupEmitArgs &a, int cus, hipStream_t stream);
+
+// Aggregate functions (hjgpu_group_agg*, gen_kernels.hip; DESIGN.md section 5 "Aggregate functions"): hj_launch_group_sum's tables and
+// pre-conditions - g.vals[c] is aggregate c's column a, g.nvals the number of aggregates - with agg_layout.hpp's function per slot word.
+// hj_launch_agg_group: g.nkeys 1 or 2, group_sum_kernel's grid.  hj_launch_agg_scalar: g.nkeys 0, no key is read and every selected row
+// goes to the slot of tuple 0 (merge[merge_mask + 1]); agg_layout.hpp's scalar grid.  hj_launch_agg_emit: hj_launch_group_emit with
+// nkeys 0 to 2 and the words of the extremes turned back into the columns' values.
+struct AggArgs {
+    GroupArgs g;
+    const uint32_t *b[hj_agg::MAX_AGGS]; // SUM_MUL: the second factor's column
+    uint32_t fn[hj_agg::MAX_AGGS], flags[hj_agg::MAX_AGGS];
+};
+struct AggEmitArgs {
+    GroupEmitArgs g;
+    uint32_t fn[hj_agg::MAX_AGGS], flags[hj_agg::MAX_AGGS];
+};
+int hj_launch_agg_group(const AggArgs &a, int cus, hipStream_t stream);
+int hj_launch_agg_scalar(const AggArgs &a, int cus, hipStream_t stream);
+int hj_launch_agg_emit(const AggEmitArgs &a, int cus, hipStream_t stream);
 
 // Filter (hjgpu_filter_selected*, gen_kernels.hip; DESIGN.md section 5 "Filter"): one persistent grid of filter_layout.hpp's geometry.  Row
 // i < n passes when it is selected (select_bits NULL: every row) and preds[p] holds on cols[p][i] for every p < npreds; bits_out (NULL:

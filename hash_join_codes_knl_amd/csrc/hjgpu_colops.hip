@@ -1,4 +1,4 @@
-// hjgpu_colops.hip - the column operators of include/hjgpu.h over a bitmap's rows: hjgpu_compact_selected, hjgpu_group_sum,
+// hjgpu_colops.hip - the column operators of include/hjgpu.h over a bitmap's rows: hjgpu_compact_selected, hjgpu_group_sum, hjgpu_group_agg,
 // hjgpu_filter_selected, hjgpu_gather_selected and their _async forms.  What they refuse from their arguments alone is
 // colop_checks.hpp; their kernels are gen_kernels.hip's.  The blocking and the enqueue-only form of an operator are ONE path (X_call): they
 // differ in where the count words lie - the context's, or the caller's in device memory - and in the blocking form's tail.
@@ -121,6 +121,57 @@ static int group_call(hjgpu_ctx *ctx, const GroupCall &g, uint64_t *ngroups, boo
     return HJGPU_OK;
 }
 
+// ---- aggregate functions ----------------------------------------------------------
+// group_enqueue's three enqueues and its stats mapping; the aggregation is the grouped road (nkeys 1 or 2) or the scalar road (nkeys 0:
+// every selected row goes to the slot of tuple 0, which the emit turns into J = 0 or 1)
+static int group_agg_enqueue(hjgpu_ctx *ctx, const GroupAggCall &g, u64 *d_ngroups, hipStream_t stream)
+{
+    const u64 slots = hj_group::merge_slots(g.capacity);
+    char *ws = reinterpret_cast<char *>(ctx->group.p);
+    begin_span(ctx, ALGO_GROUP_AGG, stream);
+    HIPCHK(ctx, hj_zero_async(d_ngroups, sizeof(u64), stream));
+    if (g.n) HIPCHK(ctx, hj_zero_async(ws + sizeof(u64), (size_t)(hj_group::workspace_bytes(slots) - sizeof(u64)), stream));
+    record(ctx, EV_S_HIST, stream);
+    if (g.n) {
+        AggArgs a{};
+        a.g.select_bits = g.bits; a.g.n = g.n; a.g.nkeys = g.nkeys; a.g.nvals = g.naggs;
+        for (uint32_t c = 0; c < g.nkeys; ++c) a.g.keys[c] = g.keys_in[c];
+        for (uint32_t c = 0; c < g.naggs; ++c) { a.g.vals[c] = g.aggs[c].d_a; a.b[c] = g.aggs[c].d_b; a.fn[c] = g.aggs[c].fn; a.flags[c] = g.aggs[c].flags; }
+        a.g.merge = reinterpret_cast<hj_group::Slot *>(ws + hj_group::WORKSPACE_HEAD);
+        a.g.merge_mask = slots - 1;
+        a.g.overflow = reinterpret_cast<uint32_t *>(ws + sizeof(u64));
+        CHK(g.nkeys ? hj_launch_agg_group(a, ctx->cus, stream) : hj_launch_agg_scalar(a, ctx->cus, stream));
+    }
+    record(ctx, EV_JOIN, stream);
+    if (g.n) {
+        AggEmitArgs e{};
+        e.g.merge = reinterpret_cast<const hj_group::Slot *>(ws + hj_group::WORKSPACE_HEAD);
+        e.g.slots = slots; e.g.nkeys = g.nkeys; e.g.nvals = g.naggs; e.g.capacity = g.capacity; e.g.counts_out = reinterpret_cast<u64 *>(g.counts_out);
+        for (uint32_t c = 0; c < g.nkeys; ++c) e.g.keys_out[c] = g.keys_out[c];
+        for (uint32_t c = 0; c < g.naggs; ++c) { e.g.sums_out[c] = reinterpret_cast<u64 *>(g.aggs_out[c]); e.fn[c] = g.aggs[c].fn; e.flags[c] = g.aggs[c].flags; }
+        e.g.d_ngroups = d_ngroups;
+        CHK(hj_launch_agg_emit(e, ctx->cus, stream));
+    }
+    record(ctx, EV_GAPS, stream);
+    return HJGPU_OK;
+}
+
+// group_call's workspace, shared with hjgpu_group_sum: one context runs one call at a time, and the clears are ordered by the stream
+static int group_agg_call(hjgpu_ctx *ctx, const GroupAggCall &g, uint64_t *ngroups, bool device_count, void *stream_)
+{
+    if (!ctx) return HJGPU_EINVAL;
+    hipStream_t stream = (hipStream_t)stream_;
+    CHK(colop_begin(ctx, check_group_agg(g, ngroups, device_count), stream, ctx->group, (size_t)hj_group::workspace_bytes(hj_group::merge_slots(g.capacity))));
+    u64 *d_ngroups = reinterpret_cast<u64 *>(device_count ? (void *)ngroups : ctx->group.p);
+    CHK(group_agg_enqueue(ctx, g, d_ngroups, stream));
+    if (device_count) return HJGPU_OK;
+    u64 got[2];
+    CHK(read_back(ctx, d_ngroups, 1, got, ngroups, stream));
+    if (got[0] > g.capacity)
+        return fail(ctx, HJGPU_EOVERFLOW, "hjgpu_group_agg: more groups than capacity (*ngroups holds a lower bound of their number that exceeds capacity; the outputs are unspecified)");
+    return HJGPU_OK;
+}
+
 // ---- filter -----------------------------------------------------------------------
 // the two enqueues: the clear of the count word (d_count NULL: none), the kernel (n == 0: none).  hjgpu_get_stats afterwards: ms_histogram =
 // the clear, ms_join = the kernel, ms_total = both
@@ -217,6 +268,20 @@ int hjgpu_group_sum(hjgpu_ctx *ctx, const uint32_t *d_select_bits, size_t n, uin
                     uint64_t *const *d_sums_out, size_t capacity, uint64_t *ngroups, void *stream)
 {
     return group_call(ctx, {d_select_bits, n, nkeys, nvals, d_keys_in, d_vals_in, d_keys_out, d_counts_out, d_sums_out, capacity}, ngroups, false, stream);
+}
+
+int hjgpu_group_agg_async(hjgpu_ctx *ctx, const uint32_t *d_select_bits, size_t n, uint32_t nkeys, const uint32_t *const *d_keys_in,
+                          uint32_t naggs, const hjgpu_aggregate *aggs, uint32_t *const *d_keys_out, uint64_t *d_counts_out,
+                          uint64_t *const *d_aggs_out, size_t capacity, uint64_t *d_ngroups, void *stream)
+{
+    return group_agg_call(ctx, {d_select_bits, n, nkeys, naggs, d_keys_in, aggs, d_keys_out, d_counts_out, d_aggs_out, capacity}, d_ngroups, true, stream);
+}
+
+int hjgpu_group_agg(hjgpu_ctx *ctx, const uint32_t *d_select_bits, size_t n, uint32_t nkeys, const uint32_t *const *d_keys_in,
+                    uint32_t naggs, const hjgpu_aggregate *aggs, uint32_t *const *d_keys_out, uint64_t *d_counts_out,
+                    uint64_t *const *d_aggs_out, size_t capacity, uint64_t *ngroups, void *stream)
+{
+    return group_agg_call(ctx, {d_select_bits, n, nkeys, naggs, d_keys_in, aggs, d_keys_out, d_counts_out, d_aggs_out, capacity}, ngroups, false, stream);
 }
 
 int hjgpu_filter_selected_async(hjgpu_ctx *ctx, const uint32_t *d_select_bits, size_t n, uint32_t npreds, const uint32_t *const *d_cols,

@@ -286,7 +286,8 @@ int  hjgpu_get_stats(hjgpu_ctx *ctx, hjgpu_stats *stats);
  *                      merge table in device memory
  *   "filter_step_rows" the rows that hjgpu_filter_selected's whole grid covers in one iteration of its loop (the grid is smaller when the
  *                      rows are fewer)
- *   "gather_step_rows" the same for hjgpu_gather_selected */
+ *   "gather_step_rows" the same for hjgpu_gather_selected
+ *   "agg_step_rows", "agg_scalar_step_rows"   the same for hjgpu_group_agg with key columns and without (nkeys == 0) */
 int  hjgpu_get_counter(hjgpu_ctx *ctx, const char *name, uint64_t *value);
 
 /* ---- device memory helpers for hosts that do not link HIP (mamalloc/free,
@@ -651,6 +652,50 @@ int  hjgpu_group_sum(hjgpu_ctx *ctx, const uint32_t *d_select_bits, size_t n,
 int  hjgpu_group_sum_async(hjgpu_ctx *ctx, const uint32_t *d_select_bits, size_t n,
                            uint32_t nkeys, const uint32_t *const *d_keys_in, uint32_t nvals, const uint32_t *const *d_vals_in,
                            uint32_t *const *d_keys_out, uint64_t *d_counts_out, uint64_t *const *d_sums_out,
+                           size_t capacity, uint64_t *d_ngroups, void *stream);
+
+/* ---- aggregate functions: GROUP BY nothing, one or two columns; COUNT(*) and up to four of SUM(a), SUM(a * b), MIN(a), MAX(a) -------
+ * hjgpu_group_sum's contract, word for word, wherever the two meet: d_select_bits (and NULL: every row), every key value legal and the
+ * groups in unspecified order, n == 0, the count, overflow and *ngroups, alignment, the overlap refusals, the capturing stream, refusals
+ * decided from the arguments alone before anything is allocated or enqueued, the untouched async status, calls queued back to back on
+ * one stream.  On top of it:
+ *   nkeys            0, 1 or 2 (more: HJGPU_EINVAL).  nkeys == 0 is the scalar aggregate - no GROUP BY: J is 1 when at least one row is
+ *                    selected and 0 when none is (a group has at least one row, as everywhere in the library), the one row of outputs is
+ *                    index 0, d_keys_in and d_keys_out may be NULL, and capacity == 0 with J == 1 is HJGPU_EOVERFLOW.
+ *   aggs             a HOST array of naggs hjgpu_aggregate, copied by value; naggs is 0 to HJGPU_AGG_MAX_AGGS (0: the counts alone; aggs
+ *                    and d_aggs_out may then be NULL).  HJGPU_EINVAL, each with a text that names the aggregate's index: fn > 3, a flag
+ *                    bit outside HJGPU_AGG_SIGNED, d_a == NULL, d_b == NULL under HJGPU_AGG_SUM_MUL, d_b != NULL under any other fn, a
+ *                    NULL d_aggs_out entry.  d_a may equal d_b (a sum of squares); a column may appear in several aggregates and also
+ *                    as a key.  Columns hold n uint32 (int32 under HJGPU_AGG_SIGNED), 16-byte aligned.
+ *   d_aggs_out       a HOST array of naggs device pointers; d_aggs_out[c] holds capacity uint64, and for group j
+ *                      HJGPU_AGG_SUM      the sum of a modulo 2^64; a is zero-extended, or sign-extended under HJGPU_AGG_SIGNED (the
+ *                                         caller then reads the word as int64);
+ *                      HJGPU_AGG_SUM_MUL  the sum modulo 2^64 of the exact product per row: uint32 x uint32 -> uint64, or
+ *                                         int32 x int32 -> int64 under HJGPU_AGG_SIGNED;
+ *                      HJGPU_AGG_MIN/MAX  the extreme of a in unsigned order, zero-extended; under HJGPU_AGG_SIGNED the extreme in int32
+ *                                         order, sign-extended.
+ *                    HJGPU_NULL_VAL in a looked-up column is the ordinary value 0xFFFFFFFF, as it is for the filter.
+ *   d_counts_out     capacity uint64, or NULL: no counts.
+ * The workspace is hjgpu_group_sum's merge table in the context (one context runs one call at a time).  Three enqueues ordered by the
+ * stream - the clears, the aggregation, the emit - and no workgroup waits for another; with keys the aggregation is hjgpu_group_sum's
+ * (LDS tables, then the merge table), without keys every lane aggregates in registers and a workgroup adds its totals to one slot.
+ * hjgpu_get_stats afterwards: hjgpu_group_sum's mapping (ms_histogram = the clears, ms_join = the aggregation, ms_close_gaps = the emit).
+ * hjgpu_get_counter "agg_step_rows" / "agg_scalar_step_rows": the rows one loop iteration of the whole grid covers with / without keys.
+ * Plain unsigned sums of a GROUP BY are hjgpu_group_sum's job as much as this one's: the results are the same. */
+#define HJGPU_AGG_SUM      0u   /* SUM(a)                                                        */
+#define HJGPU_AGG_SUM_MUL  1u   /* SUM(a * b): the exact 64-bit product of the two 32-bit values */
+#define HJGPU_AGG_MIN      2u   /* MIN(a)                                                        */
+#define HJGPU_AGG_MAX      3u   /* MAX(a)                                                        */
+#define HJGPU_AGG_SIGNED   1u   /* flags: a (and b) are int32                                    */
+#define HJGPU_AGG_MAX_AGGS 4u
+typedef struct { uint32_t fn, flags; const uint32_t *d_a, *d_b; } hjgpu_aggregate;
+int  hjgpu_group_agg(hjgpu_ctx *ctx, const uint32_t *d_select_bits, size_t n,
+                     uint32_t nkeys, const uint32_t *const *d_keys_in, uint32_t naggs, const hjgpu_aggregate *aggs,
+                     uint32_t *const *d_keys_out, uint64_t *d_counts_out, uint64_t *const *d_aggs_out,
+                     size_t capacity, uint64_t *ngroups, void *stream);
+int  hjgpu_group_agg_async(hjgpu_ctx *ctx, const uint32_t *d_select_bits, size_t n,
+                           uint32_t nkeys, const uint32_t *const *d_keys_in, uint32_t naggs, const hjgpu_aggregate *aggs,
+                           uint32_t *const *d_keys_out, uint64_t *d_counts_out, uint64_t *const *d_aggs_out,
                            size_t capacity, uint64_t *d_ngroups, void *stream);
 
 /* ---- whole joins on HBM-resident columns (replace run()/run_hj()) ---------------- */
