@@ -52,6 +52,7 @@ EXPORTS = [
     "hjgpu_compact_selected", "hjgpu_compact_selected_async",
     "hjgpu_group_sum", "hjgpu_group_sum_async",
     "hjgpu_group_agg", "hjgpu_group_agg_async",
+    "hjgpu_group_by", "hjgpu_group_by_async",
     "hjgpu_npj", "hjgpu_phj", "hjgpu_cpra",
     "hjgpu_npj_async", "hjgpu_phj_async", "hjgpu_cpra_async", "hjgpu_phj_overlapped_async",
     "hjgpu_phj_build", "hjgpu_phj_probe", "hjgpu_phj_probe_async",
@@ -310,6 +311,8 @@ def load_library(build_if_missing=True):
     agg = [vp, vp, sz, u32, C.POINTER(vp), u32, C.POINTER(Aggregate), C.POINTER(vp), vp, C.POINTER(vp), sz]
     L.hjgpu_group_agg.argtypes = agg + [u64p, vp]
     L.hjgpu_group_agg_async.argtypes = agg + [vp, vp]
+    L.hjgpu_group_by.argtypes = agg + [u64p, vp]
+    L.hjgpu_group_by_async.argtypes = agg + [vp, vp]
     L.hjgpu_npj_lookup_table_selected.argtypes = [vp, vp, sz, vp, sz, u32, vp, vp, vp, C.POINTER(Result), vp]
     join = [vp, vp, vp, sz, vp, vp, sz]
     L.hjgpu_npj.argtypes = join + [C.POINTER(NpjParams), C.POINTER(Result), C.POINTER(Output), vp]
@@ -477,7 +480,9 @@ class HjGpu:
         "compact_ranges" / "compact_chunk_rows" (compact_selected's geometry: its ranges, and the rows of a chunk),
         "group_lds_groups" (the distinct groups a workgroup's LDS table of group_sum holds before further ones go to device memory),
         "filter_step_rows" / "gather_step_rows" (the rows filter_selected's / gather_selected's whole grid covers in one iteration of its
-        loop), "agg_step_rows" / "agg_scalar_step_rows" (the same for group_agg with key columns / without)."""
+        loop), "agg_step_rows" / "agg_scalar_step_rows" (the same for group_agg with key columns / without),
+        "group_by_lds_groups" / "group_by_step_rows" (group_by with three and four key columns: the distinct groups a workgroup's wide LDS
+        table holds, and the rows its whole grid covers in one iteration of its loop)."""
         v = C.c_uint64()
         self._check(self.lib.hjgpu_get_counter(self.handle, name.encode(), C.byref(v)))
         return v.value
@@ -713,12 +718,12 @@ class HjGpu:
                                                    self._ptr(d_ngroups), stream))
 
     # ---- aggregate functions: GROUP BY nothing, one or two keys; COUNT(*), SUM(a), SUM(a * b), MIN(a), MAX(a) ----------------------
-    def _agg_args(self, keys_in, aggs, keys_out, aggs_out, counts_out, capacity):
+    def _agg_args(self, keys_in, aggs, keys_out, aggs_out, counts_out, capacity, who="group_agg"):
         keys_in, aggs, keys_out, aggs_out = list(keys_in or ()), list(aggs or ()), list(keys_out or ()), list(aggs_out or ())
         if len(keys_in) != len(keys_out) or len(aggs) != len(aggs_out):
-            raise ValueError("group_agg: %d key columns with %d outputs, %d aggregates with %d outputs"
-                             % (len(keys_in), len(keys_out), len(aggs), len(aggs_out)))
-        capacity = self._default_capacity(capacity, keys_out + aggs_out + ([counts_out] if counts_out is not None else []), "group_agg")
+            raise ValueError("%s: %d key columns with %d outputs, %d aggregates with %d outputs"
+                             % (who, len(keys_in), len(keys_out), len(aggs), len(aggs_out)))
+        capacity = self._default_capacity(capacity, keys_out + aggs_out + ([counts_out] if counts_out is not None else []), who)
         rows = []
         for g in aggs:                                                  # (fn, a[, b[, flags]]) or an Aggregate
             if not isinstance(g, Aggregate):
@@ -747,6 +752,24 @@ class HjGpu:
         nk, kin, na, ag, kout, cout, aout, capacity = self._agg_args(keys_in, aggs, keys_out, aggs_out, counts_out, capacity)
         self._check(self.lib.hjgpu_group_agg_async(self.handle, self._ptr(select_bits), n, nk, kin, na, ag, kout, cout, aout, capacity,
                                                    self._ptr(d_ngroups), stream))
+
+    # ---- GROUP BY up to four key columns ----------------------------------------------------------------------------------------------
+    def group_by(self, select_bits, n, keys_in, aggs, keys_out, aggs_out, counts_out=None, capacity=None, stream=None):
+        """hjgpu_group_by: group_agg with up to four keys_in columns.  No, one or two of them are group_agg itself; three and four take
+        the wide tables, in which every key value stays legal in every column.  Returns J; J > capacity (default: the shortest output)
+        raises HjGpuError(HJGPU_EOVERFLOW) that carries .count; the outputs are unspecified then."""
+        nk, kin, na, ag, kout, cout, aout, capacity = self._agg_args(keys_in, aggs, keys_out, aggs_out, counts_out, capacity, "group_by")
+        count = C.c_uint64()
+        self._check(self.lib.hjgpu_group_by(self.handle, self._ptr(select_bits), n, nk, kin, na, ag, kout, cout, aout, capacity,
+                                            C.byref(count), stream), count=count.value)
+        return count.value
+
+    def group_by_async(self, select_bits, n, keys_in, aggs, keys_out, aggs_out, counts_out, capacity, d_ngroups, stream=None):
+        """hjgpu_group_by_async: enqueue only; the number of groups goes to d_ngroups (uint64 in device memory), which the caller
+        compares with capacity (None: the shortest output)"""
+        nk, kin, na, ag, kout, cout, aout, capacity = self._agg_args(keys_in, aggs, keys_out, aggs_out, counts_out, capacity, "group_by")
+        self._check(self.lib.hjgpu_group_by_async(self.handle, self._ptr(select_bits), n, nk, kin, na, ag, kout, cout, aout, capacity,
+                                                  self._ptr(d_ngroups), stream))
 
     # ---- whole joins ------------------------------------------------------------------
     def _join(self, fn, params, rk, rv, inner, sk, sv, outer, out, stream):

@@ -1,4 +1,4 @@
-// colop_checks.hpp - what the column operators (hjgpu_compact_selected, hjgpu_group_sum, hjgpu_group_agg, hjgpu_filter_selected, hjgpu_gather_selected: hjgpu_colops.hip)
+// colop_checks.hpp - what the column operators (hjgpu_compact_selected, hjgpu_group_sum, hjgpu_group_agg, hjgpu_group_by, hjgpu_filter_selected, hjgpu_gather_selected: hjgpu_colops.hip)
 // and the selected look-ups refuse from their arguments alone, before anything is allocated or enqueued (DESIGN.md section 5 "Argument checks
 // of the column operators").  Plain host C++, no HIP and no context: a check returns {status, text}, its caller hands that to fail().
 // tests/test_colop_checks.py compiles it with g++ and compares every decision with the hand-written checkers it replaced.
@@ -14,6 +14,7 @@
 
 #include "../../include/hjgpu.h"
 #include "group_layout.hpp"
+#include "wide_group_layout.hpp"
 
 namespace colop {
 
@@ -52,9 +53,9 @@ struct Operand {
     int in_place;                                       // a written operand: the read operand it may coincide with exactly, or -1
 };
 
-// the largest table, hjgpu_group_agg_async's: the mask, 2 keys, 4 aggregates' a and b, 2 key outputs, 4 aggregate outputs, the counts and
-// the count word (19; a compaction has the mask, 8 inputs, 8 outputs and the row numbers: 18)
-constexpr int MAX_OPERANDS = 1 + 2 * HJGPU_GROUP_MAX_KEYS + 3 * HJGPU_AGG_MAX_AGGS + 2;
+// the largest table, hjgpu_group_by_async's: the mask, 4 keys, 4 aggregates' a and b, 4 key outputs, 4 aggregate outputs, the counts and
+// the count word (23; a compaction has the mask, 8 inputs, 8 outputs and the row numbers: 18)
+constexpr int MAX_OPERANDS = 1 + 2 * HJGPU_GROUP_BY_MAX_KEYS + 3 * HJGPU_AGG_MAX_AGGS + 2;
 static_assert(MAX_OPERANDS >= 2 * HJGPU_COMPACT_MAX_COLS + 2, "the operand table holds a compaction's operands");
 
 struct Operands {
@@ -184,12 +185,13 @@ struct GroupAggCall {
     size_t capacity;
 };
 
-// check_group's head with nkeys == 0 legal (the scalar aggregate: the key arrays may then be NULL), then every aggregate by its index
-inline Verdict check_group_agg(const GroupAggCall &g, const uint64_t *ngroups, bool device_count)
+// check_group's head with nkeys == 0 legal (the scalar aggregate: the key arrays may then be NULL) and no more than max_keys key columns
+// (too_many_keys: the refusal's text), then every aggregate by its index
+inline Verdict check_keys_and_aggregates(const GroupAggCall &g, const uint64_t *ngroups, bool device_count, uint32_t max_keys, const char *too_many_keys)
 {
     if (!ngroups) return refuse(HJGPU_EINVAL, "null group count pointer");
     if (device_count && ((uintptr_t)ngroups & 7)) return refuse(HJGPU_EALIGN, "d_ngroups must be 8-byte aligned");
-    if (g.nkeys > HJGPU_GROUP_MAX_KEYS) return refuse(HJGPU_EINVAL, "nkeys must not exceed HJGPU_GROUP_MAX_KEYS (2)");
+    if (g.nkeys > max_keys) return refuse(HJGPU_EINVAL, "%s", too_many_keys);
     if (g.naggs > HJGPU_AGG_MAX_AGGS) return refuse(HJGPU_EINVAL, "naggs must not exceed HJGPU_AGG_MAX_AGGS (4)");
     if (hj_group::merge_slots(g.capacity) == 0) return refuse(HJGPU_EINVAL, "capacity must not exceed 2^40 groups");
     if (g.n == 0) return no_objection();                      // nothing is read, nothing but the count is written: anything else may be NULL
@@ -216,6 +218,19 @@ inline Verdict check_group_agg(const GroupAggCall &g, const uint64_t *ngroups, b
     t.write(g.counts_out, g.capacity * sizeof(uint64_t), 16, "d_counts_out");
     if (device_count) t.write(ngroups, sizeof(uint64_t), 8, "d_ngroups");
     return check_operands(t);
+}
+
+inline Verdict check_group_agg(const GroupAggCall &g, const uint64_t *ngroups, bool device_count)
+{
+    return check_keys_and_aggregates(g, ngroups, device_count, HJGPU_GROUP_MAX_KEYS, "nkeys must not exceed HJGPU_GROUP_MAX_KEYS (2)");
+}
+
+// ---- hjgpu_group_by -------------------------------------------------------------------------------------------------------------------------
+// check_group_agg with up to four key inputs and four key outputs (the capacity rule is the same for both table layouts)
+inline Verdict check_group_by(const GroupAggCall &g, const uint64_t *ngroups, bool device_count)
+{
+    static_assert(hj_wide::MAX_KEYS == HJGPU_GROUP_BY_MAX_KEYS && hj_wide::MAX_CAPACITY == hj_group::MAX_CAPACITY, "one capacity rule, four key words");
+    return check_keys_and_aggregates(g, ngroups, device_count, HJGPU_GROUP_BY_MAX_KEYS, "nkeys must not exceed HJGPU_GROUP_BY_MAX_KEYS (4)");
 }
 
 // ---- hjgpu_filter_selected ------------------------------------------------------------------------------------------------------------------

@@ -1173,6 +1173,265 @@ int hj_launch_agg_emit(const AggEmitArgs &ae, int cus, hipStream_t stream)
     return hipGetLastError() == hipSuccess ? HJGPU_OK : HJGPU_EHIP;
 }
 
+// ---- wide keys (hjgpu_group_by with three and four key columns; DESIGN.md section 5 "Wide keys") ---------------------------------------
+// GROUP BY (key 0, key 1, key 2 [, key 3]) COUNT(*) and hjgpu_group_agg's aggregates.  A tuple no longer fits the one 64-bit word that
+// group_lds_slot / group_merge_slot compare and swap, and there is no 128-bit compare-and-swap: the tables are wide_group_layout.hpp's -
+// a slot has a 64-bit word per key, key | 1 << 32, never 0 - and insert-or-find is that header's find_slot: word by word, a 64-bit
+// compare-and-swap 0 -> own word wherever a word is still 0 (ds_cmpst_rtn_b64 in LDS, global_atomic_cmpswap_x2 in the merge table), on to
+// the next slot at the first word that is another tuple's.  Nobody waits and no slot stays half filled.  The words of the aggregates and
+// their combines are agg_group_kernel's.
+
+// the two memories of find_slot: relaxed atomics of workgroup scope in LDS - `used` is group_lds_slot's ticket, taken before a slot's word
+// 0 is written and handed back when that write lost, so the table never holds more than LDS_GROUPS tuples - and of agent scope in the
+// merge table, where every slot may be claimed
+struct WideLdsMemory {
+    uint32_t *used;
+    __device__ __forceinline__ u64 load(const u64 *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
+    __device__ __forceinline__ u64 cas(u64 *p, u64 word) { return atomicCAS(p, 0ull, word); }                          // ds_cmpst_rtn_b64
+    __device__ __forceinline__ bool claim()
+    {
+        if (__hip_atomic_load(used, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) >= hj_wide::LDS_GROUPS) return false;  // (a broadcast read: no ticket traffic once the table is full)
+        if (atomicAdd(used, 1u) >= hj_wide::LDS_GROUPS) { atomicSub(used, 1u); return false; }
+        return true;
+    }
+    __device__ __forceinline__ void unclaim() { atomicSub(used, 1u); }
+};
+struct WideGlobalMemory {
+    __device__ __forceinline__ u64 load(const u64 *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+    __device__ __forceinline__ u64 cas(u64 *p, u64 word) { return atomicCAS(p, 0ull, word); }                          // global_atomic_cmpswap_x2
+    __device__ __forceinline__ bool claim() { return true; }
+    __device__ __forceinline__ void unclaim() {}
+};
+
+// The slot of the tuple with key words w (hash h) in the merge table: the walk bounded by the slot count; group_merge_slot's overflow rule -
+// a tuple that finds the table full raises the overflow word, whoever sees it raised gives up at once
+template <int NKEYS>
+__device__ __forceinline__ u64 wide_merge_slot(const WideArgs &a, const u64 (&w)[hj_wide::MAX_KEYS], u64 h)
+{
+    if (__hip_atomic_load(a.overflow, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return GROUP_NO_SLOT;
+    WideGlobalMemory mem;
+    const u64 s = hj_wide::find_slot<(uint32_t)NKEYS>(mem, a.merge, a.merge_mask, h, a.merge_mask + 1, w);
+    if (s == hj_wide::NO_SLOT) atomicOr(a.overflow, 1u);
+    return s;
+}
+
+// combines x into word `word` (0: the count, 1 + c: aggregate c) of the slot at `loc`: agg_combine over the wide slot
+__device__ __forceinline__ void wide_combine(hj_wide::Slot *tab, const WideArgs &a, u64 loc, uint32_t word, bool extreme, u64 x)
+{
+    if (loc & GROUP_IN_LDS) {
+        u64 *p = &tab[(uint32_t)loc].count + word;
+        if (extreme) __hip_atomic_fetch_max(p, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);                     // ds_max_u64
+        else __hip_atomic_fetch_add(p, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);                             // ds_add_u64
+    } else if (loc != GROUP_NO_SLOT) {
+        u64 *p = &a.merge[loc].count + word;
+        if (extreme) __hip_atomic_fetch_max(p, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);                         // global_atomic_umax_x2
+        else atomicAdd(p, x);                                                                                           // global_atomic_add_x2
+    }
+}
+
+// agg_group_kernel's iteration with NKEYS key columns: the mask words and key column 0 (lookup_fetch), then the further key columns and, per
+// aggregate, column a - and b under SUM_MUL - for the lanes whose nibble is not 0; everything non-temporal; the last, partial vector of a
+// column is loaded whole and masked by the nibble.  A lane folds those of its four rows that carry the same tuple onto leaders, the leaders
+// find their slots - the workgroup's table, else the merge table - by find_slot, and each leader's folded term goes to its slot.  The walk
+// over the leaders stays in the kernel's body (a helper that took the trips' vectors made the compiler index them in memory).  The flush
+// combines the workgroup's occupied slots into the merge table, word by word.  No global store; no workgroup waits for another.
+template <int NKEYS, bool SEL>
+__global__ __launch_bounds__(hj_wide::BLOCK) void wide_group_kernel(WideArgs a)
+{
+    using namespace hj_wide;
+    static_assert(NKEYS >= (int)MIN_KEYS && NKEYS <= (int)MAX_KEYS, "three or four key columns");
+    static_assert(NO_SLOT == GROUP_NO_SLOT, "one word for \"no slot\" in the walk and in the locations");
+    constexpr int ROWS = 4 * (int)BATCH, NB = (int)BATCH;
+    __shared__ Slot tab[LDS_SLOTS];
+    __shared__ uint32_t used;
+    const uint32_t tid = threadIdx.x;
+    {
+        u64 *raw = reinterpret_cast<u64 *>(tab);
+        for (uint32_t i = tid; i < LDS_SLOTS * (uint32_t)(sizeof(Slot) / 8); i += BLOCK) raw[i] = 0;
+        if (tid == 0) used = 0;
+    }
+    __syncthreads();
+    const u64 n = a.n, nvec = (n + 3) >> 2, stride = (u64)gridDim.x * BLOCK;
+    const uint32_t naggs = a.naggs;
+    for (u64 v0 = (u64)blockIdx.x * BLOCK + (tid & ~63u); v0 < nvec; v0 += stride * NB) {
+        uint32_t nib[NB];
+        uint32_t key[NKEYS][ROWS];                      // key column c of row 4 u + j of the lane
+        {
+            uint4 k0[NB];
+            lookup_fetch<SEL, NB, true>(a.select_bits, reinterpret_cast<const uint4 *>(a.keys[0]), v0, stride, n, nib, k0);
+#pragma unroll
+            for (int u = 0; u < NB; ++u) { key[0][4 * u] = k0[u].x; key[0][4 * u + 1] = k0[u].y; key[0][4 * u + 2] = k0[u].z; key[0][4 * u + 3] = k0[u].w; }
+        }
+#pragma unroll
+        for (int c = 1; c < NKEYS; ++c) {
+            const uint4 *k4 = reinterpret_cast<const uint4 *>(a.keys[c]);
+#pragma unroll
+            for (int u = 0; u < NB; ++u) {
+                uint4 kc = make_uint4(0, 0, 0, 0);
+                if (nib[u]) kc = hj_load_nt(k4 + v0 + (u64)u * stride + hj_lane());
+                key[c][4 * u] = kc.x; key[c][4 * u + 1] = kc.y; key[c][4 * u + 2] = kc.z; key[c][4 * u + 3] = kc.w;
+            }
+        }
+        // the fold: row q = 4 u + j of the lane leads the rows of its trip that carry its tuple and that no earlier row leads
+        u64 loc[ROWS];
+        uint32_t cls = 0, lead = 0;                     // cls: a nibble per row, the rows (of its trip) it leads; lead: the rows that lead any
+#pragma unroll
+        for (int u = 0; u < NB; ++u) {
+            uint32_t left = nib[u];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                loc[4 * u + j] = GROUP_NO_SLOT;
+                uint32_t m = 0;
+#pragma unroll
+                for (int i = j; i < 4; ++i) {
+                    bool same = true;
+#pragma unroll
+                    for (int c = 0; c < NKEYS; ++c) same = same && key[c][4 * u + i] == key[c][4 * u + j];
+                    if (((left >> i) & 1u) && same) m |= 1u << i;
+                }
+                if (!((left >> j) & 1u)) m = 0;
+                left &= ~m;
+                cls |= m << (4 * (4 * u + j));
+                lead |= (m ? 1u : 0u) << (4 * u + j);
+            }
+        }
+        // the leaders' slots and counts: one copy of the walk, whichever row it serves
+        for (uint32_t work = lead; work; work &= work - 1) {
+            const uint32_t q = __ffs(work) - 1;
+            u64 w[MAX_KEYS] = {0, 0, 0, 0};
+#pragma unroll
+            for (int c = 0; c < NKEYS; ++c) {
+                uint32_t kq = key[c][0];
+#pragma unroll
+                for (int r = 1; r < ROWS; ++r) kq = q == r ? key[c][r] : kq;
+                w[c] = key_word(kq);
+            }
+            const u64 h = hash(w);
+            WideLdsMemory lds{&used};
+            u64 at = find_slot<(uint32_t)NKEYS>(lds, tab, LDS_SLOTS - 1, lds_home(h), LDS_PROBES, w);
+            if (at != NO_SLOT) at |= GROUP_IN_LDS;
+            else at = wide_merge_slot<NKEYS>(a, w, h);
+            wide_combine(tab, a, at, 0, false, (u64)__popc((cls >> (4 * q)) & 15u));
+#pragma unroll
+            for (int r = 0; r < ROWS; ++r) loc[r] = q == r ? at : loc[r];
+        }
+        for (uint32_t c = 0; c < naggs; ++c) {
+            const uint32_t fn = a.fn[c];
+            const hj_agg::Norm norm = hj_agg::normalise(fn, a.flags[c]);
+            const uint4 *x4 = reinterpret_cast<const uint4 *>(a.a[c]);
+            const uint4 *y4 = reinterpret_cast<const uint4 *>(a.b[c]);
+            uint4 x[NB], y[NB];
+#pragma unroll
+            for (int u = 0; u < NB; ++u) {
+                x[u] = make_uint4(0, 0, 0, 0);
+                if (nib[u]) x[u] = hj_load_nt(x4 + v0 + (u64)u * stride + hj_lane());
+            }
+#pragma unroll
+            for (int u = 0; u < NB; ++u) {
+                y[u] = make_uint4(0, 0, 0, 0);
+                if (fn == hj_agg::SUM_MUL && nib[u]) y[u] = hj_load_nt(y4 + v0 + (u64)u * stride + hj_lane());
+            }
+            const bool extreme = hj_agg::is_extreme(fn);
+            for (uint32_t work = lead; work; work &= work - 1) {
+                const uint32_t q = __ffs(work) - 1, m = (cls >> (4 * q)) & 15u;
+                uint4 xq = x[0], yq = y[0];
+#pragma unroll
+                for (int u = 1; u < NB; ++u) if ((int)(q >> 2) == u) { xq = x[u]; yq = y[u]; }
+                u64 at = loc[0];
+#pragma unroll
+                for (int r = 1; r < ROWS; ++r) at = q == r ? loc[r] : at;
+                wide_combine(tab, a, at, 1 + c, extreme, agg_fold_of(fn, norm, m, xq, yq));
+            }
+        }
+    }
+    __syncthreads();
+    for (uint32_t i = tid; i < LDS_SLOTS; i += BLOCK) {
+        if (tab[i].key[0] == 0) continue;
+        u64 w[MAX_KEYS] = {0, 0, 0, 0};
+#pragma unroll
+        for (int c = 0; c < NKEYS; ++c) w[c] = tab[i].key[c];
+        const u64 at = wide_merge_slot<NKEYS>(a, w, hash(w));
+        if (at != GROUP_NO_SLOT) {
+            atomicAdd(&a.merge[at].count, tab[i].count);
+            for (uint32_t c = 0; c < naggs; ++c) {
+                if (hj_agg::is_extreme(a.fn[c])) __hip_atomic_fetch_max(&a.merge[at].aggs[c], tab[i].aggs[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                else atomicAdd(&a.merge[at].aggs[c], tab[i].aggs[c]);
+            }
+        }
+    }
+}
+
+// agg_emit_kernel over wide slots: a slot is occupied when its key word 0 is not 0; a wave's occupied slots go to the dense outputs through
+// one atomic add to the cursor, which is the count word itself (0 before the launch); rows at capacity and beyond are counted and not
+// written.  Key column c is the low half of key word c
+__global__ __launch_bounds__(256) void wide_emit_kernel(WideEmitArgs a)
+{
+    const uint32_t lane = hj_lane();
+    const u64 stride = (u64)gridDim.x * 256;
+    for (u64 i0 = (u64)blockIdx.x * 256 + (threadIdx.x & ~63u); i0 < a.slots; i0 += stride) {
+        const u64 i = i0 + lane;
+        u64 w0 = 0;
+        if (i < a.slots) w0 = a.merge[i].key[0];
+        const bool occ = w0 != 0;
+        const u64 vote = __ballot(occ);
+        if (vote == 0) continue;
+        u64 base = 0;
+        if (lane == 0) base = atomicAdd(a.d_ngroups, (u64)__popcll(vote));
+        base = hj_uniform(base);
+        const u64 j = base + __popcll(vote & ((1ull << lane) - 1ull));
+        if (occ && j < a.capacity) {
+            hj_store(a.keys_out[0] + j, hj_wide::key_of(w0));
+#pragma unroll
+            for (uint32_t c = 1; c < hj_wide::MAX_KEYS; ++c)
+                if (c < a.nkeys) hj_store(a.keys_out[c] + j, hj_wide::key_of(a.merge[i].key[c]));
+            if (a.counts_out) hj_store(a.counts_out + j, a.merge[i].count);
+#pragma unroll
+            for (uint32_t c = 0; c < hj_wide::MAX_AGGS; ++c)
+                if (c < a.naggs) hj_store(a.aggs_out[c] + j, hj_agg::result(a.fn[c], a.flags[c], a.merge[i].aggs[c]));
+        }
+    }
+}
+
+// agg_args_valid for the wide road
+static bool wide_args_valid(const WideArgs &a, int cus)
+{
+    if (a.nkeys < hj_wide::MIN_KEYS || a.nkeys > hj_wide::MAX_KEYS || a.naggs > hj_wide::MAX_AGGS || !a.merge || !a.overflow || (a.merge_mask & (a.merge_mask + 1)) || cus < 1) return false;
+    uintptr_t all = (uintptr_t)a.select_bits;
+    for (uint32_t c = 0; c < a.nkeys; ++c) { if (!a.keys[c]) return false; all |= (uintptr_t)a.keys[c]; }
+    for (uint32_t c = 0; c < a.naggs; ++c) {
+        if (a.fn[c] > hj_agg::MAX || (a.flags[c] & ~hj_agg::SIGNED) || !a.a[c] || (a.fn[c] == hj_agg::SUM_MUL) != (a.b[c] != nullptr)) return false;
+        all |= (uintptr_t)a.a[c] | (uintptr_t)a.b[c];
+    }
+    return !(all & 15);
+}
+
+// hj_launch_agg_group's grid: one workgroup per compute unit (its table takes most of the unit's LDS), no more than the rows have wave trips for
+int hj_launch_wide_group(const WideArgs &a, int cus, hipStream_t stream)
+{
+    using namespace hj_wide;
+    static_assert(MAX_AGGS == hj_agg::MAX_AGGS && LDS_BYTES <= LDS_BUDGET, "an aggregate is a slot word; the table fits a compute unit's LDS");
+    if (a.n == 0) return HJGPU_OK;
+    if (!wide_args_valid(a, cus)) return HJGPU_EINVAL;
+    const u64 nvec = (a.n + 3) >> 2, need = (nvec + BLOCK - 1) / BLOCK;
+    const dim3 grid((uint32_t)std::min<u64>(need, (u64)cus));
+    hj_with_bool(a.select_bits != nullptr, [&](auto sel) {
+        constexpr bool S = decltype(sel)::value;
+        if (a.nkeys == 3) hipLaunchKernelGGL((wide_group_kernel<3, S>), grid, dim3(BLOCK), 0, stream, a);
+        else hipLaunchKernelGGL((wide_group_kernel<4, S>), grid, dim3(BLOCK), 0, stream, a);
+    });
+    return hipGetLastError() == hipSuccess ? HJGPU_OK : HJGPU_EHIP;
+}
+
+int hj_launch_wide_emit(const WideEmitArgs &a, int cus, hipStream_t stream)
+{
+    if (!a.merge || !a.d_ngroups || a.nkeys < hj_wide::MIN_KEYS || a.nkeys > hj_wide::MAX_KEYS || a.naggs > hj_wide::MAX_AGGS || (a.slots & (a.slots - 1)) || !a.slots || cus < 1) return HJGPU_EINVAL;
+    for (uint32_t c = 0; c < a.nkeys; ++c) if (!a.keys_out[c]) return HJGPU_EINVAL;
+    for (uint32_t c = 0; c < a.naggs; ++c) if (!a.aggs_out[c] || a.fn[c] > hj_agg::MAX) return HJGPU_EINVAL;
+    const u64 need = (a.slots + 255) / 256;
+    hipLaunchKernelGGL(wide_emit_kernel, dim3((uint32_t)std::min<u64>(need, (u64)cus * 8)), dim3(256), 0, stream, a);
+    return hipGetLastError() == hipSuccess ? HJGPU_OK : HJGPU_EHIP;
+}
+
 // ---- filter (hjgpu_filter_selected; DESIGN.md section 5 "Filter") -----------------------------------------------------------------------
 // Range predicates over columns into a bitmap: row i passes when it is selected and, for every p < NPREDS, filter_layout.hpp's passes()
 // holds on cols[p][i].  One persistent grid; an iteration is BATCH wave trips of hj_lookup.hpp's layout (lane L owns rows 4 L ... 4 L + 3

@@ -11,6 +11,7 @@
 #include "gather_layout.hpp"
 #include "group_layout.hpp"
 #include "scatter_layout.hpp"
+#include "wide_group_layout.hpp"
 
 typedef unsigned long long u64;
 
@@ -542,6 +543,36 @@ struct AggEmitArgs {
 int hj_launch_agg_group(const AggArgs &a, int cus, hipStream_t stream);
 int hj_launch_agg_scalar(const AggArgs &a, int cus, hipStream_t stream);
 int hj_launch_agg_emit(const AggEmitArgs &a, int cus, hipStream_t stream);
+
+// Wide keys (hjgpu_group_by* with three and four key columns, gen_kernels.hip; DESIGN.md section 5 "Wide keys"): the tables of
+// wide_group_layout.hpp.  hj_launch_wide_group: hj_launch_agg_group's pre-conditions with nkeys 3 or 4 - one persistent grid; every selected
+// row is combined into its tuple's slot of the merge table, `merge` holds merge_mask + 1 slots, all zero before the launch, as is *overflow,
+// which is raised when a tuple finds no slot.  hj_launch_wide_emit: the occupied slots go to the dense outputs (rows below capacity only),
+// the extremes turned back into the columns' values, and their number is added to *d_ngroups, which is 0 before the launch.
+struct WideArgs {
+    const uint32_t *select_bits;         // NULL: every row
+    u64 n;
+    const uint32_t *keys[hj_wide::MAX_KEYS];
+    const uint32_t *a[hj_wide::MAX_AGGS], *b[hj_wide::MAX_AGGS];      // aggregate c's column a; SUM_MUL: the second factor's column
+    uint32_t fn[hj_wide::MAX_AGGS], flags[hj_wide::MAX_AGGS];
+    uint32_t nkeys, naggs;
+    hj_wide::Slot *merge;
+    u64 merge_mask;
+    uint32_t *overflow;
+};
+struct WideEmitArgs {
+    const hj_wide::Slot *merge;
+    u64 slots;
+    uint32_t nkeys, naggs;
+    uint32_t *keys_out[hj_wide::MAX_KEYS];
+    u64 *counts_out;                     // NULL: no counts
+    u64 *aggs_out[hj_wide::MAX_AGGS];
+    uint32_t fn[hj_wide::MAX_AGGS], flags[hj_wide::MAX_AGGS];
+    u64 capacity;
+    u64 *d_ngroups;
+};
+int hj_launch_wide_group(const WideArgs &a, int cus, hipStream_t stream);
+int hj_launch_wide_emit(const WideEmitArgs &a, int cus, hipStream_t stream);
 
 // Filter (hjgpu_filter_selected*, gen_kernels.hip; DESIGN.md section 5 "Filter"): one persistent grid of filter_layout.hpp's geometry.  Row
 // i < n passes when it is selected (select_bits NULL: every row) and preds[p] holds on cols[p][i] for every p < npreds; bits_out (NULL:

@@ -1563,7 +1563,9 @@ int hjgpu_get_counter(hjgpu_ctx *ctx, const char *name, uint64_t *value)
     if (strcmp(name, "gather_step_rows") == 0) { *value = hj_gather::step_rows(ctx->cus); return HJGPU_OK; }
     if (strcmp(name, "agg_step_rows") == 0) { *value = hj_agg::group_step_rows(ctx->cus); return HJGPU_OK; }
     if (strcmp(name, "agg_scalar_step_rows") == 0) { *value = hj_agg::scalar_step_rows(ctx->cus); return HJGPU_OK; }
-    return fail(ctx, HJGPU_EINVAL, "unknown counter (probe_fallbacks, probe_exact, build_beside, lookup_lds_rows, compact_ranges, compact_chunk_rows, group_lds_groups, filter_step_rows, gather_step_rows, agg_step_rows, agg_scalar_step_rows)");
+    if (strcmp(name, "group_by_lds_groups") == 0) { *value = hj_wide::LDS_GROUPS; return HJGPU_OK; }
+    if (strcmp(name, "group_by_step_rows") == 0) { *value = hj_wide::step_rows(ctx->cus); return HJGPU_OK; }
+    return fail(ctx, HJGPU_EINVAL, "unknown counter (probe_fallbacks, probe_exact, build_beside, lookup_lds_rows, compact_ranges, compact_chunk_rows, group_lds_groups, filter_step_rows, gather_step_rows, agg_step_rows, agg_scalar_step_rows, group_by_lds_groups, group_by_step_rows)");
 }
 
 // the workspace's side of hjgpu_stats: what the context has spent growing it, and its last placement search
@@ -1620,12 +1622,12 @@ int hjgpu_get_stats(hjgpu_ctx *ctx, hjgpu_stats *s)
     if (ctx->last_algo >= ALGO_ONE_KERNEL) {
         // one operator (hjgpu_partition*, hjgpu_column_sums, the column operators): the stages it has are the events it recorded - a span to
         // or from an event it did not record is 0.  Compaction, filter and gather record EV_JOIN and EV_GAPS back to back: only the grouped
-        // aggregations (hjgpu_group_sum, hjgpu_group_agg) have a stage (the emit) between them
+        // aggregations (hjgpu_group_sum, hjgpu_group_agg, hjgpu_group_by's wide road) have a stage (the emit) between them
         memset(&r, 0, sizeof(r));
         r.ms_total = span(EV_BEGIN, EV_GAPS);
         r.ms_histogram = span(EV_BEGIN, EV_S_HIST);
         r.ms_join = span(EV_S_HIST, EV_JOIN);
-        if (ctx->last_algo == ALGO_GROUP_SUM || ctx->last_algo == ALGO_GROUP_AGG) r.ms_close_gaps = span(EV_JOIN, EV_GAPS);
+        if (ctx->last_algo == ALGO_GROUP_SUM || ctx->last_algo == ALGO_GROUP_AGG || ctx->last_algo == ALGO_GROUP_BY) r.ms_close_gaps = span(EV_JOIN, EV_GAPS);
         fill_reserve(ctx, &r);
         *s = r;
         return HJGPU_OK;

@@ -1,5 +1,5 @@
 // hjgpu_colops.hip - the column operators of include/hjgpu.h over a bitmap's rows: hjgpu_compact_selected, hjgpu_group_sum, hjgpu_group_agg,
-// hjgpu_filter_selected, hjgpu_gather_selected and their _async forms.  What they refuse from their arguments alone is
+// hjgpu_group_by, hjgpu_filter_selected, hjgpu_gather_selected and their _async forms.  What they refuse from their arguments alone is
 // colop_checks.hpp; their kernels are gen_kernels.hip's.  The blocking and the enqueue-only form of an operator are ONE path (X_call): they
 // differ in where the count words lie - the context's, or the caller's in device memory - and in the blocking form's tail.
 #include "hjgpu_ctx.hpp"
@@ -172,6 +172,58 @@ static int group_agg_call(hjgpu_ctx *ctx, const GroupAggCall &g, uint64_t *ngrou
     return HJGPU_OK;
 }
 
+// ---- GROUP BY up to four columns ----------------------------------------------------
+// the wide road (nkeys 3 or 4): group_agg_enqueue's three enqueues and its stats mapping over the tables of wide_group_layout.hpp
+static int group_by_enqueue(hjgpu_ctx *ctx, const GroupAggCall &g, u64 *d_ngroups, hipStream_t stream)
+{
+    const u64 slots = hj_wide::merge_slots(g.capacity);
+    char *ws = reinterpret_cast<char *>(ctx->group.p);
+    begin_span(ctx, ALGO_GROUP_BY, stream);
+    HIPCHK(ctx, hj_zero_async(d_ngroups, sizeof(u64), stream));
+    if (g.n) HIPCHK(ctx, hj_zero_async(ws + sizeof(u64), (size_t)(hj_wide::workspace_bytes(slots) - sizeof(u64)), stream));
+    record(ctx, EV_S_HIST, stream);
+    if (g.n) {
+        WideArgs a{};
+        a.select_bits = g.bits; a.n = g.n; a.nkeys = g.nkeys; a.naggs = g.naggs;
+        for (uint32_t c = 0; c < g.nkeys; ++c) a.keys[c] = g.keys_in[c];
+        for (uint32_t c = 0; c < g.naggs; ++c) { a.a[c] = g.aggs[c].d_a; a.b[c] = g.aggs[c].d_b; a.fn[c] = g.aggs[c].fn; a.flags[c] = g.aggs[c].flags; }
+        a.merge = reinterpret_cast<hj_wide::Slot *>(ws + hj_wide::WORKSPACE_HEAD);
+        a.merge_mask = slots - 1;
+        a.overflow = reinterpret_cast<uint32_t *>(ws + sizeof(u64));
+        CHK(hj_launch_wide_group(a, ctx->cus, stream));
+    }
+    record(ctx, EV_JOIN, stream);
+    if (g.n) {
+        WideEmitArgs e{};
+        e.merge = reinterpret_cast<const hj_wide::Slot *>(ws + hj_wide::WORKSPACE_HEAD);
+        e.slots = slots; e.nkeys = g.nkeys; e.naggs = g.naggs; e.capacity = g.capacity; e.counts_out = reinterpret_cast<u64 *>(g.counts_out);
+        for (uint32_t c = 0; c < g.nkeys; ++c) e.keys_out[c] = g.keys_out[c];
+        for (uint32_t c = 0; c < g.naggs; ++c) { e.aggs_out[c] = reinterpret_cast<u64 *>(g.aggs_out[c]); e.fn[c] = g.aggs[c].fn; e.flags[c] = g.aggs[c].flags; }
+        e.d_ngroups = d_ngroups;
+        CHK(hj_launch_wide_emit(e, ctx->cus, stream));
+    }
+    record(ctx, EV_GAPS, stream);
+    return HJGPU_OK;
+}
+
+// The road is chosen by nkeys: up to two key columns are hjgpu_group_agg itself.  The wide road's workspace is group_call's buffer, grown
+// to the wide table's size when needed: one context runs one call at a time, and the clears are ordered by the stream
+static int group_by_call(hjgpu_ctx *ctx, const GroupAggCall &g, uint64_t *ngroups, bool device_count, void *stream_)
+{
+    if (g.nkeys <= HJGPU_GROUP_MAX_KEYS) return group_agg_call(ctx, g, ngroups, device_count, stream_);
+    if (!ctx) return HJGPU_EINVAL;
+    hipStream_t stream = (hipStream_t)stream_;
+    CHK(colop_begin(ctx, check_group_by(g, ngroups, device_count), stream, ctx->group, (size_t)hj_wide::workspace_bytes(hj_wide::merge_slots(g.capacity))));
+    u64 *d_ngroups = reinterpret_cast<u64 *>(device_count ? (void *)ngroups : ctx->group.p);
+    CHK(group_by_enqueue(ctx, g, d_ngroups, stream));
+    if (device_count) return HJGPU_OK;
+    u64 got[2];
+    CHK(read_back(ctx, d_ngroups, 1, got, ngroups, stream));
+    if (got[0] > g.capacity)
+        return fail(ctx, HJGPU_EOVERFLOW, "hjgpu_group_by: more groups than capacity (*ngroups holds a lower bound of their number that exceeds capacity; the outputs are unspecified)");
+    return HJGPU_OK;
+}
+
 // ---- filter -----------------------------------------------------------------------
 // the two enqueues: the clear of the count word (d_count NULL: none), the kernel (n == 0: none).  hjgpu_get_stats afterwards: ms_histogram =
 // the clear, ms_join = the kernel, ms_total = both
@@ -282,6 +334,20 @@ int hjgpu_group_agg(hjgpu_ctx *ctx, const uint32_t *d_select_bits, size_t n, uin
                     uint64_t *const *d_aggs_out, size_t capacity, uint64_t *ngroups, void *stream)
 {
     return group_agg_call(ctx, {d_select_bits, n, nkeys, naggs, d_keys_in, aggs, d_keys_out, d_counts_out, d_aggs_out, capacity}, ngroups, false, stream);
+}
+
+int hjgpu_group_by_async(hjgpu_ctx *ctx, const uint32_t *d_select_bits, size_t n, uint32_t nkeys, const uint32_t *const *d_keys_in,
+                         uint32_t naggs, const hjgpu_aggregate *aggs, uint32_t *const *d_keys_out, uint64_t *d_counts_out,
+                         uint64_t *const *d_aggs_out, size_t capacity, uint64_t *d_ngroups, void *stream)
+{
+    return group_by_call(ctx, {d_select_bits, n, nkeys, naggs, d_keys_in, aggs, d_keys_out, d_counts_out, d_aggs_out, capacity}, d_ngroups, true, stream);
+}
+
+int hjgpu_group_by(hjgpu_ctx *ctx, const uint32_t *d_select_bits, size_t n, uint32_t nkeys, const uint32_t *const *d_keys_in,
+                   uint32_t naggs, const hjgpu_aggregate *aggs, uint32_t *const *d_keys_out, uint64_t *d_counts_out,
+                   uint64_t *const *d_aggs_out, size_t capacity, uint64_t *ngroups, void *stream)
+{
+    return group_by_call(ctx, {d_select_bits, n, nkeys, naggs, d_keys_in, aggs, d_keys_out, d_counts_out, d_aggs_out, capacity}, ngroups, false, stream);
 }
 
 int hjgpu_filter_selected_async(hjgpu_ctx *ctx, const uint32_t *d_select_bits, size_t n, uint32_t npreds, const uint32_t *const *d_cols,

@@ -52,7 +52,8 @@ enum { EV_BEGIN = 0, EV_S_HIST, EV_S_PLAN, EV_S_SC1, EV_S_SC2, EV_WAITED,
 // (begin_span) that records EV_S_HIST and EV_JOIN where it has stages
 enum Algo { ALGO_NONE = -1, ALGO_NPJ = 0, ALGO_PHJ = 1,        // (PHJ, CPRA and the LDS-road look-up)
             ALGO_ONE_KERNEL = 2,                               // hjgpu_partition*, hjgpu_column_sums, the hjgpu_*_ms probes
-            ALGO_COMPACT = 3, ALGO_GROUP_SUM = 4, ALGO_FILTER = 5, ALGO_GATHER = 6, ALGO_GROUP_AGG = 7 };
+            ALGO_COMPACT = 3, ALGO_GROUP_SUM = 4, ALGO_FILTER = 5, ALGO_GATHER = 6, ALGO_GROUP_AGG = 7,
+            ALGO_GROUP_BY = 8 };                               // hjgpu_group_by's wide road (three and four key columns)
 
 struct hjgpu_ctx {
     int device = 0;

@@ -287,7 +287,9 @@ int  hjgpu_get_stats(hjgpu_ctx *ctx, hjgpu_stats *stats);
  *   "filter_step_rows" the rows that hjgpu_filter_selected's whole grid covers in one iteration of its loop (the grid is smaller when the
  *                      rows are fewer)
  *   "gather_step_rows" the same for hjgpu_gather_selected
- *   "agg_step_rows", "agg_scalar_step_rows"   the same for hjgpu_group_agg with key columns and without (nkeys == 0) */
+ *   "agg_step_rows", "agg_scalar_step_rows"   the same for hjgpu_group_agg with key columns and without (nkeys == 0)
+ *   "group_by_lds_groups", "group_by_step_rows"   hjgpu_group_by with three and four key columns: the distinct groups a workgroup's wide
+ *                      LDS table holds, and the rows its whole grid covers in one iteration of its loop */
 int  hjgpu_get_counter(hjgpu_ctx *ctx, const char *name, uint64_t *value);
 
 /* ---- device memory helpers for hosts that do not link HIP (mamalloc/free,
@@ -697,6 +699,36 @@ int  hjgpu_group_agg_async(hjgpu_ctx *ctx, const uint32_t *d_select_bits, size_t
                            uint32_t nkeys, const uint32_t *const *d_keys_in, uint32_t naggs, const hjgpu_aggregate *aggs,
                            uint32_t *const *d_keys_out, uint64_t *d_counts_out, uint64_t *const *d_aggs_out,
                            size_t capacity, uint64_t *d_ngroups, void *stream);
+
+/* ---- GROUP BY up to four columns ---------------------------------------------------------------------------------------------------------
+ * hjgpu_group_agg's contract, word for word, except that nkeys is 0 to HJGPU_GROUP_BY_MAX_KEYS (4): the mask and NULL, hjgpu_aggregate and
+ * its refusals with the aggregate's index in the text, every key value legal - 0 and HJGPU_NULL_VAL included, in every key column -, the
+ * groups in unspecified order, n == 0, *ngroups, HJGPU_EOVERFLOW with a lower bound of J above capacity, capacity == 0 and capacity > 2^40,
+ * alignment (HJGPU_EALIGN), the "overlaps" refusals, the capturing stream, every refusal decided from the arguments alone before anything
+ * is allocated or enqueued, the untouched async status, calls queued back to back on one stream.  nkeys > 4 is HJGPU_EINVAL ("nkeys" in
+ * hjgpu_last_error); d_keys_in and d_keys_out are HOST arrays of nkeys device pointers; the same key column may be given more than once.
+ * The road is chosen by nkeys, as hjgpu_lookup chooses its road by inner:
+ *   nkeys <= 2       hjgpu_group_agg itself: its checks (an error text may name hjgpu_group_agg), its kernels, its results, its stats.
+ *   nkeys 3 or 4     the wide road.  A tuple no longer fits one 64-bit word, so a slot of the tables has a 64-bit word per key column,
+ *                    key | 1 << 32 - never 0, whatever the key - and insert-or-find goes through a slot's words in order with one 64-bit
+ *                    compare-and-swap per word that is still empty; no lane waits for another and no slot is ever left half owned
+ *                    (DESIGN.md section 5 "Wide keys").  Everything else is hjgpu_group_agg's: one pass over the mask, the key columns
+ *                    and the aggregates' columns, a pre-aggregation per workgroup in LDS, the merge table in the context's workspace (a
+ *                    power of two of at least 2 * capacity and at least 1024 slots of 72 bytes; it shares hjgpu_group_sum's buffer and
+ *                    grows the first time a capacity is seen: hjgpu_stats.ms_reserve), the emit.  Three enqueues ordered by the stream.
+ * hjgpu_get_stats after the wide road: hjgpu_group_agg's mapping - ms_histogram = the clears, ms_join = the aggregation, ms_close_gaps =
+ * the emit, ms_total = all of it, every other phase 0, fanout1 = fanout2 = buckets = groups = 0.  hjgpu_get_counter "group_by_lds_groups":
+ * the distinct groups a workgroup's wide LDS table holds; "group_by_step_rows": the rows one loop iteration of the whole grid covers.
+ * hjgpu_group_sum and hjgpu_group_agg keep refusing nkeys > 2. */
+#define HJGPU_GROUP_BY_MAX_KEYS 4u
+int  hjgpu_group_by(hjgpu_ctx *ctx, const uint32_t *d_select_bits, size_t n,
+                    uint32_t nkeys, const uint32_t *const *d_keys_in, uint32_t naggs, const hjgpu_aggregate *aggs,
+                    uint32_t *const *d_keys_out, uint64_t *d_counts_out, uint64_t *const *d_aggs_out,
+                    size_t capacity, uint64_t *ngroups, void *stream);
+int  hjgpu_group_by_async(hjgpu_ctx *ctx, const uint32_t *d_select_bits, size_t n,
+                          uint32_t nkeys, const uint32_t *const *d_keys_in, uint32_t naggs, const hjgpu_aggregate *aggs,
+                          uint32_t *const *d_keys_out, uint64_t *d_counts_out, uint64_t *const *d_aggs_out,
+                          size_t capacity, uint64_t *d_ngroups, void *stream);
 
 /* ---- whole joins on HBM-resident columns (replace run()/run_hj()) ---------------- */
 /* run(), npj.cpp:769-927 */
