@@ -487,6 +487,29 @@ class HjGpu:
         self._check(self.lib.hjgpu_get_counter(self.handle, name.encode(), C.byref(v)))
         return v.value
 
+    def audit_next_seq(self):
+        """hjgpu_audit_read with no records asked for: the sequence number the context's next audited call gets (option "audit")."""
+        nxt = C.c_uint64()
+        self._check(self.lib.hjgpu_audit_read(self.handle, C.byref(nxt), 0, 0, None, None))
+        return nxt.value
+
+    def audit_read(self, first_seq, count=1, stream=None):
+        """hjgpu_audit_read: the records of the audited calls first_seq .. first_seq + count - 1, after waiting for `stream`;
+        a record = 8 stages x [misplaced, sum of keys, sum of payloads, tuples] (include/hjgpu.h)."""
+        buf = (C.c_uint64 * (32 * count))() if count else None
+        self._check(self.lib.hjgpu_audit_read(self.handle, None, first_seq, count, buf, stream))
+        return [[[int(buf[32 * i + 4 * s + w]) for w in range(4)] for s in range(8)] for i in range(count)]
+
+    def audit_recheck(self):
+        """hjgpu_audit_recheck: the partition checks of the last audited call again with the device quiet:
+        [(stage, [4 words as a fresh kernel counts], [4 words as the host counts from a hipMemcpy])]."""
+        n = C.c_size_t(0)
+        self._check(self.lib.hjgpu_audit_recheck(self.handle, None, 0, C.byref(n)))
+        buf = (C.c_uint64 * max(1, 9 * n.value))()
+        self._check(self.lib.hjgpu_audit_recheck(self.handle, buf, n.value, C.byref(n)))
+        return [(int(buf[9 * i]), [int(buf[9 * i + 1 + w]) for w in range(4)], [int(buf[9 * i + 5 + w]) for w in range(4)])
+                for i in range(n.value)]
+
     def synchronize(self, stream=None):
         self._check(self.lib.hjgpu_synchronize(self.handle, stream))
 

@@ -260,7 +260,30 @@ int  hjgpu_set_option(hjgpu_ctx *ctx, const char *name, const char *value);
  * prepared build side); 6 the join's result; 7 {sequence number, kind (0 whole join, 1 build only, 2 probe only,
  * 3 hjgpu_partition_packed*), build rows, probe rows}.  The context keeps its last 256 records.  *next_seq (may be NULL) =
  * the sequence number the next call will get; records[count][32] = the calls first_seq .. first_seq + count - 1 (waits for
- * `stream`). */
+ * `stream`).
+ * Which stages a call fills (a stage that is not filled is all zero; the first word of every filled stage 0-5 of a sound call is 0):
+ *   0 / 3     whenever the relation has rows - the caller's columns, or the rows [chunk_offsets[0], chunk_offsets[chunks]) of a
+ *             pre-partitioned relation's array;
+ *   1 / 4     two-pass plans of one chunk over the caller's columns (not hjgpu_cpra's chunks, not pre-partitioned pieces, not a probe
+ *             side partitioned in batches, option "batch_tuples"): pass 1's fanout1 partitions;
+ *   2 / 5     whenever the relation has rows: fanout1 * fanout2 parts, each holding the partition of its number - chunks * fanout1 *
+ *             fanout2 under option "dense2" and of a single pass over chunks, part q then holding partition q % (fanout1 * fanout2);
+ *             the partition of a pre-partitioned piece's tuple counts from the layout's first_partition;
+ *   6         the four words of the call's hjgpu_result in the order of its fields (count, sum_keys, sum_outer_vals,
+ *             sum_inner_vals) when a join ran, whatever its mode;
+ *   kind 3    (hjgpu_partition_packed_async, _own_last_async, _counted_async; build rows = n) 0 = the columns as read, 1 = the
+ *             packed output where the own-last layout puts it; n == 0 leaves stage 7 alone.
+ * Which calls get a sequence number: every call that goes through the PHJ enqueue path or the packed partition operator while
+ * the option is set - hjgpu_phj, hjgpu_cpra, their _async forms and hjgpu_phj_overlapped_async (kind 0), hjgpu_phj_build and
+ * hjgpu_phj_build_prepartitioned (1), every hjgpu_phj_probe* of them (2), hjgpu_partition_packed* (3).  None: hjgpu_npj*, the
+ * look-ups, the column form hjgpu_partition, hjgpu_join_partitions, the column operators, a broadcast join (a small build side
+ * without explicit fan-outs, and an anti- or left outer join without build rows), a call that fails its argument checks,
+ * hjgpu_audit_recheck, and any call made while the option is off.
+ * A grouped plan (see hjgpu_phj; the option selects its host-planned form) leaves ONE kind-0 record PER GROUP that is joined,
+ * consecutively and in the order of the groups: the group's rows in stage 7, its own plan's partitions in 1-2 / 4-5, its share of
+ * the result in 6 - the stage-0 / stage-3 / stage-6 words of a call's records add up to the whole relations' and the call's result.
+ * Pass 0 leaves no record of its own; neither does a group that is skipped (nothing can match) or joined by the broadcast road,
+ * nor the grouped plan of hjgpu_phj_overlapped_async, which is planned on the device whatever the option says. */
 int  hjgpu_audit_read(hjgpu_ctx *ctx, uint64_t *next_seq, uint64_t first_seq, uint32_t count, uint64_t *records, void *stream);
 /* Option "audit", second look (diagnostics): the partition checks of the context's LAST audited call done again with the device quiet
  * (hipDeviceSynchronize first) - by a fresh kernel, and on the host from a copy of the partitions made with hipMemcpy (the copy
