@@ -2345,11 +2345,16 @@ static int phj_like(hjgpu_ctx *ctx, uint32_t chunks, const Rel &R, const Rel &S,
         const bool claim = blocking && chunks == 1 && !inner_ready && !local_join && !d_result && claimed_probe_allowed(ctx);
         const EnqueueOpts whole = {.out = out, .inner_ready = (hipEvent_t)inner_ready};
         CHK(phj_prepare(ctx, inner, outer, prm, chunks, &pl, {.claim_s = claim}));
-        CHK(phj_enqueue(ctx, pl, R, S, stream, whole));
+        // (option "probe_slack" = 0 and fewer probe rows than fanout1: pass 1's regions hold no tuple - cap1 = 0, full before the first row.
+        // Pass 1 has no launch for such a region: the overflow is known here, and the claimed attempt is left out)
+        const bool full_at_once = pl.claim_s && pl.cap1 == 0;
+        if (!full_at_once) CHK(phj_enqueue(ctx, pl, R, S, stream, whole));
         if (pl.claim_s) {
-            DevState h;
-            CHK(read_state(ctx, h, stream));
-            if (!h.probe_overflow) return finish_from(ctx, h, result, out);
+            if (!full_at_once) {
+                DevState h;
+                CHK(read_state(ctx, h, stream));
+                if (!h.probe_overflow) return finish_from(ctx, h, result, out);
+            }
             // an optimistic region of the probe side was full (skewed keys): the join again, exactly (K4 of S, range bases), and every
             // later join of this context exactly at once; the caller's result and rows are those of this second join
             ctx->probe_exact = true;

@@ -238,7 +238,9 @@ int  hjgpu_get_device_info(hjgpu_ctx *ctx, hjgpu_device_info *info);
  * twin, 1..16; "placement_ms": the search's wall-clock budget, default 500, 0 = none; "placement_log" 1: every candidate's fill time on stderr); "batch_tuples" (n, 0 = off); "group_from" / "group_inner" (tuples), "group_always" and "group_device" (0 / 1), "group_slack" (per cent): the
  * grouped plans of hjgpu_phj / hjgpu_cpra (below); "exact_probe_counts" (0 / 1, default 0: a blocking two-pass hjgpu_phj of one chunk
  * partitions its probe side without the histogram pass, into optimistic regions, and joins again exactly when one is full -
- * hjgpu_get_counter; 1: always the exact path) and "probe_slack" (per cent of slack in those regions, default 12, 0 = none);
+ * hjgpu_get_counter; 1: always the exact path) and "probe_slack" (per cent of slack in those regions, default 12, 0 = none: a region is
+ * then the mean number of rows in whole 16-tuple lines - rows that fill it to the last tuple are no overflow, one row more is - and
+ * with fewer probe rows than partitions it holds no tuple at all: such a join always falls back, and is counted);
  * "build_beside" (0 / 1, default 1: such a join, when both relations have rows, partitions its build side on a second stream of the
  * context while the probe side goes through its passes on the caller's - a fork and a join inside the call; 0: one stream, the build
  * side first; a join under option "solo" never forks: its plain stores rest on the promise of one stream) and "build_cus" (the CUs the
