@@ -30,6 +30,8 @@ FILTER_MAX_PREDS = 4    # HJGPU_FILTER_MAX_PREDS
 PRED_NOT = 1            # HJGPU_PRED_NOT: the rows OUTSIDE [lo, hi] pass
 PRED_SIGNED = 2         # HJGPU_PRED_SIGNED: lo, hi and the column are int32 (two's complement order)
 GATHER_MAX_COLS = 4     # HJGPU_GATHER_MAX_COLS
+LOOKUP_WIDE_MIN_KEYS = 2    # HJGPU_LOOKUP_WIDE_MIN_KEYS
+LOOKUP_WIDE_MAX_KEYS = 4    # HJGPU_LOOKUP_WIDE_MAX_KEYS
 AGG_SUM = 0             # HJGPU_AGG_SUM: SUM(a)
 AGG_SUM_MUL = 1         # HJGPU_AGG_SUM_MUL: SUM(a * b), the exact 64-bit product of the two 32-bit values
 AGG_MIN = 2             # HJGPU_AGG_MIN: MIN(a)
@@ -47,6 +49,7 @@ EXPORTS = [
     "hjgpu_npj_build", "hjgpu_npj_probe",
     "hjgpu_npj_lookup", "hjgpu_npj_lookup_async", "hjgpu_npj_lookup_table", "hjgpu_lookup", "hjgpu_lookup_async",
     "hjgpu_lookup_selected", "hjgpu_lookup_selected_async", "hjgpu_npj_lookup_table_selected",
+    "hjgpu_lookup_wide", "hjgpu_lookup_wide_async",
     "hjgpu_filter_selected", "hjgpu_filter_selected_async",
     "hjgpu_gather_selected", "hjgpu_gather_selected_async",
     "hjgpu_compact_selected", "hjgpu_compact_selected_async",
@@ -299,6 +302,8 @@ def load_library(build_if_missing=True):
     L.hjgpu_npj_lookup_table.argtypes = [vp, vp, sz, vp, sz, u32, vp, vp, C.POINTER(Result), vp]
     L.hjgpu_lookup_selected.argtypes = [vp, vp, vp, sz, vp, sz, C.POINTER(NpjParams), vp, vp, vp, C.POINTER(Result), vp]
     L.hjgpu_lookup_selected_async.argtypes = [vp, vp, vp, sz, vp, sz, C.POINTER(NpjParams), vp, vp, vp, vp, vp]
+    L.hjgpu_lookup_wide.argtypes = [vp, u32, C.POINTER(vp), vp, sz, C.POINTER(vp), sz, C.POINTER(NpjParams), vp, vp, vp, C.POINTER(Result), vp]
+    L.hjgpu_lookup_wide_async.argtypes = [vp, u32, C.POINTER(vp), vp, sz, C.POINTER(vp), sz, C.POINTER(NpjParams), vp, vp, vp, vp, vp]
     L.hjgpu_filter_selected.argtypes = [vp, vp, sz, u32, C.POINTER(vp), C.POINTER(Predicate), vp, u64p, vp]
     L.hjgpu_filter_selected_async.argtypes = [vp, vp, sz, u32, C.POINTER(vp), C.POINTER(Predicate), vp, vp, vp]
     L.hjgpu_gather_selected.argtypes = [vp, vp, vp, sz, u32, C.POINTER(vp), sz, C.POINTER(vp), vp, u64p, vp]
@@ -482,7 +487,8 @@ class HjGpu:
         "filter_step_rows" / "gather_step_rows" (the rows filter_selected's / gather_selected's whole grid covers in one iteration of its
         loop), "agg_step_rows" / "agg_scalar_step_rows" (the same for group_agg with key columns / without),
         "group_by_lds_groups" / "group_by_step_rows" (group_by with three and four key columns: the distinct groups a workgroup's wide LDS
-        table holds, and the rows its whole grid covers in one iteration of its loop)."""
+        table holds, and the rows its whole grid covers in one iteration of its loop), "lookup_wide_step_rows" (the rows lookup_wide's
+        whole look-up grid covers in one iteration of its loop)."""
         v = C.c_uint64()
         self._check(self.lib.hjgpu_get_counter(self.handle, name.encode(), C.byref(v)))
         return v.value
@@ -631,6 +637,33 @@ class HjGpu:
                                                              self._ptr(select_bits), self._ptr(vals_out), self._ptr(match_bits),
                                                              C.byref(r), stream))
         return r.as_tuple()
+
+    # ---- wide look-up: two to four key columns per side; every key value is legal ----------------------------------------------------
+    def _lookup_wide_args(self, inner_keys, outer_keys):
+        inner_keys, outer_keys = list(inner_keys or ()), list(outer_keys or ())
+        if len(inner_keys) != len(outer_keys):
+            raise ValueError("lookup_wide: %d build key columns, %d probe key columns" % (len(inner_keys), len(outer_keys)))
+        # (no column: NULL arrays - the library refuses nkeys == 0)
+        return len(inner_keys), self._ptr_array(inner_keys), self._ptr_array(outer_keys)
+
+    def lookup_wide(self, inner_keys, rv, inner, outer_keys, outer, params=None, select_bits=None, vals_out=None, match_bits=None, stream=None):
+        """hjgpu_lookup_wide: lookup_selected on LOOKUP_WIDE_MIN_KEYS to LOOKUP_WIDE_MAX_KEYS key columns - vals_out[i] = rv[j] for a build
+        row j whose key values equal probe row i's in every column, position by position; NULL_VAL and bit 0 for a row that is unselected or
+        unmatched.  Every key value is legal, 0 included.  With the row number as the payload (rv = arange) and gather_selected behind it
+        this is a composite-key N:1 join.  Returns (count, sum of key column 0, 0, sum of the payloads) over the selected rows with a match."""
+        nkeys, rk, sk = self._lookup_wide_args(inner_keys, outer_keys)
+        r = Result()
+        self._check(self.lib.hjgpu_lookup_wide(self.handle, nkeys, rk, self._ptr(rv), inner, sk, outer,
+                                               C.byref(params) if params is not None else None, self._ptr(select_bits),
+                                               self._ptr(vals_out), self._ptr(match_bits), C.byref(r), stream))
+        return r.as_tuple()
+
+    def lookup_wide_async(self, inner_keys, rv, inner, outer_keys, outer, params, select_bits, vals_out, match_bits, d_result, stream=None):
+        """hjgpu_lookup_wide_async: enqueue only; the four aggregates go to d_result (32 bytes of device memory, 16-byte aligned, or None)"""
+        nkeys, rk, sk = self._lookup_wide_args(inner_keys, outer_keys)
+        self._check(self.lib.hjgpu_lookup_wide_async(self.handle, nkeys, rk, self._ptr(rv), inner, sk, outer,
+                                                     C.byref(params) if params is not None else None, self._ptr(select_bits),
+                                                     self._ptr(vals_out), self._ptr(match_bits), self._ptr(d_result), stream))
 
     # ---- filter: range predicates over columns into a bitmap (match_bits' layout), in place or not ---------------------------------
     def _filter_args(self, cols, preds):

@@ -1,4 +1,4 @@
-// colop_checks.hpp - what the column operators (hjgpu_compact_selected, hjgpu_group_sum, hjgpu_group_agg, hjgpu_group_by, hjgpu_filter_selected, hjgpu_gather_selected: hjgpu_colops.hip)
+// colop_checks.hpp - what the column operators (hjgpu_compact_selected, hjgpu_group_sum, hjgpu_group_agg, hjgpu_group_by, hjgpu_filter_selected, hjgpu_gather_selected, hjgpu_lookup_wide: hjgpu_colops.hip)
 // and the selected look-ups refuse from their arguments alone, before anything is allocated or enqueued (DESIGN.md section 5 "Argument checks
 // of the column operators").  Plain host C++, no HIP and no context: a check returns {status, text}, its caller hands that to fail().
 // tests/test_colop_checks.py compiles it with g++ and compares every decision with the hand-written checkers it replaced.
@@ -15,6 +15,7 @@
 #include "../../include/hjgpu.h"
 #include "group_layout.hpp"
 #include "wide_group_layout.hpp"
+#include "wide_lookup_layout.hpp"
 
 namespace colop {
 
@@ -295,6 +296,48 @@ inline Verdict check_gather(const GatherCall &g, const uint64_t *d_counts)
     for (uint32_t k = 0; k < g.ncols; ++k) t.write(g.out[k], cbytes, 16, "an output column", idx);
     t.write(g.bits_out, bitmap_bytes(g.n), 16, "d_bits_out", mask);
     t.write(d_counts, 2 * sizeof(uint64_t), 16, "d_counts");
+    return check_operands(t);
+}
+
+// ---- hjgpu_lookup_wide ------------------------------------------------------------------------------------------------------------------------
+struct LookupWideCall {
+    uint32_t nkeys;
+    const uint32_t *const *inner_keys;                  // host arrays of nkeys device pointers, copied by value
+    const uint32_t *inner_vals;
+    size_t inner;
+    const uint32_t *const *outer_keys;
+    size_t outer;
+    const hjgpu_npj_params *params;                     // NULL: the defaults
+    const uint32_t *select_bits;
+    uint32_t *vals_out, *match_bits;
+};
+
+// d_result: the device form's result words (NULL: none, and the blocking form, whose words are the context's).  The join-mode flags are
+// the entry point's to refuse (refuse_join_mode names them).  outer == 0: nothing is read, not even the build side; inner == 0: no key of
+// either side is read
+inline Verdict check_lookup_wide(const LookupWideCall &c, const hjgpu_result *d_result)
+{
+    static_assert(hj_wlk::MIN_KEYS == HJGPU_LOOKUP_WIDE_MIN_KEYS && hj_wlk::MAX_KEYS == HJGPU_LOOKUP_WIDE_MAX_KEYS, "two to four key words");
+    if (c.nkeys == 1) return refuse(HJGPU_EINVAL, "nkeys must be 2 to HJGPU_LOOKUP_WIDE_MAX_KEYS (4): one key column is hjgpu_lookup_selected");
+    if (c.nkeys < HJGPU_LOOKUP_WIDE_MIN_KEYS || c.nkeys > HJGPU_LOOKUP_WIDE_MAX_KEYS) return refuse(HJGPU_EINVAL, "nkeys must be 2 to HJGPU_LOOKUP_WIDE_MAX_KEYS (4)");
+    if (c.params && !(c.params->load >= 0 && c.params->load <= hj_wlk::MAX_LOAD)) return refuse(HJGPU_EINVAL, "load must be 0 (the default, 0.5) or in (0, 0.99]");
+    if ((uintptr_t)d_result & 15) return refuse(HJGPU_EALIGN, "d_result must be 16-byte aligned");
+    if (c.outer == 0) return no_objection();                  // nothing is read, nothing but the result is written: anything else may be NULL
+    if (c.inner) {
+        if (!c.inner_keys || !c.outer_keys) return refuse(HJGPU_EINVAL, "null key column array");
+        for (uint32_t k = 0; k < c.nkeys; ++k)
+            if (!c.inner_keys[k] || !c.outer_keys[k]) return refuse(HJGPU_EINVAL, "null key column pointer");
+        if (!c.inner_vals) return refuse(HJGPU_EINVAL, "null d_inner_vals");
+    }
+    Operands t;
+    const size_t obytes = c.outer * sizeof(uint32_t), ibytes = c.inner * sizeof(uint32_t);
+    const int mask = t.read(c.select_bits, bitmap_bytes(c.outer), 16, "d_select_bits");
+    for (uint32_t k = 0; c.inner && k < c.nkeys; ++k) t.read(c.outer_keys[k], obytes, 16, "a probe key column");
+    for (uint32_t k = 0; c.inner && k < c.nkeys; ++k) t.read(c.inner_keys[k], ibytes, 16, "a build key column");
+    t.read(c.inner_vals, ibytes, 16, "d_inner_vals");
+    t.write(c.vals_out, obytes, 16, "d_vals_out");
+    t.write(c.match_bits, bitmap_bytes(c.outer), 16, "d_match_bits", mask);
+    t.write(d_result, sizeof(hjgpu_result), 16, "d_result");
     return check_operands(t);
 }
 

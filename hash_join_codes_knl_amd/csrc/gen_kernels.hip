@@ -13,6 +13,7 @@
 #include "hj_device.hpp"
 #include "hj_internal.hpp"
 #include "hj_lookup.hpp"
+#include "hj_emit.hpp"
 #include <algorithm>
 #include <math.h>
 
@@ -1635,6 +1636,193 @@ int hj_launch_gather(const GatherArgs &a, uint32_t ncols, int cus, hipStream_t s
         case 3: hipLaunchKernelGGL((gather_kernel<3, S>), grid, dim3(BLOCK), 0, stream, a); break;
         default: hipLaunchKernelGGL((gather_kernel<4, S>), grid, dim3(BLOCK), 0, stream, a); break;
         }
+    });
+    return hipGetLastError() == hipSuccess ? HJGPU_OK : HJGPU_EHIP;
+}
+
+// ---- wide look-up (hjgpu_lookup_wide; DESIGN.md section 5 "Wide look-up") ------------------------------------------------------------------
+// The positional look-up on two to four key columns: the table, the hash and the two walks are wide_lookup_layout.hpp's.  Two launches
+// behind the clear of the table, ordered by the stream; no workgroup waits for another.
+// The kernels stand in the header's namespace: their symbols begin with the namespace, and "wide_" at the start of a symbol stays
+// hjgpu_group_by's (tests/test_group_by_isa.py reads every such kernel as one of its own).
+namespace hj_wlk {
+
+// component j of a vector (j is a constant wherever this is called: the loops over a lane's four rows are unrolled)
+__device__ __forceinline__ uint32_t comp(const uint4 &q, int j) { return j == 0 ? q.x : j == 1 ? q.y : j == 2 ? q.z : q.w; }
+
+// a whole slot in one (two keys) or two (three and four keys) 16-byte loads from one line: the claim word, then the key words
+template <uint32_t NKEYS>
+__device__ __forceinline__ void load_slot(const Slot<NKEYS> *s, u64 &claim, uint32_t (&seen)[NKEYS])
+{
+    const uint4 *p = reinterpret_cast<const uint4 *>(s);
+    const uint4 lo = p[0];
+    claim = (u64)lo.x | ((u64)lo.y << 32);
+    seen[0] = lo.z; seen[1] = lo.w;
+    if constexpr (NKEYS > 2) {
+        const uint4 hi = p[1];
+        seen[2] = hi.x;
+        if constexpr (NKEYS > 3) seen[3] = hi.y;
+    }
+}
+
+// the memory of insert and find: the claim is a relaxed 64-bit compare-and-swap of agent scope (global_atomic_cmpswap_x2), the winner's
+// key words leave through hj_store, two at a time, and a slot is read by plain loads - in the look-up kernel, a later launch
+struct GlobalMemory {
+    __device__ __forceinline__ u64 cas(u64 *p, u64 word) { return atomicCAS(p, 0ull, word); }
+    __device__ __forceinline__ void store_pair(uint32_t *p, uint32_t lo, uint32_t hi) { hj_store(reinterpret_cast<u64 *>(p), (u64)lo | ((u64)hi << 32)); }
+    template <uint32_t NKEYS>
+    __device__ __forceinline__ void load(const Slot<NKEYS> *s, u64 &claim, uint32_t (&seen)[NKEYS]) { load_slot<NKEYS>(s, claim, seen); }
+};
+
+// The build.  A lane loads vector v of every key column and of the payload column, 16 bytes each and non-temporal (the build side is read
+// once; the last, partial vector is loaded whole and cut at n), and inserts its four rows one after the other: one build row per lane and
+// trip through insert's walk.  No key is compared and no slot is read; the only stores are the winners' key words.
+template <int NKEYS>
+__global__ __launch_bounds__(BLOCK) void wide_lookup_build_kernel(WideLookupBuildArgs a)
+{
+    const u64 n = a.n, nvec = (n + 3) >> 2, stride = (u64)gridDim.x * BLOCK;
+    Slot<(uint32_t)NKEYS> *tab = reinterpret_cast<Slot<(uint32_t)NKEYS> *>(a.table);
+    const u64 slots = a.slots;
+    const uint4 *p4 = reinterpret_cast<const uint4 *>(a.vals);
+    GlobalMemory mem;
+    for (u64 v = (u64)blockIdx.x * BLOCK + threadIdx.x; v < nvec; v += stride) {
+        uint4 kk[NKEYS];
+#pragma unroll
+        for (int c = 0; c < NKEYS; ++c) kk[c] = hj_load_nt(reinterpret_cast<const uint4 *>(a.keys[c]) + v);
+        const uint4 pv = hj_load_nt(p4 + v);
+        const u64 g = v << 2;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if (g + j < n) {
+                uint32_t k[NKEYS];
+#pragma unroll
+                for (int c = 0; c < NKEYS; ++c) k[c] = comp(kk[c], j);
+                (void)insert<(uint32_t)NKEYS>(mem, tab, slots, k, comp(pv, j));
+            }
+        }
+    }
+}
+
+// The look-up.  One persistent grid; an iteration is BATCH wave trips of hj_lookup.hpp's layout (lane L owns rows 4 L ... 4 L + 3 of a
+// trip, a group of 8 lanes one word of either bitmap and one 128-byte line of every key column).  The head is lookup_fetch on key column 0:
+// all trips' mask words (SEL), then the key vectors, non-temporal, none where a group's mask word is 0, the nibble cut at n.  The further
+// key columns' vectors are loaded by the same lane where its nibble is not 0 - without SEL that is lookup_fetch's own gate, with SEL it
+// lies inside it: a group of 8 lanes whose mask word is 0 loads no key of any column.  Then the walk of wide_lookup_layout.hpp's find for
+// the lane's four rows at once: home, and round by round the slot loads of all rows still walking before the first of them is judged, so
+// that four slots are in flight.  A row that is not to be looked up is never walking: it issues no table load.  slots == 0 (an empty build
+// side): nobody walks.  The end of a trip is lookup_leave (the in-place rule for match_bits == select_bits is hj_lookup.hpp's), the
+// aggregates hj_add_to_result's.
+template <int NKEYS, bool SEL, bool VALS, bool BITS>
+__global__ __launch_bounds__(BLOCK) void wide_lookup_kernel(WideLookupArgs a)
+{
+    constexpr uint32_t NK = (uint32_t)NKEYS;
+    constexpr int NB = (int)BATCH, NW = (int)(BLOCK / 64);
+    __shared__ u64 red[4][NW];
+    const u64 n = a.n, nvec = (n + 3) >> 2, stride = (u64)gridDim.x * BLOCK;
+    const Slot<NK> *tab = reinterpret_cast<const Slot<NK> *>(a.table);
+    const u64 slots = a.slots;
+
+    u64 acc_n = 0, acc_k = 0, acc_i = 0;
+    // whole waves iterate together (the bitmaps' words need all lanes)
+    for (u64 v0 = (u64)blockIdx.x * BLOCK + (threadIdx.x & ~63u); v0 < nvec; v0 += stride * NB) {
+        uint32_t look[NB];
+        uint4 kk[NKEYS][NB];
+        lookup_fetch<SEL, NB, true>(a.select_bits, reinterpret_cast<const uint4 *>(a.keys[0]), v0, stride, n, look, kk[0]);
+#pragma unroll
+        for (int c = 1; c < NKEYS; ++c) {
+#pragma unroll
+            for (int u = 0; u < NB; ++u) {
+                kk[c][u] = make_uint4(0, 0, 0, 0);
+                if (look[u] != 0u) kk[c][u] = hj_load_nt(reinterpret_cast<const uint4 *>(a.keys[c]) + (v0 + (u64)u * stride + hj_lane()));
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < NB; ++u) {
+            if (v0 + (u64)u * stride >= nvec) break;                     // the wave's trip lies beyond the columns (the same for all its lanes)
+            const u64 v = v0 + (u64)u * stride + hj_lane();
+            const uint32_t kc[4] = {kk[0][u].x, kk[0][u].y, kk[0][u].z, kk[0][u].w};
+            uint32_t res[4] = {NULL_VAL, NULL_VAL, NULL_VAL, NULL_VAL};
+            uint32_t nib = 0;
+            uint32_t key[4][NKEYS];
+            u64 s[4];
+            bool act[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+#pragma unroll
+                for (int c = 0; c < NKEYS; ++c) key[j][c] = comp(kk[c][u], j);
+                act[j] = slots != 0 && ((look[u] >> j) & 1u);
+                s[j] = home(hash<NK>(key[j]), slots);
+            }
+            while (act[0] | act[1] | act[2] | act[3]) {
+                u64 claim[4];
+                uint32_t seen[4][NKEYS];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {                           // the slots of all rows still walking in flight together
+                    claim[j] = 0;
+#pragma unroll
+                    for (int c = 0; c < NKEYS; ++c) seen[j][c] = 0;
+                    if (act[j]) load_slot<NK>(tab + s[j], claim[j], seen[j]);
+                }
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    if (act[j]) {
+                        const Step st = judge<NK>(claim[j], seen[j], key[j]);
+                        if (st == STEP_NEXT) s[j] = next(s[j], slots);
+                        else {
+                            if (st == STEP_HIT) { res[j] = payload_of(claim[j]); nib |= 1u << j; }
+                            act[j] = false;
+                        }
+                    }
+                }
+            }
+            lookup_leave<VALS, BITS>(a.vals_out, a.match_bits, n, v, kc, res, nib, acc_n, acc_k, acc_i);
+        }
+    }
+    hj_add_to_result(red, a.result, acc_n, acc_k, 0ull, acc_i);
+}
+}  // namespace hj_wlk
+
+// the build's grid: no more workgroups than the rows have vectors for
+int hj_launch_wide_lookup_build(const WideLookupBuildArgs &a, uint32_t nkeys, int cus, hipStream_t stream)
+{
+    using namespace hj_wlk;
+    if (a.n == 0) return HJGPU_OK;
+    if (nkeys < MIN_KEYS || nkeys > MAX_KEYS || !a.vals || !a.table || a.slots <= a.n || cus < 1) return HJGPU_EINVAL;
+    uintptr_t all = (uintptr_t)a.vals;
+    for (uint32_t c = 0; c < nkeys; ++c) { if (!a.keys[c]) return HJGPU_EINVAL; all |= (uintptr_t)a.keys[c]; }
+    if ((all & 15) || ((uintptr_t)a.table & 31)) return HJGPU_EINVAL;
+    const u64 nvec = (a.n + 3) >> 2, need = (nvec + BLOCK - 1) / BLOCK;
+    const dim3 grid((uint32_t)std::min<u64>(need, (u64)cus * BUILD_RESIDENT));
+    switch (nkeys) {
+    case 2: hipLaunchKernelGGL((wide_lookup_build_kernel<2>), grid, dim3(BLOCK), 0, stream, a); break;
+    case 3: hipLaunchKernelGGL((wide_lookup_build_kernel<3>), grid, dim3(BLOCK), 0, stream, a); break;
+    default: hipLaunchKernelGGL((wide_lookup_build_kernel<4>), grid, dim3(BLOCK), 0, stream, a); break;
+    }
+    return hipGetLastError() == hipSuccess ? HJGPU_OK : HJGPU_EHIP;
+}
+
+// wide_lookup_layout.hpp's grid, no more workgroups than the rows have wave trips for
+int hj_launch_wide_lookup(const WideLookupArgs &a, uint32_t nkeys, int cus, hipStream_t stream)
+{
+    using namespace hj_wlk;
+    if (a.n == 0) return HJGPU_OK;
+    if (nkeys < MIN_KEYS || nkeys > MAX_KEYS || !a.result || (a.slots != 0 && !a.table) || cus < 1) return HJGPU_EINVAL;
+    uintptr_t all = (uintptr_t)a.select_bits | (uintptr_t)a.vals_out | (uintptr_t)a.match_bits | (uintptr_t)a.result;
+    for (uint32_t c = 0; c < nkeys; ++c) { if (!a.keys[c]) return HJGPU_EINVAL; all |= (uintptr_t)a.keys[c]; }
+    if ((all & 15) || ((uintptr_t)a.table & 31)) return HJGPU_EINVAL;
+    const u64 nvec = (a.n + 3) >> 2, need = (nvec + BLOCK - 1) / BLOCK;
+    const dim3 grid((uint32_t)std::min<u64>(need, (u64)grid_of(cus)));
+    hj_with_bool(a.select_bits != nullptr, [&](auto sel) {
+        hj_with_bool(a.vals_out != nullptr, [&](auto vals) {
+            hj_with_bool(a.match_bits != nullptr, [&](auto bits) {
+                constexpr bool S = decltype(sel)::value, V = decltype(vals)::value, M = decltype(bits)::value;
+                switch (nkeys) {
+                case 2: hipLaunchKernelGGL((wide_lookup_kernel<2, S, V, M>), grid, dim3(BLOCK), 0, stream, a); break;
+                case 3: hipLaunchKernelGGL((wide_lookup_kernel<3, S, V, M>), grid, dim3(BLOCK), 0, stream, a); break;
+                default: hipLaunchKernelGGL((wide_lookup_kernel<4, S, V, M>), grid, dim3(BLOCK), 0, stream, a); break;
+                }
+            });
+        });
     });
     return hipGetLastError() == hipSuccess ? HJGPU_OK : HJGPU_EHIP;
 }

@@ -12,6 +12,7 @@
 #include "group_layout.hpp"
 #include "scatter_layout.hpp"
 #include "wide_group_layout.hpp"
+#include "wide_lookup_layout.hpp"
 
 typedef unsigned long long u64;
 
@@ -605,6 +606,33 @@ struct GatherArgs {
     uint32_t *out[hj_gather::MAX_COLS];
 };
 int hj_launch_gather(const GatherArgs &a, uint32_t ncols, int cus, hipStream_t stream);
+
+// Wide look-up (hjgpu_lookup_wide*, gen_kernels.hip; DESIGN.md section 5 "Wide look-up"): the table of wide_lookup_layout.hpp - `slots`
+// slots of hj_wlk::slot_bytes(nkeys) bytes at `table`, 32-byte aligned.  hj_launch_wide_lookup_build: every build row claims a slot on its
+// tuple's path and stores its keys there; the table is all zero before the launch and has more slots than `n` rows.  n == 0 launches nothing.
+// hj_launch_wide_lookup: one persistent grid; row i < n that is selected (select_bits NULL: every row) gets the payload of the first slot
+// on its tuple's path that holds the tuple and bit 1, every other row HJGPU_NULL_VAL and bit 0; count, the sum of key column 0 and the sum
+// of the payloads over the matched rows are ADDED to *result.  slots == 0: no table, no row matches.  match_bits may be select_bits itself.
+// Every column, the mask, both outputs and the result 16-byte aligned; either output may be NULL; n == 0 launches nothing.
+struct WideLookupBuildArgs {
+    const uint32_t *keys[hj_wlk::MAX_KEYS];
+    const uint32_t *vals;
+    u64 n;
+    void *table;
+    u64 slots;
+};
+struct WideLookupArgs {
+    const uint32_t *select_bits;         // NULL: every row
+    const uint32_t *keys[hj_wlk::MAX_KEYS];
+    u64 n;
+    const void *table;
+    u64 slots;
+    hjgpu_result *result;
+    uint32_t *vals_out;
+    uint32_t *match_bits;
+};
+int hj_launch_wide_lookup_build(const WideLookupBuildArgs &a, uint32_t nkeys, int cus, hipStream_t stream);
+int hj_launch_wide_lookup(const WideLookupArgs &a, uint32_t nkeys, int cus, hipStream_t stream);
 
 // K9: compact the per-wave partially filled tail blocks (npj.cpp:475-514).
 // moves: scratch of 2*HJ_MAX_WORKERS entries of 24 bytes + HJ_MAX_WORKERS entries of 8 bytes.

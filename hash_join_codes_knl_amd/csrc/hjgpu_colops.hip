@@ -1,5 +1,5 @@
 // hjgpu_colops.hip - the column operators of include/hjgpu.h over a bitmap's rows: hjgpu_compact_selected, hjgpu_group_sum, hjgpu_group_agg,
-// hjgpu_group_by, hjgpu_filter_selected, hjgpu_gather_selected and their _async forms.  What they refuse from their arguments alone is
+// hjgpu_group_by, hjgpu_filter_selected, hjgpu_gather_selected, hjgpu_lookup_wide and their _async forms.  What they refuse from their arguments alone is
 // colop_checks.hpp; their kernels are gen_kernels.hip's.  The blocking and the enqueue-only form of an operator are ONE path (X_call): they
 // differ in where the count words lie - the context's, or the caller's in device memory - and in the blocking form's tail.
 #include "hjgpu_ctx.hpp"
@@ -294,7 +294,79 @@ static int gather_call(hjgpu_ctx *ctx, const GatherCall &g, uint64_t *counts, bo
     return HJGPU_OK;
 }
 
+// ---- wide look-up: two to four key columns ---------------------------------------------
+// the three enqueues: the clear of the aggregate words and the table, the build, the look-up - for an empty build side no table, and
+// the two fills that make every row a NULL row in the look-up's place (no key of either side is read); for outer == 0 the clear of the
+// aggregate words alone.  hjgpu_get_stats afterwards: ms_histogram = the clear and the build, ms_join = the look-up, ms_total = all of it
+// (and, in the device form, the copy of the aggregate words to d_result), buckets = the table's slots
+static int lookup_wide_enqueue(hjgpu_ctx *ctx, const LookupWideCall &c, u64 slots, hjgpu_result *d_result, hipStream_t stream)
+{
+    char *ws = reinterpret_cast<char *>(ctx->wide_lookup.p);
+    hjgpu_result *words = reinterpret_cast<hjgpu_result *>(ws);
+    void *table = ws + hj_wlk::WORKSPACE_HEAD;
+    begin_span(ctx, ALGO_LOOKUP_WIDE, stream);
+    ctx->stats.fanout1 = ctx->stats.fanout2 = 0; ctx->stats.buckets = slots; ctx->stats.batches = 0;
+    HIPCHK(ctx, hj_zero_async(ws, (size_t)hj_wlk::workspace_bytes(slots, c.nkeys), stream));
+    if (slots) {
+        WideLookupBuildArgs b{};
+        for (uint32_t k = 0; k < c.nkeys; ++k) b.keys[k] = c.inner_keys[k];
+        b.vals = c.inner_vals; b.n = c.inner; b.table = table; b.slots = slots;
+        CHK(hj_launch_wide_lookup_build(b, c.nkeys, ctx->cus, stream));
+    }
+    record(ctx, EV_S_HIST, stream);
+    if (slots) {
+        WideLookupArgs a{};
+        a.select_bits = c.select_bits; a.n = c.outer; a.table = table; a.slots = slots; a.result = words;
+        for (uint32_t k = 0; k < c.nkeys; ++k) a.keys[k] = c.outer_keys[k];
+        a.vals_out = c.vals_out; a.match_bits = c.match_bits;
+        CHK(hj_launch_wide_lookup(a, c.nkeys, ctx->cus, stream));
+    } else if (c.outer) {
+        if (c.vals_out) HIPCHK(ctx, hj_fill_async(c.vals_out, HJGPU_NULL_VAL, c.outer * sizeof(uint32_t), stream));
+        if (c.match_bits) HIPCHK(ctx, hj_zero_async(c.match_bits, bitmap_bytes(c.outer), stream));
+    }
+    record(ctx, EV_JOIN, stream);
+    if (d_result) HIPCHK(ctx, hj_copy_async(d_result, words, sizeof(hjgpu_result), stream));
+    record(ctx, EV_GAPS, stream);
+    return HJGPU_OK;
+}
+
+// the context's workspace (wide_lookup_layout.hpp; sized from the build side and the load): the call's aggregate words, then its table.
+// Its own buffer: neither ctx->state nor the NPJ table nor a prepared build side is touched
+static int lookup_wide_call(hjgpu_ctx *ctx, const LookupWideCall &c, hjgpu_result *result, bool device_result, void *stream_, const char *entry)
+{
+    if (!ctx) return HJGPU_EINVAL;
+    hipStream_t stream = (hipStream_t)stream_;
+    CHK(refused(ctx, check_lookup_wide(c, device_result ? result : nullptr)));
+    if (c.params) CHK(refuse_join_mode(ctx, c.params->flags, entry));
+    // (outer == 0: nothing is looked up, so nothing is built)
+    const u64 slots = c.outer ? hj_wlk::slots_of(c.inner, c.params ? c.params->load : 0.0) : 0;
+    CHK(colop_begin(ctx, no_objection(), stream, ctx->wide_lookup, (size_t)hj_wlk::workspace_bytes(slots, c.nkeys)));
+    CHK(lookup_wide_enqueue(ctx, c, slots, device_result ? result : nullptr, stream));
+    if (device_result) return HJGPU_OK;
+    hjgpu_result got;
+    HIPCHK(ctx, hipMemcpyAsync(&got, ctx->wide_lookup.p, sizeof(got), hipMemcpyDeviceToHost, stream));
+    HIPCHK(ctx, hipStreamSynchronize(stream));
+    if (result) *result = got;
+    return HJGPU_OK;
+}
+
 extern "C" {
+
+int hjgpu_lookup_wide_async(hjgpu_ctx *ctx, uint32_t nkeys, const uint32_t *const *d_inner_keys, const uint32_t *d_inner_vals, size_t inner,
+                            const uint32_t *const *d_outer_keys, size_t outer, const hjgpu_npj_params *params, const uint32_t *d_select_bits,
+                            uint32_t *d_vals_out, uint32_t *d_match_bits, hjgpu_result *d_result, void *stream)
+{
+    return lookup_wide_call(ctx, {nkeys, d_inner_keys, d_inner_vals, inner, d_outer_keys, outer, params, d_select_bits, d_vals_out, d_match_bits},
+                            d_result, true, stream, "hjgpu_lookup_wide_async");
+}
+
+int hjgpu_lookup_wide(hjgpu_ctx *ctx, uint32_t nkeys, const uint32_t *const *d_inner_keys, const uint32_t *d_inner_vals, size_t inner,
+                      const uint32_t *const *d_outer_keys, size_t outer, const hjgpu_npj_params *params, const uint32_t *d_select_bits,
+                      uint32_t *d_vals_out, uint32_t *d_match_bits, hjgpu_result *result, void *stream)
+{
+    return lookup_wide_call(ctx, {nkeys, d_inner_keys, d_inner_vals, inner, d_outer_keys, outer, params, d_select_bits, d_vals_out, d_match_bits},
+                            result, false, stream, "hjgpu_lookup_wide");
+}
 
 int hjgpu_compact_selected_async(hjgpu_ctx *ctx, const uint32_t *d_select_bits, size_t n, uint32_t ncols, const uint32_t *const *d_cols_in,
                                  uint32_t *const *d_cols_out, uint32_t *d_rows_out, size_t capacity, uint64_t *d_count, void *stream)

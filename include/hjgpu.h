@@ -484,6 +484,62 @@ int  hjgpu_npj_lookup_table_selected(hjgpu_ctx *ctx, const uint32_t *d_keys, siz
                                      uint32_t *d_vals_out, uint32_t *d_match_bits,
                                      hjgpu_result *result, void *stream);
 
+/* ---- wide positional look-up: two to four key columns -----------------------------------
+ * hjgpu_lookup_selected for ON a.k0 = b.k0 AND a.k1 = b.k1 (AND ...): a (partkey, suppkey) dimension, a (year, week) calendar, a
+ * (store, item) price list.  With the row number as the build payload and hjgpu_gather_selected behind it, it is a composite-key N:1 join.
+ * The contract is hjgpu_lookup_selected's wherever the two meet:
+ *   outputs          d_vals_out[i] (NULL: none) = the payload of a build row whose nkeys key values equal probe row i's, position by
+ *                    position - (a, b) does not match (b, a) -, bit i of d_match_bits (NULL: none) = there is one; HJGPU_NULL_VAL and bit 0
+ *                    for a row that is unselected or unmatched.  No element at index >= outer and no word at index >= (outer + 31) / 32 is
+ *                    written; the last word's high bits are 0.
+ *   d_select_bits    (outer + 31) / 32 words; bit i & 31 of word i >> 5 says whether row i is selected.  Bits of the last word at
+ *                    positions >= outer are ignored (they may hold anything), no word at index >= (outer + 31) / 32 is read.  NULL: every
+ *                    row is selected.  An unselected row costs no table access and is counted in no aggregate.
+ *   in place         d_match_bits may be the very pointer d_select_bits: afterwards the bitmap is select AND match (the last word's high
+ *                    bits 0).  Any other overlap of the two bitmaps is HJGPU_EINVAL.
+ *   empty sides      outer == 0: nothing is written and nothing is read.  inner == 0: every row gets HJGPU_NULL_VAL and bit 0, count 0.
+ *   stream           a capturing stream is HJGPU_EINVAL.
+ *   refusals         every refusal is decided from the arguments alone, before anything is allocated or enqueued.
+ * What is the wide look-up's own:
+ *   nkeys            2, 3 or 4 (HJGPU_LOOKUP_WIDE_MIN_KEYS .. _MAX_KEYS); 0, 1 and 5 are HJGPU_EINVAL ("nkeys" in hjgpu_last_error; one key
+ *                    column is hjgpu_lookup_selected).  d_inner_keys and d_outer_keys are HOST arrays of nkeys device pointers, copied by
+ *                    value: build columns of `inner` values, probe columns of `outer` values.  The same column may be given twice.
+ *   key values       every value is legal in every key column on both sides, 0 and 0xFFFFFFFF included: this call never returns
+ *                    HJGPU_EZEROKEY.
+ *   duplicates       which copy of a duplicated build tuple answers is unspecified; within one call every position with the same probe
+ *                    tuple receives the SAME copy (one table, one walk).
+ *   result           count = the selected rows with a match, sum_keys = the sum of key column 0 over them, sum_outer_vals = 0,
+ *                    sum_inner_vals = the sum of the looked-up payloads.  `result` is host memory, `d_result` (the _async form) 32 bytes of
+ *                    16-byte aligned device memory; either may be NULL.
+ *   params           load sizes the table: slots = max(16, inner + 1, floor(inner / load)) rounded up to a multiple of 8; 0 = 0.5; load >
+ *                    0.99 is HJGPU_EINVAL.  factor and HJGPU_FLAG_UNIQUE are ignored.  Any join-mode flag is HJGPU_EINVAL naming the flag.
+ *   alignment        every column, the mask, both outputs and d_result are 16-byte aligned (HJGPU_EALIGN).
+ *   overlap          a written operand (d_vals_out, d_match_bits, d_result) that shares a byte with a read operand or with another written
+ *                    one is HJGPU_EINVAL ("overlaps"); the one declared in-place pair is d_match_bits on d_select_bits.
+ *   state            the table and the aggregate words are a workspace of the call's own in the context, grown the first time a size is
+ *                    seen (either form; counted in ms_reserve).  The call touches neither the NPJ table, nor a prepared build side
+ *                    (hjgpu_phj_build), nor what hjgpu_get_async_status / hjgpu_accumulate_async_status report.  The _async form only
+ *                    enqueues and needs no hjgpu_reserve; calls may be queued back to back on one stream of one context.
+ *   hjgpu_get_stats  afterwards: ms_histogram = the clear of the table and the build, ms_join = the look-up kernel, ms_total = all of it,
+ *                    ms_close_gaps = 0, fanout1 = fanout2 = groups = 0, buckets = the table's slots.  hjgpu_get_counter
+ *                    "lookup_wide_step_rows": the rows the look-up's whole grid covers in one iteration of its loop. */
+#define HJGPU_LOOKUP_WIDE_MIN_KEYS 2u
+#define HJGPU_LOOKUP_WIDE_MAX_KEYS 4u
+int  hjgpu_lookup_wide(hjgpu_ctx *ctx, uint32_t nkeys,
+                       const uint32_t *const *d_inner_keys, const uint32_t *d_inner_vals, size_t inner,
+                       const uint32_t *const *d_outer_keys, size_t outer,
+                       const hjgpu_npj_params *params,
+                       const uint32_t *d_select_bits,   /* (outer + 31) / 32 uint32, or NULL: every row */
+                       uint32_t *d_vals_out, uint32_t *d_match_bits,   /* either may be NULL */
+                       hjgpu_result *result, void *stream);
+int  hjgpu_lookup_wide_async(hjgpu_ctx *ctx, uint32_t nkeys,
+                             const uint32_t *const *d_inner_keys, const uint32_t *d_inner_vals, size_t inner,
+                             const uint32_t *const *d_outer_keys, size_t outer,
+                             const hjgpu_npj_params *params,
+                             const uint32_t *d_select_bits,
+                             uint32_t *d_vals_out, uint32_t *d_match_bits,
+                             hjgpu_result *d_result, void *stream);
+
 /* ---- filter: range predicates over up to 4 columns into a bitmap --------------------------------------------
  * What makes, or narrows, a bitmap in d_match_bits' layout from the fact table's own columns - lo_discount BETWEEN 1 AND 3 AND lo_quantity
  * < 25, a date range, a status code - and from a looked-up value column (d_year BETWEEN 1992 AND 1997): the other half of a star query's
