@@ -658,11 +658,20 @@ __device__ __forceinline__ u64 group_merge_slot(const GroupArgs &a, u64 t, u64 h
     return GROUP_NO_SLOT;
 }
 
-// adds x to word `word` (0: the count, 1 + c: sum c) of the slot at `loc`
-__device__ __forceinline__ void group_add(hj_group::Slot *tab, const GroupArgs &a, u64 loc, uint32_t word, u64 x)
+// combines x into word `word` (0: the count, 1 + c: sum or aggregate c) of the slot at `loc` of either table layout - group_layout.hpp's or
+// wide_group_layout.hpp's slots, which both end in the count and four words: added, or the unsigned maximum for an extreme
+template <class Slot>
+__device__ __forceinline__ void group_combine(Slot *tab, Slot *merge, u64 loc, uint32_t word, bool extreme, u64 x)
 {
-    if (loc & GROUP_IN_LDS) __hip_atomic_fetch_add(&tab[(uint32_t)loc].count + word, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);   // ds_add_u64
-    else if (loc != GROUP_NO_SLOT) atomicAdd(&a.merge[loc].count + word, x);                   // global_atomic_add_x2
+    if (loc & GROUP_IN_LDS) {
+        u64 *p = &tab[(uint32_t)loc].count + word;
+        if (extreme) __hip_atomic_fetch_max(p, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);                     // ds_max_u64
+        else __hip_atomic_fetch_add(p, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);                             // ds_add_u64
+    } else if (loc != GROUP_NO_SLOT) {
+        u64 *p = &merge[loc].count + word;
+        if (extreme) __hip_atomic_fetch_max(p, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);                         // global_atomic_umax_x2
+        else atomicAdd(p, x);                                                                                           // global_atomic_add_x2
+    }
 }
 
 // One persistent grid.  An iteration is BATCH wave trips of hj_lookup.hpp's layout (lane L owns rows 4 L ... 4 L + 3 of a trip): the mask
@@ -731,7 +740,7 @@ __global__ __launch_bounds__(hj_group::BLOCK) void group_sum_kernel(GroupArgs a)
             const u64 h = mix(tq);
             u64 at = group_lds_slot(tab, &used, tq, h);
             if (at == GROUP_NO_SLOT) at = group_merge_slot(a, tq, h);
-            group_add(tab, a, at, 0, (u64)__popc((cls >> (4 * q)) & 15u));
+            group_combine(tab, a.merge, at, 0, false, (u64)__popc((cls >> (4 * q)) & 15u));
 #pragma unroll
             for (int r = 0; r < ROWS; ++r) loc[r] = q == r ? at : loc[r];
         }
@@ -752,7 +761,7 @@ __global__ __launch_bounds__(hj_group::BLOCK) void group_sum_kernel(GroupArgs a)
 #pragma unroll
                 for (int r = 1; r < ROWS; ++r) at = q == r ? loc[r] : at;
                 const u64 sum = (u64)((m & 1u) ? xq.x : 0u) + ((m & 2u) ? xq.y : 0u) + ((m & 4u) ? xq.z : 0u) + ((m & 8u) ? xq.w : 0u);
-                group_add(tab, a, at, 1 + c, sum);
+                group_combine(tab, a.merge, at, 1 + c, false, sum);
             }
         }
     }
@@ -769,79 +778,13 @@ __global__ __launch_bounds__(hj_group::BLOCK) void group_sum_kernel(GroupArgs a)
     }
 }
 
-// The occupied slots of the merge table go to the dense outputs, a wave's through one atomic add to the cursor, which is the count word
-// itself (0 before the launch): behind the launch it holds the number of occupied slots - the group count J, or, when the overflow word
-// was raised, the full table: a lower bound of J that is greater than capacity (the table has at least 2 * capacity slots).  Rows at
-// capacity and beyond are counted and not written.
-__global__ __launch_bounds__(256) void group_emit_kernel(GroupEmitArgs a)
-{
-    const uint32_t lane = hj_lane();
-    const u64 total = a.slots + 1, stride = (u64)gridDim.x * 256;
-    for (u64 i0 = (u64)blockIdx.x * 256 + (threadIdx.x & ~63u); i0 < total; i0 += stride) {
-        const u64 i = i0 + lane;
-        u64 t = 0, cnt = 0;
-        if (i < total) { t = a.merge[i].tuple; cnt = a.merge[i].count; }
-        const bool occ = i < a.slots ? t != 0 : i == a.slots && cnt != 0;
-        const u64 vote = __ballot(occ);
-        if (vote == 0) continue;
-        u64 base = 0;
-        if (lane == 0) base = atomicAdd(a.d_ngroups, (u64)__popcll(vote));
-        base = hj_uniform(base);
-        const u64 j = base + __popcll(vote & ((1ull << lane) - 1ull));
-        if (occ && j < a.capacity) {
-            hj_store(a.keys_out[0] + j, (uint32_t)t);
-            if (a.nkeys > 1) hj_store(a.keys_out[1] + j, (uint32_t)(t >> 32));
-            if (a.counts_out) hj_store(a.counts_out + j, cnt);
-#pragma unroll
-            for (uint32_t c = 0; c < hj_group::MAX_VALS; ++c)
-                if (c < a.nvals) hj_store(a.sums_out[c] + j, a.merge[i].sums[c]);
-        }
-    }
-}
-
-// one workgroup per compute unit (its table takes most of the unit's LDS), no more than the rows have wave trips for
-int hj_launch_group_sum(const GroupArgs &a, int cus, hipStream_t stream)
-{
-    using namespace hj_group;
-    if (a.n == 0) return HJGPU_OK;
-    if (a.nkeys < 1 || a.nkeys > MAX_KEYS || a.nvals > MAX_VALS || !a.merge || !a.overflow || (a.merge_mask & (a.merge_mask + 1)) || cus < 1) return HJGPU_EINVAL;
-    uintptr_t all = (uintptr_t)a.select_bits;
-    for (uint32_t c = 0; c < a.nkeys; ++c) { if (!a.keys[c]) return HJGPU_EINVAL; all |= (uintptr_t)a.keys[c]; }
-    for (uint32_t c = 0; c < a.nvals; ++c) { if (!a.vals[c]) return HJGPU_EINVAL; all |= (uintptr_t)a.vals[c]; }
-    if (all & 15) return HJGPU_EINVAL;
-    const u64 nvec = (a.n + 3) >> 2, need = (nvec + BLOCK - 1) / BLOCK;
-    const dim3 grid((uint32_t)std::min<u64>(need, (u64)cus));
-    hj_with_bool(a.select_bits != nullptr, [&](auto sel) {
-        constexpr bool S = decltype(sel)::value;
-        if (a.nkeys == 1) hipLaunchKernelGGL((group_sum_kernel<1, S>), grid, dim3(BLOCK), 0, stream, a);
-        else hipLaunchKernelGGL((group_sum_kernel<2, S>), grid, dim3(BLOCK), 0, stream, a);
-    });
-    return hipGetLastError() == hipSuccess ? HJGPU_OK : HJGPU_EHIP;
-}
-
-int hj_launch_group_emit(const GroupEmitArgs &a, int cus, hipStream_t stream)
-{
-    if (!a.merge || !a.d_ngroups || a.nkeys < 1 || a.nkeys > hj_group::MAX_KEYS || a.nvals > hj_group::MAX_VALS || cus < 1) return HJGPU_EINVAL;
-    const u64 need = (a.slots + 1 + 255) / 256;
-    hipLaunchKernelGGL(group_emit_kernel, dim3((uint32_t)std::min<u64>(need, (u64)cus * 8)), dim3(256), 0, stream, a);
-    return hipGetLastError() == hipSuccess ? HJGPU_OK : HJGPU_EHIP;
-}
-
 // ---- aggregate functions (hjgpu_group_agg; DESIGN.md section 5 "Aggregate functions") ---------------------------------------------------
 // GROUP BY (nothing | key 0 [, key 1]) COUNT(*) and up to four of SUM(a), SUM(a * b), MIN(a), MAX(a) over the rows a bitmap selects.  The
 // grouped road is group_sum_kernel's body with two differences: what a row contributes to an aggregate's word of its slot, and how words
 // are combined - agg_layout.hpp's term() and combine(): a sum is added, an extreme is an unsigned maximum of a transformed value whose
 // neutral word is the tables' initial 0 (ds_max_u64 in LDS, global_atomic_umax_x2 in the merge table).  fn and flags are uniform run-time
 // values per aggregate: every branch on them is a scalar branch.  The tables, insert-or-find, the fold, the spill rule and the flush are
-// group_sum_kernel's own (group_lds_slot, group_merge_slot, group_add).
-
-// combines x into word `word` (1 + c: aggregate c) of the slot at `loc`: group_add for a sum, the unsigned maximum for an extreme
-__device__ __forceinline__ void agg_combine(hj_group::Slot *tab, const GroupArgs &a, u64 loc, uint32_t word, bool extreme, u64 x)
-{
-    if (!extreme) group_add(tab, a, loc, word, x);
-    else if (loc & GROUP_IN_LDS) __hip_atomic_fetch_max(&tab[(uint32_t)loc].count + word, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);   // ds_max_u64
-    else if (loc != GROUP_NO_SLOT) __hip_atomic_fetch_max(&a.merge[loc].count + word, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);          // global_atomic_umax_x2
-}
+// group_sum_kernel's own (group_lds_slot, group_merge_slot, group_combine).
 
 // the terms of the rows of nibble m of one vector, combined: a row outside m contributes the neutral 0.  Straight-line code: the terms of
 // all four rows are computed and chosen by the nibble's bits
@@ -951,7 +894,7 @@ __global__ __launch_bounds__(hj_group::BLOCK) void agg_group_kernel(AggArgs aa)
             const u64 h = mix(tq);
             u64 at = group_lds_slot(tab, &used, tq, h);
             if (at == GROUP_NO_SLOT) at = group_merge_slot(a, tq, h);
-            group_add(tab, a, at, 0, (u64)__popc((cls >> (4 * q)) & 15u));
+            group_combine(tab, a.merge, at, 0, false, (u64)__popc((cls >> (4 * q)) & 15u));
 #pragma unroll
             for (int r = 0; r < ROWS; ++r) loc[r] = q == r ? at : loc[r];
         }
@@ -980,7 +923,7 @@ __global__ __launch_bounds__(hj_group::BLOCK) void agg_group_kernel(AggArgs aa)
                 u64 at = loc[0];
 #pragma unroll
                 for (int r = 1; r < ROWS; ++r) at = q == r ? loc[r] : at;
-                agg_combine(tab, a, at, 1 + c, extreme, agg_fold_of(fn, norm, m, xq, yq));
+                group_combine(tab, a.merge, at, 1 + c, extreme, agg_fold_of(fn, norm, m, xq, yq));
             }
         }
     }
@@ -1091,96 +1034,13 @@ __global__ __launch_bounds__(hj_agg::SCALAR_BLOCK) void agg_scalar_kernel(AggArg
     }
 }
 
-// group_emit_kernel with no, one or two key columns and agg_layout.hpp's result() per aggregate column: the sums leave as they are, the
-// extremes in the column's own values
-__global__ __launch_bounds__(256) void agg_emit_kernel(AggEmitArgs ae)
-{
-    const GroupEmitArgs &a = ae.g;
-    const uint32_t lane = hj_lane();
-    const u64 total = a.slots + 1, stride = (u64)gridDim.x * 256;
-    for (u64 i0 = (u64)blockIdx.x * 256 + (threadIdx.x & ~63u); i0 < total; i0 += stride) {
-        const u64 i = i0 + lane;
-        u64 t = 0, cnt = 0;
-        if (i < total) { t = a.merge[i].tuple; cnt = a.merge[i].count; }
-        const bool occ = i < a.slots ? t != 0 : i == a.slots && cnt != 0;
-        const u64 vote = __ballot(occ);
-        if (vote == 0) continue;
-        u64 base = 0;
-        if (lane == 0) base = atomicAdd(a.d_ngroups, (u64)__popcll(vote));
-        base = hj_uniform(base);
-        const u64 j = base + __popcll(vote & ((1ull << lane) - 1ull));
-        if (occ && j < a.capacity) {
-            if (a.nkeys > 0) hj_store(a.keys_out[0] + j, (uint32_t)t);
-            if (a.nkeys > 1) hj_store(a.keys_out[1] + j, (uint32_t)(t >> 32));
-            if (a.counts_out) hj_store(a.counts_out + j, cnt);
-#pragma unroll
-            for (uint32_t c = 0; c < hj_agg::MAX_AGGS; ++c)
-                if (c < a.nvals) hj_store(a.sums_out[c] + j, hj_agg::result(ae.fn[c], ae.flags[c], a.merge[i].sums[c]));
-        }
-    }
-}
-
-static bool agg_args_valid(const AggArgs &aa, uint32_t min_keys, uint32_t max_keys, int cus)
-{
-    const GroupArgs &a = aa.g;
-    if (a.nkeys < min_keys || a.nkeys > max_keys || a.nvals > hj_agg::MAX_AGGS || !a.merge || !a.overflow || (a.merge_mask & (a.merge_mask + 1)) || cus < 1) return false;
-    uintptr_t all = (uintptr_t)a.select_bits;
-    for (uint32_t c = 0; c < a.nkeys; ++c) { if (!a.keys[c]) return false; all |= (uintptr_t)a.keys[c]; }
-    for (uint32_t c = 0; c < a.nvals; ++c) {
-        if (aa.fn[c] > hj_agg::MAX || (aa.flags[c] & ~hj_agg::SIGNED) || !a.vals[c] || (aa.fn[c] == hj_agg::SUM_MUL) != (aa.b[c] != nullptr)) return false;
-        all |= (uintptr_t)a.vals[c] | (uintptr_t)aa.b[c];
-    }
-    return !(all & 15);
-}
-
-// hj_launch_group_sum's grid: one workgroup per compute unit, no more than the rows have wave trips for
-int hj_launch_agg_group(const AggArgs &aa, int cus, hipStream_t stream)
-{
-    using namespace hj_group;
-    static_assert(hj_agg::MAX_AGGS == MAX_VALS && hj_agg::GROUP_BLOCK == BLOCK, "an aggregate is a slot word; the grouped road's geometry is group_sum_kernel's");
-    if (aa.g.n == 0) return HJGPU_OK;
-    if (!agg_args_valid(aa, 1, MAX_KEYS, cus)) return HJGPU_EINVAL;
-    const u64 nvec = (aa.g.n + 3) >> 2, need = (nvec + BLOCK - 1) / BLOCK;
-    const dim3 grid((uint32_t)std::min<u64>(need, (u64)cus));
-    hj_with_bool(aa.g.select_bits != nullptr, [&](auto sel) {
-        constexpr bool S = decltype(sel)::value;
-        if (aa.g.nkeys == 1) hipLaunchKernelGGL((agg_group_kernel<1, S>), grid, dim3(BLOCK), 0, stream, aa);
-        else hipLaunchKernelGGL((agg_group_kernel<2, S>), grid, dim3(BLOCK), 0, stream, aa);
-    });
-    return hipGetLastError() == hipSuccess ? HJGPU_OK : HJGPU_EHIP;
-}
-
-// agg_layout.hpp's scalar grid, no more workgroups than the rows have wave trips for
-int hj_launch_agg_scalar(const AggArgs &aa, int cus, hipStream_t stream)
-{
-    using namespace hj_agg;
-    if (aa.g.n == 0) return HJGPU_OK;
-    if (!agg_args_valid(aa, 0, 0, cus)) return HJGPU_EINVAL;
-    const u64 nvec = (aa.g.n + 3) >> 2, need = (nvec + SCALAR_BLOCK - 1) / SCALAR_BLOCK;
-    const dim3 grid((uint32_t)std::min<u64>(need, (u64)scalar_grid_of(cus)));
-    hj_with_bool(aa.g.select_bits != nullptr, [&](auto sel) {
-        constexpr bool S = decltype(sel)::value;
-        hipLaunchKernelGGL((agg_scalar_kernel<S>), grid, dim3(SCALAR_BLOCK), 0, stream, aa);
-    });
-    return hipGetLastError() == hipSuccess ? HJGPU_OK : HJGPU_EHIP;
-}
-
-int hj_launch_agg_emit(const AggEmitArgs &ae, int cus, hipStream_t stream)
-{
-    const GroupEmitArgs &a = ae.g;
-    if (!a.merge || !a.d_ngroups || a.nkeys > hj_group::MAX_KEYS || a.nvals > hj_agg::MAX_AGGS || cus < 1) return HJGPU_EINVAL;
-    const u64 need = (a.slots + 1 + 255) / 256;
-    hipLaunchKernelGGL(agg_emit_kernel, dim3((uint32_t)std::min<u64>(need, (u64)cus * 8)), dim3(256), 0, stream, ae);
-    return hipGetLastError() == hipSuccess ? HJGPU_OK : HJGPU_EHIP;
-}
-
 // ---- wide keys (hjgpu_group_by with three and four key columns; DESIGN.md section 5 "Wide keys") ---------------------------------------
 // GROUP BY (key 0, key 1, key 2 [, key 3]) COUNT(*) and hjgpu_group_agg's aggregates.  A tuple no longer fits the one 64-bit word that
 // group_lds_slot / group_merge_slot compare and swap, and there is no 128-bit compare-and-swap: the tables are wide_group_layout.hpp's -
 // a slot has a 64-bit word per key, key | 1 << 32, never 0 - and insert-or-find is that header's find_slot: word by word, a 64-bit
 // compare-and-swap 0 -> own word wherever a word is still 0 (ds_cmpst_rtn_b64 in LDS, global_atomic_cmpswap_x2 in the merge table), on to
 // the next slot at the first word that is another tuple's.  Nobody waits and no slot stays half filled.  The words of the aggregates and
-// their combines are agg_group_kernel's.
+// their combines are agg_group_kernel's (group_combine).
 
 // the two memories of find_slot: relaxed atomics of workgroup scope in LDS - `used` is group_lds_slot's ticket, taken before a slot's word
 // 0 is written and handed back when that write lost, so the table never holds more than LDS_GROUPS tuples - and of agent scope in the
@@ -1207,27 +1067,13 @@ struct WideGlobalMemory {
 // The slot of the tuple with key words w (hash h) in the merge table: the walk bounded by the slot count; group_merge_slot's overflow rule -
 // a tuple that finds the table full raises the overflow word, whoever sees it raised gives up at once
 template <int NKEYS>
-__device__ __forceinline__ u64 wide_merge_slot(const WideArgs &a, const u64 (&w)[hj_wide::MAX_KEYS], u64 h)
+__device__ __forceinline__ u64 wide_merge_slot(const decltype(WideArgs::g) &a, const u64 (&w)[hj_wide::MAX_KEYS], u64 h)
 {
     if (__hip_atomic_load(a.overflow, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return GROUP_NO_SLOT;
     WideGlobalMemory mem;
     const u64 s = hj_wide::find_slot<(uint32_t)NKEYS>(mem, a.merge, a.merge_mask, h, a.merge_mask + 1, w);
     if (s == hj_wide::NO_SLOT) atomicOr(a.overflow, 1u);
     return s;
-}
-
-// combines x into word `word` (0: the count, 1 + c: aggregate c) of the slot at `loc`: agg_combine over the wide slot
-__device__ __forceinline__ void wide_combine(hj_wide::Slot *tab, const WideArgs &a, u64 loc, uint32_t word, bool extreme, u64 x)
-{
-    if (loc & GROUP_IN_LDS) {
-        u64 *p = &tab[(uint32_t)loc].count + word;
-        if (extreme) __hip_atomic_fetch_max(p, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);                     // ds_max_u64
-        else __hip_atomic_fetch_add(p, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);                             // ds_add_u64
-    } else if (loc != GROUP_NO_SLOT) {
-        u64 *p = &a.merge[loc].count + word;
-        if (extreme) __hip_atomic_fetch_max(p, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);                         // global_atomic_umax_x2
-        else atomicAdd(p, x);                                                                                           // global_atomic_add_x2
-    }
 }
 
 // agg_group_kernel's iteration with NKEYS key columns: the mask words and key column 0 (lookup_fetch), then the further key columns and, per
@@ -1237,9 +1083,10 @@ __device__ __forceinline__ void wide_combine(hj_wide::Slot *tab, const WideArgs 
 // over the leaders stays in the kernel's body (a helper that took the trips' vectors made the compiler index them in memory).  The flush
 // combines the workgroup's occupied slots into the merge table, word by word.  No global store; no workgroup waits for another.
 template <int NKEYS, bool SEL>
-__global__ __launch_bounds__(hj_wide::BLOCK) void wide_group_kernel(WideArgs a)
+__global__ __launch_bounds__(hj_wide::BLOCK) void wide_group_kernel(WideArgs aa)
 {
     using namespace hj_wide;
+    const auto &a = aa.g;
     static_assert(NKEYS >= (int)MIN_KEYS && NKEYS <= (int)MAX_KEYS, "three or four key columns");
     static_assert(NO_SLOT == GROUP_NO_SLOT, "one word for \"no slot\" in the walk and in the locations");
     constexpr int ROWS = 4 * (int)BATCH, NB = (int)BATCH;
@@ -1253,7 +1100,7 @@ __global__ __launch_bounds__(hj_wide::BLOCK) void wide_group_kernel(WideArgs a)
     }
     __syncthreads();
     const u64 n = a.n, nvec = (n + 3) >> 2, stride = (u64)gridDim.x * BLOCK;
-    const uint32_t naggs = a.naggs;
+    const uint32_t naggs = a.nvals;
     for (u64 v0 = (u64)blockIdx.x * BLOCK + (tid & ~63u); v0 < nvec; v0 += stride * NB) {
         uint32_t nib[NB];
         uint32_t key[NKEYS][ROWS];                      // key column c of row 4 u + j of the lane
@@ -1312,15 +1159,15 @@ __global__ __launch_bounds__(hj_wide::BLOCK) void wide_group_kernel(WideArgs a)
             u64 at = find_slot<(uint32_t)NKEYS>(lds, tab, LDS_SLOTS - 1, lds_home(h), LDS_PROBES, w);
             if (at != NO_SLOT) at |= GROUP_IN_LDS;
             else at = wide_merge_slot<NKEYS>(a, w, h);
-            wide_combine(tab, a, at, 0, false, (u64)__popc((cls >> (4 * q)) & 15u));
+            group_combine(tab, a.merge, at, 0, false, (u64)__popc((cls >> (4 * q)) & 15u));
 #pragma unroll
             for (int r = 0; r < ROWS; ++r) loc[r] = q == r ? at : loc[r];
         }
         for (uint32_t c = 0; c < naggs; ++c) {
-            const uint32_t fn = a.fn[c];
-            const hj_agg::Norm norm = hj_agg::normalise(fn, a.flags[c]);
-            const uint4 *x4 = reinterpret_cast<const uint4 *>(a.a[c]);
-            const uint4 *y4 = reinterpret_cast<const uint4 *>(a.b[c]);
+            const uint32_t fn = aa.fn[c];
+            const hj_agg::Norm norm = hj_agg::normalise(fn, aa.flags[c]);
+            const uint4 *x4 = reinterpret_cast<const uint4 *>(a.vals[c]);
+            const uint4 *y4 = reinterpret_cast<const uint4 *>(aa.b[c]);
             uint4 x[NB], y[NB];
 #pragma unroll
             for (int u = 0; u < NB; ++u) {
@@ -1341,7 +1188,7 @@ __global__ __launch_bounds__(hj_wide::BLOCK) void wide_group_kernel(WideArgs a)
                 u64 at = loc[0];
 #pragma unroll
                 for (int r = 1; r < ROWS; ++r) at = q == r ? loc[r] : at;
-                wide_combine(tab, a, at, 1 + c, extreme, agg_fold_of(fn, norm, m, xq, yq));
+                group_combine(tab, a.merge, at, 1 + c, extreme, agg_fold_of(fn, norm, m, xq, yq));
             }
         }
     }
@@ -1355,25 +1202,59 @@ __global__ __launch_bounds__(hj_wide::BLOCK) void wide_group_kernel(WideArgs a)
         if (at != GROUP_NO_SLOT) {
             atomicAdd(&a.merge[at].count, tab[i].count);
             for (uint32_t c = 0; c < naggs; ++c) {
-                if (hj_agg::is_extreme(a.fn[c])) __hip_atomic_fetch_max(&a.merge[at].aggs[c], tab[i].aggs[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (hj_agg::is_extreme(aa.fn[c])) __hip_atomic_fetch_max(&a.merge[at].aggs[c], tab[i].aggs[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 else atomicAdd(&a.merge[at].aggs[c], tab[i].aggs[c]);
             }
         }
     }
 }
 
-// agg_emit_kernel over wide slots: a slot is occupied when its key word 0 is not 0; a wave's occupied slots go to the dense outputs through
-// one atomic add to the cursor, which is the count word itself (0 before the launch); rows at capacity and beyond are counted and not
-// written.  Key column c is the low half of key word c
-__global__ __launch_bounds__(256) void wide_emit_kernel(WideEmitArgs a)
+// ---- the emit of the three grouped operators --------------------------------------------------------------------------------------------
+// What the one emit body has to know of a merge table: which slots there are behind the `slots` hashed ones (EMIT_EXTRA), what a lane
+// keeps of slot i (Seen), when that slot is occupied, and where its key column c and its count lie.
+struct NarrowEmitTable {                                // group_layout.hpp: the tuple word; the slot of tuple 0 is merge[slots], occupied when its count is not 0
+    using Slot = hj_group::Slot;
+    static constexpr uint32_t MAX_KEYS = hj_group::MAX_KEYS;
+    static constexpr u64 EMIT_EXTRA = 1;
+    struct Seen { u64 t, count; };
+    __device__ __forceinline__ static Seen see(const Slot *merge, u64 i, u64 slots)
+    {
+        Seen s{0, 0};
+        if (i <= slots) { s.t = merge[i].tuple; s.count = merge[i].count; }
+        return s;
+    }
+    __device__ __forceinline__ static bool occupied(const Seen &s, u64 i, u64 slots) { return i < slots ? s.t != 0 : i == slots && s.count != 0; }
+    __device__ __forceinline__ static uint32_t key(const Seen &s, const Slot &, uint32_t c) { return (uint32_t)(c == 0 ? s.t : s.t >> 32); }
+    __device__ __forceinline__ static u64 count(const Seen &s, const Slot &) { return s.count; }
+};
+struct WideEmitTable {                                  // wide_group_layout.hpp: occupied when key word 0 is not 0; key column c is the low half of key word c
+    using Slot = hj_wide::Slot;
+    static constexpr uint32_t MAX_KEYS = hj_wide::MAX_KEYS;
+    static constexpr u64 EMIT_EXTRA = 0;
+    struct Seen { u64 w0; };
+    __device__ __forceinline__ static Seen see(const Slot *merge, u64 i, u64 slots) { return Seen{i < slots ? merge[i].key[0] : 0}; }
+    __device__ __forceinline__ static bool occupied(const Seen &s, u64, u64) { return s.w0 != 0; }
+    __device__ __forceinline__ static uint32_t key(const Seen &s, const Slot &slot, uint32_t c) { return hj_wide::key_of(c == 0 ? s.w0 : slot.key[c]); }
+    __device__ __forceinline__ static u64 count(const Seen &, const Slot &slot) { return slot.count; }
+};
+static_assert(sizeof(hj_group::Slot) - offsetof(hj_group::Slot, count) == (1 + hj_agg::MAX_AGGS) * sizeof(u64) &&
+              sizeof(hj_wide::Slot) - offsetof(hj_wide::Slot, count) == (1 + hj_agg::MAX_AGGS) * sizeof(u64), "either slot ends in its count and four words");
+
+
+// The body of the three emit kernels.  The occupied slots of the merge table go to the dense outputs, a wave's through one atomic add to
+// the cursor, which is the count word itself (0 before the launch): behind the launch it holds the number of occupied slots - the group
+// count J, or, when the overflow word was raised, the full table: a lower bound of J that is greater than capacity (the table has at least
+// 2 * capacity slots).  Rows at capacity and beyond are counted and not written.  RESULT: agg_layout.hpp's result() per aggregate column -
+// the sums leave as they are, the extremes in the column's own values (kinds: their functions).  Every store is hj_store.
+template <class Table, bool RESULT, class Args, class Kinds>
+__device__ __forceinline__ void group_emit_body(const Args &a, const Kinds &kinds)
 {
     const uint32_t lane = hj_lane();
-    const u64 stride = (u64)gridDim.x * 256;
-    for (u64 i0 = (u64)blockIdx.x * 256 + (threadIdx.x & ~63u); i0 < a.slots; i0 += stride) {
+    const u64 total = a.slots + Table::EMIT_EXTRA, stride = (u64)gridDim.x * 256;
+    for (u64 i0 = (u64)blockIdx.x * 256 + (threadIdx.x & ~63u); i0 < total; i0 += stride) {
         const u64 i = i0 + lane;
-        u64 w0 = 0;
-        if (i < a.slots) w0 = a.merge[i].key[0];
-        const bool occ = w0 != 0;
+        const typename Table::Seen seen = Table::see(a.merge, i, a.slots);
+        const bool occ = Table::occupied(seen, i, a.slots);
         const u64 vote = __ballot(occ);
         if (vote == 0) continue;
         u64 base = 0;
@@ -1381,57 +1262,113 @@ __global__ __launch_bounds__(256) void wide_emit_kernel(WideEmitArgs a)
         base = hj_uniform(base);
         const u64 j = base + __popcll(vote & ((1ull << lane) - 1ull));
         if (occ && j < a.capacity) {
-            hj_store(a.keys_out[0] + j, hj_wide::key_of(w0));
 #pragma unroll
-            for (uint32_t c = 1; c < hj_wide::MAX_KEYS; ++c)
-                if (c < a.nkeys) hj_store(a.keys_out[c] + j, hj_wide::key_of(a.merge[i].key[c]));
-            if (a.counts_out) hj_store(a.counts_out + j, a.merge[i].count);
+            for (uint32_t c = 0; c < Table::MAX_KEYS; ++c)
+                if (c < a.nkeys) hj_store(a.keys_out[c] + j, Table::key(seen, a.merge[i], c));
+            if (a.counts_out) hj_store(a.counts_out + j, Table::count(seen, a.merge[i]));
 #pragma unroll
-            for (uint32_t c = 0; c < hj_wide::MAX_AGGS; ++c)
-                if (c < a.naggs) hj_store(a.aggs_out[c] + j, hj_agg::result(a.fn[c], a.flags[c], a.merge[i].aggs[c]));
+            for (uint32_t c = 0; c < hj_agg::MAX_AGGS; ++c) {
+                if (c >= a.nvals) continue;
+                u64 word = (&a.merge[i].count)[1 + c];
+                if constexpr (RESULT) word = hj_agg::result(kinds.fn[c], kinds.flags[c], word);
+                hj_store(a.sums_out[c] + j, word);
+            }
         }
     }
 }
 
-// agg_args_valid for the wide road
-static bool wide_args_valid(const WideArgs &a, int cus)
+__global__ __launch_bounds__(256) void group_emit_kernel(GroupEmitArgs a) { group_emit_body<NarrowEmitTable, false>(a, a); }
+__global__ __launch_bounds__(256) void agg_emit_kernel(AggEmitArgs a) { group_emit_body<NarrowEmitTable, true>(a.g, a); }
+__global__ __launch_bounds__(256) void wide_emit_kernel(WideEmitArgs a) { group_emit_body<WideEmitTable, true>(a.g, a); }
+
+// The aggregation launches' check and grid: `per_cu` workgroups of `block` lanes per compute unit, no more than the rows have wave trips for
+// (launch(sel, grid): the kernel with or without a mask)
+template <class Args, class Launch>
+static int grouped_launch(const Args &a, uint32_t min_keys, uint32_t max_keys, uint32_t block, int cus, uint32_t per_cu, Launch launch)
 {
-    if (a.nkeys < hj_wide::MIN_KEYS || a.nkeys > hj_wide::MAX_KEYS || a.naggs > hj_wide::MAX_AGGS || !a.merge || !a.overflow || (a.merge_mask & (a.merge_mask + 1)) || cus < 1) return false;
-    uintptr_t all = (uintptr_t)a.select_bits;
-    for (uint32_t c = 0; c < a.nkeys; ++c) { if (!a.keys[c]) return false; all |= (uintptr_t)a.keys[c]; }
-    for (uint32_t c = 0; c < a.naggs; ++c) {
-        if (a.fn[c] > hj_agg::MAX || (a.flags[c] & ~hj_agg::SIGNED) || !a.a[c] || (a.fn[c] == hj_agg::SUM_MUL) != (a.b[c] != nullptr)) return false;
-        all |= (uintptr_t)a.a[c] | (uintptr_t)a.b[c];
+    const auto &g = a.g;
+    if (g.n == 0) return HJGPU_OK;
+    if (g.nkeys < min_keys || g.nkeys > max_keys || g.nvals > hj_agg::MAX_AGGS || !g.merge || !g.overflow || (g.merge_mask & (g.merge_mask + 1)) || cus < 1) return HJGPU_EINVAL;
+    uintptr_t all = (uintptr_t)g.select_bits;
+    for (uint32_t c = 0; c < g.nkeys; ++c) { if (!g.keys[c]) return HJGPU_EINVAL; all |= (uintptr_t)g.keys[c]; }
+    for (uint32_t c = 0; c < g.nvals; ++c) {
+        if (a.fn[c] > hj_agg::MAX || (a.flags[c] & ~hj_agg::SIGNED) || !g.vals[c] || (a.fn[c] == hj_agg::SUM_MUL) != (a.b[c] != nullptr)) return HJGPU_EINVAL;
+        all |= (uintptr_t)g.vals[c] | (uintptr_t)a.b[c];
     }
-    return !(all & 15);
+    if (all & 15) return HJGPU_EINVAL;
+    const u64 nvec = (g.n + 3) >> 2, need = (nvec + block - 1) / block;
+    const dim3 grid((uint32_t)std::min<u64>(need, (u64)cus * per_cu));
+    hj_with_bool(g.select_bits != nullptr, [&](auto sel) { launch(sel, grid); });
+    return hipGetLastError() == hipSuccess ? HJGPU_OK : HJGPU_EHIP;
 }
 
-// hj_launch_agg_group's grid: one workgroup per compute unit (its table takes most of the unit's LDS), no more than the rows have wave trips for
+// the grouped roads: one workgroup per compute unit (its table takes most of the unit's LDS)
+int hj_launch_group_sum(const AggArgs &a, int cus, hipStream_t stream)
+{
+    using namespace hj_group;
+    if (a.g.nvals > MAX_VALS) return HJGPU_EINVAL;
+    for (uint32_t c = 0; c < a.g.nvals; ++c) if (a.fn[c] != hj_agg::SUM || a.flags[c]) return HJGPU_EINVAL;  // (the kernels read no function)
+    return grouped_launch(a, 1, MAX_KEYS, BLOCK, cus, 1, [&](auto sel, dim3 grid) {
+        constexpr bool S = decltype(sel)::value;
+        if (a.g.nkeys == 1) hipLaunchKernelGGL((group_sum_kernel<1, S>), grid, dim3(BLOCK), 0, stream, a.g);
+        else hipLaunchKernelGGL((group_sum_kernel<2, S>), grid, dim3(BLOCK), 0, stream, a.g);
+    });
+}
+
+// no key column: agg_layout.hpp's scalar grid (scalar_grid_of: SCALAR_RESIDENT workgroups per compute unit)
+int hj_launch_agg_group(const AggArgs &a, int cus, hipStream_t stream)
+{
+    using namespace hj_group;
+    if (a.g.nkeys == 0)
+        return grouped_launch(a, 0, 0, hj_agg::SCALAR_BLOCK, cus, hj_agg::SCALAR_RESIDENT, [&](auto sel, dim3 grid) {
+            hipLaunchKernelGGL((agg_scalar_kernel<decltype(sel)::value>), grid, dim3(hj_agg::SCALAR_BLOCK), 0, stream, a);
+        });
+    return grouped_launch(a, 1, MAX_KEYS, BLOCK, cus, 1, [&](auto sel, dim3 grid) {
+        constexpr bool S = decltype(sel)::value;
+        if (a.g.nkeys == 1) hipLaunchKernelGGL((agg_group_kernel<1, S>), grid, dim3(BLOCK), 0, stream, a);
+        else hipLaunchKernelGGL((agg_group_kernel<2, S>), grid, dim3(BLOCK), 0, stream, a);
+    });
+}
+
 int hj_launch_wide_group(const WideArgs &a, int cus, hipStream_t stream)
 {
     using namespace hj_wide;
-    static_assert(MAX_AGGS == hj_agg::MAX_AGGS && LDS_BYTES <= LDS_BUDGET, "an aggregate is a slot word; the table fits a compute unit's LDS");
-    if (a.n == 0) return HJGPU_OK;
-    if (!wide_args_valid(a, cus)) return HJGPU_EINVAL;
-    const u64 nvec = (a.n + 3) >> 2, need = (nvec + BLOCK - 1) / BLOCK;
-    const dim3 grid((uint32_t)std::min<u64>(need, (u64)cus));
-    hj_with_bool(a.select_bits != nullptr, [&](auto sel) {
+    return grouped_launch(a, MIN_KEYS, MAX_KEYS, BLOCK, cus, 1, [&](auto sel, dim3 grid) {
         constexpr bool S = decltype(sel)::value;
-        if (a.nkeys == 3) hipLaunchKernelGGL((wide_group_kernel<3, S>), grid, dim3(BLOCK), 0, stream, a);
+        if (a.g.nkeys == 3) hipLaunchKernelGGL((wide_group_kernel<3, S>), grid, dim3(BLOCK), 0, stream, a);
         else hipLaunchKernelGGL((wide_group_kernel<4, S>), grid, dim3(BLOCK), 0, stream, a);
     });
+}
+
+// The emit launches' check and grid: one lane per slot of the merge table - `extra`: and of tuple 0's behind them -, eight workgroups per
+// compute unit at the most
+template <class Args, class Launch>
+static int group_emit_launch(const Args &e, uint32_t min_keys, uint32_t max_keys, u64 extra, int cus, Launch launch)
+{
+    const auto &g = e.g;
+    if (!g.merge || !g.d_ngroups || g.nkeys < min_keys || g.nkeys > max_keys || g.nvals > hj_agg::MAX_AGGS || (g.slots & (g.slots - 1)) || !g.slots || cus < 1) return HJGPU_EINVAL;
+    for (uint32_t c = 0; c < g.nkeys; ++c) if (!g.keys_out[c]) return HJGPU_EINVAL;
+    for (uint32_t c = 0; c < g.nvals; ++c) if (!g.sums_out[c] || e.fn[c] > hj_agg::MAX) return HJGPU_EINVAL;
+    const u64 need = (g.slots + extra + 255) / 256;
+    launch(dim3((uint32_t)std::min<u64>(need, (u64)cus * 8)));
     return hipGetLastError() == hipSuccess ? HJGPU_OK : HJGPU_EHIP;
 }
 
-int hj_launch_wide_emit(const WideEmitArgs &a, int cus, hipStream_t stream)
+int hj_launch_group_emit(const AggEmitArgs &e, int cus, hipStream_t stream)
 {
-    if (!a.merge || !a.d_ngroups || a.nkeys < hj_wide::MIN_KEYS || a.nkeys > hj_wide::MAX_KEYS || a.naggs > hj_wide::MAX_AGGS || (a.slots & (a.slots - 1)) || !a.slots || cus < 1) return HJGPU_EINVAL;
-    for (uint32_t c = 0; c < a.nkeys; ++c) if (!a.keys_out[c]) return HJGPU_EINVAL;
-    for (uint32_t c = 0; c < a.naggs; ++c) if (!a.aggs_out[c] || a.fn[c] > hj_agg::MAX) return HJGPU_EINVAL;
-    const u64 need = (a.slots + 255) / 256;
-    hipLaunchKernelGGL(wide_emit_kernel, dim3((uint32_t)std::min<u64>(need, (u64)cus * 8)), dim3(256), 0, stream, a);
-    return hipGetLastError() == hipSuccess ? HJGPU_OK : HJGPU_EHIP;
+    return group_emit_launch(e, 1, hj_group::MAX_KEYS, 1, cus, [&](dim3 grid) { hipLaunchKernelGGL(group_emit_kernel, grid, dim3(256), 0, stream, e.g); });
 }
+
+int hj_launch_agg_emit(const AggEmitArgs &e, int cus, hipStream_t stream)
+{
+    return group_emit_launch(e, 0, hj_group::MAX_KEYS, 1, cus, [&](dim3 grid) { hipLaunchKernelGGL(agg_emit_kernel, grid, dim3(256), 0, stream, e); });
+}
+
+int hj_launch_wide_emit(const WideEmitArgs &e, int cus, hipStream_t stream)
+{
+    return group_emit_launch(e, hj_wide::MIN_KEYS, hj_wide::MAX_KEYS, 0, cus, [&](dim3 grid) { hipLaunchKernelGGL(wide_emit_kernel, grid, dim3(256), 0, stream, e); });
+}
+
 
 // ---- filter (hjgpu_filter_selected; DESIGN.md section 5 "Filter") -----------------------------------------------------------------------
 // Range predicates over columns into a bitmap: row i passes when it is selected and, for every p < NPREDS, filter_layout.hpp's passes()

@@ -499,81 +499,65 @@ int hj_launch_compact_count(const uint32_t *select_bits, const hj_compact::Layou
 int hj_launch_compact(const CompactArgs &a, uint32_t ncols, hipStream_t stream);
 int hj_launch_compact_total(const u64 *counts, uint32_t ranges, u64 *d_count, hipStream_t stream);
 
-// Grouped aggregation (hjgpu_group_sum*, gen_kernels.hip; DESIGN.md section 5 "Grouped aggregation"): the tables of group_layout.hpp.
-// hj_launch_group_sum: one persistent grid; every selected row (select_bits NULL: every row) of the key and measure columns is added to
-// its tuple's slot of the merge table - `merge` holds merge_mask + 1 hashed slots and the slot of tuple 0 behind them, all zero before the
-// launch, as is *overflow, which is raised when a tuple finds no slot.  hj_launch_group_emit: the occupied slots go to the dense outputs
-// (rows below capacity only) and their number is added to *d_ngroups, which is 0 before the launch.  All columns 16-byte aligned.
-struct GroupArgs {
+// Grouped aggregation (hjgpu_group_sum*, hjgpu_group_agg*, hjgpu_group_by*, gen_kernels.hip; DESIGN.md section 5 "Grouped aggregation",
+// "Aggregate functions", "Wide keys").  Three roads over one argument shape, one emit body and one host path, which differ in the tables - group_layout.hpp's
+// (one 64-bit tuple word: up to two key columns) or wide_group_layout.hpp's (a word per key: three and four) - and in what a row contributes:
+// plain 32-bit sums, or agg_layout.hpp's function per slot word.
+// The aggregation: one persistent grid; every selected row (select_bits NULL: every row) of the key columns and of vals[c] - aggregate c's
+// column a - is combined into its tuple's slot of the merge table.  `merge` holds merge_mask + 1 hashed slots (the narrow tables: and the
+// slot of tuple 0 behind them), all zero before the launch, as is *overflow, which is raised when a tuple finds no slot.  The emit: the
+// occupied slots go to the dense outputs (rows below capacity only), the words of the extremes turned back into the columns' values, and
+// their number is added to *d_ngroups, which is 0 before the launch.  All columns 16-byte aligned.
+template <class Slot, uint32_t MAX_KEYS>
+struct GroupedArgs {
     const uint32_t *select_bits;         // NULL: every row
     u64 n;
-    const uint32_t *keys[hj_group::MAX_KEYS];
-    const uint32_t *vals[hj_group::MAX_VALS];
+    const uint32_t *keys[MAX_KEYS];
+    const uint32_t *vals[hj_agg::MAX_AGGS];
     uint32_t nkeys, nvals;
-    hj_group::Slot *merge;
+    Slot *merge;
     u64 merge_mask;
     uint32_t *overflow;
 };
-struct GroupEmitArgs {
-    const hj_group::Slot *merge;
-    u64 slots;                           // the hashed slots; the slot of tuple 0 is merge[slots]
+template <class Slot, uint32_t MAX_KEYS>
+struct GroupedEmitArgs {
+    const Slot *merge;
+    u64 slots;                           // the hashed slots (the narrow tables: the slot of tuple 0 is merge[slots])
     uint32_t nkeys, nvals;
-    uint32_t *keys_out[hj_group::MAX_KEYS];
+    uint32_t *keys_out[MAX_KEYS];
     u64 *counts_out;                     // NULL: no counts
-    u64 *sums_out[hj_group::MAX_VALS];
+    u64 *sums_out[hj_agg::MAX_AGGS];
     u64 capacity;
     u64 *d_ngroups;
 };
-int hj_launch_group_sum(const GroupArgs &a, int cus, hipStream_t stream);
-int hj_launch_group_emit(const GroupEmitArgs &a, int cus, hipStream_t stream);
-
-// Aggregate functions (hjgpu_group_agg*, gen_kernels.hip; DESIGN.md section 5 "Aggregate functions"): hj_launch_group_sum's tables and
-// pre-conditions - g.vals[c] is aggregate c's column a, g.nvals the number of aggregates - with agg_layout.hpp's function per slot word.
-// hj_launch_agg_group: g.nkeys 1 or 2, group_sum_kernel's grid.  hj_launch_agg_scalar: g.nkeys 0, no key is read and every selected row
-// goes to the slot of tuple 0 (merge[merge_mask + 1]); agg_layout.hpp's scalar grid.  hj_launch_agg_emit: hj_launch_group_emit with
-// nkeys 0 to 2 and the words of the extremes turned back into the columns' values.
-struct AggArgs {
-    GroupArgs g;
+// the functions of a road with aggregates, behind its tables' arguments g
+template <class Head>
+struct GroupedKindArgs {
+    Head g;
     const uint32_t *b[hj_agg::MAX_AGGS]; // SUM_MUL: the second factor's column
     uint32_t fn[hj_agg::MAX_AGGS], flags[hj_agg::MAX_AGGS];
 };
-struct AggEmitArgs {
-    GroupEmitArgs g;
+template <class Head>
+struct GroupedKindEmitArgs {
+    Head g;
     uint32_t fn[hj_agg::MAX_AGGS], flags[hj_agg::MAX_AGGS];
 };
+// (named structs: the kernels' symbols carry these names)
+struct GroupArgs : GroupedArgs<hj_group::Slot, hj_group::MAX_KEYS> {};
+struct GroupEmitArgs : GroupedEmitArgs<hj_group::Slot, hj_group::MAX_KEYS> {};
+struct AggArgs : GroupedKindArgs<GroupArgs> {};
+struct AggEmitArgs : GroupedKindEmitArgs<GroupEmitArgs> {};
+struct WideArgs : GroupedKindArgs<GroupedArgs<hj_wide::Slot, hj_wide::MAX_KEYS>> {};
+struct WideEmitArgs : GroupedKindEmitArgs<GroupedEmitArgs<hj_wide::Slot, hj_wide::MAX_KEYS>> {};
+// A road's two launches.  hj_launch_group_sum / _emit: g.nkeys 1 or 2, every function SUM without flags, which the kernels do not read.
+// hj_launch_agg_group / _emit: g.nkeys 0 to 2; with no key column no key is read and every selected row goes to the slot of tuple 0
+// (merge[merge_mask + 1]) through agg_layout.hpp's scalar grid.  hj_launch_wide_group / _emit: g.nkeys 3 or 4.
+int hj_launch_group_sum(const AggArgs &a, int cus, hipStream_t stream);
+int hj_launch_group_emit(const AggEmitArgs &e, int cus, hipStream_t stream);
 int hj_launch_agg_group(const AggArgs &a, int cus, hipStream_t stream);
-int hj_launch_agg_scalar(const AggArgs &a, int cus, hipStream_t stream);
-int hj_launch_agg_emit(const AggEmitArgs &a, int cus, hipStream_t stream);
-
-// Wide keys (hjgpu_group_by* with three and four key columns, gen_kernels.hip; DESIGN.md section 5 "Wide keys"): the tables of
-// wide_group_layout.hpp.  hj_launch_wide_group: hj_launch_agg_group's pre-conditions with nkeys 3 or 4 - one persistent grid; every selected
-// row is combined into its tuple's slot of the merge table, `merge` holds merge_mask + 1 slots, all zero before the launch, as is *overflow,
-// which is raised when a tuple finds no slot.  hj_launch_wide_emit: the occupied slots go to the dense outputs (rows below capacity only),
-// the extremes turned back into the columns' values, and their number is added to *d_ngroups, which is 0 before the launch.
-struct WideArgs {
-    const uint32_t *select_bits;         // NULL: every row
-    u64 n;
-    const uint32_t *keys[hj_wide::MAX_KEYS];
-    const uint32_t *a[hj_wide::MAX_AGGS], *b[hj_wide::MAX_AGGS];      // aggregate c's column a; SUM_MUL: the second factor's column
-    uint32_t fn[hj_wide::MAX_AGGS], flags[hj_wide::MAX_AGGS];
-    uint32_t nkeys, naggs;
-    hj_wide::Slot *merge;
-    u64 merge_mask;
-    uint32_t *overflow;
-};
-struct WideEmitArgs {
-    const hj_wide::Slot *merge;
-    u64 slots;
-    uint32_t nkeys, naggs;
-    uint32_t *keys_out[hj_wide::MAX_KEYS];
-    u64 *counts_out;                     // NULL: no counts
-    u64 *aggs_out[hj_wide::MAX_AGGS];
-    uint32_t fn[hj_wide::MAX_AGGS], flags[hj_wide::MAX_AGGS];
-    u64 capacity;
-    u64 *d_ngroups;
-};
+int hj_launch_agg_emit(const AggEmitArgs &e, int cus, hipStream_t stream);
 int hj_launch_wide_group(const WideArgs &a, int cus, hipStream_t stream);
-int hj_launch_wide_emit(const WideEmitArgs &a, int cus, hipStream_t stream);
+int hj_launch_wide_emit(const WideEmitArgs &e, int cus, hipStream_t stream);
 
 // Filter (hjgpu_filter_selected*, gen_kernels.hip; DESIGN.md section 5 "Filter"): one persistent grid of filter_layout.hpp's geometry.  Row
 // i < n passes when it is selected (select_bits NULL: every row) and preds[p] holds on cols[p][i] for every p < npreds; bits_out (NULL:

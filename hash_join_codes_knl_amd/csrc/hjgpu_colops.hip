@@ -70,158 +70,98 @@ static int compact_call(hjgpu_ctx *ctx, const CompactCall &c, uint64_t *count, b
     return HJGPU_OK;
 }
 
-// ---- grouped aggregation ----------------------------------------------------------
+// ---- grouped aggregation: hjgpu_group_sum, hjgpu_group_agg, hjgpu_group_by ----------
+// One path for the three entry points.  A road is what it has to know of theirs: the tables (group_layout.hpp's for up to two key columns,
+// wide_group_layout.hpp's for three and four) and the two launches over them
+template <class Args, class EmitArgs>
+struct GroupedRoad {
+    Algo algo;
+    const char *entry;                                  // the entry point's name in the overflow message
+    u64 (*merge_slots)(u64 capacity);
+    u64 (*workspace_bytes)(u64 slots);
+    int (*aggregate)(const Args &a, int cus, hipStream_t stream);
+    int (*emit)(const EmitArgs &e, int cus, hipStream_t stream);
+};
+static_assert(hj_group::WORKSPACE_HEAD == hj_wide::WORKSPACE_HEAD, "either workspace: the blocking form's count word, the overflow word, the merge table");
+static const GroupedRoad<AggArgs, AggEmitArgs> ROAD_SUMS{ALGO_GROUP_SUM, "hjgpu_group_sum", hj_group::merge_slots, hj_group::workspace_bytes, hj_launch_group_sum, hj_launch_group_emit};
+// (nkeys 0: the scalar road - every selected row goes to the slot of tuple 0, which the emit turns into J = 0 or 1)
+static const GroupedRoad<AggArgs, AggEmitArgs> ROAD_AGGREGATES{ALGO_GROUP_AGG, "hjgpu_group_agg", hj_group::merge_slots, hj_group::workspace_bytes, hj_launch_agg_group, hj_launch_agg_emit};
+static const GroupedRoad<WideArgs, WideEmitArgs> ROAD_WIDE{ALGO_GROUP_BY, "hjgpu_group_by", hj_wide::merge_slots, hj_wide::workspace_bytes, hj_launch_wide_group, hj_launch_wide_emit};
+
 // the three enqueues: the clears (the count word; for n > 0 the overflow word and the merge table), the aggregation, the emit.
 // hjgpu_get_stats afterwards: ms_histogram = the clears, ms_join = the aggregation, ms_close_gaps = the emit, ms_total = all of them
-static int group_enqueue(hjgpu_ctx *ctx, const GroupCall &g, u64 *d_ngroups, hipStream_t stream)
+template <class Args, class EmitArgs>
+static int grouped_enqueue(hjgpu_ctx *ctx, const GroupedRoad<Args, EmitArgs> &road, const GroupAggCall &g, u64 *d_ngroups, hipStream_t stream)
 {
-    const u64 slots = hj_group::merge_slots(g.capacity);
+    const u64 slots = road.merge_slots(g.capacity);
     char *ws = reinterpret_cast<char *>(ctx->group.p);
-    begin_span(ctx, ALGO_GROUP_SUM, stream);
+    begin_span(ctx, road.algo, stream);
     HIPCHK(ctx, hj_zero_async(d_ngroups, sizeof(u64), stream));
-    if (g.n) HIPCHK(ctx, hj_zero_async(ws + sizeof(u64), (size_t)(hj_group::workspace_bytes(slots) - sizeof(u64)), stream));
+    if (g.n) HIPCHK(ctx, hj_zero_async(ws + sizeof(u64), (size_t)(road.workspace_bytes(slots) - sizeof(u64)), stream));
     record(ctx, EV_S_HIST, stream);
     if (g.n) {
-        GroupArgs a{};
-        a.select_bits = g.bits; a.n = g.n; a.nkeys = g.nkeys; a.nvals = g.nvals;
-        for (uint32_t c = 0; c < g.nkeys; ++c) a.keys[c] = g.keys_in[c];
-        for (uint32_t c = 0; c < g.nvals; ++c) a.vals[c] = g.vals_in[c];
-        a.merge = reinterpret_cast<hj_group::Slot *>(ws + hj_group::WORKSPACE_HEAD);
-        a.merge_mask = slots - 1;
-        a.overflow = reinterpret_cast<uint32_t *>(ws + sizeof(u64));
-        CHK(hj_launch_group_sum(a, ctx->cus, stream));
-    }
-    record(ctx, EV_JOIN, stream);
-    if (g.n) {
-        GroupEmitArgs e{};
-        e.merge = reinterpret_cast<const hj_group::Slot *>(ws + hj_group::WORKSPACE_HEAD);
-        e.slots = slots; e.nkeys = g.nkeys; e.nvals = g.nvals; e.capacity = g.capacity; e.counts_out = reinterpret_cast<u64 *>(g.counts_out);
-        for (uint32_t c = 0; c < g.nkeys; ++c) e.keys_out[c] = g.keys_out[c];
-        for (uint32_t c = 0; c < g.nvals; ++c) e.sums_out[c] = reinterpret_cast<u64 *>(g.sums_out[c]);
-        e.d_ngroups = d_ngroups;
-        CHK(hj_launch_group_emit(e, ctx->cus, stream));
-    }
-    record(ctx, EV_GAPS, stream);
-    return HJGPU_OK;
-}
-
-// the context's workspace (group_layout.hpp; sized from the capacity): the blocking form's count word first, the overflow word, the merge table
-static int group_call(hjgpu_ctx *ctx, const GroupCall &g, uint64_t *ngroups, bool device_count, void *stream_)
-{
-    if (!ctx) return HJGPU_EINVAL;
-    hipStream_t stream = (hipStream_t)stream_;
-    CHK(colop_begin(ctx, check_group(g, ngroups, device_count), stream, ctx->group, (size_t)hj_group::workspace_bytes(hj_group::merge_slots(g.capacity))));
-    u64 *d_ngroups = reinterpret_cast<u64 *>(device_count ? (void *)ngroups : ctx->group.p);
-    CHK(group_enqueue(ctx, g, d_ngroups, stream));
-    if (device_count) return HJGPU_OK;
-    u64 got[2];
-    CHK(read_back(ctx, d_ngroups, 1, got, ngroups, stream));
-    if (got[0] > g.capacity)
-        return fail(ctx, HJGPU_EOVERFLOW, "hjgpu_group_sum: more groups than capacity (*ngroups holds a lower bound of their number that exceeds capacity; the outputs are unspecified)");
-    return HJGPU_OK;
-}
-
-// ---- aggregate functions ----------------------------------------------------------
-// group_enqueue's three enqueues and its stats mapping; the aggregation is the grouped road (nkeys 1 or 2) or the scalar road (nkeys 0:
-// every selected row goes to the slot of tuple 0, which the emit turns into J = 0 or 1)
-static int group_agg_enqueue(hjgpu_ctx *ctx, const GroupAggCall &g, u64 *d_ngroups, hipStream_t stream)
-{
-    const u64 slots = hj_group::merge_slots(g.capacity);
-    char *ws = reinterpret_cast<char *>(ctx->group.p);
-    begin_span(ctx, ALGO_GROUP_AGG, stream);
-    HIPCHK(ctx, hj_zero_async(d_ngroups, sizeof(u64), stream));
-    if (g.n) HIPCHK(ctx, hj_zero_async(ws + sizeof(u64), (size_t)(hj_group::workspace_bytes(slots) - sizeof(u64)), stream));
-    record(ctx, EV_S_HIST, stream);
-    if (g.n) {
-        AggArgs a{};
+        Args a{};
         a.g.select_bits = g.bits; a.g.n = g.n; a.g.nkeys = g.nkeys; a.g.nvals = g.naggs;
         for (uint32_t c = 0; c < g.nkeys; ++c) a.g.keys[c] = g.keys_in[c];
         for (uint32_t c = 0; c < g.naggs; ++c) { a.g.vals[c] = g.aggs[c].d_a; a.b[c] = g.aggs[c].d_b; a.fn[c] = g.aggs[c].fn; a.flags[c] = g.aggs[c].flags; }
-        a.g.merge = reinterpret_cast<hj_group::Slot *>(ws + hj_group::WORKSPACE_HEAD);
+        a.g.merge = reinterpret_cast<decltype(a.g.merge)>(ws + hj_group::WORKSPACE_HEAD);
         a.g.merge_mask = slots - 1;
         a.g.overflow = reinterpret_cast<uint32_t *>(ws + sizeof(u64));
-        CHK(g.nkeys ? hj_launch_agg_group(a, ctx->cus, stream) : hj_launch_agg_scalar(a, ctx->cus, stream));
+        CHK(road.aggregate(a, ctx->cus, stream));
     }
     record(ctx, EV_JOIN, stream);
     if (g.n) {
-        AggEmitArgs e{};
-        e.g.merge = reinterpret_cast<const hj_group::Slot *>(ws + hj_group::WORKSPACE_HEAD);
+        EmitArgs e{};
+        e.g.merge = reinterpret_cast<decltype(e.g.merge)>(ws + hj_group::WORKSPACE_HEAD);
         e.g.slots = slots; e.g.nkeys = g.nkeys; e.g.nvals = g.naggs; e.g.capacity = g.capacity; e.g.counts_out = reinterpret_cast<u64 *>(g.counts_out);
         for (uint32_t c = 0; c < g.nkeys; ++c) e.g.keys_out[c] = g.keys_out[c];
         for (uint32_t c = 0; c < g.naggs; ++c) { e.g.sums_out[c] = reinterpret_cast<u64 *>(g.aggs_out[c]); e.fn[c] = g.aggs[c].fn; e.flags[c] = g.aggs[c].flags; }
         e.g.d_ngroups = d_ngroups;
-        CHK(hj_launch_agg_emit(e, ctx->cus, stream));
+        CHK(road.emit(e, ctx->cus, stream));
     }
     record(ctx, EV_GAPS, stream);
     return HJGPU_OK;
 }
 
-// group_call's workspace, shared with hjgpu_group_sum: one context runs one call at a time, and the clears are ordered by the stream
-static int group_agg_call(hjgpu_ctx *ctx, const GroupAggCall &g, uint64_t *ngroups, bool device_count, void *stream_)
+// The context's workspace (sized from the capacity by the road's tables): the blocking form's count word first, the overflow word, the
+// merge table.  One buffer for every road, grown when needed: one context runs one call at a time, and the clears are ordered by the stream
+template <class Args, class EmitArgs>
+static int grouped_call(hjgpu_ctx *ctx, const GroupedRoad<Args, EmitArgs> &road, const Verdict &checked, const GroupAggCall &g, uint64_t *ngroups, bool device_count, void *stream_)
 {
     if (!ctx) return HJGPU_EINVAL;
     hipStream_t stream = (hipStream_t)stream_;
-    CHK(colop_begin(ctx, check_group_agg(g, ngroups, device_count), stream, ctx->group, (size_t)hj_group::workspace_bytes(hj_group::merge_slots(g.capacity))));
+    CHK(colop_begin(ctx, checked, stream, ctx->group, (size_t)road.workspace_bytes(road.merge_slots(g.capacity))));
     u64 *d_ngroups = reinterpret_cast<u64 *>(device_count ? (void *)ngroups : ctx->group.p);
-    CHK(group_agg_enqueue(ctx, g, d_ngroups, stream));
+    CHK(grouped_enqueue(ctx, road, g, d_ngroups, stream));
     if (device_count) return HJGPU_OK;
     u64 got[2];
     CHK(read_back(ctx, d_ngroups, 1, got, ngroups, stream));
-    if (got[0] > g.capacity)
-        return fail(ctx, HJGPU_EOVERFLOW, "hjgpu_group_agg: more groups than capacity (*ngroups holds a lower bound of their number that exceeds capacity; the outputs are unspecified)");
-    return HJGPU_OK;
+    if (got[0] <= g.capacity) return HJGPU_OK;
+    char text[256];
+    snprintf(text, sizeof(text), "%s: more groups than capacity (*ngroups holds a lower bound of their number that exceeds capacity; the outputs are unspecified)", road.entry);
+    return fail(ctx, HJGPU_EOVERFLOW, text);
 }
 
-// ---- GROUP BY up to four columns ----------------------------------------------------
-// the wide road (nkeys 3 or 4): group_agg_enqueue's three enqueues and its stats mapping over the tables of wide_group_layout.hpp
-static int group_by_enqueue(hjgpu_ctx *ctx, const GroupAggCall &g, u64 *d_ngroups, hipStream_t stream)
+// hjgpu_group_sum: its measures as unsigned sums (the launch takes them for what they are: its kernels read no function)
+static int group_call(hjgpu_ctx *ctx, const GroupCall &g, uint64_t *ngroups, bool device_count, void *stream_)
 {
-    const u64 slots = hj_wide::merge_slots(g.capacity);
-    char *ws = reinterpret_cast<char *>(ctx->group.p);
-    begin_span(ctx, ALGO_GROUP_BY, stream);
-    HIPCHK(ctx, hj_zero_async(d_ngroups, sizeof(u64), stream));
-    if (g.n) HIPCHK(ctx, hj_zero_async(ws + sizeof(u64), (size_t)(hj_wide::workspace_bytes(slots) - sizeof(u64)), stream));
-    record(ctx, EV_S_HIST, stream);
-    if (g.n) {
-        WideArgs a{};
-        a.select_bits = g.bits; a.n = g.n; a.nkeys = g.nkeys; a.naggs = g.naggs;
-        for (uint32_t c = 0; c < g.nkeys; ++c) a.keys[c] = g.keys_in[c];
-        for (uint32_t c = 0; c < g.naggs; ++c) { a.a[c] = g.aggs[c].d_a; a.b[c] = g.aggs[c].d_b; a.fn[c] = g.aggs[c].fn; a.flags[c] = g.aggs[c].flags; }
-        a.merge = reinterpret_cast<hj_wide::Slot *>(ws + hj_wide::WORKSPACE_HEAD);
-        a.merge_mask = slots - 1;
-        a.overflow = reinterpret_cast<uint32_t *>(ws + sizeof(u64));
-        CHK(hj_launch_wide_group(a, ctx->cus, stream));
-    }
-    record(ctx, EV_JOIN, stream);
-    if (g.n) {
-        WideEmitArgs e{};
-        e.merge = reinterpret_cast<const hj_wide::Slot *>(ws + hj_wide::WORKSPACE_HEAD);
-        e.slots = slots; e.nkeys = g.nkeys; e.naggs = g.naggs; e.capacity = g.capacity; e.counts_out = reinterpret_cast<u64 *>(g.counts_out);
-        for (uint32_t c = 0; c < g.nkeys; ++c) e.keys_out[c] = g.keys_out[c];
-        for (uint32_t c = 0; c < g.naggs; ++c) { e.aggs_out[c] = reinterpret_cast<u64 *>(g.aggs_out[c]); e.fn[c] = g.aggs[c].fn; e.flags[c] = g.aggs[c].flags; }
-        e.d_ngroups = d_ngroups;
-        CHK(hj_launch_wide_emit(e, ctx->cus, stream));
-    }
-    record(ctx, EV_GAPS, stream);
-    return HJGPU_OK;
+    const Verdict checked = check_group(g, ngroups, device_count);
+    hjgpu_aggregate sums[HJGPU_GROUP_MAX_VALS] = {};
+    if (checked.status == HJGPU_OK && g.n)
+        for (uint32_t c = 0; c < g.nvals; ++c) sums[c] = {HJGPU_AGG_SUM, 0, g.vals_in[c], nullptr};
+    return grouped_call(ctx, ROAD_SUMS, checked, {g.bits, g.n, g.nkeys, g.nvals, g.keys_in, sums, g.keys_out, g.counts_out, g.sums_out, g.capacity}, ngroups, device_count, stream_);
 }
 
-// The road is chosen by nkeys: up to two key columns are hjgpu_group_agg itself.  The wide road's workspace is group_call's buffer, grown
-// to the wide table's size when needed: one context runs one call at a time, and the clears are ordered by the stream
+static int group_agg_call(hjgpu_ctx *ctx, const GroupAggCall &g, uint64_t *ngroups, bool device_count, void *stream_)
+{
+    return grouped_call(ctx, ROAD_AGGREGATES, check_group_agg(g, ngroups, device_count), g, ngroups, device_count, stream_);
+}
+
+// The road is chosen by nkeys: up to two key columns are hjgpu_group_agg itself
 static int group_by_call(hjgpu_ctx *ctx, const GroupAggCall &g, uint64_t *ngroups, bool device_count, void *stream_)
 {
     if (g.nkeys <= HJGPU_GROUP_MAX_KEYS) return group_agg_call(ctx, g, ngroups, device_count, stream_);
-    if (!ctx) return HJGPU_EINVAL;
-    hipStream_t stream = (hipStream_t)stream_;
-    CHK(colop_begin(ctx, check_group_by(g, ngroups, device_count), stream, ctx->group, (size_t)hj_wide::workspace_bytes(hj_wide::merge_slots(g.capacity))));
-    u64 *d_ngroups = reinterpret_cast<u64 *>(device_count ? (void *)ngroups : ctx->group.p);
-    CHK(group_by_enqueue(ctx, g, d_ngroups, stream));
-    if (device_count) return HJGPU_OK;
-    u64 got[2];
-    CHK(read_back(ctx, d_ngroups, 1, got, ngroups, stream));
-    if (got[0] > g.capacity)
-        return fail(ctx, HJGPU_EOVERFLOW, "hjgpu_group_by: more groups than capacity (*ngroups holds a lower bound of their number that exceeds capacity; the outputs are unspecified)");
-    return HJGPU_OK;
+    return grouped_call(ctx, ROAD_WIDE, check_group_by(g, ngroups, device_count), g, ngroups, device_count, stream_);
 }
 
 // ---- filter -----------------------------------------------------------------------
