@@ -38,6 +38,11 @@ AGG_MIN = 2             # HJGPU_AGG_MIN: MIN(a)
 AGG_MAX = 3             # HJGPU_AGG_MAX: MAX(a)
 AGG_SIGNED = 1          # HJGPU_AGG_SIGNED: a (and b) are int32
 AGG_MAX_AGGS = 4        # HJGPU_AGG_MAX_AGGS
+ORDER_MAX_KEYS = 4      # HJGPU_ORDER_MAX_KEYS
+ORDER_MAX_COLS = 8      # HJGPU_ORDER_MAX_COLS
+ORDER_DESC = 1          # HJGPU_ORDER_DESC: this key descending
+ORDER_SIGNED = 2        # HJGPU_ORDER_SIGNED: the key column is int32 (int64 with ORDER_WIDE)
+ORDER_WIDE = 4          # HJGPU_ORDER_WIDE: the column holds 64-bit words
 
 EXPORTS = [
     "hjgpu_kernel_hash", "hjgpu_library_hash", "hjgpu_device_count", "hjgpu_create", "hjgpu_destroy", "hjgpu_last_error", "hjgpu_status_string",
@@ -56,6 +61,7 @@ EXPORTS = [
     "hjgpu_group_sum", "hjgpu_group_sum_async",
     "hjgpu_group_agg", "hjgpu_group_agg_async",
     "hjgpu_group_by", "hjgpu_group_by_async",
+    "hjgpu_order_by", "hjgpu_order_by_async",
     "hjgpu_npj", "hjgpu_phj", "hjgpu_cpra",
     "hjgpu_npj_async", "hjgpu_phj_async", "hjgpu_cpra_async", "hjgpu_phj_overlapped_async",
     "hjgpu_phj_build", "hjgpu_phj_probe", "hjgpu_phj_probe_async",
@@ -116,6 +122,16 @@ class Aggregate(C.Structure):
     """hjgpu_aggregate: fn (AGG_SUM, AGG_SUM_MUL, AGG_MIN, AGG_MAX) over the device column d_a - and d_b, the second factor, under
     AGG_SUM_MUL alone; flags: AGG_SIGNED (the columns are int32)."""
     _fields_ = [("fn", C.c_uint32), ("flags", C.c_uint32), ("d_a", C.c_void_p), ("d_b", C.c_void_p)]
+
+
+class OrderKey(C.Structure):
+    """hjgpu_order_key: the device column d_col and its flags - ORDER_DESC, ORDER_SIGNED, ORDER_WIDE."""
+    _fields_ = [("d_col", C.c_void_p), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class OrderColumn(C.Structure):
+    """hjgpu_order_column: a carried column - d_in, d_out and flags, 0 or ORDER_WIDE."""
+    _fields_ = [("d_in", C.c_void_p), ("d_out", C.c_void_p), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 class Stats(C.Structure):
@@ -318,6 +334,9 @@ def load_library(build_if_missing=True):
     L.hjgpu_group_agg_async.argtypes = agg + [vp, vp]
     L.hjgpu_group_by.argtypes = agg + [u64p, vp]
     L.hjgpu_group_by_async.argtypes = agg + [vp, vp]
+    order = [vp, vp, sz, u32, C.POINTER(OrderKey), u32, C.POINTER(OrderColumn), vp, sz]
+    L.hjgpu_order_by.argtypes = order + [u64p, vp]
+    L.hjgpu_order_by_async.argtypes = order + [vp, vp]
     L.hjgpu_npj_lookup_table_selected.argtypes = [vp, vp, sz, vp, sz, u32, vp, vp, vp, C.POINTER(Result), vp]
     join = [vp, vp, vp, sz, vp, vp, sz]
     L.hjgpu_npj.argtypes = join + [C.POINTER(NpjParams), C.POINTER(Result), C.POINTER(Output), vp]
@@ -488,7 +507,8 @@ class HjGpu:
         loop), "agg_step_rows" / "agg_scalar_step_rows" (the same for group_agg with key columns / without),
         "group_by_lds_groups" / "group_by_step_rows" (group_by with three and four key columns: the distinct groups a workgroup's wide LDS
         table holds, and the rows its whole grid covers in one iteration of its loop), "lookup_wide_step_rows" (the rows lookup_wide's
-        whole look-up grid covers in one iteration of its loop)."""
+        whole look-up grid covers in one iteration of its loop), "order_lds_rows" (the largest n that order_by sorts in one workgroup's
+        LDS), "order_ranges" / "order_chunk_rows" (order_by beyond that: the ranges its permutation is cut into, and the rows of a chunk)."""
         v = C.c_uint64()
         self._check(self.lib.hjgpu_get_counter(self.handle, name.encode(), C.byref(v)))
         return v.value
@@ -826,6 +846,35 @@ class HjGpu:
         nk, kin, na, ag, kout, cout, aout, capacity = self._agg_args(keys_in, aggs, keys_out, aggs_out, counts_out, capacity, "group_by")
         self._check(self.lib.hjgpu_group_by_async(self.handle, self._ptr(select_bits), n, nk, kin, na, ag, kout, cout, aout, capacity,
                                                   self._ptr(d_ngroups), stream))
+
+    # ---- ORDER BY up to four keys with LIMIT over the selected rows -------------------------------------------------------------------
+    def _order_args(self, n, keys, cols_in, cols_out, rows_out, limit):
+        keys, cols_in, cols_out = list(keys or ()), list(cols_in or ()), list(cols_out or ())
+        if len(cols_in) != len(cols_out):
+            raise ValueError("order_by: %d input columns, %d output columns" % (len(cols_in), len(cols_out)))
+        krows = [k if isinstance(k, OrderKey) else OrderKey(self._ptr(k[0]), int(k[1]), 0) for k in keys]
+        crows = []
+        for cin, cout in zip(cols_in, cols_out):                        # a column, or (column, flags); a DeviceColumn of 8-byte words is ORDER_WIDE
+            cin, flags = cin if isinstance(cin, tuple) else (cin, ORDER_WIDE if isinstance(cin, DeviceColumn) and cin.dtype.itemsize == 8 else 0)
+            crows.append(OrderColumn(self._ptr(cin), self._ptr(cout), int(flags), 0))
+        return (len(krows), (OrderKey * len(krows))(*krows) if krows else None, len(crows), (OrderColumn * len(crows))(*crows) if crows else None,
+                self._ptr(rows_out), n if limit is None else limit)
+
+    def order_by(self, select_bits, n, keys, cols_in, cols_out, rows_out=None, limit=None, stream=None):
+        """hjgpu_order_by: the rows whose bit is set in select_bits (match_bits' layout; None: every row) ordered by keys - a list of
+        (column, flags), flags of ORDER_DESC, ORDER_SIGNED and ORDER_WIDE (a uint64 column) - and, where every key ties, by ascending row
+        number.  For j < min(J, limit): rows_out[j] (uint32; None: none) = the j-th row's number, cols_out[c][j] = cols_in[c][that row].
+        An entry of cols_in is a column - a DeviceColumn of 8-byte words is carried as such - or (column, flags).  limit None: n.
+        Returns J, the number of selected rows, whatever limit is."""
+        nk, ks, nc, cs, rows, limit = self._order_args(n, keys, cols_in, cols_out, rows_out, limit)
+        count = C.c_uint64()
+        self._check(self.lib.hjgpu_order_by(self.handle, self._ptr(select_bits), n, nk, ks, nc, cs, rows, limit, C.byref(count), stream))
+        return count.value
+
+    def order_by_async(self, select_bits, n, keys, cols_in, cols_out, rows_out, limit, d_count, stream=None):
+        """hjgpu_order_by_async: enqueue only; the number of selected rows goes to d_count (uint64 in device memory)"""
+        nk, ks, nc, cs, rows, limit = self._order_args(n, keys, cols_in, cols_out, rows_out, limit)
+        self._check(self.lib.hjgpu_order_by_async(self.handle, self._ptr(select_bits), n, nk, ks, nc, cs, rows, limit, self._ptr(d_count), stream))
 
     # ---- whole joins ------------------------------------------------------------------
     def _join(self, fn, params, rk, rv, inner, sk, sv, outer, out, stream):

@@ -1,4 +1,4 @@
-// colop_checks.hpp - what the column operators (hjgpu_compact_selected, hjgpu_group_sum, hjgpu_group_agg, hjgpu_group_by, hjgpu_filter_selected, hjgpu_gather_selected, hjgpu_lookup_wide: hjgpu_colops.hip)
+// colop_checks.hpp - what the column operators (hjgpu_compact_selected, hjgpu_group_sum, hjgpu_group_agg, hjgpu_group_by, hjgpu_filter_selected, hjgpu_gather_selected, hjgpu_lookup_wide, hjgpu_order_by: hjgpu_colops.hip)
 // and the selected look-ups refuse from their arguments alone, before anything is allocated or enqueued (DESIGN.md section 5 "Argument checks
 // of the column operators").  Plain host C++, no HIP and no context: a check returns {status, text}, its caller hands that to fail().
 // tests/test_colop_checks.py compiles it with g++ and compares every decision with the hand-written checkers it replaced.
@@ -16,6 +16,7 @@
 #include "group_layout.hpp"
 #include "wide_group_layout.hpp"
 #include "wide_lookup_layout.hpp"
+#include "order_layout.hpp"
 
 namespace colop {
 
@@ -338,6 +339,60 @@ inline Verdict check_lookup_wide(const LookupWideCall &c, const hjgpu_result *d_
     t.write(c.vals_out, obytes, 16, "d_vals_out");
     t.write(c.match_bits, bitmap_bytes(c.outer), 16, "d_match_bits", mask);
     t.write(d_result, sizeof(hjgpu_result), 16, "d_result");
+    return check_operands(t);
+}
+
+// ---- hjgpu_order_by ---------------------------------------------------------------------------------------------------------------------------
+struct OrderCall {
+    const uint32_t *bits;                               // NULL: every row
+    size_t n;
+    uint32_t nkeys;
+    const hjgpu_order_key *keys;                        // host arrays, copied by value
+    uint32_t ncols;
+    const hjgpu_order_column *cols;
+    uint32_t *rows_out;
+    size_t limit;
+};
+
+static_assert(MAX_OPERANDS >= 1 + HJGPU_ORDER_MAX_KEYS + 2 * HJGPU_ORDER_MAX_COLS + 2, "the operand table holds an ordering's operands");
+static_assert(hj_order::MAX_KEYS == HJGPU_ORDER_MAX_KEYS && hj_order::MAX_COLS == HJGPU_ORDER_MAX_COLS && hj_order::DESC == HJGPU_ORDER_DESC &&
+              hj_order::SIGNED == HJGPU_ORDER_SIGNED && hj_order::WIDE == HJGPU_ORDER_WIDE, "order_layout.hpp speaks the header's flags");
+
+// not in place: an output is checked over its first min(limit, n) elements
+inline Verdict check_order_by(const OrderCall &o, const uint64_t *count, bool device_count)
+{
+    if (!count) return refuse(HJGPU_EINVAL, "null count pointer");
+    if (device_count && ((uintptr_t)count & 7)) return refuse(HJGPU_EALIGN, "d_count must be 8-byte aligned");
+    if (o.nkeys == 0) return refuse(HJGPU_EINVAL, "nkeys must be 1 to HJGPU_ORDER_MAX_KEYS (4): with no key the call is hjgpu_compact_selected");
+    if (o.nkeys > HJGPU_ORDER_MAX_KEYS) return refuse(HJGPU_EINVAL, "nkeys must be 1 to HJGPU_ORDER_MAX_KEYS (4)");
+    if (o.ncols > HJGPU_ORDER_MAX_COLS) return refuse(HJGPU_EINVAL, "ncols must not exceed HJGPU_ORDER_MAX_COLS (8)");
+    if (o.n > 0xFFFFFFFFull) return refuse(HJGPU_EINVAL, "n must not exceed 0xFFFFFFFF: a row number is a uint32");
+    if (o.n == 0) return no_objection();                      // nothing is read, nothing but the count is written: anything else may be NULL
+    if (!o.keys) return refuse(HJGPU_EINVAL, "null key array");
+    if (o.ncols && !o.cols) return refuse(HJGPU_EINVAL, "null column array");
+    for (uint32_t k = 0; k < o.nkeys; ++k) {
+        const hjgpu_order_key &key = o.keys[k];
+        if (key.flags & ~(HJGPU_ORDER_DESC | HJGPU_ORDER_SIGNED | HJGPU_ORDER_WIDE))
+            return refuse(HJGPU_EINVAL, "key %u: unknown flag (HJGPU_ORDER_DESC, _SIGNED and _WIDE are defined)", k);
+        if (key.reserved) return refuse(HJGPU_EINVAL, "key %u: the reserved word must be 0", k);
+        if (!key.d_col) return refuse(HJGPU_EINVAL, "key %u: null d_col", k);
+    }
+    for (uint32_t c = 0; c < o.ncols; ++c) {
+        const hjgpu_order_column &col = o.cols[c];
+        if (col.flags & ~HJGPU_ORDER_WIDE) return refuse(HJGPU_EINVAL, "column %u: unknown flag (HJGPU_ORDER_WIDE is defined)", c);
+        if (col.reserved) return refuse(HJGPU_EINVAL, "column %u: the reserved word must be 0", c);
+        if (!col.d_in) return refuse(HJGPU_EINVAL, "column %u: null d_in", c);
+        if (!col.d_out) return refuse(HJGPU_EINVAL, "column %u: null d_out", c);
+    }
+    Operands t;
+    const size_t m = o.limit < o.n ? o.limit : o.n;
+    auto width = [](uint32_t flags) -> size_t { return (flags & HJGPU_ORDER_WIDE) ? sizeof(uint64_t) : sizeof(uint32_t); };
+    t.read(o.bits, bitmap_bytes(o.n), 16, "d_select_bits");
+    for (uint32_t k = 0; k < o.nkeys; ++k) t.read(o.keys[k].d_col, o.n * width(o.keys[k].flags), 16, "a key column");
+    for (uint32_t c = 0; c < o.ncols; ++c) t.read(o.cols[c].d_in, o.n * width(o.cols[c].flags), 16, "a carried input column");
+    for (uint32_t c = 0; c < o.ncols; ++c) t.write(o.cols[c].d_out, m * width(o.cols[c].flags), 16, "an output column");
+    t.write(o.rows_out, m * sizeof(uint32_t), 16, "d_rows_out");
+    if (device_count) t.write(count, sizeof(uint64_t), 8, "d_count");
     return check_operands(t);
 }
 

@@ -1763,3 +1763,380 @@ int hj_launch_wide_lookup(const WideLookupArgs &a, uint32_t nkeys, int cus, hipS
     });
     return hipGetLastError() == hipSuccess ? HJGPU_OK : HJGPU_EHIP;
 }
+
+// ---- order by (hjgpu_order_by; DESIGN.md section 5 "Order by") ------------------------------------------------------------------------------
+// A least-significant-digit radix sort of a PERMUTATION of row numbers: every pass of order_layout.hpp is a stable counting sort by one
+// 8-bit digit of key[perm[i]].  Both roads rank a chunk through ONE body, order_rank_chunk; no workgroup ever waits for another.
+
+// entry k of a small kernel-argument array, k uniform but not a constant (selects: a run-time index would put the array into scratch)
+template <class T, int N>
+__device__ __forceinline__ T order_pick(T const (&v)[N], uint32_t k)
+{
+    T x = v[0];
+#pragma unroll
+    for (int i = 1; i < N; ++i) if (k == (uint32_t)i) x = v[i];
+    return x;
+}
+
+template <int BLOCK>
+struct OrderRankLds {
+    uint32_t wave_hist[BLOCK / 64][hj_order::DIGITS];   // a wave's running count per digit, then its first rank among the chunk's elements of that digit
+    uint32_t start[hj_order::DIGITS];                   // the chunk's elements of smaller digits
+    uint32_t scan[BLOCK / 64 + 1];
+};
+
+// Rank a chunk stably by digit.  A chunk is BLOCK * ITEMS elements in wave-striped order: element i of lane L of wave w stands at
+// position w * 64 * ITEMS + i * 64 + L.  rank[i] = the elements of a smaller digit + the elements of the same digit at an earlier
+// position; an invalid element has no rank and counts nowhere.  Inside a wave and step the lanes of one digit find each other by eight
+// ballots (peers); all of them read the wave's count of the digit before the first of them adds their number to it - a wave's LDS
+// instructions are performed in the order they were issued.  Thread d < 256 then owns digit d: it turns the waves' counts into their
+// exclusive prefix, and a scan over the digits gives the chunk's; its count and first rank come back in my_count / my_start.
+// Every thread of the workgroup calls it; four workgroup barriers.  BLOCK >= 256.
+template <int BLOCK, int ITEMS>
+__device__ __forceinline__ void order_rank_chunk(OrderRankLds<BLOCK> &s, const uint32_t (&dig)[ITEMS], const bool (&valid)[ITEMS],
+                                                 uint32_t (&rank)[ITEMS], uint32_t &my_count, uint32_t &my_start)
+{
+    static_assert(BLOCK >= (int)hj_order::DIGITS && BLOCK % 64 == 0, "a thread per digit");
+    constexpr int NW = BLOCK / 64;
+    const uint32_t wave = threadIdx.x >> 6, lane = hj_lane();
+    for (uint32_t e = lane; e < hj_order::DIGITS; e += 64) s.wave_hist[wave][e] = 0;
+    compact_wave_sync();
+    const u64 before = (1ull << lane) - 1ull;
+#pragma unroll
+    for (int i = 0; i < ITEMS; ++i) {
+        u64 peers = __ballot(valid[i]);
+#pragma unroll
+        for (uint32_t b = 0; b < hj_order::DIGIT_BITS; ++b) {
+            const bool bit = (dig[i] >> b) & 1u;
+            const u64 has = __ballot(bit);
+            peers &= bit ? has : ~has;
+        }
+        const uint32_t earlier = __popcll(peers & before);
+        uint32_t seen = 0;
+        if (valid[i]) seen = s.wave_hist[wave][dig[i]];
+        compact_wave_sync();
+        if (valid[i] && earlier == 0) s.wave_hist[wave][dig[i]] = seen + (uint32_t)__popcll(peers);
+        compact_wave_sync();
+        rank[i] = seen + earlier;
+    }
+    hj_barrier_lds();
+    uint32_t c = 0;
+    if (threadIdx.x < hj_order::DIGITS) {
+#pragma unroll
+        for (int w = 0; w < NW; ++w) { const uint32_t x = s.wave_hist[w][threadIdx.x]; s.wave_hist[w][threadIdx.x] = c; c += x; }
+    }
+    const uint32_t first = block_exclusive_scan<BLOCK, uint32_t>(c, s.scan);
+    if (threadIdx.x < hj_order::DIGITS) s.start[threadIdx.x] = first;
+    my_count = c; my_start = first;
+    hj_barrier_lds();
+#pragma unroll
+    for (int i = 0; i < ITEMS; ++i)
+        if (valid[i]) rank[i] += s.start[dig[i]] + s.wave_hist[wave][dig[i]];
+}
+
+// The LDS road: ONE workgroup.  Thread t turns the mask's byte of rows [8 t, 8 t + 8) into row numbers (a block scan of the popcounts: the
+// selected row numbers ascending, in LDS), then every lane holds LDS_ITEMS elements of the wave-striped order: the row number and, key by key
+// from the last to the first, the key's normalised word - read once per key column.  A pass ranks the chunk, every element goes to its
+// rank in LDS with its key and comes back by position.  A pass in which one digit holds every row changes nothing and is skipped: thread d
+// sees it in its count, the decision travels through LDS and is the same for every thread.  At the end the first min(J, limit) elements
+// store their row number and fetch and store the carried columns, 256 or 512 contiguous bytes per wave instruction.
+__global__ __launch_bounds__(hj_order::LDS_BLOCK) void order_lds_kernel(OrderLdsArgs a)
+{
+    using namespace hj_order;
+    constexpr int B = (int)LDS_BLOCK, IT = (int)LDS_ITEMS;
+    static_assert(LDS_ITEMS == 8, "a thread owns one byte of the mask");
+    __shared__ OrderRankLds<B> s;
+    __shared__ u64 skey[LDS_ROWS];
+    __shared__ uint32_t sperm[LDS_ROWS];
+    __shared__ uint32_t same;
+    const uint32_t tid = threadIdx.x, n = a.n;
+    if (tid == 0) same = 0xFFFFFFFFu;
+    const uint32_t r0 = tid * 8u;
+    uint32_t bits = 0;
+    if (r0 < n) {
+        bits = a.select_bits ? (a.select_bits[r0 >> 5] >> (r0 & 31u)) & 0xFFu : 0xFFu;
+        if (n - r0 < 8u) bits &= (1u << (n - r0)) - 1u;
+    }
+    uint32_t at = block_exclusive_scan<B, uint32_t>((uint32_t)__popc(bits), s.scan);
+    const uint32_t J = hj_uniform(s.scan[B / 64]);
+#pragma unroll
+    for (uint32_t j = 0; j < 8u; ++j)
+        if ((bits >> j) & 1u) sperm[at++] = r0 + j;
+    __syncthreads();
+    const uint32_t pos0 = (tid >> 6) * (uint32_t)(IT * 64) + hj_lane();
+    uint32_t p[IT];
+    bool valid[IT];
+#pragma unroll
+    for (int i = 0; i < IT; ++i) {
+        valid[i] = pos0 + i * 64 < J;
+        p[i] = valid[i] ? sperm[pos0 + i * 64] : 0u;
+    }
+    __syncthreads();
+    uint32_t pass = 0;
+    for (uint32_t k = a.nkeys; k-- > 0;) {
+        const void *col = order_pick(a.keys, k);
+        const uint32_t flags = order_pick(a.key_flags, k);
+        u64 key[IT];
+#pragma unroll
+        for (int i = 0; i < IT; ++i) {
+            u64 x = 0;
+            if (valid[i]) x = (flags & WIDE) ? reinterpret_cast<const u64 *>(col)[p[i]] : (u64) reinterpret_cast<const uint32_t *>(col)[p[i]];
+            key[i] = norm(x, flags);
+        }
+        const uint32_t nd = digits_of(flags);
+        for (uint32_t d = 0; d < nd; ++d, ++pass) {
+            uint32_t dig[IT], rank[IT], count, first;
+#pragma unroll
+            for (int i = 0; i < IT; ++i) dig[i] = digit(key[i], d);
+            order_rank_chunk<B, IT>(s, dig, valid, rank, count, first);
+            if (tid < DIGITS && count == J) same = pass;
+            hj_barrier_lds();
+            if (same == pass) continue;                                 // (uniform: every thread reads the same word)
+#pragma unroll
+            for (int i = 0; i < IT; ++i)
+                if (valid[i]) { skey[rank[i]] = key[i]; sperm[rank[i]] = p[i]; }
+            hj_barrier_lds();
+#pragma unroll
+            for (int i = 0; i < IT; ++i)
+                if (valid[i]) { key[i] = skey[pos0 + i * 64]; p[i] = sperm[pos0 + i * 64]; }
+            hj_barrier_lds();
+        }
+    }
+    if (tid == 0) hj_store(a.d_count, (u64)J);
+    const uint32_t m = (u64)J < a.limit ? J : (uint32_t)a.limit;
+    if (a.rows_out) {
+#pragma unroll
+        for (int i = 0; i < IT; ++i)
+            if (pos0 + i * 64 < m) hj_store(a.rows_out + pos0 + i * 64, p[i]);
+    }
+    for (uint32_t c = 0; c < a.ncols; ++c) {
+        const void *in = order_pick(a.in, c);
+        void *out = order_pick(a.out, c);
+        if ((a.wide_cols >> c) & 1u) {
+            u64 x[IT];
+#pragma unroll
+            for (int i = 0; i < IT; ++i) x[i] = pos0 + i * 64 < m ? reinterpret_cast<const u64 *>(in)[p[i]] : 0ull;
+#pragma unroll
+            for (int i = 0; i < IT; ++i)
+                if (pos0 + i * 64 < m) hj_store(reinterpret_cast<u64 *>(out) + pos0 + i * 64, x[i]);
+        } else {
+            uint32_t x[IT];
+#pragma unroll
+            for (int i = 0; i < IT; ++i) x[i] = pos0 + i * 64 < m ? reinterpret_cast<const uint32_t *>(in)[p[i]] : 0u;
+#pragma unroll
+            for (int i = 0; i < IT; ++i)
+                if (pos0 + i * 64 < m) hj_store(reinterpret_cast<uint32_t *>(out) + pos0 + i * 64, x[i]);
+        }
+    }
+}
+
+// The device road's initial permutation under a NULL mask: perm[i] = i for i < rows in 16-byte stores (the tail by words), *d_count = count
+__global__ __launch_bounds__(256) void order_iota_kernel(uint32_t *perm, u64 rows, u64 count, u64 *d_count)
+{
+    const u64 t = (u64)blockIdx.x * 256 + threadIdx.x, stride = (u64)gridDim.x * 256, nvec = rows >> 2;
+    for (u64 v = t; v < nvec; v += stride) {
+        const uint32_t r = (uint32_t)(v << 2);
+        hj_store(reinterpret_cast<uint4 *>(perm) + v, make_uint4(r, r + 1u, r + 2u, r + 3u));
+    }
+    if (t < (rows & 3)) hj_store(perm + (nvec << 2) + t, (uint32_t)((nvec << 2) + t));
+    if (t == 0) hj_store(d_count, count);
+}
+
+// the live end of range g of the current permutation: the ranges are laid out from n, the permutation holds *d_count elements
+__device__ __forceinline__ u64 order_range_end(const OrderPassArgs &a, uint32_t g, u64 live)
+{
+    const u64 e = a.lay.end(g);
+    return e < live ? e : live;
+}
+
+// a chunk's elements in wave-striped order: the row number and the pass's digit of its key (one 32-bit word of the key column per row)
+template <int ITEMS>
+__device__ __forceinline__ void order_load_chunk(const OrderPassArgs &a, u64 chunk0, u64 end, uint32_t (&p)[ITEMS], uint32_t (&dig)[ITEMS], bool (&valid)[ITEMS])
+{
+    const u64 pos0 = chunk0 + (u64)(threadIdx.x >> 6) * (ITEMS * 64) + hj_lane();
+#pragma unroll
+    for (int i = 0; i < ITEMS; ++i) {
+        valid[i] = pos0 + i * 64 < end;
+        p[i] = valid[i] ? a.perm_in[pos0 + i * 64] : 0u;
+    }
+#pragma unroll
+    for (int i = 0; i < ITEMS; ++i) {
+        const uint32_t w = valid[i] ? a.key_words[(u64)p[i] * a.pass.stride + a.pass.word] : 0u;
+        dig[i] = hj_order::pass_digit(w, a.pass.xor_mask, a.pass.shift);
+    }
+}
+
+// A pass, launch 1: workgroup g counts the digits of its range in LDS (a wave whose lanes all hold one digit adds their number once: the
+// constant high bytes of a 64-bit sum), stores counts[digit * ranges + g] and adds what it has of a digit to the pass's totals.
+__global__ __launch_bounds__(hj_order::BLOCK) void order_histogram_kernel(OrderPassArgs a)
+{
+    using namespace hj_order;
+    __shared__ uint32_t hist[BLOCK / 64][DIGITS];
+    const uint32_t tid = threadIdx.x, wave = tid >> 6, g = blockIdx.x;
+#pragma unroll
+    for (uint32_t w = 0; w < BLOCK / 64; ++w) hist[w][tid] = 0;
+    __syncthreads();
+    const u64 begin = a.lay.begin(g), end = order_range_end(a, g, *a.d_count);
+    for (u64 chunk0 = begin; chunk0 < end; chunk0 += CHUNK_ROWS) {
+        uint32_t p[ITEMS], dig[ITEMS];
+        bool valid[ITEMS];
+        order_load_chunk<(int)ITEMS>(a, chunk0, end, p, dig, valid);
+#pragma unroll
+        for (int i = 0; i < (int)ITEMS; ++i) {
+            const u64 live = __ballot(valid[i]);
+            if (live == 0) continue;
+            const uint32_t d0 = (uint32_t)__builtin_amdgcn_readlane((int)dig[i], __ffsll((long long)live) - 1);
+            if (__ballot(valid[i] && dig[i] != d0) == 0) {
+                if (hj_lane() == 0) atomicAdd(&hist[wave][d0], (uint32_t)__popcll(live));
+            } else if (valid[i]) atomicAdd(&hist[wave][dig[i]], 1u);
+        }
+    }
+    __syncthreads();
+    uint32_t c = 0;
+#pragma unroll
+    for (uint32_t w = 0; w < BLOCK / 64; ++w) c += hist[w][tid];
+    hj_store(&a.counts[(size_t)tid * a.lay.ranges + g], c);
+    if (c) atomicAdd(&a.totals[tid], c);
+}
+
+// A pass, launch 2: workgroup d scans digit d's row of the counts over the ranges, from the total of the smaller digits:
+// bases[d * ranges + g] = where range g's first element of digit d goes
+__global__ __launch_bounds__(256) void order_scan_kernel(OrderPassArgs a)
+{
+    using namespace hj_order;
+    static_assert(MAX_RANGES <= 4 * 256 && DIGITS == 256, "four ranges per thread, a workgroup per digit");
+    __shared__ uint32_t red[4];
+    __shared__ uint32_t scan[256 / 64 + 1];
+    const uint32_t tid = threadIdx.x, d = blockIdx.x, ranges = a.lay.ranges;
+    uint32_t below = tid < d ? a.totals[tid] : 0u;
+    below = wave_reduce_sum(below);
+    if (hj_lane() == 0) red[tid >> 6] = below;
+    __syncthreads();
+    below = red[0] + red[1] + red[2] + red[3];
+    uint32_t c[4], sum = 0;
+#pragma unroll
+    for (uint32_t j = 0; j < 4; ++j) {
+        c[j] = tid * 4 + j < ranges ? a.counts[(size_t)d * ranges + tid * 4 + j] : 0u;
+        sum += c[j];
+    }
+    uint32_t at = below + block_exclusive_scan<256, uint32_t>(sum, scan);
+#pragma unroll
+    for (uint32_t j = 0; j < 4; ++j) {
+        if (tid * 4 + j < ranges) hj_store(&a.bases[(size_t)d * ranges + tid * 4 + j], at);
+        at += c[j];
+    }
+}
+
+// A pass, launch 3: workgroup g walks its range chunk by chunk, in order.  Thread d keeps where the range's next element of digit d goes
+// (from bases, advanced by every chunk's count).  A chunk is ranked by order_rank_chunk, its row numbers go to their ranks in LDS - the
+// chunk sorted by digit - and leave from there: consecutive lanes store consecutive elements, which go to consecutive addresses as long
+// as the digit stays the same.  Positions are 32-bit: the permutation has at most 2^32 - 1 elements.
+__global__ __launch_bounds__(hj_order::BLOCK) void order_scatter_kernel(OrderPassArgs a)
+{
+    using namespace hj_order;
+    __shared__ OrderRankLds<(int)BLOCK> s;
+    __shared__ uint32_t sorted[CHUNK_ROWS], sdig[CHUNK_ROWS];
+    __shared__ uint32_t shift_of[DIGITS];               // digit d's elements: rank r of the chunk goes to position shift_of[d] + r (modulo 2^32)
+    const uint32_t tid = threadIdx.x, g = blockIdx.x;
+    const u64 begin = a.lay.begin(g), end = order_range_end(a, g, *a.d_count);
+    uint32_t next = 0;
+    if (begin < end) next = a.bases[(size_t)tid * a.lay.ranges + g];
+    for (u64 chunk0 = begin; chunk0 < end; chunk0 += CHUNK_ROWS) {
+        uint32_t p[ITEMS], dig[ITEMS], rank[ITEMS], count, first;
+        bool valid[ITEMS];
+        order_load_chunk<(int)ITEMS>(a, chunk0, end, p, dig, valid);
+        order_rank_chunk<(int)BLOCK, (int)ITEMS>(s, dig, valid, rank, count, first);
+        shift_of[tid] = next - first;
+        next += count;
+#pragma unroll
+        for (int i = 0; i < (int)ITEMS; ++i)
+            if (valid[i]) { sorted[rank[i]] = p[i]; sdig[rank[i]] = dig[i]; }
+        hj_barrier_lds();
+        const uint32_t m = end - chunk0 < CHUNK_ROWS ? (uint32_t)(end - chunk0) : CHUNK_ROWS;
+        for (uint32_t r = tid; r < m; r += BLOCK) hj_store(a.perm_out + (size_t)(uint32_t)(shift_of[sdig[r]] + r), sorted[r]);
+        hj_barrier_lds();
+    }
+}
+
+// The last launch: for j < min(*d_count, limit), rows_out[j] = perm[j] and out[c][j] = in[c][perm[j]], 4- or 8-byte elements
+__global__ __launch_bounds__(256) void order_gather_kernel(OrderGatherArgs a)
+{
+    const u64 live = *a.d_count, m = live < a.limit ? live : a.limit, stride = (u64)gridDim.x * 256;
+    for (u64 j = (u64)blockIdx.x * 256 + threadIdx.x; j < m; j += stride) {
+        const uint32_t r = a.perm[j];
+        if (a.rows_out) hj_store(a.rows_out + j, r);
+        for (uint32_t c = 0; c < a.ncols; ++c) {
+            const void *in = order_pick(a.in, c);
+            void *out = order_pick(a.out, c);
+            if ((a.wide_cols >> c) & 1u) hj_store(reinterpret_cast<u64 *>(out) + j, reinterpret_cast<const u64 *>(in)[r]);
+            else hj_store(reinterpret_cast<uint32_t *>(out) + j, reinterpret_cast<const uint32_t *>(in)[r]);
+        }
+    }
+}
+
+static bool order_aligned(std::initializer_list<const void *> ps)
+{
+    uintptr_t all = 0;
+    for (const void *p : ps) all |= (uintptr_t)p;
+    return (all & 15) == 0;
+}
+
+int hj_launch_order_lds(const OrderLdsArgs &a, hipStream_t stream)
+{
+    using namespace hj_order;
+    if (a.n == 0 || a.n > LDS_ROWS || a.nkeys < 1 || a.nkeys > MAX_KEYS || a.ncols > MAX_COLS || !a.d_count || ((uintptr_t)a.d_count & 7)) return HJGPU_EINVAL;
+    if (!order_aligned({a.select_bits, a.rows_out})) return HJGPU_EINVAL;
+    for (uint32_t k = 0; k < a.nkeys; ++k) if (!a.keys[k] || !order_aligned({a.keys[k]})) return HJGPU_EINVAL;
+    for (uint32_t c = 0; c < a.ncols; ++c) if (!a.in[c] || !a.out[c] || !order_aligned({a.in[c], a.out[c]})) return HJGPU_EINVAL;
+    hipLaunchKernelGGL(order_lds_kernel, dim3(1), dim3(LDS_BLOCK), 0, stream, a);
+    return hipGetLastError() == hipSuccess ? HJGPU_OK : HJGPU_EHIP;
+}
+
+int hj_launch_order_iota(uint32_t *perm, u64 rows, u64 count, u64 *d_count, int cus, hipStream_t stream)
+{
+    if ((rows && !perm) || !d_count || !order_aligned({perm}) || ((uintptr_t)d_count & 7) || cus < 1) return HJGPU_EINVAL;
+    const u64 need = ((rows >> 2) + 255) / 256;
+    const dim3 grid((uint32_t)std::max<u64>(1, std::min<u64>(need, (u64)cus * 8)));
+    hipLaunchKernelGGL(order_iota_kernel, grid, dim3(256), 0, stream, perm, rows, count, d_count);
+    return hipGetLastError() == hipSuccess ? HJGPU_OK : HJGPU_EHIP;
+}
+
+static bool order_pass_ok(const OrderPassArgs &a)
+{
+    return a.perm_in && a.perm_out && a.perm_in != a.perm_out && a.key_words && a.d_count && a.counts && a.bases && a.totals &&
+           a.lay.ranges >= 1 && a.lay.ranges <= hj_order::MAX_RANGES && a.lay.n <= 0xFFFFFFFFull && a.pass.stride >= 1 && a.pass.stride <= 2 &&
+           a.pass.word < a.pass.stride && a.pass.shift < 32;
+}
+
+int hj_launch_order_histogram(const OrderPassArgs &a, hipStream_t stream)
+{
+    if (!order_pass_ok(a)) return HJGPU_EINVAL;
+    hipLaunchKernelGGL(order_histogram_kernel, dim3(a.lay.ranges), dim3(hj_order::BLOCK), 0, stream, a);
+    return hipGetLastError() == hipSuccess ? HJGPU_OK : HJGPU_EHIP;
+}
+
+int hj_launch_order_scan(const OrderPassArgs &a, hipStream_t stream)
+{
+    if (!order_pass_ok(a)) return HJGPU_EINVAL;
+    hipLaunchKernelGGL(order_scan_kernel, dim3(hj_order::DIGITS), dim3(256), 0, stream, a);
+    return hipGetLastError() == hipSuccess ? HJGPU_OK : HJGPU_EHIP;
+}
+
+int hj_launch_order_scatter(const OrderPassArgs &a, hipStream_t stream)
+{
+    if (!order_pass_ok(a)) return HJGPU_EINVAL;
+    hipLaunchKernelGGL(order_scatter_kernel, dim3(a.lay.ranges), dim3(hj_order::BLOCK), 0, stream, a);
+    return hipGetLastError() == hipSuccess ? HJGPU_OK : HJGPU_EHIP;
+}
+
+// no more workgroups than min(n, limit) - the most rows there can be - has elements for
+int hj_launch_order_gather(const OrderGatherArgs &a, u64 n, int cus, hipStream_t stream)
+{
+    if (!a.perm || !a.d_count || a.ncols > hj_order::MAX_COLS || cus < 1) return HJGPU_EINVAL;
+    for (uint32_t c = 0; c < a.ncols; ++c) if (!a.in[c] || !a.out[c]) return HJGPU_EINVAL;
+    const u64 most = std::min<u64>(n, a.limit);
+    if (most == 0 || (a.ncols == 0 && !a.rows_out)) return HJGPU_OK;
+    const dim3 grid((uint32_t)std::min<u64>((most + 255) / 256, (u64)cus * 8));
+    hipLaunchKernelGGL(order_gather_kernel, grid, dim3(256), 0, stream, a);
+    return hipGetLastError() == hipSuccess ? HJGPU_OK : HJGPU_EHIP;
+}

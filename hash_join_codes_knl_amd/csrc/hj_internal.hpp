@@ -10,6 +10,7 @@
 #include "filter_layout.hpp"
 #include "gather_layout.hpp"
 #include "group_layout.hpp"
+#include "order_layout.hpp"
 #include "scatter_layout.hpp"
 #include "wide_group_layout.hpp"
 #include "wide_lookup_layout.hpp"
@@ -617,6 +618,52 @@ struct WideLookupArgs {
 };
 int hj_launch_wide_lookup_build(const WideLookupBuildArgs &a, uint32_t nkeys, int cus, hipStream_t stream);
 int hj_launch_wide_lookup(const WideLookupArgs &a, uint32_t nkeys, int cus, hipStream_t stream);
+
+// Order by (hjgpu_order_by*, gen_kernels.hip; DESIGN.md section 5 "Order by"): a radix sort of a permutation of row numbers by the digit
+// passes of order_layout.hpp.  Every pointer 16-byte aligned, d_count 8-byte.
+// The LDS road, hj_launch_order_lds: n <= hj_order::LDS_ROWS, ONE workgroup makes the selected row numbers (select_bits NULL: every row),
+// sorts them by keys[0 .. nkeys) and writes *d_count = J and, for j < min(J, limit), rows_out[j] (NULL: none) and out[c][j] = in[c][row],
+// 8-byte elements where bit c of wide_cols is set.
+struct OrderLdsArgs {
+    const uint32_t *select_bits;         // NULL: every row
+    uint32_t n, nkeys, ncols, wide_cols;
+    const void *keys[hj_order::MAX_KEYS];
+    uint32_t key_flags[hj_order::MAX_KEYS];
+    const void *in[hj_order::MAX_COLS];
+    void *out[hj_order::MAX_COLS];
+    uint32_t *rows_out;
+    u64 limit;
+    u64 *d_count;
+};
+int hj_launch_order_lds(const OrderLdsArgs &a, hipStream_t stream);
+// The device road.  hj_launch_order_iota: perm[i] = i for i < rows, *d_count = count.  One pass over the live permutation [0, *d_count),
+// cut into lay's ranges: hj_launch_order_histogram leaves counts[digit * ranges + g] and ADDS the digits' totals to totals[256] (0 before
+// the launch); hj_launch_order_scan turns them into bases[digit * ranges + g], where range g's first element of that digit goes;
+// hj_launch_order_scatter writes perm_out, stably.  perm_in is not perm_out.  hj_launch_order_gather: rows_out and the columns for
+// j < min(*d_count, limit) from the sorted permutation.
+struct OrderPassArgs {
+    const uint32_t *perm_in;
+    uint32_t *perm_out;
+    const uint32_t *key_words;           // the pass's key column as 32-bit words
+    hj_order::Pass pass;
+    hj_order::Layout lay;
+    const u64 *d_count;
+    uint32_t *counts, *bases, *totals;
+};
+struct OrderGatherArgs {
+    const uint32_t *perm;
+    const u64 *d_count;
+    u64 limit;
+    uint32_t ncols, wide_cols;
+    const void *in[hj_order::MAX_COLS];
+    void *out[hj_order::MAX_COLS];
+    uint32_t *rows_out;                  // NULL: no row numbers
+};
+int hj_launch_order_iota(uint32_t *perm, u64 rows, u64 count, u64 *d_count, int cus, hipStream_t stream);
+int hj_launch_order_histogram(const OrderPassArgs &a, hipStream_t stream);
+int hj_launch_order_scan(const OrderPassArgs &a, hipStream_t stream);
+int hj_launch_order_scatter(const OrderPassArgs &a, hipStream_t stream);
+int hj_launch_order_gather(const OrderGatherArgs &a, u64 n, int cus, hipStream_t stream);
 
 // K9: compact the per-wave partially filled tail blocks (npj.cpp:475-514).
 // moves: scratch of 2*HJ_MAX_WORKERS entries of 24 bytes + HJ_MAX_WORKERS entries of 8 bytes.

@@ -1474,7 +1474,7 @@ int hjgpu_destroy(hjgpu_ctx *ctx)
     (void)hipDeviceSynchronize();
     DevBuf *all[] = {&ctx->tmp[0], &ctx->tmp[1], &ctx->tmp[2], &ctx->tmp[3], &ctx->tmp[4], &ctx->tmp[5],
                      &ctx->tmp[6], &ctx->tmp[7], &ctx->meta, &ctx->table, &ctx->state, &ctx->moves,
-                     &ctx->final_offsets, &ctx->build_bits, &ctx->grp[0], &ctx->grp[1], &ctx->grp[2], &ctx->grp[3], &ctx->grp_off, &ctx->audit, &ctx->audit_lay, &ctx->compact, &ctx->group, &ctx->count_words, &ctx->wide_lookup};
+                     &ctx->final_offsets, &ctx->build_bits, &ctx->grp[0], &ctx->grp[1], &ctx->grp[2], &ctx->grp[3], &ctx->grp_off, &ctx->audit, &ctx->audit_lay, &ctx->compact, &ctx->group, &ctx->count_words, &ctx->wide_lookup, &ctx->order};
     for (DevBuf *b : all) if (b->p) (void)hipFree(b->p);
     for (int i = 0; i < EV_COUNT; ++i) (void)hipEventDestroy(ctx->ev[i]);
     if (ctx->aux) (void)hipStreamDestroy(ctx->aux);
@@ -1566,7 +1566,10 @@ int hjgpu_get_counter(hjgpu_ctx *ctx, const char *name, uint64_t *value)
     if (strcmp(name, "group_by_lds_groups") == 0) { *value = hj_wide::LDS_GROUPS; return HJGPU_OK; }
     if (strcmp(name, "group_by_step_rows") == 0) { *value = hj_wide::step_rows(ctx->cus); return HJGPU_OK; }
     if (strcmp(name, "lookup_wide_step_rows") == 0) { *value = hj_wlk::step_rows(ctx->cus); return HJGPU_OK; }
-    return fail(ctx, HJGPU_EINVAL, "unknown counter (probe_fallbacks, probe_exact, build_beside, lookup_lds_rows, compact_ranges, compact_chunk_rows, group_lds_groups, filter_step_rows, gather_step_rows, agg_step_rows, agg_scalar_step_rows, group_by_lds_groups, group_by_step_rows, lookup_wide_step_rows)");
+    if (strcmp(name, "order_lds_rows") == 0) { *value = hj_order::LDS_ROWS; return HJGPU_OK; }
+    if (strcmp(name, "order_ranges") == 0) { *value = hj_order::ranges_of(ctx->cus); return HJGPU_OK; }
+    if (strcmp(name, "order_chunk_rows") == 0) { *value = hj_order::CHUNK_ROWS; return HJGPU_OK; }
+    return fail(ctx, HJGPU_EINVAL, "unknown counter (probe_fallbacks, probe_exact, build_beside, lookup_lds_rows, compact_ranges, compact_chunk_rows, group_lds_groups, filter_step_rows, gather_step_rows, agg_step_rows, agg_scalar_step_rows, group_by_lds_groups, group_by_step_rows, lookup_wide_step_rows, order_lds_rows, order_ranges, order_chunk_rows)");
 }
 
 // the workspace's side of hjgpu_stats: what the context has spent growing it, and its last placement search
@@ -1623,12 +1626,12 @@ int hjgpu_get_stats(hjgpu_ctx *ctx, hjgpu_stats *s)
     if (ctx->last_algo >= ALGO_ONE_KERNEL) {
         // one operator (hjgpu_partition*, hjgpu_column_sums, the column operators): the stages it has are the events it recorded - a span to
         // or from an event it did not record is 0.  Compaction, filter and gather record EV_JOIN and EV_GAPS back to back: only the grouped
-        // aggregations (hjgpu_group_sum, hjgpu_group_agg, hjgpu_group_by's wide road) have a stage (the emit) between them
+        // aggregations (hjgpu_group_sum, hjgpu_group_agg, hjgpu_group_by's wide road: the emit) and hjgpu_order_by (the gather) have a stage between them
         memset(&r, 0, sizeof(r));
         r.ms_total = span(EV_BEGIN, EV_GAPS);
         r.ms_histogram = span(EV_BEGIN, EV_S_HIST);
         r.ms_join = span(EV_S_HIST, EV_JOIN);
-        if (ctx->last_algo == ALGO_GROUP_SUM || ctx->last_algo == ALGO_GROUP_AGG || ctx->last_algo == ALGO_GROUP_BY) r.ms_close_gaps = span(EV_JOIN, EV_GAPS);
+        if (ctx->last_algo == ALGO_GROUP_SUM || ctx->last_algo == ALGO_GROUP_AGG || ctx->last_algo == ALGO_GROUP_BY || ctx->last_algo == ALGO_ORDER_BY) r.ms_close_gaps = span(EV_JOIN, EV_GAPS);
         if (ctx->last_algo == ALGO_LOOKUP_WIDE) r.buckets = ctx->stats.buckets;      // (hjgpu_lookup_wide: its table's slots)
         fill_reserve(ctx, &r);
         *s = r;

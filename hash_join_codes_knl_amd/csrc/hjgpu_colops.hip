@@ -1,5 +1,5 @@
 // hjgpu_colops.hip - the column operators of include/hjgpu.h over a bitmap's rows: hjgpu_compact_selected, hjgpu_group_sum, hjgpu_group_agg,
-// hjgpu_group_by, hjgpu_filter_selected, hjgpu_gather_selected, hjgpu_lookup_wide and their _async forms.  What they refuse from their arguments alone is
+// hjgpu_group_by, hjgpu_filter_selected, hjgpu_gather_selected, hjgpu_lookup_wide, hjgpu_order_by and their _async forms.  What they refuse from their arguments alone is
 // colop_checks.hpp; their kernels are gen_kernels.hip's.  The blocking and the enqueue-only form of an operator are ONE path (X_call): they
 // differ in where the count words lie - the context's, or the caller's in device memory - and in the blocking form's tail.
 #include "hjgpu_ctx.hpp"
@@ -290,7 +290,104 @@ static int lookup_wide_call(hjgpu_ctx *ctx, const LookupWideCall &c, hjgpu_resul
     return HJGPU_OK;
 }
 
+// ---- order by ----------------------------------------------------------------------------------
+// The road is chosen by n alone (order_layout.hpp).  The LDS road is one launch.  The device road: the initial permutation - the
+// compaction's row numbers, or an iota under a NULL mask - and the clear of the passes' digit totals; three launches per pass between the
+// workspace's two permutation buffers; the gather.  J stays in *d_count, where every kernel reads it.  hjgpu_get_stats afterwards:
+// ms_histogram = the initial permutation, ms_join = the passes (the LDS road's one launch), ms_close_gaps = the gather, ms_total = all of it
+static int order_enqueue(hjgpu_ctx *ctx, const OrderCall &o, u64 *d_count, hipStream_t stream)
+{
+    using namespace hj_order;
+    char *ws = reinterpret_cast<char *>(ctx->order.p);
+    const bool outputs = o.ncols || o.rows_out;
+    uint32_t key_flags[MAX_KEYS] = {};
+    for (uint32_t k = 0; o.n && k < o.nkeys; ++k) key_flags[k] = o.keys[k].flags;
+    begin_span(ctx, ALGO_ORDER_BY, stream);
+    if (o.n == 0) HIPCHK(ctx, hj_zero_async(d_count, sizeof(u64), stream));
+    else if (lds_road(o.n)) {
+        record(ctx, EV_S_HIST, stream);
+        OrderLdsArgs a{};
+        a.select_bits = o.bits; a.n = (uint32_t)o.n; a.nkeys = o.nkeys; a.ncols = o.ncols;
+        for (uint32_t k = 0; k < o.nkeys; ++k) { a.keys[k] = o.keys[k].d_col; a.key_flags[k] = key_flags[k]; }
+        for (uint32_t c = 0; c < o.ncols; ++c) { a.in[c] = o.cols[c].d_in; a.out[c] = o.cols[c].d_out; a.wide_cols |= (o.cols[c].flags & HJGPU_ORDER_WIDE ? 1u : 0u) << c; }
+        a.rows_out = o.rows_out; a.limit = o.limit; a.d_count = d_count;
+        CHK(hj_launch_order_lds(a, stream));
+        record(ctx, EV_JOIN, stream);
+        record(ctx, EV_GAPS, stream);
+        return HJGPU_OK;
+    } else {
+        uint32_t *perm[2] = {reinterpret_cast<uint32_t *>(ws + WORKSPACE_HEAD), reinterpret_cast<uint32_t *>(ws + WORKSPACE_HEAD + perm_bytes(o.n))};
+        u64 *compact_counts = reinterpret_cast<u64 *>(ws + COMPACT_COUNTS_AT);
+        uint32_t *totals = reinterpret_cast<uint32_t *>(ws + TOTALS_AT);
+        // (the count alone: no permutation is made, let alone sorted)
+        if (o.bits) {
+            static_assert(COMPACT_COUNTS_BYTES == hj_compact::MAX_RANGES * sizeof(u64), "the compaction's counts");
+            CompactArgs c{};
+            c.select_bits = o.bits; c.lay = hj_compact::layout(o.n, hj_compact::ranges_of(ctx->cus)); c.counts = compact_counts;
+            c.d_count = d_count; c.capacity = o.n; c.rows_out = perm[0];
+            CHK(hj_launch_compact_count(o.bits, c.lay, compact_counts, stream));
+            if (outputs) CHK(hj_launch_compact(c, 0, stream));
+            else CHK(hj_launch_compact_total(compact_counts, c.lay.ranges, d_count, stream));
+        } else CHK(hj_launch_order_iota(perm[0], outputs ? o.n : 0, o.n, d_count, ctx->cus, stream));
+        record(ctx, EV_S_HIST, stream);
+        const uint32_t passes = outputs ? passes_of(o.nkeys, key_flags) : 0;
+        if (passes) HIPCHK(ctx, hj_zero_async(totals, TOTALS_BYTES, stream));
+        for (uint32_t p = 0; p < passes; ++p) {
+            OrderPassArgs a{};
+            a.pass = pass_of(o.nkeys, key_flags, p);
+            a.perm_in = perm[p & 1]; a.perm_out = perm[(p & 1) ^ 1];
+            a.key_words = reinterpret_cast<const uint32_t *>(o.keys[a.pass.key].d_col);
+            a.lay = layout(o.n, ranges_of(ctx->cus));
+            a.d_count = d_count;
+            a.counts = reinterpret_cast<uint32_t *>(ws + COUNTS_AT); a.bases = reinterpret_cast<uint32_t *>(ws + BASES_AT);
+            a.totals = totals + (size_t)p * DIGITS;
+            CHK(hj_launch_order_histogram(a, stream));
+            CHK(hj_launch_order_scan(a, stream));
+            CHK(hj_launch_order_scatter(a, stream));
+        }
+        record(ctx, EV_JOIN, stream);
+        if (outputs) {
+            OrderGatherArgs g{};
+            g.perm = perm[passes & 1]; g.d_count = d_count; g.limit = o.limit; g.ncols = o.ncols; g.rows_out = o.rows_out;
+            for (uint32_t c = 0; c < o.ncols; ++c) { g.in[c] = o.cols[c].d_in; g.out[c] = o.cols[c].d_out; g.wide_cols |= (o.cols[c].flags & HJGPU_ORDER_WIDE ? 1u : 0u) << c; }
+            CHK(hj_launch_order_gather(g, o.n, ctx->cus, stream));
+        }
+        record(ctx, EV_GAPS, stream);
+        return HJGPU_OK;
+    }
+    record(ctx, EV_S_HIST, stream);
+    record(ctx, EV_JOIN, stream);
+    record(ctx, EV_GAPS, stream);
+    return HJGPU_OK;
+}
+
+// the context's workspace (order_layout.hpp; sized from n alone): the blocking form's count word first
+static int order_call(hjgpu_ctx *ctx, const OrderCall &o, uint64_t *count, bool device_count, void *stream_)
+{
+    if (!ctx) return HJGPU_EINVAL;
+    hipStream_t stream = (hipStream_t)stream_;
+    const Verdict checked = check_order_by(o, count, device_count);
+    CHK(colop_begin(ctx, checked, stream, ctx->order, (size_t)hj_order::workspace_bytes(checked.status == HJGPU_OK ? o.n : 0)));
+    u64 *d_count = reinterpret_cast<u64 *>(device_count ? (void *)count : ctx->order.p);
+    CHK(order_enqueue(ctx, o, d_count, stream));
+    if (device_count) return HJGPU_OK;
+    u64 got[2];
+    return read_back(ctx, d_count, 1, got, count, stream);
+}
+
 extern "C" {
+
+int hjgpu_order_by_async(hjgpu_ctx *ctx, const uint32_t *d_select_bits, size_t n, uint32_t nkeys, const hjgpu_order_key *keys, uint32_t ncols,
+                         const hjgpu_order_column *cols, uint32_t *d_rows_out, size_t limit, uint64_t *d_count, void *stream)
+{
+    return order_call(ctx, {d_select_bits, n, nkeys, keys, ncols, cols, d_rows_out, limit}, d_count, true, stream);
+}
+
+int hjgpu_order_by(hjgpu_ctx *ctx, const uint32_t *d_select_bits, size_t n, uint32_t nkeys, const hjgpu_order_key *keys, uint32_t ncols,
+                   const hjgpu_order_column *cols, uint32_t *d_rows_out, size_t limit, uint64_t *count, void *stream)
+{
+    return order_call(ctx, {d_select_bits, n, nkeys, keys, ncols, cols, d_rows_out, limit}, count, false, stream);
+}
 
 int hjgpu_lookup_wide_async(hjgpu_ctx *ctx, uint32_t nkeys, const uint32_t *const *d_inner_keys, const uint32_t *d_inner_vals, size_t inner,
                             const uint32_t *const *d_outer_keys, size_t outer, const hjgpu_npj_params *params, const uint32_t *d_select_bits,

@@ -54,7 +54,8 @@ enum Algo { ALGO_NONE = -1, ALGO_NPJ = 0, ALGO_PHJ = 1,        // (PHJ, CPRA and
             ALGO_ONE_KERNEL = 2,                               // hjgpu_partition*, hjgpu_column_sums, the hjgpu_*_ms probes
             ALGO_COMPACT = 3, ALGO_GROUP_SUM = 4, ALGO_FILTER = 5, ALGO_GATHER = 6, ALGO_GROUP_AGG = 7,
             ALGO_GROUP_BY = 8,                                 // hjgpu_group_by's wide road (three and four key columns)
-            ALGO_LOOKUP_WIDE = 9 };                            // hjgpu_lookup_wide: EV_S_HIST behind the clear and the build, stats.buckets = its slots
+            ALGO_LOOKUP_WIDE = 9,                              // hjgpu_lookup_wide: EV_S_HIST behind the clear and the build, stats.buckets = its slots
+            ALGO_ORDER_BY = 10 };                              // hjgpu_order_by: EV_S_HIST behind the initial permutation, EV_JOIN behind the passes, then the gather
 
 struct hjgpu_ctx {
     int device = 0;
@@ -72,6 +73,8 @@ struct hjgpu_ctx {
     DevBuf count_words;     // hjgpu_filter_selected (the first word) and hjgpu_gather_selected (both): the count words that the kernel adds to - the blocking
                             // forms read them back (16 bytes, made by the first call of either)
     DevBuf wide_lookup;     // hjgpu_lookup_wide: the call's aggregate words and its table (wide_lookup_layout.hpp; grows with the build side)
+    DevBuf order;           // hjgpu_order_by: the blocking form's count word, and on the device road the passes' tables and the two permutation buffers
+                            // (order_layout.hpp; grows with n)
     DevBuf build_bits;      // right / full outer joins: one bit per row of the partitioned build array (PHJ / CPRA) or per bucket (NPJ)
     hipEvent_t ev[EV_COUNT];
     bool ev_valid[EV_COUNT];
@@ -196,7 +199,7 @@ struct ReserveClock {
     std::chrono::steady_clock::time_point t0;
     static size_t held(const hjgpu_ctx *c)
     {
-        size_t n = c->meta.cap + c->table.cap + c->state.cap + c->group.cap + c->wide_lookup.cap;
+        size_t n = c->meta.cap + c->table.cap + c->state.cap + c->group.cap + c->wide_lookup.cap + c->order.cap;
         for (const DevBuf &b : c->tmp) n += b.cap;
         return n;
     }

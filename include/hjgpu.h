@@ -314,7 +314,11 @@ int  hjgpu_get_stats(hjgpu_ctx *ctx, hjgpu_stats *stats);
  *   "gather_step_rows" the same for hjgpu_gather_selected
  *   "agg_step_rows", "agg_scalar_step_rows"   the same for hjgpu_group_agg with key columns and without (nkeys == 0)
  *   "group_by_lds_groups", "group_by_step_rows"   hjgpu_group_by with three and four key columns: the distinct groups a workgroup's wide
- *                      LDS table holds, and the rows its whole grid covers in one iteration of its loop */
+ *                      LDS table holds, and the rows its whole grid covers in one iteration of its loop
+ *   "lookup_wide_step_rows"   the rows hjgpu_lookup_wide's whole look-up grid covers in one iteration of its loop
+ *   "order_lds_rows"   the largest n that hjgpu_order_by sorts in one workgroup's LDS
+ *   "order_ranges", "order_chunk_rows"   hjgpu_order_by beyond that: the ranges (= workgroups of a pass's histogram and scatter launches) the
+ *                      current permutation is cut into, and the rows of a chunk, of which every range holds a whole number */
 int  hjgpu_get_counter(hjgpu_ctx *ctx, const char *name, uint64_t *value);
 
 /* ---- device memory helpers for hosts that do not link HIP (mamalloc/free,
@@ -810,6 +814,68 @@ int  hjgpu_group_by_async(hjgpu_ctx *ctx, const uint32_t *d_select_bits, size_t 
                           uint32_t nkeys, const uint32_t *const *d_keys_in, uint32_t naggs, const hjgpu_aggregate *aggs,
                           uint32_t *const *d_keys_out, uint64_t *d_counts_out, uint64_t *const *d_aggs_out,
                           size_t capacity, uint64_t *d_ngroups, void *stream);
+
+/* ---- ORDER BY up to four keys with LIMIT over a bitmap's rows -------------------------------------------------------------------------------
+ * What ends a chain of column operators: the groups of hjgpu_group_by, the rows of a compaction or of a materialised join come out in
+ * unspecified order, and a query ends in ORDER BY ... [LIMIT k].  Let the selected rows be the rows i < n whose bit is set in
+ * d_select_bits, J their number and m = min(J, limit).  The selected rows are ordered lexicographically by keys[0], then keys[1], ...,
+ * every key in its own direction and signedness, and TIES IN EVERY KEY ARE BROKEN BY ASCENDING ROW NUMBER, whatever the directions: the
+ * result is fully determined and bit-for-bit reproducible.  For j < m, with r_j the j-th row of that order:
+ *   d_rows_out[j] = (uint32_t) r_j (d_rows_out may be NULL) and cols[c].d_out[j] = cols[c].d_in[r_j], elements of 4 bytes, or of 8 under
+ *   HJGPU_ORDER_WIDE.  Nothing is written at index >= m of any output; the mask and the inputs are never written.
+ *   d_select_bits    hjgpu_lookup_selected's mask, word for word: (n + 31) / 32 words, bit i & 31 of word i >> 5 selects row i, bits of the
+ *                    last word at positions >= n are ignored, no word at index >= (n + 31) / 32 is read.  16-byte aligned (HJGPU_EALIGN).
+ *                    NULL selects every row.
+ *   keys             a HOST array of nkeys hjgpu_order_key, copied by value.  d_col holds n uint32, or n uint64 under HJGPU_ORDER_WIDE (what
+ *                    the grouped operators' counts and aggregates are); HJGPU_ORDER_SIGNED: the column is int32 (int64 with _WIDE), two's
+ *                    complement order; HJGPU_ORDER_DESC: this key descending.  nkeys is 1 to HJGPU_ORDER_MAX_KEYS; nkeys == 0 is HJGPU_EINVAL
+ *                    ("nkeys" in hjgpu_last_error): with no key the call is hjgpu_compact_selected.
+ *   key values       every value is legal.  HJGPU_NULL_VAL in a looked-up column is the ordinary value 0xFFFFFFFF, as it is for the filter:
+ *                    last in unsigned ascending order, -1 under HJGPU_ORDER_SIGNED.  There is no NULLS FIRST / NULLS LAST.
+ *   cols             a HOST array of ncols hjgpu_order_column, copied by value: the carried columns.  flags is 0 (n uint32 in, limit-or-n
+ *                    uint32 out) or HJGPU_ORDER_WIDE (uint64).  ncols is 0 to HJGPU_ORDER_MAX_COLS; a key column may also be carried, and
+ *                    the same column may appear several times.  ncols == 0 with d_rows_out == NULL: the count alone.
+ *   refusals by index   HJGPU_EINVAL, each with a text that names the entry ("key 2", "column 5"): a flag bit outside those defined,
+ *                    reserved != 0, a NULL pointer among the first nkeys / ncols entries.
+ *   n                n > 0xFFFFFFFF is HJGPU_EINVAL: a row number is a uint32.
+ *   count            *count (blocking form, host memory) / *d_count (_async form, device memory, 8-byte aligned: HJGPU_EALIGN) = J, exact
+ *                    whatever limit is.  limit < J is LIMIT, not an error: HJGPU_EOVERFLOW is never returned.
+ *   alignment        the mask, every key column, every carried input, every output and d_rows_out 16-byte aligned (HJGPU_EALIGN).
+ *   not in place     the first min(limit, n) elements of an output, or the _async form's count word, that share a byte with the mask, a key
+ *                    column, a carried input or another output: HJGPU_EINVAL, "overlaps" in hjgpu_last_error.
+ *   n == 0           reads nothing, writes nothing but the count (0), accepts NULL everywhere else.
+ * Every refusal is decided from the arguments alone, before anything is allocated or enqueued; a capturing stream is HJGPU_EINVAL; what
+ * hjgpu_get_async_status reports is untouched.  The _async form only enqueues and needs no hjgpu_reserve; calls may be queued back to
+ * back on one stream of one context.  The method is a least-significant-digit radix sort of the PERMUTATION - uint32 row numbers, never
+ * the columns - in digits of 8 bits, from the last key's lowest digit to the first key's highest, every pass a stable counting sort; the
+ * initial permutation is the selected row numbers ascending, which is where the tie rule comes from.  The road is chosen by n alone, as
+ * hjgpu_lookup chooses by inner:
+ *   n <= "order_lds_rows"   ONE launch of ONE workgroup: the permutation is made from the mask, sorted and gathered in LDS; a pass whose
+ *                    digit is the same for every row is skipped.
+ *   beyond           the initial permutation is hjgpu_compact_selected's row numbers (with a NULL mask: an iota); every pass is three
+ *                    launches ordered by the stream - a digit histogram per range of the current permutation, an exclusive scan over
+ *                    (digit, range), a scatter in which each workgroup ranks its range chunk by chunk - and a last launch gathers the
+ *                    outputs.  J stays in device memory.  No workgroup ever waits for another.
+ * The workspace is the call's own, in the context, sized from n and never from J: 16 bytes on the LDS road, 8 bytes per row (the two
+ * permutation buffers) plus 2,146,320 bytes beyond it; it grows the first time a size is seen (hjgpu_stats.ms_reserve).  hjgpu_get_stats
+ * afterwards: ms_histogram = the initial permutation, ms_join = the sorting passes, ms_close_gaps = the final gather, ms_total = all of it
+ * (the LDS road's one launch is ms_join), every other phase 0, fanout1 = fanout2 = buckets = groups = 0.  hjgpu_get_counter
+ * "order_lds_rows": the rows one workgroup's LDS holds; "order_ranges" / "order_chunk_rows": the device road's geometry - the current
+ * permutation is cut into that many contiguous ranges of whole chunks of that many rows, the tail in the last non-empty one.
+ * More than four keys or eight carried columns: a further call, or d_rows_out as the index of hjgpu_gather_selected. */
+#define HJGPU_ORDER_MAX_KEYS 4u
+#define HJGPU_ORDER_MAX_COLS 8u
+#define HJGPU_ORDER_DESC   1u   /* this key descending */
+#define HJGPU_ORDER_SIGNED 2u   /* the key column is int32 (int64 with _WIDE): two's complement order */
+#define HJGPU_ORDER_WIDE   4u   /* the column holds 64-bit words */
+typedef struct { const void *d_col; uint32_t flags, reserved; } hjgpu_order_key;
+typedef struct { const void *d_in; void *d_out; uint32_t flags /* 0 or HJGPU_ORDER_WIDE */, reserved; } hjgpu_order_column;
+int  hjgpu_order_by(hjgpu_ctx *ctx, const uint32_t *d_select_bits, size_t n,
+                    uint32_t nkeys, const hjgpu_order_key *keys, uint32_t ncols, const hjgpu_order_column *cols,
+                    uint32_t *d_rows_out, size_t limit, uint64_t *count, void *stream);
+int  hjgpu_order_by_async(hjgpu_ctx *ctx, const uint32_t *d_select_bits, size_t n,
+                          uint32_t nkeys, const hjgpu_order_key *keys, uint32_t ncols, const hjgpu_order_column *cols,
+                          uint32_t *d_rows_out, size_t limit, uint64_t *d_count, void *stream);
 
 /* ---- whole joins on HBM-resident columns (replace run()/run_hj()) ---------------- */
 /* run(), npj.cpp:769-927 */
